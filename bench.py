@@ -5,11 +5,16 @@
 (boxes, scores, classes, bit-packed mask + statistics, embedding), the one gather to rank 0 when there are several ranks,
 and their copy to pinned host memory — what the services persist.
 
-  python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  `value` is the DENSE schedule (every frame through all
-three networks: the throughput mode, YOLO on its f16 plan); `reference_schedule` reports the services' own schedule (YOLO +
+Prints ONE JSON line on rank 0.  A plain run only sets up, warms up, times the `--steps` steps of the headline path and
+prints `value` / `ms_per_step`; `--dump-outputs DIR` then also writes the records the last timed step delivered to host
+memory as DIR/<name>.npy (see dump_outputs).  Everything else below (`reference_schedule`, the other multi-rank form,
+`roofline`, `per_config`, `cpu_baseline`) runs only with `--full`; the `--no-*` options switch parts of it off.
+
+`value` is the DENSE schedule (every frame through all three networks: the throughput mode, YOLO on its f16 plan);
+`reference_schedule` reports the services' own schedule (YOLO +
 SAM on frames 0, 15, ..., 135, DINO on 0, 30, ..., 120: yolo main.py:67, dinov3 main.py:127) on the same clip with YOLO on its
 EXACT plan (keep-sets of the fp32 path: the mode whose JSON must match).
 With N > 1 ranks the headline is the path north_star describes — ONE 150-frame clip per step, rank r runs its contiguous block
@@ -202,6 +207,35 @@ def per_config_rates(fx, dev, rank, world, log, dist):
     return out
 
 
+DUMP_BUDGET = 56_000_000  # bytes of array data over all files of --dump-outputs (under 64 MB with the .npy headers)
+
+
+def dump_outputs(rec, out_dir):
+    """rec: {name: host tensor [n, ...]} = the per-frame records of the last timed step, as unpacked from the pinned host
+    buffer the step filled -> out_dir/<name>.npy, float fields as they are, integer fields as float64 (64-bit) or float32
+    (narrower: exact).  The fields share DUMP_BUDGET, smallest first; one larger than its share (the bit-packed masks) is
+    written as out_dir/<name>_sample.npy: its elements at the sorted flat indices
+    numpy.random.default_rng(0).choice(size, share // itemsize, replace=False), the same sample in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    fields = []
+    for name, t in rec.items():
+        a = t.numpy()
+        dt = np.dtype(np.float64 if a.dtype.itemsize == 8 else np.float32)
+        fields.append((a.size * dt.itemsize, name, a, dt))
+    fields.sort(key=lambda f: (f[0], f[1]))
+    left = DUMP_BUDGET
+    for i, (nbytes, name, a, dt) in enumerate(fields):
+        share = left // (len(fields) - i)
+        if nbytes > share:
+            k = share // dt.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+            name += "_sample"
+        a = np.ascontiguousarray(a, dtype=dt)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    return [f[1] for f in fields]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -213,13 +247,21 @@ def main():
     ap.add_argument("--shard-sam-chunk", type=int, default=0, help="frames per SAM pass of a rank's block in the sharded-clip step (0: one pass up to 24 frames, else equal passes of <= 30)")
     ap.add_argument("--clip-per-gpu", action="store_true", help="N > 1: make the clip-per-GPU (weak) rate the headline instead of the sharded clip")
     ap.add_argument("--shard-clip", action="store_true", help="N > 1: sharded clip as the headline (the default; kept for explicitness)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-reference-schedule", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-per-config", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: reference schedule, the other multi-rank form, roofline, per_config, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last timed step as DIR/<name>.npy (float32/float64, < 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-reference-schedule", action="store_true", help="with --full: skip reference_schedule")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
+    ap.add_argument("--no-per-config", action="store_true", help="with --full: skip per_config")
     ap.add_argument("--cpu-frames", type=int, default=10)
-    ap.add_argument("--shapes-out", default=None, help="write the per-shape table of the roofline leg (text) to this file")
+    ap.add_argument("--shapes-out", default=None, help="with --full: write the per-shape table of the roofline leg (text) to this file")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.shapes_out and not (args.full and not args.no_roofline):
+        ap.error("--shapes-out writes the roofline leg's table: it needs --full (without --no-roofline)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -253,39 +295,49 @@ def main():
         if rank == 0:
             print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
+    strong = world > 1 and not args.clip_per_gpu
+    run_dense = args.full or not strong  # the clip-per-GPU form: the headline, or (--full) beside the sharded clip
+    run_shard = world > 1 and (args.full or strong)
+    run_ref = args.full and not args.no_reference_schedule
+
     log("building synthetic weights")
     fx = pipeline.FusedExtractor(dev)
     log(f"generating the synthetic clip ({args.frames} unique 1080p frames per rank)")
     # clip-per-GPU (weak) form: every rank owns one clip (seed = 100 + rank); frames are unique within the clip
-    host = synth.synth_clip(100 + rank, args.frames)
-    frames = torch.from_numpy(host).to(dev)
-    del host
+    frames = None
+    if run_dense or rank == 0:
+        host = synth.synth_clip(100 + rank, args.frames)
+        frames = torch.from_numpy(host).to(dev)
+        del host
     i_det, i_emb = max(1, args.fps // 2), max(1, args.fps)
     sched = sorted(set(range(0, args.frames, i_det)) | set(range(0, args.frames, i_emb)))
-    sched_frames = frames[sched].contiguous()
+    sched_frames = frames[sched].contiguous() if run_ref else None
     det_idx = [j for j, i in enumerate(sched) if i % i_det == 0]
     emb_idx = [j for j, i in enumerate(sched) if i % i_emb == 0]
     # sharded-clip (strong) form: ONE clip (seed 100) per step, rank r keeps the frames of its contiguous block
     lo, hi = ldist.shard_range(args.frames, rank, world)
     shard = None
-    if world > 1:
-        shard = frames[lo:hi] if rank == 0 else torch.from_numpy(synth.synth_clip(100, hi - lo, start=lo)).to(dev) if hi > lo else frames[:0]
+    if run_shard:
+        shard = (frames[lo:hi] if rank == 0 else torch.from_numpy(synth.synth_clip(100, hi - lo, start=lo)).to(dev) if hi > lo
+                 else torch.empty((0, 1080, 1920, 3), dtype=torch.uint8, device=dev))
     # SAM pass size of a rank's block: one pass up to 24 frames (measured on one MI355X, 19-frame blocks = 8 ranks: one pass
     # 536 frames/s, two passes of 10 501, passes of 7 528, of 5 534), else equal passes of at most 30 frames
     blk = max(1, hi - lo)
     shard_chunk = args.shard_sam_chunk or (blk if blk <= 24 else -(-blk // -(-blk // 30)))
     pinned = {}
+    last = {}  # the host buffer the latest step filled and its record layout (--dump-outputs)
 
-    def to_host(buf):
+    def to_host(buf, layout):
         key = tuple(buf.shape)
         if key not in pinned:
             pinned[key] = torch.empty(buf.shape, dtype=torch.uint8).pin_memory()
         pinned[key].copy_(buf, non_blocking=True)
+        last["buf"], last["layout"] = pinned[key], layout
 
     def persist(out):
         """What leaves the GPU per clip: ONE packed record buffer -> (one gather to rank 0) -> pinned host memory."""
         out = {k: v for k, v in out.items() if k != "mask"}
-        buf, _ = ldist.pack_records(out)
+        buf, layout = ldist.pack_records(out)
         if world > 1:
             # ONE collective per step.  all_gather_into_tensor by default (RCCL's most travelled path; every rank then holds the
             # records, rank 0 persists them); LMX_BENCH_GATHER=root uses the gather-to-rank-0 form the service uses
@@ -297,7 +349,7 @@ def main():
                 buf = ldist.gather_packed(buf, root=None)
                 if rank != 0:
                     return
-        to_host(buf)
+        to_host(buf, layout)
 
     # the dense schedule is the THROUGHPUT mode: YOLO on its f16 plan; the reference schedule is the mode whose JSON must match
     # the reference: YOLO on its exact plan (lmx.yolo.YoloDetector)
@@ -311,10 +363,10 @@ def main():
         """north_star's multi-GPU path: this rank's block of THE clip, then ONE gather of the packed records to rank 0 (the
         service's collective: lmx.dist.gather_clip_records pads the short last blocks), D2H on rank 0."""
         out = {k: v for k, v in fx.step(shard, sam_chunk=shard_chunk, precision="f16").items() if k != "mask"}
-        buf, _ = ldist.pack_records(out, ldist.shard_rows(args.frames, world))
+        buf, layout = ldist.pack_records(out, ldist.shard_rows(args.frames, world))
         g = ldist.gather_packed(buf, root=0)
         if g is not None:
-            to_host(g)
+            to_host(g, layout)
 
     def timed(step, label):
         for i in range(args.warmup):
@@ -338,18 +390,24 @@ def main():
         log(f"{label}: {args.steps} steps in {dt:.3f}s")
         return dt
 
-    strong = world > 1 and not args.clip_per_gpu
-    dt_shard = timed(step_sharded, "sharded clip (one clip per step over all ranks)") if world > 1 else None
-    dt_dense = timed(step_dense, "dense schedule, one clip per GPU")
-    dt = dt_shard if strong else dt_dense
-    dt_ref = None if args.no_reference_schedule else timed(step_reference, "reference schedule")
+    shard_label, dense_label = "sharded clip (one clip per step over all ranks)", "dense schedule, one clip per GPU"
+    dt = timed(step_sharded, shard_label) if strong else timed(step_dense, dense_label)
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(ldist.unpack_records(last["buf"], last["layout"]), args.dump_outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}")
+    # --full only from here on: the other multi-rank form, the reference schedule, the roofline leg, per_config, cpu_baseline
+    if strong:
+        dt_shard, dt_dense = dt, (timed(step_dense, dense_label) if run_dense else None)
+    else:
+        dt_shard, dt_dense = (timed(step_sharded, shard_label) if run_shard else None), dt
+    dt_ref = timed(step_reference, "reference schedule") if run_ref else None
 
     # Roofline leg: the timed steps keep up to seven HIP streams in flight, so an event pair around one launch would time its
     # neighbours too.  Every launch is therefore bracketed on K more steps of the SAME workload run on one stream (not part
     # of `value`); rocprofv3's per-kernel averages in profiles/ are taken the same way (LMX_SERIAL=1).
     # (every rank replays, without collectives; rank 0 reports)
     classes, traced_share, dt_serial = None, None, None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         fx.serial = True
         fx.step(frames, sam_chunk=args.sam_chunk, precision="f16")
         torch.cuda.synchronize()
@@ -373,7 +431,7 @@ def main():
             c["launches_per_step"] = c.pop("launches") // max(args.steps, 1)
         log(f"roofline pass: {args.steps} serialized steps in {dt_serial:.3f}s")
 
-    per_config = None if args.no_per_config else per_config_rates(fx, dev, rank, world, log, dist)
+    per_config = per_config_rates(fx, dev, rank, world, log, dist) if args.full and not args.no_per_config else None
 
     if rank == 0:
         job_frames = args.frames * args.steps * (1 if strong else world)
@@ -395,9 +453,10 @@ def main():
                                        if strong else f"one clip per GPU, {world} GPU(s), one gather per step"),
                        "gflop_per_frame": sum(GFLOP_PER_FRAME.values()), "streams": fx.max_streams},
         }
-        if world > 1:
+        if dt_dense is not None and world > 1:
             line["weak_scaling"] = {"value": args.frames * world * args.steps / dt_dense, "unit": "frames/s", "ms_per_step": dt_dense / args.steps * 1e3,
                                     "note": "every rank its own 150-frame clip per step (per-GPU work fixed), one all-gather of the records per step"}
+        if dt_shard is not None:
             line["sharded_clip"] = {"value": args.frames * args.steps / dt_shard, "unit": "frames/s", "ms_per_step": dt_shard / args.steps * 1e3,
                                     "frames_per_gpu_per_step": ldist.shard_rows(args.frames, world), "sam_chunk": shard_chunk,
                                     "note": "north_star's path: decoded frames of ONE clip shard across the GPUs, RCCL gather only to reassemble per-clip outputs"}
@@ -417,7 +476,7 @@ def main():
             line["roofline_classes"] = classes
         if per_config:
             line["per_config"] = per_config
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(args.cpu_frames, 100)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -28,6 +28,21 @@ def test_library_exports_every_symbol():
     assert lib.lmx_version() == 100
 
 
+def test_library_shares_torchs_hip_runtime():
+    """Loaded before torch (build() does so), the library must still bind to torch's HIP runtime: a second libamdhip64
+    in the process finds no device.  A fresh interpreter, so that nothing has imported torch yet."""
+    import subprocess
+    import sys
+
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.fail(f"{_lib.LIB_PATH} missing: run __graft_entry__.build() first")
+    code = ("import sys; sys.path.insert(0, sys.argv[1]); from lmx import _lib; _lib.load(); import torch; "
+            "print(*sorted({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}))")
+    pkg = os.path.dirname(os.path.dirname(os.path.abspath(_lib.__file__)))
+    out = subprocess.run([sys.executable, "-c", code, pkg], capture_output=True, text=True, timeout=300, check=True).stdout
+    assert len(out.split()) == 1, f"HIP runtimes loaded: {out}"
+
+
 def test_missing_library_is_loud(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))

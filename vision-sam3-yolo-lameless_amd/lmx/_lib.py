@@ -101,6 +101,11 @@ def load():
         raise ImportError(
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  lmx has no CPU fallback.")
+    # torch first: the library's libamdhip64.so.7 then binds to the HIP runtime torch already loaded, the one that owns the
+    # tensors and streams it is handed.  Loaded first, it pulls in ROCm's own HIP + HSA runtime beside the one torch ships,
+    # and its first launch fails with "no ROCm-capable device is detected" (build() then smoke() in one process did so).
+    import torch  # noqa: F401
+
     lib = C.CDLL(LIB_PATH, mode=os.RTLD_NOW)  # resolve every symbol now: a broken build fails here, not mid-run
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
