@@ -1,0 +1,193 @@
+"""A frame's bits do not depend on the batch it rides in: lmx_k_gemm picks its kernel and tiling from M
+(csrc/gemm.hip lmx_k_gemm: register-staged 128 x 64 / 128 x 128 below M = 512, or for 3 x 3 convolutions with N = 64 below
+M = 65536; csrc/gemm2.hip lmx_gemm2_launch: four dense tilings keyed on tiles256 / q256 / tiles, two convolution tilings keyed on
+t256 >= 230).  Every one of them must return the same bits for the same output rows: the same 16x16x32 MFMA in the same k order
+and one rounding sequence in every epilogue.
+
+GEMM level: one problem computed whole, then again in row chunks whose sizes land in the OTHER branches (the branch of each is
+in the comments, derived from the rules above and confirmed under a kernel trace); the concatenation must be torch.equal to the
+whole.  Model level: a frame / prompt alone against the same frame / prompt inside a batch that crosses the thresholds.
+Branches are reached by shape only (the LMX_GEMM_* development switches are process-wide and would leak into later tests)."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+
+def _chunked(fn, M, sizes):
+    """fn(r0, r1) -> rows [r0, r1) of the result; the chunks' results concatenated."""
+    assert sum(sizes) == M
+    out, r0 = [], 0
+    for s in sizes:
+        out.append(fn(r0, r0 + s))
+        r0 += s
+    return torch.cat(out, 0)
+
+
+def _assert_equal(got, whole, what):
+    if not torch.equal(got, whole):
+        bad = (got != whole).reshape(got.shape[0], -1).any(1).nonzero().flatten()
+        raise AssertionError(f"{what}: {len(bad)} rows differ from the whole problem's, first {bad[:8].tolist()}")
+
+
+# N = 1792, K = 448 (the fc1 of Hiera stage 3).  Rows -> branch:
+#     500 -> v1 128x128 (M < 512) | 4096 -> staggered 256x128x64 (tiles256 = 112, tiles = 224 <= 256) |
+#     8192 -> 256x256x64 (tiles256 = 224, q256 = 0.875) | 12000 -> 256x128x32 (tiles256 = 329, q256 = 0.64; tiles = 658) |
+#     whole 24788 -> 256x256x64 (tiles256 = 679, q256 = 0.88)
+DENSE_SIZES = [500, 4096, 8192, 12000]
+# short K (256 x 256 short-K rule: K < 448, N = 224 .. 1536 not a multiple of 256, tiles256 >= 200, q256 >= 0.75):
+#     N = 672, K = 112: 17152 rows -> 256x256x64 short K (tiles256 201); 16896 -> 256x128x32 (tiles256 198); 256 -> v1 128x128
+#     N = 1344, K = 224: 8704 rows -> 256x256x32 short K (tiles256 204); 8448 -> 256x128x32 (198); 256 -> v1 128x128
+SHAPES = [(1792, 448, 24788, DENSE_SIZES), (672, 112, 17152, [16896, 256]), (1344, 224, 8704, [8448, 256])]
+
+FORMS = ["f16_silu_res", "f16_gelu_res", "f32_scale_res", "f32_res_rows", "a_rep2"]
+# (a_rep needs K % 64 == 0: the N = 1792 / K = 448 shape only)
+CASES = [(N, K, M, sizes, f) for N, K, M, sizes in SHAPES for f in FORMS if f != "a_rep2" or K % 64 == 0]
+
+
+@pytest.mark.parametrize("N,K,M,sizes,form", CASES, ids=[f"N{c[0]}K{c[1]}-{c[4]}" for c in CASES])
+def test_gemm_rows_are_independent_of_the_batch(cuda, N, K, M, sizes, form):
+    """The forms the plans launch: f16 out with SiLU / GELU and an f16 residual (YOLO, ViT MLPs), f32 out with LayerScale and
+    the residual stream (ViT blocks; the exact plan's scale), a res_rows-broadcast table (patch embed + position table), a_rep 2
+    (the SAM ViT exact plan)."""
+    from lmx import kernels as K_
+
+    g = torch.Generator(device=cuda).manual_seed(N + K)
+    a = torch.randn((M, K), device=cuda, generator=g).half()
+    w = (torch.randn((N, 2 * K if form == "a_rep2" else K), device=cuda, generator=g) * K ** -0.5).half()
+    b = torch.randn((N,), device=cuda, generator=g)
+    s = torch.rand((N,), device=cuda, generator=g) + 0.5
+    res_rows = 4
+    if form == "f32_res_rows":
+        res = torch.randn((res_rows, N), device=cuda, generator=g)
+    else:
+        res = torch.randn((M, N), device=cuda, generator=g)
+        res = res.half() if form.startswith("f16") else res
+    if form == "a_rep2":
+        sizes = [4096, M - 4096 - 512, 512] if M > 9000 else [M - 512, 512]  # a_rep needs M >= 512 (the LDS-DMA kernel only)
+
+    def run(r0, r1):
+        if form == "f16_silu_res":
+            return K_.gemm(a[r0:r1], w, bias=b, act=K_.ACT_SILU, res=res[r0:r1])
+        if form == "f16_gelu_res":
+            return K_.gemm(a[r0:r1], w, bias=b, act=K_.ACT_GELU, scale=s, res=res[r0:r1])
+        if form == "f32_scale_res":
+            return K_.gemm(a[r0:r1], w, bias=b, scale=s, res=res[r0:r1], out_dtype=torch.float32)
+        if form == "f32_res_rows":
+            assert r0 % res_rows == 0
+            return K_.gemm(a[r0:r1], w, bias=b, act=K_.ACT_RELU, scale=s, res=res, res_rows=res_rows, out_dtype=torch.float32)
+        return K_.gemm(a[r0:r1], w, bias=b, a_rep=2, scale=s, res=res[r0:r1], out_dtype=torch.float32)
+
+    whole = run(0, M)
+    _assert_equal(_chunked(run, M, sizes), whole, f"N={N} K={K} {form} chunks {sizes}")
+    # and in the other order of sizes: a chunk boundary inside another kernel's tile
+    _assert_equal(_chunked(run, M, sizes[::-1]), whole, f"N={N} K={K} {form} chunks {sizes[::-1]}")
+
+
+# (label, frames per chunk, H, W, Cin (x3: 3 x logical), Cout, stride, form)
+#   x3 Cin' = 192, Cout = 64 on 96 x 160: 5 frames (M = 76800 >= 65536) -> LDS-DMA 256x128x32, 4 frames and 1 -> v1 128x64
+#   Cout = 256 on 40 x 64: 24 frames (t256 = 240) -> staggered 256x256x32, 1 frame (t256 = 10) -> 256x128x32
+#   16 x 16, Cout = 128: 2 frames (M = 512) -> 256x128x32, 1 frame (M = 256) -> v1 128x128
+CONV_CASES = [
+    ("x3 N=64 rule", 5, [4, 1], 96, 160, 192, 64, 1, "f32_scale"),
+    ("t256 rule", 24, [1] * 24, 40, 64, 96, 256, 1, "f32_scale"),
+    ("t256 rule f16", 24, [11, 1, 12], 40, 64, 96, 256, 1, "f16_silu_res"),
+    ("v1 / gemm2", 2, [1, 1], 16, 16, 64, 128, 1, "f16_silu_res"),
+    ("v1 / gemm2 stride 2", 2, [1, 1], 32, 32, 64, 128, 2, "f32_scale"),
+]
+
+
+@pytest.mark.parametrize("label,n,sizes,H,W,cin,cout,stride,form", CONV_CASES, ids=[c[0] for c in CONV_CASES])
+def test_conv3x3_frames_are_independent_of_the_batch(cuda, label, n, sizes, H, W, cin, cout, stride, form):
+    from lmx import kernels as K_
+
+    g = torch.Generator(device=cuda).manual_seed(cin + cout + H)
+    x = torch.randn((n, H, W, cin), device=cuda, generator=g).half()
+    w = (torch.randn((cout, 9 * cin), device=cuda, generator=g) * (9 * cin) ** -0.5).half()
+    b = torch.randn((cout,), device=cuda, generator=g)
+    s = torch.rand((cout,), device=cuda, generator=g) + 0.5
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    res = torch.randn((n, Ho, Wo, cout), device=cuda, generator=g).half()
+
+    def run(f0, f1):
+        if form == "f32_scale":
+            return K_.conv3x3(x[f0:f1], w, b, act=K_.ACT_NONE, stride=stride, scale=s, out_dtype=torch.float32)
+        return K_.conv3x3(x[f0:f1], w, b, act=K_.ACT_SILU, stride=stride, res=res[f0:f1])
+
+    _assert_equal(_chunked(run, n, sizes), run(0, n), f"conv {label}")
+
+
+def test_conv3x3_split_k_partials_are_independent_of_the_batch(cuda):
+    """split_k partials (the exact plan's long-K convolutions) across the t256 crossing: 24 frames of 40 x 64 with Cout = 256 take
+    the staggered 256x256x32 tiling, one frame 256x128x32; every partial of a frame is the same."""
+    from lmx import kernels as K_
+
+    g = torch.Generator(device=cuda).manual_seed(77)
+    n, H, W, cin, cout, S = 24, 40, 64, 96, 256, 4
+    x = torch.randn((n, H, W, cin), device=cuda, generator=g).half()
+    w = (torch.randn((cout, 9 * cin), device=cuda, generator=g) * (9 * cin) ** -0.5).half()
+    b = torch.randn((cout,), device=cuda, generator=g)
+    s = torch.rand((cout,), device=cuda, generator=g) + 0.5
+    whole = K_.conv3x3(x, w, b, act=K_.ACT_NONE, scale=s, out_dtype=torch.float32, split_k=S)
+    for f in (0, 13, 23):
+        alone = K_.conv3x3(x[f:f + 1], w, b, act=K_.ACT_NONE, scale=s, out_dtype=torch.float32, split_k=S)
+        _assert_equal(alone[:, 0], whole[:, f], f"split_k partials of frame {f}")
+
+
+# ------------------------------------------------------------------------------------------------ model level
+def test_yolo_exact_frame_alone_equals_frame_in_batch(cuda):
+    """Exact YOLOv8-l on 1080p frames: model.2's 3 x 3 convolutions (96 x 160 per frame, N = 64) change kernel between 4 and 5
+    frames (M >= 65536); a frame alone returns the bits it returns inside 5."""
+    from lmx import synth, yolo
+
+    cfg = yolo.YoloConfig("l")
+    det = yolo.YoloDetector(cfg, yolo.synthetic_state_dict(cfg, 7, yolo.bn_stats_path("l")), cuda)
+    assert det.precision == "exact"
+    fr = torch.from_numpy(np.stack([synth.synth_frame(3, 40 + 7 * i) for i in range(5)], 0)).to(cuda)
+    img, _ = det.preprocess(fr)
+    print("yolov8l exact: letterboxed", tuple(img.shape))
+    whole = det.forward_letterboxed(img)
+    for j in (0, 4):
+        _assert_equal(det.forward_letterboxed(img[j:j + 1]), whole[j:j + 1], f"yolov8l exact frame {j}")
+
+
+@pytest.mark.parametrize("precision", ["exact", "f16"])
+def test_sam_decoder_prompt_alone_equals_prompt_in_batch(cuda, precision):
+    """MaskDecoder.predict: the 7-token Linears run on 7 n rows and change kernel between 73 and 74 prompts, the 4096-row image
+    side changes tiling with n; prompt 0 and prompt 79 alone return the bits they return among 80."""
+    from lmx import sam_decoder
+
+    dec = sam_decoder.MaskDecoder(sam_decoder.synthetic_state_dict(41), cuda, precision=precision)
+    n = 80
+    g = torch.Generator(device=cuda).manual_seed(9)
+    base = torch.nn.functional.interpolate(torch.randn((4, 256, 8, 8), device=cuda, generator=g), size=(64, 64), mode="bilinear")
+    emb = base.permute(0, 2, 3, 1).reshape(4, 4096, 256)[torch.arange(n, device=cuda) % 4].reshape(n * 4096, 256).contiguous()
+    emb = emb if precision == "exact" else emb.half()
+    boxes = torch.rand((n, 4), device=cuda, generator=g) * torch.tensor([900.0, 500.0, 900.0, 500.0], device=cuda)
+    boxes[:, 2:] += boxes[:, :2] + 50
+    hw, rhw = (1080, 1920), (576, 1024)
+    whole = {k: v.clone() for k, v in dec.predict(emb, boxes, hw, rhw).items()}
+    for j in (0, n - 1):
+        alone = dec.predict(emb[j * 4096:(j + 1) * 4096].contiguous(), boxes[j:j + 1].contiguous(), hw, rhw)
+        for k in ("lowres", "iou", "mask", "stats"):
+            _assert_equal(alone[k], whole[k][j:j + 1], f"{precision} decoder prompt {j}: {k}")
+
+
+def test_dino_frame_alone_equals_frame_in_batch(cuda):
+    """A small DINOv3 (201 tokens per frame): one frame runs every GEMM on 201 rows (register-staged kernel), three frames on
+    603 (LDS-DMA kernel); the frame's hidden states and embedding are the same bits."""
+    from lmx import dino, synth, weights
+
+    cfg = dino.DinoConfig(hidden=256, layers=4, heads=4, mlp=1024, registers=4)
+    assert cfg.tokens < 512 < 3 * cfg.tokens
+    sd = weights.synth_state_dict(dino.param_spec(cfg), seed=21)
+    m = dino.DinoEmbedder(cfg, sd, cuda)
+    frames = torch.from_numpy(np.stack([synth.synth_frame(9, i) for i in (0, 40, 80)], 0)).to(cuda)
+    patches = m.preprocess(frames)
+    whole = m.hidden_states(patches, 3)
+    np_ = cfg.grid * cfg.grid
+    for j in (0, 2):
+        alone = m.hidden_states(patches[j * np_:(j + 1) * np_].contiguous(), 1)
+        _assert_equal(alone, whole[j * cfg.tokens:(j + 1) * cfg.tokens], f"dino frame {j} hidden states")
+    _assert_equal(m.embed_frames(frames[2:3]), m.embed_frames(frames)[2:3], "dino embedding of frame 2")

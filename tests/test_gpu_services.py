@@ -149,9 +149,9 @@ def test_clip_curation_tracker(cuda):
     frames = torch.from_numpy(np.stack([synth.synth_frame(3, i) for i in (40, 41, 42)], 0)).to(cuda)
     recs = CowTracker(det, conf=0.3, batch=2).track(frames, fps=30.0, first_frame=100)
     assert [r["frame"] for r in recs] == [100, 101, 102] and abs(recs[1]["time"] - 101 / 30.0) < 1e-12
-    # same batches as the tracker: the GEMM dispatch depends on the row count (the 12x20 level of a 2-frame batch has
-    # M = 480 < 512 rows and takes the register-staged kernel), so another batching may differ in the last f32 bit of an
-    # accumulation — and a random 60-layer network amplifies that to a fraction of a pixel
+    # same batches as the tracker (the kernel choice depends on the row count — the 12x20 level of a 2-frame batch has M = 480
+    # < 512 rows and takes the register-staged kernel — but every kernel returns the same bits for the same rows:
+    # tests/test_gpu_dispatch.py; the tracker's own batching is what this test pins)
     for i0 in (0, 2):
         boxes, scores, cls, _, counts = (t.cpu().numpy() for t in det.detect(frames[i0:i0 + 2], conf=0.3))
         for b in range(boxes.shape[0]):
@@ -193,7 +193,8 @@ def test_fused_step_is_bit_reproducible(cuda, n_frames):
 def test_fused_step_on_shards_equals_the_whole_clip(cuda, precision):
     """What makes the multi-GPU JSON equal to the single-GPU one: FusedExtractor.step on contiguous blocks of a
     clip — the ranks' shards, ragged here: 13 + 11 of 24 frames — returns, frame for frame, the bits of the step on the whole clip,
-    on the exact plans the services run and on the throughput plans; every kernel choice is independent of the batch size."""
+    on the exact plans the services run and on the throughput plans.  The GEMM kernel and tiling ARE chosen from the row count, so
+    this holds because every choice returns the same bits for the same rows (tests/test_gpu_dispatch.py crosses each threshold)."""
     import numpy as np
     import torch
 
