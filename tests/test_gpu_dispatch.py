@@ -176,7 +176,8 @@ def test_sam_decoder_prompt_alone_equals_prompt_in_batch(cuda, precision):
 
 def test_dino_frame_alone_equals_frame_in_batch(cuda):
     """A small DINOv3 (201 tokens per frame): one frame runs every GEMM on 201 rows (register-staged kernel), three frames on
-    603 (LDS-DMA kernel); the frame's hidden states and embedding are the same bits."""
+    603 (LDS-DMA kernel); the frame's hidden states and embedding are the same bits.  GEMM tilings only: 4 heads x 3 frames = 12
+    attention items stay on attn_sp (the attn_spp switch at 64 items is test_dino_l_heads_frame_alone_equals_frame_in_batch)."""
     from lmx import dino, synth, weights
 
     cfg = dino.DinoConfig(hidden=256, layers=4, heads=4, mlp=1024, registers=4)
@@ -191,3 +192,60 @@ def test_dino_frame_alone_equals_frame_in_batch(cuda):
         alone = m.hidden_states(patches[j * np_:(j + 1) * np_].contiguous(), 1)
         _assert_equal(alone, whole[j * cfg.tokens:(j + 1) * cfg.tokens], f"dino frame {j} hidden states")
     _assert_equal(m.embed_frames(frames[2:3]), m.embed_frames(frames)[2:3], "dino embedding of frame 2")
+
+
+# ------------------------------------------------------------------------------------------------ attention: attn_sp / attn_spp
+# lmx_k_attention runs 128 < Tk <= 208 (64 < Tq <= 208, hd <= 64) on attn_sp below B * H = 64 items and on the persistent
+# attn_spp from 64 (csrc/attn.hip lmx_k_attention; window geometry needs both pad vectors).  A frame's rows must be the same
+# bits either way: the whole problem (>= 64 items, attn_spp) against batch chunks of < 64 items each (attn_sp).
+# (label, items per batch element (H, or H x windows per image), B, chunk sizes in batch elements, hd, window)
+ATTN_CASES = [
+    ("flat T201 hd56 H16", 16, 8, [3, 1, 2, 2], 56, None),
+    ("flat T201 hd64 H16", 16, 8, [3, 1, 2, 2], 64, None),
+    ("win14 28x28 pad vectors hd56 H2", 2, 8 * 4, [3, 1, 4], 56, dict(Gh=28, Gw=28, ws=14, q_stride=1)),
+    ("win14 20x20 pad vectors hd64 H2", 2, 8 * 4, [7, 1], 64, dict(Gh=20, Gw=20, ws=14, q_stride=1)),
+]
+
+
+@pytest.mark.parametrize("label,H,B,sizes,hd,window", ATTN_CASES, ids=[c[0] for c in ATTN_CASES])
+def test_attention_rows_are_independent_of_the_batch(cuda, label, H, B, sizes, hd, window):
+    """sizes in batch elements (frames | windows); for windows a chunk is whole images (4 windows of 14 x 14 each)."""
+    from lmx import kernels as K_
+
+    T = 201 if window is None else 196
+    g = torch.Generator(device=cuda).manual_seed(hd + B)
+    heads, per = H, (1 if window is None else 4)
+    rows_per = T if window is None else window["Gh"] * window["Gw"]
+    n_elem = B // per  # batch elements in token rows: frames, or images for windows
+    D = heads * hd
+    qkv = (torch.randn((n_elem * rows_per, 3 * D), device=cuda, generator=g) * 1.5).half()
+    pad = torch.randn((3 * D,), device=cuda, generator=g).half()
+    assert B * heads >= 64 and all(s * per * heads < 64 for s in sizes)
+
+    def run(e0, e1):
+        x = qkv[e0 * rows_per:e1 * rows_per]
+        out = torch.empty((x.shape[0], D), dtype=torch.float16, device=cuda)
+        K_.attention(x[:, :D], x[:, D:2 * D], x[:, 2 * D:], out, (e1 - e0) * per, heads, T, T, hd, hd ** -0.5, window=window,
+                     pad_k=pad[D:2 * D] if window else None, pad_v=pad[2 * D:] if window else None)
+        return out
+
+    whole = run(0, n_elem)
+    _assert_equal(_chunked(run, n_elem, sizes), whole, f"attention {label} chunks {sizes}")
+
+
+def test_dino_l_heads_frame_alone_equals_frame_in_batch(cuda):
+    """DINOv3-L attention geometry (16 heads of 64, 201 tokens) on 2 layers: frame 0 alone is 16 attention items (attn_sp), the
+    same frame among 4 is 64 (attn_spp); hidden states and embedding must be the same bits."""
+    from lmx import dino, synth, weights
+
+    cfg = dino.DinoConfig(hidden=1024, layers=2, heads=16, mlp=4096, registers=4)
+    assert cfg.head_dim == 64 and cfg.tokens == 201 and cfg.heads < 64 <= 4 * cfg.heads
+    sd = weights.synth_state_dict(dino.param_spec(cfg), seed=23)
+    m = dino.DinoEmbedder(cfg, sd, cuda)
+    frames = torch.from_numpy(np.stack([synth.synth_frame(5, i) for i in (0, 30, 60, 90)], 0)).to(cuda)
+    patches = m.preprocess(frames)
+    whole = m.hidden_states(patches, 4)
+    np_ = cfg.grid * cfg.grid
+    alone = m.hidden_states(patches[:np_].contiguous(), 1)
+    _assert_equal(alone, whole[:cfg.tokens], "dino-L heads: frame 0 hidden states")
+    _assert_equal(m.embed_frames(frames[:1]), m.embed_frames(frames)[:1], "dino-L heads: embedding of frame 0")

@@ -621,6 +621,72 @@ def test_hiera_attn_pool_fused_block(cuda, Din, D, heads, ws, n, Gh, Gw):
     assert d < 4e-3
 
 
+@pytest.mark.parametrize("kernel", ["hiera_attn8", "hiera_attn4", "hiera_attn_pool"])
+def test_hiera_fused_attention_large_logits(cuda, kernel):
+    """The fused Hiera attention halves with the q rows of wqkv scaled so that the window logits reach +-40 (exp without the max
+    subtraction overflows f16): fused against the unfused launches (lmx_k_attention, pinned to float64 by
+    tests/test_gpu_attention.py), finite, < 4e-3 apart."""
+    from lmx import kernels as Kk
+    from lmx import sam
+
+    D, heads, ws, Din = {"hiera_attn8": (112, 2, 8, 112), "hiera_attn4": (224, 4, 4, 224), "hiera_attn_pool": (224, 4, 8, 112)}[kernel]
+    n, Gh, Gw = 2, 16, 24
+    hd, rows = D // heads, n * Gh * Gw
+    h = _rand((rows, Din), 121, 1.0).half()
+    x = _rand((rows, D), 122, 1.0)
+    wqkv = _rand((3 * D, Din), 123, 1.0) * Din ** -0.5
+    wqkv[:D] *= 12.0
+    wqkv = wqkv.half().float()
+    bqkv = _rand((3 * D,), 124, 0.2)
+    wo = (_rand((D, D), 125, 1.0) * D ** -0.5).half().float()
+    bo = _rand((D,), 126, 0.2)
+    qkv = (h.float() @ wqkv.t() + bqkv).view(n, Gh, Gw, 3, heads, hd)
+    win = qkv[0, :ws, :ws].reshape(ws * ws, 3, heads, hd)  # the first window (unpooled queries)
+    logits = torch.einsum("qhd,khd->hqk", win[:, 0], win[:, 1]) * hd ** -0.5
+    assert float(logits.abs().max()) >= 40, float(logits.abs().max())
+    hd_ = h.to(cuda)
+    q3 = Kk.gemm(hd_, wqkv.half().to(cuda), bias=bqkv.to(cuda))
+    pads = dict(pad_k=q3[0, D:2 * D].contiguous(), pad_v=q3[0, 2 * D:].contiguous())
+    nW = n * (Gh // ws) * (Gw // ws)
+    if kernel == "hiera_attn_pool":
+        wsc = (_rand((D, Din), 127, 1.0) * Din ** -0.5).half().float()
+        bsc = _rand((D,), 128, 0.2)
+        packed = tuple(torch.from_numpy(a).to(cuda) for a in sam.pack_hiera_attn_pool(wsc.numpy(), bsc.numpy(), wqkv.numpy(), bqkv.numpy(),
+                                                                                      wo.numpy(), bo.numpy(), heads))
+        fused = Kk.hiera_attn_pool(hd_, packed, n, Gh, Gw, heads, D)
+        scu = Kk.gemm(hd_, wsc.half().to(cuda), bias=bsc.to(cuda), out_dtype=torch.float32)
+        pooled = torch.empty((n, Gh // 2, Gw // 2, D), dtype=torch.float32, device=cuda)
+        Kk.maxpool2(scu.view(n, Gh, Gw, D), pooled)
+        qp = torch.empty((n, Gh // 2, Gw // 2, D), dtype=torch.float16, device=cuda)
+        Kk.maxpool2(q3.view(n, Gh, Gw, 3 * D)[..., :D], qp)
+        a = torch.empty((rows // 4, D), dtype=torch.float16, device=cuda)
+        wq = ws // 2
+        Kk.attention(qp.view(-1, D), q3[:, D:2 * D], q3[:, 2 * D:], a, nW, heads, wq * wq, ws * ws, hd, hd ** -0.5,
+                     window=dict(Gh=Gh, Gw=Gw, ws=ws, q_stride=2), **pads)
+        unfused = torch.empty((rows // 4, D), dtype=torch.float32, device=cuda)
+        Kk.gemm(a, wo.half().to(cuda), bias=bo.to(cuda), res=pooled.view(-1, D), out=unfused)
+    else:
+        if kernel == "hiera_attn8":
+            packed = tuple(torch.from_numpy(a).to(cuda) for a in sam.pack_hiera_attn(wqkv.numpy(), bqkv.numpy(), wo.numpy(), bo.numpy(),
+                                                                                     heads, ln_inside=False))
+            fused = x.to(cuda)
+            Kk.hiera_attn8(fused, packed, n, Gh, Gw, heads, h=hd_)
+        else:
+            packed = tuple(torch.from_numpy(a).to(cuda) for a in sam.pack_hiera_attn4(wqkv.numpy(), bqkv.numpy(), wo.numpy(), bo.numpy(),
+                                                                                      heads))
+            fused = x.to(cuda)
+            Kk.hiera_attn4(hd_, fused, packed, n, Gh, Gw, heads)
+        a = torch.empty((rows, D), dtype=torch.float16, device=cuda)
+        Kk.attention(q3[:, :D], q3[:, D:2 * D], q3[:, 2 * D:], a, nW, heads, ws * ws, ws * ws, hd, hd ** -0.5,
+                     window=dict(Gh=Gh, Gw=Gw, ws=ws, q_stride=1), **pads)
+        unfused = x.to(cuda)
+        Kk.gemm(a, wo.half().to(cuda), bias=bo.to(cuda), res=unfused, out=unfused)
+    assert bool(torch.isfinite(fused).all()) and bool(torch.isfinite(unfused).all())
+    d = (fused - unfused).abs().max().item()
+    print(f"{kernel} logits up to {float(logits.abs().max()):.1f}: max |fused - unfused| {d:.3e}")
+    assert d < 4e-3
+
+
 @pytest.mark.parametrize("D,rows", [(112, 256), (112, 5000), (224, 300), (224, 70000)])
 def test_ln_mlp_img(cuda, D, rows):
     """lmx_k_ln_mlp_img (csrc/hiera.hip hiera_mlp_kernel): x += fc2(gelu(fc1(LayerNorm(x)))) with the weights streamed as LDS images,
