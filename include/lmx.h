@@ -358,6 +358,35 @@ int lmx_k_hyper_mask(const void* up, const float* hyper, float* logits, int n, i
  * workspace: n*nh*nw floats (the cropped TxT intermediate, so each output pixel costs 4 taps instead of 16). */
 int lmx_k_mask_post(const float* logits, int n, int L, int T, int nh, int nw, int h, int w, uint8_t* mask,
                     int64_t* stats, float* workspace, lmx_stream_t stream);
+/* ---- SAM prompt paths beyond the box (segment_anything SamPredictor.predict with point_coords / mask_input /
+ * multimask_output / return_logits; TF:models/sam/modeling_sam.py:596-698, :432-543; csrc/prompt.hip) ------------------ */
+/* SamPromptEncoder._embed_points + _embed_boxes: points f32 [n][Np][2] xy and labels int32 [n][Np] (1 foreground, 0 background,
+ * -1 not a point), boxes f32 [n][>=4] xyxy or NULL, all in FRAME pixels -> sparse f32 [n][Ns][2F], Ns = Np + (boxes ? 2 : 1),
+ * tokens [points..., box corners] or [points..., pad].  Coordinates as lmx_k_prompt_box (apply_coords in double, f32, +0.5,
+ * /S, random-Fourier PE); label 0 / 1 adds point_embed f32 [2][2F] row 0 / 1; label -1 and the pad token (no box) are
+ * not_a_point f32 [2F] alone; corner as lmx_k_prompt_box.  Np = 0 with a box gives lmx_k_prompt_box's bits.  A label outside
+ * {-1, 0, 1} makes its token NaN (callers check labels on the host first). */
+int lmx_k_prompt_points(const float* points, const int32_t* labels, int Np, const float* boxes, int64_t ldb, float* sparse, int n,
+                        double sx, double sy, float S, const float* gauss, const float* point_embed, const float* not_a_point,
+                        const float* corner, int F, lmx_stream_t stream);
+/* SamMaskEmbedding + the dense add, replacing lmx_k_add_bcast(emb, no_mask) when a mask is given: mask_input f32 [n][4G][4G]
+ * (the low-res logits of an earlier call) -> Conv2d(1,4,k2,s2) -> LayerNorm2d -> GELU -> Conv2d(4,16,k2,s2) -> LayerNorm2d ->
+ * GELU -> Conv2d(16,256,k1) = dense [n][G][G][256]; keys f32 [n*G*G][ldk] = emb (f32 or f16 rows [n*G*G][lde]) + dense.
+ * LayerNorm2d eps 1e-6, GELU the erf form, plain f32.  params f32 [LMX_MASK_EMBED_PARAMS], the torch tensors flattened in
+ * this order: conv1.weight [4][1][2][2], conv1.bias [4], layer_norm1.weight [4], .bias [4], conv2.weight [16][4][2][2],
+ * conv2.bias [16], layer_norm2.weight [16], .bias [16], conv3.weight [256][16][1][1], conv3.bias [256]. */
+#define LMX_MASK_EMBED_PARAMS 4684
+int lmx_k_mask_embed(const float* mask_input, const void* emb, int emb_dtype, int64_t lde, const float* params, float* keys,
+                     int64_t ldk, int n, int G, lmx_stream_t stream);
+/* masks[:, m] = hyper_in[:, m] @ upscaled for M = 1..4 masks in one pass over `up` (read once, not M times): hyper f32
+ * [n][M][C] -> logits f32 [n][M][4G][4G].  Slice m equals lmx_k_hyper_mask / lmx_k_hyper_mask_f32 with hyper[:, m] bit for
+ * bit.  _multi: up f16 as lmx_k_hyper_mask; _multi_f32: up f32 and act as lmx_k_hyper_mask_f32. */
+int lmx_k_hyper_mask_multi(const void* up, const float* hyper, float* logits, int n, int M, int G, int C, lmx_stream_t stream);
+int lmx_k_hyper_mask_multi_f32(const float* up, const float* hyper, float* logits, int n, int M, int G, int C, int act,
+                               lmx_stream_t stream);
+/* Sam.postprocess_masks without the threshold (predict(return_logits=True)): logits f32 [n][L][L] -> out f32 [n][h][w] with
+ * lmx_k_mask_post's interpolation arithmetic, so (out > 0) is lmx_k_mask_post's mask bit for bit.  out 16-byte aligned. */
+int lmx_k_mask_logits(const float* logits, int n, int L, int T, int nh, int nw, int h, int w, float* out, lmx_stream_t stream);
 /* Bit-pack a 0/non-0 byte image: dst[r][c] holds pixels 8c..8c+7 of row r, first pixel in the most significant bit
  * (numpy.packbits order); rows are padded to ceil(w/8) bytes.  Used for the mask persisted / gathered per frame
  * (services/sam3-pipeline/app/main.py:83-89 returns a bool[H,W] mask; SURVEY.md §8b `mask_bits [n, h, ceil(w/8)]`):

@@ -147,3 +147,33 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// ---- helpers of the bit-exact files (compiled there with -ffp-contract=off) ----
+// SiLU as torch's CPU kernel writes it: x / (1 + exp(-x)) with a true division (the f16 plan's v_exp / v_rcp form is 1-2 ulp
+// looser, which the exact plan cannot afford to spend)
+__device__ __forceinline__ float act_exact(float v, int act) {
+  if (act == LMX_ACT_SILU) return v / (1.0f + expf(-v));
+  if (act == LMX_ACT_RELU) return fmaxf(v, 0.0f);
+  if (act == LMX_ACT_GELU) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));  // the erf form torch's GELU evaluates
+  return v;
+}
+
+// torch upsample_bilinear2d(align_corners=False) source index: scale*(dst+0.5)-0.5 clamped at 0
+__device__ __forceinline__ void bil_idx(float scale, int dst, int in_size, int& i0, int& i1, float& l1) {
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)src;
+  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+  l1 = src - (float)i0;
+}
+
+__device__ __forceinline__ float sample_mid(const float* __restrict__ lg, int L, int T, float sLT, int Y, int X) {
+  // value of the TxT bilinear upsample of the LxL logits at integer position (Y, X)
+  int y0, y1, x0, x1;
+  float ly, lx;
+  bil_idx(sLT, Y, L, y0, y1, ly);
+  bil_idx(sLT, X, L, x0, x1, lx);
+  const float t0 = (1.f - lx) * lg[y0 * L + x0] + lx * lg[y0 * L + x1];
+  const float t1 = (1.f - lx) * lg[y1 * L + x0] + lx * lg[y1 * L + x1];
+  return (1.f - ly) * t0 + ly * t1;
+}

@@ -33,15 +33,6 @@ __device__ __forceinline__ void split_hi_lo(float v, half_t& hi, half_t& lo) {
 }
 __device__ __forceinline__ float join_hi_lo(half_t hi, half_t lo) { return (float)hi + (float)lo * (1.0f / 2048.0f); }
 
-// SiLU as torch's CPU kernel writes it: x / (1 + exp(-x)) with a true division (the f16 plan's v_exp / v_rcp form is 1-2 ulp
-// looser, which the exact plan cannot afford to spend)
-__device__ __forceinline__ float act_exact(float v, int act) {
-  if (act == LMX_ACT_SILU) return v / (1.0f + expf(-v));
-  if (act == LMX_ACT_RELU) return fmaxf(v, 0.0f);
-  if (act == LMX_ACT_GELU) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));  // the erf form torch's GELU evaluates
-  return v;
-}
-
 // rows x N f32 (row stride ldx) -> x3 groups of width g in a channel slice with pixel stride ldo (in f16 elements); an
 // optional x3 residual (same grouping, pixel stride ldr) is added after the activation (C2f's shortcut: y = x + cv2(cv1(x)))
 __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ x, int64_t ldx, int act, const half_t* __restrict__ res,

@@ -145,26 +145,6 @@ __global__ __launch_bounds__(256) void hyper_mask_kernel(const half_t* __restric
   }
 }
 
-// torch upsample_bilinear2d(align_corners=False) source index: scale*(dst+0.5)-0.5 clamped at 0
-__device__ __forceinline__ void bil_idx(float scale, int dst, int in_size, int& i0, int& i1, float& l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-}
-
-__device__ __forceinline__ float sample_mid(const float* __restrict__ lg, int L, int T, float sLT, int Y, int X) {
-  // value of the TxT bilinear upsample of the LxL logits at integer position (Y, X)
-  int y0, y1, x0, x1;
-  float ly, lx;
-  bil_idx(sLT, Y, L, y0, y1, ly);
-  bil_idx(sLT, X, L, x0, x1, lx);
-  const float t0 = (1.f - lx) * lg[y0 * L + x0] + lx * lg[y0 * L + x1];
-  const float t1 = (1.f - lx) * lg[y1 * L + x0] + lx * lg[y1 * L + x1];
-  return (1.f - ly) * t0 + ly * t1;
-}
-
 // pass 1: the T x T bilinear upsample of the L x L logits, only the [nh][nw] crop that pass 2 reads
 // DBG 0 is the product (plain loads).  LMX_DBG_MASK selects the others in the development build only (make dbg, see
 // ld_mid): 1 = as the product but compiled WITH the SLP vectoriser in liblmx_dbg.so (reproduces the defect); 2 = pass 1

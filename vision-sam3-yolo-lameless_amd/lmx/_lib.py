@@ -87,6 +87,11 @@ SIGNATURES = {
     "lmx_k_prompt_box": (_I, [_VP, _I64, _VP, _I, _D, _D, _F, _VP, _VP, _I, _VP]),
     "lmx_k_hyper_mask": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
     "lmx_k_mask_post": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "lmx_k_prompt_points": (_I, [_VP, _VP, _I, _VP, _I64, _VP, _I, _D, _D, _F, _VP, _VP, _VP, _VP, _I, _VP]),
+    "lmx_k_mask_embed": (_I, [_VP, _VP, _I, _I64, _VP, _VP, _I64, _I, _I, _VP]),
+    "lmx_k_hyper_mask_multi": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP]),
+    "lmx_k_hyper_mask_multi_f32": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
+    "lmx_k_mask_logits": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _VP, _VP]),
 }
 
 _lib = None

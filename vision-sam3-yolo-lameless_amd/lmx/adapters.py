@@ -7,7 +7,10 @@ reference's own `main.py` files run on liblmx with their call sites unchanged (I
   services/sam3-pipeline/app/main.py:51-72,80-89    sam_model_registry[type](checkpoint=p) ; SamPredictor(sam) ;
                                                     predictor.set_image(frame) ; predictor.predict(point_coords=None,
                                                     point_labels=None, box=b[None, :], multimask_output=False)
-                                                    -> (masks [1,H,W] bool, scores [1], low_res [1,256,256])
+                                                    -> (masks [1,H,W] bool, scores [1], low_res [1,256,256]);
+                                                    and the rest of SamPredictor.predict: point_coords / point_labels,
+                                                    mask_input, multimask_output (the default, 3 masks), return_logits;
+                                                    get_image_embedding()
   services/dinov3-pipeline/app/main.py:34-36,98-113 AutoImageProcessor / AutoModel .from_pretrained(name) ;
                                                     inputs = processor(images=pil, return_tensors="pt") ;
                                                     {k: v.to(device)} ; model(**inputs).last_hidden_state [B,T,D]
@@ -19,7 +22,8 @@ no CPU path (a missing library or a CPU-only torch raises).
 Single-frame calls — the shape of every call the reference's loops make — can be replayed from a HIP graph captured on the first
 call of an input shape (LMX_GRAPHS=1; lmx/graphs.py: same kernels, same bits, one launch instead of 200 - 700).  Measured, the
 replay is no faster than the eager call (the latency is the GPU's chain of small kernels), so it is off by default; it frees the
-host thread.  Calls with several frames always run eagerly."""
+host thread.  Calls with several frames, and SamPredictor.predict calls other than the service's (box, single mask, thresholded),
+always run eagerly."""
 from pathlib import Path
 
 import numpy as np
@@ -224,27 +228,59 @@ class LmxSamPredictor:
         self.features = e2.reshape(-1, e2.shape[-1])
         self.is_image_set = True
 
+    def get_image_embedding(self):
+        """The image embedding set_image computed, f32 [1,256,G,G] on the device (segment_anything's NCHW form)."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) to generate an embedding.")
+        G = self.decoder.G
+        return self.features.float().view(1, G, G, -1).permute(0, 3, 1, 2)
+
     def predict(self, point_coords=None, point_labels=None, box=None, mask_input=None, multimask_output=True, return_logits=False):
+        """segment_anything's SamPredictor.predict: points [N,2] xy with labels [N] (1 foreground, 0 background, -1 ignored),
+        box [4] or [1,4] xyxy, both in frame pixels; mask_input [1,256,256] low-res logits of an earlier call.  Returns (masks
+        [C,H,W] bool, or f32 logits with return_logits; scores f32 [C]; low_res f32 [C,256,256]), C = 3 with multimask_output
+        (the default), else 1.  Malformed prompts raise ValueError."""
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
-        if point_coords is not None or point_labels is not None or mask_input is not None:
-            raise NotImplementedError("lmx implements the box prompt the service uses (sam3 main.py:83-88)")
-        if box is None:
-            raise ValueError("predict needs box=np.ndarray [4] or [1,4] (xyxy, frame pixels)")
-        if multimask_output:
-            raise NotImplementedError("lmx decodes the single-mask output (multimask_output=False, sam3 main.py:87)")
-        b = torch.from_numpy(np.asarray(box, np.float64).reshape(1, 4).astype(np.float32)).to(self.device)
+        if (point_coords is None) != (point_labels is None):
+            raise ValueError("point_coords and point_labels must be given together")
+        dev = self.device
+        pts = lbl = bx = mk = None
+        if point_coords is not None:
+            p = np.asarray(point_coords, np.float64)
+            lab = np.asarray(point_labels)
+            if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] == 0 or lab.shape != (p.shape[0],):
+                raise ValueError(f"point_coords must be [N,2] and point_labels [N] (N >= 1), got {p.shape} and {lab.shape}")
+            if not np.isin(lab, (-1, 0, 1)).all():
+                raise ValueError(f"point_labels must be 1 (foreground), 0 (background) or -1 (ignored), got {np.unique(lab).tolist()}")
+            pts = torch.from_numpy(p.astype(np.float32)[None]).to(dev)
+            lbl = torch.from_numpy(lab.astype(np.int32)[None]).to(dev)
+        if box is not None:
+            b = np.asarray(box, np.float64)
+            if b.size != 4:
+                raise ValueError(f"box must be [4] or [1,4] (xyxy, frame pixels), got {b.shape}")
+            bx = torch.from_numpy(b.reshape(1, 4).astype(np.float32)).to(dev)
+        if mask_input is not None:
+            m = np.asarray(mask_input, np.float32)
+            if m.shape != (1, 256, 256):
+                raise ValueError(f"mask_input must be [1,256,256] (the low_res logits of an earlier call), got {m.shape}")
+            mk = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
+        if pts is None and bx is None:
+            raise ValueError("predict needs a prompt: point_coords with point_labels, and / or box")
         key = (self.original_size, self.input_size)
-        g = self._g_decode.get(key)
-        if g is None and len(self._g_decode) < 4:
-            g = self._g_decode[key] = GraphedFn(lambda f, bx, k=key: self.decoder.predict(f, bx, k[0], k[1]), clone_outputs=False)
-        out = g(self.features, b) if g is not None else self.decoder.predict(self.features, b, *key)
-        low = out["lowres"].cpu().numpy()
-        scores = out["iou"].cpu().numpy()
-        if return_logits:
-            raise NotImplementedError("return_logits=True: full-resolution logits are not materialised (the service thresholds)")
-        masks = out["mask"].cpu().numpy().astype(bool)
-        return masks, scores, low
+        if pts is None and mk is None and not multimask_output and not return_logits:
+            # the service's call (sam3 main.py:83-88): box, single mask, thresholded — replayable from a HIP graph
+            g = self._g_decode.get(key)
+            if g is None and len(self._g_decode) < 4:
+                g = self._g_decode[key] = GraphedFn(lambda f, bx, k=key: self.decoder.predict(f, bx, k[0], k[1]), clone_outputs=False)
+            out = g(self.features, bx) if g is not None else self.decoder.predict(self.features, bx, *key)
+            masks = out["mask"].cpu().numpy().astype(bool)
+            return masks, out["iou"].cpu().numpy(), out["lowres"].cpu().numpy()
+        # every other prompt structure runs eagerly
+        out = self.decoder.decode(self.features, key[0], key[1], points=pts, labels=lbl, boxes=bx, mask_input=mk,
+                                  multimask=multimask_output, return_logits=return_logits)
+        masks = out["logits"][0].cpu().numpy() if return_logits else out["mask"][0].cpu().numpy().astype(bool)
+        return masks, out["iou"][0].cpu().numpy(), out["lowres"][0].cpu().numpy()
 
 
 SamPredictor = LmxSamPredictor

@@ -715,6 +715,86 @@ def mask_post(logits, T, nh, nw, h, w):
     return mask, stats
 
 
+def prompt_points(points, labels, boxes, sx, sy, S, gauss, point_embed, not_a_point, corner):
+    """points f32 [n,Np,2], labels int32 [n,Np] (or both None with a box), boxes f32 [n,>=4] or None, frame pixels -> sparse
+    f32 [n,Ns,2F] with Ns = Np + (2 if boxes else 1) (lmx_k_prompt_points).  Labels outside {-1,0,1} give NaN tokens."""
+    dev = _dev(points, labels, boxes, gauss)
+    Np = 0 if points is None else points.shape[1]
+    if Np:
+        if (points.dtype != torch.float32 or labels.dtype != torch.int32 or not points.is_contiguous() or not labels.is_contiguous()
+                or points.dim() != 3 or points.shape[2] != 2 or tuple(labels.shape) != tuple(points.shape[:2])):
+            raise LmxError("prompt_points: points must be contiguous f32 [n,Np,2], labels contiguous int32 [n,Np]")
+    if boxes is not None and (boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] < 4 or boxes.stride(1) != 1):
+        raise LmxError("prompt_points: boxes must be f32 [n,>=4] rows")
+    n = points.shape[0] if Np else boxes.shape[0]
+    if boxes is not None and boxes.shape[0] != n:
+        raise LmxError("prompt_points: points and boxes disagree on n")
+    Fq = gauss.shape[1]
+    ldb = 0 if boxes is None else (boxes.stride(0) if n > 1 else boxes.shape[1])  # (a single row may carry any stride)
+    out = torch.empty((n, Np + (2 if boxes is not None else 1), 2 * Fq), dtype=torch.float32, device=dev)
+    check(_lib.load().lmx_k_prompt_points(_ptr(points if Np else None), _ptr(labels if Np else None), Np, _ptr(boxes), ldb,
+                                          _ptr(out), n, float(sx), float(sy), float(S),
+                                          _ptr(gauss), _ptr(point_embed), _ptr(not_a_point), _ptr(corner), Fq, _stream(dev)),
+          "lmx_k_prompt_points")
+    return out
+
+
+MASK_EMBED_PARAMS = 4684  # LMX_MASK_EMBED_PARAMS
+
+
+def mask_embed(mask_input, emb, params, G=64):
+    """keys f32 [n*G*G,256] = emb (f32/f16 rows) + SamMaskEmbedding(mask_input f32 [n,4G,4G]) (lmx_k_mask_embed); params f32
+    [MASK_EMBED_PARAMS] in lmx.h's order."""
+    dev = _dev(mask_input, emb, params)
+    rows, D_, lde = _rows(emb, "mask_embed emb")
+    n = mask_input.shape[0]
+    if (mask_input.dtype != torch.float32 or not mask_input.is_contiguous() or tuple(mask_input.shape[1:]) != (4 * G, 4 * G)
+            or D_ != 256 or rows != n * G * G or emb.dtype not in _DT):
+        raise LmxError(f"mask_embed: mask_input f32 [n,{4 * G},{4 * G}] and emb [n*{G * G},256] expected")
+    if params.dtype != torch.float32 or params.numel() != MASK_EMBED_PARAMS or not params.is_contiguous():
+        raise LmxError("mask_embed: params must be contiguous f32 [%d]" % MASK_EMBED_PARAMS)
+    keys = torch.empty((rows, 256), dtype=torch.float32, device=dev)
+    check(_lib.load().lmx_k_mask_embed(_ptr(mask_input), _ptr(emb), _DT[emb.dtype], lde, _ptr(params), _ptr(keys), 256, n, G,
+                                       _stream(dev)), "lmx_k_mask_embed")
+    return keys
+
+
+def hyper_mask_multi(up, hyper, n, G, C_):
+    """hyper f32 [n,M,C] against f16 up -> logits f32 [n,M,4G,4G] (lmx_k_hyper_mask_multi)."""
+    dev = _dev(up, hyper)
+    if hyper.dtype != torch.float32 or not hyper.is_contiguous() or hyper.dim() != 3 or hyper.shape[0] != n or hyper.shape[2] != C_:
+        raise LmxError("hyper_mask_multi: hyper must be contiguous f32 [n,M,C]")
+    M = hyper.shape[1]
+    logits = torch.empty((n, M, 4 * G, 4 * G), dtype=torch.float32, device=up.device)
+    check(_lib.load().lmx_k_hyper_mask_multi(_ptr(up), _ptr(hyper), _ptr(logits), n, M, G, C_, _stream(dev)), "lmx_k_hyper_mask_multi")
+    return logits
+
+
+def hyper_mask_multi_f32(up, hyper, n, G, C_, act=ACT_NONE):
+    """hyper f32 [n,M,C] against f32 up -> logits f32 [n,M,4G,4G] (lmx_k_hyper_mask_multi_f32)."""
+    dev = _dev(up, hyper)
+    if up.dtype != torch.float32 or not up.is_contiguous():
+        raise LmxError("hyper_mask_multi_f32: up must be contiguous float32")
+    if hyper.dtype != torch.float32 or not hyper.is_contiguous() or hyper.dim() != 3 or hyper.shape[0] != n or hyper.shape[2] != C_:
+        raise LmxError("hyper_mask_multi_f32: hyper must be contiguous f32 [n,M,C]")
+    M = hyper.shape[1]
+    logits = torch.empty((n, M, 4 * G, 4 * G), dtype=torch.float32, device=up.device)
+    check(_lib.load().lmx_k_hyper_mask_multi_f32(_ptr(up), _ptr(hyper), _ptr(logits), n, M, G, C_, act, _stream(dev)),
+          "lmx_k_hyper_mask_multi_f32")
+    return logits
+
+
+def mask_logits(logits, T, nh, nw, h, w):
+    """Sam.postprocess_masks without the threshold: logits f32 [n,L,L] -> f32 [n,h,w] (lmx_k_mask_logits)."""
+    dev = _dev(logits)
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 3:
+        raise LmxError("mask_logits: logits must be contiguous f32 [n,L,L]")
+    n, L, _ = logits.shape
+    out = torch.empty((n, h, w), dtype=torch.float32, device=logits.device)
+    check(_lib.load().lmx_k_mask_logits(_ptr(logits), n, L, T, nh, nw, h, w, _ptr(out), _stream(dev)), "lmx_k_mask_logits")
+    return out
+
+
 def contour_features(mask):
     """mask u8 [n,h,w] (0 / non-0) on device -> int64 [n,8] = 2*contourArea, unit steps, diagonal steps, min x, min y, max x,
     max y, number of external contours of the largest external contour (lmx_k_contour_features, csrc/contour.hip)."""

@@ -1,15 +1,17 @@
-"""SAM prompt encoder + mask decoder + mask post-processing on liblmx — the ``predictor.predict(box=..., multimask_output=False)``
-half of services/sam3-pipeline/app/main.py:83-89.  The decoder is SAM v1's (the code
-path the service calls); it consumes a [n,64,64,256] image embedding, so it serves the Hiera FPN level-2 output
-(BASELINE cfg#3/#5) and a SAM ViT neck alike.
+"""SAM prompt encoder + mask decoder + mask post-processing on liblmx — ``predictor.predict(...)`` of segment_anything: the
+``box=..., multimask_output=False`` call of services/sam3-pipeline/app/main.py:83-89 through
+predict(), every other prompt (points, mask input, multimask, logits) through decode().  The decoder is SAM v1's; it consumes a
+[n,64,64,256] image embedding, so it serves the Hiera FPN level-2 output (BASELINE cfg#3/#5) and a SAM ViT neck alike.
 
 Launch sequence per batch of n frames (all through the C-ABI; activations f32 in HBM, GEMM operands f16):
-  prompt : 2 box corners -> random-Fourier PE (host, 2x256 floats per frame) + corner embeddings
-  decoder: two-way transformer on 7 tokens x 4096 image tokens (GEMMs batched over frames; flash attention kernel with
-           Tq=7/Tk=4096 and Tq=4096/Tk=7), then the upscaler as two per-pixel GEMMs (ConvTranspose2d k2 s2 == a 1x1 GEMM
-           to 4*Cout channels + pixel shuffle, so LayerNorm2d/GELU stay row-wise and the shuffle is folded into the
-           final hyper-network dot product), lmx_k_hyper_mask -> 256x256 logits of mask 0
-  post   : lmx_k_mask_post: bilinear 256->1024, crop, bilinear -> frame size, >0, plus area / centroid sums / bounding box.
+  prompt : 2 box corners -> random-Fourier PE + corner embeddings (lmx_k_prompt_box); decode(): points + labels (+ box) ->
+           Ns sparse tokens (lmx_k_prompt_points), a mask input -> SamMaskEmbedding + image embedding (lmx_k_mask_embed)
+  decoder: two-way transformer on T = 5 + Ns tokens (7 for a box) x 4096 image tokens (GEMMs batched over frames; flash
+           attention kernel with Tq=T/Tk=4096 and Tq=4096/Tk=T), then the upscaler as two per-pixel GEMMs (ConvTranspose2d k2 s2
+           == a 1x1 GEMM to 4*Cout channels + pixel shuffle, so LayerNorm2d/GELU stay row-wise and the shuffle is folded into the
+           final hyper-network dot product), lmx_k_hyper_mask_multi -> 256x256 logits of mask 0 (or of masks 1..3 in one pass)
+  post   : lmx_k_mask_post: bilinear 256->1024, crop, bilinear -> frame size, >0, plus area / centroid sums / bounding box
+           (lmx_k_mask_logits: the same without the threshold).
 """
 import math
 
@@ -80,6 +82,21 @@ def param_spec():
     return s
 
 
+def mask_embed_param_spec():
+    """Ordered {name: (shape, init kind)} of SamMaskEmbedding (the dense prompt of a `mask_input`), in the order
+    lmx_k_mask_embed's parameter block packs them.  Kept apart from param_spec(): checkpoints hold these tensors, but a
+    decoder built without them still serves every prompt except `mask_input`."""
+    p = "prompt_encoder.mask_embed."
+    s = {}
+    for conv, ln, cin, cout, k in (("conv1", "layer_norm1", 1, 4, 2), ("conv2", "layer_norm2", 4, 16, 2), ("conv3", None, 16, D, 1)):
+        s[p + conv + ".weight"] = ((cout, cin, k, k), "w")
+        s[p + conv + ".bias"] = ((cout,), "b")
+        if ln:
+            s[p + ln + ".weight"] = ((cout,), "g")
+            s[p + ln + ".bias"] = ((cout,), "b")
+    return s
+
+
 def synthetic_state_dict(seed):
     """Synthetic decoder weights.  SAM has ONE random-Fourier matrix (segment_anything's pe_layer) used for both the
     prompt points and the dense image PE; transformers stores it under two tied names, so both get the same values."""
@@ -92,7 +109,8 @@ def synthetic_state_dict(seed):
 
 class MaskDecoder:
     """Device-resident SAM prompt encoder + mask decoder.  ``predict(emb, boxes, frame_hw, resized_hw)`` -> dict(mask u8
-    [n,h,w], stats int64 [n,8], iou f32 [n], lowres f32 [n,256,256])."""
+    [n,h,w], stats int64 [n,8], iou f32 [n], lowres f32 [n,256,256]); ``decode(...)`` serves every prompt of
+    SamPredictor.predict (points, box, mask input, multimask, logits)."""
 
     def __init__(self, state_dict, device="cuda", image_size=1024, grid=64, precision="exact"):
         """precision: the default plan of predict() — "exact" (services, adapters, the reference schedule: f32 activations,
@@ -123,6 +141,10 @@ class MaskDecoder:
         c = 2 * np.pi * ((2 * yx - 1) @ torch.from_numpy(gauss))
         self.key_pe = torch.cat([torch.sin(c), torch.cos(c)], -1).reshape(grid * grid, D).contiguous().to(dev)
         self.no_mask = t32(sd["prompt_encoder.no_mask_embed.weight"])                          # [1,256]
+        self.point_embed = t32(np.concatenate([sd["prompt_encoder.point_embed.0.weight"], sd["prompt_encoder.point_embed.1.weight"]], 0))
+        self.not_a_point = t32(sd["prompt_encoder.not_a_point_embed.weight"][0])
+        me = mask_embed_param_spec()
+        self.mask_params = t32(np.concatenate([np.asarray(sd[k], np.float32).ravel() for k in me])) if all(k in sd for k in me) else None
         self.out_tokens = t32(np.concatenate([sd["mask_decoder.iou_token.weight"], sd["mask_decoder.mask_tokens.weight"]], 0))
 
         def attn(p):
@@ -152,7 +174,7 @@ class MaskDecoder:
         def ffn(p):
             return [(t16(sd[p + n_ + ".weight"]), t32(sd[p + n_ + ".bias"])) for n_ in ("proj_in", "layers.0", "proj_out")]
 
-        self.hyper0 = ffn("mask_decoder.output_hypernetworks_mlps.0.")
+        self.hypers = [ffn(f"mask_decoder.output_hypernetworks_mlps.{m}.") for m in range(4)]
         self.iou_head = ffn("mask_decoder.iou_prediction_head.")
 
     # ---- helpers ---------------------------------------------------------------------------------------------
@@ -174,13 +196,17 @@ class MaskDecoder:
         return K.gemm(h, *layers[2], out_dtype=torch.float32)
 
     # ---- forward ---------------------------------------------------------------------------------------------
-    def lowres(self, emb, sparse):
-        """emb f16/f32 [n*G*G, 256] (NHWC rows), sparse f32 [n,2,256] -> (logits f32 [n,4G,4G] of mask 0, iou f32 [n])."""
+    def lowres(self, emb, sparse, keys=None, masks=None):
+        """emb f16/f32 [n*G*G, 256] (NHWC rows), sparse f32 [n,Ns,256] -> (logits f32 [n,4G,4G] of mask 0, iou f32 [n]).
+        keys: f32 [n*G*G,256] = emb + the dense prompt of a mask input (lmx_k_mask_embed); None = emb + the no-mask embedding.
+        masks: a tuple of mask indices to decode -> (logits f32 [n,len(masks),4G,4G], iou f32 [n,4]); None = mask 0 as above."""
         n = sparse.shape[0]
-        T, P = 7, self.G * self.G
+        T, P = 5 + sparse.shape[1], self.G * self.G
+        sel = (0,) if masks is None else tuple(masks)
         eps = 1e-6
         tokens = torch.cat([self.out_tokens[None].expand(n, -1, -1), sparse], dim=1).reshape(n * T, D).contiguous()
-        keys = K.add_bcast(emb, self.no_mask)                 # image embedding + dense no-mask embedding, f32
+        if keys is None:
+            keys = K.add_bcast(emb, self.no_mask)             # image embedding + dense no-mask embedding, f32
         queries, qpe = tokens, tokens
         for i, L in enumerate(self.layers):
             if i == 0:
@@ -208,15 +234,15 @@ class MaskDecoder:
         queries = K.layernorm(queries, *self.ln_final, 1e-5, out_dtype=torch.float32)
         q3 = queries.view(n, T, D)
         iou_tok = K.cast_f16(q3[:, 0].contiguous())
-        mask_tok = K.cast_f16(q3[:, 1].contiguous())
         # upscaler: per-pixel GEMMs, LayerNorm2d+GELU row-wise on the [.., quadrant, 64] view, pixel shuffle deferred
         u = K.gemm(keys16, *self.up1, out_dtype=torch.float32)                       # [n*P, 4*64]
         u = K.layernorm(u.view(n * P * 4, 64), *self.up_ln, eps, act=K.ACT_GELU)      # f16 [n*P*4, 64]
         u = K.gemm(u, *self.up2, act=K.ACT_GELU)                                     # f16 [n*P*4, 4*32]
-        hyper = self._ffn(self.hyper0, mask_tok)                                     # f32 [n,32]
-        logits = K.hyper_mask(u, hyper, n, self.G, 32)
-        iou = self._ffn(self.iou_head, iou_tok)[:, 0]
-        return logits, iou
+        hs = [self._ffn(self.hypers[m], K.cast_f16(q3[:, 1 + m].contiguous())) for m in sel]
+        hyper = hs[0][:, None] if len(hs) == 1 else torch.stack(hs, 1)              # f32 [n,M,32]
+        logits = K.hyper_mask_multi(u, hyper, n, self.G, 32)                         # one pass over u for all M masks
+        iou = self._ffn(self.iou_head, iou_tok)                                      # f32 [n,4]
+        return (logits[:, 0], iou[:, 0]) if masks is None else (logits, iou)
 
     # ---- exact plan: f32 activations, x3 operands (csrc/exact.hip), f32 attention ---------------------------------------
     def _lin(self, x, name, act_in=K.ACT_NONE, act=K.ACT_NONE, res=None, w2d=None, bias=None):
@@ -248,14 +274,17 @@ class MaskDecoder:
         h = self._lin(h, p + "layers.0", act=K.ACT_RELU)
         return self._lin(h, p + "proj_out")
 
-    def lowres_exact(self, emb, sparse):
-        """The exact plan of lowres(): same launch structure, every tensor f32 (TF:models/sam/modeling_sam.py:432-543)."""
+    def lowres_exact(self, emb, sparse, keys=None, masks=None):
+        """The exact plan of lowres() (same arguments and results): same launch structure, every tensor f32
+        (TF:models/sam/modeling_sam.py:432-543)."""
         n = sparse.shape[0]
-        T, P = 7, self.G * self.G
+        T, P = 5 + sparse.shape[1], self.G * self.G
+        sel = (0,) if masks is None else tuple(masks)
         eps = 1e-6
         f32 = torch.float32
         tokens = torch.cat([self.out_tokens[None].expand(n, -1, -1), sparse], dim=1).reshape(n * T, D).contiguous()
-        keys = K.add_bcast(emb, self.no_mask)                 # image embedding + dense no-mask embedding, f32
+        if keys is None:
+            keys = K.add_bcast(emb, self.no_mask)             # image embedding + dense no-mask embedding, f32
         queries, qpe = tokens, tokens
         for i in range(2):
             p = f"mask_decoder.transformer.layers.{i}."
@@ -282,7 +311,7 @@ class MaskDecoder:
         queries = self._attn_exact(p + "final_attn_token_to_image.", q_, k_, keys, n, T, P, queries)
         queries = K.layernorm(queries, *self.ln_final, 1e-5, out_dtype=f32)
         q3 = queries.view(n, T, D)
-        iou_tok, mask_tok = q3[:, 0].contiguous(), q3[:, 1].contiguous()
+        iou_tok = q3[:, 0].contiguous()
         # upscaler: ConvTranspose2d(k2, s2) as per-pixel GEMMs (weights re-laid as in __init__), LayerNorm2d row-wise on the
         # [.., quadrant, 64] view, exact GELUs folded into the next split / the final dot product
         w1 = self._sd["mask_decoder.upscale_conv1.weight"]
@@ -293,10 +322,11 @@ class MaskDecoder:
         u = self._lin(u, "mask_decoder.upscale_conv2", act_in=K.ACT_GELU,
                       w2d=np.transpose(w2, (2, 3, 1, 0)).reshape(4 * w2.shape[1], w2.shape[0]),
                       bias=np.tile(self._sd["mask_decoder.upscale_conv2.bias"], 4))                    # [n*P*4, 4*32], pre-GELU
-        hyper = self._ffn_exact("mask_decoder.output_hypernetworks_mlps.0.", mask_tok)                # f32 [n,32]
-        logits = K.hyper_mask_f32(u, hyper, n, self.G, 32, act=K.ACT_GELU)
-        iou = self._ffn_exact("mask_decoder.iou_prediction_head.", iou_tok)[:, 0]
-        return logits, iou
+        hs = [self._ffn_exact(f"mask_decoder.output_hypernetworks_mlps.{m}.", q3[:, 1 + m].contiguous()) for m in sel]
+        hyper = hs[0][:, None] if len(hs) == 1 else torch.stack(hs, 1)                                 # f32 [n,M,32]
+        logits = K.hyper_mask_multi_f32(u, hyper, n, self.G, 32, act=K.ACT_GELU)
+        iou = self._ffn_exact("mask_decoder.iou_prediction_head.", iou_tok)                             # f32 [n,4]
+        return (logits[:, 0], iou[:, 0]) if masks is None else (logits, iou)
 
     def predict(self, emb, boxes, frame_hw, resized_hw, precision=None):
         """emb [n*G*G,256] rows of the NHWC image embedding; boxes f32 [n,>=4] device, xyxy in FRAME pixels.
@@ -310,3 +340,40 @@ class MaskDecoder:
         logits, iou = (self.lowres_exact if precision == "exact" else self.lowres)(emb, sparse)
         mask, stats = K.mask_post(logits, self.S, nh, nw, h, w)
         return dict(mask=mask, stats=stats, iou=iou, lowres=logits)
+
+    def decode(self, emb, frame_hw, resized_hw, points=None, labels=None, boxes=None, mask_input=None, multimask=False,
+               return_logits=False, precision=None):
+        """SamPredictor.predict_torch for n frames with one prompt set each (all frames share Np and whether a box / a mask
+        is given).  emb [n*G*G,256] rows; points f32 [n,Np,2] with labels int32 [n,Np] (1 / 0 / -1), boxes f32 [n,>=4], all
+        device tensors in FRAME pixels; mask_input f32 [n,4G,4G] (an earlier call's low-res logits).  Labels outside
+        {-1,0,1} give NaN tokens (LmxSamPredictor checks them on the host).
+        -> dict(iou f32 [n,C], lowres f32 [n,C,4G,4G], and mask u8 [n,C,h,w] + stats int64 [n,C,8] or, with return_logits,
+        logits f32 [n,C,h,w]); C = 3 (masks 1..3) with multimask, else 1 (mask 0)."""
+        h, w = frame_hw
+        nh, nw = resized_hw
+        if points is None and boxes is None:
+            raise ValueError("decode needs points (with labels) or boxes")
+        if (points is None) != (labels is None):
+            raise ValueError("points and labels go together")
+        precision = precision or self.precision
+        if precision not in ("exact", "f16"):
+            raise ValueError(f"precision {precision!r}: expected 'exact' or 'f16'")
+        sparse = K.prompt_points(points, labels, boxes, nw / w, nh / h, float(self.S), self.gauss, self.point_embed, self.not_a_point,
+                                 self.corner)
+        keys = None
+        if mask_input is not None:
+            if self.mask_params is None:
+                raise ValueError("mask_input needs the prompt_encoder.mask_embed.* weights (mask_embed_param_spec()), which this "
+                                 "decoder's state dict does not hold")
+            keys = K.mask_embed(mask_input, emb, self.mask_params, self.G)
+        sel = (1, 2, 3) if multimask else (0,)
+        logits, iou = (self.lowres_exact if precision == "exact" else self.lowres)(emb, sparse, keys=keys, masks=sel)
+        n, C, L, _ = logits.shape
+        out = dict(iou=iou[:, sel[0]:sel[-1] + 1], lowres=logits)
+        flat = logits.view(n * C, L, L)
+        if return_logits:
+            out["logits"] = K.mask_logits(flat, self.S, nh, nw, h, w).view(n, C, h, w)
+        else:
+            mask, stats = K.mask_post(flat, self.S, nh, nw, h, w)
+            out["mask"], out["stats"] = mask.view(n, C, h, w), stats.view(n, C, 8)
+        return out
