@@ -387,6 +387,25 @@ int lmx_k_hyper_mask_multi_f32(const float* up, const float* hyper, float* logit
 /* Sam.postprocess_masks without the threshold (predict(return_logits=True)): logits f32 [n][L][L] -> out f32 [n][h][w] with
  * lmx_k_mask_post's interpolation arithmetic, so (out > 0) is lmx_k_mask_post's mask bit for bit.  out 16-byte aligned. */
 int lmx_k_mask_logits(const float* logits, int n, int L, int T, int nh, int nw, int h, int w, float* out, lmx_stream_t stream);
+
+/* ---- SamAutomaticMaskGenerator (segment_anything automatic_mask_generator.py; lmx/amg.py) ----------------------------------
+ * lmx_k_mask_score replaces calculate_stability_score + (masks > mask_threshold) + batched_mask_to_box applied to the
+ * full-resolution output of Sam.postprocess_masks in _process_batch, without writing any output pixel (csrc/amg.hip).
+ * logits f32 [.][L][L]; row i scores logits[idx ? idx[i] : i] (idx int32 [n] on the device, entries in range, or NULL).
+ * v is lmx_k_mask_logits' value at each of the h x w output pixels, bit for bit.  out int64 [n][8] =
+ *   { count(v > f32(thr + off)), count(v > f32(thr - off)), count(v > f32(thr)) (the area),
+ *     min_x, min_y, max_x, max_y of v > f32(thr) (inclusive; [0,0,0,0] for an empty mask, as batched_mask_to_box), 0 }.
+ * The thresholds are rounded as torch compares an f32 tensor with a Python float.  n <= 65535 per launch. */
+int lmx_k_mask_score(const float* logits, int n, int L, int T, int nh, int nw, int h, int w, double thr, double off,
+                     const int32_t* idx, int64_t* out, lmx_stream_t stream);
+/* lmx_k_nms_boxes replaces torchvision.ops.batched_nms with one category in _process_crop (scores = iou_preds) and
+ * _generate_masks (scores = 1 / crop box area) (csrc/nms.hip).  boxes f32 [n][ldb] xyxy (first 4 columns), scores f32 [n]
+ * of any sign, valid u8 [n] (0 = not a candidate) or NULL; n <= 16384.  Greedy suppression of IoU > iou in the order
+ * descending score, ties to the lower index (a stable argsort of -scores; -0 == +0); IoU in f32 as torchvision's CPU
+ * kernel, compared in double.  keep_out int32 [n]: kept indices in that order, then -1; count_out int32 [1].
+ * workspace: n * 20 bytes, 16-byte aligned. */
+int lmx_k_nms_boxes(const float* boxes, int64_t ldb, const float* scores, const uint8_t* valid, int n, double iou, int32_t* keep_out,
+                    int32_t* count_out, void* workspace, lmx_stream_t stream);
 /* Bit-pack a 0/non-0 byte image: dst[r][c] holds pixels 8c..8c+7 of row r, first pixel in the most significant bit
  * (numpy.packbits order); rows are padded to ceil(w/8) bytes.  Used for the mask persisted / gathered per frame
  * (services/sam3-pipeline/app/main.py:83-89 returns a bool[H,W] mask; SURVEY.md §8b `mask_bits [n, h, ceil(w/8)]`):

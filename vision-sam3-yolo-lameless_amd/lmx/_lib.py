@@ -92,6 +92,8 @@ SIGNATURES = {
     "lmx_k_hyper_mask_multi": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "lmx_k_hyper_mask_multi_f32": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "lmx_k_mask_logits": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _VP, _VP]),
+    "lmx_k_mask_score": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _D, _D, _VP, _VP, _VP]),
+    "lmx_k_nms_boxes": (_I, [_VP, _I64, _VP, _VP, _I, _D, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -185,6 +185,47 @@ sam_model_registry = {"default": _sam_builder("vit_h"), "vit_h": _sam_builder("v
                       "vit_b": _sam_builder("vit_b")}
 
 
+class ResizeLongestSide:
+    """segment_anything.utils.transforms.ResizeLongestSide: coordinates and boxes from the original frame to the resized
+    input frame (longest side = target_length).  The same arithmetic: numpy in float64, torch in f32 (a Python-float scale
+    applied to the f32 tensor); apply_image is PIL's bilinear resize, as torchvision's resize of a PIL image is."""
+
+    def __init__(self, target_length):
+        self.target_length = target_length
+
+    @staticmethod
+    def get_preprocess_shape(oldh, oldw, long_side_length):
+        return sam.resize_longest_side(oldh, oldw, long_side_length)
+
+    def apply_image(self, image):
+        from PIL import Image
+
+        h, w = self.get_preprocess_shape(image.shape[0], image.shape[1], self.target_length)
+        return np.array(Image.fromarray(image).resize((w, h), Image.BILINEAR))
+
+    def apply_coords(self, coords, original_size):
+        old_h, old_w = original_size
+        new_h, new_w = self.get_preprocess_shape(old_h, old_w, self.target_length)
+        coords = np.array(coords).astype(float)
+        coords[..., 0] = coords[..., 0] * (new_w / old_w)
+        coords[..., 1] = coords[..., 1] * (new_h / old_h)
+        return coords
+
+    def apply_boxes(self, boxes, original_size):
+        return self.apply_coords(np.asarray(boxes).reshape(-1, 2, 2), original_size).reshape(-1, 4)
+
+    def apply_coords_torch(self, coords, original_size):
+        old_h, old_w = original_size
+        new_h, new_w = self.get_preprocess_shape(old_h, old_w, self.target_length)
+        coords = coords.clone().to(torch.float)
+        coords[..., 0] = coords[..., 0] * (new_w / old_w)
+        coords[..., 1] = coords[..., 1] * (new_h / old_h)
+        return coords
+
+    def apply_boxes_torch(self, boxes, original_size):
+        return self.apply_coords_torch(boxes.reshape(-1, 2, 2), original_size).reshape(-1, 4)
+
+
 class LmxSamPredictor:
     """`SamPredictor(sam)`: set_image caches the image embedding, predict decodes a prompt against it (the only state kept
     across calls, as in the reference: sam3 main.py:80-88).  `model` may also be any encoder with the HieraEncoder surface
@@ -194,6 +235,7 @@ class LmxSamPredictor:
         self.model = sam_model
         self.encoder, self.decoder = sam_model.image_encoder, sam_model.mask_decoder
         self.device = sam_model.device
+        self.transform = ResizeLongestSide(self.encoder.cfg.image)
         self.is_image_set = False
         # the embedding is a static buffer of the capture (valid until the next set_image: the predictor's own contract); the
         # decoder's outputs are copied to the host before predict returns
@@ -283,7 +325,41 @@ class LmxSamPredictor:
         return masks, out["iou"][0].cpu().numpy(), out["lowres"][0].cpu().numpy()
 
 
+    def predict_torch(self, point_coords, point_labels, boxes=None, mask_input=None, multimask_output=True, return_logits=False):
+        """segment_anything's SamPredictor.predict_torch: B prompt sets against the image set_image cached, all as device
+        tensors in the RESIZED INPUT frame (predictor.transform.apply_coords_torch / apply_boxes_torch): point_coords [B,N,2]
+        with point_labels [B,N], boxes [B,4], mask_input [B,1,256,256].  Returns device tensors (masks [B,C,H,W] bool, or
+        f32 logits with return_logits; iou_predictions f32 [B,C]; low_res_masks f32 [B,C,256,256]), C = 3 with
+        multimask_output, else 1.  Runs eagerly; prompt i gives the bits it gets in a batch of its own."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        if (point_coords is None) != (point_labels is None):
+            raise ValueError("point_coords and point_labels must be given together")
+        if point_coords is None and boxes is None:
+            raise ValueError("predict_torch needs a prompt: point_coords with point_labels, and / or boxes")
+        dev = self.device
+        pts = lbl = bx = mk = None
+        if point_coords is not None:
+            if point_coords.dim() != 3 or point_coords.shape[2] != 2 or tuple(point_labels.shape) != tuple(point_coords.shape[:2]):
+                raise ValueError(f"point_coords must be [B,N,2] and point_labels [B,N], got {tuple(point_coords.shape)} and "
+                                 f"{tuple(point_labels.shape)}")
+            pts = point_coords.to(dev, torch.float32).contiguous()
+            lbl = point_labels.to(dev, torch.int32).contiguous()
+        if boxes is not None:
+            bx = boxes.to(dev, torch.float32).reshape(-1, 4).contiguous()
+        if mask_input is not None:
+            if mask_input.dim() != 4 or tuple(mask_input.shape[1:]) != (1, 256, 256):
+                raise ValueError(f"mask_input must be [B,1,256,256], got {tuple(mask_input.shape)}")
+            mk = mask_input.to(dev, torch.float32)[:, 0].contiguous()
+        out = self.decoder.decode(self.features, self.original_size, self.input_size, points=pts, labels=lbl, boxes=bx, mask_input=mk,
+                                  multimask=multimask_output, return_logits=return_logits, input_frame=True)
+        masks = out["logits"] if return_logits else out["mask"].bool()
+        return masks, out["iou"], out["lowres"]
+
+
 SamPredictor = LmxSamPredictor
+
+from .amg import SamAutomaticMaskGenerator  # noqa: E402  (lmx.amg builds on LmxSamPredictor)
 
 
 # ---- transformers AutoImageProcessor / AutoModel ----------------------------------------------------------------------------

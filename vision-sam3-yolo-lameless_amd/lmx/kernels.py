@@ -795,6 +795,55 @@ def mask_logits(logits, T, nh, nw, h, w):
     return out
 
 
+def mask_score(logits, T, nh, nw, h, w, thr=0.0, off=1.0, idx=None):
+    """SamAutomaticMaskGenerator's stability counts, area and box of (mask_logits(logits, ...) > thr) without the full-size
+    logits: logits f32 [N,L,L] -> int64 [n,8] = count(v > thr + off), count(v > thr - off), area, min_x, min_y, max_x, max_y
+    (inclusive; 0 0 0 0 when empty), 0 (lmx_k_mask_score).  idx: optional int32 [n] rows of `logits` to score (n = N
+    without it); launches of at most 65535 rows."""
+    dev = _dev(logits, idx)
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 3:
+        raise LmxError("mask_score: logits must be contiguous f32 [n,L,L]")
+    N, L, _ = logits.shape
+    if idx is not None:
+        if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+            raise LmxError("mask_score: idx must be contiguous int32 [n]")
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+            raise LmxError(f"mask_score: idx outside 0..{N - 1}")
+    n = N if idx is None else idx.numel()
+    out = torch.empty((n, 8), dtype=torch.int64, device=logits.device)
+    lib = _lib.load()
+    for s in range(0, n, 65535):
+        k = min(65535, n - s)
+        src = logits[s:s + k] if idx is None else logits
+        check(lib.lmx_k_mask_score(_ptr(src), k, L, T, nh, nw, h, w, float(thr), float(off), _ptr(None if idx is None else idx[s:s + k]),
+                                   _ptr(out[s:s + k]), _stream(dev)), "lmx_k_mask_score")
+    return out
+
+
+NMS_BOXES_MAX = 16384
+
+
+def nms_boxes(boxes, scores, iou, valid=None):
+    """torchvision.ops.nms on device: boxes f32 [n,>=4] xyxy rows, scores f32 [n] (any sign), valid bool/u8 [n] or None ->
+    (keep int32 [n]: kept indices in suppression order then -1, count int32 [1]) (lmx_k_nms_boxes)."""
+    dev = _dev(boxes, scores, valid)
+    n, cols, ldb = _rows(boxes, "nms_boxes boxes")
+    if boxes.dtype != torch.float32 or cols < 4 or scores.dtype != torch.float32 or tuple(scores.shape) != (n,) or not scores.is_contiguous():
+        raise LmxError("nms_boxes: boxes f32 [n,>=4] and scores contiguous f32 [n] expected")
+    if not 0 < n <= NMS_BOXES_MAX:
+        raise LmxError(f"nms_boxes: {n} candidates (1..{NMS_BOXES_MAX})")
+    if valid is not None:
+        if valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (n,):
+            raise LmxError("nms_boxes: valid must be bool / uint8 [n]")
+        valid = valid.contiguous().view(torch.uint8)
+    keep = torch.empty((n,), dtype=torch.int32, device=boxes.device)
+    count = torch.empty((1,), dtype=torch.int32, device=boxes.device)
+    ws = torch.empty((n * 5,), dtype=torch.float32, device=boxes.device)
+    check(_lib.load().lmx_k_nms_boxes(_ptr(boxes), ldb, _ptr(scores), _ptr(valid), n, float(iou), _ptr(keep), _ptr(count), _ptr(ws),
+                                      _stream(dev)), "lmx_k_nms_boxes")
+    return keep, count
+
+
 def contour_features(mask):
     """mask u8 [n,h,w] (0 / non-0) on device -> int64 [n,8] = 2*contourArea, unit steps, diagonal steps, min x, min y, max x,
     max y, number of external contours of the largest external contour (lmx_k_contour_features, csrc/contour.hip)."""

@@ -341,14 +341,13 @@ class MaskDecoder:
         mask, stats = K.mask_post(logits, self.S, nh, nw, h, w)
         return dict(mask=mask, stats=stats, iou=iou, lowres=logits)
 
-    def decode(self, emb, frame_hw, resized_hw, points=None, labels=None, boxes=None, mask_input=None, multimask=False,
-               return_logits=False, precision=None):
-        """SamPredictor.predict_torch for n frames with one prompt set each (all frames share Np and whether a box / a mask
-        is given).  emb [n*G*G,256] rows; points f32 [n,Np,2] with labels int32 [n,Np] (1 / 0 / -1), boxes f32 [n,>=4], all
-        device tensors in FRAME pixels; mask_input f32 [n,4G,4G] (an earlier call's low-res logits).  Labels outside
-        {-1,0,1} give NaN tokens (LmxSamPredictor checks them on the host).
-        -> dict(iou f32 [n,C], lowres f32 [n,C,4G,4G], and mask u8 [n,C,h,w] + stats int64 [n,C,8] or, with return_logits,
-        logits f32 [n,C,h,w]); C = 3 (masks 1..3) with multimask, else 1 (mask 0)."""
+    def decode_lowres(self, emb, frame_hw, resized_hw, points=None, labels=None, boxes=None, mask_input=None, multimask=False,
+                      precision=None, input_frame=False):
+        """The prompt encoder and mask decoder of decode() without the post-processing -> (lowres f32 [n,C,4G,4G], iou f32
+        [n,C]).  emb holds n*G*G rows (one image per prompt set) or G*G rows: ONE image embedding that serves all n prompt
+        sets (SamPredictor.predict_torch's batch of prompts; every prompt gets the keys of that embedding, so prompt i
+        decodes to the bits it gets alone).  input_frame: points / boxes are already in the resized input frame (predict_torch's
+        convention: scale 1 in lmx_k_prompt_points) instead of frame pixels."""
         h, w = frame_hw
         nh, nw = resized_hw
         if points is None and boxes is None:
@@ -358,8 +357,14 @@ class MaskDecoder:
         precision = precision or self.precision
         if precision not in ("exact", "f16"):
             raise ValueError(f"precision {precision!r}: expected 'exact' or 'f16'")
-        sparse = K.prompt_points(points, labels, boxes, nw / w, nh / h, float(self.S), self.gauss, self.point_embed, self.not_a_point,
+        sx, sy = (1.0, 1.0) if input_frame else (nw / w, nh / h)
+        sparse = K.prompt_points(points, labels, boxes, sx, sy, float(self.S), self.gauss, self.point_embed, self.not_a_point,
                                  self.corner)
+        n, P = sparse.shape[0], self.G * self.G
+        if emb.shape[0] == P and n > 1:
+            emb = emb.repeat(n, 1)  # one image, n prompt sets
+        elif emb.shape[0] != n * P:
+            raise ValueError(f"emb has {emb.shape[0]} rows: expected {P} (one image) or {n * P} ({n} images)")
         keys = None
         if mask_input is not None:
             if self.mask_params is None:
@@ -368,8 +373,23 @@ class MaskDecoder:
             keys = K.mask_embed(mask_input, emb, self.mask_params, self.G)
         sel = (1, 2, 3) if multimask else (0,)
         logits, iou = (self.lowres_exact if precision == "exact" else self.lowres)(emb, sparse, keys=keys, masks=sel)
+        return logits, iou[:, sel[0]:sel[-1] + 1]
+
+    def decode(self, emb, frame_hw, resized_hw, points=None, labels=None, boxes=None, mask_input=None, multimask=False,
+               return_logits=False, precision=None, input_frame=False):
+        """SamPredictor.predict_torch for n prompt sets (all share Np and whether a box / a mask is given), against n image
+        embeddings or one (decode_lowres).  emb [n*G*G,256] or [G*G,256] rows; points f32 [n,Np,2] with labels int32 [n,Np]
+        (1 / 0 / -1), boxes f32 [n,>=4], all device tensors in FRAME pixels (in the resized input frame with input_frame);
+        mask_input f32 [n,4G,4G] (an earlier call's low-res logits).  Labels outside {-1,0,1} give NaN tokens
+        (LmxSamPredictor checks them on the host).
+        -> dict(iou f32 [n,C], lowres f32 [n,C,4G,4G], and mask u8 [n,C,h,w] + stats int64 [n,C,8] or, with return_logits,
+        logits f32 [n,C,h,w]); C = 3 (masks 1..3) with multimask, else 1 (mask 0)."""
+        h, w = frame_hw
+        nh, nw = resized_hw
+        logits, iou = self.decode_lowres(emb, frame_hw, resized_hw, points=points, labels=labels, boxes=boxes, mask_input=mask_input,
+                                         multimask=multimask, precision=precision, input_frame=input_frame)
         n, C, L, _ = logits.shape
-        out = dict(iou=iou[:, sel[0]:sel[-1] + 1], lowres=logits)
+        out = dict(iou=iou, lowres=logits)
         flat = logits.view(n * C, L, L)
         if return_logits:
             out["logits"] = K.mask_logits(flat, self.S, nh, nw, h, w).view(n, C, h, w)
