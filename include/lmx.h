@@ -41,7 +41,8 @@ int lmx_device_count(void);
 
 /* ---- dtypes / activations -------------------------------------------------------------------------- */
 enum { LMX_F16 = 0, LMX_F32 = 1 };
-enum { LMX_ACT_NONE = 0, LMX_ACT_SILU = 1, LMX_ACT_GELU = 2 /* erf form */, LMX_ACT_RELU = 3 };
+enum { LMX_ACT_NONE = 0, LMX_ACT_SILU = 1, LMX_ACT_GELU = 2 /* erf form */, LMX_ACT_RELU = 3,
+       LMX_ACT_SWIGLU = 4 /* lmx_k_gemm only: gated epilogue, see there */ };
 
 /* ---- K3/K12/K2: GEMM / 1x1 conv / 3x3 conv (implicit GEMM), f16 in, f32 MFMA accumulate ------------
  * C[m][n] = res[m][n] + scale[n] * act( sum_k A[m][k] * W[n][k] + bias[n] )
@@ -58,6 +59,15 @@ enum { LMX_ACT_NONE = 0, LMX_ACT_SILU = 1, LMX_ACT_GELU = 2 /* erf form */, LMX_
  *             transitions, TF:models/sam2/modeling_sam2.py Sam2MultiScaleBlock, and of the pooled queries).  No
  *             residual / scale / activation; M >= 512, N >= 96, N%8==0 (the LDS-DMA kernel); A smaller than 2 GB.
  * W is f16 [N][K] (K contiguous).  Requirements: K%8==0, N%4==0, lda%8==0, Cin%8==0, 16-byte aligned bases.
+ *
+ * act = LMX_ACT_SWIGLU (the gated MLPs of DINOv3 ViT-S+/H+ `down(silu(gate(x)) * up(x))`, TF:models/dinov3_vit/modeling_dinov3_vit.py
+ * DINOv3ViTGatedMLP, and of DINOv2 giant, TF:models/dinov2/modeling_dinov2.py Dinov2SwiGLUFFN): W holds the gate AND the up
+ * projection, N = 2 I rows interleaved in blocks of 16 — rows 32t .. 32t+15 are gate rows 16t .. 16t+15, rows 32t+16 .. 32t+31
+ * the up rows of the same channels (lmx/dino.py pack_gated) — and bias [N] is interleaved the same way.  Then
+ *   C[m][j] = scale[j] * ( silu(acc[m][g(j)] + bias[g(j)]) * (acc[m][u(j)] + bias[u(j)]) ),  g(j) = 32 (j / 16) + j % 16, u(j) = g(j) + 16
+ * N in the descriptor stays the GEMM's N (2 I); C HAS N / 2 COLUMNS (ldc >= N / 2) and scale, if given, N / 2 entries.  The
+ * 2 I-wide intermediate is never written.  f32 accumulator + f32 bias, silu and the product in f32, ONE rounding to f16 — in
+ * every kernel variant, so a row's bits do not depend on M.  a_mode 0 and f16 output only, N%32==0, no residual, a_rep or split_k.
  */
 typedef struct {
   const void* A;
@@ -101,6 +111,12 @@ void lmx_dbg_set_gemm2_variant(int v);
 int lmx_k_layernorm(const void* x, int in_dtype, int64_t ldx, const float* gamma, const float* beta,
                     void* y, int out_dtype, int64_t ldy, int rows, int D, float eps, int act, lmx_stream_t stream);
 /* (act = LMX_ACT_NONE or LMX_ACT_GELU applied after the affine: the SAM decoder's LayerNorm2d -> GELU, TF sam :523) */
+
+/* ---- the gate of a gated MLP as its own pass: out[r][j] = f16( silu(gu[r][j]) * gu[r][I + j] ), gu f16 [rows][2 I] (gate columns
+ * first, row stride ldg), out f16 [rows][I] (row stride ldo); I%8==0.  The unfused form of LMX_ACT_SWIGLU — plain GEMM to a 2 I-wide f16
+ * buffer, then this — which rounds gate and up to f16 before the product: kept as the timing reference of the fused epilogue
+ * (tools/swiglu_timing.py); the DINO plan always uses the epilogue. */
+int lmx_k_swiglu(const void* gu, int64_t ldg, void* out, int64_t ldo, int rows, int I, lmx_stream_t stream);
 
 /* ---- K11 + K8-K10 + K14 for Hiera's 8 x 8-token windows: x += proj(window_attention(qkv(layer_norm1(x)))) as one kernel ---------
  * Replaces, for the blocks of Hiera-B+ stage 1 (D = 112, 2 heads; TF:models/sam2/modeling_sam2.py Sam2MultiScaleBlock.forward,

@@ -2,6 +2,7 @@
 // networks need, and an implicit-GEMM A-operand generator for NHWC 3x3 convolutions.
 //
 //   C[m][n] = res[m][n] + scale[n] * act( sum_k A[m][k] * W[n][k] + bias[n] )
+//   (LMX_ACT_SWIGLU: C[m][j] = scale[j] * silu(gate_j) * up_j from interleaved gate / up rows of W; N / 2 output columns)
 //
 // Replaces (see include/lmx.h): Conv2d+BN+SiLU of YOLOv8, the qkv/proj/fc1/fc2 Linears of
 // the SAM / Hiera / DINO ViT blocks (Appendix A.2-A.5).
@@ -166,6 +167,44 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const lmx_gemm_desc p) {
     __syncthreads();
   }
 
+  // gated epilogue (LMX_ACT_SWIGLU, lmx.h): W's rows alternate 16 gate and 16 up rows, so fragment j (even) holds the gate and
+  // fragment j + 1 the up projection of the SAME 4 output channels of this lane's row: no cross-lane traffic.  Rounding sequence
+  // shared with gemm2_kernel: f32 accumulator + f32 bias, silu in f32, product in f32, (scale in f32,) one rounding to f16.
+  if (p.act == LMX_ACT_SWIGLU) {
+    if constexpr (OUT_DT == LMX_F16 && FN % 2 == 0) {
+      half_t* C = reinterpret_cast<half_t*>(p.C);
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+        const int m = m0 + wm * (BM / 2) + i * 16 + frow;
+        if (m >= p.M) continue;
+#pragma unroll
+        for (int j = 0; j < FN; j += 2) {
+          const int n = n0 + wn * (BN / 2) + j * 16 + fq * 4;  // gate rows of W; the up rows are n + 16 (N % 32 == 0)
+          if (n >= p.N) continue;
+          f32x4 g = acc[i][j], u = acc[i][j + 1];
+          if (p.bias) {
+            g += *reinterpret_cast<const f32x4*>(p.bias + n);
+            u += *reinterpret_cast<const f32x4*>(p.bias + n + 16);
+          }
+          const int no = (n >> 5) * 16 + (n & 15);  // output channel
+          f32x4 v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = __fmul_rn(lmx_act(g[e], LMX_ACT_SILU), u[e]);
+          if (p.scale) {
+            const f32x4 s = *reinterpret_cast<const f32x4*>(p.scale + no);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = __fmul_rn(v[e], s[e]);
+          }
+          half4_t o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (half_t)v[e];
+          *reinterpret_cast<half4_t*>(C + (int64_t)m * p.ldc + no) = o;
+        }
+      }
+    }
+    return;
+  }
+
   // epilogue: lane owns row m = ..+(lane&15), channels n..n+3 with n = ..+(lane>>4)*4
 #pragma unroll
   for (int i = 0; i < FM; ++i) {
@@ -260,12 +299,19 @@ extern "C" int lmx_k_gemm(const lmx_gemm_desc* dp, lmx_stream_t stream) {
   LMX_REQUIRE(d.K % 8 == 0, "lmx_k_gemm: K=%d must be a multiple of 8", d.K);
   LMX_REQUIRE(d.N % 4 == 0, "lmx_k_gemm: N=%d must be a multiple of 4", d.N);
   LMX_REQUIRE(d.lda % 8 == 0, "lmx_k_gemm: lda=%lld must be a multiple of 8", (long long)d.lda);
-  LMX_REQUIRE(d.ldc % 4 == 0 && d.ldc >= d.N, "lmx_k_gemm: bad ldc=%lld", (long long)d.ldc);
+  const bool gated = d.act == LMX_ACT_SWIGLU;  // C then has N / 2 columns
+  LMX_REQUIRE(d.ldc % 4 == 0 && d.ldc >= (gated ? d.N / 2 : d.N), "lmx_k_gemm: bad ldc=%lld", (long long)d.ldc);
   LMX_REQUIRE(aligned16(d.A) && aligned16(d.W), "lmx_k_gemm: A/W must be 16-byte aligned");
   LMX_REQUIRE((((uintptr_t)d.C) & 7) == 0, "lmx_k_gemm: C must be 8-byte aligned");
   LMX_REQUIRE(d.out_dtype == LMX_F16 || d.out_dtype == LMX_F32, "lmx_k_gemm: bad out_dtype %d", d.out_dtype);
   LMX_REQUIRE(d.out_dtype == LMX_F16 || aligned16(d.C), "lmx_k_gemm: f32 C must be 16-byte aligned");
-  LMX_REQUIRE(d.act >= LMX_ACT_NONE && d.act <= LMX_ACT_RELU, "lmx_k_gemm: bad act %d", d.act);
+  LMX_REQUIRE(d.act >= LMX_ACT_NONE && d.act <= LMX_ACT_SWIGLU, "lmx_k_gemm: bad act %d", d.act);
+  if (gated) {
+    LMX_REQUIRE(d.N % 32 == 0, "lmx_k_gemm: LMX_ACT_SWIGLU: N=%d (gate + up rows, interleaved by 16) must be a multiple of 32", d.N);
+    LMX_REQUIRE(!d.res, "lmx_k_gemm: LMX_ACT_SWIGLU takes no residual");
+    LMX_REQUIRE(d.a_mode == 0 && d.a_rep <= 1 && d.split_k <= 1, "lmx_k_gemm: LMX_ACT_SWIGLU: dense A only (a_mode 0; no pooled rows, convolution, a_rep or split_k); a_mode=%d", d.a_mode);
+    LMX_REQUIRE(d.out_dtype == LMX_F16, "lmx_k_gemm: LMX_ACT_SWIGLU writes f16 (one rounding of the f32 product)");
+  }
   if (d.bias) LMX_REQUIRE(aligned16(d.bias), "lmx_k_gemm: bias must be 16-byte aligned");
   if (d.scale) LMX_REQUIRE(aligned16(d.scale), "lmx_k_gemm: scale must be 16-byte aligned");
   if (d.res) LMX_REQUIRE(d.ldr % 4 == 0 && d.ldr >= d.N, "lmx_k_gemm: bad ldr=%lld", (long long)d.ldr);

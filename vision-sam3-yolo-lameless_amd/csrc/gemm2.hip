@@ -54,7 +54,10 @@ constexpr int waves_per_simd(int BM, int BN, int BK, int NSTAGE) {
   const int wps = (smem <= 80 * 1024 ? 2 : 1) * nwave / 4;
   return wps < 1 ? 1 : wps;
 }
-template <int OUT_DT, int BM, int BN, int BK, int NSTAGE, int AMODE, int STAG>
+// GATED: the LMX_ACT_SWIGLU epilogue (lmx.h) as an instantiation of its own — compiled into the common kernel it costs the other
+// epilogues registers (the f16 256 x 256 x 64 tiling went from 0 to 7 spilled VGPRs, the staggered 256 x 128 x 64 one from 3 waves
+// per SIMD to 2; bench.py -1 %).  With GATED = false the kernel is the code it was before the gated epilogue existed.
+template <int OUT_DT, int BM, int BN, int BK, int NSTAGE, int AMODE, int STAG, bool GATED = false>
 __global__ __launch_bounds__(waves_per_simd(BM, BN, BK, NSTAGE) * 256) void gemm2_kernel(const lmx_gemm_desc p, const int ntiles, const int nt_ok) {
   constexpr int NWAVE = (BM / 64) * (BN / 64);
   constexpr int STAGE_BYTES = (BM + BN) * BK * 2;
@@ -199,7 +202,11 @@ __global__ __launch_bounds__(waves_per_simd(BM, BN, BK, NSTAGE) * 256) void gemm
   float bias_v = 0.f, scale_v = 1.f;
   if (AMODE != 1 && tid < BN && n0 + tid < p.N) {
     if (p.bias && sp_ == 0) bias_v = p.bias[n0 + tid];
-    if (p.scale) scale_v = p.scale[n0 + tid];
+    if constexpr (GATED) {  // scale is per OUTPUT channel: N / 2 of them, BN / 2 in this tile
+      if (p.scale && tid < BN / 2 && (n0 >> 1) + tid < (p.N >> 1)) scale_v = p.scale[(n0 >> 1) + tid];
+    } else {
+      if (p.scale) scale_v = p.scale[n0 + tid];
+    }
   }
 
 #pragma unroll
@@ -333,7 +340,51 @@ __global__ __launch_bounds__(waves_per_simd(BM, BN, BK, NSTAGE) * 256) void gemm
       if constexpr (SCALE) v *= *reinterpret_cast<const f32x4*>(blj + BN + j * 16);
       return v;
     };
-    if constexpr (OUT_DT == LMX_F16 && AMODE == 2) {
+    if constexpr (ACT == LMX_ACT_SWIGLU) {
+      // gated epilogue (lmx.h LMX_ACT_SWIGLU; f16 out, dense A: checked by lmx_k_gemm).  W's rows alternate 16 gate and 16 up rows, so
+      // fragments 2jj / 2jj + 1 hold gate / up of the same 4 output channels of a lane: the wave's 64 x 64 accumulators become a
+      // 64 x 32 output tile, transposed through the wave's LDS slice as below.  Rounding sequence of gemm_kernel (gemm.hip): f32
+      // accumulator + f32 bias, silu in f32, product in f32, (scale,) one rounding to f16.
+      if constexpr (OUT_DT == LMX_F16 && AMODE == 0) {
+        half_t* t16 = reinterpret_cast<half_t*>(my);
+        constexpr int RS = 40;  // halfs per LDS row: 32 + 8
+        const bool nt_g = nt_ok && ((p.ldc * 2) & 127) == 0 && (int64_t)p.M * p.N >= (32ll << 20);
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+          for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+              const f32x4 g = acc[pass * 2 + ii][2 * jj] + *reinterpret_cast<const f32x4*>(blj + jj * 32);
+              const f32x4 u = acc[pass * 2 + ii][2 * jj + 1] + *reinterpret_cast<const f32x4*>(blj + jj * 32 + 16);
+              f32x4 v;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = __fmul_rn(act_apply(g[e], LMX_ACT_SILU), u[e]);
+              if constexpr (SCALE) {
+                const f32x4 sc = *reinterpret_cast<const f32x4*>(bl + BN + wn * 32 + jj * 16 + fq * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = __fmul_rn(v[e], sc[e]);
+              }
+              const half4_t o = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+              *reinterpret_cast<half4_t*>(t16 + (ii * 16 + frow) * RS + jj * 16 + fq * 4) = o;
+            }
+#pragma unroll
+          for (int it = 0; it < 2; ++it) {
+            const int row = it * 16 + (lane >> 2), c8 = lane & 3;
+            const half8_t o = *reinterpret_cast<const half8_t*>(t16 + row * RS + c8 * 8);
+            const int m = m0 + wm * 64 + pass * 32 + row;
+            const int no = ((n0 + wn * 64) >> 1) + c8 * 8;  // output channel
+            if (m < p.M && no < (p.N >> 1)) {
+              half8_t* dst = reinterpret_cast<half8_t*>(reinterpret_cast<half_t*>(p.C) + (int64_t)m * p.ldc + no);
+              if (nt_g)
+                asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(o) : "memory");
+              else
+                *dst = o;
+            }
+          }
+        }
+      }
+    } else if constexpr (OUT_DT == LMX_F16 && AMODE == 2) {
       // pooled rows, f16 out (Hiera's pooled queries): as the f32 form below, 8 bytes per lane
 #pragma unroll
       for (int pass = 0; pass < 4; ++pass)
@@ -452,7 +503,10 @@ __global__ __launch_bounds__(waves_per_simd(BM, BN, BK, NSTAGE) * 256) void gemm
     using T = std::true_type;
     using F = std::false_type;
     const int act = p.act;
-    if (p.scale) {
+    if constexpr (GATED) {
+      if (p.scale) epilogue(std::integral_constant<int, LMX_ACT_SWIGLU>{}, T{});
+      else epilogue(std::integral_constant<int, LMX_ACT_SWIGLU>{}, F{});
+    } else if (p.scale) {
       if (act == LMX_ACT_NONE) epilogue(std::integral_constant<int, LMX_ACT_NONE>{}, T{});
       else if (act == LMX_ACT_SILU) epilogue(std::integral_constant<int, LMX_ACT_SILU>{}, T{});
       else if (act == LMX_ACT_GELU) epilogue(std::integral_constant<int, LMX_ACT_GELU>{}, T{});
@@ -490,6 +544,20 @@ int launch2(const lmx_gemm_desc& d, hipStream_t st) {
     nt_ok = getenv("LMX_GEMM2_NO_NT") ? 0 : 1;
   }
   if (persist > 0 && grid > 256 * persist) grid = 256 * persist;
+  if (d.act == LMX_ACT_SWIGLU) {  // (f16 out, dense A: checked by lmx_k_gemm)
+    if constexpr (AMODE == 0) {
+      static bool gated_attr_set = false;
+      if (!gated_attr_set) {
+        LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<LMX_F16, BM, BN, BK, NSTAGE, AMODE, STAG, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        gated_attr_set = true;
+      }
+      hipLaunchKernelGGL((gemm2_kernel<LMX_F16, BM, BN, BK, NSTAGE, AMODE, STAG, true>), dim3(grid), dim3(BM * BN / 64), smem, st, d, ntiles, nt_ok);
+      return lmx_launch_check("gemm2_kernel (gated)");
+    } else {
+      return LMX_EINVAL;
+    }
+  }
   if (d.out_dtype == LMX_F16)
     hipLaunchKernelGGL((gemm2_kernel<LMX_F16, BM, BN, BK, NSTAGE, AMODE, STAG>), dim3(grid), dim3(BM * BN / 64), smem, st, d, ntiles, nt_ok);
   else

@@ -258,6 +258,24 @@ __global__ __launch_bounds__(256) void rope_kernel(half_t* __restrict__ x, int64
   }
 }
 
+// out[r][j] = f16( silu(gu[r][j]) * gu[r][I + j] ): the gate of a gated MLP as its own pass over an f16 [rows][2 I] GEMM output
+// (gate columns first).  The unfused form of lmx_k_gemm's LMX_ACT_SWIGLU epilogue; a thread owns 8 channels.
+__global__ __launch_bounds__(256) void swiglu_kernel(const half_t* __restrict__ gu, int64_t ldg, half_t* __restrict__ out,
+                                                     int64_t ldo, int rows, int I) {
+  const int per_row = I / 8;
+  const int64_t total = (int64_t)rows * per_row;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % per_row) * 8;
+    const int64_t r = i / per_row;
+    const half8_t g = *reinterpret_cast<const half8_t*>(gu + r * ldg + c);
+    const half8_t u = *reinterpret_cast<const half8_t*>(gu + r * ldg + I + c);
+    half8_t o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (half_t)__fmul_rn(lmx_act((float)g[e], LMX_ACT_SILU), (float)u[e]);
+    *reinterpret_cast<half8_t*>(out + r * ldo + c) = o;
+  }
+}
+
 inline int grid_for(int64_t total, int block = 256) {
   int64_t g = (total + block - 1) / block;
   if (g > 256 * 8) g = 256 * 8;  // 8 blocks per CU, grid-stride the rest
@@ -364,4 +382,15 @@ extern "C" int lmx_k_rope(void* x, int64_t ld, int B, int T, int H, int hd, int 
   hipLaunchKernelGGL(rope_kernel, dim3(grid_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<half_t*>(x), ld, B, T, H, hd, n_prefix, cos_t, sin_t);
   return lmx_launch_check("rope_kernel");
+}
+
+extern "C" int lmx_k_swiglu(const void* gu, int64_t ldg, void* out, int64_t ldo, int rows, int I, lmx_stream_t stream) {
+  LMX_REQUIRE(gu && out, "lmx_k_swiglu: null pointer");
+  LMX_REQUIRE(rows > 0 && I > 0 && I % 8 == 0, "lmx_k_swiglu: rows=%d I=%d (need I%%8==0)", rows, I);
+  LMX_REQUIRE(ldg % 8 == 0 && ldo % 8 == 0 && ldg >= 2 * (int64_t)I && ldo >= I, "lmx_k_swiglu: strides");
+  LMX_REQUIRE(aligned16(gu) && aligned16(out), "lmx_k_swiglu: alignment");
+  const int64_t total = (int64_t)rows * (I / 8);
+  hipLaunchKernelGGL(swiglu_kernel, dim3(grid_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const half_t*>(gu), ldg, reinterpret_cast<half_t*>(out), ldo, rows, I);
+  return lmx_launch_check("swiglu_kernel");
 }

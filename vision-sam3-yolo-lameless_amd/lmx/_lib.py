@@ -62,6 +62,7 @@ SIGNATURES = {
     "lmx_k_patchify_norm": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I64, _VP, _VP]),
     "lmx_k_assemble_tokens": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "lmx_k_token_mean": (_I, [_VP, _I, _VP, _I, _I, _I, _VP]),
+    "lmx_k_swiglu": (_I, [_VP, _I64, _VP, _I64, _I, _I, _VP]),
     "lmx_nms_workspace_bytes": (_I64, [_I, _I]),
     "lmx_k_nms": (_I, [_VP, _I, _I, _I, _F, _D, _I, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lmx_k_letterbox": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),

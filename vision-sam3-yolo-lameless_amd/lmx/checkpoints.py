@@ -220,24 +220,54 @@ def load_yolo_weights(path):
 # ---- DINOv2 / DINOv3 ---------------------------------------------------------------------------------------------------------
 def load_dino_dir(model_dir):
     """A local Hugging Face model directory (config.json + model.safetensors) -> (DinoConfig, state dict).  The service asks
-    the hub by name (dinov3 main.py:34-35); offline deployments point models.dinov3.model_name at such a directory."""
+    the hub by name (dinov3 main.py:34-35); offline deployments point models.dinov3.model_name at such a directory.
+
+    Loads: dinov2 (plain MLP, or `use_swiglu_ffn` as in giant), dinov2_with_registers, dinov3_vit (plain or `use_gated_mlp`, any
+    of query / key / value / proj / mlp bias switched off).  Refuses, naming the config field: a head dim the attention kernels do
+    not serve (DINOv3-7B's 128), a `hidden_act` other than gelu (plain) / silu (gated), and a checkpoint whose MLP tensors are
+    not those of the configured form — a gated checkpoint must not run as a plain MLP, nor the reverse."""
     from . import dino
 
     d = Path(model_dir)
     with open(d / "config.json") as f:
         c = json.load(f)
     mt = c.get("model_type", "")
-    if mt == "dinov2":
+    if mt in ("dinov2", "dinov2_with_registers"):
+        gated = bool(c.get("use_swiglu_ffn", False))
+        ratio = c.get("mlp_ratio", 4)
         cfg = dino.DinoConfig(arch="dinov2", hidden=c["hidden_size"], layers=c["num_hidden_layers"], heads=c["num_attention_heads"],
-                              mlp=int(c["hidden_size"] * c.get("mlp_ratio", 4)), patch=c["patch_size"], registers=0,
-                              eps=c.get("layer_norm_eps", 1e-6), pos_grid=c.get("image_size", 518) // c["patch_size"])
+                              mlp=dino.swiglu_hidden(c["hidden_size"], ratio) if gated else int(c["hidden_size"] * ratio),
+                              patch=c["patch_size"], registers=c.get("num_register_tokens", 4) if mt == "dinov2_with_registers" else 0,
+                              eps=c.get("layer_norm_eps", 1e-6), pos_grid=c.get("image_size", 518) // c["patch_size"], gated=gated)
+        # (Dinov2SwiGLUFFN hard-codes SiLU; hidden_act configures the plain MLP only)
+        if not gated and c.get("hidden_act", "gelu") != "gelu":
+            raise RuntimeError(f"{d}: hidden_act {c['hidden_act']!r} is not supported (the plain MLP is built with gelu)")
+        gate_key, form = "encoder.layer.0.mlp.weights_in.weight", "use_swiglu_ffn"
     elif mt == "dinov3_vit":
+        gated = bool(c.get("use_gated_mlp", False))
         cfg = dino.DinoConfig(arch="dinov3", hidden=c["hidden_size"], layers=c["num_hidden_layers"], heads=c["num_attention_heads"],
                               mlp=c["intermediate_size"], patch=c["patch_size"], registers=c.get("num_register_tokens", 4),
-                              eps=c.get("layer_norm_eps", 1e-5), rope_theta=c.get("rope_theta", 100.0))
+                              eps=c.get("layer_norm_eps", 1e-5), rope_theta=c.get("rope_theta", 100.0), gated=gated,
+                              q_bias=bool(c.get("query_bias", True)), k_bias=bool(c.get("key_bias", False)),
+                              v_bias=bool(c.get("value_bias", True)), proj_bias=bool(c.get("proj_bias", True)),
+                              mlp_bias=bool(c.get("mlp_bias", True)))
+        want = "silu" if gated else "gelu"
+        if c.get("hidden_act", want) != want:
+            raise RuntimeError(f"{d}: hidden_act {c['hidden_act']!r} with use_gated_mlp={gated} is not supported (built: gelu for the "
+                               "plain MLP, silu for the gated one)")
+        gate_key, form = "model.layer.0.mlp.gate_proj.weight", "use_gated_mlp"
     else:
-        raise RuntimeError(f"{d}: model_type {mt!r} is neither dinov2 nor dinov3_vit")
+        raise RuntimeError(f"{d}: model_type {mt!r} is not one of dinov2, dinov2_with_registers, dinov3_vit")
+    try:
+        dino.check_head_dim(cfg)
+    except RuntimeError as e:
+        raise RuntimeError(f"{d}: {e}") from None
     sd = weights.load_state_dict_file(str(d / "model.safetensors"))
+    if gated and gate_key not in sd:
+        raise RuntimeError(f"{d}: config says {form}=true but the checkpoint has no gate tensor ({gate_key})")
+    if not gated and gate_key in sd:
+        raise RuntimeError(f"{d}: config says {form}=false but the checkpoint has a gate tensor ({gate_key}): it would run as a "
+                           "plain MLP and give wrong embeddings")
     missing = [k for k in dino.param_spec(cfg) if k not in sd]
     if missing:
         raise RuntimeError(f"{d}: {len(missing)} tensors missing, e.g. {missing[:3]}")

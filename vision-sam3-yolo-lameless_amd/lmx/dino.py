@@ -3,12 +3,17 @@
 
 Two architectures behind one launch sequence:
   * ``dinov2``  — what the service loads by default (facebook/dinov2-base): patch 14, learned position table
-                   (bicubic-interpolated to the input grid once, at load), separate q/k/v with bias, eps 1e-6.
+                   (bicubic-interpolated to the input grid once, at load), separate q/k/v with bias, eps 1e-6;
+                   ``registers > 0`` is dinov2_with_registers (tokens [CLS, registers, patches], the position table
+                   added to CLS and patches only).
   * ``dinov3``  — the BASELINE config (ViT-L/16): patch 16, CLS + 4 register tokens, no position table, RoPE on the
                    patch tokens of q/k, key without bias, eps 1e-5.
 Layer = LN -> fused qkv GEMM -> (RoPE) -> flash attention -> out-proj GEMM with LayerScale+residual epilogue ->
 LN -> fc1 GEMM with GELU epilogue -> fc2 GEMM with LayerScale+residual epilogue.  The residual stream is f32 in
 HBM; every GEMM/attention operand is f16 with f32 accumulation.
+``gated`` MLPs (DINOv3 ViT-S+/H+ ``down(silu(gate(x)) * up(x))``, DINOv2 giant's SwiGLU FFN): fc1 is ONE GEMM over the
+gate and up rows interleaved by 16 (``pack_gated``) whose epilogue is the gate (lmx_k_gemm LMX_ACT_SWIGLU): the
+2 x mlp wide intermediate is never written.  Head dims up to 96 (every ViT up to H+ / giant has 64); DINOv3-7B's 128 is refused at load.
 """
 import math
 from dataclasses import dataclass
@@ -34,6 +39,13 @@ class DinoConfig:
     image: int = 224              # crop size fed to the network
     resize_edge: int = 256        # shortest-edge resize before the crop
     pos_grid: int = 37            # dinov2 only: side of the learned position grid (518/14)
+    gated: bool = False           # MLP form: down(silu(gate(x)) * up(x)) instead of down(gelu(up(x)))
+    # dinov3 only (DINOv3ViTConfig query_bias / key_bias / value_bias / proj_bias / mlp_bias): which projections have a bias
+    q_bias: bool = True
+    k_bias: bool = False
+    v_bias: bool = True
+    proj_bias: bool = True
+    mlp_bias: bool = True
 
     @property
     def head_dim(self):
@@ -41,7 +53,7 @@ class DinoConfig:
 
     @property
     def n_prefix(self):
-        return 1 + (self.registers if self.arch == "dinov3" else 0)
+        return 1 + self.registers
 
     @property
     def grid(self):
@@ -60,8 +72,56 @@ def dinov2_base():
     return DinoConfig(arch="dinov2", hidden=768, layers=12, heads=12, mlp=3072, patch=14, registers=0, eps=1e-6)
 
 
+def dinov3_vitsplus16(**kw):
+    """DINOv3 ViT-S+/16: gated MLP."""
+    return DinoConfig(**{**dict(hidden=384, layers=12, heads=6, mlp=1536, gated=True), **kw})
+
+
+def dinov3_vithplus16(**kw):
+    """DINOv3 ViT-H+/16: gated MLP."""
+    return DinoConfig(**{**dict(hidden=1280, layers=32, heads=20, mlp=5120, gated=True), **kw})
+
+
+def swiglu_hidden(hidden, mlp_ratio=4):
+    """Dinov2SwiGLUFFN's hidden_features (TF:models/dinov2/modeling_dinov2.py): 2/3 of the plain width, rounded up to 8."""
+    return (int(int(hidden * mlp_ratio) * 2 / 3) + 7) // 8 * 8
+
+
+def dinov2_giant(**kw):
+    """DINOv2 giant: SwiGLU FFN (hidden_features 4096)."""
+    return DinoConfig(**{**dict(arch="dinov2", hidden=1536, layers=40, heads=24, mlp=swiglu_hidden(1536), patch=14, registers=0,
+                              eps=1e-6, gated=True), **kw})
+
+
+def dinov2_reg_base(**kw):
+    """DINOv2-with-registers base: 4 register tokens."""
+    return DinoConfig(**{**dict(arch="dinov2", hidden=768, layers=12, heads=12, mlp=3072, patch=14, registers=4, eps=1e-6), **kw})
+
+
+def check_head_dim(cfg):
+    """The attention kernels serve head dims up to 96 in multiples of 8; every released DINOv2 / DINOv3 ViT up to H+ has 64.
+    DINOv3-7B (128) is refused here rather than mis-run."""
+    hd = cfg.head_dim
+    if cfg.hidden % cfg.heads or hd % 8 or hd > 96:
+        raise K.LmxError(f"head dim {hd} (hidden_size {cfg.hidden} / num_attention_heads {cfg.heads}) is not supported: the attention "
+                         "kernels serve multiples of 8 up to 96 (DINOv3-7B, head dim 128, is out of scope)")
+
+
+def pack_gated(gate, up):
+    """Gate and up rows ([I, ...] each) -> the [2I, ...] operand of lmx_k_gemm's LMX_ACT_SWIGLU: blocks of 16 gate rows alternate
+    with the 16 up rows of the same channels (g0..g15, u0..u15, g16..), so that a lane of the 16x16 MFMA holds gate and up of
+    one output channel in two accumulators of its own.  Works for the [I] biases too."""
+    gate, up = np.asarray(gate), np.asarray(up)
+    I = gate.shape[0]
+    if gate.shape != up.shape or I % 16:
+        raise ValueError(f"pack_gated: gate {gate.shape} / up {up.shape}: equal shapes with a multiple of 16 rows")
+    rest = gate.shape[1:]
+    return np.stack([gate.reshape((I // 16, 16) + rest), up.reshape((I // 16, 16) + rest)], axis=1).reshape((2 * I,) + rest)
+
+
 def param_spec(cfg):
-    """Ordered {HF parameter name: (shape, init kind)} — the names transformers' DINOv3ViTModel / Dinov2Model use."""
+    """Ordered {HF parameter name: (shape, init kind)} — exactly the tensors transformers' DINOv3ViTModel / Dinov2Model /
+    Dinov2WithRegistersModel have for this configuration."""
     D, I, P = cfg.hidden, cfg.mlp, cfg.patch
     s = {}
     if cfg.arch == "dinov3":
@@ -75,25 +135,32 @@ def param_spec(cfg):
             s[p + "norm1.weight"] = ((D,), "g")
             s[p + "norm1.bias"] = ((D,), "b")
             s[p + "attention.k_proj.weight"] = ((D, D), "w")
+            if cfg.k_bias:
+                s[p + "attention.k_proj.bias"] = ((D,), "b")
             s[p + "attention.v_proj.weight"] = ((D, D), "w")
-            s[p + "attention.v_proj.bias"] = ((D,), "b")
+            if cfg.v_bias:
+                s[p + "attention.v_proj.bias"] = ((D,), "b")
             s[p + "attention.q_proj.weight"] = ((D, D), "w")
-            s[p + "attention.q_proj.bias"] = ((D,), "b")
+            if cfg.q_bias:
+                s[p + "attention.q_proj.bias"] = ((D,), "b")
             s[p + "attention.o_proj.weight"] = ((D, D), "w")
-            s[p + "attention.o_proj.bias"] = ((D,), "b")
+            if cfg.proj_bias:
+                s[p + "attention.o_proj.bias"] = ((D,), "b")
             s[p + "layer_scale1.lambda1"] = ((D,), "ls")
             s[p + "norm2.weight"] = ((D,), "g")
             s[p + "norm2.bias"] = ((D,), "b")
-            s[p + "mlp.up_proj.weight"] = ((I, D), "w")
-            s[p + "mlp.up_proj.bias"] = ((I,), "b")
-            s[p + "mlp.down_proj.weight"] = ((D, I), "w")
-            s[p + "mlp.down_proj.bias"] = ((D,), "b")
+            for n, shp in ((("gate_proj", (I, D)),) if cfg.gated else ()) + (("up_proj", (I, D)), ("down_proj", (D, I))):
+                s[p + f"mlp.{n}.weight"] = (shp, "w")
+                if cfg.mlp_bias:
+                    s[p + f"mlp.{n}.bias"] = ((shp[0],), "b")
             s[p + "layer_scale2.lambda1"] = ((D,), "ls")
         s["norm.weight"] = ((D,), "g")
         s["norm.bias"] = ((D,), "b")
     else:
         s["embeddings.cls_token"] = ((1, 1, D), "tok")
         s["embeddings.mask_token"] = ((1, D), "zero")
+        if cfg.registers:
+            s["embeddings.register_tokens"] = ((1, cfg.registers, D), "tok")
         s["embeddings.position_embeddings"] = ((1, 1 + cfg.pos_grid * cfg.pos_grid, D), "tok")
         s["embeddings.patch_embeddings.projection.weight"] = ((D, 3, P, P), "w")
         s["embeddings.patch_embeddings.projection.bias"] = ((D,), "b")
@@ -109,10 +176,16 @@ def param_spec(cfg):
             s[p + "layer_scale1.lambda1"] = ((D,), "ls")
             s[p + "norm2.weight"] = ((D,), "g")
             s[p + "norm2.bias"] = ((D,), "b")
-            s[p + "mlp.fc1.weight"] = ((I, D), "w")
-            s[p + "mlp.fc1.bias"] = ((I,), "b")
-            s[p + "mlp.fc2.weight"] = ((D, I), "w")
-            s[p + "mlp.fc2.bias"] = ((D,), "b")
+            if cfg.gated:  # Dinov2SwiGLUFFN: weights_in = [gate; up] (x1, x2 = chunk(2); silu(x1) * x2)
+                s[p + "mlp.weights_in.weight"] = ((2 * I, D), "w")
+                s[p + "mlp.weights_in.bias"] = ((2 * I,), "b")
+                s[p + "mlp.weights_out.weight"] = ((D, I), "w")
+                s[p + "mlp.weights_out.bias"] = ((D,), "b")
+            else:
+                s[p + "mlp.fc1.weight"] = ((I, D), "w")
+                s[p + "mlp.fc1.bias"] = ((I,), "b")
+                s[p + "mlp.fc2.weight"] = ((D, I), "w")
+                s[p + "mlp.fc2.bias"] = ((D,), "b")
             s[p + "layer_scale2.lambda1"] = ((D,), "ls")
         s["layernorm.weight"] = ((D,), "g")
         s["layernorm.bias"] = ((D,), "b")
@@ -133,16 +206,18 @@ def rope_tables(cfg, gh, gw):
     return torch.cos(angles).contiguous(), torch.sin(angles).contiguous()
 
 
-def interpolate_pos_embed(pos, grid_in, grid_out):
+def interpolate_pos_embed(pos, grid_in, grid_out, antialias=False):
     """Dinov2Embeddings.interpolate_pos_encoding (TF:models/dinov2/modeling_dinov2.py:57-95): bicubic,
-    align_corners=False, computed in f32 on the host once at load.  pos: torch [1, 1+gi*gi, D]."""
+    align_corners=False, computed in f32 on the host once at load.  pos: torch [1, 1+gi*gi, D].
+    antialias=True: Dinov2WithRegistersEmbeddings' form (TF:models/dinov2_with_registers/modeling_dinov2_with_registers.py:128-134),
+    which low-pass filters the table when it shrinks it."""
     if grid_in == grid_out:
         return pos
     cls, patch = pos[:, :1], pos[:, 1:]
     D = pos.shape[-1]
     patch = patch.reshape(1, grid_in, grid_in, D).permute(0, 3, 1, 2)
     patch = torch.nn.functional.interpolate(patch.to(torch.float32), size=(grid_out, grid_out), mode="bicubic",
-                                            align_corners=False)
+                                            align_corners=False, antialias=antialias)
     patch = patch.permute(0, 2, 3, 1).reshape(1, -1, D)
     return torch.cat((cls, patch), dim=1)
 
@@ -165,6 +240,13 @@ class DinoEmbedder:
 
         sd = state_dict
         v3 = cfg.arch == "dinov3"
+        check_head_dim(cfg)
+        gate_key = ("model.layer.0.mlp.gate_proj.weight" if v3 else "encoder.layer.0.mlp.weights_in.weight")
+        if cfg.gated != (gate_key in sd):
+            raise K.LmxError(f"DinoEmbedder: gated={cfg.gated} but the state dict {'has' if gate_key in sd else 'lacks'} {gate_key}")
+
+        def zeros(n):
+            return np.zeros(n, np.float32)
         pe_w = sd["embeddings.patch_embeddings.weight" if v3 else "embeddings.patch_embeddings.projection.weight"]
         pe_b = sd["embeddings.patch_embeddings.bias" if v3 else "embeddings.patch_embeddings.projection.bias"]
         # conv weight [D,3,P,P] -> GEMM weight [D, (ky,kx,c)], K padded to a multiple of 8 with zero columns
@@ -180,8 +262,16 @@ class DinoEmbedder:
             self.rope = tuple(t.to(dev) for t in rope_tables(cfg, cfg.grid, cfg.grid))
         else:
             prefix = sd["embeddings.cls_token"][0]
-            pos = interpolate_pos_embed(torch.from_numpy(sd["embeddings.position_embeddings"]), cfg.pos_grid, cfg.grid)
-            self.pos = pos[0].to(torch.float32).contiguous().to(dev)
+            pos = interpolate_pos_embed(torch.from_numpy(sd["embeddings.position_embeddings"]), cfg.pos_grid, cfg.grid,
+                                        antialias=cfg.registers > 0)
+            pos = pos[0].to(torch.float32).contiguous()
+            if cfg.registers:
+                # Dinov2WithRegistersEmbeddings.forward: the position table is added to [CLS, patches] BEFORE the registers are
+                # inserted behind CLS.  Prefix rows = CLS + pos[0] (the same f32 sum), then the registers; the table handed to
+                # assemble_tokens is zero over the prefix rows and pos[1:] over the patches
+                prefix = np.concatenate([prefix + pos[:1].numpy(), sd["embeddings.register_tokens"][0]], axis=0)
+                pos = torch.cat([torch.zeros((cfg.n_prefix, D), dtype=torch.float32), pos[1:]], dim=0)
+            self.pos = pos.contiguous().to(dev)
             self.rope = None
         self.prefix = t32(prefix)
         self.layers = []
@@ -189,18 +279,26 @@ class DinoEmbedder:
             if v3:
                 p = f"model.layer.{i}."
                 qw, kw, vw = (sd[p + f"attention.{n}_proj.weight"] for n in "qkv")
-                qb, vb = sd[p + "attention.q_proj.bias"], sd[p + "attention.v_proj.bias"]
-                kb = sd.get(p + "attention.k_proj.bias", np.zeros(D, np.float32))
-                ow, ob = sd[p + "attention.o_proj.weight"], sd[p + "attention.o_proj.bias"]
-                w1, b1 = sd[p + "mlp.up_proj.weight"], sd[p + "mlp.up_proj.bias"]
-                w2, b2 = sd[p + "mlp.down_proj.weight"], sd[p + "mlp.down_proj.bias"]
+                # absent biases (query_bias / key_bias / value_bias / proj_bias / mlp_bias false) are zeros
+                qb, kb, vb = (sd.get(p + f"attention.{n}_proj.bias", zeros(D)) for n in "qkv")
+                ow, ob = sd[p + "attention.o_proj.weight"], sd.get(p + "attention.o_proj.bias", zeros(D))
+                w1, b1 = sd[p + "mlp.up_proj.weight"], sd.get(p + "mlp.up_proj.bias", zeros(cfg.mlp))
+                w2, b2 = sd[p + "mlp.down_proj.weight"], sd.get(p + "mlp.down_proj.bias", zeros(D))
+                if cfg.gated:
+                    w1 = pack_gated(sd[p + "mlp.gate_proj.weight"], w1)
+                    b1 = pack_gated(sd.get(p + "mlp.gate_proj.bias", zeros(cfg.mlp)), b1)
             else:
                 p = f"encoder.layer.{i}."
                 qw, kw, vw = (sd[p + f"attention.attention.{n}.weight"] for n in ("query", "key", "value"))
                 qb, kb, vb = (sd[p + f"attention.attention.{n}.bias"] for n in ("query", "key", "value"))
                 ow, ob = sd[p + "attention.output.dense.weight"], sd[p + "attention.output.dense.bias"]
-                w1, b1 = sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"]
-                w2, b2 = sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"]
+                if cfg.gated:
+                    wi, bi = sd[p + "mlp.weights_in.weight"], sd[p + "mlp.weights_in.bias"]
+                    w1, b1 = pack_gated(wi[:cfg.mlp], wi[cfg.mlp:]), pack_gated(bi[:cfg.mlp], bi[cfg.mlp:])
+                    w2, b2 = sd[p + "mlp.weights_out.weight"], sd[p + "mlp.weights_out.bias"]
+                else:
+                    w1, b1 = sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"]
+                    w2, b2 = sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"]
             self.layers.append(dict(
                 g1=t32(sd[p + "norm1.weight"]), b1=t32(sd[p + "norm1.bias"]),
                 wqkv=t16(np.concatenate([qw, kw, vw], 0)), bqkv=t32(np.concatenate([qb, kb, vb], 0)),
@@ -221,6 +319,7 @@ class DinoEmbedder:
         xp = K.gemm(patches, self.pe_w, bias=self.pe_b)
         x = K.assemble_tokens(xp, self.prefix, self.pos, B, np_, cfg.n_prefix, D)
         scale = hd ** -0.5
+        act1 = K.ACT_SWIGLU if cfg.gated else K.ACT_GELU
         for L in self.layers:
             h = K.layernorm(x, L["g1"], L["b1"], cfg.eps)
             qkv = K.gemm(h, L["wqkv"], bias=L["bqkv"])
@@ -232,7 +331,7 @@ class DinoEmbedder:
             K.attention(q, k, v, a, B, H, T, T, hd, scale)
             K.gemm(a, L["wo"], bias=L["bo"], scale=L["ls1"], res=x, out=x)
             h = K.layernorm(x, L["g2"], L["b2"], cfg.eps)
-            u = K.gemm(h, L["w1"], bias=L["bb1"], act=K.ACT_GELU)
+            u = K.gemm(h, L["w1"], bias=L["bb1"], act=act1)
             K.gemm(u, L["w2"], bias=L["bb2"], scale=L["ls2"], res=x, out=x)
         return K.layernorm(x, self.gf, self.bf, cfg.eps, out_dtype=torch.float32)
 

@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import AttnDesc, GemmDesc, LmxError, check
 
 F16, F32 = 0, 1
-ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU = 0, 1, 2, 3
+ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU, ACT_SWIGLU = 0, 1, 2, 3, 4
 _DT = {torch.float16: F16, torch.float32: F32}
 
 
@@ -66,7 +66,9 @@ def gemm(a, w, bias=None, act=ACT_NONE, scale=None, res=None, out=None, out_dtyp
     res_rows > 0: res is a [res_rows, N] table broadcast over the batch (row m uses res[m % res_rows]).
     pool_hw=(H, W): the rows of `a` are an [n, H, W] token grid and the result is the 2 x 2 max-pool of the product over that
     grid, [M/4, N] in [n, H/2, W/2] order (a_mode 2: the bits of gemm(...) followed by maxpool2, without the full-size
-    intermediate)."""
+    intermediate).
+    act=ACT_SWIGLU: w [2I, K] and bias [2I] hold gate and up rows interleaved by 16 (lmx.dino.pack_gated); the result is
+    scale * silu(gate) * up with N/2 = I columns (scale [I]); f16 out, no residual."""
     dev = _dev(a, w, bias, scale, res, out)
     M, K, lda = _rows(a, "gemm A")
     N, K2, ldw = _rows(w, "gemm W")
@@ -75,11 +77,12 @@ def gemm(a, w, bias=None, act=ACT_NONE, scale=None, res=None, out=None, out_dtyp
     if a.dtype != torch.float16 or w.dtype != torch.float16:
         raise LmxError("gemm: A and W must be float16")
     Mout = M // 4 if pool_hw else M
+    Nout = N // 2 if act == ACT_SWIGLU else N
     if out is None:
-        out = torch.empty((Mout, N), dtype=out_dtype, device=a.device)
+        out = torch.empty((Mout, Nout), dtype=out_dtype, device=a.device)
     Mo, No, ldc = _rows(out, "gemm C")
-    if (Mo, No) != (Mout, N):
-        raise LmxError(f"gemm: out shape {tuple(out.shape)} != ({Mout},{N})")
+    if (Mo, No) != (Mout, Nout):
+        raise LmxError(f"gemm: out shape {tuple(out.shape)} != ({Mout},{Nout})")
     d = GemmDesc()
     d.A, d.W, d.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
@@ -87,8 +90,8 @@ def gemm(a, w, bias=None, act=ACT_NONE, scale=None, res=None, out=None, out_dtyp
     d.lda, d.ldc, d.ldr = lda, ldc, 0
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
         raise LmxError("gemm: bias must be float32 [N]")
-    if scale is not None and (scale.dtype != torch.float32 or scale.numel() != N):
-        raise LmxError("gemm: scale must be float32 [N]")
+    if scale is not None and (scale.dtype != torch.float32 or scale.numel() != Nout):
+        raise LmxError("gemm: scale must be float32 [N] (ACT_SWIGLU: [N/2])")
     if res is not None:
         Mr, Nr, ldr = _rows(res, "gemm res")
         if (Mr, Nr) != ((res_rows or M), N) or res.dtype != out.dtype:
@@ -473,6 +476,22 @@ def assemble_tokens(patch, prefix, pos, B, np_, n_prefix, D):
     out = torch.empty((B * (np_ + n_prefix), D), dtype=torch.float32, device=patch.device)
     check(_lib.load().lmx_k_assemble_tokens(_ptr(patch), _ptr(prefix), _ptr(pos), _ptr(out), B, np_, n_prefix, D,
                                             _stream(dev)), "lmx_k_assemble_tokens")
+    return out
+
+
+def swiglu(gu, out=None):
+    """f16 [rows, 2I] (gate columns first) -> f16 [rows, I] = silu(gate) * up (lmx_k_swiglu): the unfused form of ACT_SWIGLU,
+    kept as its timing reference."""
+    dev = _dev(gu, out)
+    rows, N, ldg = _rows(gu, "swiglu in")
+    if gu.dtype != torch.float16 or N % 2:
+        raise LmxError("swiglu: input must be float16 [rows, 2I]")
+    if out is None:
+        out = torch.empty((rows, N // 2), dtype=torch.float16, device=gu.device)
+    ro, Io, ldo = _rows(out, "swiglu out")
+    if (ro, Io) != (rows, N // 2) or out.dtype != torch.float16:
+        raise LmxError(f"swiglu: out must be float16 ({rows},{N // 2})")
+    check(_lib.load().lmx_k_swiglu(_ptr(gu), ldg, _ptr(out), ldo, rows, N // 2, _stream(dev)), "lmx_k_swiglu")
     return out
 
 
@@ -876,7 +895,7 @@ def _work(name, args):
         a_bytes = 2 * M * (Kd // max(d.a_rep, 1))
         if d.a_mode == 1:  # 3x3 implicit GEMM: the input image is read once, not 9 times
             a_bytes = 2 * (M // max(d.Ho * d.Wo, 1)) * d.H * d.W_ * d.Cin
-        by = a_bytes + 2 * N * Kd + osz * (M // 4 if d.a_mode == 2 else M) * N + (osz * (d.res_rows or M) * N if d.res else 0)
+        by = a_bytes + 2 * N * Kd + osz * (M // 4 if d.a_mode == 2 else M) * (N // 2 if d.act == ACT_SWIGLU else N) + (osz * (d.res_rows or M) * N if d.res else 0)
         fl = 2.0 * M * N * Kd
         key = f"gemm M={M} N={N} K={Kd} out={'f32' if osz == 4 else 'f16'} conv3x3={d.a_mode} act={d.act} res={int(bool(d.res))}"
         return ("gemm/mfma-bound" if fl / by >= RIDGE_FLOP_PER_BYTE else "gemm/hbm-bound"), fl, by, key
