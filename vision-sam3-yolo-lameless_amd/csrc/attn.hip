@@ -1550,33 +1550,21 @@ extern "C" int lmx_k_attention(const lmx_attn_desc* dp, lmx_stream_t stream) {
     hipLaunchKernelGGL(attn_small_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, d, g, (int)items);
     return lmx_launch_check("attn_small_kernel");
   }
-  static int no_sp = -1;
-  if (no_sp < 0) no_sp = getenv("LMX_ATTN_NO_SP") ? 1 : 0;
+  static const int no_sp = lmx_env_set("LMX_ATTN_NO_SP");
   if (!no_sp && !d.rel && d.hd <= 64 && d.Tk > 128 && d.Tk <= 208 && d.Tq > 64 && d.Tq <= 208) {  // whole sequence per workgroup
     const int64_t items = (int64_t)d.B * d.H;
     LMX_REQUIRE(items < (1ll << 31), "lmx_k_attention: grid too large");
-    static int sp_qb = 0, no_spp = -1;
-    if (!sp_qb) sp_qb = getenv("LMX_ATTN_SP_QB") ? atoi(getenv("LMX_ATTN_SP_QB")) : 2;
-    if (no_spp < 0) no_spp = getenv("LMX_ATTN_NO_SPP") ? 1 : 0;
+    static const int sp_qb = lmx_env_int("LMX_ATTN_SP_QB", 2), no_spp = lmx_env_set("LMX_ATTN_NO_SPP");
     // persistent double-buffered form (one 8-wave workgroup per CU walks a range of items): window geometry needs both padding
     // vectors (a padded key with no vector would have to be WRITTEN as zeros, which the masked DMA does not do)
     if (!no_spp && items >= 64 && (d.mode == 0 || (d.pad_k && d.pad_v)) && d.hd % 8 == 0) {
       constexpr int SMEM = 2 * 3 * 208 * 64 * 2;
-      static bool attr_set = false;
-      if (!attr_set) {
-        LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_spp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-        LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_spp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-        attr_set = true;
-      }
-      static int n_cu = 0;
-      if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        LMX_HIP(hipGetDevice(&dev));
-        LMX_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-      }
-      const unsigned grid = (unsigned)(items < n_cu ? items : n_cu);
+      int dev;
+      unsigned grid;
+      LMX_TRY(lmx_stream_device(st, &dev));
+      LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&attn_spp_kernel<true>), SMEM, dev));
+      LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&attn_spp_kernel<false>), SMEM, dev));
+      LMX_TRY(lmx_persistent_grid(items, dev, &grid));
       if (d.hd <= 56)
         hipLaunchKernelGGL((attn_spp_kernel<true>), dim3(grid), dim3(512), SMEM, st, d, g, (int)items);
       else
@@ -1601,20 +1589,15 @@ extern "C" int lmx_k_attention(const lmx_attn_desc* dp, lmx_stream_t stream) {
   LMX_REQUIRE(nblk < (1ll << 31), "lmx_k_attention: grid too large");
   const bool ones = d.hd <= 56;
   // LDS-DMA staging: flat geometry without bias, at least a few key tiles, per-(batch) K/V extent within a 31-bit buffer
-  static int no_dma = -1, no_lazy = 0, no_gp = 0;
-  if (no_dma < 0) {
-    no_gp = getenv("LMX_ATTN_NO_GP") ? 1 : 0;  // A/B: the unpipelined LDS-DMA form of attn_kernel
-    no_dma = getenv("LMX_ATTN_NO_DMA") ? 1 : 0;
-    no_lazy = getenv("LMX_ATTN_NO_LAZY") ? 1 : 0;
-  }
+  static const int no_dma = lmx_env_set("LMX_ATTN_NO_DMA"), no_lazy = lmx_env_set("LMX_ATTN_NO_LAZY");
+  static const int no_gp = lmx_env_set("LMX_ATTN_NO_GP");  // A/B: the unpipelined LDS-DMA form of attn_kernel
   const bool dma = !no_dma && !wide && d.mode == 0 && !d.rel && big && d.Tk >= 256 && (int64_t)d.Tk * d.ldk * 2 < 0x7fff0000ll &&
                    (int64_t)d.Tk * d.ldv * 2 < 0x7fff0000ll;
   if (no_lazy) nQT = -nQT;
   // the pipelined kernel runs 4 waves (128 queries) per workgroup; LMX_ATTN_GP_WAVES=8 selects the 8-wave form (256 queries share a
   // K / V tile, one LDS-DMA piece per wave and tensor instead of two): measured SLOWER, 1595 vs 1526 us at B = 30, H = 8, T = 4096 —
   // the barrier among eight waves costs more than the saved issue slots (identical bits)
-  static int gp_waves = -1;
-  if (gp_waves < 0) gp_waves = getenv("LMX_ATTN_GP_WAVES") ? atoi(getenv("LMX_ATTN_GP_WAVES")) : 4;
+  static const int gp_waves = lmx_env_int("LMX_ATTN_GP_WAVES", 4);
   const bool gp8 = gp_waves == 8;
   const int nQT8 = (d.Tq + 255) / 256;
 #define GP_LAUNCH(ones)                                                                                                                    \

@@ -35,6 +35,33 @@ void lmx_set_error(const char* fmt, ...);
     }                                                                                   \
   } while (0)
 
+// propagate the LMX_* code of a host helper (its error text is already set)
+#define LMX_TRY(call)               \
+  do {                              \
+    const int rc_ = (call);         \
+    if (rc_ != LMX_OK) return rc_;  \
+  } while (0)
+
+// ---- per-device launch state (api.hip).  A launcher keeps NO static of its own for these: one process drives several
+// devices from several threads (lmx/kernels.py _stream), so whatever is learned or set once is keyed by the device the
+// stream belongs to and guarded there.
+// the ordinal of the device a launch on `st` goes to.  The NULL stream (torch's default stream) belongs to no device: such a launch
+// goes to the calling thread's CURRENT device, which the caller must have made the operands' device
+int lmx_stream_device(hipStream_t st, int* dev);
+// multiProcessorCount of device `dev` (256 if the runtime reports none), queried once per device; < 0: an LMX_* error
+int lmx_cu_count(int dev);
+// the grid of a persistent kernel: one workgroup per CU of `dev`, or `need` of them if that is fewer
+int lmx_persistent_grid(int64_t need, int dev, unsigned* grid);
+// allow `kernel` up to `bytes` of dynamic LDS on device `dev` (hipFuncAttributeMaxDynamicSharedMemorySize): the runtime is
+// called once per (kernel, device), later calls only look the pair up
+int lmx_allow_lds(const void* kernel, int bytes, int dev);
+// development switches.  A switch that steers dispatch is read ONCE, as the initialiser of a function-local `static const int`
+// (C++11 evaluates it once, thread-safe); only an argument check may ask per call (lmx_k_ln_mlp's LMX_MLP448).
+// atoi of the variable or dflt if it is unset | 1 if it is set at all | its first character (0: unset or empty)
+int lmx_env_int(const char* name, int dflt);
+int lmx_env_set(const char* name);
+int lmx_env_char(const char* name);
+
 static inline int lmx_launch_check(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

@@ -261,12 +261,9 @@ template <int BM, int BN, int AMODE, int OUT_DT>
 int launch(const lmx_gemm_desc& d, hipStream_t st) {
   const int MT = (d.M + BM - 1) / BM, NT = (d.N + BN - 1) / BN;
   const size_t smem = (size_t)2 * (BM + BN) * BK * sizeof(half_t);
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, AMODE, OUT_DT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    attr_set = true;
-  }
+  int dev;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, AMODE, OUT_DT>), (int)smem, dev));
   hipLaunchKernelGGL((gemm_kernel<BM, BN, AMODE, OUT_DT>), dim3(MT * NT), dim3(256), smem, st, d);
   return lmx_launch_check("gemm_kernel");
 }
@@ -283,12 +280,8 @@ int dispatch_tile(const lmx_gemm_desc& d, hipStream_t st) {
 int lmx_gemm2_launch(const lmx_gemm_desc& d, hipStream_t st);  // gemm2.hip
 
 static bool force_v1() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("LMX_GEMM_V1");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
+  static const int v = lmx_env_char("LMX_GEMM_V1");
+  return v == '1';
 }
 
 extern "C" int lmx_k_gemm(const lmx_gemm_desc* dp, lmx_stream_t stream) {
@@ -366,8 +359,7 @@ extern "C" int lmx_k_gemm(const lmx_gemm_desc* dp, lmx_stream_t stream) {
   // (3 x 3 convolutions with 64 output channels — YOLOv8-l's first C2f stage and Detect's box branch: 2.3 M rows at 150 frames — also
   // take the LDS-DMA kernel: half of its 128-wide n-tile is zero-filled, but these launches are bound by A staging, not by the MFMA:
   // LMX_GEMM_N64=0 restores the register-staged kernel for them)
-  static int n64 = -1;
-  if (n64 < 0) n64 = (getenv("LMX_GEMM_N64") && getenv("LMX_GEMM_N64")[0] == '0') ? 0 : 1;
+  static const int n64 = lmx_env_char("LMX_GEMM_N64") != '0';
   const int n_min = (conv_ok && n64 && d.M >= 65536) ? 64 : 96;
   if ((d.a_mode == 0 || conv_ok) && d.M >= 512 && d.N >= n_min && d.N % 8 == 0 && d.ldc % 8 == 0 && (!d.res || d.ldr % 8 == 0) &&
       aligned16(d.C) && (!d.res || aligned16(d.res)) && !force_v1())

@@ -527,31 +527,19 @@ template <int BM, int BN, int BK, int NSTAGE, int AMODE, int STAG = 0>
 int launch2(const lmx_gemm_desc& d, hipStream_t st) {
   const int MT = (d.M + BM - 1) / BM, NT = (d.N + BN - 1) / BN;
   const size_t smem = smem_bytes(BM, BN, BK, NSTAGE);  // the ring is >= NWAVE * 4608 B of epilogue staging for every variant
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<LMX_F16, BM, BN, BK, NSTAGE, AMODE, STAG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<LMX_F32, BM, BN, BK, NSTAGE, AMODE, STAG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    attr_set = true;
-  }
+  int dev;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  // (both here, before the gated form below: the order in which host code first names the instantiations is their order in the code object)
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&gemm2_kernel<LMX_F16, BM, BN, BK, NSTAGE, AMODE, STAG>), (int)smem, dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&gemm2_kernel<LMX_F32, BM, BN, BK, NSTAGE, AMODE, STAG>), (int)smem, dev));
   const int ntiles = MT * NT * (d.split_k > 1 ? d.split_k : 1);
   int grid = ntiles;
-  static int persist = -1, nt_ok = 1;  // LMX_GEMM2_PERSIST = workgroups per CU of the persistent grid (0: one per tile)
-  if (persist < 0) {
-    const char* e = getenv("LMX_GEMM2_PERSIST");
-    persist = e ? atoi(e) : 0;
-    nt_ok = getenv("LMX_GEMM2_NO_NT") ? 0 : 1;
-  }
+  static const int persist = lmx_env_int("LMX_GEMM2_PERSIST", 0);  // workgroups per CU of the persistent grid (0: one per tile)
+  static const int nt_ok = !lmx_env_set("LMX_GEMM2_NO_NT");
   if (persist > 0 && grid > 256 * persist) grid = 256 * persist;
   if (d.act == LMX_ACT_SWIGLU) {  // (f16 out, dense A: checked by lmx_k_gemm)
     if constexpr (AMODE == 0) {
-      static bool gated_attr_set = false;
-      if (!gated_attr_set) {
-        LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<LMX_F16, BM, BN, BK, NSTAGE, AMODE, STAG, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        gated_attr_set = true;
-      }
+      LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&gemm2_kernel<LMX_F16, BM, BN, BK, NSTAGE, AMODE, STAG, true>), (int)smem, dev));
       hipLaunchKernelGGL((gemm2_kernel<LMX_F16, BM, BN, BK, NSTAGE, AMODE, STAG, true>), dim3(grid), dim3(BM * BN / 64), smem, st, d, ntiles, nt_ok);
       return lmx_launch_check("gemm2_kernel (gated)");
     } else {
@@ -575,15 +563,11 @@ static int g_variant = -1;  // -1: read LMX_GEMM2_VARIANT on first use; lmx_dbg_
 extern "C" void lmx_dbg_set_gemm2_variant(int v) { g_variant = v; }
 
 int lmx_gemm2_launch(const lmx_gemm_desc& d, hipStream_t st) {
-  if (g_variant < 0) {
-    const char* e = getenv("LMX_GEMM2_VARIANT");
-    g_variant = e ? e[0] : 0;
-  }
+  if (g_variant < 0) g_variant = lmx_env_char("LMX_GEMM2_VARIANT");
   const int variant = g_variant;
   if (d.a_mode == 2) return launch2<256, 256, 64, 2, 2>(d, st);  // pooled rows (f32 out): one tiling
   if (d.a_mode == 1) {  // 3x3 convolution, Cin % 32 == 0 (checked by the caller)
-    static int conv_small = -1;
-    if (conv_small < 0) conv_small = getenv("LMX_GEMM2_CONV_SMALL") ? 1 : 0;
+    static const int conv_small = lmx_env_set("LMX_GEMM2_CONV_SMALL");
     const int64_t t256 = (int64_t)((d.M + 255) / 256) * ((d.N + 255) / 256);
     const double q256 = (double)t256 / (double)(((t256 + 255) / 256) * 256);
     if (!conv_small && d.N % 256 == 0 && t256 >= 230 && q256 >= 0.75) return launch2<256, 256, 32, 3, 1, 1>(d, st);

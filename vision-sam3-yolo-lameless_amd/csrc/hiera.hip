@@ -306,23 +306,13 @@ extern "C" int lmx_k_hiera_attn8(const void* h, float* x, int64_t ldx, const flo
   LMX_REQUIRE(ldx >= D && ldx % 4 == 0 && aligned16(x) && aligned16(h) && aligned16(wqkv_p) && aligned16(wo_p), "lmx_k_hiera_attn8: ldx / alignment");
   const int64_t nwin = (int64_t)n_img * (Gh / 8) * (Gw / 8);
   LMX_REQUIRE(nwin < (1ll << 31), "lmx_k_hiera_attn8: too many windows");
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_attn8_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_attn8_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    attr_set = true;
-  }
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    LMX_HIP(hipGetDevice(&dev));
-    LMX_HIP(hipGetDeviceProperties(&prop, dev));
-    n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  const int64_t need = (nwin + 3) / 4;
-  const unsigned grid = (unsigned)(need < n_cu ? need : n_cu);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int dev;
+  unsigned grid;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&hiera_attn8_kernel<true>), SMEM, dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&hiera_attn8_kernel<false>), SMEM, dev));
+  LMX_TRY(lmx_persistent_grid((nwin + 3) / 4, dev, &grid));
   const half_t* hp = reinterpret_cast<const half_t*>(h);
   const half_t *wq = reinterpret_cast<const half_t*>(wqkv_p), *wop = reinterpret_cast<const half_t*>(wo_p);
   const float sl2 = scale * 1.44269504088896340736f;
@@ -531,21 +521,13 @@ extern "C" int lmx_k_hiera_attn4(const void* h, float* x, int64_t ldx, const voi
   const int64_t nwin = (int64_t)n_img * (Gh / 4) * (Gw / 4);
   LMX_REQUIRE(nwin < (1ll << 31), "lmx_k_hiera_attn4: too many windows");
   const int64_t ngroup = (nwin + NW4 * TB4 - 1) / (NW4 * TB4);
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_attn4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM4));
-    attr_set = true;
-  }
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    LMX_HIP(hipGetDevice(&dev));
-    LMX_HIP(hipGetDeviceProperties(&prop, dev));
-    n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  const unsigned grid = (unsigned)(ngroup < n_cu ? ngroup : n_cu);
-  hipLaunchKernelGGL(hiera_attn4_kernel, dim3(grid), dim3(NW4 * 64), SMEM4, reinterpret_cast<hipStream_t>(stream),
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int dev;
+  unsigned grid;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&hiera_attn4_kernel), SMEM4, dev));
+  LMX_TRY(lmx_persistent_grid(ngroup, dev, &grid));
+  hipLaunchKernelGGL(hiera_attn4_kernel, dim3(grid), dim3(NW4 * 64), SMEM4, st,
                      reinterpret_cast<const half_t*>(h), x, ldx, reinterpret_cast<const half_t*>(w_img), bias, Gh, Gw, (int)nwin, (int)ngroup,
                      scale * 1.44269504088896340736f);
   return lmx_launch_check("hiera_attn4_kernel");
@@ -974,27 +956,19 @@ extern "C" int lmx_k_hiera_attn_pool(const void* h, float* out, const void* w_im
   LMX_REQUIRE(nwin < (1ll << 31), "lmx_k_hiera_attn_pool: too many windows");
   const int per = s3 ? NW2 * 4 : NWP;  // windows per workgroup pass
   const int64_t ngroup = (nwin + per - 1) / per;
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_attnp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEMP));
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_attnq_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2));
-    attr_set = true;
-  }
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    LMX_HIP(hipGetDevice(&dev));
-    LMX_HIP(hipGetDeviceProperties(&prop, dev));
-    n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  const unsigned grid = (unsigned)(ngroup < n_cu ? ngroup : n_cu);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int dev;
+  unsigned grid;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&hiera_attnp_kernel), SMEMP, dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&hiera_attnq_kernel), SMEM2, dev));
+  LMX_TRY(lmx_persistent_grid(ngroup, dev, &grid));
   if (s3)
-    hipLaunchKernelGGL(hiera_attnq_kernel, dim3(grid), dim3(NW2 * 64), SMEM2, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(hiera_attnq_kernel, dim3(grid), dim3(NW2 * 64), SMEM2, st,
                        reinterpret_cast<const half_t*>(h), out, reinterpret_cast<const half_t*>(w_img), bias, Gh, Gw, (int)nwin, (int)ngroup,
                        scale * 1.44269504088896340736f);
   else
-    hipLaunchKernelGGL(hiera_attnp_kernel, dim3(grid), dim3(NWP * 64), SMEMP, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(hiera_attnp_kernel, dim3(grid), dim3(NWP * 64), SMEMP, st,
                        reinterpret_cast<const half_t*>(h), out, reinterpret_cast<const half_t*>(w_img), bias, Gh, Gw, (int)nwin, (int)ngroup,
                        scale * 1.44269504088896340736f);
   return lmx_launch_check("hiera_attn_pool kernel");
@@ -1219,22 +1193,13 @@ __global__ __launch_bounds__(NWM * 64, 2) void hiera_mlp_kernel(float* __restric
 template <int DD>
 int launch_hiera_mlp(float* x, int64_t ldx, const void* img, const float* bias, float eps, int64_t rows, void* x16, void* h_next, hipStream_t st) {
   constexpr int SM = NSTM * MAT + MlpCfg<DD>::NB * 4, TBM = mlp_tb<DD>();
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_mlp_kernel<DD>), hipFuncAttributeMaxDynamicSharedMemorySize, SM));
-    attr_set = true;
-  }
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    LMX_HIP(hipGetDevice(&dev));
-    LMX_HIP(hipGetDeviceProperties(&prop, dev));
-    n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
   const int64_t ngroup = (rows + NWM * TBM * 16 - 1) / (NWM * TBM * 16);
   LMX_REQUIRE(ngroup < (1ll << 31), "lmx_k_ln_mlp_img: too many rows");
-  const unsigned grid = (unsigned)(ngroup < n_cu ? ngroup : n_cu);
+  int dev;
+  unsigned grid;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&hiera_mlp_kernel<DD>), SM, dev));
+  LMX_TRY(lmx_persistent_grid(ngroup, dev, &grid));
   hipLaunchKernelGGL(hiera_mlp_kernel<DD>, dim3(grid), dim3(NWM * 64), SM, st, x, ldx, reinterpret_cast<const half_t*>(img), bias, eps, rows,
                      reinterpret_cast<half_t*>(x16), reinterpret_cast<half_t*>(h_next), (int)ngroup);
   return lmx_launch_check("hiera_mlp_kernel");

@@ -363,19 +363,15 @@ int launch(float* x, int64_t ldx, const half_t* hn, const float* gam, const floa
            const half_t* w2, const float* b2, int64_t rows, half_t* x16, const float* gam_n, const float* bet_n, half_t* h_n, hipStream_t st) {
   constexpr int DP = D <= 128 ? 128 : (D <= 256 ? 256 : 512);
   const size_t smem = (size_t)NST * (HC * DP * 2 + DP * 64) + 4 * D * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_mlp_kernel<D, QB, NW, NST, OCC, INLN, RING>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem));
-    attr_set = true;
-  }
+  int dev;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&ln_mlp_kernel<D, QB, NW, NST, OCC, INLN, RING>), (int)smem, dev));
   const int64_t per = NW * 16 * QB;
   const int64_t nb = (rows + per - 1) / per;
   LMX_REQUIRE(nb < 0x7fffffffll, "lmx_k_ln_mlp: too many rows");
   // staggered LDS-DMA issue (see the kernel): -3 % at D = 224, -6 % at D = 448, neutral at D = 112 (four waves at three workgroups
   // per CU are de-phased anyway); identical bits.  LMX_MLP_STAGGER=0 / 1 overrides.
-  static int stagger_env = -2;
-  if (stagger_env == -2) stagger_env = getenv("LMX_MLP_STAGGER") ? atoi(getenv("LMX_MLP_STAGGER")) : -1;
+  static const int stagger_env = lmx_env_int("LMX_MLP_STAGGER", -1);
   const int stagger = stagger_env >= 0 ? stagger_env : (D >= 224 ? 1 : 0);
   hipLaunchKernelGGL((ln_mlp_kernel<D, QB, NW, NST, OCC, INLN, RING>), dim3((unsigned)nb), dim3(NW * 64), smem, st, x, ldx, hn, gam, bet, eps, w1, b1, w2,
                      b2, rows, x16, gam_n, bet_n, h_n, stagger);
@@ -390,7 +386,7 @@ extern "C" int lmx_k_ln_mlp(float* x, int64_t ldx, const float* gamma, const flo
                             const float* gamma_next, const float* beta_next, void* h_next, lmx_stream_t stream) {
   LMX_REQUIRE(x && gamma && beta && w1 && b1 && w2 && b2 && workspace, "lmx_k_ln_mlp: null pointer");
   // (D = 448 is a development configuration: instantiated, measured slower than the unfused launches, reachable only with LMX_MLP448 set)
-  LMX_REQUIRE(D == 112 || D == 224 || (D == 448 && getenv("LMX_MLP448")), "lmx_k_ln_mlp: D=%d (built for the Hiera stage widths 112 and 224)", D);
+  LMX_REQUIRE(D == 112 || D == 224 || (D == 448 && lmx_env_set("LMX_MLP448")), "lmx_k_ln_mlp: D=%d (built for the Hiera stage widths 112 and 224)", D);
   LMX_REQUIRE(rows > 0 && rows < 0x7fffffffll && ldx >= D && ldx % 4 == 0, "lmx_k_ln_mlp: rows=%lld ldx=%lld", (long long)rows,
               (long long)ldx);
   LMX_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(w1) && aligned16(b1) && aligned16(w2) && aligned16(b2) &&
@@ -404,11 +400,8 @@ extern "C" int lmx_k_ln_mlp(float* x, int64_t ldx, const float* gamma, const flo
   LMX_REQUIRE(!h_next || (gamma_next && beta_next && aligned16(gamma_next) && aligned16(beta_next) && ((((uintptr_t)h_next) & 7) == 0)),
               "lmx_k_ln_mlp: h_next needs gamma_next / beta_next (16-byte aligned) and an 8-byte aligned output");
   LMX_REQUIRE(!x16 || ((((uintptr_t)x16) & 7) == 0), "lmx_k_ln_mlp: x16 must be 8-byte aligned");
-  static int one_per_cu = -1, split_ln = 0;  // LMX_MLP_ONE_PER_CU=1: the 8-wave, one-workgroup-per-CU configuration of the narrow width too
-  if (one_per_cu < 0) {
-    one_per_cu = getenv("LMX_MLP_ONE_PER_CU") ? 1 : 0;
-    split_ln = getenv("LMX_MLP_SPLIT_LN") ? 1 : 0;  // the round-1 form: a LayerNorm launch into the workspace, then the fused MLP on it
-  }
+  static const int one_per_cu = lmx_env_set("LMX_MLP_ONE_PER_CU");  // the 8-wave, one-workgroup-per-CU configuration of the narrow width too
+  static const int split_ln = lmx_env_set("LMX_MLP_SPLIT_LN");  // the round-1 form: a LayerNorm launch into the workspace, then the fused MLP on it
   // D = 112: 4 waves x 32 tokens, 48 KB ring, three workgroups per CU.  D = 224: 8 waves x 32 tokens, 128 KB ring, one per CU.
   // D = 448 (Hiera-B+ stage 3), round 3: two configurations, both correct, neither faster than the unfused launches at 122 880 tokens
   // (LayerNorm + fc1 + fc2 = 0.69 ms; profiles/r03_fused_mlp_d448.txt): LMX_MLP448=2: 4 waves x 32 tokens, one wave per SIMD (336
@@ -416,17 +409,14 @@ extern "C" int lmx_k_ln_mlp(float* x, int64_t ldx, const float* gamma, const flo
   // issue.  Every 128-token tile streams all 3.2 MB of weights through LDS with ONE 64 KB chunk in flight (the ring holds two), 56
   // chunks each behind a vmcnt(0) + barrier.  Not dispatched by lmx/sam.py.
   if (D == 448) {
-    static int v448 = -1;
-    if (v448 < 0) v448 = getenv("LMX_MLP448") ? atoi(getenv("LMX_MLP448")) : 1;
+    static const int v448 = lmx_env_int("LMX_MLP448", 1);
     if (v448 == 2) return launch<448, 2, 4, 2, 1, true>(x, ldx, nullptr, gamma, beta, eps, W1, b1, W2, b2, rows, X16, gamma_next, beta_next, HN, st);
     return launch<448, 1, 8, 2, 1, true>(x, ldx, nullptr, gamma, beta, eps, W1, b1, W2, b2, rows, X16, gamma_next, beta_next, HN, st);
   }
   // fragment reads through a register ring (RING): D = 224 0.72 -> 0.68 ms per 524 288 tokens, D = 112 0.88 -> 0.87 ms, identical bits
   // (tools/mlp_ab.sh); LMX_MLP_RING=0 is the plain form, 2 the ring with D = 112 at two workgroups per CU (no better)
-  static int ring = -1;
-  if (ring < 0) ring = getenv("LMX_MLP_RING") ? atoi(getenv("LMX_MLP_RING")) : 1;
-  static int cfg = -1;  // development: LMX_MLP_CFG selects experimental tilings (tools/mlp_ab.sh)
-  if (cfg < 0) cfg = getenv("LMX_MLP_CFG") ? atoi(getenv("LMX_MLP_CFG")) : 0;
+  static const int ring = lmx_env_int("LMX_MLP_RING", 1);
+  static const int cfg = lmx_env_int("LMX_MLP_CFG", 0);  // development: LMX_MLP_CFG selects experimental tilings (tools/mlp_ab.sh)
   if (cfg == 3 && D == 224) return launch<224, 1, 8, 2, 2, true, true>(x, ldx, nullptr, gamma, beta, eps, W1, b1, W2, b2, rows, X16, gamma_next, beta_next, HN, st);
   if (cfg == 3 && D == 112) return launch<112, 1, 4, 2, 4, true, true>(x, ldx, nullptr, gamma, beta, eps, W1, b1, W2, b2, rows, X16, gamma_next, beta_next, HN, st);
   if (cfg == 4 && D == 224) return launch<224, 1, 8, 3, 1, true, true>(x, ldx, nullptr, gamma, beta, eps, W1, b1, W2, b2, rows, X16, gamma_next, beta_next, HN, st);

@@ -333,12 +333,9 @@ extern "C" int lmx_k_nms(const float* pred, int n, int A, int nc, float conf, do
   int npow2 = 64;
   while (npow2 < A) npow2 <<= 1;
   const size_t smem = (size_t)npow2 * 9 + 64 * sizeof(Box);
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_greedy_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)MAX_A * 9 + 64 * sizeof(Box))));
-    attr_set = true;
-  }
+  int dev;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&nms_greedy_kernel), (int)((size_t)MAX_A * 9 + 64 * sizeof(Box)), dev));
   hipLaunchKernelGGL(nms_greedy_kernel, dim3(n), dim3(1024), smem, st, pred, A, nc, iou, max_det, max_wh, keys, cand_counts,
                      sbox, boxes, scores, cls, src, counts);
   return lmx_launch_check("nms_greedy_kernel");
@@ -352,13 +349,11 @@ extern "C" int lmx_k_nms_boxes(const float* boxes, int64_t ldb, const float* sco
   int npow2 = 64;
   while (npow2 < n) npow2 <<= 1;
   const size_t smem = (size_t)npow2 * 9 + 64 * sizeof(Box);
-  static bool attr_set = false;
-  if (!attr_set) {
-    LMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_boxes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((size_t)MAX_A * 9 + 64 * sizeof(Box))));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(nms_boxes_kernel, dim3(1), dim3(1024), smem, reinterpret_cast<hipStream_t>(stream), boxes, ldb, scores, valid, n,
-                     iou, reinterpret_cast<float*>(workspace), keep_out, count_out);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int dev;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&nms_boxes_kernel), (int)((size_t)MAX_A * 9 + 64 * sizeof(Box)), dev));
+  hipLaunchKernelGGL(nms_boxes_kernel, dim3(1), dim3(1024), smem, st, boxes, ldb, scores, valid, n, iou, reinterpret_cast<float*>(workspace),
+                     keep_out, count_out);
   return lmx_launch_check("nms_boxes_kernel");
 }

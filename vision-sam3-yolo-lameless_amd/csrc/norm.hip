@@ -311,8 +311,7 @@ extern "C" int lmx_k_layernorm(const void* x, int in_dtype, int64_t ldx, const f
   }
   dim3 grid((rows + 3) / 4), block(256);
   // many rows of a ViT width, f32 stream -> f16: the several-rows-per-wave form (LMX_LN_ONE_ROW=1: the one-row-per-wave kernel)
-  static int one_row = -1;
-  if (one_row < 0) one_row = getenv("LMX_LN_ONE_ROW") ? 1 : 0;
+  static const int one_row = lmx_env_set("LMX_LN_ONE_ROW");
   if (!one_row && rows >= 16384 && act == LMX_ACT_NONE && in_dtype == LMX_F32 && out_dtype == LMX_F16 && D <= 1024) {
     dim3 g2(256 * 8);  // eight workgroups of four waves per CU, each wave walking rows / 8192 rows
     if (D <= 512)

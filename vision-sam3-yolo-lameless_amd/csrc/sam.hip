@@ -438,7 +438,7 @@ extern "C" int lmx_k_mask_post(const float* logits, int n, int L, int T, int nh,
   const unsigned gmid = grid_for((int64_t)n * nh * nw);
   unsigned long long* su = reinterpret_cast<unsigned long long*>(stats);
 #ifdef LMX_DBG_VARIANTS  // development build only (make dbg -> liblmx_dbg.so): the probes of DESIGN.md section 6
-  static const int dbg = getenv("LMX_DBG_MASK") ? atoi(getenv("LMX_DBG_MASK")) : 0;
+  static const int dbg = lmx_env_int("LMX_DBG_MASK", 0);
 #define LMX_MASK_VARIANT(M, P)                                                                                         \
   {                                                                                                                    \
     hipLaunchKernelGGL(mask_mid_kernel<M>, dim3(gmid), dim3(256), 0, st, logits, workspace, n, L, T, nh, nw, su);      \
