@@ -249,6 +249,20 @@ int lmx_k_pil_resize_v(const uint8_t* src, uint8_t* dst, int n, int sh, int dh, 
 int lmx_k_patchify_norm(const uint8_t* img, void* out, int n, int ih, int iw, int top, int left, int gh, int gw,
                         int P, int64_t ldo, const float* lut, lmx_stream_t stream);
 
+/* DINOv3ViTImageProcessor (`AutoImageProcessor.from_pretrained` of a dinov3_vit directory, dinov3 main.py:34 / :107) in ONE
+ * pass: u8 -> float32, * rescale, antialiased float32 resize of the WHOLE frame to gh*P x gw*P (width, then height, f32
+ * intermediate: torch F.interpolate(antialias=True) on a CPU float tensor, which torchvision's resize calls), (x - mean) / std,
+ * rounded to f16 and written as the patch matrix in lmx_k_patchify_norm's layout (columns beyond P*P*3 are not written).
+ * src u8 [n][sh][sw][3]; swap_rb: src is BGR (cv2), the model's channel order and mean / std are RGB.
+ * Tables from the host (lmx/resample.py aa_tables, ATen's float32 arithmetic), on the DEVICE: bounds_*[2*out] = (first
+ * source index, taps), kk_*[out*ksize_*] f32 weights; bounds_h / kk_h have gw*P rows over sw, bounds_v / kk_v gh*P rows over
+ * sh.  A centre crop is a slice of the tables.  seg_cols: the most source columns any run of 256 consecutive output columns
+ * (starting at a multiple of 256) reads — the LDS segment, at most 5460.  mean_std: HOST float[6] = mean[3], std[3]. */
+int lmx_k_float_resize_patchify(const uint8_t* src, void* out, int n, int sh, int sw, int gh, int gw, int P, int64_t ldo,
+                                const int32_t* bounds_h, const float* kk_h, int ksize_h, const int32_t* bounds_v,
+                                const float* kk_v, int ksize_v, int seg_cols, float rescale, const float* mean_std,
+                                int swap_rb, lmx_stream_t stream);
+
 /* tokens: out[b][0..n_prefix) = prefix[t][:] (+pos), out[b][n_prefix + p] = patch[b*np + p][:] + pos[n_prefix+p]
  * (f32 residual stream; pos may be NULL — DINOv3 has no learned position table). */
 int lmx_k_assemble_tokens(const void* patch_f16, const float* prefix, const float* pos, float* out, int B, int np,

@@ -1,6 +1,7 @@
 // pre.hip — frame preprocessing (K9/K21): Pillow-exact separable u8 resampling and the crop/normalise/patchify
 // pass that writes the ViT patch matrix.  HBM-bound byte work: a 1080p BGR frame is 6.2 MB in, the outputs are
-// small, so the figure of merit is input bytes / time.
+// small, so the figure of merit is input bytes / time.  Plus the float path of DINOv3ViTImageProcessor
+// (rescale -> float32 antialiased resize -> normalize) as one kernel that writes the same patch matrix.
 //
 // Pillow reference (not in this tree; Pillow 10+ src/libImaging/Resample.c): ImagingResampleHorizontal_8bpc /
 // ImagingResampleVertical_8bpc with PRECISION_BITS = 22: acc starts at 1<<21, adds u8*coef (int32 wraps never
@@ -147,6 +148,138 @@ __global__ __launch_bounds__(256) void patchify_norm_kernel(const uint8_t* __res
   }
 }
 
+// ---- DINOv3ViTImageProcessor: rescale -> float32 antialiased resize -> normalize, written as the patch matrix ----------
+// torch reference (not in this tree; aten/src/ATen/native/cpu/UpSampleKernel.cpp, the separable antialias path): width is
+// resampled first, then height, the intermediate is f32, and each output is src[0]*w[0] followed by one fused multiply-add
+// per further tap, in tap order.  The weights come from the host (lmx/resample.py aa_tables, ATen's f32 arithmetic).
+//
+// workgroup = FR_ROWS output rows x FR_COLS output columns of one frame; thread = one output column.  The source rows the
+// band needs are walked ONCE, top to bottom: a row's segment is staged into LDS as f32 (u8 -> float, * rescale: done once
+// per source element, 16-byte coalesced loads), every thread resamples its column horizontally from LDS, and the value is
+// folded at once into the vertical accumulators of the output rows whose tap range holds this source row — rows arrive in
+// increasing order, so every output sees its taps in ATen's order.  No intermediate image exists, in HBM or in LDS; a
+// source row is re-read only by the neighbouring band (tap overlap: 2 x support rows per band, L2 hits mostly).
+constexpr int FR_ROWS = 8;
+constexpr int FR_COLS = 256;
+constexpr int FR_MAX_LDS = 65536;  // bytes: (seg_cols * 3 + 4) floats
+
+__global__ __launch_bounds__(FR_COLS) void float_resize_patchify_kernel(
+    const uint8_t* __restrict__ src, half_t* __restrict__ out, int sh, int sw, int gh, int gw, int P, int64_t ldo,
+    const int32_t* __restrict__ bh, const float* __restrict__ kh, int ksh, const int32_t* __restrict__ bv,
+    const float* __restrict__ kv, int ksv, int seg_cols, float rescale, float m0, float m1, float m2, float s0, float s1,
+    float s2, int swap_rb) {
+  extern __shared__ __attribute__((aligned(16))) float seg[];
+  const int tid = threadIdx.x;
+  const int dh = gh * P, dw = gw * P;
+  const int img = blockIdx.z;
+  const int x0 = blockIdx.x * FR_COLS, xo = x0 + tid;
+  const int y0 = blockIdx.y * FR_ROWS;
+  const bool live = xo < dw;
+  // source columns of this tile: bounds are monotone in the output index.  Everything read from the tables is clamped
+  // to the frame and to the LDS segment, so a malformed table gives wrong pixels, never an access outside either.
+  const int xl = (x0 + FR_COLS < dw ? x0 + FR_COLS : dw) - 1;
+  int c_lo = bh[2 * x0];
+  c_lo = c_lo < 0 ? 0 : (c_lo > sw ? sw : c_lo);
+  int c_hi = bh[2 * xl] + bh[2 * xl + 1];
+  c_hi = c_hi > sw ? sw : c_hi;
+  if (c_hi > c_lo + seg_cols) c_hi = c_lo + seg_cols;
+  if (c_hi < c_lo) c_hi = c_lo;
+  int xmin = 0, xcnt = 0;
+  if (live) {
+    xmin = bh[2 * xo];
+    xcnt = bh[2 * xo + 1];
+    if (xmin < c_lo) xmin = c_lo;
+    if (xcnt > ksh) xcnt = ksh;
+    if (xcnt > c_hi - xmin) xcnt = c_hi - xmin;
+    if (xcnt < 0) xcnt = 0;
+  }
+  const float* kx = kh + (int64_t)(live ? xo : 0) * ksh;
+  // tap ranges of the band's output rows (uniform over the workgroup)
+  int ymin[FR_ROWS], ycnt[FR_ROWS];
+  int r_lo = sh, r_hi = 0;
+#pragma unroll
+  for (int r = 0; r < FR_ROWS; ++r) {
+    ymin[r] = 0;
+    ycnt[r] = 0;
+    if (y0 + r < dh) {
+      int a = bv[2 * (y0 + r)], c = bv[2 * (y0 + r) + 1];
+      a = a < 0 ? 0 : a;
+      c = c > ksv ? ksv : c;
+      c = c > sh - a ? sh - a : c;
+      c = c < 0 ? 0 : c;
+      ymin[r] = a;
+      ycnt[r] = c;
+      if (c > 0) {
+        r_lo = a < r_lo ? a : r_lo;
+        r_hi = a + c > r_hi ? a + c : r_hi;
+      }
+    }
+  }
+  float acc[FR_ROWS][3];
+#pragma unroll
+  for (int r = 0; r < FR_ROWS; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 0.f;
+
+  const int nbytes = (c_hi - c_lo) * 3;
+  for (int y = r_lo; y < r_hi; ++y) {
+    const uint8_t* srow = src + (((int64_t)img * sh + y) * sw + c_lo) * 3;
+    // 16-byte loads aligned on the global address; the LDS index is shifted by `pad` so that the vector part of the
+    // segment starts on a 16-byte LDS boundary too
+    const int mis = (int)(reinterpret_cast<uintptr_t>(srow) & 15);
+    int head = mis ? 16 - mis : 0;
+    head = head > nbytes ? nbytes : head;
+    const int pad = (4 - (head & 3)) & 3;
+    float* s = seg + pad;
+    if (tid < head) s[tid] = (float)srow[tid] * rescale;
+    const int nvec = (nbytes - head) / 16;
+    for (int v = tid; v < nvec; v += FR_COLS) {
+      const u32x4 x = *reinterpret_cast<const u32x4*>(srow + head + v * 16);
+      f32x4* d = reinterpret_cast<f32x4*>(s + head + v * 16);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x4 f;
+        f[0] = (float)(x[q] & 255u) * rescale;
+        f[1] = (float)((x[q] >> 8) & 255u) * rescale;
+        f[2] = (float)((x[q] >> 16) & 255u) * rescale;
+        f[3] = (float)(x[q] >> 24) * rescale;
+        d[q] = f;
+      }
+    }
+    for (int i = head + nvec * 16 + tid; i < nbytes; i += FR_COLS) s[i] = (float)srow[i] * rescale;
+    __syncthreads();
+    float h0 = 0.f, h1 = 0.f, h2 = 0.f;
+    const float* p = s + (xmin - c_lo) * 3;
+    for (int j = 0; j < xcnt; ++j) {
+      const float w = kx[j];
+      h0 = __builtin_fmaf(p[3 * j + 0], w, h0);
+      h1 = __builtin_fmaf(p[3 * j + 1], w, h1);
+      h2 = __builtin_fmaf(p[3 * j + 2], w, h2);
+    }
+#pragma unroll
+    for (int r = 0; r < FR_ROWS; ++r) {
+      if (y >= ymin[r] && y < ymin[r] + ycnt[r]) {
+        const float w = kv[(int64_t)(y0 + r) * ksv + (y - ymin[r])];
+        acc[r][0] = __builtin_fmaf(h0, w, acc[r][0]);
+        acc[r][1] = __builtin_fmaf(h1, w, acc[r][1]);
+        acc[r][2] = __builtin_fmaf(h2, w, acc[r][2]);
+      }
+    }
+    __syncthreads();  // the next row overwrites the segment
+  }
+  if (!live) return;
+  const int px = xo / P, kxp = xo - px * P;
+#pragma unroll
+  for (int r = 0; r < FR_ROWS; ++r) {
+    const int yo = y0 + r;
+    if (yo >= dh) break;
+    const int py = yo / P, ky = yo - py * P;
+    half_t* d = out + (((int64_t)img * gh + py) * gw + px) * ldo + (ky * P + kxp) * 3;
+    // torchvision normalize: (x - mean) / std, a true f32 division
+    d[0] = (half_t)(((swap_rb ? acc[r][2] : acc[r][0]) - m0) / s0);
+    d[1] = (half_t)((acc[r][1] - m1) / s1);
+    d[2] = (half_t)(((swap_rb ? acc[r][0] : acc[r][2]) - m2) / s2);
+  }
+}
+
 inline int grid_for(int64_t total) {
   int64_t g = (total + 255) / 256;
   if (g > 256 * 8) g = 256 * 8;
@@ -179,6 +312,27 @@ extern "C" int lmx_k_pil_resize_v(const uint8_t* src, uint8_t* dst, int n, int s
   hipLaunchKernelGGL(pil_resize_v_kernel, dim3(grid_for((int64_t)n * dh * w * 3)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), src, dst, n, sh, dh, w, bounds, kk, ksize);
   return lmx_launch_check("pil_resize_v_kernel");
+}
+
+extern "C" int lmx_k_float_resize_patchify(const uint8_t* src, void* out, int n, int sh, int sw, int gh, int gw, int P,
+                                           int64_t ldo, const int32_t* bounds_h, const float* kk_h, int ksize_h,
+                                           const int32_t* bounds_v, const float* kk_v, int ksize_v, int seg_cols,
+                                           float rescale, const float* mean_std, int swap_rb, lmx_stream_t stream) {
+  LMX_REQUIRE(src && out && bounds_h && kk_h && bounds_v && kk_v && mean_std, "lmx_k_float_resize_patchify: null pointer");
+  LMX_REQUIRE(n > 0 && n <= 65535 && sh > 0 && sw > 0 && gh > 0 && gw > 0 && P > 0 && ksize_h > 0 && ksize_v > 0,
+              "lmx_k_float_resize_patchify: shape");
+  LMX_REQUIRE(ldo >= (int64_t)P * P * 3, "lmx_k_float_resize_patchify: ldo %lld < P*P*3", (long long)ldo);
+  LMX_REQUIRE((int64_t)gh * P <= 65535 * (int64_t)FR_ROWS && (int64_t)gw * P <= (1 << 20), "lmx_k_float_resize_patchify: output size");
+  LMX_REQUIRE(seg_cols > 0 && seg_cols <= sw, "lmx_k_float_resize_patchify: seg_cols %d outside 1..%d", seg_cols, sw);
+  const int64_t lds = ((int64_t)seg_cols * 3 + 4) * (int64_t)sizeof(float);
+  LMX_REQUIRE(lds <= FR_MAX_LDS, "lmx_k_float_resize_patchify: a tile of %d output columns reads %d source columns; more than %d are not staged",
+              FR_COLS, seg_cols, (FR_MAX_LDS / 4 - 4) / 3);
+  LMX_REQUIRE(mean_std[3] != 0.f && mean_std[4] != 0.f && mean_std[5] != 0.f, "lmx_k_float_resize_patchify: zero std");
+  const dim3 grid((unsigned)((gw * P + FR_COLS - 1) / FR_COLS), (unsigned)((gh * P + FR_ROWS - 1) / FR_ROWS), (unsigned)n);
+  hipLaunchKernelGGL(float_resize_patchify_kernel, grid, dim3(FR_COLS), (size_t)lds, reinterpret_cast<hipStream_t>(stream), src,
+                     reinterpret_cast<half_t*>(out), sh, sw, gh, gw, P, ldo, bounds_h, kk_h, ksize_h, bounds_v, kk_v, ksize_v,
+                     seg_cols, rescale, mean_std[0], mean_std[1], mean_std[2], mean_std[3], mean_std[4], mean_std[5], swap_rb);
+  return lmx_launch_check("float_resize_patchify_kernel");
 }
 
 extern "C" int lmx_k_patchify_norm(const uint8_t* img, void* out, int n, int ih, int iw, int top, int left, int gh,

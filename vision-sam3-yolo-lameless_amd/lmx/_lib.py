@@ -60,6 +60,7 @@ SIGNATURES = {
     "lmx_k_pil_resize_h": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP]),
     "lmx_k_pil_resize_v": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _I, _VP]),
     "lmx_k_patchify_norm": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I64, _VP, _VP]),
+    "lmx_k_float_resize_patchify": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I64, _VP, _VP, _I, _VP, _VP, _I, _I, _F, _VP, _I, _VP]),
     "lmx_k_assemble_tokens": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "lmx_k_token_mean": (_I, [_VP, _I, _VP, _I, _I, _I, _VP]),
     "lmx_k_swiglu": (_I, [_VP, _I64, _VP, _I64, _I, _I, _VP]),

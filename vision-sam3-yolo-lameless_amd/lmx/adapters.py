@@ -423,8 +423,11 @@ class LmxDinoModel:
 
 
 class LmxImageProcessor:
-    """`AutoImageProcessor.from_pretrained(dir)` replacement (dinov2-base preprocessing: bicubic shortest-edge 256, centre
-    crop 224, /255, ImageNet mean/std — bit-exact against Pillow + BitImageProcessorPil, tests/test_oracle_preprocess.py).
+    """`AutoImageProcessor.from_pretrained(dir)` replacement: applies the recipe of the model's directory
+    (preprocessor_config.json, lmx.checkpoints.read_dino_preprocess) — BitImageProcessor's PIL u8 path (bit-exact against Pillow +
+    BitImageProcessorPil, tests/test_oracle_preprocess.py) or DINOv3ViTImageProcessor's float antialiased resize; a directory
+    without that file gets dinov2-base's (bicubic shortest-edge 256, centre crop 224, /255, ImageNet mean/std).  Either way the
+    single-frame call goes through the same `GraphedFn` (`_g_pre`; replay only with LMX_GRAPHS=1).
     images: a PIL image or an HWC RGB uint8 array (or a list of them, equal sizes)."""
 
     def __init__(self, model):

@@ -12,6 +12,7 @@ parameter names (image_encoder.* / prompt_encoder.* / mask_decoder.*) are mapped
 SamModel names, which is what the oracle is pinned to).  An Ultralytics `.pt` pickles the model OBJECT: it cannot be read
 without the ultralytics package, so the detector takes a state dict exported from it (`model.N.*` names, as
 `YOLO(p).model.state_dict()` gives) — see INTEGRATION.md."""
+import dataclasses
 import json
 import re
 from pathlib import Path
@@ -218,9 +219,104 @@ def load_yolo_weights(path):
 
 
 # ---- DINOv2 / DINOv3 ---------------------------------------------------------------------------------------------------------
+PREPROCESSOR_FILE = "preprocessor_config.json"
+_PROCESSOR_KINDS = {"BitImageProcessor": "pil", "BitImageProcessorFast": "pil",
+                    "DINOv3ViTImageProcessor": "float", "DINOv3ViTImageProcessorFast": "float"}
+# class defaults of the two processors for the keys a file leaves out (transformers BitImageProcessor / DINOv3ViTImageProcessor)
+_PROCESSOR_DEFAULTS = {
+    "pil": dict(do_resize=True, size={"shortest_edge": 224}, resample=3, do_center_crop=True, crop_size={"height": 224, "width": 224},
+                do_rescale=True, rescale_factor=1 / 255, do_normalize=True, image_mean=[0.48145466, 0.4578275, 0.40821073],
+                image_std=[0.26862954, 0.26130258, 0.27577711]),
+    "float": dict(do_resize=True, size={"height": 224, "width": 224}, resample=2, do_center_crop=False, crop_size=None,
+                  do_rescale=True, rescale_factor=1 / 255, do_normalize=True, image_mean=[0.485, 0.456, 0.406],
+                  image_std=[0.229, 0.224, 0.225]),
+}
+
+
+def read_dino_preprocess(model_dir, patch):
+    """`<dir>/preprocessor_config.json` -> lmx.dino.DinoPreprocess, or None when the directory has no such file (the embedder
+    then runs the dinov2-base recipe).  `AutoImageProcessor.from_pretrained(model_name)` (dinov3 main.py:34) builds the
+    processor that file names; here its computation is reproduced exactly or the load is refused, naming the file and the
+    field — a recipe silently approximated would feed the model other pixels than the reference's service does.
+
+    image_processor_type BitImageProcessor[Fast]: the PIL u8 path (the project stays pinned to the PIL backend for this
+    family).  DINOv3ViTImageProcessor[Fast]: the float path.  Refused: another processor; `resample` other than 2 (bilinear) / 3
+    (bicubic); do_resize / do_rescale / do_normalize false; a network input (crop_size, or size without a crop) that is not a
+    square multiple of the patch size; a crop larger than the resized image where the file alone decides that."""
+    from . import dino, resample
+
+    path = Path(model_dir) / PREPROCESSOR_FILE
+    if not path.exists():
+        return None
+    with open(path) as f:
+        p = json.load(f)
+
+    def refuse(field, why):
+        raise RuntimeError(f"{path}: {field} {why}")
+
+    kind = _PROCESSOR_KINDS.get(p.get("image_processor_type"))
+    if kind is None:
+        refuse("image_processor_type", f"{p.get('image_processor_type')!r} is not one of {', '.join(_PROCESSOR_KINDS)}")
+    get = {**_PROCESSOR_DEFAULTS[kind], **{k: v for k, v in p.items() if v is not None}}.get
+    for flag in ("do_resize", "do_rescale", "do_normalize"):
+        if not get(flag):
+            refuse(flag, "false is not supported (resize, rescale and normalize always run)")
+    filt = {2: resample.BILINEAR, 3: resample.BICUBIC}.get(get("resample"))
+    if filt is None:
+        refuse("resample", f"{get('resample')!r} is not supported (2 bilinear, 3 bicubic)")
+
+    def square(field, v):
+        """transformers' get_size_dict: an int is a square, a dict has height and width."""
+        if isinstance(v, int) and not isinstance(v, bool):
+            v = {"height": v, "width": v}
+        if not isinstance(v, dict) or not all(isinstance(v.get(k), int) and v[k] > 0 for k in ("height", "width")):
+            refuse(field, f"{v!r} must give a positive height and width")
+        if v["height"] != v["width"]:
+            refuse(field, f"{v['height']} x {v['width']} is not square (the network input is a square grid of patches)")
+        if v["height"] % patch:
+            refuse(field, f"{v['height']} is not a multiple of the patch size {patch}")
+        return v["height"]
+
+    size = get("size")
+    if isinstance(size, int) and not isinstance(size, bool):  # get_size_dict(default_to_square=False) for Bit, square for DINOv3
+        size = {"shortest_edge": size} if kind == "pil" else {"height": size, "width": size}
+    if not isinstance(size, dict):
+        refuse("size", f"{size!r} must be a dictionary")
+    crop = square("crop_size", get("crop_size")) if get("do_center_crop") else None
+    edge = hw = None
+    if set(size) == {"shortest_edge"} and isinstance(size["shortest_edge"], int) and size["shortest_edge"] > 0:
+        edge = size["shortest_edge"]
+        if crop is None:
+            refuse("size", "with shortest_edge only and do_center_crop false gives no square network input")
+        if crop > edge:
+            refuse("crop_size", f"{crop} is larger than the resized image's shortest edge {edge} (the processor would pad with zeros)")
+    elif set(size) == {"height", "width"}:
+        if crop is None:
+            square("size", size)
+        elif not all(isinstance(size[k], int) and size[k] >= crop for k in ("height", "width")):
+            refuse("crop_size", f"{crop} is larger than the resized image {size['height']} x {size['width']} (the processor would "
+                                "pad with zeros)")
+        hw = (size["height"], size["width"])
+    else:
+        refuse("size", f"{size!r} must hold shortest_edge, or height and width")
+    mean, std = get("image_mean"), get("image_std")
+    for field, v in (("image_mean", mean), ("image_std", std)):
+        if not isinstance(v, (list, tuple)) or len(v) != 3 or not all(isinstance(x, (int, float)) for x in v):
+            refuse(field, f"{v!r} must list three numbers")
+    if any(x == 0 for x in std):
+        refuse("image_std", "holds a zero")
+    scale = get("rescale_factor")
+    if not isinstance(scale, (int, float)) or isinstance(scale, bool) or not scale > 0:
+        refuse("rescale_factor", f"{scale!r} must be a positive number")
+    return dino.DinoPreprocess(kind=kind, filt=filt, shortest_edge=edge, size_hw=hw, crop=crop, rescale=float(scale),
+                               mean=tuple(float(x) for x in mean), std=tuple(float(x) for x in std))
+
+
 def load_dino_dir(model_dir):
-    """A local Hugging Face model directory (config.json + model.safetensors) -> (DinoConfig, state dict).  The service asks
-    the hub by name (dinov3 main.py:34-35); offline deployments point models.dinov3.model_name at such a directory.
+    """A local Hugging Face model directory (config.json + model.safetensors, optionally preprocessor_config.json) ->
+    (DinoConfig, state dict).  The service asks the hub by name (dinov3 main.py:34-35); offline deployments point
+    models.dinov3.model_name at such a directory.  With a preprocessor_config.json the configuration carries its recipe
+    (`preproc`, read_dino_preprocess) and `image` is the network input that file sets; without one it is the dinov2-base recipe.
 
     Loads: dinov2 (plain MLP, or `use_swiglu_ffn` as in giant), dinov2_with_registers, dinov3_vit (plain or `use_gated_mlp`, any
     of query / key / value / proj / mlp bias switched off).  Refuses, naming the config field: a head dim the attention kernels do
@@ -262,6 +358,11 @@ def load_dino_dir(model_dir):
         dino.check_head_dim(cfg)
     except RuntimeError as e:
         raise RuntimeError(f"{d}: {e}") from None
+    # the network input follows the file: a dinov2 position table is interpolated to the new grid by DinoEmbedder, RoPE is
+    # built for it, and no kernel of the layer sequence bounds the token count, so any multiple of the patch size is served
+    pre = read_dino_preprocess(d, cfg.patch)
+    if pre is not None:
+        cfg = dataclasses.replace(cfg, preproc=pre, image=pre.input_size, resize_edge=pre.shortest_edge or cfg.resize_edge)
     sd = weights.load_state_dict_file(str(d / "model.safetensors"))
     if gated and gate_key not in sd:
         raise RuntimeError(f"{d}: config says {form}=true but the checkpoint has no gate tensor ({gate_key})")

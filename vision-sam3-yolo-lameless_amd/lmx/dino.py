@@ -14,15 +14,47 @@ HBM; every GEMM/attention operand is f16 with f32 accumulation.
 ``gated`` MLPs (DINOv3 ViT-S+/H+ ``down(silu(gate(x)) * up(x))``, DINOv2 giant's SwiGLU FFN): fc1 is ONE GEMM over the
 gate and up rows interleaved by 16 (``pack_gated``) whose epilogue is the gate (lmx_k_gemm LMX_ACT_SWIGLU): the
 2 x mlp wide intermediate is never written.  Head dims up to 96 (every ViT up to H+ / giant has 64); DINOv3-7B's 128 is refused at load.
+Preprocessing is the recipe of the model directory's preprocessor_config.json (``DinoPreprocess``): BitImageProcessor's PIL
+u8 path or DINOv3ViTImageProcessor's float antialiased resize; a configuration without one runs dinov2-base's.
 """
 import math
 from dataclasses import dataclass
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import kernels as K
 from . import resample
+
+
+@dataclass(frozen=True)
+class DinoPreprocess:
+    """The computation of the image processor a model directory names (lmx.checkpoints.read_dino_preprocess turns
+    ``preprocessor_config.json`` into one).  Two families, two different computations:
+      * ``pil``   — BitImageProcessor (dinov2, dinov2_with_registers): Pillow resize on u8 -> centre crop -> rescale -> normalize,
+                     bit-exact (lmx_k_pil_resize_* + lmx_k_patchify_norm).
+      * ``float`` — DINOv3ViTImageProcessor: rescale -> float32 antialiased resize -> (centre crop) -> normalize
+                     (lmx_k_float_resize_patchify).
+    The resize target is ``shortest_edge`` (aspect kept, the other side truncated) or ``size_hw`` (the whole frame squashed).
+    The defaults are the dinov2-base recipe, the one a DinoConfig without ``preproc`` gets."""
+    kind: str = "pil"
+    filt: str = resample.BICUBIC  # lmx.resample.BILINEAR | BICUBIC (`resample` 2 | 3)
+    shortest_edge: Optional[int] = 256
+    size_hw: Optional[Tuple[int, int]] = None
+    crop: Optional[int] = 224
+    rescale: float = 1.0 / 255.0
+    mean: Tuple[float, float, float] = resample.IMAGENET_MEAN
+    std: Tuple[float, float, float] = resample.IMAGENET_STD
+
+    @property
+    def input_size(self):
+        """Side of the square the network is fed: the crop, or the resize target when nothing is cropped."""
+        return self.crop if self.crop is not None else self.size_hw[0]
+
+    def resized(self, h, w):
+        """(height, width) a frame of h x w is resized to."""
+        return tuple(self.size_hw) if self.size_hw is not None else resample.shortest_edge_size(h, w, self.shortest_edge)
 
 
 @dataclass
@@ -46,6 +78,9 @@ class DinoConfig:
     v_bias: bool = True
     proj_bias: bool = True
     mlp_bias: bool = True
+    # the model directory's preprocessing recipe; None: the dinov2-base recipe with `resize_edge` and `image` (what a config
+    # built by hand gets).  When set, `image` is the recipe's input_size
+    preproc: Optional[DinoPreprocess] = None
 
     @property
     def head_dim(self):
@@ -307,7 +342,11 @@ class DinoEmbedder:
                 w1=t16(w1), bb1=t32(b1), w2=t16(w2), bb2=t32(b2), ls2=t32(sd[p + "layer_scale2.lambda1"])))
         self.gf = t32(sd["norm.weight" if v3 else "layernorm.weight"])
         self.bf = t32(sd["norm.bias" if v3 else "layernorm.bias"])
-        self.lut = t32(resample.norm_lut(resample.IMAGENET_MEAN, resample.IMAGENET_STD))
+        self.recipe = cfg.preproc if cfg.preproc is not None else DinoPreprocess(shortest_edge=cfg.resize_edge, crop=cfg.image)
+        if self.recipe.kind not in ("pil", "float") or self.recipe.input_size != cfg.image:
+            raise K.LmxError(f"DinoEmbedder: the preprocessing recipe ({self.recipe.kind}) feeds {self.recipe.input_size} x "
+                             f"{self.recipe.input_size}, the configuration's image is {cfg.image}")
+        self.lut = t32(resample.norm_lut(self.recipe.mean, self.recipe.std, self.recipe.rescale))
         self._tabs = {}
 
     # ---- the network --------------------------------------------------------------------------------------
@@ -344,28 +383,47 @@ class DinoEmbedder:
     def _tables(self, h, w):
         key = (h, w)
         if key not in self._tabs:
-            nh, nw = resample.shortest_edge_size(h, w, self.cfg.resize_edge)
+            rc = self.recipe
+            nh, nw = rc.resized(h, w)
+            if nh < self.cfg.image or nw < self.cfg.image:
+                raise K.LmxError(f"frame {h}x{w} resizes to {nh}x{nw}, smaller than the {self.cfg.image} crop")
             dev = self.device
 
             def up(tab):
                 b, k, ks = tab
                 return (torch.from_numpy(b).to(dev), torch.from_numpy(k).to(dev), ks)
 
-            # the horizontal pass always runs: it also does the BGR->RGB swap (identity table if the width is kept)
-            th = up(resample.coeff_tables(w, nw, resample.BICUBIC)) if nw != w else up(_identity_table(w))
-            tv = up(resample.coeff_tables(h, nh, resample.BICUBIC)) if nh != h else None
-            self._tabs[key] = (nh, nw, th, tv)
+            if rc.kind == "pil":
+                # the horizontal pass always runs: it also does the BGR->RGB swap (identity table if the width is kept)
+                th = up(resample.coeff_tables(w, nw, rc.filt)) if nw != w else up(_identity_table(w))
+                tv = up(resample.coeff_tables(h, nh, rc.filt)) if nh != h else None
+                self._tabs[key] = (nh, nw, th, tv)
+            else:
+                # the centre crop of the resized image (TorchvisionBackend.center_crop: int((size - crop) / 2)) is a slice of
+                # the tables: only the rows and columns that survive it are ever computed
+                S = self.cfg.image
+
+                def cut(tab, n_out):
+                    b, k, ks = tab
+                    o = int((n_out - S) / 2.0)
+                    return np.ascontiguousarray(b.reshape(-1, 2)[o:o + S]).reshape(-1), np.ascontiguousarray(k.reshape(-1, ks)[o:o + S]).reshape(-1), ks
+
+                th, tv = cut(resample.aa_tables(w, nw, rc.filt), nw), cut(resample.aa_tables(h, nh, rc.filt), nh)
+                self._tabs[key] = (up(th), up(tv), resample.segment_cols(th[0]))
         return self._tabs[key]
 
     def preprocess(self, frames_bgr, rgb=False):
         """u8 [B,H,W,3] BGR (cv2 order; `rgb=True`: already RGB, as the PIL image the glue hands the processor) on device
-        -> f16 patch matrix [B*np, k_pad]:
-        cvtColor(BGR2RGB) -> PIL bicubic shortest-edge resize -> center crop -> /255 -> ImageNet normalise."""
-        cfg = self.cfg
+        -> f16 patch matrix [B*np, k_pad], by the recipe of the model directory (`cfg.preproc`; none: dinov2-base's):
+          pil   : cvtColor(BGR2RGB) -> PIL resize on u8 -> center crop -> rescale -> normalise
+          float : cvtColor(BGR2RGB) -> rescale -> float32 antialiased resize -> (center crop) -> normalise, one kernel."""
+        cfg, rc = self.cfg, self.recipe
         B, h, w, _ = frames_bgr.shape
+        if rc.kind == "float":
+            th, tv, seg = self._tables(h, w)
+            return K.float_resize_patchify(frames_bgr, cfg.grid, cfg.grid, cfg.patch, th, tv, seg, rc.rescale, rc.mean, rc.std,
+                                           swap_rb=not rgb, k_pad=self.k_pad)
         nh, nw, th, tv = self._tables(h, w)
-        if nh < cfg.image or nw < cfg.image:
-            raise K.LmxError(f"frame {h}x{w} resizes to {nh}x{nw}, smaller than the {cfg.image} crop")
         img = K.pil_resize(frames_bgr, nw, nh, th, tv, swap_rb=not rgb)
         top, left = (nh - cfg.image) // 2, (nw - cfg.image) // 2
         return K.patchify_norm(img, top, left, cfg.grid, cfg.grid, cfg.patch, self.lut, k_pad=self.k_pad)

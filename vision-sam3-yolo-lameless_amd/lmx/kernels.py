@@ -471,6 +471,33 @@ def patchify_norm(img, top, left, gh, gw, P, lut, k_pad=None):
     return out
 
 
+def float_resize_patchify(src, gh, gw, P, tab_h, tab_v, seg_cols, rescale, mean, std, swap_rb=False, k_pad=None):
+    """u8 [n,sh,sw,3] -> f16 [n*gh*gw, k_pad or P*P*3] patch matrix (columns beyond P*P*3 zero) of the float antialiased
+    resize to gh*P x gw*P: DINOv3ViTImageProcessor's rescale -> resize -> normalize in one kernel.  tab_* = (bounds i32
+    [2*out], kk f32 [out*ksize], ksize) device tensors from lmx.resample.aa_tables, seg_cols from lmx.resample.segment_cols."""
+    bh, kh, ksh = tab_h
+    bv, kv, ksv = tab_v
+    dev = _dev(src, bh, kh, bv, kv)
+    n, sh, sw, c = src.shape
+    if c != 3 or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise LmxError("float_resize_patchify: src must be contiguous uint8 [n,h,w,3]")
+    if (bh.dtype, bv.dtype, kh.dtype, kv.dtype) != (torch.int32, torch.int32, torch.float32, torch.float32):
+        raise LmxError("float_resize_patchify: bounds must be int32 and weights float32")
+    if (bh.numel(), kh.numel(), bv.numel(), kv.numel()) != (2 * gw * P, gw * P * ksh, 2 * gh * P, gh * P * ksv):
+        raise LmxError(f"float_resize_patchify: tables do not describe a {gh * P} x {gw * P} output")
+    if len(mean) != 3 or len(std) != 3:
+        raise LmxError("float_resize_patchify: mean and std must have 3 entries")
+    K = P * P * 3
+    ldo = k_pad or K
+    alloc = torch.zeros if ldo != K else torch.empty
+    out = alloc((n * gh * gw, ldo), dtype=torch.float16, device=src.device)
+    ms = (C.c_float * 6)(*mean, *std)
+    check(_lib.load().lmx_k_float_resize_patchify(_ptr(src), _ptr(out), n, sh, sw, gh, gw, P, ldo, _ptr(bh), _ptr(kh), ksh,
+                                                  _ptr(bv), _ptr(kv), ksv, seg_cols, rescale, ms, 1 if swap_rb else 0,
+                                                  _stream(dev)), "lmx_k_float_resize_patchify")
+    return out
+
+
 def assemble_tokens(patch, prefix, pos, B, np_, n_prefix, D):
     dev = _dev(patch, prefix, pos)
     out = torch.empty((B * (np_ + n_prefix), D), dtype=torch.float32, device=patch.device)
