@@ -7,7 +7,10 @@ and one rounding sequence in every epilogue.
 GEMM level: one problem computed whole, then again in row chunks whose sizes land in the OTHER branches (the branch of each is
 in the comments, derived from the rules above and confirmed under a kernel trace); the concatenation must be torch.equal to the
 whole.  Model level: a frame / prompt alone against the same frame / prompt inside a batch that crosses the thresholds.
-Branches are reached by shape only (the LMX_GEMM_* development switches are process-wide and would leak into later tests)."""
+Branches are reached by shape only (the LMX_GEMM_* development switches are process-wide and would leak into later tests).
+
+lmx_k_layernorm switches on rows = frames x tokens too (layernorm_rows_kernel from 16384 rows): that threshold is crossed by
+tests/test_gpu_rowwise.py::test_layernorm_bits_do_not_depend_on_the_row_count, beside the float64 comparison of both kernels."""
 import numpy as np
 import pytest
 import torch
