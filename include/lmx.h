@@ -102,6 +102,20 @@ int lmx_k_gemm(const lmx_gemm_desc* d, lmx_stream_t stream);
 /* development hook (tools/gemm_sweep.py): force one tiling of the LDS-DMA GEMM for every following launch; v = 0 restores
  * the launcher's per-shape choice, otherwise one of the letters documented at lmx_gemm2_launch (csrc/gemm2.hip) */
 void lmx_dbg_set_gemm2_variant(int v);
+/* ---- which kernel would run: lmx_h_gemm_route, lmx_h_attn_route (below, at lmx_k_attention) and lmx_h_layernorm_route.
+ * lmx_k_gemm, lmx_k_attention and lmx_k_layernorm validate and choose their kernel in one pure host function each and launch in
+ * another; these three entry points run the first half alone.  They NEVER touch the GPU and NEVER dereference the operand pointers
+ * (null and alignment checks only: any non-null, suitably aligned address will do), so they work on a host without a device.
+ * An invalid descriptor returns what the launcher returns for it, with the same lmx_last_error text; otherwise LMX_OK and, in
+ * name[cap], the route: the kernel and the template arguments of the instantiation, e.g.
+ *   GEMM        v1_128x64 (register-staged, BM x BN) | dma_256x256x64_s2, dma_256x128x64_s3_stag (LDS-DMA: BM x BN x BK, ring slots,
+ *               staggered wave groups)
+ *   attention   small | sp_qb2_ones | spp_dot2 | gp4_ones | tiled_q2_dot2_rel_hd64, tiled_q2_ones_dma_hd64 (ones / dot2: how the
+ *               row sums are taken; q: 16-query blocks per wave; hd: the LDS row class)
+ *   LayerNorm   narrow | rows_it2 | row_it16 (it: float4 per lane)
+ * The development switches (LMX_GEMM_*, LMX_GEMM2_*, LMX_ATTN_*, LMX_LN_ONE_ROW, lmx_dbg_set_gemm2_variant) steer the answer as
+ * they steer the launch.  LMX_EINVAL too if the name does not fit cap bytes. */
+int lmx_h_gemm_route(const lmx_gemm_desc* d, char* name, int cap);
 
 /* ---- K11: LayerNorm over the last dim, f32 or f16 in -> f16 or f32 out ------------------------------
  * Replaces torch.nn.LayerNorm inside the ViT blocks (TF:models/dinov3_vit/modeling_dinov3_vit.py:400-445,
@@ -111,6 +125,7 @@ void lmx_dbg_set_gemm2_variant(int v);
 int lmx_k_layernorm(const void* x, int in_dtype, int64_t ldx, const float* gamma, const float* beta,
                     void* y, int out_dtype, int64_t ldy, int rows, int D, float eps, int act, lmx_stream_t stream);
 /* (act = LMX_ACT_NONE or LMX_ACT_GELU applied after the affine: the SAM decoder's LayerNorm2d -> GELU, TF sam :523) */
+int lmx_h_layernorm_route(int in_dtype, int out_dtype, int rows, int D, int act, char* name, int cap); /* see lmx_h_gemm_route */
 
 /* ---- the gate of a gated MLP as its own pass: out[r][j] = f16( silu(gu[r][j]) * gu[r][I + j] ), gu f16 [rows][2 I] (gate columns
  * first, row stride ldg), out f16 [rows][I] (row stride ldo); I%8==0.  The unfused form of LMX_ACT_SWIGLU — plain GEMM to a 2 I-wide f16
@@ -214,6 +229,7 @@ typedef struct {
   const void* rel; int32_t rel_S;
 } lmx_attn_desc;
 int lmx_k_attention(const lmx_attn_desc* d, lmx_stream_t stream);
+int lmx_h_attn_route(const lmx_attn_desc* d, char* name, int cap); /* see lmx_h_gemm_route */
 /* rel[(b*H+h)*T + t][j]      = sum_c q[b,t,h,c] * rel_pos_h[ty - j + S-1][c]        (j < S)
  * rel[(b*H+h)*T + t][S + j]  = sum_c q[b,t,h,c] * rel_pos_w[tx - j + S-1][c]        (t = ty*S + tx, T = S*S)
  * q addressed with the attention geometry of `d` (mode 0 or window mode; d->Q, ldq, B, H, Tq, hd, mode, Gh, Gw, ws used),

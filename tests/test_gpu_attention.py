@@ -4,7 +4,9 @@
 
 on the stress inputs of attnref.make_inputs (benign, large logits, a late maximum, f16-subnormal probability mass, dominant
 padded keys).  Branches are reached by shape only (the LMX_ATTN_* switches are process-wide statics); each case id names the
-kernel the dispatch picks for it.  q / k / v are views with ld > H * hd inside NaN-filled buffers (gap columns and the rows after
+kernel the dispatch picks for it and each row of SHAPES ends with that kernel's route name (lmx_h_attn_route, include/lmx.h), which
+the test asserts of the library's own selection before it launches (tests/test_dispatch_routes_host.py does so without a GPU).
+q / k / v are views with ld > H * hd inside NaN-filled buffers (gap columns and the rows after
 the last described row), `out` a strided view of a sentinel-filled buffer: every result must be finite and every cell outside
 the described output must keep the sentinel.  The tests print each case's ratio as a power of two."""
 import math
@@ -29,62 +31,71 @@ def _win(Gh, ws, qs=1):
     return dict(Gh=Gh, Gw=Gh, ws=ws, q_stride=qs)
 
 
-# (id naming the branch, family, (B, H, Tq, Tk, hd, window), rel_S, stresses)
+# (id naming the branch, family, (B, H, Tq, Tk, hd, window), rel_S, stresses, route)
 SHAPES = [
-    ("small 7x7 hd32 items15", "small", (3, 5, 7, 7, 32, None), None, ALL),
-    ("small Tq16 Tk1 hd64", "small", (2, 3, 16, 1, 64, None), None, ("benign", "late_max")),
-    ("small Tq1 Tk16 hd16", "small", (24, 1, 1, 16, 16, None), None, ALL),
-    ("small win4 qs2 12x12", "small", (2 * 9, 3, 4, 16, 32, _win(12, 4, 2)), None, ALL),
-    ("small win4 padded 10x10", "small", (2 * 9, 3, 16, 16, 48, _win(10, 4)), None, WIN),
-    ("kernel<1> ones Tq7 Tk4096 hd16", "kernel", (2, 8, 7, 4096, 16, None), None, ALL),
-    ("kernel<1> dot2 Tq17 Tk300 hd64", "kernel", (2, 3, 17, 300, 64, None), None, ALL),
-    ("kernel<1> ones Tq33 Tk100 hd8", "kernel", (2, 2, 33, 100, 8, None), None, ALL),
-    ("kernel<1> ones Tq64 Tk130 hd24", "kernel", (1, 3, 64, 130, 24, None), None, ALL),
-    ("kernel<2> ones Tq4096 Tk7 hd16", "kernel", (2, 8, 4096, 7, 16, None), None, ALL),
-    ("kernel<2> dot2 T209 hd64", "kernel", (2, 3, 209, 209, 64, None), None, ALL),
-    ("kernel<2> dot2 Tq500 Tk100 hd64", "kernel", (1, 2, 500, 100, 64, None), None, ALL),
-    ("kernel<2> ones win16 padded 20x20 hd48", "kernel", (4, 2, 256, 256, 48, _win(20, 16)), None, WIN),
-    ("wide hd72 Tq30 Tk100", "wide", (2, 2, 30, 100, 72, None), None, ALL),
-    ("wide hd80 Tq300 Tk150", "wide", (1, 2, 300, 150, 80, None), None, ALL),
-    ("wide hd96 Tq100 Tk600", "wide", (1, 2, 100, 600, 96, None), None, ALL),
-    ("wide hd80 win14 padded 20x20", "wide", (4, 2, 196, 196, 80, _win(20, 14)), None, WIN),
-    ("sp ones T201 hd56", "sp", (2, 4, 201, 201, 56, None), None, ALL),
-    ("spp ones T201 hd56", "spp", (4, 16, 201, 201, 56, None), None, ALL),
-    ("sp dot2 T201 hd64", "sp", (2, 4, 201, 201, 64, None), None, ALL),
-    ("spp dot2 T201 hd64", "spp", (4, 16, 201, 201, 64, None), None, ALL),
-    ("sp ones Tq65 Tk208 hd56", "sp", (2, 3, 65, 208, 56, None), None, BL),
-    ("spp ones Tq65 Tk208 hd56", "spp", (8, 8, 65, 208, 56, None), None, BL),
-    ("sp dot2 Tq65 Tk208 hd64", "sp", (2, 3, 65, 208, 64, None), None, BL),
-    ("spp dot2 Tq65 Tk208 hd64", "spp", (8, 8, 65, 208, 64, None), None, BL),
-    ("sp ones Tq208 Tk129 hd56", "sp", (2, 3, 208, 129, 56, None), None, BL),
-    ("spp ones Tq208 Tk129 hd56", "spp", (8, 8, 208, 129, 56, None), None, BL),
-    ("sp dot2 Tq208 Tk129 hd64", "sp", (2, 3, 208, 129, 64, None), None, BL),
-    ("spp dot2 Tq208 Tk129 hd64", "spp", (8, 8, 208, 129, 64, None), None, BL),
-    ("sp ones win14 padded 20x20 hd56", "sp", (4, 4, 196, 196, 56, _win(20, 14)), None, WIN),
-    ("spp ones win14 padded 20x20 hd56", "spp", (16, 4, 196, 196, 56, _win(20, 14)), None, WIN),
-    ("sp dot2 win14 padded 20x20 hd64", "sp", (4, 4, 196, 196, 64, _win(20, 14)), None, WIN),
-    ("spp dot2 win14 padded 20x20 hd64", "spp", (16, 4, 196, 196, 64, _win(20, 14)), None, WIN),
-    ("sp dot2 items63 T201", "sp", (63, 1, 201, 201, 64, None), None, BL),
-    ("spp dot2 items64 T201", "spp", (64, 1, 201, 201, 64, None), None, BL),
-    ("gp ones T256 hd56", "gp", (1, 2, 256, 256, 56, None), None, ALL),
-    ("gp dot2 T256 hd64", "gp", (1, 2, 256, 256, 64, None), None, ALL),
-    ("gp ones T257 hd56", "gp", (2, 2, 257, 257, 56, None), None, ALL),
-    ("gp dot2 T257 hd64", "gp", (2, 2, 257, 257, 64, None), None, ALL),
-    ("gp ones T4096 hd56", "gp", (1, 2, 4096, 4096, 56, None), None, ALL),
-    ("gp dot2 T4096 hd64", "gp", (1, 2, 4096, 4096, 64, None), None, ALL),
-    ("gp ones Tq65 Tk300 hd56", "gp", (2, 2, 65, 300, 56, None), None, ALL),
-    ("gp dot2 Tq65 Tk300 hd64", "gp", (2, 2, 65, 300, 64, None), None, ALL),
-    ("gp ones Tq1024 Tk4096 hd56", "gp", (1, 2, 1024, 4096, 56, None), None, BL),
-    ("gp dot2 Tq1024 Tk4096 hd64", "gp", (1, 2, 1024, 4096, 64, None), None, BL),
-    ("rel kernel<2> S64 hd64", "rel", (1, 2, 4096, 4096, 64, None), 64, ("benign", "large", "late_max")),
-    ("rel wide S64 hd80", "rel", (1, 2, 4096, 4096, 80, None), 64, ("benign", "large", "late_max")),
-    ("rel kernel<1> win8 padded 12x12 hd64", "rel", (4, 2, 64, 64, 64, _win(12, 8)), 8, ("benign", "late_max", "pad_heavy")),
-    ("rel kernel<2> win16 padded 20x20 hd64", "rel", (4, 2, 256, 256, 64, _win(20, 16)), 16, ("benign", "late_max", "pad_heavy")),
-    ("rel wide win16 padded 20x20 hd80", "rel", (4, 2, 256, 256, 80, _win(20, 16)), 16, ("benign", "late_max", "pad_heavy")),
-    ("rel kernel<2> win14 padded 20x20 hd64", "rel", (4, 2, 196, 196, 64, _win(20, 14)), 14, ("benign", "large", "pad_heavy")),
-    ("rel wide win14 padded 20x20 hd80", "rel", (4, 2, 196, 196, 80, _win(20, 14)), 14, ("benign", "large", "pad_heavy")),
+    ("small 7x7 hd32 items15", "small", (3, 5, 7, 7, 32, None), None, ALL, "small"),
+    ("small Tq16 Tk1 hd64", "small", (2, 3, 16, 1, 64, None), None, ("benign", "late_max"), "small"),
+    ("small Tq1 Tk16 hd16", "small", (24, 1, 1, 16, 16, None), None, ALL, "small"),
+    ("small win4 qs2 12x12", "small", (2 * 9, 3, 4, 16, 32, _win(12, 4, 2)), None, ALL, "small"),
+    ("small win4 padded 10x10", "small", (2 * 9, 3, 16, 16, 48, _win(10, 4)), None, WIN, "small"),
+    ("kernel<1> ones Tq7 Tk4096 hd16", "kernel", (2, 8, 7, 4096, 16, None), None, ALL, "tiled_q1_ones_hd64"),
+    ("kernel<1> dot2 Tq17 Tk300 hd64", "kernel", (2, 3, 17, 300, 64, None), None, ALL, "tiled_q1_dot2_hd64"),
+    ("kernel<1> ones Tq33 Tk100 hd8", "kernel", (2, 2, 33, 100, 8, None), None, ALL, "tiled_q1_ones_hd64"),
+    ("kernel<1> ones Tq64 Tk130 hd24", "kernel", (1, 3, 64, 130, 24, None), None, ALL, "tiled_q1_ones_hd64"),
+    ("kernel<2> ones Tq4096 Tk7 hd16", "kernel", (2, 8, 4096, 7, 16, None), None, ALL, "tiled_q2_ones_hd64"),
+    ("kernel<2> dot2 T209 hd64", "kernel", (2, 3, 209, 209, 64, None), None, ALL, "tiled_q2_dot2_hd64"),
+    ("kernel<2> dot2 Tq500 Tk100 hd64", "kernel", (1, 2, 500, 100, 64, None), None, ALL, "tiled_q2_dot2_hd64"),
+    ("kernel<2> ones win16 padded 20x20 hd48", "kernel", (4, 2, 256, 256, 48, _win(20, 16)), None, WIN, "tiled_q2_ones_hd64"),
+    ("wide hd72 Tq30 Tk100", "wide", (2, 2, 30, 100, 72, None), None, ALL, "tiled_q1_dot2_hd96"),
+    ("wide hd80 Tq300 Tk150", "wide", (1, 2, 300, 150, 80, None), None, ALL, "tiled_q1_dot2_hd96"),
+    ("wide hd96 Tq100 Tk600", "wide", (1, 2, 100, 600, 96, None), None, ALL, "tiled_q1_dot2_hd96"),
+    ("wide hd80 win14 padded 20x20", "wide", (4, 2, 196, 196, 80, _win(20, 14)), None, WIN, "tiled_q1_dot2_hd96"),
+    ("sp ones T201 hd56", "sp", (2, 4, 201, 201, 56, None), None, ALL, "sp_qb2_ones"),
+    ("spp ones T201 hd56", "spp", (4, 16, 201, 201, 56, None), None, ALL, "spp_ones"),
+    ("sp dot2 T201 hd64", "sp", (2, 4, 201, 201, 64, None), None, ALL, "sp_qb2_dot2"),
+    ("spp dot2 T201 hd64", "spp", (4, 16, 201, 201, 64, None), None, ALL, "spp_dot2"),
+    ("sp ones Tq65 Tk208 hd56", "sp", (2, 3, 65, 208, 56, None), None, BL, "sp_qb2_ones"),
+    ("spp ones Tq65 Tk208 hd56", "spp", (8, 8, 65, 208, 56, None), None, BL, "spp_ones"),
+    ("sp dot2 Tq65 Tk208 hd64", "sp", (2, 3, 65, 208, 64, None), None, BL, "sp_qb2_dot2"),
+    ("spp dot2 Tq65 Tk208 hd64", "spp", (8, 8, 65, 208, 64, None), None, BL, "spp_dot2"),
+    ("sp ones Tq208 Tk129 hd56", "sp", (2, 3, 208, 129, 56, None), None, BL, "sp_qb2_ones"),
+    ("spp ones Tq208 Tk129 hd56", "spp", (8, 8, 208, 129, 56, None), None, BL, "spp_ones"),
+    ("sp dot2 Tq208 Tk129 hd64", "sp", (2, 3, 208, 129, 64, None), None, BL, "sp_qb2_dot2"),
+    ("spp dot2 Tq208 Tk129 hd64", "spp", (8, 8, 208, 129, 64, None), None, BL, "spp_dot2"),
+    ("sp ones win14 padded 20x20 hd56", "sp", (4, 4, 196, 196, 56, _win(20, 14)), None, WIN, "sp_qb2_ones"),
+    ("spp ones win14 padded 20x20 hd56", "spp", (16, 4, 196, 196, 56, _win(20, 14)), None, WIN, "spp_ones"),
+    ("sp dot2 win14 padded 20x20 hd64", "sp", (4, 4, 196, 196, 64, _win(20, 14)), None, WIN, "sp_qb2_dot2"),
+    ("spp dot2 win14 padded 20x20 hd64", "spp", (16, 4, 196, 196, 64, _win(20, 14)), None, WIN, "spp_dot2"),
+    ("sp dot2 items63 T201", "sp", (63, 1, 201, 201, 64, None), None, BL, "sp_qb2_dot2"),
+    ("spp dot2 items64 T201", "spp", (64, 1, 201, 201, 64, None), None, BL, "spp_dot2"),
+    ("gp ones T256 hd56", "gp", (1, 2, 256, 256, 56, None), None, ALL, "gp4_ones"),
+    ("gp dot2 T256 hd64", "gp", (1, 2, 256, 256, 64, None), None, ALL, "gp4_dot2"),
+    ("gp ones T257 hd56", "gp", (2, 2, 257, 257, 56, None), None, ALL, "gp4_ones"),
+    ("gp dot2 T257 hd64", "gp", (2, 2, 257, 257, 64, None), None, ALL, "gp4_dot2"),
+    ("gp ones T4096 hd56", "gp", (1, 2, 4096, 4096, 56, None), None, ALL, "gp4_ones"),
+    ("gp dot2 T4096 hd64", "gp", (1, 2, 4096, 4096, 64, None), None, ALL, "gp4_dot2"),
+    ("gp ones Tq65 Tk300 hd56", "gp", (2, 2, 65, 300, 56, None), None, ALL, "gp4_ones"),
+    ("gp dot2 Tq65 Tk300 hd64", "gp", (2, 2, 65, 300, 64, None), None, ALL, "gp4_dot2"),
+    ("gp ones Tq1024 Tk4096 hd56", "gp", (1, 2, 1024, 4096, 56, None), None, BL, "gp4_ones"),
+    ("gp dot2 Tq1024 Tk4096 hd64", "gp", (1, 2, 1024, 4096, 64, None), None, BL, "gp4_dot2"),
+    ("rel kernel<2> S64 hd64", "rel", (1, 2, 4096, 4096, 64, None), 64, ("benign", "large", "late_max"), "tiled_q2_dot2_rel_hd64"),
+    ("rel wide S64 hd80", "rel", (1, 2, 4096, 4096, 80, None), 64, ("benign", "large", "late_max"), "tiled_q1_dot2_rel_hd96"),
+    ("rel kernel<1> win8 padded 12x12 hd64", "rel", (4, 2, 64, 64, 64, _win(12, 8)), 8, ("benign", "late_max", "pad_heavy"), "tiled_q1_dot2_rel_hd64"),
+    ("rel kernel<2> win16 padded 20x20 hd64", "rel", (4, 2, 256, 256, 64, _win(20, 16)), 16, ("benign", "late_max", "pad_heavy"), "tiled_q2_dot2_rel_hd64"),
+    ("rel wide win16 padded 20x20 hd80", "rel", (4, 2, 256, 256, 80, _win(20, 16)), 16, ("benign", "late_max", "pad_heavy"), "tiled_q1_dot2_rel_hd96"),
+    ("rel kernel<2> win14 padded 20x20 hd64", "rel", (4, 2, 196, 196, 64, _win(20, 14)), 14, ("benign", "large", "pad_heavy"), "tiled_q2_dot2_rel_hd64"),
+    ("rel wide win14 padded 20x20 hd80", "rel", (4, 2, 196, 196, 80, _win(20, 14)), 14, ("benign", "large", "pad_heavy"), "tiled_q1_dot2_rel_hd96"),
 ]
-CASES = [(sid, fam, shape, rel_S, kind) for sid, fam, shape, rel_S, kinds in SHAPES for kind in kinds]
+CASES = [(sid, fam, shape, rel_S, kind, route) for sid, fam, shape, rel_S, kinds, route in SHAPES for kind in kinds]
+VIEW_COL0, VIEW_GAP = 8, 16  # _view: q / k / v / out are views with ld = 8 + H * hd + 16
+
+
+def shape_route(shape, rel_S):
+    """The route lmx_k_attention takes for a row of SHAPES as run_attention launches it (windows with both pad vectors)."""
+    from lmx import kernels as K_
+
+    B, H, Tq, Tk, hd, win = shape
+    return K_.attention_route(B, H, Tq, Tk, hd, window=win, pad=win is not None, rel_S=rel_S or 0, ld=VIEW_COL0 + H * hd + VIEW_GAP)
 
 
 def _geo(shape):
@@ -92,7 +103,7 @@ def _geo(shape):
     return A.Geo(B, H, Tq, Tk, hd, win)
 
 
-def _view(x, cuda, fill=math.nan, col0=8, gap=16, extra_rows=5):
+def _view(x, cuda, fill=math.nan, col0=VIEW_COL0, gap=VIEW_GAP, extra_rows=5):
     """x [rows, D] -> (buffer, view): the view starts at column col0 of a buffer with ld = col0 + D + gap and extra_rows more
     rows, everything outside the view filled with `fill`."""
     rows, D = x.shape
@@ -138,8 +149,9 @@ def _check_stress(kind, ref, geo):
     return ""
 
 
-@pytest.mark.parametrize("sid,fam,shape,rel_S,kind", CASES, ids=[f"{c[0]}-{c[4]}" for c in CASES])
-def test_attention_matches_float64(cuda, sid, fam, shape, rel_S, kind):
+@pytest.mark.parametrize("sid,fam,shape,rel_S,kind,route", CASES, ids=[f"{c[0]}-{c[4]}" for c in CASES])
+def test_attention_matches_float64(cuda, sid, fam, shape, rel_S, kind, route):
+    assert shape_route(shape, rel_S) == route, sid
     geo = _geo(shape)
     inp = A.make_inputs(kind, geo, seed=sum(shape[:5]) + A.STRESSES.index(kind), rel_S=rel_S)
     got = run_attention(inp, geo, cuda)

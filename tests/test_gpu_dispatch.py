@@ -4,9 +4,10 @@ M = 65536; csrc/gemm2.hip lmx_gemm2_launch: four dense tilings keyed on tiles256
 t256 >= 230).  Every one of them must return the same bits for the same output rows: the same 16x16x32 MFMA in the same k order
 and one rounding sequence in every epilogue.
 
-GEMM level: one problem computed whole, then again in row chunks whose sizes land in the OTHER branches (the branch of each is
-in the comments, derived from the rules above and confirmed under a kernel trace); the concatenation must be torch.equal to the
-whole.  Model level: a frame / prompt alone against the same frame / prompt inside a batch that crosses the thresholds.
+GEMM level: one problem computed whole, then again in row chunks whose sizes land in the OTHER branches; the concatenation must
+be torch.equal to the whole.  The branch of each chunk is a row of the route tables below: every case asserts, before it launches,
+that the library's own selection (lmx.kernels.gemm_route / conv3x3_route / attention_route) names that kernel for it, and
+tests/test_dispatch_routes_host.py holds the same tables to the selection without a GPU.  Model level: a frame / prompt alone against the same frame / prompt inside a batch that crosses the thresholds.
 Branches are reached by shape only (the LMX_GEMM_* development switches are process-wide and would leak into later tests).
 
 lmx_k_layernorm switches on rows = frames x tokens too (layernorm_rows_kernel from 16384 rows): that threshold is crossed by
@@ -34,19 +35,49 @@ def _assert_equal(got, whole, what):
         raise AssertionError(f"{what}: {len(bad)} rows differ from the whole problem's, first {bad[:8].tolist()}")
 
 
-# N = 1792, K = 448 (the fc1 of Hiera stage 3).  Rows -> branch:
-#     500 -> v1 128x128 (M < 512) | 4096 -> staggered 256x128x64 (tiles256 = 112, tiles = 224 <= 256) |
-#     8192 -> 256x256x64 (tiles256 = 224, q256 = 0.875) | 12000 -> 256x128x32 (tiles256 = 329, q256 = 0.64; tiles = 658) |
-#     whole 24788 -> 256x256x64 (tiles256 = 679, q256 = 0.88)
+# the route names of lmx_h_gemm_route (include/lmx.h): register-staged 128 x BN, or LDS-DMA BM x BN x BK, ring slots, staggered
+V1, V1_N64 = "v1_128x128", "v1_128x64"
+DMA_STAG, DMA_Z, DMA_C = "dma_256x128x64_s3_stag", "dma_256x256x64_s2", "dma_256x128x32_s3"
+DMA_E, DMA_Y = "dma_256x256x32_s3", "dma_256x256x32_s3_stag"
+
+# N = 1792, K = 448 (the fc1 of Hiera stage 3).  Rows -> route:
+#     500 (M < 512) | 4096 (tiles256 = 112, tiles = 224 <= 256) | 8192 (tiles256 = 224, q256 = 0.875) |
+#     12000 (tiles256 = 329, q256 = 0.64; tiles = 658) | whole 24788 (tiles256 = 679, q256 = 0.88)
 DENSE_SIZES = [500, 4096, 8192, 12000]
+DENSE_ROUTES = {500: V1, 4096: DMA_STAG, 8192: DMA_Z, 12000: DMA_C, 24788: DMA_Z}
+# the same shape with a_rep 2 (K = 896 in the descriptor; M >= 512 only): 20180 rows have tiles256 = 553, q256 = 0.72
+AREP_ROUTES = {512: DMA_STAG, 4096: DMA_STAG, 20180: DMA_C, 24788: DMA_Z}
 # short K (256 x 256 short-K rule: K < 448, N = 224 .. 1536 not a multiple of 256, tiles256 >= 200, q256 >= 0.75):
-#     N = 672, K = 112: 17152 rows -> 256x256x64 short K (tiles256 201); 16896 -> 256x128x32 (tiles256 198); 256 -> v1 128x128
-#     N = 1344, K = 224: 8704 rows -> 256x256x32 short K (tiles256 204); 8448 -> 256x128x32 (198); 256 -> v1 128x128
-SHAPES = [(1792, 448, 24788, DENSE_SIZES), (672, 112, 17152, [16896, 256]), (1344, 224, 8704, [8448, 256])]
+#     N = 672, K = 112: 17152 rows -> 64-deep short K (tiles256 201); 16896 (tiles256 198)
+#     N = 1344, K = 224: 8704 rows -> 32-deep short K (tiles256 204); 8448 (198)
+# (N, K, M, chunk sizes, {rows: route} for M and every chunk size)
+SHAPES = [(1792, 448, 24788, DENSE_SIZES, DENSE_ROUTES),
+          (672, 112, 17152, [16896, 256], {17152: DMA_Z, 16896: DMA_C, 256: V1}),
+          (1344, 224, 8704, [8448, 256], {8704: DMA_E, 8448: DMA_C, 256: V1})]
 
 FORMS = ["f16_silu_res", "f16_gelu_res", "f32_scale_res", "f32_res_rows", "a_rep2"]
+# what gemm_route needs to know of a form (the activation does not enter the selection)
+FORM_ROUTE_ARGS = {
+    "f16_silu_res": dict(out_dtype=torch.float16, res=True),
+    "f16_gelu_res": dict(out_dtype=torch.float16, scale=True, res=True),
+    "f32_scale_res": dict(out_dtype=torch.float32, scale=True, res=True),
+    "f32_res_rows": dict(out_dtype=torch.float32, scale=True, res=True, res_rows=4),
+    "a_rep2": dict(out_dtype=torch.float32, scale=True, res=True, a_rep=2),
+}
 # (a_rep needs K % 64 == 0: the N = 1792 / K = 448 shape only)
-CASES = [(N, K, M, sizes, f) for N, K, M, sizes in SHAPES for f in FORMS if f != "a_rep2" or K % 64 == 0]
+CASES = [(N, K, M, sizes, f) for N, K, M, sizes, _ in SHAPES for f in FORMS if f != "a_rep2" or K % 64 == 0]
+
+
+def gemm_case_sizes(M, sizes, form):
+    """The chunk sizes a case of CASES runs (a_rep needs M >= 512: the LDS-DMA kernel only)."""
+    if form == "a_rep2":
+        return [4096, M - 4096 - 512, 512] if M > 9000 else [M - 512, 512]
+    return sizes
+
+
+def gemm_case_routes(N, K, form):
+    """{rows: route} of a case of CASES: the whole problem and every chunk size."""
+    return AREP_ROUTES if form == "a_rep2" else next(r for n, k, _, _, r in SHAPES if (n, k) == (N, K))
 
 
 @pytest.mark.parametrize("N,K,M,sizes,form", CASES, ids=[f"N{c[0]}K{c[1]}-{c[4]}" for c in CASES])
@@ -67,8 +98,10 @@ def test_gemm_rows_are_independent_of_the_batch(cuda, N, K, M, sizes, form):
     else:
         res = torch.randn((M, N), device=cuda, generator=g)
         res = res.half() if form.startswith("f16") else res
-    if form == "a_rep2":
-        sizes = [4096, M - 4096 - 512, 512] if M > 9000 else [M - 512, 512]  # a_rep needs M >= 512 (the LDS-DMA kernel only)
+    sizes = gemm_case_sizes(M, sizes, form)
+    routes = gemm_case_routes(N, K, form)
+    for rows in [M] + sizes:
+        assert K_.gemm_route(rows, N, K, **FORM_ROUTE_ARGS[form]) == routes[rows], f"N={N} K={K} {form}: {rows} rows"
 
     def run(r0, r1):
         if form == "f16_silu_res":
@@ -88,22 +121,29 @@ def test_gemm_rows_are_independent_of_the_batch(cuda, N, K, M, sizes, form):
     _assert_equal(_chunked(run, M, sizes[::-1]), whole, f"N={N} K={K} {form} chunks {sizes[::-1]}")
 
 
-# (label, frames per chunk, H, W, Cin (x3: 3 x logical), Cout, stride, form)
-#   x3 Cin' = 192, Cout = 64 on 96 x 160: 5 frames (M = 76800 >= 65536) -> LDS-DMA 256x128x32, 4 frames and 1 -> v1 128x64
-#   Cout = 256 on 40 x 64: 24 frames (t256 = 240) -> staggered 256x256x32, 1 frame (t256 = 10) -> 256x128x32
-#   16 x 16, Cout = 128: 2 frames (M = 512) -> 256x128x32, 1 frame (M = 256) -> v1 128x128
+# (label, frames, frames per chunk, H, W, Cin (x3: 3 x logical), Cout, stride, form, {frames: route} for the whole and every chunk)
+#   x3 Cin' = 192, Cout = 64 on 96 x 160: 5 frames are M = 76800 >= 65536, 4 frames and 1 stay on the register-staged kernel
+#   Cout = 256 on 40 x 64: 24 frames have t256 = 240, 12 frames 120, 1 frame 10
+#   16 x 16 output pixels, Cout = 128: 2 frames are M = 512, 1 frame M = 256
 CONV_CASES = [
-    ("x3 N=64 rule", 5, [4, 1], 96, 160, 192, 64, 1, "f32_scale"),
-    ("t256 rule", 24, [1] * 24, 40, 64, 96, 256, 1, "f32_scale"),
-    ("t256 rule f16", 24, [11, 1, 12], 40, 64, 96, 256, 1, "f16_silu_res"),
-    ("v1 / gemm2", 2, [1, 1], 16, 16, 64, 128, 1, "f16_silu_res"),
-    ("v1 / gemm2 stride 2", 2, [1, 1], 32, 32, 64, 128, 2, "f32_scale"),
+    ("x3 N=64 rule", 5, [4, 1], 96, 160, 192, 64, 1, "f32_scale", {5: DMA_C, 4: V1_N64, 1: V1_N64}),
+    ("t256 rule", 24, [1] * 24, 40, 64, 96, 256, 1, "f32_scale", {24: DMA_Y, 1: DMA_C}),
+    ("t256 rule f16", 24, [11, 1, 12], 40, 64, 96, 256, 1, "f16_silu_res", {24: DMA_Y, 12: DMA_C, 11: DMA_C, 1: DMA_C}),
+    ("v1 / gemm2", 2, [1, 1], 16, 16, 64, 128, 1, "f16_silu_res", {2: DMA_C, 1: V1}),
+    ("v1 / gemm2 stride 2", 2, [1, 1], 32, 32, 64, 128, 2, "f32_scale", {2: DMA_C, 1: V1}),
 ]
+CONV_FORM_ROUTE_ARGS = {"f32_scale": dict(out_dtype=torch.float32, act=0, scale=True), "f16_silu_res": dict(out_dtype=torch.float16, res=True)}
+# test_conv3x3_split_k_partials_are_independent_of_the_batch: (frames, H, W, Cin, Cout, split_k, {frames: route})
+SPLIT_K_CASE = (24, 40, 64, 96, 256, 4, {24: DMA_Y, 1: DMA_C})
 
 
-@pytest.mark.parametrize("label,n,sizes,H,W,cin,cout,stride,form", CONV_CASES, ids=[c[0] for c in CONV_CASES])
-def test_conv3x3_frames_are_independent_of_the_batch(cuda, label, n, sizes, H, W, cin, cout, stride, form):
+@pytest.mark.parametrize("label,n,sizes,H,W,cin,cout,stride,form,routes", CONV_CASES, ids=[c[0] for c in CONV_CASES])
+def test_conv3x3_frames_are_independent_of_the_batch(cuda, label, n, sizes, H, W, cin, cout, stride, form, routes):
     from lmx import kernels as K_
+
+    for frames in [n] + sizes:
+        got = K_.conv3x3_route(frames, H, W, cin, cout, stride=stride, **CONV_FORM_ROUTE_ARGS[form])
+        assert got == routes[frames], f"conv {label}: {frames} frames"
 
     g = torch.Generator(device=cuda).manual_seed(cin + cout + H)
     x = torch.randn((n, H, W, cin), device=cuda, generator=g).half()
@@ -127,7 +167,9 @@ def test_conv3x3_split_k_partials_are_independent_of_the_batch(cuda):
     from lmx import kernels as K_
 
     g = torch.Generator(device=cuda).manual_seed(77)
-    n, H, W, cin, cout, S = 24, 40, 64, 96, 256, 4
+    n, H, W, cin, cout, S, routes = SPLIT_K_CASE
+    for frames in (n, 1):
+        assert K_.conv3x3_route(frames, H, W, cin, cout, out_dtype=torch.float32, act=0, scale=True, split_k=S) == routes[frames]
     x = torch.randn((n, H, W, cin), device=cuda, generator=g).half()
     w = (torch.randn((cout, 9 * cin), device=cuda, generator=g) * (9 * cin) ** -0.5).half()
     b = torch.randn((cout,), device=cuda, generator=g)
@@ -201,17 +243,23 @@ def test_dino_frame_alone_equals_frame_in_batch(cuda):
 # lmx_k_attention runs 128 < Tk <= 208 (64 < Tq <= 208, hd <= 64) on attn_sp below B * H = 64 items and on the persistent
 # attn_spp from 64 (csrc/attn.hip lmx_k_attention; window geometry needs both pad vectors).  A frame's rows must be the same
 # bits either way: the whole problem (>= 64 items, attn_spp) against batch chunks of < 64 items each (attn_sp).
-# (label, items per batch element (H, or H x windows per image), B, chunk sizes in batch elements, hd, window)
+# (label, items per batch element (H, or H x windows per image), B, chunk sizes in batch elements, hd, window,
+#  (route of the whole, route of every chunk): lmx_h_attn_route's names)
 ATTN_CASES = [
-    ("flat T201 hd56 H16", 16, 8, [3, 1, 2, 2], 56, None),
-    ("flat T201 hd64 H16", 16, 8, [3, 1, 2, 2], 64, None),
-    ("win14 28x28 pad vectors hd56 H2", 2, 8 * 4, [3, 1, 4], 56, dict(Gh=28, Gw=28, ws=14, q_stride=1)),
-    ("win14 20x20 pad vectors hd64 H2", 2, 8 * 4, [7, 1], 64, dict(Gh=20, Gw=20, ws=14, q_stride=1)),
+    ("flat T201 hd56 H16", 16, 8, [3, 1, 2, 2], 56, None, ("spp_ones", "sp_qb2_ones")),
+    ("flat T201 hd64 H16", 16, 8, [3, 1, 2, 2], 64, None, ("spp_dot2", "sp_qb2_dot2")),
+    ("win14 28x28 pad vectors hd56 H2", 2, 8 * 4, [3, 1, 4], 56, dict(Gh=28, Gw=28, ws=14, q_stride=1), ("spp_ones", "sp_qb2_ones")),
+    ("win14 20x20 pad vectors hd64 H2", 2, 8 * 4, [7, 1], 64, dict(Gh=20, Gw=20, ws=14, q_stride=1), ("spp_dot2", "sp_qb2_dot2")),
 ]
 
 
-@pytest.mark.parametrize("label,H,B,sizes,hd,window", ATTN_CASES, ids=[c[0] for c in ATTN_CASES])
-def test_attention_rows_are_independent_of_the_batch(cuda, label, H, B, sizes, hd, window):
+def attn_case_batches(B, sizes, window):
+    """B of the whole problem, then of every chunk of a case of ATTN_CASES, as lmx_k_attention counts it (windows: 4 per image)."""
+    return [B] + [s * (1 if window is None else 4) for s in sizes]
+
+
+@pytest.mark.parametrize("label,H,B,sizes,hd,window,routes", ATTN_CASES, ids=[c[0] for c in ATTN_CASES])
+def test_attention_rows_are_independent_of_the_batch(cuda, label, H, B, sizes, hd, window, routes):
     """sizes in batch elements (frames | windows); for windows a chunk is whole images (4 windows of 14 x 14 each)."""
     from lmx import kernels as K_
 
@@ -224,6 +272,9 @@ def test_attention_rows_are_independent_of_the_batch(cuda, label, H, B, sizes, h
     qkv = (torch.randn((n_elem * rows_per, 3 * D), device=cuda, generator=g) * 1.5).half()
     pad = torch.randn((3 * D,), device=cuda, generator=g).half()
     assert B * heads >= 64 and all(s * per * heads < 64 for s in sizes)
+    for i, b in enumerate(attn_case_batches(B, sizes, window)):
+        got = K_.attention_route(b, heads, T, T, hd, window=window, pad=window is not None, ld=3 * D)
+        assert got == routes[min(i, 1)], f"attention {label}: B = {b}"
 
     def run(e0, e1):
         x = qkv[e0 * rows_per:e1 * rows_per]

@@ -1528,7 +1528,21 @@ extern "C" int lmx_k_relpos_tables(const lmx_attn_desc* dp, const float* rel_pos
   return lmx_launch_check("relpos_tables_kernel");
 }
 
-extern "C" int lmx_k_attention(const lmx_attn_desc* dp, lmx_stream_t stream) {
+// The kernel lmx_k_attention launches and everything the launch needs: what attn_route fills.  The template arguments that do not
+// apply to a kernel keep their defaults below.
+enum AttnKernel { ATTN_SMALL, ATTN_SP, ATTN_SPP, ATTN_GP, ATTN_TILED };
+struct AttnRoute {
+  AttnKernel kernel;
+  int QB = 1;                                  // sp, tiled: 16-query blocks per wave
+  bool ONES = false, REL = false, DMA = false;  // ONES: row sums on the MFMA (hd <= 56) | tiled: relative-position bias, LDS-DMA staging
+  int HDW = 64, NWV = 4;                       // tiled: halfs per LDS row / 2 (64: hd <= 64, 96: the wide class) | gp: waves per workgroup
+  unsigned grid = 0, block = 256;              // (spp: grid = the items; the launch caps it at the device's CUs)
+  int lds = 0;                                 // dynamic LDS bytes
+  int arg = 0;                                 // small, spp: items | gp, tiled: query tiles per (batch, head), negative = no lazy rescaling
+};
+
+// validation and kernel selection of lmx_k_attention: a pure function of the descriptor and the development switches
+static int attn_route(const lmx_attn_desc* dp, AttnRoute& r, Geo& g) {
   LMX_REQUIRE(dp != nullptr, "lmx_k_attention: null descriptor");
   const lmx_attn_desc& d = *dp;
   LMX_REQUIRE(d.Q && d.K && d.V && d.O, "lmx_k_attention: null Q/K/V/O");
@@ -1537,105 +1551,150 @@ extern "C" int lmx_k_attention(const lmx_attn_desc* dp, lmx_stream_t stream) {
   LMX_REQUIRE(d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 4 == 0, "lmx_k_attention: strides");
   LMX_REQUIRE(aligned16(d.Q) && aligned16(d.K) && aligned16(d.V) && ((((uintptr_t)d.O) & 7) == 0),
               "lmx_k_attention: alignment");
-  Geo g{};
-  {
-    const int rc = build_geo(d, g);
-    if (rc) return rc;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-
-  if (d.Tq <= 16 && d.Tk <= 16 && !d.rel && d.hd <= 64) {  // one wave per (batch | window, head)
-    const int64_t items = (int64_t)d.B * d.H;
-    LMX_REQUIRE(items < (1ll << 31), "lmx_k_attention: grid too large");
-    hipLaunchKernelGGL(attn_small_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, d, g, (int)items);
-    return lmx_launch_check("attn_small_kernel");
-  }
-  static const int no_sp = lmx_env_set("LMX_ATTN_NO_SP");
-  if (!no_sp && !d.rel && d.hd <= 64 && d.Tk > 128 && d.Tk <= 208 && d.Tq > 64 && d.Tq <= 208) {  // whole sequence per workgroup
-    const int64_t items = (int64_t)d.B * d.H;
-    LMX_REQUIRE(items < (1ll << 31), "lmx_k_attention: grid too large");
-    static const int sp_qb = lmx_env_int("LMX_ATTN_SP_QB", 2), no_spp = lmx_env_set("LMX_ATTN_NO_SPP");
-    // persistent double-buffered form (one 8-wave workgroup per CU walks a range of items): window geometry needs both padding
-    // vectors (a padded key with no vector would have to be WRITTEN as zeros, which the masked DMA does not do)
-    if (!no_spp && items >= 64 && (d.mode == 0 || (d.pad_k && d.pad_v)) && d.hd % 8 == 0) {
-      constexpr int SMEM = 2 * 3 * 208 * 64 * 2;
-      int dev;
-      unsigned grid;
-      LMX_TRY(lmx_stream_device(st, &dev));
-      LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&attn_spp_kernel<true>), SMEM, dev));
-      LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&attn_spp_kernel<false>), SMEM, dev));
-      LMX_TRY(lmx_persistent_grid(items, dev, &grid));
-      if (d.hd <= 56)
-        hipLaunchKernelGGL((attn_spp_kernel<true>), dim3(grid), dim3(512), SMEM, st, d, g, (int)items);
-      else
-        hipLaunchKernelGGL((attn_spp_kernel<false>), dim3(grid), dim3(512), SMEM, st, d, g, (int)items);
-      return lmx_launch_check("attn_spp_kernel");
-    }
-    if (d.hd <= 56 && sp_qb == 2)
-      hipLaunchKernelGGL((attn_sp_kernel<2, true>), dim3((unsigned)items), dim3(256), 0, st, d, g);
-    else if (d.hd <= 56)
-      hipLaunchKernelGGL((attn_sp_kernel<1, true>), dim3((unsigned)items), dim3(256), 0, st, d, g);
-    else if (sp_qb == 2)
-      hipLaunchKernelGGL((attn_sp_kernel<2, false>), dim3((unsigned)items), dim3(256), 0, st, d, g);
-    else
-      hipLaunchKernelGGL((attn_sp_kernel<1, false>), dim3((unsigned)items), dim3(256), 0, st, d, g);
-    return lmx_launch_check("attn_sp_kernel");
-  }
-  const bool wide = d.hd > 64;  // SAM ViT-H (head dim 80): 128-half LDS rows, one 16-query block per wave
-  const bool big = d.Tq > 64 && !wide;
-  const int qtile = big ? 128 : 64;
-  int nQT = (d.Tq + qtile - 1) / qtile;
-  const int64_t nblk = (int64_t)d.B * d.H * nQT;
-  LMX_REQUIRE(nblk < (1ll << 31), "lmx_k_attention: grid too large");
-  const bool ones = d.hd <= 56;
-  // LDS-DMA staging: flat geometry without bias, at least a few key tiles, per-(batch) K/V extent within a 31-bit buffer
+  LMX_TRY(build_geo(d, g));
+  static const int no_sp = lmx_env_set("LMX_ATTN_NO_SP"), sp_qb = lmx_env_int("LMX_ATTN_SP_QB", 2), no_spp = lmx_env_set("LMX_ATTN_NO_SPP");
   static const int no_dma = lmx_env_set("LMX_ATTN_NO_DMA"), no_lazy = lmx_env_set("LMX_ATTN_NO_LAZY");
   static const int no_gp = lmx_env_set("LMX_ATTN_NO_GP");  // A/B: the unpipelined LDS-DMA form of attn_kernel
-  const bool dma = !no_dma && !wide && d.mode == 0 && !d.rel && big && d.Tk >= 256 && (int64_t)d.Tk * d.ldk * 2 < 0x7fff0000ll &&
-                   (int64_t)d.Tk * d.ldv * 2 < 0x7fff0000ll;
-  if (no_lazy) nQT = -nQT;
   // the pipelined kernel runs 4 waves (128 queries) per workgroup; LMX_ATTN_GP_WAVES=8 selects the 8-wave form (256 queries share a
   // K / V tile, one LDS-DMA piece per wave and tensor instead of two): measured SLOWER, 1595 vs 1526 us at B = 30, H = 8, T = 4096 —
   // the barrier among eight waves costs more than the saved issue slots (identical bits)
   static const int gp_waves = lmx_env_int("LMX_ATTN_GP_WAVES", 4);
-  const bool gp8 = gp_waves == 8;
-  const int nQT8 = (d.Tq + 255) / 256;
-#define GP_LAUNCH(ones)                                                                                                                    \
-  do {                                                                                                                                     \
-    if (gp8)                                                                                                                               \
-      hipLaunchKernelGGL((attn_gp_kernel<ones, 8>), dim3((unsigned)((int64_t)d.B * d.H * nQT8)), dim3(512), 2 * 3 * 64 * 64 * 2, st, d,    \
-                         no_lazy ? -nQT8 : nQT8);                                                                                          \
-    else                                                                                                                                   \
-      hipLaunchKernelGGL((attn_gp_kernel<ones, 4>), dim3((unsigned)nblk), dim3(256), 2 * 3 * 64 * 64 * 2, st, d, nQT);                     \
-  } while (0)
-  if (d.rel) {
+
+  r = AttnRoute{};
+  r.ONES = d.hd <= 56;
+  const int64_t items = (int64_t)d.B * d.H;
+  const bool narrow = !d.rel && d.hd <= 64;  // the kernels without bias for head dims up to 64
+  if (narrow && d.Tq <= 16 && d.Tk <= 16) {  // one wave per (batch | window, head)
+    LMX_REQUIRE(items < (1ll << 31), "lmx_k_attention: grid too large");
+    r.kernel = ATTN_SMALL;
+    r.ONES = false;
+    r.grid = (unsigned)((items + 3) / 4);
+    r.arg = (int)items;
+    return LMX_OK;
+  }
+  if (!no_sp && narrow && d.Tk > 128 && d.Tk <= 208 && d.Tq > 64 && d.Tq <= 208) {  // whole sequence per workgroup
+    LMX_REQUIRE(items < (1ll << 31), "lmx_k_attention: grid too large");
+    r.grid = (unsigned)items;
+    // persistent double-buffered form (one 8-wave workgroup per CU walks a range of items): window geometry needs both padding
+    // vectors (a padded key with no vector would have to be WRITTEN as zeros, which the masked DMA does not do)
+    if (!no_spp && items >= 64 && (d.mode == 0 || (d.pad_k && d.pad_v))) {
+      r.kernel = ATTN_SPP;
+      r.block = 512;
+      r.lds = 2 * 3 * 208 * 64 * 2;
+      r.arg = (int)items;
+    } else {
+      r.kernel = ATTN_SP;
+      r.QB = sp_qb == 2 ? 2 : 1;
+    }
+    return LMX_OK;
+  }
+  const bool wide = d.hd > 64;  // SAM ViT-H (head dim 80): 128-half LDS rows, one 16-query block per wave
+  const bool big = d.Tq > 64 && !wide;
+  const int nQT = (d.Tq + (big ? 128 : 64) - 1) / (big ? 128 : 64);
+  const int64_t nblk = items * nQT;
+  LMX_REQUIRE(nblk < (1ll << 31), "lmx_k_attention: grid too large");
+  if (d.rel)
     LMX_REQUIRE(d.rel_S > 0 && d.rel_S * d.rel_S == d.Tk && d.Tq == d.Tk, "lmx_k_attention: rel_S=%d does not match Tq=%d Tk=%d",
                 d.rel_S, d.Tq, d.Tk);
-    if (wide)
-      hipLaunchKernelGGL((attn_kernel<1, false, true, false, 96>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-    else if (big)
-      hipLaunchKernelGGL((attn_kernel<2, false, true, false, 64>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-    else
-      hipLaunchKernelGGL((attn_kernel<1, false, true, false, 64>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-  } else if (wide)
-    hipLaunchKernelGGL((attn_kernel<1, false, false, false, 96>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-  else if (dma && !no_gp && ones)
-    GP_LAUNCH(true);
-  else if (dma && !no_gp)
-    GP_LAUNCH(false);
-  else if (dma && ones)
-    hipLaunchKernelGGL((attn_kernel<2, true, false, true, 64>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-  else if (dma)
-    hipLaunchKernelGGL((attn_kernel<2, false, false, true, 64>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-  else if (big && ones)
-    hipLaunchKernelGGL((attn_kernel<2, true, false, false, 64>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-  else if (big)
-    hipLaunchKernelGGL((attn_kernel<2, false, false, false, 64>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-  else if (ones)
-    hipLaunchKernelGGL((attn_kernel<1, true, false, false, 64>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-  else
-    hipLaunchKernelGGL((attn_kernel<1, false, false, false, 64>), dim3((unsigned)nblk), dim3(256), 0, st, d, g, nQT);
-  return lmx_launch_check("attn_kernel");
+  // LDS-DMA staging: flat geometry without bias, at least a few key tiles, per-(batch) K/V extent within a 31-bit buffer
+  const bool dma = !no_dma && !wide && d.mode == 0 && !d.rel && big && d.Tk >= 256 && (int64_t)d.Tk * d.ldk * 2 < 0x7fff0000ll &&
+                   (int64_t)d.Tk * d.ldv * 2 < 0x7fff0000ll;
+  if (dma && !no_gp) {
+    r.kernel = ATTN_GP;
+    r.NWV = gp_waves == 8 ? 8 : 4;
+    const int nQTw = (d.Tq + r.NWV * 32 - 1) / (r.NWV * 32);
+    r.grid = (unsigned)(items * nQTw);
+    r.block = r.NWV * 64;
+    r.lds = 2 * 3 * 64 * 64 * 2;
+    r.arg = no_lazy ? -nQTw : nQTw;
+    return LMX_OK;
+  }
+  r.kernel = ATTN_TILED;
+  r.QB = big ? 2 : 1;
+  r.ONES = r.ONES && !d.rel;
+  r.REL = d.rel != nullptr;
+  r.DMA = dma;
+  r.HDW = wide ? 96 : 64;
+  r.grid = (unsigned)nblk;
+  r.arg = no_lazy ? -nQT : nQT;
+  return LMX_OK;
+}
+
+// one case per instantiation
+static constexpr int attn_key(int kernel, int QB, bool ONES, bool REL, bool DMA, int HDW, int NWV) {
+  return (((((kernel * 4 + QB) * 2 + ONES) * 2 + REL) * 2 + DMA) * 128 + HDW) * 16 + NWV;
+}
+
+extern "C" int lmx_k_attention(const lmx_attn_desc* dp, lmx_stream_t stream) {
+  AttnRoute r;
+  Geo g{};
+  LMX_TRY(attn_route(dp, r, g));
+  const lmx_attn_desc& d = *dp;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 block(r.block);
+  dim3 grid(r.grid);
+  if (r.kernel == ATTN_SPP) {
+    int dev;
+    LMX_TRY(lmx_stream_device(st, &dev));
+    LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&attn_spp_kernel<true>), r.lds, dev));
+    LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&attn_spp_kernel<false>), r.lds, dev));
+    LMX_TRY(lmx_persistent_grid(r.grid, dev, &grid.x));
+  }
+#define LMX_SP(QB, ONES) \
+  case attn_key(ATTN_SP, QB, ONES, false, false, 64, 4): hipLaunchKernelGGL((attn_sp_kernel<QB, ONES>), grid, block, 0, st, d, g); break
+#define LMX_SPP(ONES) \
+  case attn_key(ATTN_SPP, 1, ONES, false, false, 64, 4): hipLaunchKernelGGL((attn_spp_kernel<ONES>), grid, block, r.lds, st, d, g, r.arg); break
+#define LMX_GP(ONES, NWV) \
+  case attn_key(ATTN_GP, 1, ONES, false, false, 64, NWV): hipLaunchKernelGGL((attn_gp_kernel<ONES, NWV>), grid, block, r.lds, st, d, r.arg); break
+#define LMX_TILED(QB, ONES, REL, DMA, HDW) \
+  case attn_key(ATTN_TILED, QB, ONES, REL, DMA, HDW, 4): hipLaunchKernelGGL((attn_kernel<QB, ONES, REL, DMA, HDW>), grid, block, 0, st, d, g, r.arg); break
+  switch (attn_key(r.kernel, r.QB, r.ONES, r.REL, r.DMA, r.HDW, r.NWV)) {
+    case attn_key(ATTN_SMALL, 1, false, false, false, 64, 4): hipLaunchKernelGGL(attn_small_kernel, grid, block, 0, st, d, g, r.arg); break;
+    LMX_SPP(true);
+    LMX_SPP(false);
+    LMX_SP(2, true);
+    LMX_SP(1, true);
+    LMX_SP(2, false);
+    LMX_SP(1, false);
+    LMX_TILED(1, false, true, false, 96);
+    LMX_TILED(2, false, true, false, 64);
+    LMX_TILED(1, false, true, false, 64);
+    LMX_TILED(1, false, false, false, 96);
+    LMX_GP(true, 8);
+    LMX_GP(true, 4);
+    LMX_GP(false, 8);
+    LMX_GP(false, 4);
+    LMX_TILED(2, true, false, true, 64);
+    LMX_TILED(2, false, false, true, 64);
+    LMX_TILED(2, true, false, false, 64);
+    LMX_TILED(2, false, false, false, 64);
+    LMX_TILED(1, true, false, false, 64);
+    LMX_TILED(1, false, false, false, 64);
+    default: LMX_REQUIRE(false, "lmx_k_attention: no kernel for route %d", (int)r.kernel);
+  }
+#undef LMX_SP
+#undef LMX_SPP
+#undef LMX_GP
+#undef LMX_TILED
+  static const char* const what[] = {"attn_small_kernel", "attn_sp_kernel", "attn_spp_kernel", "attn_gp_kernel", "attn_kernel"};
+  return lmx_launch_check(what[r.kernel]);
+}
+
+extern "C" int lmx_h_attn_route(const lmx_attn_desc* dp, char* name, int cap) {
+  AttnRoute r;
+  Geo g{};
+  LMX_TRY(attn_route(dp, r, g));
+  const char* sums = r.ONES ? "ones" : "dot2";
+  switch (r.kernel) {
+    case ATTN_SMALL: LMX_ROUTE_NAME(name, cap, "small"); break;
+    case ATTN_SP: LMX_ROUTE_NAME(name, cap, "sp_qb%d_%s", r.QB, sums); break;
+    case ATTN_SPP: LMX_ROUTE_NAME(name, cap, "spp_%s", sums); break;
+    case ATTN_GP: LMX_ROUTE_NAME(name, cap, "gp%d_%s", r.NWV, sums); break;
+    case ATTN_TILED:
+      LMX_ROUTE_NAME(name, cap, "tiled_q%d_%s%s%s_hd%d", r.QB, sums, r.REL ? "_rel" : "", r.DMA ? "_dma" : "", r.HDW);
+      break;
+  }
+  return LMX_OK;
 }
 
 static int build_geo(const lmx_attn_desc& d, Geo& g) {

@@ -62,6 +62,22 @@ int lmx_env_int(const char* name, int dflt);
 int lmx_env_set(const char* name);
 int lmx_env_char(const char* name);
 
+// ---- kernel selection (Reproducibility).  lmx_k_gemm, lmx_k_attention and lmx_k_layernorm each validate and choose in one
+// pure host function (gemm_route, attn_route, ln_route: no HIP call, nothing read behind the descriptor's pointers) and launch in
+// another, which holds one switch from the route to the instantiation; lmx_h_*_route return the route's name without a GPU.
+// the kernel of a GEMM: the register-staged gemm_kernel (gemm.hip; BM x BN x 64, two LDS buffers) or the LDS-DMA gemm2_kernel
+// (gemm2.hip) with its tiling
+struct GemmRoute {
+  bool dma;
+  int BM, BN, BK, NSTAGE, STAG;
+};
+// a route's name into the caller's buffer (the lmx_h_*_route entry points only: no launch formats a string)
+#define LMX_ROUTE_NAME(name, cap, ...)                                                                          \
+  do {                                                                                                          \
+    LMX_REQUIRE((name) != nullptr && (cap) > 0, "%s: no room for the name", __func__);                          \
+    LMX_REQUIRE(snprintf((name), (size_t)(cap), __VA_ARGS__) < (cap), "%s: name buffer of %d bytes is too short", __func__, (cap)); \
+  } while (0)
+
 static inline int lmx_launch_check(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

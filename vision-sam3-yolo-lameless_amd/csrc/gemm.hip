@@ -268,23 +268,23 @@ int launch(const lmx_gemm_desc& d, hipStream_t st) {
   return lmx_launch_check("gemm_kernel");
 }
 
-template <int AMODE, int OUT_DT>
-int dispatch_tile(const lmx_gemm_desc& d, hipStream_t st) {
-  // narrow outputs (Detect head 64/80 channels, small stems) take the 128x64 tile
-  if (d.N <= 64 || (d.N < 128 && d.N % 128 != 0)) return launch<128, 64, AMODE, OUT_DT>(d, st);
-  return launch<128, 128, AMODE, OUT_DT>(d, st);
-}
-
 }  // namespace
 
-int lmx_gemm2_launch(const lmx_gemm_desc& d, hipStream_t st);  // gemm2.hip
+GemmRoute lmx_gemm2_tiling(const lmx_gemm_desc& d);                                 // gemm2.hip
+int lmx_gemm2_launch(const lmx_gemm_desc& d, const GemmRoute& r, hipStream_t st);  // gemm2.hip
 
-static bool force_v1() {
-  static const int v = lmx_env_char("LMX_GEMM_V1");
-  return v == '1';
+// What the LDS-DMA kernel (gemm2.hip) can take, stated once: dense or pooled rows, or a 3 x 3 convolution whose Cin is a multiple
+// of 32 on an image below 32768 x 32768; 16-byte output rows (and residual rows); at least m_min rows and n_min columns.  The
+// floors are the caller's: split_k takes any M (whether a layer is split must not depend on the batch, or a frame's bits would; the
+// kernel zero-fills short tiles) and N from 64, everything else M >= 512 and N >= 96 (long 64-channel convolutions: N >= 64).
+static bool dma_ok(const lmx_gemm_desc& d, int m_min, int n_min) {
+  const bool a_ok = d.a_mode != 1 || (d.Cin % 32 == 0 && d.H < 32768 && d.W_ < 32768);  // (f32 out: the exact plan's pre-activations)
+  return a_ok && d.M >= m_min && d.N >= n_min && d.N % 8 == 0 && d.ldc % 8 == 0 && aligned16(d.C) &&
+         (!d.res || (d.ldr % 8 == 0 && aligned16(d.res)));
 }
 
-extern "C" int lmx_k_gemm(const lmx_gemm_desc* dp, lmx_stream_t stream) {
+// validation and kernel selection of lmx_k_gemm: a pure function of the descriptor and the development switches
+static int gemm_route(const lmx_gemm_desc* dp, GemmRoute& r) {
   LMX_REQUIRE(dp != nullptr, "lmx_k_gemm: null descriptor");
   const lmx_gemm_desc& d = *dp;
   LMX_REQUIRE(d.A && d.W && d.C, "lmx_k_gemm: null A/W/C");
@@ -327,45 +327,78 @@ extern "C" int lmx_k_gemm(const lmx_gemm_desc* dp, lmx_stream_t stream) {
                 "lmx_k_gemm: pooled rows need an even H x W token grid that divides M (H=%d W=%d M=%d)", d.H, d.W_, d.M);
     LMX_REQUIRE(!d.res && !d.scale && d.act == LMX_ACT_NONE, "lmx_k_gemm: pooled rows: no residual / scale / activation");
     LMX_REQUIRE(((int64_t)d.M * d.lda + d.K) * 2 < 0x7fffffffll, "lmx_k_gemm: pooled rows: A must be smaller than 2 GB");
-    LMX_REQUIRE(d.M >= 512 && d.N >= 96 && d.N % 8 == 0 && d.ldc % 8 == 0 && aligned16(d.C),
+    LMX_REQUIRE(dma_ok(d, 512, 96),
                 "lmx_k_gemm: pooled rows are built for the LDS-DMA kernel (M >= 512, N >= 96, N %% 8 == 0): use GEMM + maxpool2 for M=%d N=%d", d.M, d.N);
   } else {
     LMX_REQUIRE(false, "lmx_k_gemm: bad a_mode %d", d.a_mode);
   }
   LMX_REQUIRE(d.a_rep >= 0 && d.a_rep <= 3, "lmx_k_gemm: a_rep=%d (0..3)", d.a_rep);
   LMX_REQUIRE(d.split_k >= 0 && d.split_k <= 64, "lmx_k_gemm: split_k=%d (0..64)", d.split_k);
-  if (d.split_k > 1) {
-    LMX_REQUIRE(d.out_dtype == LMX_F32 && d.act == LMX_ACT_NONE && d.a_mode != 2 && d.a_rep <= 1, "lmx_k_gemm: split_k needs f32 output, no activation, a_mode 0 or 1");
-    LMX_REQUIRE(d.split_stride >= (int64_t)(d.M - 1) * d.ldc + d.N && d.split_stride % 4 == 0, "lmx_k_gemm: split_stride=%lld", (long long)d.split_stride);
-    LMX_REQUIRE((d.K + 63) / 64 >= d.split_k, "lmx_k_gemm: split_k=%d exceeds the k-tiles of K=%d", d.split_k, d.K);
-    const bool conv_ok2 = d.a_mode == 1 && d.Cin % 32 == 0 && d.H < 32768 && d.W_ < 32768;
-    // (any M: whether a layer is split must not depend on the batch, or a frame's bits would; the LDS-DMA kernel zero-fills short tiles)
-    LMX_REQUIRE((d.a_mode == 0 || conv_ok2) && d.N >= 64 && d.N % 8 == 0 && d.ldc % 8 == 0 && (!d.res || d.ldr % 8 == 0) &&
-                    aligned16(d.C) && (!d.res || aligned16(d.res)),
-                "lmx_k_gemm: split_k is built into the LDS-DMA kernel only (N >= 64, N %% 8 == 0; conv: Cin %% 32 == 0); M=%d N=%d", d.M, d.N);
-    return lmx_gemm2_launch(d, reinterpret_cast<hipStream_t>(stream));
-  }
-  if (d.a_rep > 1) {
-    LMX_REQUIRE(d.a_mode == 0 && d.K % d.a_rep == 0 && (d.K / d.a_rep) % 64 == 0, "lmx_k_gemm: a_rep=%d needs a_mode 0 and K / a_rep a multiple of 64 (K=%d)", d.a_rep, d.K);
-    LMX_REQUIRE(d.lda >= d.K / d.a_rep, "lmx_k_gemm: lda=%lld < K / a_rep", (long long)d.lda);
-    LMX_REQUIRE(d.M >= 512 && d.N >= 96 && d.N % 8 == 0 && d.ldc % 8 == 0 && (!d.res || d.ldr % 8 == 0) && aligned16(d.C) && (!d.res || aligned16(d.res)),
-                "lmx_k_gemm: a_rep is built into the LDS-DMA kernel only (M >= 512, N >= 96, N %% 8 == 0); M=%d N=%d", d.M, d.N);
-    return lmx_gemm2_launch(d, reinterpret_cast<hipStream_t>(stream));
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // large dense problems take the LDS-DMA 256x128 kernel (gemm2.hip); small / narrow ones and the conv generator stay here
-  const bool conv_ok = d.a_mode == 1 && d.Cin % 32 == 0 && d.H < 32768 && d.W_ < 32768;  // (f32 out: the exact plan's pre-activations)
-  if (d.a_mode == 2) return lmx_gemm2_launch(d, st);
+  static const int v1 = lmx_env_char("LMX_GEMM_V1") == '1';
   // (3 x 3 convolutions with 64 output channels — YOLOv8-l's first C2f stage and Detect's box branch: 2.3 M rows at 150 frames — also
   // take the LDS-DMA kernel: half of its 128-wide n-tile is zero-filled, but these launches are bound by A staging, not by the MFMA:
   // LMX_GEMM_N64=0 restores the register-staged kernel for them)
   static const int n64 = lmx_env_char("LMX_GEMM_N64") != '0';
-  const int n_min = (conv_ok && n64 && d.M >= 65536) ? 64 : 96;
-  if ((d.a_mode == 0 || conv_ok) && d.M >= 512 && d.N >= n_min && d.N % 8 == 0 && d.ldc % 8 == 0 && (!d.res || d.ldr % 8 == 0) &&
-      aligned16(d.C) && (!d.res || aligned16(d.res)) && !force_v1())
-    return lmx_gemm2_launch(d, st);
-  if (d.a_mode == 0) {
-    return d.out_dtype == LMX_F16 ? dispatch_tile<0, LMX_F16>(d, st) : dispatch_tile<0, LMX_F32>(d, st);
+  bool dma;
+  if (d.split_k > 1) {
+    LMX_REQUIRE(d.out_dtype == LMX_F32 && d.act == LMX_ACT_NONE && d.a_mode != 2 && d.a_rep <= 1, "lmx_k_gemm: split_k needs f32 output, no activation, a_mode 0 or 1");
+    LMX_REQUIRE(d.split_stride >= (int64_t)(d.M - 1) * d.ldc + d.N && d.split_stride % 4 == 0, "lmx_k_gemm: split_stride=%lld", (long long)d.split_stride);
+    LMX_REQUIRE((d.K + 63) / 64 >= d.split_k, "lmx_k_gemm: split_k=%d exceeds the k-tiles of K=%d", d.split_k, d.K);
+    LMX_REQUIRE(dma_ok(d, 1, 64),
+                "lmx_k_gemm: split_k is built into the LDS-DMA kernel only (N >= 64, N %% 8 == 0; conv: Cin %% 32 == 0); M=%d N=%d", d.M, d.N);
+    dma = true;
+  } else if (d.a_rep > 1) {
+    LMX_REQUIRE(d.a_mode == 0 && d.K % d.a_rep == 0 && (d.K / d.a_rep) % 64 == 0, "lmx_k_gemm: a_rep=%d needs a_mode 0 and K / a_rep a multiple of 64 (K=%d)", d.a_rep, d.K);
+    LMX_REQUIRE(d.lda >= d.K / d.a_rep, "lmx_k_gemm: lda=%lld < K / a_rep", (long long)d.lda);
+    LMX_REQUIRE(dma_ok(d, 512, 96),
+                "lmx_k_gemm: a_rep is built into the LDS-DMA kernel only (M >= 512, N >= 96, N %% 8 == 0); M=%d N=%d", d.M, d.N);
+    dma = true;
+  } else if (d.a_mode == 2) {
+    dma = true;  // (checked above: pooled rows have no register-staged form)
+  } else {
+    // large dense problems take the LDS-DMA kernel (gemm2.hip); small / narrow ones and the other convolutions stay here
+    dma = !v1 && dma_ok(d, 512, d.a_mode == 1 && n64 && d.M >= 65536 ? 64 : 96);
   }
-  return d.out_dtype == LMX_F16 ? dispatch_tile<1, LMX_F16>(d, st) : dispatch_tile<1, LMX_F32>(d, st);
+  if (dma) {
+    r = lmx_gemm2_tiling(d);
+  } else {
+    // narrow outputs (Detect head 64/80 channels, small stems) take the 128x64 tile
+    const bool narrow = d.N <= 64 || (d.N < 128 && d.N % 128 != 0);
+    r = GemmRoute{false, 128, narrow ? 64 : 128, BK, 2, 0};
+  }
+  return LMX_OK;
+}
+
+static constexpr int v1_key(int BN, int a_mode, int out_dtype) { return BN * 4 + a_mode * 2 + out_dtype; }
+
+extern "C" int lmx_k_gemm(const lmx_gemm_desc* dp, lmx_stream_t stream) {
+  GemmRoute r;
+  LMX_TRY(gemm_route(dp, r));
+  const lmx_gemm_desc& d = *dp;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (r.dma) return lmx_gemm2_launch(d, r, st);
+#define LMX_V1(BN, AMODE, OUT_DT) \
+  case v1_key(BN, AMODE, OUT_DT): return launch<128, BN, AMODE, OUT_DT>(d, st)
+  switch (v1_key(r.BN, d.a_mode, d.out_dtype)) {
+    LMX_V1(64, 0, LMX_F16);
+    LMX_V1(128, 0, LMX_F16);
+    LMX_V1(64, 0, LMX_F32);
+    LMX_V1(128, 0, LMX_F32);
+    LMX_V1(64, 1, LMX_F16);
+    LMX_V1(128, 1, LMX_F16);
+    LMX_V1(64, 1, LMX_F32);
+    LMX_V1(128, 1, LMX_F32);
+  }
+#undef LMX_V1
+  LMX_REQUIRE(false, "lmx_k_gemm: no register-staged kernel 128x%d for a_mode %d, out_dtype %d", r.BN, d.a_mode, d.out_dtype);
+}
+
+extern "C" int lmx_h_gemm_route(const lmx_gemm_desc* dp, char* name, int cap) {
+  GemmRoute r;
+  LMX_TRY(gemm_route(dp, r));
+  if (r.dma)
+    LMX_ROUTE_NAME(name, cap, "dma_%dx%dx%d_s%d%s", r.BM, r.BN, r.BK, r.NSTAGE, r.STAG ? "_stag" : "");
+  else
+    LMX_ROUTE_NAME(name, cap, "v1_%dx%d", r.BM, r.BN);
+  return LMX_OK;
 }

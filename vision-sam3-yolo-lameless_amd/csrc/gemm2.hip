@@ -556,70 +556,102 @@ int launch2(const lmx_gemm_desc& d, hipStream_t st) {
 }  // namespace lmx_gemm2
 using namespace lmx_gemm2;
 
-// called from lmx_k_gemm (gemm.hip) after validation, for a_mode 0.  LMX_GEMM2_VARIANT picks a tiling for experiments:
+// The tiling of a problem that gemm_route (gemm.hip) sends to this kernel: a pure function of the shape.  LMX_GEMM2_VARIANT picks a
+// dense tiling for experiments:
 //   A: 256x128x64, 3 slots (144 KB), 8 waves, 1 block/CU      B: 128x128x64, 2 slots (64 KB), 4 waves, 2 blocks/CU
 //   C: 256x128x32, 3 slots (72 KB), 8 waves, 2 blocks/CU      D: 256x128x32, 2 slots (48 KB), 8 waves, 3 blocks/CU
 static int g_variant = -1;  // -1: read LMX_GEMM2_VARIANT on first use; lmx_dbg_set_gemm2_variant overrides it (tools/gemm_sweep.py)
 extern "C" void lmx_dbg_set_gemm2_variant(int v) { g_variant = v; }
 
-int lmx_gemm2_launch(const lmx_gemm_desc& d, hipStream_t st) {
+static constexpr GemmRoute tiling(int BM, int BN, int BK, int NSTAGE, int STAG = 0) { return GemmRoute{true, BM, BN, BK, NSTAGE, STAG}; }
+
+GemmRoute lmx_gemm2_tiling(const lmx_gemm_desc& d) {
   if (g_variant < 0) g_variant = lmx_env_char("LMX_GEMM2_VARIANT");
-  const int variant = g_variant;
-  if (d.a_mode == 2) return launch2<256, 256, 64, 2, 2>(d, st);  // pooled rows (f32 out): one tiling
+  if (d.a_mode == 2) return tiling(256, 256, 64, 2);  // pooled rows: one tiling
   if (d.a_mode == 1) {  // 3x3 convolution, Cin % 32 == 0 (checked by the caller)
     static const int conv_small = lmx_env_set("LMX_GEMM2_CONV_SMALL");
     const int64_t t256 = (int64_t)((d.M + 255) / 256) * ((d.N + 255) / 256);
     const double q256 = (double)t256 / (double)(((t256 + 255) / 256) * 256);
-    if (!conv_small && d.N % 256 == 0 && t256 >= 230 && q256 >= 0.75) return launch2<256, 256, 32, 3, 1, 1>(d, st);
-    return launch2<256, 128, 32, 3, 1>(d, st);
+    if (!conv_small && d.N % 256 == 0 && t256 >= 230 && q256 >= 0.75) return tiling(256, 256, 32, 3, 1);
+    return tiling(256, 128, 32, 3);
   }
-  switch (variant) {
-    case 'A': return launch2<256, 128, 64, 3, 0>(d, st);
-    case 'B': return launch2<128, 128, 64, 2, 0>(d, st);
-    case 'C': return launch2<256, 128, 32, 3, 0>(d, st);
-    case 'D': return launch2<256, 128, 32, 2, 0>(d, st);
-    case 'E': return launch2<256, 256, 32, 3, 0>(d, st);  // 16 waves, 96 KB, 1 block/CU: half the L2->LDS bytes per flop
-    case 'F': return launch2<256, 256, 32, 4, 0>(d, st);  // ... 128 KB ring: three k-tiles in flight
-    case 'H': return launch2<128, 128, 32, 2, 0>(d, st);  // 4 waves, 32 KB: up to 4 blocks/CU for short-K (HBM-bound) shapes
-    case 'I': return launch2<128, 128, 32, 3, 0>(d, st);  // 4 waves, 48 KB: 3 blocks/CU
-    case 'S': return launch2<256, 128, 32, 6, 0, 1>(d, st);  // staggered wave groups, 6 x 24 KB ring, 1 block/CU
-    case 'T': return launch2<256, 128, 64, 3, 0, 1>(d, st);  // staggered, 3 x 48 KB ring
-    case 'U': return launch2<256, 128, 32, 3, 0, 1>(d, st);  // staggered, 3 x 24 KB ring, 2 blocks/CU
-    case 'V': return launch2<256, 128, 32, 4, 0, 1>(d, st);  // staggered, 4 x 24 KB ring
-    case 'W': return launch2<256, 256, 32, 4, 0, 1>(d, st);  // staggered 256x256, 16 waves, 4 x 32 KB ring
-    case 'Y': return launch2<256, 256, 32, 3, 0, 1>(d, st);  // staggered 256x256, 3 x 32 KB ring
-    case 'Z': return launch2<256, 256, 64, 2, 0>(d, st);     // 256x256x64, 2 x 64 KB: half the barriers, 128-byte DMA row pieces
-    default: {
-      // measured on the model shapes (profiles/r01_gemm_variants.txt, r01_gemm_staggered_variants.txt): with K < ~1.8k the
-      // per-tile prologue/epilogue dominates and two co-resident workgroups (C) hide it; long-K problems, and problems with
-      // no more tiles than CUs, prefer the staggered schedule on the 3 x 48 KB ring (T), one workgroup per CU
-      // 256 x 256 tiles (staggered, 16 waves, 3 x 32 KB ring, one workgroup per CU) move a third fewer L2->LDS bytes per
-      // flop and win 13-24 % where the tile grid wastes little (profiles/r01_gemm_staggered_variants.txt): N a multiple of
-      // 256 (or >= 85 % of its last tile when K >= 896 amortises the waste), at least ~one tile per CU, and a last round of
-      // tiles that is not mostly empty
-      const int64_t nt256 = (d.N + 255) / 256, tiles256 = (int64_t)((d.M + 255) / 256) * nt256;
-      const double nfrac = (double)d.N / (double)(nt256 * 256);
-      const double q256 = (double)tiles256 / (double)(((tiles256 + 255) / 256) * 256);
-      // The rules below were re-derived with COLD A operands (tools/gemm_sweep.py LMX_SWEEP_COLD=1: buffer sets rotated so that
-      // the A operands alone exceed the 256 MB Infinity Cache).  A loop over one buffer set keeps A cache-resident and
-      // flatters the 256 x 128 tiling, which re-reads A twice as often: the qkv GEMM of Hiera stage 3 (N = 1344) measures 176 us
-      // that way with 256 x 128 and 181 with 256 x 256, but 235 vs 199 us behind the LayerNorm that produces its input, as in
-      // the model (tools/gemm_context_probe.py, profiles/r02_gemm_cold_sweep.txt).
-      if (d.K >= 448 && tiles256 >= 200 && q256 >= 0.75 && nfrac >= 0.85) {
-        // 64-deep k-tiles on a 2 x 64 KB ring (half the barriers, 128-byte DMA row pieces): 4-5 % ahead of the staggered
-        // 32-deep schedule at K >= 1792 (profiles/r02_gemm_sweep_interleaved.txt, variant Z) and, since the epilogue resolves
-        // the activation per tile, 2-5 % ahead at K = 448 .. 1024 too (fc1 of Hiera stage 3 274 vs 289 us, DINO fc1 260 vs 265;
-        // profiles/r02_gemm_epilogue.txt).  Eight waves of 128 x 64 on the same ring (a quarter fewer fragment reads) measured
-        // 4-7 % BEHIND sixteen of 64 x 64 on every model shape: the k-loop is not bound by LDS read volume.
-        return launch2<256, 256, 64, 2, 0>(d, st);
-      }
-      // short K, N = 224 .. 1536 filling >= 85 % of its 256-wide tiles (Hiera's 224 / 448 / 672 / 896 / 1344 with K = 112, 224):
-      // 256 x 256 tiles move a third fewer L2->LDS bytes per flop than 256 x 128 and win 5-15 % cold; K = 224 prefers the
-      // 32-deep 3-slot ring (N = 1344: 502 vs 518 us), K = 112 the 64-deep one (N = 672: 809 vs 841 us)
-      if (d.K < 448 && d.N >= 224 && d.N <= 1536 && d.N % 256 != 0 && nfrac >= 0.85 && tiles256 >= 200 && q256 >= 0.75)
-        return d.K > 128 ? launch2<256, 256, 32, 3, 0>(d, st) : launch2<256, 256, 64, 2, 0>(d, st);
-      const int64_t tiles = (int64_t)((d.M + 255) / 256) * ((d.N + 127) / 128);
-      return (d.K >= 1792 || tiles <= 256) ? launch2<256, 128, 64, 3, 0, 1>(d, st) : launch2<256, 128, 32, 3, 0>(d, st);
-    }
+  switch (g_variant) {
+    case 'A': return tiling(256, 128, 64, 3);
+    case 'B': return tiling(128, 128, 64, 2);
+    case 'C': return tiling(256, 128, 32, 3);
+    case 'D': return tiling(256, 128, 32, 2);
+    case 'E': return tiling(256, 256, 32, 3);  // 16 waves, 96 KB, 1 block/CU: half the L2->LDS bytes per flop
+    case 'F': return tiling(256, 256, 32, 4);  // ... 128 KB ring: three k-tiles in flight
+    case 'H': return tiling(128, 128, 32, 2);  // 4 waves, 32 KB: up to 4 blocks/CU for short-K (HBM-bound) shapes
+    case 'I': return tiling(128, 128, 32, 3);  // 4 waves, 48 KB: 3 blocks/CU
+    case 'S': return tiling(256, 128, 32, 6, 1);  // staggered wave groups, 6 x 24 KB ring, 1 block/CU
+    case 'T': return tiling(256, 128, 64, 3, 1);  // staggered, 3 x 48 KB ring
+    case 'U': return tiling(256, 128, 32, 3, 1);  // staggered, 3 x 24 KB ring, 2 blocks/CU
+    case 'V': return tiling(256, 128, 32, 4, 1);  // staggered, 4 x 24 KB ring
+    case 'W': return tiling(256, 256, 32, 4, 1);  // staggered 256x256, 16 waves, 4 x 32 KB ring
+    case 'Y': return tiling(256, 256, 32, 3, 1);  // staggered 256x256, 3 x 32 KB ring
+    case 'Z': return tiling(256, 256, 64, 2);     // 256x256x64, 2 x 64 KB: half the barriers, 128-byte DMA row pieces
   }
+  // measured on the model shapes (profiles/r01_gemm_variants.txt, r01_gemm_staggered_variants.txt): with K < ~1.8k the
+  // per-tile prologue/epilogue dominates and two co-resident workgroups (C) hide it; long-K problems, and problems with
+  // no more tiles than CUs, prefer the staggered schedule on the 3 x 48 KB ring (T), one workgroup per CU
+  // 256 x 256 tiles (staggered, 16 waves, 3 x 32 KB ring, one workgroup per CU) move a third fewer L2->LDS bytes per
+  // flop and win 13-24 % where the tile grid wastes little (profiles/r01_gemm_staggered_variants.txt): N a multiple of
+  // 256 (or >= 85 % of its last tile when K >= 896 amortises the waste), at least ~one tile per CU, and a last round of
+  // tiles that is not mostly empty
+  const int64_t nt256 = (d.N + 255) / 256, tiles256 = (int64_t)((d.M + 255) / 256) * nt256;
+  const double nfrac = (double)d.N / (double)(nt256 * 256);
+  const double q256 = (double)tiles256 / (double)(((tiles256 + 255) / 256) * 256);
+  // The rules below were re-derived with COLD A operands (tools/gemm_sweep.py LMX_SWEEP_COLD=1: buffer sets rotated so that
+  // the A operands alone exceed the 256 MB Infinity Cache).  A loop over one buffer set keeps A cache-resident and
+  // flatters the 256 x 128 tiling, which re-reads A twice as often: the qkv GEMM of Hiera stage 3 (N = 1344) measures 176 us
+  // that way with 256 x 128 and 181 with 256 x 256, but 235 vs 199 us behind the LayerNorm that produces its input, as in
+  // the model (tools/gemm_context_probe.py, profiles/r02_gemm_cold_sweep.txt).
+  if (d.K >= 448 && tiles256 >= 200 && q256 >= 0.75 && nfrac >= 0.85) {
+    // 64-deep k-tiles on a 2 x 64 KB ring (half the barriers, 128-byte DMA row pieces): 4-5 % ahead of the staggered
+    // 32-deep schedule at K >= 1792 (profiles/r02_gemm_sweep_interleaved.txt, variant Z) and, since the epilogue resolves
+    // the activation per tile, 2-5 % ahead at K = 448 .. 1024 too (fc1 of Hiera stage 3 274 vs 289 us, DINO fc1 260 vs 265;
+    // profiles/r02_gemm_epilogue.txt).  Eight waves of 128 x 64 on the same ring (a quarter fewer fragment reads) measured
+    // 4-7 % BEHIND sixteen of 64 x 64 on every model shape: the k-loop is not bound by LDS read volume.
+    return tiling(256, 256, 64, 2);
+  }
+  // short K, N = 224 .. 1536 filling >= 85 % of its 256-wide tiles (Hiera's 224 / 448 / 672 / 896 / 1344 with K = 112, 224):
+  // 256 x 256 tiles move a third fewer L2->LDS bytes per flop than 256 x 128 and win 5-15 % cold; K = 224 prefers the
+  // 32-deep 3-slot ring (N = 1344: 502 vs 518 us), K = 112 the 64-deep one (N = 672: 809 vs 841 us)
+  if (d.K < 448 && d.N >= 224 && d.N <= 1536 && d.N % 256 != 0 && nfrac >= 0.85 && tiles256 >= 200 && q256 >= 0.75)
+    return d.K > 128 ? tiling(256, 256, 32, 3) : tiling(256, 256, 64, 2);
+  const int64_t tiles = (int64_t)((d.M + 255) / 256) * ((d.N + 127) / 128);
+  return (d.K >= 1792 || tiles <= 256) ? tiling(256, 128, 64, 3, 1) : tiling(256, 128, 32, 3);
+}
+
+// one case per instantiation: the tiling and the A generator (0 dense, 1 3x3 convolution, 2 pooled rows)
+static constexpr int64_t tiling_key(int BM, int BN, int BK, int NSTAGE, int a_mode, int STAG) {
+  return ((((int64_t)BM * 1024 + BN) * 1024 + BK) * 16 + NSTAGE) * 16 + a_mode * 2 + STAG;
+}
+
+int lmx_gemm2_launch(const lmx_gemm_desc& d, const GemmRoute& r, hipStream_t st) {
+#define LMX_T(BM, BN, BK, NSTAGE, AMODE, STAG) \
+  case tiling_key(BM, BN, BK, NSTAGE, AMODE, STAG): return launch2<BM, BN, BK, NSTAGE, AMODE, STAG>(d, st)
+  switch (tiling_key(r.BM, r.BN, r.BK, r.NSTAGE, d.a_mode, r.STAG)) {
+    LMX_T(256, 256, 64, 2, 2, 0);
+    LMX_T(256, 256, 32, 3, 1, 1);
+    LMX_T(256, 128, 32, 3, 1, 0);
+    LMX_T(256, 128, 64, 3, 0, 0);
+    LMX_T(128, 128, 64, 2, 0, 0);
+    LMX_T(256, 128, 32, 3, 0, 0);
+    LMX_T(256, 128, 32, 2, 0, 0);
+    LMX_T(256, 256, 32, 3, 0, 0);
+    LMX_T(256, 256, 32, 4, 0, 0);
+    LMX_T(128, 128, 32, 2, 0, 0);
+    LMX_T(128, 128, 32, 3, 0, 0);
+    LMX_T(256, 128, 32, 6, 0, 1);
+    LMX_T(256, 128, 64, 3, 0, 1);
+    LMX_T(256, 128, 32, 3, 0, 1);
+    LMX_T(256, 128, 32, 4, 0, 1);
+    LMX_T(256, 256, 32, 4, 0, 1);
+    LMX_T(256, 256, 32, 3, 0, 1);
+    LMX_T(256, 256, 64, 2, 0, 0);
+  }
+#undef LMX_T
+  LMX_REQUIRE(false, "lmx_k_gemm: no LDS-DMA kernel %dx%dx%d, %d slots, staggered %d for a_mode %d", r.BM, r.BN, r.BK, r.NSTAGE, r.STAG, d.a_mode);
 }

@@ -285,8 +285,17 @@ inline int grid_for(int64_t total, int block = 256) {
 
 }  // namespace
 
-extern "C" int lmx_k_layernorm(const void* x, int in_dtype, int64_t ldx, const float* gamma, const float* beta,
-                               void* y, int out_dtype, int64_t ldy, int rows, int D, float eps, int act, lmx_stream_t stream) {
+// The kernel lmx_k_layernorm launches: eight narrow rows per wave pass (D <= 128), several rows per wave of a ViT width (many rows,
+// f32 -> f16, no activation), or one row per wave; ITERS float4 per lane cover the row.
+enum LnKernel { LN_NARROW, LN_ROWS, LN_ROW };
+struct LnRoute {
+  LnKernel kernel;
+  int ITERS;
+};
+
+// validation and kernel selection of lmx_k_layernorm: a pure function of its arguments and the development switch
+static int ln_route(const void* x, int in_dtype, int64_t ldx, const float* gamma, const float* beta, const void* y, int out_dtype,
+                    int64_t ldy, int rows, int D, int act, LnRoute& r) {
   LMX_REQUIRE(x && y && gamma && beta, "lmx_k_layernorm: null pointer");
   LMX_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 4096, "lmx_k_layernorm: rows=%d D=%d (need D%%4==0, D<=4096)", rows, D);
   LMX_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, "lmx_k_layernorm: strides");
@@ -294,56 +303,74 @@ extern "C" int lmx_k_layernorm(const void* x, int in_dtype, int64_t ldx, const f
   LMX_REQUIRE(aligned16(gamma) && aligned16(beta), "lmx_k_layernorm: gamma/beta alignment");
   LMX_REQUIRE((((uintptr_t)x) & (in_dtype == LMX_F32 ? 15 : 7)) == 0, "lmx_k_layernorm: x alignment");
   LMX_REQUIRE((((uintptr_t)y) & (out_dtype == LMX_F32 ? 15 : 7)) == 0, "lmx_k_layernorm: y alignment");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (D <= 128) {
-    dim3 g8((rows + 7) / 8), b256(256);
-    if (in_dtype == LMX_F32 && out_dtype == LMX_F16)
-      hipLaunchKernelGGL((layernorm_narrow_kernel<LMX_F32, LMX_F16>), g8, b256, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps, act);
-    else if (in_dtype == LMX_F32 && out_dtype == LMX_F32)
-      hipLaunchKernelGGL((layernorm_narrow_kernel<LMX_F32, LMX_F32>), g8, b256, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps, act);
-    else if (in_dtype == LMX_F16 && out_dtype == LMX_F16)
-      hipLaunchKernelGGL((layernorm_narrow_kernel<LMX_F16, LMX_F16>), g8, b256, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps, act);
-    else if (in_dtype == LMX_F16 && out_dtype == LMX_F32)
-      hipLaunchKernelGGL((layernorm_narrow_kernel<LMX_F16, LMX_F32>), g8, b256, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps, act);
-    else
-      LMX_REQUIRE(false, "lmx_k_layernorm: bad dtypes %d -> %d", in_dtype, out_dtype);
-    return lmx_launch_check("layernorm_narrow_kernel");
-  }
-  dim3 grid((rows + 3) / 4), block(256);
+  LMX_REQUIRE((in_dtype == LMX_F32 || in_dtype == LMX_F16) && (out_dtype == LMX_F32 || out_dtype == LMX_F16),
+              "lmx_k_layernorm: bad dtypes %d -> %d", in_dtype, out_dtype);
   // many rows of a ViT width, f32 stream -> f16: the several-rows-per-wave form (LMX_LN_ONE_ROW=1: the one-row-per-wave kernel)
   static const int one_row = lmx_env_set("LMX_LN_ONE_ROW");
-  if (!one_row && rows >= 16384 && act == LMX_ACT_NONE && in_dtype == LMX_F32 && out_dtype == LMX_F16 && D <= 1024) {
-    dim3 g2(256 * 8);  // eight workgroups of four waves per CU, each wave walking rows / 8192 rows
-    if (D <= 512)
-      hipLaunchKernelGGL((layernorm_rows_kernel<LMX_F32, LMX_F16, 2>), g2, block, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps);
-    else
-      hipLaunchKernelGGL((layernorm_rows_kernel<LMX_F32, LMX_F16, 4>), g2, block, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps);
-    return lmx_launch_check("layernorm_rows_kernel");
-  }
-#define LMX_LN(IN, OUT, IT) \
-  hipLaunchKernelGGL((layernorm_kernel<IN, OUT, IT>), grid, block, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps, act)
-#define LMX_LN_IT(IN, OUT)        \
-  do {                            \
-    if (D <= 512)                 \
-      LMX_LN(IN, OUT, 2);         \
-    else if (D <= 1024)           \
-      LMX_LN(IN, OUT, 4);         \
-    else                          \
-      LMX_LN(IN, OUT, 16);        \
-  } while (0)
-  if (in_dtype == LMX_F32 && out_dtype == LMX_F16)
-    LMX_LN_IT(LMX_F32, LMX_F16);
-  else if (in_dtype == LMX_F32 && out_dtype == LMX_F32)
-    LMX_LN_IT(LMX_F32, LMX_F32);
-  else if (in_dtype == LMX_F16 && out_dtype == LMX_F16)
-    LMX_LN_IT(LMX_F16, LMX_F16);
-  else if (in_dtype == LMX_F16 && out_dtype == LMX_F32)
-    LMX_LN_IT(LMX_F16, LMX_F32);
+  r.ITERS = D <= 512 ? 2 : D <= 1024 ? 4 : 16;
+  if (D <= 128)
+    r.kernel = LN_NARROW;
+  else if (!one_row && rows >= 16384 && act == LMX_ACT_NONE && in_dtype == LMX_F32 && out_dtype == LMX_F16 && D <= 1024)
+    r.kernel = LN_ROWS;
   else
-    LMX_REQUIRE(false, "lmx_k_layernorm: bad dtypes %d -> %d", in_dtype, out_dtype);
-#undef LMX_LN_IT
-#undef LMX_LN
-  return lmx_launch_check("layernorm_kernel");
+    r.kernel = LN_ROW;
+  return LMX_OK;
+}
+
+// one case per instantiation
+static constexpr int ln_key(int kernel, int in_dtype, int out_dtype, int ITERS) { return ((kernel * 2 + in_dtype) * 2 + out_dtype) * 32 + ITERS; }
+
+extern "C" int lmx_k_layernorm(const void* x, int in_dtype, int64_t ldx, const float* gamma, const float* beta,
+                               void* y, int out_dtype, int64_t ldy, int rows, int D, float eps, int act, lmx_stream_t stream) {
+  LnRoute r;
+  LMX_TRY(ln_route(x, in_dtype, ldx, gamma, beta, y, out_dtype, ldy, rows, D, act, r));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 block(256);
+  // narrow: 8 rows per wave pass | rows: eight workgroups of four waves per CU, each wave walking rows / 8192 rows | row: a wave per row
+  const dim3 grid(r.kernel == LN_NARROW ? (rows + 7) / 8 : r.kernel == LN_ROWS ? 256 * 8 : (rows + 3) / 4);
+#define LMX_LN_NARROW(IN, OUT)        \
+  case ln_key(LN_NARROW, IN, OUT, 2): \
+    hipLaunchKernelGGL((layernorm_narrow_kernel<IN, OUT>), grid, block, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps, act); break
+#define LMX_LN_ROWS(IT)                       \
+  case ln_key(LN_ROWS, LMX_F32, LMX_F16, IT): \
+    hipLaunchKernelGGL((layernorm_rows_kernel<LMX_F32, LMX_F16, IT>), grid, block, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps); break
+#define LMX_LN_ROW(IN, OUT, IT)      \
+  case ln_key(LN_ROW, IN, OUT, IT): \
+    hipLaunchKernelGGL((layernorm_kernel<IN, OUT, IT>), grid, block, 0, st, x, ldx, gamma, beta, y, ldy, rows, D, eps, act); break
+#define LMX_LN_ROW3(IN, OUT) \
+  LMX_LN_ROW(IN, OUT, 2);    \
+  LMX_LN_ROW(IN, OUT, 4);    \
+  LMX_LN_ROW(IN, OUT, 16)
+  switch (ln_key(r.kernel, in_dtype, out_dtype, r.kernel == LN_NARROW ? 2 : r.ITERS)) {
+    LMX_LN_NARROW(LMX_F32, LMX_F16);
+    LMX_LN_NARROW(LMX_F32, LMX_F32);
+    LMX_LN_NARROW(LMX_F16, LMX_F16);
+    LMX_LN_NARROW(LMX_F16, LMX_F32);
+    LMX_LN_ROWS(2);
+    LMX_LN_ROWS(4);
+    LMX_LN_ROW3(LMX_F32, LMX_F16);
+    LMX_LN_ROW3(LMX_F32, LMX_F32);
+    LMX_LN_ROW3(LMX_F16, LMX_F16);
+    LMX_LN_ROW3(LMX_F16, LMX_F32);
+    default: LMX_REQUIRE(false, "lmx_k_layernorm: no kernel for route %d, %d float4 per lane", (int)r.kernel, r.ITERS);
+  }
+#undef LMX_LN_NARROW
+#undef LMX_LN_ROWS
+#undef LMX_LN_ROW
+#undef LMX_LN_ROW3
+  static const char* const what[] = {"layernorm_narrow_kernel", "layernorm_rows_kernel", "layernorm_kernel"};
+  return lmx_launch_check(what[r.kernel]);
+}
+
+extern "C" int lmx_h_layernorm_route(int in_dtype, int out_dtype, int rows, int D, int act, char* name, int cap) {
+  alignas(16) static const float dummy[4] = {};  // stands for x, y, gamma and beta: the route checks pointers for null and alignment only
+  LnRoute r;
+  LMX_TRY(ln_route(dummy, in_dtype, D, dummy, dummy, dummy, out_dtype, D, rows, D, act, r));
+  if (r.kernel == LN_NARROW)
+    LMX_ROUTE_NAME(name, cap, "narrow");
+  else
+    LMX_ROUTE_NAME(name, cap, "%s_it%d", r.kernel == LN_ROWS ? "rows" : "row", r.ITERS);
+  return LMX_OK;
 }
 
 extern "C" int lmx_k_assemble_tokens(const void* patch_f16, const float* prefix, const float* pos, float* out, int B,

@@ -54,6 +54,74 @@ def _rows(t, what):
     return t.shape[0], t.shape[1], t.stride(0)
 
 
+# ---- which kernel a launch would take (lmx_h_*_route, include/lmx.h).  lmx_k_gemm, lmx_k_attention and lmx_k_layernorm choose their
+# kernel from sizes that grow with the batch; these ask the library's own selection for shapes, without tensors and without a GPU.
+_ROUTE_PTR = 4096  # stands for every operand: the route functions check pointers for null and alignment only, and never follow them
+
+
+def _route_name(fn, *args):
+    name = C.create_string_buffer(64)
+    check(fn(*args, name, len(name)), fn.__name__)
+    return name.value.decode()
+
+
+def gemm_route(M, N, K, *, out_dtype=torch.float16, act=ACT_NONE, scale=False, res=False, res_rows=0, a_rep=1, pool_hw=None,
+               lda=None, ldc=None, ldr=None):
+    """The kernel gemm() launches for a [M, K] x [N, a_rep * K] problem (scale, res: whether one is given; lda / ldc / ldr default
+    to dense rows): 'v1_128x64', 'dma_256x128x64_s3_stag', ...; LmxError where gemm() raises it."""
+    d = GemmDesc()
+    d.A = d.W = d.C = d.bias = _ROUTE_PTR
+    d.scale = _ROUTE_PTR if scale else None
+    d.res = _ROUTE_PTR if res else None
+    d.M, d.N, d.K = M, N, a_rep * K
+    d.lda = K if lda is None else lda
+    d.ldc = (N // 2 if act == ACT_SWIGLU else N) if ldc is None else ldc
+    d.ldr = (N if ldr is None else ldr) if res else 0
+    d.res_rows, d.a_rep = res_rows, a_rep
+    d.act, d.out_dtype, d.a_mode = act, _DT[out_dtype], 0
+    if pool_hw:
+        d.a_mode, d.H, d.W_ = 2, int(pool_hw[0]), int(pool_hw[1])
+    return _route_name(_lib.load().lmx_h_gemm_route, C.byref(d))
+
+
+def conv3x3_route(n, H, W, cin, cout, *, stride=1, out_dtype=torch.float16, act=ACT_SILU, res=False, scale=False, split_k=1):
+    """The kernel conv3x3() launches for n dense NHWC frames of H x W x cin."""
+    Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+    d = GemmDesc()
+    d.A = d.W = d.C = d.bias = _ROUTE_PTR
+    d.scale = _ROUTE_PTR if scale else None
+    d.res = _ROUTE_PTR if res else None
+    d.lda, d.ldc, d.ldr = cin, cout, (cout if res else 0)
+    d.M, d.N, d.K = n * Ho * Wo, cout, 9 * cin
+    d.act, d.out_dtype, d.a_mode = act, _DT[out_dtype], 1
+    d.H, d.W_, d.Cin, d.conv_stride, d.Ho, d.Wo = H, W, cin, stride, Ho, Wo
+    if split_k > 1:
+        d.split_k, d.split_stride = split_k, n * Ho * Wo * cout
+    return _route_name(_lib.load().lmx_h_gemm_route, C.byref(d))
+
+
+def attention_route(B, H, Tq, Tk, hd, *, window=None, pad=False, rel_S=0, ld=None):
+    """The kernel attention() launches (window as there; pad: whether pad_k and pad_v are given; rel_S > 0: with the
+    relative-position tables of an S x S grid; ld: the row stride of q / k / v / out, H * hd if None)."""
+    d = AttnDesc()
+    d.Q = d.K = d.V = d.O = _ROUTE_PTR
+    d.ldq = d.ldk = d.ldv = d.ldo = H * hd if ld is None else ld
+    d.B, d.H, d.Tq, d.Tk, d.hd = B, H, Tq, Tk, hd
+    d.scale = 1.0
+    if window is not None:
+        d.mode = 1
+        d.Gh, d.Gw, d.ws, d.q_stride = window["Gh"], window["Gw"], window["ws"], window.get("q_stride", 1)
+        d.pad_k = d.pad_v = _ROUTE_PTR if pad else None
+    if rel_S:
+        d.rel, d.rel_S = _ROUTE_PTR, rel_S
+    return _route_name(_lib.load().lmx_h_attn_route, C.byref(d))
+
+
+def layernorm_route(rows, D, in_dtype=torch.float32, out_dtype=torch.float16, act=ACT_NONE):
+    """The kernel layernorm() launches: 'narrow', 'rows_it2', 'row_it16', ..."""
+    return _route_name(_lib.load().lmx_h_layernorm_route, _DT[in_dtype], _DT[out_dtype], rows, D, act)
+
+
 def pooled_gemm_ok(M, N):
     """Shapes lmx_k_gemm's pooled-row mode (a_mode 2) is built for (the LDS-DMA kernel); smaller ones take GEMM + maxpool2."""
     return M >= 512 and N >= 96 and N % 8 == 0
