@@ -97,6 +97,19 @@ typedef struct {
    * (lmx_k_split3's `nsum`): deterministic, unlike atomics.  0 / 1: no split. */
   int32_t split_k;
   int64_t split_stride;
+  /* the LayerNorm that reads the result, from the same launch (ln_out != NULL): besides C, the kernel writes
+   *   ln_out[m][n] = f16( (C[m][n] - mean_m) * rstd_m * ln_gamma[n] + ln_beta[n] ),  rstd_m = 1 / sqrt(var_m + ln_eps)
+   * (f16 [M][N], row stride ld_ln) from the f32 values it stores to C: mean first, then the centred squares, both summed in
+   * lmx_k_layernorm's order — the bits of lmx_k_layernorm on C without the second pass over it.  A workgroup must hold whole
+   * rows for this, so the request has a kernel of its own (route dma_128xrow_ln: 128 rows x N tiles) FOR EVERY M — a layer's
+   * choice, never the batch's — and only for: f32 C with a residual (no res_rows), N <= 448, N%16==0, K <= 448, a_mode 0, no
+   * activation / scale / a_rep / split_k.  C's bits are those of the same descriptor without ln_out.  Any other request that
+   * carries ln_out is LMX_EINVAL.  (Hiera stage 3: the attention projection writes layer_norm2's rows.) */
+  void* ln_out;
+  const float* ln_gamma; /* [N], 16-byte aligned */
+  const float* ln_beta;  /* [N], 16-byte aligned */
+  int64_t ld_ln;
+  float ln_eps;
 } lmx_gemm_desc;
 int lmx_k_gemm(const lmx_gemm_desc* d, lmx_stream_t stream);
 /* development hook (tools/gemm_sweep.py): force one tiling of the LDS-DMA GEMM for every following launch; v = 0 restores
@@ -109,7 +122,7 @@ void lmx_dbg_set_gemm2_variant(int v);
  * An invalid descriptor returns what the launcher returns for it, with the same lmx_last_error text; otherwise LMX_OK and, in
  * name[cap], the route: the kernel and the template arguments of the instantiation, e.g.
  *   GEMM        v1_128x64 (register-staged, BM x BN) | dma_256x256x64_s2, dma_256x128x64_s3_stag (LDS-DMA: BM x BN x BK, ring slots,
- *               staggered wave groups)
+ *               staggered wave groups) | dma_128xrow_ln (ln_out: 128 rows x the whole row)
  *   attention   small | sp_qb2_ones | spp_dot2 | gp4_ones | tiled_q2_dot2_rel_hd64, tiled_q2_ones_dma_hd64 (ones / dot2: how the
  *               row sums are taken; q: 16-query blocks per wave; hd: the LDS row class)
  *   LayerNorm   narrow | rows_it2 | row_it16 (it: float4 per lane)

@@ -66,10 +66,12 @@ int lmx_env_char(const char* name);
 // pure host function (gemm_route, attn_route, ln_route: no HIP call, nothing read behind the descriptor's pointers) and launch in
 // another, which holds one switch from the route to the instantiation; lmx_h_*_route return the route's name without a GPU.
 // the kernel of a GEMM: the register-staged gemm_kernel (gemm.hip; BM x BN x 64, two LDS buffers) or the LDS-DMA gemm2_kernel
-// (gemm2.hip) with its tiling
+// (gemm2.hip) with its tiling; rowln: gemm2_rowln_kernel, 128 rows x the whole row with the next LayerNorm in its epilogue
+// (lmx_gemm_desc.ln_out)
 struct GemmRoute {
   bool dma;
   int BM, BN, BK, NSTAGE, STAG;
+  bool rowln = false;
 };
 // a route's name into the caller's buffer (the lmx_h_*_route entry points only: no launch formats a string)
 #define LMX_ROUTE_NAME(name, cap, ...)                                                                          \

@@ -339,6 +339,19 @@ static int gemm_route(const lmx_gemm_desc* dp, GemmRoute& r) {
   // take the LDS-DMA kernel: half of its 128-wide n-tile is zero-filled, but these launches are bound by A staging, not by the MFMA:
   // LMX_GEMM_N64=0 restores the register-staged kernel for them)
   static const int n64 = lmx_env_char("LMX_GEMM_N64") != '0';
+  if (d.ln_out) {
+    // the next LayerNorm from this launch (lmx.h): a kernel of its own whose tile is 128 whole rows, for EVERY M — which layers ask
+    // for it is the plan's choice, so a frame's bits do not depend on its batch — and for nothing but the shapes it was built for
+    LMX_REQUIRE(d.out_dtype == LMX_F32 && d.res && d.res_rows == 0, "lmx_k_gemm: ln_out needs f32 output with a full residual (out_dtype=%d res_rows=%d)", d.out_dtype, d.res_rows);
+    LMX_REQUIRE(d.N <= 448 && d.N % 16 == 0 && d.K <= 448, "lmx_k_gemm: ln_out: a tile holds whole rows of N <= 448 (N %% 16 == 0) over K <= 448; N=%d K=%d", d.N, d.K);
+    LMX_REQUIRE(d.a_mode == 0 && d.a_rep <= 1 && d.split_k <= 1, "lmx_k_gemm: ln_out: dense A only (a_mode=%d a_rep=%d split_k=%d)", d.a_mode, d.a_rep, d.split_k);
+    LMX_REQUIRE(d.act == LMX_ACT_NONE && !d.scale, "lmx_k_gemm: ln_out takes no activation and no scale");
+    LMX_REQUIRE(d.ln_gamma && d.ln_beta && aligned16(d.ln_gamma) && aligned16(d.ln_beta), "lmx_k_gemm: ln_gamma / ln_beta must be given, 16-byte aligned");
+    LMX_REQUIRE(d.ld_ln % 4 == 0 && d.ld_ln >= d.N && (((uintptr_t)d.ln_out) & 7) == 0, "lmx_k_gemm: ln_out must be 8-byte aligned with ld_ln=%lld a multiple of 4, >= N", (long long)d.ld_ln);
+    LMX_REQUIRE(aligned16(d.res), "lmx_k_gemm: ln_out: the residual must be 16-byte aligned");
+    r = GemmRoute{true, 128, 448, BK, 2, 0, true};
+    return LMX_OK;
+  }
   bool dma;
   if (d.split_k > 1) {
     LMX_REQUIRE(d.out_dtype == LMX_F32 && d.act == LMX_ACT_NONE && d.a_mode != 2 && d.a_rep <= 1, "lmx_k_gemm: split_k needs f32 output, no activation, a_mode 0 or 1");
@@ -396,7 +409,9 @@ extern "C" int lmx_k_gemm(const lmx_gemm_desc* dp, lmx_stream_t stream) {
 extern "C" int lmx_h_gemm_route(const lmx_gemm_desc* dp, char* name, int cap) {
   GemmRoute r;
   LMX_TRY(gemm_route(dp, r));
-  if (r.dma)
+  if (r.rowln)
+    LMX_ROUTE_NAME(name, cap, "dma_128xrow_ln");
+  else if (r.dma)
     LMX_ROUTE_NAME(name, cap, "dma_%dx%dx%d_s%d%s", r.BM, r.BN, r.BK, r.NSTAGE, r.STAG ? "_stag" : "");
   else
     LMX_ROUTE_NAME(name, cap, "v1_%dx%d", r.BM, r.BN);

@@ -553,6 +553,226 @@ int launch2(const lmx_gemm_desc& d, hipStream_t st) {
   return lmx_launch_check("gemm2_kernel");
 }
 
+// ---- 128 rows x the WHOLE row (N <= 448), with the LayerNorm that reads the result (lmx_gemm_desc.ln_out; route dma_128xrow_ln).
+// The 256 x 256 tiles above split a 448-wide row between two workgroups, so the LayerNorm that follows a residual GEMM had to read
+// the f32 stream back.  Here a workgroup owns its rows: 8 waves as 2(m) x 4(n), 64 x 112 = 4 x 7 MFMA fragments each, the k-loop of
+// gemm2_kernel (same LDS image and swizzle, 64-deep k-tiles in ascending order on a 2 x 72 KB ring: the accumulators are the bits of
+// every other tiling), then an epilogue in four passes of 32 rows through the idle ring: the waves transpose their fragments (+ bias)
+// into f32 rows, and each wave takes 4 whole rows as lmx_k_layernorm's kernels hold them (lane L: columns 4L.. and 256 + 4L..) —
+// adds the residual, stores the f32 row, reduces mean and centred variance in layernorm_rows_kernel's order (norm.hip: per-lane
+// partials, xor butterfly 32 .. 1 — no M, no tile index enters) and stores the f16 LayerNorm row.
+constexpr int RL_BM = 128, RL_BN = 448, RL_BK = 64, RL_NSTAGE = 2;
+constexpr int RL_STAGE_BYTES = (RL_BM + RL_BN) * RL_BK * 2;  // 72 KB
+constexpr int RL_RS = RL_BN + 4;                             // floats per LDS row of the epilogue (the pad of the 64-wide transposer)
+constexpr int RL_SMEM = RL_NSTAGE * RL_STAGE_BYTES + 3 * RL_BN * 4;  // ring + bias / gamma / beta
+static_assert(2 * 32 * RL_RS * 4 <= RL_NSTAGE * RL_STAGE_BYTES, "two 32-row epilogue buffers inside the ring");
+
+// wave_sum (common.h) of four values at once: the same xor butterfly per value, the four chains interleaved
+__device__ __forceinline__ void wave_sum4(float (&v)[4]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    float t[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t[r] = __shfl_xor(v[r], o, 64);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] += t[r];
+  }
+}
+
+__global__ __launch_bounds__(512) void gemm2_rowln_kernel(const lmx_gemm_desc p) {
+  constexpr int BM = RL_BM, BN = RL_BN, BK = RL_BK, NSTAGE = RL_NSTAGE, STAGE_BYTES = RL_STAGE_BYTES;
+  constexpr int NWAVE = 8;
+  constexpr int A_INSTR = BM * BK * 2 / 1024 / NWAVE;  // 2 LDS-DMA wave-instructions (1 KB = 8 rows each) per wave per k-tile
+  constexpr int W_INSTR = BN * BK * 2 / 1024 / NWAVE;  // 7
+  constexpr int FJ = BN / 4 / 16;                     // 7 fragments of 16 channels per wave
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave & 1, wn = wave >> 1;
+  const int swz = blockIdx.x;  // one tile per workgroup, W (<= 392 KB) is every tile's: no tile order to choose
+  const int m0 = swz * BM;
+  TL(0, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));
+  TL(1, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20));
+  TL(2, wall_clock64());
+  TL(5, (unsigned long long)swz);
+
+  const char* Ab = reinterpret_cast<const char*>(p.A) + (int64_t)m0 * p.lda * 2;
+  int64_t a_bytes = ((int64_t)(p.M - m0 - 1) * p.lda + p.K) * 2;
+  if (a_bytes > 0x7FFFFFF0ll) a_bytes = 0x7FFFFFF0ll;
+  const int w_bytes = p.N * p.K * 2;  // (<= 448 x 448 halfs)
+  const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Ab), 0, (int)a_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, w_bytes, 0x00020000);
+
+  // (the LDS image, the source-side swizzle and the K tail: gemm2_kernel)
+  const int lrow = lane >> 3;
+  const int lchunk = (lane & 7) ^ lrow;
+  unsigned a_off[A_INSTR], w_off[W_INSTR];
+#pragma unroll
+  for (int j = 0; j < A_INSTR; ++j) a_off[j] = (unsigned)(((wave * A_INSTR + j) * 8 + lrow) * (int)p.lda * 2 + lchunk * 16);
+#pragma unroll
+  for (int j = 0; j < W_INSTR; ++j) w_off[j] = (unsigned)(((wave * W_INSTR + j) * 8 + lrow) * p.K * 2 + lchunk * 16);  // rows >= N: past w_bytes, zero
+  const unsigned OOB = 0x80000000u;
+  const int nk = (p.K + BK - 1) / BK;
+  const bool k_tail_lane = (nk - 1) * BK + lchunk * 8 >= p.K;
+  auto issue = [&](int kt, int slot) {
+    char* st = smem + slot * STAGE_BYTES;
+    const bool kill = (kt == nk - 1) && k_tail_lane;
+    const int soff = kt * (BK * 2);
+#pragma unroll
+    for (int j = 0; j < A_INSTR; ++j) lds_dma16(a_rs, st + (wave * A_INSTR + j) * 1024, kill ? OOB : a_off[j], soff);
+#pragma unroll
+    for (int j = 0; j < W_INSTR; ++j) lds_dma16(w_rs, st + BM * BK * 2 + (wave * W_INSTR + j) * 1024, kill ? OOB : w_off[j], soff);
+  };
+
+  f32x4 acc[4][FJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // bias and the LayerNorm's gamma / beta: requested now, parked in LDS behind the ring after the k-loop
+  float* bl = reinterpret_cast<float*>(smem + NSTAGE * STAGE_BYTES);  // [3][BN]
+  float bias_v = 0.f, gamma_v = 0.f, beta_v = 0.f;
+  if (tid < p.N) {
+    if (p.bias) bias_v = p.bias[tid];
+    gamma_v = p.ln_gamma[tid];
+    beta_v = p.ln_beta[tid];
+  }
+
+  issue(0, 0);
+  const int frow = lane & 15, fq = lane >> 4;
+  const int fsw = frow & 7;
+  for (int kt = 0; kt < nk; ++kt) {
+    wait_vmcnt<0>();  // (a 2-slot ring has one k-tile in flight: nothing younger than the tile that must have landed)
+    __builtin_amdgcn_s_barrier();
+    if (kt + 1 < nk) issue(kt + 1, (kt + 1) % NSTAGE);
+    const char* st = smem + (kt % NSTAGE) * STAGE_BYTES;
+    const half_t* as = reinterpret_cast<const half_t*>(st) + (wm * 64 + frow) * BK;
+    const half_t* ws = reinterpret_cast<const half_t*>(st + BM * BK * 2) + (wn * (BN / 4) + frow) * BK;
+#pragma unroll
+    for (int ks = 0; ks < BK / 32; ++ks) {
+      const int coff = (((ks << 2) + fq) ^ fsw) << 3;
+      half8_t af[4], wf[FJ];
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) wf[j] = *reinterpret_cast<const half8_t*>(ws + j * 16 * BK + coff);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const half8_t*>(as + i * 16 * BK + coff);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < FJ; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[j], af[i], acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
+  }
+
+  if (tid < BN) {
+    bl[tid] = bias_v;
+    bl[BN + tid] = gamma_v;
+    bl[2 * BN + tid] = beta_v;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // a raw s_barrier does not wait for this wave's LDS writes
+  __builtin_amdgcn_s_barrier();  // every wave is done reading the last k-tile; bias / gamma / beta are in LDS
+  TL(3, wall_clock64());
+
+  // ---- epilogue.  Pass ps takes the fragment row ps of every wave: rows wm * 64 + ps * 16 + (0 .. 15) of the tile, 32 rows, in one
+  // of two LDS buffers (pass ps + 1 writes the other one, whose readers of pass ps - 1 are behind the barrier of pass ps).
+  const int D = p.N;
+  const int c0 = lane * 4, c1 = (64 + lane) * 4;  // this lane's columns of a row: layernorm_rows_kernel's, 2 float4 per lane
+  const bool ok0 = c0 < D, ok1 = c1 < D;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 g0 = ok0 ? *reinterpret_cast<const f32x4*>(bl + BN + c0) : z4, g1 = ok1 ? *reinterpret_cast<const f32x4*>(bl + BN + c1) : z4;
+  const f32x4 b0 = ok0 ? *reinterpret_cast<const f32x4*>(bl + 2 * BN + c0) : z4, b1 = ok1 ? *reinterpret_cast<const f32x4*>(bl + 2 * BN + c1) : z4;
+  const float* blj = bl + wn * (BN / 4) + fq * 4;
+  const float* res = reinterpret_cast<const float*>(p.res);
+  float* Cf = reinterpret_cast<float*>(p.C);
+  half_t* Lh = reinterpret_cast<half_t*>(p.ln_out);
+#pragma unroll
+  for (int ps = 0; ps < 4; ++ps) {
+    float* buf = reinterpret_cast<float*>(smem) + (ps & 1) * 32 * RL_RS;
+    // this wave's 4 rows of the pass: LDS rows wave * 4 + (0 .. 3); their residual is requested before the transposition
+    f32x4 r0[4], r1[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int lr = wave * 4 + rr;
+      const int m = m0 + (lr >> 4) * 64 + ps * 16 + (lr & 15);
+      r0[rr] = r1[rr] = z4;
+      if (m < p.M) {
+        if (ok0) r0[rr] = *reinterpret_cast<const f32x4*>(res + (int64_t)m * p.ldr + c0);
+        if (ok1) r1[rr] = *reinterpret_cast<const f32x4*>(res + (int64_t)m * p.ldr + c1);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < FJ; ++j)
+      *reinterpret_cast<f32x4*>(buf + (wm * 16 + frow) * RL_RS + wn * (BN / 4) + j * 16 + fq * 4) = acc[ps][j] + *reinterpret_cast<const f32x4*>(blj + j * 16);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // (the four rows side by side: a row's two reductions are twelve dependent cross-lane steps, and eight waves per CU have nobody
+    // else to hide them behind)
+    f32x4 v0[4], v1[4];
+    float s[4], q[4], mean[4], rstd[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int lr = wave * 4 + rr;
+      // (branch-free: a lane without columns reads column 0 and drops it)
+      const f32x4 t0 = *reinterpret_cast<const f32x4*>(buf + lr * RL_RS + (ok0 ? c0 : 0)), t1 = *reinterpret_cast<const f32x4*>(buf + lr * RL_RS + (ok1 ? c1 : 0));
+      v0[rr] = (ok0 ? t0 : z4) + r0[rr];  // (acc + bias) + residual: the rounding sequence of every f32 epilogue
+      v1[rr] = (ok1 ? t1 : z4) + r1[rr];
+      // LayerNorm of the row as written: the arithmetic of layernorm_rows_kernel<F32, F16, 2> (norm.hip), expression for expression
+      // (a lane without columns holds zeros and adds 0 where that kernel adds nothing)
+      s[rr] = 0.f;
+      s[rr] += (v0[rr][0] + v0[rr][1]) + (v0[rr][2] + v0[rr][3]);
+      s[rr] += (v1[rr][0] + v1[rr][1]) + (v1[rr][2] + v1[rr][3]);
+    }
+    wave_sum4(s);
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      mean[rr] = s[rr] / (float)D;
+      q[rr] = 0.f;
+      {
+        const f32x4 dlt = v0[rr] - mean[rr];
+        const float t = (dlt[0] * dlt[0] + dlt[1] * dlt[1]) + (dlt[2] * dlt[2] + dlt[3] * dlt[3]);
+        q[rr] += ok0 ? t : 0.f;
+      }
+      {
+        const f32x4 dlt = v1[rr] - mean[rr];
+        const float t = (dlt[0] * dlt[0] + dlt[1] * dlt[1]) + (dlt[2] * dlt[2] + dlt[3] * dlt[3]);
+        q[rr] += ok1 ? t : 0.f;
+      }
+    }
+    wave_sum4(q);
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int lr = wave * 4 + rr;
+      const int m = m0 + (lr >> 4) * 64 + ps * 16 + (lr & 15);
+      rstd[rr] = 1.0f / sqrtf(q[rr] / (float)D + p.ln_eps);
+      if (m < p.M) {  // (wave-uniform)
+        if (ok0) *reinterpret_cast<f32x4*>(Cf + (int64_t)m * p.ldc + c0) = v0[rr];
+        if (ok1) *reinterpret_cast<f32x4*>(Cf + (int64_t)m * p.ldc + c1) = v1[rr];
+        if (ok0) {
+          const f32x4 o = (v0[rr] - mean[rr]) * rstd[rr] * g0 + b0;
+          *reinterpret_cast<half4_t*>(Lh + (int64_t)m * p.ld_ln + c0) = half4_t{(half_t)o[0], (half_t)o[1], (half_t)o[2], (half_t)o[3]};
+        }
+        if (ok1) {
+          const f32x4 o = (v1[rr] - mean[rr]) * rstd[rr] * g1 + b1;
+          *reinterpret_cast<half4_t*>(Lh + (int64_t)m * p.ld_ln + c1) = half4_t{(half_t)o[0], (half_t)o[1], (half_t)o[2], (half_t)o[3]};
+        }
+      }
+    }
+  }
+  TL(4, wall_clock64());
+}
+
+int launch_rowln(const lmx_gemm_desc& d, hipStream_t st) {
+  int dev;
+  LMX_TRY(lmx_stream_device(st, &dev));
+  LMX_TRY(lmx_allow_lds(reinterpret_cast<const void*>(&gemm2_rowln_kernel), RL_SMEM, dev));
+  hipLaunchKernelGGL(gemm2_rowln_kernel, dim3((d.M + RL_BM - 1) / RL_BM), dim3(512), RL_SMEM, st, d);
+  return lmx_launch_check("gemm2_rowln_kernel");
+}
+
 }  // namespace lmx_gemm2
 using namespace lmx_gemm2;
 
@@ -630,6 +850,7 @@ static constexpr int64_t tiling_key(int BM, int BN, int BK, int NSTAGE, int a_mo
 }
 
 int lmx_gemm2_launch(const lmx_gemm_desc& d, const GemmRoute& r, hipStream_t st) {
+  if (r.rowln) return launch_rowln(d, st);
 #define LMX_T(BM, BN, BK, NSTAGE, AMODE, STAG) \
   case tiling_key(BM, BN, BK, NSTAGE, AMODE, STAG): return launch2<BM, BN, BK, NSTAGE, AMODE, STAG>(d, st)
   switch (tiling_key(r.BM, r.BN, r.BK, r.NSTAGE, d.a_mode, r.STAG)) {

@@ -23,6 +23,7 @@ class GemmDesc(C.Structure):
         ("act", C.c_int32), ("out_dtype", C.c_int32), ("a_mode", C.c_int32),
         ("H", C.c_int32), ("W_", C.c_int32), ("Cin", C.c_int32), ("conv_stride", C.c_int32),
         ("Ho", C.c_int32), ("Wo", C.c_int32), ("res_rows", C.c_int32), ("a_rep", C.c_int32), ("split_k", C.c_int32), ("split_stride", C.c_int64),
+        ("ln_out", C.c_void_p), ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ld_ln", C.c_int64), ("ln_eps", C.c_float),
     ]
 
 

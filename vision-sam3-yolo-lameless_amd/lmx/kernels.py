@@ -66,9 +66,10 @@ def _route_name(fn, *args):
 
 
 def gemm_route(M, N, K, *, out_dtype=torch.float16, act=ACT_NONE, scale=False, res=False, res_rows=0, a_rep=1, pool_hw=None,
-               lda=None, ldc=None, ldr=None):
-    """The kernel gemm() launches for a [M, K] x [N, a_rep * K] problem (scale, res: whether one is given; lda / ldc / ldr default
-    to dense rows): 'v1_128x64', 'dma_256x128x64_s3_stag', ...; LmxError where gemm() raises it."""
+               lda=None, ldc=None, ldr=None, ln_out=False, split_k=1):
+    """The kernel gemm() launches for a [M, K] x [N, a_rep * K] problem (scale, res, ln_out: whether one is given; lda / ldc / ldr
+    default to dense rows; split_k: the descriptor's, for the rules that refuse it): 'v1_128x64', 'dma_256x128x64_s3_stag',
+    'dma_128xrow_ln', ...; LmxError where gemm() raises it."""
     d = GemmDesc()
     d.A = d.W = d.C = d.bias = _ROUTE_PTR
     d.scale = _ROUTE_PTR if scale else None
@@ -81,6 +82,11 @@ def gemm_route(M, N, K, *, out_dtype=torch.float16, act=ACT_NONE, scale=False, r
     d.act, d.out_dtype, d.a_mode = act, _DT[out_dtype], 0
     if pool_hw:
         d.a_mode, d.H, d.W_ = 2, int(pool_hw[0]), int(pool_hw[1])
+    if ln_out:
+        d.ln_out = d.ln_gamma = d.ln_beta = _ROUTE_PTR
+        d.ld_ln, d.ln_eps = N, 1e-6
+    if split_k > 1:
+        d.split_k, d.split_stride = split_k, M * d.ldc
     return _route_name(_lib.load().lmx_h_gemm_route, C.byref(d))
 
 
@@ -127,7 +133,8 @@ def pooled_gemm_ok(M, N):
     return M >= 512 and N >= 96 and N % 8 == 0
 
 
-def gemm(a, w, bias=None, act=ACT_NONE, scale=None, res=None, out=None, out_dtype=torch.float16, res_rows=0, pool_hw=None, a_rep=1):
+def gemm(a, w, bias=None, act=ACT_NONE, scale=None, res=None, out=None, out_dtype=torch.float16, res_rows=0, pool_hw=None, a_rep=1,
+         ln_out=None):
     """out[M,N] = res + scale * act(a[M,K] @ w[N,K]^T + bias)   (lmx_k_gemm, a_mode 0).
     a_rep > 1: w is [N, a_rep*K] and a's K columns are walked a_rep times (w = [whi | wlo]: f16 activations against 22-bit
     weights in one launch).
@@ -136,8 +143,11 @@ def gemm(a, w, bias=None, act=ACT_NONE, scale=None, res=None, out=None, out_dtyp
     grid, [M/4, N] in [n, H/2, W/2] order (a_mode 2: the bits of gemm(...) followed by maxpool2, without the full-size
     intermediate).
     act=ACT_SWIGLU: w [2I, K] and bias [2I] hold gate and up rows interleaved by 16 (lmx.dino.pack_gated); the result is
-    scale * silu(gate) * up with N/2 = I columns (scale [I]); f16 out, no residual."""
-    dev = _dev(a, w, bias, scale, res, out)
+    scale * silu(gate) * up with N/2 = I columns (scale [I]); f16 out, no residual.
+    ln_out=(h, gamma, beta, eps): the same launch also writes h = LayerNorm(out) as f16 [M, N] (gamma, beta f32 [N]) from the f32
+    rows it stores — the bits of layernorm(out, gamma, beta, eps) without its pass over out.  A kernel of its own at every M, for
+    an f32 result with a residual, N <= 448 and K <= 448 only (lmx_gemm_desc.ln_out, include/lmx.h); anything else raises."""
+    dev = _dev(a, w, bias, scale, res, out, *(ln_out[:3] if ln_out is not None else ()))
     M, K, lda = _rows(a, "gemm A")
     N, K2, ldw = _rows(w, "gemm W")
     if K2 != a_rep * K or ldw != K2:
@@ -170,6 +180,14 @@ def gemm(a, w, bias=None, act=ACT_NONE, scale=None, res=None, out=None, out_dtyp
     d.act, d.out_dtype, d.a_mode, d.a_rep = act, _DT[out.dtype], 0, a_rep
     if pool_hw:
         d.a_mode, d.H, d.W_ = 2, int(pool_hw[0]), int(pool_hw[1])
+    if ln_out is not None:
+        h, g, b, eps = ln_out
+        Mh, Nh, ldh = _rows(h, "gemm ln_out")
+        if (Mh, Nh) != (Mout, Nout) or h.dtype != torch.float16:
+            raise LmxError(f"gemm: ln_out must be float16 [{Mout},{Nout}], got {h.dtype} {tuple(h.shape)}")
+        if any(t.dtype != torch.float32 or t.numel() != Nout or not t.is_contiguous() for t in (g, b)):
+            raise LmxError("gemm: ln_out's gamma and beta must be contiguous float32 [N]")
+        d.ln_out, d.ln_gamma, d.ln_beta, d.ld_ln, d.ln_eps = h.data_ptr(), g.data_ptr(), b.data_ptr(), ldh, float(eps)
     check(_lib.load().lmx_k_gemm(C.byref(d), _stream(dev)), "lmx_k_gemm")
     return out
 
@@ -991,8 +1009,9 @@ def _work(name, args):
         if d.a_mode == 1:  # 3x3 implicit GEMM: the input image is read once, not 9 times
             a_bytes = 2 * (M // max(d.Ho * d.Wo, 1)) * d.H * d.W_ * d.Cin
         by = a_bytes + 2 * N * Kd + osz * (M // 4 if d.a_mode == 2 else M) * (N // 2 if d.act == ACT_SWIGLU else N) + (osz * (d.res_rows or M) * N if d.res else 0)
+        by += 2 * M * N if d.ln_out else 0  # the f16 LayerNorm rows of the same launch
         fl = 2.0 * M * N * Kd
-        key = f"gemm M={M} N={N} K={Kd} out={'f32' if osz == 4 else 'f16'} conv3x3={d.a_mode} act={d.act} res={int(bool(d.res))}"
+        key = f"gemm M={M} N={N} K={Kd} out={'f32' if osz == 4 else 'f16'} conv3x3={d.a_mode} act={d.act} res={int(bool(d.res))}" + (" ln_out" if d.ln_out else "")
         return ("gemm/mfma-bound" if fl / by >= RIDGE_FLOP_PER_BYTE else "gemm/hbm-bound"), fl, by, key
     if name == "lmx_k_attention":
         d = args[0]._obj

@@ -336,6 +336,9 @@ class HieraEncoder:
                     np.asarray(sd[p + "proj.weight"], np.float32), np.asarray(sd[p + "proj.bias"], np.float32),
                     np.asarray(sd[p + "attn.qkv.weight"], np.float32), np.asarray(qkv_b, np.float32),
                     np.asarray(sd[p + "attn.proj.weight"], np.float32), np.asarray(sd[p + "attn.proj.bias"], np.float32), heads))
+            # stage 3 of Hiera-B+ after its opening block (separate launches): the projection's tile holds whole 448-wide rows and writes
+            # layer_norm2's rows with the residual stream (K.gemm ln_out).  The layer's choice, whatever the batch
+            blk["proj_ln"] = dim == dim_out == 448 and not qs and not (self.fused_mlp and dim_out in K.FUSED_MLP_WIDTHS)
             self.blocks.append(blk)
         for i, blk in enumerate(self.blocks):  # the fused MLP's operands as LDS images, with the NEXT block's layer_norm1 vectors
             if blk["dim_out"] in (112, 224) and self.fused_mlp:
@@ -388,6 +391,7 @@ class HieraEncoder:
         for i, B in enumerate(self.blocks):
             dim, D, heads, qs = B["dim"], B["dim_out"], B["heads"], B["qs"]
             rows = n * H * W
+            h2 = None
             if self._attn8(i, H, W):  # [layer_norm1 ->] qkv -> window attention -> proj + residual in one launch (csrc/hiera.hip)
                 if B["attn8_ln"]:
                     K.hiera_attn8(x, B["attn8"], n, H, W, heads, ln=(B["g1"], B["b1"], cfg.eps))
@@ -413,7 +417,7 @@ class HieraEncoder:
                     res = sc
                 else:
                     res = x
-                x, H, W = self._attention_half(B, h, x, res, n, H, W)
+                x, H, W, h2 = self._attention_half(B, h, x, res, n, H, W)
             h_next = None
             x16 = None
             if D in K.FUSED_MLP_WIDTHS and self.fused_mlp:
@@ -428,7 +432,8 @@ class HieraEncoder:
                 else:
                     K.ln_mlp(x, B["g2"], B["b2"], B["w1"], B["bb1"], B["w2"], B["bb2"], cfg.eps, x16=x16, next_ln=nxt)  # one pass over x (csrc/mlp.hip)
             else:
-                h2 = K.layernorm(x, B["g2"], B["b2"], cfg.eps)
+                if h2 is None:  # (else: written by the attention projection, proj_ln)
+                    h2 = K.layernorm(x, B["g2"], B["b2"], cfg.eps)
                 u = K.gemm(h2, B["w1"], bias=B["bb1"], act=K.ACT_GELU)
                 K.gemm(u, B["w2"], bias=B["bb2"], res=x, out=x)
             if i in stage_ends:
@@ -444,7 +449,8 @@ class HieraEncoder:
         return "attn8" in B and B["dim"] == B["dim_out"] and K.hiera_attn8_ok(B["dim_out"], B["heads"], B["win"], H, W, B["qs"])
 
     def _attention_half(self, B, h, x, res, n, H, W):
-        """qkv GEMM -> [Q-pool] -> attention -> proj GEMM + residual as separate launches; returns (x, H, W) after the block's pooling."""
+        """qkv GEMM -> [Q-pool] -> attention -> proj GEMM + residual as separate launches; returns (x, H, W) after the block's pooling
+        and layer_norm2(x) where the projection wrote it (B["proj_ln"]), else None."""
         D, heads, win, qs = B["dim_out"], B["heads"], B["win"], B["qs"]
         hd = D // heads
         rows = n * H * W
@@ -475,8 +481,9 @@ class HieraEncoder:
         else:
             K.attention(q, k, v, a, n, heads, Hq * Wq, H * W, hd, hd ** -0.5)
         xo = torch.empty((n * Hq * Wq, D), dtype=torch.float32, device=dev) if res is not x else x
-        K.gemm(a, B["wo"], bias=B["bo"], res=res, out=xo)
-        return xo, Hq, Wq
+        h2 = torch.empty((n * Hq * Wq, D), dtype=torch.float16, device=dev) if B["proj_ln"] else None
+        K.gemm(a, B["wo"], bias=B["bo"], res=res, out=xo, ln_out=(h2, B["g2"], B["b2"], self.cfg.eps) if B["proj_ln"] else None)
+        return xo, Hq, Wq, h2
 
     def fpn(self, stages, stages16=None):
         cfg = self.cfg
