@@ -396,6 +396,21 @@ int lmx_k_maxpool2(const void* src, int64_t lds, void* dst, int64_t ldd, int dty
 /* f32 -> f16 row-wise convert (stage outputs of the f32 residual stream feeding the FPN 1x1 convs). */
 int lmx_k_cast_f32_f16(const float* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int cols,
                        lmx_stream_t stream);
+/* The band of token rows of a Hiera trunk that depends on the frame.  A frame resized to nh x nw sits at the top-left of the zero
+ * canvas (4 * grid pixels a side); until the first global-attention block, tokens mix only inside windows and 2 x 2 pools, so a
+ * token whose windows never reach a real pixel has a value that the weights alone decide.  window[i] / q_stride[i], i < n_blocks: the
+ * block plan (window 0 = global attention, q_stride 2 = the block pools its queries; a block's windows tile the grid it READS).
+ * *band = the number of stage-1 token rows (of `grid`) that the blocks in front of the first global one must compute per frame:
+ * the smallest count that covers every row whose 7 x 7 / stride 4 / pad 3 patch touches a pixel row < nh — (nh + 2) / 4 + 1 rows —
+ * and is a whole number of windows (and of pooled pairs) of each of those blocks at that block's resolution; 56 * ceil(.. / 56) for
+ * Hiera-B+.  *band = 0 (no band: compute the whole grid) when that count is the whole grid or more, when block 0 is global or no
+ * block is, and when nw < 4 * grid (padding on the right: columns are not cut).  Pure host arithmetic: no HIP call. */
+int lmx_h_hiera_band(const int* window, const int* q_stride, int n_blocks, int grid, int nh, int nw, int* band);
+/* out [n][H][W][D] = rows < Hb of each image from band [n][Hb][W][D], rows >= Hb from table [(H - Hb) * W][D], the same for every
+ * image: the frame-dependent band of a Hiera token grid (lmx_h_hiera_band) joined with its constant rows.  dtype f16 or f32, dense
+ * operands; a row of D elements must be a multiple of 16 bytes and 1 <= Hb <= H - 1. */
+int lmx_k_band_join(const void* band, const void* table, void* out, int dtype, int n, int H, int Hb, int W, int D,
+                    lmx_stream_t stream);
 
 /* ---- SAM mask decoder glue (TF:models/sam/modeling_sam.py:432-543; K18/K19) --------------------------------------- */
 /* out[r][:] = a[r][:] + b[r % b_rows][:]  (a, b f32; out f32 or f16): queries + point embeddings, keys + image PE,

@@ -92,6 +92,15 @@ __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ src
   }
 }
 
+// blockIdx.y = image; a thread moves 16-byte chunks: the first `cb` chunks of the image come from its band, the rest from the table
+// every image shares (lmx_k_band_join).  ci / cb: chunks of one whole image / of its band
+__global__ __launch_bounds__(256) void band_join_kernel(const u32x4* __restrict__ band, const u32x4* __restrict__ table,
+                                                        u32x4* __restrict__ out, int64_t ci, int64_t cb) {
+  const u32x4* bsrc = band + (int64_t)blockIdx.y * cb;
+  u32x4* o = out + (int64_t)blockIdx.y * ci;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ci; i += (int64_t)gridDim.x * blockDim.x)
+    o[i] = i < cb ? bsrc[i] : table[i - cb];
+}
 
 // out[r] = a[r] + b[r % b_rows]
 template <int IN_DT, int OUT_DT>
@@ -386,6 +395,62 @@ extern "C" int lmx_k_cast_f32_f16(const float* src, int64_t lds, void* dst, int6
   hipLaunchKernelGGL(cast_kernel, dim3(grid_for(rows * (cols / 4))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, lds,
                      reinterpret_cast<half_t*>(dst), ldd, rows, cols);
   return lmx_launch_check("cast_kernel");
+}
+
+// The rows of a Hiera token grid that depend on the frame (include/lmx.h).  `unit`: stage-1 rows of the smallest piece that is whole
+// windows (and whole pooled pairs) at every block in front of the first global one; `scale`: stage-1 rows per token row of the grid
+// the block reads.  Host arithmetic only.
+extern "C" int lmx_h_hiera_band(const int* window, const int* q_stride, int n_blocks, int grid, int nh, int nw, int* band) {
+  LMX_REQUIRE(window && q_stride && band, "lmx_h_hiera_band: null pointer");
+  LMX_REQUIRE(n_blocks > 0 && grid > 0 && grid <= (1 << 20) && nh > 0 && nw > 0 && nh <= 4 * grid && nw <= 4 * grid,
+              "lmx_h_hiera_band: n_blocks=%d grid=%d nh=%d nw=%d", n_blocks, grid, nh, nw);
+  *band = 0;
+  if (nw < 4 * grid) return LMX_OK;  // padding on the right: the band is a cut of rows only
+  int64_t unit = 1, scale = 1;
+  int first_global = -1;
+  for (int i = 0; i < n_blocks; ++i) {
+    LMX_REQUIRE(window[i] >= 0 && (q_stride[i] == 0 || q_stride[i] == 1 || q_stride[i] == 2), "lmx_h_hiera_band: block %d: window=%d q_stride=%d",
+                i, window[i], q_stride[i]);
+    if (window[i] == 0) {
+      first_global = i;
+      break;
+    }
+    const int64_t pieces[2] = {window[i] * scale, q_stride[i] == 2 ? 2 * scale : scale};
+    for (int64_t p : pieces) {
+      int64_t a = unit, b = p;  // unit = lcm(unit, p)
+      while (b) {
+        const int64_t t = a % b;
+        a = b;
+        b = t;
+      }
+      unit = unit / a * p;
+    }
+    if (unit >= grid) return LMX_OK;  // not even one piece is less than the grid
+    if (q_stride[i] == 2) scale *= 2;
+  }
+  if (first_global <= 0) return LMX_OK;  // block 0 mixes every token, or no block does and nothing marks where the band would end
+  const int64_t d1 = (nh + 2) / 4 + 1;  // token row r reads pixel rows 4 r - 3 .. 4 r + 3
+  const int64_t b = (d1 + unit - 1) / unit * unit;
+  if (b < grid) *band = (int)b;
+  return LMX_OK;
+}
+
+extern "C" int lmx_k_band_join(const void* band, const void* table, void* out, int dtype, int n, int H, int Hb, int W, int D,
+                               lmx_stream_t stream) {
+  LMX_REQUIRE(band && table && out, "lmx_k_band_join: null pointer");
+  LMX_REQUIRE(dtype == LMX_F16 || dtype == LMX_F32, "lmx_k_band_join: dtype %d", dtype);
+  LMX_REQUIRE(n > 0 && n <= 65535 && H > 0 && W > 0 && D > 0, "lmx_k_band_join: n=%d H=%d W=%d D=%d", n, H, W, D);
+  LMX_REQUIRE(Hb >= 1 && Hb <= H - 1, "lmx_k_band_join: Hb=%d outside 1 .. H - 1 = %d", Hb, H - 1);
+  const int64_t row_bytes = (int64_t)D * (dtype == LMX_F32 ? 4 : 2);
+  LMX_REQUIRE(row_bytes % 16 == 0, "lmx_k_band_join: a row of %lld bytes is not a multiple of 16", (long long)row_bytes);
+  LMX_REQUIRE(aligned16(band) && aligned16(table) && aligned16(out), "lmx_k_band_join: alignment");
+  const int64_t ci = (int64_t)H * W * (row_bytes / 16), cb = (int64_t)Hb * W * (row_bytes / 16);
+  int gx = grid_for(ci);
+  const int cap = 256 * 32 / n > 0 ? 256 * 32 / n : 1;  // ~32 workgroups per CU over all images
+  if (gx > cap) gx = cap;
+  hipLaunchKernelGGL(band_join_kernel, dim3(gx, n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const u32x4*>(band), reinterpret_cast<const u32x4*>(table), reinterpret_cast<u32x4*>(out), ci, cb);
+  return lmx_launch_check("band_join_kernel");
 }
 
 extern "C" int lmx_k_prompt_box(const float* boxes, int64_t ldb, float* sparse, int n, double sx, double sy, float S,

@@ -239,7 +239,7 @@ class LmxSamPredictor:
         self.is_image_set = False
         # the embedding is a static buffer of the capture (valid until the next set_image: the predictor's own contract); the
         # decoder's outputs are copied to the host before predict returns
-        self._g_encode = GraphedFn(lambda f: self.encoder.encode(f)["fpn"][2], clone_outputs=False)
+        self._g_encode = GraphedFn(lambda f: self.encoder.encode(f, outputs="embedding")["fpn"][2], clone_outputs=False)
         self._g_decode = {}  # (original_size, input_size) -> GraphedFn(features, box)
 
     @classmethod

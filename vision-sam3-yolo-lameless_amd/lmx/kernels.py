@@ -226,6 +226,34 @@ def cast_f16(x, out=None):
     return out
 
 
+def hiera_band(windows, q_strides, grid, nh, nw):
+    """Stage-1 token rows of a Hiera trunk that depend on a frame resized to nh x nw on its 4 * grid canvas, 0 = no band
+    (lmx_h_hiera_band, include/lmx.h: host arithmetic, no GPU).  windows / q_strides: the block plan, window 0 = global attention."""
+    nb = len(windows)
+    if nb != len(q_strides):
+        raise LmxError("hiera_band: windows and q_strides must be the same length")
+    band = C.c_int(0)
+    check(_lib.load().lmx_h_hiera_band((C.c_int * nb)(*windows), (C.c_int * nb)(*q_strides), nb, grid, nh, nw, C.byref(band)),
+          "lmx_h_hiera_band")
+    return band.value
+
+
+def band_join(band, table, H):
+    """[n, H, W, D]: rows < Hb of each image from band [n, Hb, W, D], rows >= Hb from table [(H - Hb) * W, D], the same for every
+    image (lmx_k_band_join).  f16 or f32, contiguous."""
+    dev = _dev(band, table)
+    if band.dim() != 4 or table.dim() != 2 or not band.is_contiguous() or not table.is_contiguous():
+        raise LmxError("band_join: band must be contiguous [n, Hb, W, D] and table contiguous [(H - Hb) * W, D]")
+    n, Hb, W, D = band.shape
+    if band.dtype not in _DT or table.dtype != band.dtype or tuple(table.shape) != ((H - Hb) * W, D):
+        raise LmxError(f"band_join: table {table.dtype} {tuple(table.shape)} does not hold rows {Hb} .. {H - 1} of a {band.dtype} "
+                       f"[{H}, {W}, {D}] grid")
+    out = torch.empty((n, H, W, D), dtype=band.dtype, device=band.device)
+    check(_lib.load().lmx_k_band_join(_ptr(band), _ptr(table), _ptr(out), _DT[band.dtype], n, H, Hb, W, D, _stream(dev)),
+          "lmx_k_band_join")
+    return out
+
+
 def _nhwc(t, what):
     """[n,H,W,C] view of (a channel slice of) a dense NHWC buffer; returns (n,H,W,C,pixel_stride)."""
     if t.dim() != 4 or t.stride(3) != 1:
@@ -1058,6 +1086,9 @@ def _work(name, args):
     if name == "lmx_k_add_bcast":
         a_dt, o_dt, rows, D = args[1], args[7], args[9], args[10]
         return "streaming glue", 0.0, rows * D * ((4 if a_dt == F32 else 2) + (4 if o_dt == F32 else 2)), f"add_bcast rows={rows} D={D}"
+    if name == "lmx_k_band_join":
+        dt, n_, H, Hb, W, D = args[3:9]
+        return "streaming glue", 0.0, 2 * (4 if dt == F32 else 2) * n_ * H * W * D, f"band_join n={n_} H={H} Hb={Hb} W={W} D={D} dtype={dt}"
     if name == "lmx_k_rope":
         B, T, H, hd = args[2], args[3], args[4], args[5]
         return "streaming glue", 0.0, 2 * 2 * 2 * B * T * H * hd, f"rope B={B} T={T} H={H} hd={hd}"  # q and k, read + written, f16

@@ -139,7 +139,7 @@ class FusedExtractor:
         masks, stats, ious, conts = [], [], [], []
         for i, st in zip(chunks, sam_streams):  # Hiera activations are ~100 MB/frame: a chunk bounds the live set
             with torch.cuda.stream(st):
-                enc = self.sam.encode(frames[i:i + sam_chunk], precision=precision)
+                enc = self.sam.encode(frames[i:i + sam_chunk], precision=precision, outputs="embedding")  # the decoder reads fpn[2] alone
                 e2 = enc["fpn"][2]
                 st.wait_event(det_done)  # the decoder needs the boxes
                 # the service prompts SAM with the first (highest-confidence) detection of the frame (sam3 main.py:199-206);

@@ -13,6 +13,7 @@ sequence over the C-ABI kernels:
 """
 import math
 import os
+import threading
 from dataclasses import dataclass
 
 import numpy as np
@@ -277,10 +278,18 @@ def pack_ln_mlp(w1, b1, w2, b2, g2, e2, gn=None, en=None):
 
 class HieraEncoder:
     """Device-resident Hiera trunk + FPN.  ``encode(frames)`` -> dict(fpn=[3 NHWC f16 levels, high->low res],
-    stages=[4 f32 stage outputs]).  Token grids are [n, H, W, C] row-major throughout (no partition copies)."""
+    stages=[4 f32 stage outputs]).  Token grids are [n, H, W, C] row-major throughout (no partition copies).
 
-    def __init__(self, cfg, state_dict, device="cuda", fused_mlp=True):
+    band (default on): a landscape frame fills only the top rows of the square canvas, and until the first global-attention block
+    tokens mix only inside windows and 2 x 2 pools — a token row whose windows never reach a pixel holds the same values for every
+    frame.  The blocks in front of the first global one then run on the top rows alone (K.hiera_band: 168 of 256 stage-1 rows for a
+    16:9 frame); the other rows come from a table built once per frame geometry (_band_table) and are joined in front of the first
+    global block (K.band_join).  Every kernel computes a row from its window alone, whatever the grid's height, so the result is
+    bit for bit that of band=False (tests/test_gpu_hiera_band.py)."""
+
+    def __init__(self, cfg, state_dict, device="cuda", fused_mlp=True, band=True):
         self.cfg = cfg
+        self.band = band
         self.device = torch.device(device)
         # False: LN / GEMM / GEMM launches for every width (A/B comparisons and tests; LMX_NO_FUSED_MLP=1 forces it)
         self.fused_mlp = fused_mlp and not os.environ.get("LMX_NO_FUSED_MLP")
@@ -353,6 +362,8 @@ class HieraEncoder:
         self.neck = [(t16(sd[f"neck.convs.{n - i}.weight"][:, :, 0, 0]), t32(sd[f"neck.convs.{n - i}.bias"])) for i in range(n + 1)]
         self.lut = t32(sam_norm_lut())
         self._tabs = {}
+        self.first_global = next((i for i, B in enumerate(self.blocks) if B["win"] == 0), None)
+        self._bands, self._band_tabs, self._band_lock = {}, {}, threading.Lock()
 
     # ---- preprocessing ------------------------------------------------------------------------------------
     def _tables(self, h, w):
@@ -370,25 +381,87 @@ class HieraEncoder:
             self._tabs[key] = (nh, nw, th, tv)
         return self._tabs[key]
 
-    def preprocess(self, frames):
-        """u8 [n,h,w,3] (channel order as handed over) -> (PIL-resized u8 [n,nh,nw,3], patch matrix f16 [n*g*g, 152])."""
+    def preprocess(self, frames, band=0):
+        """u8 [n,h,w,3] (channel order as handed over) -> (PIL-resized u8 [n,nh,nw,3], patch matrix f16 [n*g*g, 152]); band > 0: the
+        patches of the top `band` token rows only, [n*band*g, 152] (a canvas of 4 * band pixel rows)."""
         n, h, w, _ = frames.shape
         nh, nw, th, tv = self._tables(h, w)
         img = K.pil_resize(frames, nw, nh, th, tv, swap_rb=False)
         S = self.cfg.image
-        return img, K.im2col_u8(img, self.lut, S, S, 7, 7, 4, 3, self.k_pad)
+        return img, K.im2col_u8(img, self.lut, 4 * band if band else S, S, 7, 7, 4, 3, self.k_pad)
+
+    # ---- the band of rows that depends on the frame ---------------------------------------------------------
+    def band_rows(self, nh, nw):
+        """Stage-1 token rows the blocks in front of the first global one compute for a frame resized to nh x nw; 0: the whole grid."""
+        if (nh, nw) not in self._bands:
+            plan = self.cfg.block_plan()
+            self._bands[(nh, nw)] = K.hiera_band([p[3] for p in plan], [p[4] for p in plan], self.grid0, nh, nw)
+        return self._bands[(nh, nw)]
+
+    def _selection(self):
+        """What selects the kernels of the blocks in front of the first global one, switches included: part of the table's key."""
+        H = W = self.grid0
+        sel = []
+        for i, B in enumerate(self.blocks[:self.first_global]):
+            dim, D, heads, win, qs = B["dim"], B["dim_out"], B["heads"], B["win"], B["qs"]
+            sel.append((self._attn8(i, H, W), "attnp" in B and K.hiera_attn_pool_ok(dim, D, heads, win, H, W, qs),
+                        "attn4" in B and K.hiera_attn4_ok(D, heads, win, H, W, qs), "mlp_img" in B and K.ln_mlp_img_ok(D, H * W)))
+            if qs:
+                H, W = H // 2, W // 2
+        return tuple(sel)
+
+    def _band_table(self, frames, nh, nw, band):
+        """The rows below the band, the same for every frame of this geometry: dict(x = the f32 stream in front of the first global
+        block, stages / stages16 = the stage outputs before it), each [(H_s - band_s) * W_s, D].  Built once per (geometry, kernel
+        selection) by the full-grid path on one frame, outside any running launch trace (a trace describes the steady step), and
+        finished with a synchronisation of the building stream: passes on other streams read the table without an event."""
+        key = (nh, nw, band, self._selection())
+        tab = self._band_tabs.get(key)
+        if tab is not None:
+            return tab
+        if torch.cuda.is_current_stream_capturing():
+            raise K.LmxError("HieraEncoder: the constant rows below the band are not built for this frame geometry, and a stream capture "
+                             "cannot build them (it needs a synchronisation): call encode() once before capturing")
+        with self._band_lock:
+            if key in self._band_tabs:
+                return self._band_tabs[key]
+            trace, K.LAUNCH_TRACE = K.LAUNCH_TRACE, None
+            try:
+                g = self.grid0
+                x, H, W, stages, stages16 = self.trunk(self.preprocess(frames[:1])[1], 1, until=self.first_global)
+
+                def below(t, Hs, Ws):  # rows >= the band of a [1, Hs, Ws, D] grid, as a table of its own
+                    return t.reshape(Hs, Ws, -1)[band * Hs // g:].reshape(-1, t.shape[-1]).clone()
+
+                tab = dict(x=below(x, H, W), stages=[below(s, *s.shape[1:3]) for s in stages],
+                           stages16=[below(s16, *s.shape[1:3]) if s16 is not None else None for s, s16 in zip(stages, stages16)])
+            finally:
+                K.LAUNCH_TRACE = trace
+            torch.cuda.current_stream(self.device).synchronize()
+            self._band_tabs[key] = tab  # (tables of earlier selections stay: a pass on another stream may still read one)
+        return tab
 
     # ---- network ------------------------------------------------------------------------------------------
-    def trunk(self, patches, n):
+    def trunk(self, patches, n, band=0, table=None, lowest=0, until=None):
+        """patches -> (stages, stages16).  band > 0: `patches` hold the top `band` stage-1 token rows of each frame; the blocks in front
+        of the first global one run on those rows, and `table` (_band_table) supplies the others where the band ends and in the stage
+        outputs before it.  lowest: stage outputs below this index are not kept (None).  until: stop in front of block `until` and
+        return (x, H, W, stages, stages16) as they stand there."""
         cfg = self.cfg
         g = self.grid0
-        x = K.gemm(patches, self.pe_w, bias=self.pe_b, res=self.pos, res_rows=g * g, out_dtype=torch.float32)
-        H = W = g
+        H, W = band or g, g
+        Hf = g  # rows of the whole grid at this resolution (H while the band lasts: the band's)
+        x = K.gemm(patches, self.pe_w, bias=self.pe_b, res=self.pos[:H * g], res_rows=H * g, out_dtype=torch.float32)
         stage_ends = set(int(v) for v in np.cumsum(cfg.blocks) - 1)
         stages, stages16 = [], []
         dev = x.device
         h_next = None
         for i, B in enumerate(self.blocks):
+            if i == until:
+                return x, H, W, stages, stages16
+            if band and i == self.first_global:  # the band ends: from here every token sees every other
+                x = K.band_join(x.view(n, H, W, -1), table["x"], Hf).view(n * Hf * W, -1)
+                H, band, h_next = Hf, 0, None
             dim, D, heads, qs = B["dim"], B["dim_out"], B["heads"], B["qs"]
             rows = n * H * W
             h2 = None
@@ -418,10 +491,13 @@ class HieraEncoder:
                 else:
                     res = x
                 x, H, W, h2 = self._attention_half(B, h, x, res, n, H, W)
+            if qs:
+                Hf //= 2
             h_next = None
             x16 = None
+            keep = i in stage_ends and len(stages) >= lowest
             if D in K.FUSED_MLP_WIDTHS and self.fused_mlp:
-                if i in stage_ends:  # the FPN's lateral convolution reads this stage output as f16: written here, not cast later
+                if keep:  # the FPN's lateral convolution reads this stage output as f16: written here, not cast later
                     x16 = torch.empty((n * H * W, D), dtype=torch.float16, device=dev)
                 nxt = None
                 if i + 1 < len(self.blocks) and not (self._attn8(i + 1, H, W) and self.blocks[i + 1]["attn8_ln"]):  # the next block's layer_norm1, on the rows while the kernel still holds them
@@ -436,7 +512,14 @@ class HieraEncoder:
                     h2 = K.layernorm(x, B["g2"], B["b2"], cfg.eps)
                 u = K.gemm(h2, B["w1"], bias=B["bb1"], act=K.ACT_GELU)
                 K.gemm(u, B["w2"], bias=B["bb2"], res=x, out=x)
-            if i in stage_ends:
+            if i in stage_ends and not keep:
+                stages.append(None)
+                stages16.append(None)
+            elif i in stage_ends and band:  # the kept output is a tensor of its own: the band's rows, then the constant ones
+                k = len(stages)
+                stages.append(K.band_join(x.view(n, H, W, D), table["stages"][k], Hf))
+                stages16.append(K.band_join(x16.view(n, H, W, D), table["stages16"][k], Hf).view(-1, D) if x16 is not None else None)
+            elif i in stage_ends:
                 stages.append(x.view(n, H, W, D))
                 stages16.append(x16)
                 if i != len(self.blocks) - 1 and self.blocks[i + 1]["dim"] == self.blocks[i + 1]["dim_out"]:
@@ -485,11 +568,12 @@ class HieraEncoder:
         K.gemm(a, B["wo"], bias=B["bo"], res=res, out=xo, ln_out=(h2, B["g2"], B["b2"], self.cfg.eps) if B["proj_ln"] else None)
         return xo, Hq, Wq, h2
 
-    def fpn(self, stages, stages16=None):
+    def fpn(self, stages, stages16=None, lowest=0):
+        """-> the three highest-resolution levels; lowest: levels below it are not computed (None)."""
         cfg = self.cfg
         nlev = len(stages) - 1
-        feats, prev = [], None
-        for i in range(nlev, -1, -1):
+        feats, prev = [None] * (nlev + 1), None
+        for i in range(nlev, lowest - 1, -1):
             s = stages[i]
             n, H, W, C = s.shape
             a = stages16[i] if stages16 and stages16[i] is not None else K.cast_f16(s.view(-1, C))
@@ -502,20 +586,29 @@ class HieraEncoder:
                 K.upsample2(prev, up)
                 K.gemm(a, w, bias=b, res=up.view(-1, cfg.fpn_dim), out=out.view(-1, cfg.fpn_dim))
             prev = out
-            feats.append(out)
-        return feats[-3:][::-1]
+            feats[i] = out
+        return feats[:3]
 
     def encode_patches(self, patches, n):
         stages, stages16 = self.trunk(patches, n)
         return dict(fpn=self.fpn(stages, stages16), stages=stages)
 
-    def encode(self, frames, precision=None):
-        """(precision is accepted for interface parity with SamVitEncoder and ignored: the Hiera trunk has one plan, f16
+    def encode(self, frames, precision=None, outputs="all"):
+        """outputs="all": every FPN level and stage output.  "embedding": what the mask decoder reads — fpn[2], stages[2:] and
+        `resized`; fpn[0], fpn[1] and the first two stage outputs are None: neither their lateral convolutions nor their f16 copies
+        (nor, with a band, their joins) run.
+        (precision is accepted for interface parity with SamVitEncoder and ignored: the Hiera trunk has one plan, f16
         operands, which meets north_star's mask bar with margin — 0.9996 raw-frame IoU with the exact decoder.)"""
-        img, patches = self.preprocess(frames)
-        out = self.encode_patches(patches, frames.shape[0])
-        out["resized"] = img
-        return out
+        if outputs not in ("all", "embedding"):
+            raise ValueError(f"outputs {outputs!r}: expected 'all' or 'embedding'")
+        lowest = 2 if outputs == "embedding" else 0
+        n, h, w, _ = frames.shape
+        nh, nw = self._tables(h, w)[:2]
+        band = self.band_rows(nh, nw) if self.band else 0
+        table = self._band_table(frames, nh, nw, band) if band else None
+        img, patches = self.preprocess(frames, band)
+        stages, stages16 = self.trunk(patches, n, band, table, lowest)
+        return dict(fpn=self.fpn(stages, stages16, lowest), stages=stages, resized=img)
 
 
 # ======================================================================================================================
@@ -710,6 +803,7 @@ class SamVitEncoder:
             y = K.layernorm(y.view(rows, cfg.out_ch), *self.n2_ln, 1e-6)
         return y.view(n, g, g, cfg.out_ch)
 
-    def encode(self, frames, precision=None):
+    def encode(self, frames, precision=None, outputs="all"):
+        """(outputs is accepted for interface parity with HieraEncoder: the embedding is all this encoder returns.)"""
         img, patches = self.preprocess(frames)
         return dict(fpn=[None, None, self.embed(patches, frames.shape[0], precision)], resized=img)

@@ -194,7 +194,7 @@ class HieraSegmenter:
         from .. import sam
 
         n, h, w, _ = frames.shape
-        enc = self.encoder.encode(frames)
+        enc = self.encoder.encode(frames, outputs="embedding")
         e2 = enc["fpn"][2]
         d = self.decoder.predict(e2.view(-1, e2.shape[-1]), boxes, (h, w), sam.resize_longest_side(h, w, self.encoder.cfg.image))
         return dict(mask=d["mask"], stats=d["stats"], contour=K.contour_features(d["mask"]), iou=d["iou"])
