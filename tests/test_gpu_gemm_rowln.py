@@ -141,7 +141,7 @@ def test_rowln_rows_do_not_depend_on_the_batch(cuda, N, K):
 
 def test_hiera_stage3_uses_rowln_and_keeps_its_bits(cuda):
     """Hiera-B+ on one frame: the 15 same-width blocks of stage 3 run their projection with ln_out and drop their layer_norm2 launch,
-    and every stage and FPN output is bit-identical to the plan with the two launches (the blocks' proj_ln switched off)."""
+    and every stage and FPN output is bit-identical to the plan with the two launches (the encoder's proj_ln switched off: no record of its plan has ln_out)."""
     import numpy as np
 
     from lmx import kernels as K_
@@ -161,9 +161,9 @@ def test_hiera_stage3_uses_rowln_and_keeps_its_bits(cuda):
         return out, rowln, ln448
 
     new, rowln, ln448 = run()
-    assert [i for i, b in enumerate(enc.blocks) if b["proj_ln"]] == list(range(6, 21))
-    for b in enc.blocks:
-        b["proj_ln"] = False
+    assert [i for i, p in enumerate(enc.plan(1, enc.grid0)) if p.ln_out] == list(range(6, 21))
+    enc.proj_ln = False
+    assert not any(p.ln_out for p in enc.plan(1, enc.grid0))
     old, rowln_old, ln448_old = run()
     assert (rowln, rowln_old) == (15, 0) and ln448_old - ln448 == 15, (rowln, rowln_old, ln448, ln448_old)
     for name in ("fpn", "stages"):

@@ -11,10 +11,12 @@ sequence over the C-ABI kernels:
           + pooled `proj` shortcut at stage changes) -> LN -> MLP GEMMs (GELU, +residual).  f32 residual stream.
   neck  : 1x1 lateral GEMMs to 256 channels, nearest-x2 top-down add on levels 2/3 (GEMM residual epilogue).
 """
+import itertools
 import math
 import os
 import threading
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -105,84 +107,52 @@ def sam_norm_lut():
     return ((u[None, :] - m[:, None]) / s[:, None]).astype(np.float32)
 
 
-def pack_hiera_attn(wqkv, bqkv, wo, bo, heads, ln_inside=False):
-    """Operands of lmx_k_hiera_attn8 (csrc/hiera.hip) from the block's torch-layout parameters: wqkv [3D, D], bqkv [3D], wo [D, D],
-    bo [D] (numpy, f32).  Returns (wqkv_p f16 [3*heads*64, 128], bqkv_p f32 [3*heads*64], wo_p f16 [D, heads*64], bo f32 [D]):
-    q | k | v sections with each head padded from D/heads to 64 rows; v's row 63 of every head is zero with bias 1 (the softmax sum
-    then rides the PV product); the 64 columns of a head in wo_p — and, with ln_inside (the kernel normalises the f32 rows itself
-    and holds them in accumulator layout), the 128 input columns of wqkv_p — are in MFMA k-slot order: position 32 s + 8 g + 4 h + i
-    holds feature 16 (2 s + h) + 4 g + i, the order in which an accumulator tile is an operand."""
-    D = wo.shape[0]
+# MFMA k-slot order (csrc/hiera.hip), the order in which an accumulator tile is an operand: position 32 s + 8 g + 4 h + i holds
+# feature KSLOT[position] = 16 (2 s + h) + 4 g + i.  Every prefix of a multiple of 32 positions is a permutation of its own range.
+KSLOT = np.array([16 * (2 * s + h) + 4 * g + i for s in range(8) for g in range(4) for h in range(2) for i in range(4)])
+
+
+def _swz_wide(r):  # rows of 256 / 512 bytes: the 16-byte chunk c of row r is stored at chunk c ^ (r & 15)
+    return r & 15
+
+
+def _swz_128(r):  # rows of 128 bytes: ... at chunk c ^ ((r >> 1) & 7)
+    return (r >> 1) & 7
+
+
+def _kslot_cols(w, n):
+    """w [rows, <= n] -> [rows, n] (n % 32 == 0): column p holds w's column KSLOT[p], zeros where w has no such column."""
+    out = np.zeros((w.shape[0], n), w.dtype)
+    ok = KSLOT[:n] < w.shape[1]
+    out[:, ok] = w[:, KSLOT[:n][ok]]
+    return out
+
+
+def _head_rows(wqkv, bqkv, heads, hh, sec):
+    """The rows of head hh in section sec (q | k | v) of the qkv projection, padded to 64: (w [64, Din], b [64]).  v's row 63 is zero
+    with bias 1: the softmax sum then rides the PV product."""
+    D = wqkv.shape[0] // 3
     hd = D // heads
-    if hd > 63 or D > 128:
-        raise ValueError("pack_hiera_attn: head dim <= 63 and D <= 128")
-    wq = np.zeros((3 * heads * 64, 128), np.float32)
-    bq = np.zeros((3 * heads * 64,), np.float32)
-    pos = np.array([32 * s_ + 8 * g + 4 * hb + i for s_ in range(4) for hb in range(2) for g in range(4) for i in range(4)])  # of feature 16(2s+hb)+4g+i
-    pos = pos[:D] if ln_inside else np.arange(D)
-    for sec in range(3):
-        for hh in range(heads):
-            r0 = sec * heads * 64 + hh * 64
-            wq[r0:r0 + hd, pos] = wqkv[sec * D + hh * hd: sec * D + (hh + 1) * hd]
-            bq[r0:r0 + hd] = bqkv[sec * D + hh * hd: sec * D + (hh + 1) * hd]
-            if sec == 2:
-                bq[r0 + 63] = 1.0
-    wop = np.zeros((D, heads * 64), np.float32)
-    for hh in range(heads):
-        for s_ in range(2):
-            for g in range(4):
-                for hb in range(2):
-                    for i in range(4):
-                        d = 16 * (2 * s_ + hb) + 4 * g + i
-                        if d < hd:
-                            wop[:, 64 * hh + 32 * s_ + 8 * g + 4 * hb + i] = wo[:, hh * hd + d]
-    return wq.astype(np.float16), bq, wop.astype(np.float16), np.ascontiguousarray(bo, dtype=np.float32)
+    w, b = np.zeros((64, wqkv.shape[1]), np.float32), np.zeros((64,), np.float32)
+    w[:hd], b[:hd] = wqkv[sec * D + hh * hd: sec * D + (hh + 1) * hd], bqkv[sec * D + hh * hd: sec * D + (hh + 1) * hd]
+    if sec == 2:
+        b[63] = 1.0
+    return w, b
 
 
-def pack_hiera_attn4(wqkv, bqkv, wo, bo, heads):
-    """Operands of lmx_k_hiera_attn4 (csrc/hiera.hip): the LDS images of the 4 * heads matrices the kernel streams, and its biases.
-    wqkv [3D, D], bqkv [3D], wo [D, D], bo [D] (numpy, f32; D = 224, heads = 4).  Image 4 h + s, s in q | k | v: 64 rows (the
-    head's 56, then zeros) of 512 bytes, the 16-byte chunk c of row r stored at chunk c ^ (r & 15); image 4 h + 3: the projection's
-    columns of head h as 256 rows (224 outputs, then zeros) of 128 bytes, chunk c of row r at c ^ ((r >> 1) & 7), the 64 columns in
-    MFMA k-slot order (position 32 s + 8 g + 4 hb + i holds the head's input 16 (2 s + hb) + 4 g + i, zeros past 56).
-    bias: [head][q | k | v][64] (v's entry 63 is 1: the softmax sum rides the PV product) then bo."""
-    D = wo.shape[0]
-    hd = D // heads
-    img = np.zeros((4 * heads, 16384), np.float16)
-    bias = np.zeros((heads * 192 + D,), np.float32)
-    for hh in range(heads):
-        for sec in range(3):
-            m = np.zeros((64, 256), np.float16)
-            m[:hd, :D] = wqkv[sec * D + hh * hd: sec * D + (hh + 1) * hd].astype(np.float16)
-            ch = m.reshape(64, 32, 8)
-            out = np.zeros_like(ch)
-            for r in range(64):
-                out[r, np.arange(32) ^ (r & 15)] = ch[r]
-            img[4 * hh + sec] = out.reshape(-1)
-            bias[hh * 192 + sec * 64: hh * 192 + sec * 64 + hd] = bqkv[sec * D + hh * hd: sec * D + (hh + 1) * hd]
-        bias[hh * 192 + 128 + 63] = 1.0
-        m = np.zeros((256, 64), np.float16)
-        for s_ in range(2):
-            for g in range(4):
-                for hb in range(2):
-                    for i in range(4):
-                        d = 16 * (2 * s_ + hb) + 4 * g + i
-                        if d < hd:
-                            m[:D, 32 * s_ + 8 * g + 4 * hb + i] = wo[:, hh * hd + d].astype(np.float16)
-        ch = m.reshape(256, 8, 8)
-        out = np.zeros_like(ch)
-        for r in range(256):
-            out[r, np.arange(8) ^ ((r >> 1) & 7)] = ch[r]
-        img[4 * hh + 3] = out.reshape(-1)
-    bias[heads * 192:] = bo
-    return img, bias
+def _head_proj(wo, heads, hh):
+    """The output projection's columns of head hh, [Dout, 64] in k-slot order, zeros past the head dim."""
+    hd = wo.shape[1] // heads
+    return _kslot_cols(wo[:, hh * hd: (hh + 1) * hd], 64)
 
 
-def _lds_image(m, key):
-    """f16 matrix [rows, cols] (cols * 2 bytes = 128 or 256 per row) -> its LDS image: the 16-byte chunk c of row r stored at chunk
-    c ^ key(r); zero-padded to 32 KB."""
-    rows, cols = m.shape
-    ch = m.reshape(rows, cols // 8, 8)
+def _lds_image(m, key, rows=None, cols=None):
+    """Matrix m, zero-padded to [rows, cols] (its own shape by default; cols * 2 bytes = 128, 256 or 512 per row), as f16 -> its LDS
+    image: the 16-byte chunk c of row r stored at chunk c ^ key(r); zero-padded to 32 KB."""
+    rows, cols = rows or m.shape[0], cols or m.shape[1]
+    ch = np.zeros((rows, cols), np.float16)
+    ch[:m.shape[0], :m.shape[1]] = m
+    ch = ch.reshape(rows, cols // 8, 8)
     out = np.zeros_like(ch)
     for r in range(rows):
         out[r, np.arange(cols // 8) ^ key(r)] = ch[r]
@@ -191,84 +161,80 @@ def _lds_image(m, key):
     return img
 
 
+def pack_hiera_attn(wqkv, bqkv, wo, bo, heads, ln_inside=False):
+    """Operands of lmx_k_hiera_attn8 (csrc/hiera.hip) from the block's torch-layout parameters: wqkv [3D, D], bqkv [3D], wo [D, D],
+    bo [D] (numpy, f32).  Returns (wqkv_p f16 [3*heads*64, 128], bqkv_p f32 [3*heads*64], wo_p f16 [D, heads*64], bo f32 [D]):
+    q | k | v sections with each head padded from D/heads to 64 rows (_head_rows); the 64 columns of a head in wo_p — and, with
+    ln_inside (the kernel normalises the f32 rows itself and holds them in accumulator layout), the 128 input columns of wqkv_p — are
+    in MFMA k-slot order (KSLOT)."""
+    D = wo.shape[0]
+    if D // heads > 63 or D > 128:
+        raise ValueError("pack_hiera_attn: head dim <= 63 and D <= 128")
+    wq = np.zeros((3 * heads * 64, 128), np.float32)
+    bq = np.zeros((3 * heads * 64,), np.float32)
+    for sec in range(3):
+        for hh in range(heads):
+            r0 = sec * heads * 64 + hh * 64
+            w, bq[r0:r0 + 64] = _head_rows(wqkv, bqkv, heads, hh, sec)
+            wq[r0:r0 + 64, :128 if ln_inside else D] = _kslot_cols(w, 128) if ln_inside else w
+    wop = np.concatenate([_head_proj(wo, heads, hh) for hh in range(heads)], 1)
+    return wq.astype(np.float16), bq, wop.astype(np.float16), np.ascontiguousarray(bo, dtype=np.float32)
+
+
+def pack_hiera_attn4(wqkv, bqkv, wo, bo, heads):
+    """Operands of lmx_k_hiera_attn4 (csrc/hiera.hip): the LDS images of the 4 * heads matrices the kernel streams, and its biases.
+    wqkv [3D, D], bqkv [3D], wo [D, D], bo [D] (numpy, f32; D = 224, heads = 4).  Image 4 h + s, s in q | k | v: the head's 64 rows
+    (_head_rows) of 512 bytes; image 4 h + 3: the projection's columns of head h (_head_proj) as 256 rows (224 outputs, then zeros)
+    of 128 bytes.  bias: [head][q | k | v][64] then bo."""
+    imgs, bias = [], []
+    for hh in range(heads):
+        for sec in range(3):
+            w, b = _head_rows(wqkv, bqkv, heads, hh, sec)
+            imgs.append(_lds_image(w, _swz_wide, 64, 256))
+            bias.append(b)
+        imgs.append(_lds_image(_head_proj(wo, heads, hh), _swz_128, 256, 64))
+    return np.stack(imgs), np.concatenate(bias + [bo]).astype(np.float32)
+
+
 def pack_hiera_attn_pool(wsc, bsc, wqkv, bqkv, wo, bo, heads):
     """Operands of lmx_k_hiera_attn_pool (csrc/hiera.hip) for a block that opens a stage: wsc [Dout, Din] / bsc: the shortcut's
     projection; wqkv [3 Dout, Din], bqkv; wo [Dout, Dout], bo (numpy, f32).  LDS images of 32 KB, in the order the kernel streams them.
     Din 112 -> Dout 224 (4 heads): 14 images — shortcut rows 0..127, shortcut rows 128.., then per head [q | k] (64 + 64 rows of 256
-    bytes, the head's 56 rows then zeros), [v], and the projection's columns of the head (rows of 128 bytes in MFMA k-slot order).
+    bytes, _head_rows), [v], and the projection's columns of the head (_head_proj, rows of 128 bytes).
     Din 224 -> Dout 448 (8 heads): 47 images — shortcut in 7 images of 64 rows (512-byte rows), then per head q, k, v (64 rows each) and
-    the projection's columns of the head in two images (output rows 0..223, 224..447).  Rows of 256 / 512 bytes are swizzled by r & 15,
-    rows of 128 bytes by (r >> 1) & 7.  bias: shortcut + projection [Dout], [head][q | k | v][64] (v's entry 63 is 1)[, Dout zeros]."""
+    the projection's columns of the head in two images (output rows 0..223, 224..447).
+    bias: shortcut + projection [Dout], [head][q | k | v][64][, Dout zeros]."""
     Dout, Din = wsc.shape
-    hd = Dout // heads
     wide = Din > 128  # 512-byte rows
-    cols = 256 if wide else 128
-    k15, k7 = (lambda r: r & 15), (lambda r: (r >> 1) & 7)
-
-    def rows_img(w, nrows):  # [<= nrows, Din] -> image of nrows rows of `cols` halfs
-        m = np.zeros((nrows, cols), np.float16)
-        m[:w.shape[0], :Din] = w.astype(np.float16)
-        return _lds_image(m, k15)
-
-    if wide:
-        imgs = [rows_img(wsc[64 * j: 64 * j + 64], 64) for j in range(7)]
-    else:
-        imgs = [rows_img(wsc[:128], 128), rows_img(wsc[128:], 128)]
-    bias = np.zeros((Dout + heads * 192 + (0 if wide else Dout),), np.float32)
-    bias[:Dout] = bsc + bo  # the shortcut's and the output projection's biases: one vector, added once
+    step, cols = (64, 256) if wide else (128, 128)
+    imgs = [_lds_image(wsc[j:j + step], _swz_wide, step, cols) for j in range(0, Dout, step)]
+    bias = [bsc + bo]  # the shortcut's and the output projection's biases: one vector, added once
     for hh in range(heads):
-        sec = []
-        for s_ in range(3):
-            sec.append(wqkv[s_ * Dout + hh * hd: s_ * Dout + (hh + 1) * hd])
-            bias[Dout + hh * 192 + s_ * 64: Dout + hh * 192 + s_ * 64 + hd] = bqkv[s_ * Dout + hh * hd: s_ * Dout + (hh + 1) * hd]
-        bias[Dout + hh * 192 + 128 + 63] = 1.0
-        if wide:
-            imgs += [rows_img(sec[0], 64), rows_img(sec[1], 64), rows_img(sec[2], 64)]
-        else:
-            qk = np.zeros((128, Din), np.float32)
-            qk[:hd], qk[64:64 + hd] = sec[0], sec[1]
-            imgs += [rows_img(qk, 128), rows_img(sec[2], 64)]
-        m = np.zeros((512 if wide else 256, 64), np.float16)
-        for s_ in range(2):
-            for g in range(4):
-                for hb in range(2):
-                    for i in range(4):
-                        d = 16 * (2 * s_ + hb) + 4 * g + i
-                        if d < hd:
-                            m[:Dout, 32 * s_ + 8 * g + 4 * hb + i] = wo[:, hh * hd + d].astype(np.float16)
-        if wide:
-            for half in range(2):
-                mm = np.zeros((256, 64), np.float16)
-                mm[:224] = m[224 * half: 224 * half + 224]
-                imgs.append(_lds_image(mm, k7))
-        else:
-            imgs.append(_lds_image(m, k7))
-    return np.stack(imgs), bias
+        (q, bq), (k, bk), (v, bv) = (_head_rows(wqkv, bqkv, heads, hh, sec) for sec in range(3))
+        bias += [bq, bk, bv]
+        sections = (q, k, v) if wide else (np.concatenate([q, k]), v)
+        imgs += [_lds_image(w, _swz_wide, len(w), cols) for w in sections]
+        proj = _head_proj(wo, heads, hh)
+        imgs += [_lds_image(half, _swz_128, 256, 64) for half in ((proj[:Dout // 2], proj[Dout // 2:]) if wide else (proj,))]
+    if not wide:
+        bias.append(np.zeros((Dout,), np.float32))
+    return np.stack(imgs), np.concatenate(bias).astype(np.float32)
 
 
 def pack_ln_mlp(w1, b1, w2, b2, g2, e2, gn=None, en=None):
     """Operands of lmx_k_ln_mlp_img (csrc/hiera.hip): w1 [4D, D], b1 [4D], w2 [D, 4D], b2 [D] (torch Linear layouts), layer_norm2's
     g2 / e2 and — for the kernel's h_next output — the next block's layer_norm1's gn / en (numpy, f32; D = 112 or 224).  Per step of
-    64 hidden units: the 64 rows of w1 with their D input columns in MFMA k-slot order (rows of 256 bytes at D = 112, 512 at 224;
-    16-byte chunk c of row r at c ^ (r & 15)) and the D rows x 64 columns of w2, columns in k-slot order (rows of 128 bytes, chunk c of
-    row r at c ^ ((r >> 1) & 7)); at D = 112 both halves share an image (w2's at byte 16384), at D = 224 they alternate."""
+    64 hidden units: the 64 rows of w1 with their D input columns in k-slot order (rows of 256 bytes at D = 112, 512 at 224) and the
+    D rows x 64 columns of w2, columns in k-slot order (rows of 128 bytes); at D = 112 both halves share an image (w2's at byte
+    16384), at D = 224 they alternate.  bias: [b1 | b2 | g2 | e2 | gn | en], zeros for gn / en where no next block is given."""
     D = w2.shape[0]
-    cols = 128 if D <= 128 else 256
-    nks = cols // 32
-    kslot = np.array([16 * (2 * s_ + hb) + 4 * g + i for s_ in range(nks) for g in range(4) for hb in range(2) for i in range(4)])  # feature at position
-    k15, k7 = (lambda r: r & 15), (lambda r: (r >> 1) & 7)
     imgs = []
-    for ch in range(4 * D // 64):
-        m1 = np.zeros((64, cols), np.float16)
-        ok = kslot < D
-        m1[:, ok] = w1[64 * ch: 64 * ch + 64][:, kslot[ok]].astype(np.float16)
-        m2 = np.zeros((D, 64), np.float16)
-        m2[:, :] = w2[:, 64 * ch + kslot[:64]].astype(np.float16)
-        i1, i2 = _lds_image(m1, k15), _lds_image(m2, k7)
+    for c in range(0, 4 * D, 64):
+        i1 = _lds_image(_kslot_cols(w1[c:c + 64], 128 if D <= 128 else 256), _swz_wide)
+        i2 = _lds_image(_kslot_cols(w2[:, c:c + 64], 64), _swz_128)
         if D <= 128:
-            both = i1.copy()
-            both[8192:8192 + D * 64] = i2[:D * 64]
-            imgs.append(both)
+            i1[8192:8192 + D * 64] = i2[:D * 64]
+            imgs.append(i1)
         else:
             imgs += [i1, i2]
     z = np.zeros((D,), np.float32)
@@ -276,9 +242,103 @@ def pack_ln_mlp(w1, b1, w2, b2, g2, e2, gn=None, en=None):
     return np.stack(imgs), bias
 
 
+# shape class (dim, dim_out, heads, window, q_stride) -> the kernel of csrc/hiera.hip that runs such a block's attention half in one
+# launch.  The encoder packs operands for every block of such a class, whatever the switches say; hiera_plan() decides per call
+FUSED_ATTN = {(112, 112, 2, 8, 0): "attn8",       # Hiera-B+ stage 1
+              (224, 224, 4, 4, 0): "attn4",       # stage 2 after its first block: the same, weights streamed
+              (112, 224, 4, 8, 2): "attn_pool",   # the blocks that open stages 2 and 3: pooled queries and shortcut
+              (224, 448, 8, 4, 2): "attn_pool"}
+
+
+def attn8_ln_inside(i, fused_mlp):
+    """Block i of the attn8 class normalises its rows in the kernel (operands packed with ln_inside): the first block, and every one
+    when no fused MLP in front writes its layer_norm1 rows (the class has D = 112, a width every fused MLP is built for)."""
+    return i == 0 or not fused_mlp
+
+
+class BlockPlan(NamedTuple):
+    """What one Hiera block runs: a record of hiera_plan(), executed by HieraEncoder.trunk()."""
+    H: int             # the token grid going in: rows (the band's while it lasts; behind a join the whole grid's), columns,
+    W: int
+    Hf: int            # and the whole grid's rows at this resolution
+    Ho: int            # the same going out (halved where the block pools its queries)
+    Wo: int
+    Hfo: int
+    join: int          # > 0: the band ends in front of this block; its `join` rows are joined with the table's to H rows
+    attn: str          # the attention half: "attn8_ln" (layer_norm1 inside) | "attn8" | "attn_pool" | "attn4" | "launches"
+    ln1: str           # layer_norm1's rows come from: "kernel" (attn8_ln) | "prev" (the previous block's MLP kernel) | "launch"
+    shortcut: str      # launches only: None | "gemm" | "gemm+maxpool" | "pooled_gemm"
+    query: str         # launches only: "qkv" | "qkv+maxpool" | "pooled_q+kv"
+    window: int        # 0: global attention
+    ln_out: bool       # launches only: the projection's tile holds whole rows and writes layer_norm2's with them (K.gemm ln_out)
+    mlp: str           # "img" (csrc/hiera.hip, streamed images) | "fused" (csrc/mlp.hip) | "launches" (LayerNorm + two GEMMs)
+    emit_ln1: bool     # the MLP kernel also writes the next block's layer_norm1 rows, while it still holds them
+    stage_end: bool
+    keep: bool         # stage end: the output is returned (else None: below `lowest`)
+    x16: bool          # ... and the MLP kernel writes the f16 copy the FPN's lateral convolution reads
+    join_out: bool     # ... as a tensor of its own: the band's rows, then the table's
+    clone: bool        # ... and the stream goes on in a copy: a same-width next block would update the kept output in place
+
+    def choices(self):
+        """The kernel choices alone: what the band's constant rows depend on besides the weights."""
+        return (self.attn, self.ln1, self.shortcut, self.query, self.ln_out, self.mlp, self.emit_ln1)
+
+
+def hiera_plan(cfg, n, rows, fused_mlp=True, lowest=0, proj_ln=True):
+    """[BlockPlan per block] for n frames whose blocks in front of the first global one run on `rows` stage-1 token rows (a band, or
+    cfg.image // 4: the whole grid).  The one place that chooses kernels, computed per call: the K.*_ok functions read their
+    environment switches every time.  lowest: stage outputs below this index are not kept.  proj_ln=False: no ln_out projections."""
+    g = cfg.image // 4
+    blocks = cfg.block_plan()
+    first_global = next((i for i, b in enumerate(blocks) if b[3] == 0), None)
+    stage_ends = [e - 1 for e in itertools.accumulate(cfg.blocks)]
+    H, W, Hf = rows, g, g
+    band = rows < g
+    plan, prev = [], None  # prev: the block before, which learns from this one's attention half whether to emit layer_norm1
+    for i, (dim, D, heads, win, qs) in enumerate(blocks):
+        join = H if band and i == first_global else 0  # the band ends: from here every token sees every other
+        if join:
+            H, band = Hf, False
+        fused = FUSED_ATTN.get((dim, D, heads, win, qs))
+        shortcut = query = None
+        if fused == "attn8" and K.hiera_attn8_ok(D, heads, win, H, W, qs):
+            attn = "attn8_ln" if attn8_ln_inside(i, fused_mlp) else "attn8"
+        elif fused == "attn_pool" and K.hiera_attn_pool_ok(dim, D, heads, win, H, W, qs):
+            attn = "attn_pool"
+        elif fused == "attn4" and K.hiera_attn4_ok(D, heads, win, H, W, qs):
+            attn = "attn4"
+        else:
+            # pooled: the GEMM writes the 2 x 2 max-pool of its product (the shortcut's; the q third's, k and v from a second launch)
+            pooled = qs and K.pooled_gemm_ok(n * H * W, D)
+            attn = "launches"
+            shortcut = None if dim == D else "pooled_gemm" if pooled else "gemm+maxpool" if qs else "gemm"
+            query = "pooled_q+kv" if pooled else "qkv+maxpool" if qs else "qkv"
+        ln1 = "kernel" if attn == "attn8_ln" else "launch"
+        if prev is not None:
+            if prev.mlp != "launches" and attn != "attn8_ln":
+                prev = prev._replace(emit_ln1=True)
+                if not join:  # (behind a join those rows are the band's alone: dropped)
+                    ln1 = "prev"
+            plan.append(prev)
+        Ho, Wo, Hfo = (H // 2, W // 2, Hf // 2) if qs else (H, W, Hf)
+        mlp = "launches" if not (fused_mlp and D in K.FUSED_MLP_WIDTHS) else "img" if K.ln_mlp_img_ok(D, n * Ho * Wo) else "fused"
+        # stage 3 of Hiera-B+ after its opening block: the layer's choice, whatever the batch
+        ln_out = attn == mlp == "launches" and proj_ln and dim == D == 448 and not qs
+        end = i in stage_ends
+        keep = end and stage_ends.index(i) >= lowest
+        prev = BlockPlan(H, W, Hf, Ho, Wo, Hfo, join, attn, ln1, shortcut, query, win, ln_out, mlp, False, end, keep,
+                         x16=keep and mlp != "launches", join_out=keep and band,
+                         clone=keep and not band and i + 1 < len(blocks) and blocks[i + 1][0] == blocks[i + 1][1])
+        H, W, Hf = Ho, Wo, Hfo
+    return plan + [prev]
+
+
 class HieraEncoder:
     """Device-resident Hiera trunk + FPN.  ``encode(frames)`` -> dict(fpn=[3 NHWC f16 levels, high->low res],
     stages=[4 f32 stage outputs]).  Token grids are [n, H, W, C] row-major throughout (no partition copies).
+
+    Every call computes its block plan on the host (hiera_plan: which kernels each block runs, where its layer_norm1 rows come from,
+    what happens at a stage end) and trunk() executes it record by record.
 
     band (default on): a landscape frame fills only the top rows of the square canvas, and until the first global-attention block
     tokens mix only inside windows and 2 x 2 pools — a token row whose windows never reach a pixel holds the same values for every
@@ -293,6 +353,7 @@ class HieraEncoder:
         self.device = torch.device(device)
         # False: LN / GEMM / GEMM launches for every width (A/B comparisons and tests; LMX_NO_FUSED_MLP=1 forces it)
         self.fused_mlp = fused_mlp and not os.environ.get("LMX_NO_FUSED_MLP")
+        self.proj_ln = True  # False: no projection writes layer_norm2 (hiera_plan's ln_out; tests compare the two)
         dev = self.device
         sd = state_dict
 
@@ -329,30 +390,20 @@ class HieraEncoder:
                        w2=t16(sd[p + "mlp.proj_out.weight"]), bb2=t32(sd[p + "mlp.proj_out.bias"]))
             if dim != dim_out:
                 blk["wp"], blk["bp"] = t16(sd[p + "proj.weight"]), t32(sd[p + "proj.bias"])
-            if dim == dim_out == 112 and heads == 2 and win_ == 8 and not qs:  # stage 1 of Hiera-B+: one kernel per attention half
-                # (the first block normalises in the kernel; later ones read the rows their predecessor's fused MLP left: see trunk)
-                blk["attn8_ln"] = i == 0 or not (self.fused_mlp and dim in K.FUSED_MLP_WIDTHS)
-                blk["attn8"] = tuple(torch.from_numpy(a).to(dev) for a in pack_hiera_attn(
-                    np.asarray(sd[p + "attn.qkv.weight"], np.float32), np.asarray(qkv_b, np.float32),
-                    np.asarray(sd[p + "attn.proj.weight"], np.float32), np.asarray(sd[p + "attn.proj.bias"], np.float32), heads,
-                    ln_inside=blk["attn8_ln"]))
-            if dim == dim_out == 224 and heads == 4 and win_ == 4 and not qs:  # stage 2 (after its first block): the same, weights streamed
-                blk["attn4"] = tuple(torch.from_numpy(a).to(dev) for a in pack_hiera_attn4(
-                    np.asarray(sd[p + "attn.qkv.weight"], np.float32), np.asarray(qkv_b, np.float32),
-                    np.asarray(sd[p + "attn.proj.weight"], np.float32), np.asarray(sd[p + "attn.proj.bias"], np.float32), heads))
-            if qs and ((dim, dim_out, heads, win_) in ((112, 224, 4, 8), (224, 448, 8, 4))):  # the blocks that open stages 2 and 3: pooled queries and shortcut
-                blk["attnp"] = tuple(torch.from_numpy(a).to(dev) for a in pack_hiera_attn_pool(
-                    np.asarray(sd[p + "proj.weight"], np.float32), np.asarray(sd[p + "proj.bias"], np.float32),
-                    np.asarray(sd[p + "attn.qkv.weight"], np.float32), np.asarray(qkv_b, np.float32),
-                    np.asarray(sd[p + "attn.proj.weight"], np.float32), np.asarray(sd[p + "attn.proj.bias"], np.float32), heads))
-            # stage 3 of Hiera-B+ after its opening block (separate launches): the projection's tile holds whole 448-wide rows and writes
-            # layer_norm2's rows with the residual stream (K.gemm ln_out).  The layer's choice, whatever the batch
-            blk["proj_ln"] = dim == dim_out == 448 and not qs and not (self.fused_mlp and dim_out in K.FUSED_MLP_WIDTHS)
+            kind = FUSED_ATTN.get((dim, dim_out, heads, win_, qs))
+            if kind:
+                f32 = lambda k: np.asarray(sd[p + k], np.float32)  # noqa: E731
+                attn = (f32("attn.qkv.weight"), f32("attn.qkv.bias"), f32("attn.proj.weight"), f32("attn.proj.bias"), heads)
+                packed = (pack_hiera_attn(*attn, ln_inside=attn8_ln_inside(i, self.fused_mlp)) if kind == "attn8" else
+                          pack_hiera_attn4(*attn) if kind == "attn4" else pack_hiera_attn_pool(f32("proj.weight"), f32("proj.bias"), *attn))
+                blk["attn"] = tuple(torch.from_numpy(a).to(dev) for a in packed)
             self.blocks.append(blk)
         for i, blk in enumerate(self.blocks):  # the fused MLP's operands as LDS images, with the NEXT block's layer_norm1 vectors
+            nxt = self.blocks[i + 1] if i + 1 < len(self.blocks) else None
+            blk["next_ln1"] = (nxt["g1"], nxt["b1"]) if nxt else None  # (csrc/mlp.hip's kernel takes them as tensors)
             if blk["dim_out"] in (112, 224) and self.fused_mlp:
                 p = f"backbone.blocks.{i}."
-                nx = f"backbone.blocks.{i + 1}." if i + 1 < len(self.blocks) else None
+                nx = f"backbone.blocks.{i + 1}." if nxt else None
                 f32 = lambda k: np.asarray(sd[k], np.float32)  # noqa: E731
                 blk["mlp_img"] = tuple(torch.from_numpy(a).to(dev) for a in pack_ln_mlp(
                     f32(p + "mlp.proj_in.weight"), f32(p + "mlp.proj_in.bias"), f32(p + "mlp.proj_out.weight"), f32(p + "mlp.proj_out.bias"),
@@ -398,24 +449,21 @@ class HieraEncoder:
             self._bands[(nh, nw)] = K.hiera_band([p[3] for p in plan], [p[4] for p in plan], self.grid0, nh, nw)
         return self._bands[(nh, nw)]
 
-    def _selection(self):
-        """What selects the kernels of the blocks in front of the first global one, switches included: part of the table's key."""
-        H = W = self.grid0
-        sel = []
-        for i, B in enumerate(self.blocks[:self.first_global]):
-            dim, D, heads, win, qs = B["dim"], B["dim_out"], B["heads"], B["win"], B["qs"]
-            sel.append((self._attn8(i, H, W), "attnp" in B and K.hiera_attn_pool_ok(dim, D, heads, win, H, W, qs),
-                        "attn4" in B and K.hiera_attn4_ok(D, heads, win, H, W, qs), "mlp_img" in B and K.ln_mlp_img_ok(D, H * W)))
-            if qs:
-                H, W = H // 2, W // 2
-        return tuple(sel)
+    def plan(self, n, rows, lowest=0):
+        """hiera_plan() of this encoder for n frames on `rows` stage-1 token rows in front of the first global block."""
+        return hiera_plan(self.cfg, n, rows, self.fused_mlp, lowest, self.proj_ln)
+
+    def _table_key(self, nh, nw, band):
+        """The band table's key: the geometry and the kernel choices of the pass that builds it — one frame, the whole grid, the blocks
+        in front of the first global one — so it never depends on a caller's batch size (K.pooled_gemm_ok does)."""
+        return (nh, nw, band, tuple(p.choices() for p in self.plan(1, self.grid0)[:self.first_global]))
 
     def _band_table(self, frames, nh, nw, band):
         """The rows below the band, the same for every frame of this geometry: dict(x = the f32 stream in front of the first global
-        block, stages / stages16 = the stage outputs before it), each [(H_s - band_s) * W_s, D].  Built once per (geometry, kernel
-        selection) by the full-grid path on one frame, outside any running launch trace (a trace describes the steady step), and
+        block, stages / stages16 = the stage outputs before it), each [(H_s - band_s) * W_s, D].  Built once per _table_key by
+        the full-grid path on one frame, outside any running launch trace (a trace describes the steady step), and
         finished with a synchronisation of the building stream: passes on other streams read the table without an event."""
-        key = (nh, nw, band, self._selection())
+        key = self._table_key(nh, nw, band)
         tab = self._band_tabs.get(key)
         if tab is not None:
             return tab
@@ -443,114 +491,94 @@ class HieraEncoder:
 
     # ---- network ------------------------------------------------------------------------------------------
     def trunk(self, patches, n, band=0, table=None, lowest=0, until=None):
-        """patches -> (stages, stages16).  band > 0: `patches` hold the top `band` stage-1 token rows of each frame; the blocks in front
-        of the first global one run on those rows, and `table` (_band_table) supplies the others where the band ends and in the stage
-        outputs before it.  lowest: stage outputs below this index are not kept (None).  until: stop in front of block `until` and
-        return (x, H, W, stages, stages16) as they stand there."""
+        """patches -> (stages, stages16): executes self.plan(n, band or the whole grid, lowest) block by block.  band > 0: `patches`
+        hold the top `band` stage-1 token rows of each frame; the blocks in front of the first global one run on those rows, and
+        `table` (_band_table) supplies the others where the band ends and in the stage outputs before it.  lowest: stage outputs
+        below this index are not kept (None).  until: stop in front of block `until` and return (x, H, W, stages, stages16) as they
+        stand there."""
         cfg = self.cfg
         g = self.grid0
-        H, W = band or g, g
-        Hf = g  # rows of the whole grid at this resolution (H while the band lasts: the band's)
+        H = band or g
         x = K.gemm(patches, self.pe_w, bias=self.pe_b, res=self.pos[:H * g], res_rows=H * g, out_dtype=torch.float32)
-        stage_ends = set(int(v) for v in np.cumsum(cfg.blocks) - 1)
         stages, stages16 = [], []
         dev = x.device
         h_next = None
-        for i, B in enumerate(self.blocks):
+        for i, (P, B) in enumerate(zip(self.plan(n, H, lowest), self.blocks)):
             if i == until:
-                return x, H, W, stages, stages16
-            if band and i == self.first_global:  # the band ends: from here every token sees every other
-                x = K.band_join(x.view(n, H, W, -1), table["x"], Hf).view(n * Hf * W, -1)
-                H, band, h_next = Hf, 0, None
-            dim, D, heads, qs = B["dim"], B["dim_out"], B["heads"], B["qs"]
-            rows = n * H * W
+                return x, P.join or P.H, P.W, stages, stages16
+            if P.join:
+                x = K.band_join(x.view(n, P.join, P.W, -1), table["x"], P.H).view(n * P.H * P.W, -1)
+            D, heads = B["dim_out"], B["heads"]
+            h = None if P.ln1 == "kernel" else h_next if P.ln1 == "prev" else K.layernorm(x, B["g1"], B["b1"], cfg.eps)
             h2 = None
-            if self._attn8(i, H, W):  # [layer_norm1 ->] qkv -> window attention -> proj + residual in one launch (csrc/hiera.hip)
-                if B["attn8_ln"]:
-                    K.hiera_attn8(x, B["attn8"], n, H, W, heads, ln=(B["g1"], B["b1"], cfg.eps))
-                else:
-                    K.hiera_attn8(x, B["attn8"], n, H, W, heads, h=h_next if h_next is not None else K.layernorm(x, B["g1"], B["b1"], cfg.eps))
-            elif "attnp" in B and K.hiera_attn_pool_ok(dim, D, heads, B["win"], H, W, qs):  # the stage-opening block: pooled q + shortcut
-                x = K.hiera_attn_pool(h_next if h_next is not None else K.layernorm(x, B["g1"], B["b1"], cfg.eps), B["attnp"], n, H, W, heads, D)
-                H, W = H // 2, W // 2
-            elif "attn4" in B and K.hiera_attn4_ok(D, heads, B["win"], H, W, qs):  # the same for 4 x 4 windows at D = 224
-                K.hiera_attn4(h_next if h_next is not None else K.layernorm(x, B["g1"], B["b1"], cfg.eps), x, B["attn4"], n, H, W, heads)
+            # the attention half, [layer_norm1 ->] qkv -> window attention -> proj + residual, in one launch (csrc/hiera.hip) ...
+            if P.attn == "attn8_ln":
+                K.hiera_attn8(x, B["attn"], n, P.H, P.W, heads, ln=(B["g1"], B["b1"], cfg.eps))
+            elif P.attn == "attn8":
+                K.hiera_attn8(x, B["attn"], n, P.H, P.W, heads, h=h)
+            elif P.attn == "attn_pool":  # the stage-opening block: pooled q + shortcut
+                x = K.hiera_attn_pool(h, B["attn"], n, P.H, P.W, heads, D)
+            elif P.attn == "attn4":
+                K.hiera_attn4(h, x, B["attn"], n, P.H, P.W, heads)
+            else:  # ... or as separate launches
+                x, h2 = self._attention_half(P, B, h, x, n)
+            rows = n * P.Ho * P.Wo
+            # the FPN's lateral convolution reads a stage output as f16: written by the MLP kernel, not cast later
+            x16 = torch.empty((rows, D), dtype=torch.float16, device=dev) if P.x16 else None
+            h_next = torch.empty((rows, D), dtype=torch.float16, device=dev) if P.emit_ln1 else None
+            if P.mlp == "img":  # (the next block's LayerNorm vectors are packed in)
+                K.ln_mlp_img(x, B["mlp_img"], cfg.eps, x16=x16, h_next=h_next)
+            elif P.mlp == "fused":  # one pass over x (csrc/mlp.hip)
+                K.ln_mlp(x, B["g2"], B["b2"], B["w1"], B["bb1"], B["w2"], B["bb2"], cfg.eps, x16=x16,
+                         next_ln=B["next_ln1"] + (h_next,) if P.emit_ln1 else None)
             else:
-                # (a block whose predecessor ran the fused MLP gets its LayerNorm from that kernel: h_next)
-                h = h_next if h_next is not None else K.layernorm(x, B["g1"], B["b1"], cfg.eps)
-                if dim != D:
-                    if qs and K.pooled_gemm_ok(rows, D):  # the shortcut's projection and its 2 x 2 max-pool in one launch
-                        sc = K.gemm(h, B["wp"], bias=B["bp"], out_dtype=torch.float32, pool_hw=(H, W))
-                    else:
-                        sc = K.gemm(h, B["wp"], bias=B["bp"], out_dtype=torch.float32)
-                        if qs:
-                            pooled = torch.empty((n, H // 2, W // 2, D), dtype=torch.float32, device=dev)
-                            K.maxpool2(sc.view(n, H, W, D), pooled)
-                            sc = pooled.view(-1, D)
-                    res = sc
-                else:
-                    res = x
-                x, H, W, h2 = self._attention_half(B, h, x, res, n, H, W)
-            if qs:
-                Hf //= 2
-            h_next = None
-            x16 = None
-            keep = i in stage_ends and len(stages) >= lowest
-            if D in K.FUSED_MLP_WIDTHS and self.fused_mlp:
-                if keep:  # the FPN's lateral convolution reads this stage output as f16: written here, not cast later
-                    x16 = torch.empty((n * H * W, D), dtype=torch.float16, device=dev)
-                nxt = None
-                if i + 1 < len(self.blocks) and not (self._attn8(i + 1, H, W) and self.blocks[i + 1]["attn8_ln"]):  # the next block's layer_norm1, on the rows while the kernel still holds them
-                    h_next = torch.empty((n * H * W, D), dtype=torch.float16, device=dev)
-                    nxt = (self.blocks[i + 1]["g1"], self.blocks[i + 1]["b1"], h_next)
-                if "mlp_img" in B and K.ln_mlp_img_ok(D, n * H * W):  # the streamed-image form (csrc/hiera.hip): the next block's LayerNorm vectors are packed in
-                    K.ln_mlp_img(x, B["mlp_img"], cfg.eps, x16=x16, h_next=h_next)
-                else:
-                    K.ln_mlp(x, B["g2"], B["b2"], B["w1"], B["bb1"], B["w2"], B["bb2"], cfg.eps, x16=x16, next_ln=nxt)  # one pass over x (csrc/mlp.hip)
-            else:
-                if h2 is None:  # (else: written by the attention projection, proj_ln)
+                if h2 is None:  # (else: written by the attention projection, ln_out)
                     h2 = K.layernorm(x, B["g2"], B["b2"], cfg.eps)
                 u = K.gemm(h2, B["w1"], bias=B["bb1"], act=K.ACT_GELU)
                 K.gemm(u, B["w2"], bias=B["bb2"], res=x, out=x)
-            if i in stage_ends and not keep:
+            if not P.stage_end:
+                continue
+            k = len(stages)
+            if not P.keep:
                 stages.append(None)
                 stages16.append(None)
-            elif i in stage_ends and band:  # the kept output is a tensor of its own: the band's rows, then the constant ones
-                k = len(stages)
-                stages.append(K.band_join(x.view(n, H, W, D), table["stages"][k], Hf))
-                stages16.append(K.band_join(x16.view(n, H, W, D), table["stages16"][k], Hf).view(-1, D) if x16 is not None else None)
-            elif i in stage_ends:
-                stages.append(x.view(n, H, W, D))
+            elif P.join_out:  # the band's rows, then the constant ones
+                stages.append(K.band_join(x.view(n, P.Ho, P.Wo, D), table["stages"][k], P.Hfo))
+                stages16.append(K.band_join(x16.view(n, P.Ho, P.Wo, D), table["stages16"][k], P.Hfo).view(-1, D) if x16 is not None else None)
+            else:
+                stages.append(x.view(n, P.Ho, P.Wo, D))
                 stages16.append(x16)
-                if i != len(self.blocks) - 1 and self.blocks[i + 1]["dim"] == self.blocks[i + 1]["dim_out"]:
-                    x = x.clone()  # the stage output is kept; a same-width next block would update it in place
+                if P.clone:
+                    x = x.clone()
         return stages, stages16  # stages16: f16 copies of the stage outputs where the stage's last kernel wrote one (else None)
 
-    def _attn8(self, i, H, W):
-        """Block i runs its attention half (layer_norm1 included) in lmx_k_hiera_attn8."""
-        B = self.blocks[i]
-        return "attn8" in B and B["dim"] == B["dim_out"] and K.hiera_attn8_ok(B["dim_out"], B["heads"], B["win"], H, W, B["qs"])
-
-    def _attention_half(self, B, h, x, res, n, H, W):
-        """qkv GEMM -> [Q-pool] -> attention -> proj GEMM + residual as separate launches; returns (x, H, W) after the block's pooling
-        and layer_norm2(x) where the projection wrote it (B["proj_ln"]), else None."""
-        D, heads, win, qs = B["dim_out"], B["heads"], B["win"], B["qs"]
+    def _attention_half(self, P, B, h, x, n):
+        """[shortcut GEMM ->] qkv GEMM -> [Q-pool] -> attention -> proj GEMM + residual as separate launches, in the forms P names;
+        returns x after the block's pooling and layer_norm2(x) where the projection wrote it (P.ln_out), else None."""
+        D, heads, win, qs = B["dim_out"], B["heads"], P.window, B["qs"]
         hd = D // heads
-        rows = n * H * W
+        H, W, Hq, Wq = P.H, P.W, P.Ho, P.Wo
         dev = h.device
-        Hq, Wq = H, W
-        if qs and K.pooled_gemm_ok(rows, D):
+        if P.shortcut is None:
+            res = x
+        elif P.shortcut == "pooled_gemm":  # the shortcut's projection and its 2 x 2 max-pool in one launch
+            res = K.gemm(h, B["wp"], bias=B["bp"], out_dtype=torch.float32, pool_hw=(H, W))
+        else:
+            res = K.gemm(h, B["wp"], bias=B["bp"], out_dtype=torch.float32)
+            if P.shortcut == "gemm+maxpool":
+                pooled = torch.empty((n, Hq, Wq, D), dtype=torch.float32, device=dev)
+                K.maxpool2(res.view(n, H, W, D), pooled)
+                res = pooled.view(-1, D)
+        if P.query == "pooled_q+kv":
             # pooled queries: the q third of the projection writes its 2 x 2 max-pool directly (a_mode 2), k and v come from
             # a second launch on the same rows — the full-resolution q is neither written nor read back by a pooling pass
-            Hq, Wq = H // 2, W // 2
             q = K.gemm(h, B["wqkv"][:D], bias=B["bqkv"][:D], pool_hw=(H, W))
             kv = K.gemm(h, B["wqkv"][D:], bias=B["bqkv"][D:])
             k, v = kv[:, :D], kv[:, D:]
         else:
             qkv = K.gemm(h, B["wqkv"], bias=B["bqkv"])
             q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
-            if qs:
-                Hq, Wq = H // 2, W // 2
+            if P.query == "qkv+maxpool":
                 qp = torch.empty((n, Hq, Wq, D), dtype=torch.float16, device=dev)
                 K.maxpool2(qkv.view(n, H, W, 3 * D)[..., :D], qp)
                 q = qp.view(-1, D)
@@ -564,9 +592,9 @@ class HieraEncoder:
         else:
             K.attention(q, k, v, a, n, heads, Hq * Wq, H * W, hd, hd ** -0.5)
         xo = torch.empty((n * Hq * Wq, D), dtype=torch.float32, device=dev) if res is not x else x
-        h2 = torch.empty((n * Hq * Wq, D), dtype=torch.float16, device=dev) if B["proj_ln"] else None
-        K.gemm(a, B["wo"], bias=B["bo"], res=res, out=xo, ln_out=(h2, B["g2"], B["b2"], self.cfg.eps) if B["proj_ln"] else None)
-        return xo, Hq, Wq, h2
+        h2 = torch.empty((n * Hq * Wq, D), dtype=torch.float16, device=dev) if P.ln_out else None
+        K.gemm(a, B["wo"], bias=B["bo"], res=res, out=xo, ln_out=(h2, B["g2"], B["b2"], self.cfg.eps) if P.ln_out else None)
+        return xo, h2
 
     def fpn(self, stages, stages16=None, lowest=0):
         """-> the three highest-resolution levels; lowest: levels below it are not computed (None)."""
