@@ -515,6 +515,68 @@ int lmx_h_mask_features(const uint8_t* mask_host, int h, int w, double* out_host
 int lmx_h_iou_matrix(const double* a, int n, const double* b, int m, double* out);
 int lmx_h_assign(const double* cost, int n, int m, int* row_to_col, int* col_to_row);
 
+/* ---- HOST functions: the coefficient tables of the preprocessing kernels (csrc/host_resample.cpp; all pointers are HOST memory) ----
+ * What a caller of lmx_k_pil_resize_h / _v and lmx_k_float_resize_patchify computes once per frame size and uploads; the C++ twins
+ * of lmx/resample.py, equal to it bit for bit (tests/test_native_dino_host.py).  One axis per call, in_size -> out_size samples,
+ * filt = LMX_FILT_BILINEAR | LMX_FILT_BICUBIC (Pillow's `resample` codes).  bounds_host int32 [out_size * 2] = (first source index,
+ * taps) per output, kk_host [out_size * ksize] (taps beyond a row's count are 0), *ksize_host = the row length.  cap = the entries
+ * kk_host holds; with bounds_host and kk_host both NULL the call only reports *ksize_host.
+ * lmx_h_pil_tables: Pillow's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c) in double, int32 fixed-point weights.
+ * lmx_h_aa_tables:  ATen's antialias weights (UpSampleKernel.cpp _compute_indices_min_size_weights_aa) for a float32 tensor: every
+ *                   step in float32 in ATen's order, the bicubic polynomials with the fused multiply-adds an FMA build of torch makes.
+ * lmx_h_identity_table: the table of an axis that keeps its size n (bounds (i, 1), weight 2^22, ksize 1): lmx_k_pil_resize_h then
+ *                   only swaps the channels.
+ * lmx_h_segment_cols: lmx_k_float_resize_patchify's seg_cols for a horizontal table of n_out rows: the most source columns any
+ *                   run of `tile` (256) consecutive outputs, starting at a multiple of `tile`, reads; < 0 on error. */
+enum { LMX_FILT_BILINEAR = 2, LMX_FILT_BICUBIC = 3 };
+int lmx_h_pil_tables(int in_size, int out_size, int filt, int32_t* bounds_host, int32_t* kk_host, int64_t cap, int* ksize_host);
+int lmx_h_aa_tables(int in_size, int out_size, int filt, int32_t* bounds_host, float* kk_host, int64_t cap, int* ksize_host);
+int lmx_h_identity_table(int n, int32_t* bounds_host, int32_t* kk_host);
+int lmx_h_segment_cols(const int32_t* bounds_host, int n_out, int tile);
+
+/* ==== MODEL level: DINO embeddings from raw frames (csrc/dino_model.hip, csrc/host_dino_image.cpp) ==================================
+ * The whole of services/dinov3-pipeline/app/main.py:98-113 — cvtColor, processor(images=...), model(**inputs), last_hidden_state
+ * .mean(dim=1) — behind one call, for a consumer that is not a Python process: the launch sequence of lmx/dino.py's DinoEmbedder
+ * (preprocess + hidden_states + token_mean) written in C++ over the lmx_k_* entry points above, with the descriptors lmx/kernels.py
+ * fills.  Same launches, same bits as DinoEmbedder.embed_frames (tests/test_gpu_native_dino.py).
+ * The model comes from a WEIGHT IMAGE: one little-endian file that lmx.native.write_dino_image(embedder, path) writes from a loaded
+ * DinoEmbedder (header, config block, tensor directory, tensors in final device form; layout in csrc/dino_image.h).  Loading
+ * safetensors / Hugging Face directories stays in Python: export once, then open the image from C.
+ * Handle rules: a handle belongs to the device that was current at lmx_dino_open_host; every call with another device current is
+ * LMX_EINVAL.  ONE host thread and ONE stream in flight per handle: all calls write the handle's workspace, so a call on another
+ * stream (or lmx_dino_embed_host, which uses a stream of the handle's) needs the previous one finished first.  Several handles are
+ * independent.  Errors: LMX_EINVAL / LMX_EHIP with lmx_last_error(), as everywhere. */
+typedef struct lmx_dino lmx_dino;
+enum { LMX_DINO_V2 = 0, LMX_DINO_V3 = 1 };       /* lmx_dino_info_t.arch */
+enum { LMX_RECIPE_PIL = 0, LMX_RECIPE_FLOAT = 1 }; /* lmx_dino_info_t.recipe_kind: BitImageProcessor | DINOv3ViTImageProcessor */
+typedef struct { int32_t arch, hidden, heads, layers, tokens, image, patch, gated, recipe_kind, max_batch; } lmx_dino_info_t;
+/* HOST only, touches no GPU (the model of services/dinov3-pipeline/app/main.py:98-113; `from_pretrained` at :34-35, the checking half):
+ * parse and validate an image — magic, version,
+ * kind, sizes against the real file, every tensor the config block calls for with the shape it calls for, a head dim the attention
+ * kernels serve.  LMX_EINVAL names the offending field.  info_host (may be NULL) receives the configuration, max_batch 0. */
+int lmx_dino_image_check_host(const char* path_host, lmx_dino_info_t* info_host);
+/* SYNCHRONOUS (the model of services/dinov3-pipeline/app/main.py:98-113; `from_pretrained(...).to(device)` at :34-36): validate the image as above, then allocate and upload the
+ * weights and the workspace of max_batch frames on the CURRENT device.  *out_host is NULL after any failure, with nothing left allocated. */
+int lmx_dino_open_host(const char* path_host, int max_batch, lmx_dino** out_host);
+/* the end of the model of services/dinov3-pipeline/app/main.py:98-113: waits for the device, then frees everything the handle owns;
+ * NULL is allowed */
+void lmx_dino_close(lmx_dino* m);
+/* the configuration of the model behind services/dinov3-pipeline/app/main.py:98-113 (hidden = `last_hidden_state.shape[-1]`, :77) and
+ * the handle's max_batch */
+int lmx_dino_info(const lmx_dino* m, lmx_dino_info_t* info_host);
+/* SYNCHRONOUS (services/dinov3-pipeline/app/main.py:98-113, what `processor(images=...)` at :107 derives from the frame size): build the resize tables of an h x w
+ * frame on the host, allocate the resized-frame workspace, upload.  A size already prepared is a lookup.  LMX_EINVAL for a frame that
+ * resizes below the network's input, and beyond 16 sizes per handle. */
+int lmx_dino_prepare(lmx_dino* m, int h, int w);
+/* services/dinov3-pipeline/app/main.py:98-113 for n frames: frames u8 [n][h][w][3] (BGR as cv2 delivers them; rgb != 0: already RGB) -> emb f32 [n][hidden],
+ * the mean over ALL tokens of the final LayerNorm.  For a frame size already prepared the call ONLY ENQUEUES on `stream`: no allocation,
+ * no synchronisation; the first call for a new size runs lmx_dino_prepare itself, and THAT call synchronises.  n > max_batch runs in
+ * chunks of max_batch (a frame's bits do not depend on the batch it rides in, so the result is the same). */
+int lmx_dino_embed(lmx_dino* m, const uint8_t* frames, int n, int h, int w, int rgb, float* emb, lmx_stream_t stream);
+/* services/dinov3-pipeline/app/main.py:98-113 for a caller with no HIP code of its own: frames_host and emb_host are HOST memory; uploads, embeds,
+ * downloads and synchronises (examples/dino_embed.c). */
+int lmx_dino_embed_host(lmx_dino* m, const uint8_t* frames_host, int n, int h, int w, int rgb, float* emb_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,405 @@
+// dino_model.hip — the model-level entry points of the C-ABI for DINO: a handle that owns the weights of one weight image
+// (dino_image.h) and the workspace of one batch, and lmx_dino_embed, the launch sequence of lmx/dino.py's DinoEmbedder
+// (preprocess + hidden_states + token_mean; services/dinov3-pipeline/app/main.py:98-113) written as host C++.
+// HOST code only: there is no kernel in this file.  Every launch goes through the same extern "C" lmx_k_* entry point the ctypes
+// binding calls, with the descriptor filled as lmx/kernels.py fills it, so the embedding is the Python plan's bit for bit
+// (tests/test_gpu_native_dino.py).
+#include <math.h>
+#include <string.h>
+
+#include <map>
+#include <memory>
+#include <utility>
+#include <vector>
+
+#include "common.h"
+#include "dino_image.h"
+
+namespace {
+
+const int MAX_FRAME_SIZES = 16;  // prepared frame sizes a handle keeps (each owns its resized-frame workspace)
+
+size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+
+// what lmx_dino_prepare builds for one frame size: the resize tables and the resized-frame workspace, one device allocation
+struct FrameSize {
+  int nh = 0, nw = 0;
+  char* blob = nullptr;
+  // pil: tab_h always (identity if the width is kept), tab_v only if the height changes; float: both, already cut to the crop
+  int32_t *bounds_h = nullptr, *bounds_v = nullptr;
+  void *kk_h = nullptr, *kk_v = nullptr;  // i32 (pil) / f32 (float)
+  int ksize_h = 0, ksize_v = 0, seg_cols = 0;
+  uint8_t *tmp_h = nullptr, *tmp_v = nullptr;  // pil: [max_batch, h, nw, 3] after the horizontal pass, [max_batch, nh, nw, 3] after the vertical
+};
+
+struct Layer {
+  const float *g1, *b1, *bqkv, *bo, *ls1, *g2, *b2, *bb1, *bb2, *ls2;
+  const void *wqkv, *wo, *w1, *w2;
+};
+
+}  // namespace
+
+struct lmx_dino {
+  int device = -1, max_batch = 0;
+  LmxDinoCfg cfg;
+  char* weights = nullptr;  // the data section of the image
+  char* work = nullptr;     // the workspace of max_batch frames
+  hipStream_t own = nullptr;  // lmx_dino_embed_host's stream
+  // weights
+  const void* pe_w = nullptr;
+  const float *pe_b = nullptr, *prefix = nullptr, *pos = nullptr, *rope_cos = nullptr, *rope_sin = nullptr, *gf = nullptr, *bf = nullptr,
+              *lut = nullptr;
+  std::vector<Layer> layers;
+  // workspace: patch matrix, patch embedding, residual stream, LayerNorm rows, qkv, attention output, MLP intermediate, final rows
+  void *patches = nullptr, *xp = nullptr, *h = nullptr, *qkv = nullptr, *a = nullptr, *u = nullptr;
+  float *x = nullptr, *y = nullptr;
+  float mean_std[6];
+  std::map<std::pair<int, int>, FrameSize> sizes;
+  // lmx_dino_embed_host's staging buffers (grown on demand; that call synchronises anyway)
+  uint8_t* stage_frames = nullptr;
+  size_t stage_bytes = 0;
+  float* stage_emb = nullptr;
+};
+
+namespace {
+
+void destroy(lmx_dino* m) {
+  if (!m) return;
+  for (auto& kv : m->sizes) (void)hipFree(kv.second.blob);
+  (void)hipFree(m->stage_frames);
+  (void)hipFree(m->stage_emb);
+  (void)hipFree(m->work);
+  (void)hipFree(m->weights);
+  if (m->own) (void)hipStreamDestroy(m->own);
+  delete m;
+}
+
+int on_device(const lmx_dino* m, const char* fn) {
+  LMX_REQUIRE(m != nullptr, "%s: null handle", fn);
+  int cur = -1;
+  LMX_HIP(hipGetDevice(&cur));
+  LMX_REQUIRE(cur == m->device, "%s: the handle was opened on device %d, the current device is %d", fn, m->device, cur);
+  return LMX_OK;
+}
+
+// the data section of the image into one device allocation, through a bounded host buffer
+int upload_weights(const char* path, const LmxDinoImage& img, char** out) {
+  const uint64_t total = img.file_bytes - img.data_offset;
+  LMX_REQUIRE(total > 0, "lmx_dino_open_host: the image holds no tensor data");
+  FILE* f = fopen(path, "rb");
+  LMX_REQUIRE(f, "lmx_dino_open_host: cannot open '%s'", path);
+  std::unique_ptr<FILE, int (*)(FILE*)> closer(f, fclose);
+  LMX_REQUIRE(fseeko(f, (off_t)img.data_offset, SEEK_SET) == 0, "lmx_dino_open_host: cannot seek to data_offset");
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(out), (size_t)total));
+  const size_t chunk = (size_t)64 << 20;
+  std::vector<char> buf((size_t)(total < chunk ? total : chunk));
+  for (uint64_t done = 0; done < total;) {
+    const size_t n = (size_t)(total - done < chunk ? total - done : chunk);
+    LMX_REQUIRE(fread(buf.data(), 1, n, f) == n, "lmx_dino_open_host: the file ends inside the tensor data (truncated while reading?)");
+    LMX_HIP(hipMemcpy(*out + done, buf.data(), n, hipMemcpyHostToDevice));
+    done += n;
+  }
+  return LMX_OK;
+}
+
+int open_into(lmx_dino* m, const char* path, int max_batch) {
+  LmxDinoImage img;
+  LMX_TRY(lmx_dino_image_parse(path, &img));
+  const LmxDinoCfg& c = img.cfg;
+  const int64_t widest = (int64_t)(3 * c.hidden > 2 * c.mlp ? 3 * c.hidden : 2 * c.mlp);
+  LMX_REQUIRE((int64_t)max_batch * c.tokens * widest < ((int64_t)1 << 31),
+              "lmx_dino_open_host: max_batch %d x tokens %d x the widest row %lld does not fit 32-bit element indices", max_batch, c.tokens,
+              (long long)widest);
+  m->cfg = c;
+  m->max_batch = max_batch;
+  LMX_HIP(hipGetDevice(&m->device));
+  for (int i = 0; i < 3; ++i) {
+    m->mean_std[i] = (float)c.mean[i];
+    m->mean_std[3 + i] = (float)c.std[i];
+  }
+  LMX_TRY(upload_weights(path, img, &m->weights));
+  const uint64_t base = img.data_offset;
+  auto at = [&](const LmxTensorRef& r) -> const void* { return r.nbytes ? m->weights + (r.offset - base) : nullptr; };
+  auto f32 = [&](const LmxTensorRef& r) { return static_cast<const float*>(at(r)); };
+  m->pe_w = at(img.pe_w);
+  m->pe_b = f32(img.pe_b);
+  m->prefix = f32(img.prefix);
+  m->pos = f32(img.pos);
+  m->rope_cos = f32(img.rope_cos);
+  m->rope_sin = f32(img.rope_sin);
+  m->gf = f32(img.gf);
+  m->bf = f32(img.bf);
+  m->lut = f32(img.lut);
+  for (const LmxDinoLayerRefs& r : img.layers)
+    m->layers.push_back(Layer{f32(r.g1), f32(r.b1), f32(r.bqkv), f32(r.bo), f32(r.ls1), f32(r.g2), f32(r.b2), f32(r.bb1), f32(r.bb2), f32(r.ls2),
+                              at(r.wqkv), at(r.wo), at(r.w1), at(r.w2)});
+
+  // the workspace of max_batch frames: one allocation, every buffer on a 256-byte boundary
+  const size_t B = (size_t)max_batch, T = (size_t)c.tokens, D = (size_t)c.hidden, I = (size_t)c.mlp, np = (size_t)c.grid * c.grid;
+  const size_t sz[8] = {B * np * c.k_pad * 2, B * np * D * 2, B * T * D * 4, B * T * D * 2, B * T * 3 * D * 2, B * T * D * 2, B * T * I * 2, B * T * D * 4};
+  size_t off[8], total = 0;
+  for (int i = 0; i < 8; ++i) {
+    off[i] = total;
+    total += up256(sz[i]);
+  }
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->work), total));
+  // the patch matrix's columns beyond 3 * patch^2 (k_pad) are never written by a kernel: zero once, as kernels.patchify_norm's torch.zeros
+  LMX_HIP(hipMemset(m->work + off[0], 0, sz[0]));
+  m->patches = m->work + off[0];
+  m->xp = m->work + off[1];
+  m->x = reinterpret_cast<float*>(m->work + off[2]);
+  m->h = m->work + off[3];
+  m->qkv = m->work + off[4];
+  m->a = m->work + off[5];
+  m->u = m->work + off[6];
+  m->y = reinterpret_cast<float*>(m->work + off[7]);
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->stage_emb), B * D * 4));
+  LMX_HIP(hipStreamCreate(&m->own));
+  LMX_HIP(hipDeviceSynchronize());
+  return LMX_OK;
+}
+
+// one axis of the float recipe: ATen's table, cut to the rows the centre crop keeps (TorchvisionBackend.center_crop: int((size - crop) / 2))
+int aa_axis(int in_size, int out_size, int filt, int S, std::vector<int32_t>* bounds, std::vector<float>* kk, int* ksize) {
+  LMX_TRY(lmx_h_aa_tables(in_size, out_size, filt, nullptr, nullptr, 0, ksize));
+  std::vector<int32_t> b((size_t)out_size * 2);
+  std::vector<float> k((size_t)out_size * *ksize);
+  LMX_TRY(lmx_h_aa_tables(in_size, out_size, filt, b.data(), k.data(), (int64_t)k.size(), ksize));
+  const int o = (int)((out_size - S) / 2.0);
+  bounds->assign(b.begin() + 2 * (size_t)o, b.begin() + 2 * (size_t)(o + S));
+  kk->assign(k.begin() + (size_t)o * *ksize, k.begin() + (size_t)(o + S) * *ksize);
+  return LMX_OK;
+}
+
+int prepare(lmx_dino* m, int h, int w, const FrameSize** out) {
+  const LmxDinoCfg& c = m->cfg;
+  const auto it = m->sizes.find({h, w});
+  if (it != m->sizes.end()) {
+    if (out) *out = &it->second;
+    return LMX_OK;
+  }
+  FrameSize fs;
+  LMX_TRY(lmx_dino_resized(c, h, w, &fs.nh, &fs.nw));
+  LMX_REQUIRE((int)m->sizes.size() < MAX_FRAME_SIZES, "lmx_dino_prepare: the handle already holds %d frame sizes; open another for more", MAX_FRAME_SIZES);
+  const int nh = fs.nh, nw = fs.nw;
+  std::vector<int32_t> bh, bv;
+  std::vector<char> kh, kv;  // i32 or f32 bytes
+  size_t tmp_h = 0, tmp_v = 0;
+  if (c.recipe_kind == LMX_RECIPE_PIL) {
+    // the horizontal pass always runs: it also does the BGR->RGB swap (identity table if the width is kept)
+    bh.resize((size_t)nw * 2);
+    if (nw != w) {
+      LMX_TRY(lmx_h_pil_tables(w, nw, c.filt, nullptr, nullptr, 0, &fs.ksize_h));
+      kh.resize((size_t)nw * fs.ksize_h * 4);
+      LMX_TRY(lmx_h_pil_tables(w, nw, c.filt, bh.data(), reinterpret_cast<int32_t*>(kh.data()), (int64_t)nw * fs.ksize_h, &fs.ksize_h));
+    } else {
+      fs.ksize_h = 1;
+      kh.resize((size_t)nw * 4);
+      LMX_TRY(lmx_h_identity_table(nw, bh.data(), reinterpret_cast<int32_t*>(kh.data())));
+    }
+    tmp_h = (size_t)m->max_batch * h * nw * 3;
+    if (nh != h) {
+      LMX_TRY(lmx_h_pil_tables(h, nh, c.filt, nullptr, nullptr, 0, &fs.ksize_v));
+      bv.resize((size_t)nh * 2);
+      kv.resize((size_t)nh * fs.ksize_v * 4);
+      LMX_TRY(lmx_h_pil_tables(h, nh, c.filt, bv.data(), reinterpret_cast<int32_t*>(kv.data()), (int64_t)nh * fs.ksize_v, &fs.ksize_v));
+      tmp_v = (size_t)m->max_batch * nh * nw * 3;
+    }
+  } else {
+    std::vector<float> fh, fv;
+    LMX_TRY(aa_axis(w, nw, c.filt, c.image, &bh, &fh, &fs.ksize_h));
+    LMX_TRY(aa_axis(h, nh, c.filt, c.image, &bv, &fv, &fs.ksize_v));
+    kh.assign(reinterpret_cast<char*>(fh.data()), reinterpret_cast<char*>(fh.data() + fh.size()));
+    kv.assign(reinterpret_cast<char*>(fv.data()), reinterpret_cast<char*>(fv.data() + fv.size()));
+    fs.seg_cols = lmx_h_segment_cols(bh.data(), c.image, 256);
+    LMX_REQUIRE(fs.seg_cols > 0, "lmx_dino_prepare: empty horizontal table for %d -> %d", w, nw);
+  }
+  const size_t sz[6] = {bh.size() * 4, kh.size(), bv.size() * 4, kv.size(), tmp_h, tmp_v};
+  size_t off[6], total = 0;
+  for (int i = 0; i < 6; ++i) {
+    off[i] = total;
+    total += up256(sz[i]);
+  }
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&fs.blob), total));
+  const void* src[4] = {bh.data(), kh.data(), bv.data(), kv.data()};
+  for (int i = 0; i < 4; ++i)
+    if (sz[i]) {
+      const hipError_t e = hipMemcpy(fs.blob + off[i], src[i], sz[i], hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        (void)hipFree(fs.blob);
+        LMX_HIP(e);
+      }
+    }
+  fs.bounds_h = reinterpret_cast<int32_t*>(fs.blob + off[0]);
+  fs.kk_h = fs.blob + off[1];
+  fs.bounds_v = sz[2] ? reinterpret_cast<int32_t*>(fs.blob + off[2]) : nullptr;
+  fs.kk_v = sz[3] ? fs.blob + off[3] : nullptr;
+  fs.tmp_h = sz[4] ? reinterpret_cast<uint8_t*>(fs.blob + off[4]) : nullptr;
+  fs.tmp_v = sz[5] ? reinterpret_cast<uint8_t*>(fs.blob + off[5]) : nullptr;
+  const auto ins = m->sizes.emplace(std::make_pair(h, w), fs);
+  if (out) *out = &ins.first->second;
+  return LMX_OK;
+}
+
+int gemm(const void* A, int64_t lda, const void* W, const float* bias, void* C, int64_t ldc, int out_dtype, int M, int N, int K, int act,
+         const float* scale, const void* res, int64_t ldr, hipStream_t st) {
+  lmx_gemm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.A = A;
+  d.W = W;
+  d.bias = bias;
+  d.scale = scale;
+  d.res = res;
+  d.C = C;
+  d.lda = lda;
+  d.ldc = ldc;
+  d.ldr = res ? ldr : 0;
+  d.M = M;
+  d.N = N;
+  d.K = K;
+  d.act = act;
+  d.out_dtype = out_dtype;
+  d.a_mode = 0;
+  d.a_rep = 1;
+  return lmx_k_gemm(&d, st);
+}
+
+// DinoEmbedder.preprocess + hidden_states + token_mean for n <= max_batch frames
+int embed_chunk(lmx_dino* m, const FrameSize& fs, const uint8_t* frames, int n, int h, int w, int rgb, float* emb, hipStream_t st) {
+  const LmxDinoCfg& c = m->cfg;
+  const int D = c.hidden, H = c.heads, hd = D / H, T = c.tokens, I = c.mlp, np = c.grid * c.grid, rows = n * T;
+  if (c.recipe_kind == LMX_RECIPE_FLOAT) {
+    LMX_TRY(lmx_k_float_resize_patchify(frames, m->patches, n, h, w, c.grid, c.grid, c.patch, c.k_pad, fs.bounds_h,
+                                        static_cast<const float*>(fs.kk_h), fs.ksize_h, fs.bounds_v, static_cast<const float*>(fs.kk_v), fs.ksize_v,
+                                        fs.seg_cols, (float)c.rescale, m->mean_std, rgb ? 0 : 1, st));
+  } else {
+    LMX_TRY(lmx_k_pil_resize_h(frames, fs.tmp_h, n, h, w, fs.nw, fs.bounds_h, static_cast<const int32_t*>(fs.kk_h), fs.ksize_h, rgb ? 0 : 1, st));
+    const uint8_t* img = fs.tmp_h;
+    if (fs.tmp_v) {
+      LMX_TRY(lmx_k_pil_resize_v(fs.tmp_h, fs.tmp_v, n, h, fs.nh, fs.nw, fs.bounds_v, static_cast<const int32_t*>(fs.kk_v), fs.ksize_v, st));
+      img = fs.tmp_v;
+    }
+    LMX_TRY(lmx_k_patchify_norm(img, m->patches, n, fs.nh, fs.nw, (fs.nh - c.image) / 2, (fs.nw - c.image) / 2, c.grid, c.grid, c.patch, c.k_pad,
+                                m->lut, st));
+  }
+  LMX_TRY(gemm(m->patches, c.k_pad, m->pe_w, m->pe_b, m->xp, D, LMX_F16, n * np, D, c.k_pad, LMX_ACT_NONE, nullptr, nullptr, 0, st));
+  LMX_TRY(lmx_k_assemble_tokens(m->xp, m->prefix, m->pos, m->x, n, np, c.n_prefix, D, st));
+  const float scale = (float)pow((double)hd, -0.5), eps = (float)c.eps;
+  const int act1 = c.gated ? LMX_ACT_SWIGLU : LMX_ACT_GELU, N1 = c.gated ? 2 * I : I;
+  half_t* q = static_cast<half_t*>(m->qkv);
+  for (const Layer& L : m->layers) {
+    LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, L.g1, L.b1, m->h, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
+    LMX_TRY(gemm(m->h, D, L.wqkv, L.bqkv, m->qkv, 3 * D, LMX_F16, rows, 3 * D, D, LMX_ACT_NONE, nullptr, nullptr, 0, st));
+    if (m->rope_cos) {
+      LMX_TRY(lmx_k_rope(q, 3 * D, n, T, H, hd, c.n_prefix, m->rope_cos, m->rope_sin, st));
+      LMX_TRY(lmx_k_rope(q + D, 3 * D, n, T, H, hd, c.n_prefix, m->rope_cos, m->rope_sin, st));
+    }
+    lmx_attn_desc ad;
+    memset(&ad, 0, sizeof(ad));
+    ad.Q = q;
+    ad.K = q + D;
+    ad.V = q + 2 * D;
+    ad.O = m->a;
+    ad.ldq = ad.ldk = ad.ldv = 3 * D;
+    ad.ldo = D;
+    ad.B = n;
+    ad.H = H;
+    ad.Tq = ad.Tk = T;
+    ad.hd = hd;
+    ad.scale = scale;
+    ad.mode = 0;
+    LMX_TRY(lmx_k_attention(&ad, st));
+    LMX_TRY(gemm(m->a, D, L.wo, L.bo, m->x, D, LMX_F32, rows, D, D, LMX_ACT_NONE, L.ls1, m->x, D, st));
+    LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, L.g2, L.b2, m->h, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
+    LMX_TRY(gemm(m->h, D, L.w1, L.bb1, m->u, I, LMX_F16, rows, N1, D, act1, nullptr, nullptr, 0, st));
+    LMX_TRY(gemm(m->u, I, L.w2, L.bb2, m->x, D, LMX_F32, rows, D, I, LMX_ACT_NONE, L.ls2, m->x, D, st));
+  }
+  LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, m->gf, m->bf, m->y, LMX_F32, D, rows, D, eps, LMX_ACT_NONE, st));
+  return lmx_k_token_mean(m->y, LMX_F32, emb, n, T, D, st);
+}
+
+int check_frames(const lmx_dino* m, const char* fn, const void* frames, int n, int h, int w, const void* emb) {
+  LMX_TRY(on_device(m, fn));
+  LMX_REQUIRE(n > 0, "%s: n = %d frames", fn, n);
+  LMX_REQUIRE(h > 0 && w > 0, "%s: frame size %d x %d", fn, h, w);
+  LMX_REQUIRE(frames && emb, "%s: null pointer", fn);
+  return LMX_OK;
+}
+
+}  // namespace
+
+extern "C" int lmx_dino_open_host(const char* path_host, int max_batch, lmx_dino** out_host) {
+  LMX_REQUIRE(out_host != nullptr, "lmx_dino_open_host: out_host is null");
+  *out_host = nullptr;
+  LMX_REQUIRE(path_host != nullptr, "lmx_dino_open_host: path_host is null");
+  LMX_REQUIRE(max_batch > 0 && max_batch <= 65535, "lmx_dino_open_host: max_batch %d outside 1 .. 65535", max_batch);
+  lmx_dino* m = new lmx_dino();
+  const int rc = open_into(m, path_host, max_batch);
+  if (rc != LMX_OK) {
+    destroy(m);  // everything a failed open allocated; the error text of the failing step stays
+    return rc;
+  }
+  *out_host = m;
+  return LMX_OK;
+}
+
+extern "C" void lmx_dino_close(lmx_dino* m) {
+  if (!m) return;
+  // work that still reads the handle's memory must be done before it is freed; frees follow the handle's device
+  int cur = -1;
+  const bool sw = hipGetDevice(&cur) == hipSuccess && cur != m->device && hipSetDevice(m->device) == hipSuccess;
+  (void)hipDeviceSynchronize();
+  destroy(m);
+  if (sw) (void)hipSetDevice(cur);
+}
+
+extern "C" int lmx_dino_info(const lmx_dino* m, lmx_dino_info_t* info_host) {
+  LMX_REQUIRE(m && info_host, "lmx_dino_info: null argument");
+  lmx_dino_fill_info(m->cfg, m->max_batch, info_host);
+  return LMX_OK;
+}
+
+extern "C" int lmx_dino_prepare(lmx_dino* m, int h, int w) {
+  LMX_TRY(on_device(m, "lmx_dino_prepare"));
+  return prepare(m, h, w, nullptr);
+}
+
+extern "C" int lmx_dino_embed(lmx_dino* m, const uint8_t* frames, int n, int h, int w, int rgb, float* emb, lmx_stream_t stream) {
+  LMX_TRY(check_frames(m, "lmx_dino_embed", frames, n, h, w, emb));
+  const FrameSize* fs = nullptr;
+  LMX_TRY(prepare(m, h, w, &fs));  // a size seen before: a lookup
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int st_dev = -1;
+  LMX_TRY(lmx_stream_device(st, &st_dev));
+  LMX_REQUIRE(st_dev == m->device, "lmx_dino_embed: the stream belongs to device %d, the handle to device %d", st_dev, m->device);
+  const size_t frame_bytes = (size_t)h * w * 3;
+  for (int done = 0; done < n; done += m->max_batch) {
+    const int nb = n - done < m->max_batch ? n - done : m->max_batch;
+    LMX_TRY(embed_chunk(m, *fs, frames + (size_t)done * frame_bytes, nb, h, w, rgb, emb + (size_t)done * m->cfg.hidden, st));
+  }
+  return LMX_OK;
+}
+
+extern "C" int lmx_dino_embed_host(lmx_dino* m, const uint8_t* frames_host, int n, int h, int w, int rgb, float* emb_host) {
+  LMX_TRY(check_frames(m, "lmx_dino_embed_host", frames_host, n, h, w, emb_host));
+  const FrameSize* fs = nullptr;
+  LMX_TRY(prepare(m, h, w, &fs));
+  const size_t frame_bytes = (size_t)h * w * 3, D = (size_t)m->cfg.hidden;
+  const size_t need = frame_bytes * (size_t)(n < m->max_batch ? n : m->max_batch);
+  if (need > m->stage_bytes) {
+    LMX_HIP(hipStreamSynchronize(m->own));
+    (void)hipFree(m->stage_frames);
+    m->stage_frames = nullptr;
+    m->stage_bytes = 0;
+    LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->stage_frames), need));
+    m->stage_bytes = need;
+  }
+  for (int done = 0; done < n; done += m->max_batch) {
+    const int nb = n - done < m->max_batch ? n - done : m->max_batch;
+    LMX_HIP(hipMemcpyAsync(m->stage_frames, frames_host + (size_t)done * frame_bytes, nb * frame_bytes, hipMemcpyHostToDevice, m->own));
+    LMX_TRY(embed_chunk(m, *fs, m->stage_frames, nb, h, w, rgb, m->stage_emb, m->own));
+    LMX_HIP(hipMemcpyAsync(emb_host + (size_t)done * D, m->stage_emb, nb * D * sizeof(float), hipMemcpyDeviceToHost, m->own));
+    LMX_HIP(hipStreamSynchronize(m->own));
+  }
+  return LMX_OK;
+}

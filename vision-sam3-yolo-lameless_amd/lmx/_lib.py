@@ -27,6 +27,10 @@ class GemmDesc(C.Structure):
     ]
 
 
+class DinoInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("arch", "hidden", "heads", "layers", "tokens", "image", "patch", "gated", "recipe_kind", "max_batch")]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [
         ("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p),
@@ -102,6 +106,17 @@ SIGNATURES = {
     "lmx_k_mask_logits": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     "lmx_k_mask_score": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _D, _D, _VP, _VP, _VP]),
     "lmx_k_nms_boxes": (_I, [_VP, _I64, _VP, _VP, _I, _D, _VP, _VP, _VP, _VP]),
+    "lmx_h_pil_tables": (_I, [_I, _I, _I, _VP, _VP, _I64, C.POINTER(C.c_int)]),
+    "lmx_h_aa_tables": (_I, [_I, _I, _I, _VP, _VP, _I64, C.POINTER(C.c_int)]),
+    "lmx_h_identity_table": (_I, [_I, _VP, _VP]),
+    "lmx_h_segment_cols": (_I, [_VP, _I, _I]),
+    "lmx_dino_image_check_host": (_I, [C.c_char_p, C.POINTER(DinoInfo)]),
+    "lmx_dino_open_host": (_I, [C.c_char_p, _I, C.POINTER(_VP)]),
+    "lmx_dino_close": (None, [_VP]),
+    "lmx_dino_info": (_I, [_VP, C.POINTER(DinoInfo)]),
+    "lmx_dino_prepare": (_I, [_VP, _I, _I]),
+    "lmx_dino_embed": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP]),
+    "lmx_dino_embed_host": (_I, [_VP, _VP, _I, _I, _I, _I, _VP]),
 }
 
 _lib = None

@@ -1,0 +1,199 @@
+"""The model-level C entry points (include/lmx.h, "MODEL level"; csrc/dino_model.hip) seen from Python.
+
+``write_dino_image`` exports a loaded ``DinoEmbedder`` as a weight image: one little-endian file holding the embedder's tensors
+bit for bit in their final device form (csrc/dino_image.h has the layout).  A C program opens it with ``lmx_dino_open_host`` and
+asks ``lmx_dino_embed`` / ``lmx_dino_embed_host`` for embeddings without Python (examples/dino_embed.c).
+
+``NativeDino`` is the thin binding of that handle.  No plan logic lives here: the launch sequence is C++, and it is the launch
+sequence of ``DinoEmbedder.embed_frames`` — same entry points, same descriptors, same bits (tests/test_gpu_native_dino.py).
+The host table functions (``lmx_h_pil_tables``, ``lmx_h_aa_tables``, ...) are bound too, for the tests that hold them to
+lmx/resample.py."""
+import ctypes as C
+import struct
+
+import numpy as np
+import torch
+
+from . import _lib, resample
+from ._lib import DinoInfo, LmxError, check
+
+MAGIC = b"LMXIMAGE"
+VERSION = 1
+KIND_DINO, KIND_YOLO, KIND_SAM = 1, 2, 3
+HEADER_BYTES, ENTRY_BYTES, NAME_BYTES = 48, 88, 48
+ARCH = {"dinov2": 0, "dinov3": 1}
+RECIPE = {"pil": 0, "float": 1}
+FILT = {resample.BILINEAR: 2, resample.BICUBIC: 3}  # Pillow's `resample` codes (LMX_FILT_*)
+_DTYPE = {np.dtype(np.float16): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2}
+LAYER_TENSORS = ("g1", "b1", "wqkv", "bqkv", "wo", "bo", "ls1", "g2", "b2", "w1", "bb1", "w2", "bb2", "ls2")
+
+
+def dino_config_block(embedder):
+    """The fixed config block of a DINO image: 20 int32 then 8 float64 (LmxDinoCfg, csrc/dino_image.h)."""
+    cfg, rc = embedder.cfg, embedder.recipe
+    size_h, size_w = rc.size_hw if rc.size_hw is not None else (0, 0)
+    ints = (ARCH[cfg.arch], cfg.hidden, cfg.heads, cfg.layers, cfg.mlp, int(cfg.gated), cfg.patch, cfg.image, cfg.grid, cfg.n_prefix,
+            cfg.tokens, embedder.k_pad, int(embedder.pos is not None), int(embedder.rope is not None), RECIPE[rc.kind], FILT[rc.filt],
+            (rc.shortest_edge or 0) if rc.size_hw is None else 0, size_h, size_w, rc.crop or 0)
+    return struct.pack("<20i8d", *ints, cfg.eps, rc.rescale, *rc.mean, *rc.std)
+
+
+def dino_tensors(embedder):
+    """Ordered {name: numpy array}: exactly the tensors the embedder holds, in its dtypes."""
+    def host(t):
+        return np.ascontiguousarray(t.detach().cpu().numpy())
+
+    e = embedder
+    out = {"pe_w": host(e.pe_w), "pe_b": host(e.pe_b), "prefix": host(e.prefix)}
+    if e.pos is not None:
+        out["pos"] = host(e.pos)
+    if e.rope is not None:
+        out["rope_cos"], out["rope_sin"] = host(e.rope[0]), host(e.rope[1])
+    for i, L in enumerate(e.layers):
+        for n in LAYER_TENSORS:
+            out[f"layer.{i}.{n}"] = host(L[n])
+    out["gf"], out["bf"], out["lut"] = host(e.gf), host(e.bf), host(e.lut)
+    return out
+
+
+def write_image(path, kind, config_block, tensors):
+    """header | config block | directory | data (64-byte aligned tensors).  Returns the file's size."""
+    n = len(tensors)
+    dir_offset = HEADER_BYTES + len(config_block)
+    data_offset = (dir_offset + n * ENTRY_BYTES + 63) // 64 * 64
+    entries, off = [], data_offset
+    for name, a in tensors.items():
+        raw = name.encode()
+        if len(raw) >= NAME_BYTES or a.dtype not in _DTYPE or not 1 <= a.ndim <= 4:
+            raise LmxError(f"write_image: tensor {name!r} ({a.dtype}, rank {a.ndim}) does not fit a directory entry")
+        shape = tuple(a.shape) + (0,) * (4 - a.ndim)
+        entries.append(struct.pack(f"<{NAME_BYTES}sII4iQQ", raw, _DTYPE[a.dtype], a.ndim, *shape, off, a.nbytes))
+        off = (off + a.nbytes + 63) // 64 * 64
+    file_bytes = off
+    with open(path, "wb") as f:
+        f.write(struct.pack("<8sIIIIQQQ", MAGIC, VERSION, kind, len(config_block), n, dir_offset, data_offset, file_bytes))
+        f.write(config_block)
+        f.write(b"".join(entries))
+        for a in tensors.values():
+            f.write(b"\0" * (-f.tell() % 64))
+            f.write(a.tobytes())
+        f.write(b"\0" * (file_bytes - f.tell()))
+    return file_bytes
+
+
+def write_dino_image(embedder, path):
+    """Export a DinoEmbedder (any device) as the weight image lmx_dino_open_host reads.  Returns the file's size in bytes."""
+    return write_image(path, KIND_DINO, dino_config_block(embedder), dino_tensors(embedder))
+
+
+def check_dino_image(path):
+    """lmx_dino_image_check_host: validate an image on the host (no GPU) -> DinoInfo; LmxError names the offending field."""
+    info = DinoInfo()
+    check(_lib.load().lmx_dino_image_check_host(str(path).encode(), C.byref(info)), "lmx_dino_image_check_host")
+    return info
+
+
+# ---- the host table functions (csrc/host_resample.cpp) ---------------------------------------------------------------------
+def _tables(fn, kk_dtype, in_size, out_size, filt):
+    ks = C.c_int(0)
+    check(fn(in_size, out_size, FILT[filt], None, None, 0, C.byref(ks)), fn.__name__)
+    bounds, kk = np.empty(out_size * 2, np.int32), np.empty(out_size * ks.value, kk_dtype)
+    check(fn(in_size, out_size, FILT[filt], bounds.ctypes.data, kk.ctypes.data, kk.size, C.byref(ks)), fn.__name__)
+    return bounds, kk, ks.value
+
+
+def pil_tables(in_size, out_size, filt):
+    """lmx_h_pil_tables: the C++ twin of resample.coeff_tables, same return value."""
+    return _tables(_lib.load().lmx_h_pil_tables, np.int32, in_size, out_size, filt)
+
+
+def aa_tables(in_size, out_size, filt):
+    """lmx_h_aa_tables: the C++ twin of resample.aa_tables, same return value."""
+    return _tables(_lib.load().lmx_h_aa_tables, np.float32, in_size, out_size, filt)
+
+
+def identity_table(n):
+    """lmx_h_identity_table: the table of an axis that keeps its size (lmx.dino._identity_table)."""
+    bounds, kk = np.empty(n * 2, np.int32), np.empty(n, np.int32)
+    check(_lib.load().lmx_h_identity_table(n, bounds.ctypes.data, kk.ctypes.data), "lmx_h_identity_table")
+    return bounds, kk, 1
+
+
+def segment_cols(bounds, tile=256):
+    """lmx_h_segment_cols: the C++ twin of resample.segment_cols."""
+    b = np.ascontiguousarray(bounds, dtype=np.int32).reshape(-1)
+    r = _lib.load().lmx_h_segment_cols(b.ctypes.data, b.size // 2, tile)
+    check(min(r, 0), "lmx_h_segment_cols")
+    return r
+
+
+# ---- the model handle ------------------------------------------------------------------------------------------------------
+class NativeDino:
+    """lmx_dino_open_host(path, max_batch) on `device` (default: torch's current device)."""
+
+    def __init__(self, path, max_batch, device=None):
+        self._lib = _lib.load()
+        self._h = None
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise LmxError(f"NativeDino: {self.device} is not a GPU")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        h = C.c_void_p(0)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_dino_open_host(str(path).encode(), int(max_batch), C.byref(h)), "lmx_dino_open_host")
+        self._h = h
+        self.info = DinoInfo()
+        check(self._lib.lmx_dino_info(self._h, C.byref(self.info)), "lmx_dino_info")
+
+    def _handle(self):
+        if self._h is None:
+            raise LmxError("NativeDino: the handle is closed")
+        return self._h
+
+    def prepare(self, h, w):
+        """lmx_dino_prepare: tables and workspace of one frame size (synchronous); embed() of that size then only enqueues."""
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_dino_prepare(self._handle(), int(h), int(w)), "lmx_dino_prepare")
+
+    def embed(self, frames, rgb=False):
+        """u8 [n,h,w,3] device tensor (BGR; rgb=True: RGB) -> f32 [n, hidden] on torch's current stream of that device."""
+        if not (frames.is_cuda and frames.device == self.device and frames.dtype == torch.uint8 and frames.dim() == 4
+                and frames.shape[3] == 3 and frames.is_contiguous()):
+            raise LmxError(f"NativeDino.embed: frames must be a contiguous uint8 [n,h,w,3] tensor on {self.device}")
+        n, h, w, _ = frames.shape
+        emb = torch.empty((n, self.info.hidden), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_dino_embed(self._handle(), C.c_void_p(frames.data_ptr()), n, h, w, 1 if rgb else 0,
+                                           C.c_void_p(emb.data_ptr()), st), "lmx_dino_embed")
+        return emb
+
+    def embed_host(self, frames, rgb=False):
+        """u8 [n,h,w,3] numpy array -> f32 [n, hidden] numpy array (lmx_dino_embed_host: uploads, embeds, downloads, synchronises)."""
+        a = np.ascontiguousarray(frames)
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+            raise LmxError("NativeDino.embed_host: frames must be a uint8 [n,h,w,3] array")
+        n, h, w, _ = a.shape
+        emb = np.empty((n, self.info.hidden), np.float32)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_dino_embed_host(self._handle(), a.ctypes.data, n, h, w, 1 if rgb else 0, emb.ctypes.data),
+                  "lmx_dino_embed_host")
+        return emb
+
+    def close(self):
+        if self._h is not None:
+            self._lib.lmx_dino_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
