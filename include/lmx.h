@@ -577,6 +577,73 @@ int lmx_dino_embed(lmx_dino* m, const uint8_t* frames, int n, int h, int w, int 
  * downloads and synchronises (examples/dino_embed.c). */
 int lmx_dino_embed_host(lmx_dino* m, const uint8_t* frames_host, int n, int h, int w, int rgb, float* emb_host);
 
+/* ---- HOST functions: the host arithmetic of the YOLO predictor (csrc/host_letterbox.cpp; all pointers are HOST memory) ----------
+ * What a caller of lmx_k_letterbox / lmx_k_scale_boxes / lmx_k_gemm's split_k computes once per frame size; the C++ twins of
+ * lmx/letterbox.py and lmx.kernels.split_k_for, equal to them bit for bit (tests/test_native_yolo_host.py).
+ * lmx_h_letterbox_geometry: ultralytics LetterBox(new_shape=imgsz, auto, scaleup=True, center=True, stride) for an sh x sw frame and
+ *                   the gain / padding ops.scale_boxes re-derives from the shapes (the predictor under yolo main.py:76): roundings are
+ *                   Python's round (half to even on a double).
+ * lmx_h_letterbox_tables: OpenCV's resizeGeneric_ table build for INTER_LINEAR on 8U, sh x sw -> rh x rw (cv2.resize inside LetterBox,
+ *                   yolo main.py:76): xofs int32 [rw], ialpha int16 [rw][2], yofs int32 [rh], ibeta int16 [rh][2] — lmx_k_letterbox's tables.
+ * lmx_h_conv_split_k: the split_k of an f32-output 3 x 3 convolution of the exact plan (yolo main.py:76 under precision "exact"): a
+ *                   function of the LAYER — pixels of ONE frame, N, K, Cin — never of the batch; 1 = no split; < 0 on error. */
+typedef struct { int32_t sh, sw, rh, rw, top, left, oh, ow; double gain, pad_x, pad_y; } lmx_letterbox_geo_t;
+int lmx_h_letterbox_geometry(int sh, int sw, int imgsz, int stride, int auto_, lmx_letterbox_geo_t* out_host);
+int lmx_h_letterbox_tables(int sh, int sw, int rh, int rw, int32_t* xofs_host, int16_t* ialpha_host, int32_t* yofs_host, int16_t* ibeta_host);
+int lmx_h_conv_split_k(int64_t px_per_frame, int N, int K, int cin);
+
+/* ==== MODEL level: YOLOv8 detections from raw frames (csrc/yolo_model.hip, csrc/host_yolo_image.cpp) ================================
+ * The whole of services/yolo-pipeline/app/main.py:76 — `self.yolo_model(frame, verbose=False, conf=...)`: LetterBox, the fused
+ * Conv-BN-SiLU stack, Detect, non_max_suppression, scale_boxes — and, for pose models, of services/tleap-pipeline/app/main.py:150
+ * (`result.keypoints`), behind one call: the launch sequence of lmx/yolo.py's YoloDetector written in C++ over the lmx_k_* entry
+ * points above, with the descriptors lmx/kernels.py fills.  Same launches, same bits as YoloDetector.detect / detect_pose on both
+ * precision plans (tests/test_gpu_native_yolo.py).
+ * The model comes from a weight image of kind YOLO that lmx.native.write_yolo_image(detector, path, plans) writes (layout in
+ * csrc/yolo_image.h): the stem, and per convolution the packed tensors of the f16 plan and / or the x3 tensors of the exact plan.
+ * Handle, image and error conventions as for lmx_dino: the handle belongs to the device current at open; ONE host thread and ONE
+ * stream in flight per handle; several handles are independent; LMX_EINVAL / LMX_EHIP with lmx_last_error(). */
+typedef struct lmx_yolo lmx_yolo;
+enum { LMX_YOLO_F16 = 0, LMX_YOLO_EXACT = 1 }; /* `precision`; lmx_yolo_info_t.plans has bit (1 << precision) for each plan the image holds */
+typedef struct { int32_t scale /* 'n' 's' 'm' 'l' 'x' */, nc, imgsz, kpt_k, kpt_ndim /* 0: no Pose head */, plans, max_batch; } lmx_yolo_info_t;
+/* HOST only, touches no GPU (`YOLO(path)` of yolo main.py:76, the checking half): parse and validate an image — magic, version, kind,
+ * sizes against the real file, the config block with its class names, and every tensor the configuration calls for (the layer table is
+ * derived from scale, nc and the keypoint shape) with its dtype and shape.  LMX_EINVAL names the offending field or tensor.
+ * info_host (may be NULL) receives the configuration, max_batch 0. */
+int lmx_yolo_image_check_host(const char* path_host, lmx_yolo_info_t* info_host);
+/* SYNCHRONOUS (`YOLO(path).to(device)` of yolo main.py:76): validate as above, then upload the weights to the CURRENT device.
+ * Workspaces come with lmx_yolo_prepare.  *out_host is NULL after any failure, with nothing left allocated. */
+int lmx_yolo_open_host(const char* path_host, int max_batch, lmx_yolo** out_host);
+/* the end of the model of yolo main.py:76: waits for the device, then frees everything the handle owns; NULL is allowed */
+void lmx_yolo_close(lmx_yolo* m);
+/* the configuration of the model behind yolo main.py:76 and the handle's max_batch */
+int lmx_yolo_info(const lmx_yolo* m, lmx_yolo_info_t* info_host);
+/* `result.names[cls]` of yolo main.py:76: the class name (UTF-8, owned by the handle), NULL out of range */
+const char* lmx_yolo_class_name(const lmx_yolo* m, int cls);
+/* SYNCHRONOUS (what the predictor of yolo main.py:76 derives from the frame size): the letterbox geometry and tables of an h x w frame
+ * and the whole workspace of max_batch frames under `precision` — letterboxed frames, every activation buffer of the plan, the f32
+ * convolution outputs and split-K partials of the exact plan, heads, pred, the NMS workspace.  A pair already prepared is a lookup.
+ * LMX_EINVAL for a plan the image does not hold, for a buffer of 2 GB or more (named: the GEMM kernels walk an operand with 32-bit byte
+ * offsets, and for these launches only this call checks it), and beyond 16 (size, plan) pairs per handle. */
+int lmx_yolo_prepare(lmx_yolo* m, int h, int w, int precision);
+/* host arithmetic of yolo main.py:76's LetterBox: the network input oh x ow of an h x w frame and its A = anchors over strides 8, 16, 32 */
+int lmx_yolo_anchors(const lmx_yolo* m, int h, int w, int* oh_host, int* ow_host, int* A_host);
+/* the network of yolo main.py:76 without NMS: frames u8 [n][h][w][3] BGR -> pred f32 [n][A][4+nc] (xywh in letterboxed pixels, class
+ * scores) = YoloDetector.forward_letterboxed(preprocess(frames)).  Enqueue-only after lmx_yolo_prepare, as lmx_yolo_detect. */
+int lmx_yolo_predict(lmx_yolo* m, const uint8_t* frames, int n, int h, int w, int precision, float* pred, lmx_stream_t stream);
+/* yolo main.py:76 for n frames (tleap main.py:150 with kpts): frames u8 [n][h][w][3] BGR -> boxes f32 [n][max_det][4] xyxy in FRAME
+ * pixels, scores f32 [n][max_det], cls int32 [n][max_det], src int32 [n][max_det] (anchor index, -1 past counts), counts int32 [n];
+ * rows past counts[b] are zero.  kpts f32 [n][max_det][K][ndim] (frame pixels, sigmoid visibility) for an image with a Pose head and
+ * NULL otherwise; anything else is LMX_EINVAL.  For a (size, precision) already prepared the call ONLY ENQUEUES on `stream`: no
+ * allocation, no synchronisation; the first call for a new pair runs lmx_yolo_prepare itself, and THAT call synchronises.
+ * n > max_batch runs in chunks of max_batch, each writing its slice of the outputs. */
+int lmx_yolo_detect(lmx_yolo* m, const uint8_t* frames, int n, int h, int w, int precision, float conf, double iou, int max_det,
+                    float* boxes, float* scores, int32_t* cls, int32_t* src, int32_t* counts, float* kpts, lmx_stream_t stream);
+/* yolo main.py:76 / tleap main.py:150 for a caller with no HIP code of its own: every pointer is HOST memory; uploads, detects,
+ * downloads and synchronises (examples/yolo_detect.c). */
+int lmx_yolo_detect_host(lmx_yolo* m, const uint8_t* frames_host, int n, int h, int w, int precision, float conf, double iou, int max_det,
+                         float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* src_host, int32_t* counts_host,
+                         float* kpts_host);
+
 #ifdef __cplusplus
 }
 #endif

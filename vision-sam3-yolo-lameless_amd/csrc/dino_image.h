@@ -16,7 +16,7 @@
 #include "../../include/lmx.h"
 
 #define LMX_IMAGE_VERSION 1u
-enum { LMX_IMAGE_DINO = 1, LMX_IMAGE_YOLO = 2, LMX_IMAGE_SAM = 3 };  // kinds; only DINO has a reader so far
+enum { LMX_IMAGE_DINO = 1, LMX_IMAGE_YOLO = 2, LMX_IMAGE_SAM = 3 };  // kinds; DINO here, YOLO in yolo_image.h; SAM has no reader yet
 enum { LMX_IMG_F16 = 0, LMX_IMG_F32 = 1, LMX_IMG_I32 = 2 };          // directory dtypes (F16 / F32 as LMX_F16 / LMX_F32)
 enum { LMX_IMAGE_HEADER_BYTES = 48, LMX_IMAGE_ENTRY_BYTES = 88, LMX_IMAGE_NAME_BYTES = 48, LMX_DINO_CONFIG_BYTES = 20 * 4 + 8 * 8 };
 

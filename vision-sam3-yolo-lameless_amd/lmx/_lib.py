@@ -31,6 +31,14 @@ class DinoInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("arch", "hidden", "heads", "layers", "tokens", "image", "patch", "gated", "recipe_kind", "max_batch")]
 
 
+class YoloInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("scale", "nc", "imgsz", "kpt_k", "kpt_ndim", "plans", "max_batch")]
+
+
+class LetterboxGeo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [
         ("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p),
@@ -117,6 +125,19 @@ SIGNATURES = {
     "lmx_dino_prepare": (_I, [_VP, _I, _I]),
     "lmx_dino_embed": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP]),
     "lmx_dino_embed_host": (_I, [_VP, _VP, _I, _I, _I, _I, _VP]),
+    "lmx_h_letterbox_geometry": (_I, [_I, _I, _I, _I, _I, C.POINTER(LetterboxGeo)]),
+    "lmx_h_letterbox_tables": (_I, [_I, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "lmx_h_conv_split_k": (_I, [_I64, _I, _I, _I]),
+    "lmx_yolo_image_check_host": (_I, [C.c_char_p, C.POINTER(YoloInfo)]),
+    "lmx_yolo_open_host": (_I, [C.c_char_p, _I, C.POINTER(_VP)]),
+    "lmx_yolo_close": (None, [_VP]),
+    "lmx_yolo_info": (_I, [_VP, C.POINTER(YoloInfo)]),
+    "lmx_yolo_class_name": (C.c_char_p, [_VP, _I]),
+    "lmx_yolo_prepare": (_I, [_VP, _I, _I, _I]),
+    "lmx_yolo_anchors": (_I, [_VP, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lmx_yolo_predict": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP]),
+    "lmx_yolo_detect": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _D, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_yolo_detect_host": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _D, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -7,15 +7,20 @@ asks ``lmx_dino_embed`` / ``lmx_dino_embed_host`` for embeddings without Python 
 ``NativeDino`` is the thin binding of that handle.  No plan logic lives here: the launch sequence is C++, and it is the launch
 sequence of ``DinoEmbedder.embed_frames`` — same entry points, same descriptors, same bits (tests/test_gpu_native_dino.py).
 The host table functions (``lmx_h_pil_tables``, ``lmx_h_aa_tables``, ...) are bound too, for the tests that hold them to
-lmx/resample.py."""
+lmx/resample.py.
+
+``write_yolo_image`` / ``NativeYolo`` are the same for a ``YoloDetector`` (csrc/yolo_model.hip, csrc/yolo_image.h,
+examples/yolo_detect.c): the launch sequence of ``YoloDetector.detect`` / ``detect_pose`` on either precision plan, with the twins of
+lmx/letterbox.py and ``kernels.split_k_for`` (``lmx_h_letterbox_geometry``, ``lmx_h_letterbox_tables``, ``lmx_h_conv_split_k``)
+bound for the tests (tests/test_native_yolo_host.py, tests/test_gpu_native_yolo.py)."""
 import ctypes as C
 import struct
 
 import numpy as np
 import torch
 
-from . import _lib, resample
-from ._lib import DinoInfo, LmxError, check
+from . import _lib, letterbox, resample
+from ._lib import DinoInfo, LetterboxGeo, LmxError, YoloInfo, check
 
 MAGIC = b"LMXIMAGE"
 VERSION = 1
@@ -25,6 +30,7 @@ ARCH = {"dinov2": 0, "dinov3": 1}
 RECIPE = {"pil": 0, "float": 1}
 FILT = {resample.BILINEAR: 2, resample.BICUBIC: 3}  # Pillow's `resample` codes (LMX_FILT_*)
 _DTYPE = {np.dtype(np.float16): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2}
+PLANS = {"f16": 0, "exact": 1}  # LMX_YOLO_F16, LMX_YOLO_EXACT; an image's plan mask has bit (1 << code) per plan it holds
 LAYER_TENSORS = ("g1", "b1", "wqkv", "bqkv", "wo", "bo", "ls1", "g2", "b2", "w1", "bb1", "w2", "bb2", "ls2")
 
 
@@ -91,6 +97,98 @@ def check_dino_image(path):
     info = DinoInfo()
     check(_lib.load().lmx_dino_image_check_host(str(path).encode(), C.byref(info)), "lmx_dino_image_check_host")
     return info
+
+
+# ---- the YOLO weight image (csrc/yolo_image.h) ------------------------------------------------------------------------------
+def yolo_conv_groups(detector):
+    """{name of a 1 x 1 convolution: the channel groups its exact-plan weight is split over}: what YoloDetector.forward_letterboxed
+    passes to _PlanExact._w at each call site (a C2f cv1 that reads a concat, every C2f cv2, SPPF cv2); absent = one group (the
+    Detect / Pose heads, the other cv1) or a 3 x 3 convolution (9 x [Cin], _PlanExact._w's own rule)."""
+    T = detector.table
+    c_out = [m.get("c2", 0) for m in T]
+    cat = {12: [c_out[9], c_out[6]], 15: [c_out[12], c_out[4]], 18: [c_out[16], c_out[12]], 21: [c_out[19], c_out[9]]}
+    groups = {}
+    for i, m in enumerate(T):
+        if m["kind"] == "c2f":
+            if i in cat:
+                groups[f"model.{i}.cv1"] = cat[i]
+            groups[f"model.{i}.cv2"] = [m["c2"] // 2] * (2 + m["n"])
+        elif m["kind"] == "sppf":
+            groups[f"model.{i}.cv2"] = [m["c1"] // 2] * 4
+    return groups
+
+
+def yolo_config_block(detector, plans):
+    """10 int32 (LmxYoloCfg, csrc/yolo_image.h), then the class names: NUL-terminated UTF-8 in class order, zero-padded to 8 bytes."""
+    cfg = detector.cfg
+    k, ndim = cfg.kpt_shape if cfg.kpt_shape is not None else (0, 0)
+    names = [detector.names[i] for i in range(len(detector.names))]
+    blob = b"".join(n.encode("utf-8") + b"\0" for n in names)
+    if any(b"\0" in n.encode("utf-8") for n in names):
+        raise LmxError("write_yolo_image: a class name contains a NUL character")
+    mask = sum(1 << PLANS[p] for p in set(plans))
+    ints = (ord(cfg.scale), cfg.nc, detector.nc_pad, cfg.imgsz, k, ndim, getattr(detector, "nk_pad", 0) if k else 0, mask, len(names), len(blob))
+    return struct.pack("<10i", *ints) + blob + b"\0" * (-len(blob) % 8)
+
+
+def yolo_tensors(detector, plans):
+    """Ordered {name: numpy array}: the stem, then per convolution of detector.w the f16 plan's (w, b) and / or the exact plan's
+    (x3 weight, ldexp'd bias, row scale) — exactly the tensors the detector's plans hold, in their dtypes."""
+    def host(t):
+        return np.ascontiguousarray(t.detach().cpu().numpy())
+
+    out = {"stem.w": host(detector.w["model.0"][0]), "stem.b": host(detector.w["model.0"][1])}
+    groups = yolo_conv_groups(detector)
+    exact = detector._plan("exact") if "exact" in plans else None
+    for name, (w, b) in detector.w.items():
+        if name == "model.0":
+            continue
+        if "f16" in plans:
+            out[f"f16.{name}.w"], out[f"f16.{name}.b"] = host(w), host(b)
+        if exact is not None:
+            x3, xb, sc = exact._w(name, groups.get(name))
+            out[f"x3.{name}.w"], out[f"x3.{name}.b"], out[f"x3.{name}.s"] = host(x3), host(xb), host(sc)
+    return out
+
+
+def write_yolo_image(detector, path, plans=("f16", "exact")):
+    """Export a YoloDetector (any device) as the weight image lmx_yolo_open_host reads, with the tensors of `plans`.  Returns the
+    file's size in bytes."""
+    plans = tuple(plans)
+    if not plans or any(p not in PLANS for p in plans):
+        raise LmxError(f"write_yolo_image: plans {plans!r}: a non-empty subset of {tuple(PLANS)}")
+    return write_image(path, KIND_YOLO, yolo_config_block(detector, plans), yolo_tensors(detector, plans))
+
+
+def check_yolo_image(path):
+    """lmx_yolo_image_check_host: validate an image on the host (no GPU) -> YoloInfo; LmxError names the offending field or tensor."""
+    info = YoloInfo()
+    check(_lib.load().lmx_yolo_image_check_host(str(path).encode(), C.byref(info)), "lmx_yolo_image_check_host")
+    return info
+
+
+# ---- the host arithmetic of the YOLO predictor (csrc/host_letterbox.cpp) -------------------------------------------------------
+def letterbox_geometry(sh, sw, imgsz=640, stride=32, auto=True):
+    """lmx_h_letterbox_geometry: the C++ twin of letterbox.geometry, same return value."""
+    g = LetterboxGeo()
+    check(_lib.load().lmx_h_letterbox_geometry(sh, sw, imgsz, stride, 1 if auto else 0, C.byref(g)), "lmx_h_letterbox_geometry")
+    return letterbox.LetterboxGeo(g.sh, g.sw, g.rh, g.rw, g.top, g.left, g.oh, g.ow, g.gain, g.pad_x, g.pad_y)
+
+
+def letterbox_tables(sh, sw, rh, rw):
+    """lmx_h_letterbox_tables: the C++ twin of letterbox.resize_tables, same return value."""
+    xofs, ialpha = np.empty(rw, np.int32), np.empty(rw * 2, np.int16)
+    yofs, ibeta = np.empty(rh, np.int32), np.empty(rh * 2, np.int16)
+    check(_lib.load().lmx_h_letterbox_tables(sh, sw, rh, rw, xofs.ctypes.data, ialpha.ctypes.data, yofs.ctypes.data, ibeta.ctypes.data),
+          "lmx_h_letterbox_tables")
+    return xofs, ialpha, yofs, ibeta
+
+
+def conv_split_k(px_per_frame, N, K, cin):
+    """lmx_h_conv_split_k: the C++ twin of kernels.split_k_for."""
+    r = _lib.load().lmx_h_conv_split_k(px_per_frame, N, K, cin)
+    check(min(r, 0), "lmx_h_conv_split_k")
+    return r
 
 
 # ---- the host table functions (csrc/host_resample.cpp) ---------------------------------------------------------------------
@@ -184,6 +282,120 @@ class NativeDino:
     def close(self):
         if self._h is not None:
             self._lib.lmx_dino_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeYolo:
+    """lmx_yolo_open_host(path, max_batch) on `device` (default: torch's current device).  `precision`: "f16" or "exact"."""
+
+    def __init__(self, path, max_batch, device=None):
+        self._lib = _lib.load()
+        self._h = None
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise LmxError(f"NativeYolo: {self.device} is not a GPU")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        h = C.c_void_p(0)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_yolo_open_host(str(path).encode(), int(max_batch), C.byref(h)), "lmx_yolo_open_host")
+        self._h = h
+        self.info = YoloInfo()
+        check(self._lib.lmx_yolo_info(self._h, C.byref(self.info)), "lmx_yolo_info")
+
+    def _handle(self):
+        if self._h is None:
+            raise LmxError("NativeYolo: the handle is closed")
+        return self._h
+
+    @property
+    def pose(self):
+        return self.info.kpt_k > 0
+
+    def class_name(self, cls):
+        """lmx_yolo_class_name: the name of class `cls`, None out of range."""
+        raw = self._lib.lmx_yolo_class_name(self._handle(), int(cls))
+        return None if raw is None else raw.decode("utf-8")
+
+    def prepare(self, h, w, precision):
+        """lmx_yolo_prepare: geometry, tables and workspace of one (frame size, plan) (synchronous); predict() / detect() of that
+        pair then only enqueue."""
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_yolo_prepare(self._handle(), int(h), int(w), PLANS[precision]), "lmx_yolo_prepare")
+
+    def anchors(self, h, w):
+        """lmx_yolo_anchors: (oh, ow, A) of an h x w frame."""
+        oh, ow, A = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.lmx_yolo_anchors(self._handle(), int(h), int(w), C.byref(oh), C.byref(ow), C.byref(A)), "lmx_yolo_anchors")
+        return oh.value, ow.value, A.value
+
+    def _frames(self, frames, what):
+        if not (frames.is_cuda and frames.device == self.device and frames.dtype == torch.uint8 and frames.dim() == 4
+                and frames.shape[3] == 3 and frames.is_contiguous()):
+            raise LmxError(f"NativeYolo.{what}: frames must be a contiguous uint8 [n,h,w,3] tensor on {self.device}")
+        return frames.shape[:3]
+
+    def predict(self, frames, precision):
+        """u8 BGR [n,h,w,3] device tensor -> pred f32 [n, A, 4+nc] on torch's current stream of that device (lmx_yolo_predict)."""
+        n, h, w = self._frames(frames, "predict")
+        A = self.anchors(h, w)[2]
+        pred = torch.empty((n, A, 4 + self.info.nc), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_yolo_predict(self._handle(), C.c_void_p(frames.data_ptr()), n, h, w, PLANS[precision], C.c_void_p(pred.data_ptr()), st),
+                  "lmx_yolo_predict")
+        return pred
+
+    def detect(self, frames, precision, conf=0.25, iou=0.7, max_det=300):
+        """u8 BGR [n,h,w,3] device tensor -> (boxes [n,max_det,4], scores, cls, src, counts), plus kpts [n,max_det,K,ndim] for a pose
+        image, on torch's current stream of that device (lmx_yolo_detect; the outputs are initialised by the call)."""
+        n, h, w = self._frames(frames, "detect")
+        md = max(int(max_det), 0)
+        dev = self.device
+        boxes = torch.empty((n, md, 4), dtype=torch.float32, device=dev)
+        scores = torch.empty((n, md), dtype=torch.float32, device=dev)
+        cls, src = (torch.empty((n, md), dtype=torch.int32, device=dev) for _ in range(2))
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        kpts = torch.empty((n, md, self.info.kpt_k, self.info.kpt_ndim), dtype=torch.float32, device=dev) if self.pose else None
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            check(self._lib.lmx_yolo_detect(self._handle(), C.c_void_p(frames.data_ptr()), n, h, w, PLANS[precision], float(conf), float(iou),
+                                            int(max_det), *(C.c_void_p(t.data_ptr()) for t in (boxes, scores, cls, src, counts)),
+                                            C.c_void_p(kpts.data_ptr()) if kpts is not None else None, st), "lmx_yolo_detect")
+        return (boxes, scores, cls, src, counts) + ((kpts,) if kpts is not None else ())
+
+    def detect_host(self, frames, precision, conf=0.25, iou=0.7, max_det=300):
+        """u8 BGR [n,h,w,3] numpy array -> the same outputs as numpy arrays (lmx_yolo_detect_host: uploads, detects, downloads,
+        synchronises)."""
+        a = np.ascontiguousarray(frames)
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+            raise LmxError("NativeYolo.detect_host: frames must be a uint8 [n,h,w,3] array")
+        n, h, w, _ = a.shape
+        md = max(int(max_det), 0)
+        boxes, scores = np.empty((n, md, 4), np.float32), np.empty((n, md), np.float32)
+        cls, src, counts = np.empty((n, md), np.int32), np.empty((n, md), np.int32), np.empty((n,), np.int32)
+        kpts = np.empty((n, md, self.info.kpt_k, self.info.kpt_ndim), np.float32) if self.pose else None
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_yolo_detect_host(self._handle(), a.ctypes.data, n, h, w, PLANS[precision], float(conf), float(iou), int(max_det),
+                                                 *(t.ctypes.data for t in (boxes, scores, cls, src, counts)),
+                                                 kpts.ctypes.data if kpts is not None else None), "lmx_yolo_detect_host")
+        return (boxes, scores, cls, src, counts) + ((kpts,) if kpts is not None else ())
+
+    def close(self):
+        if self._h is not None:
+            self._lib.lmx_yolo_close(self._h)
             self._h = None
 
     def __enter__(self):
