@@ -406,6 +406,16 @@ int lmx_k_cast_f32_f16(const float* src, int64_t lds, void* dst, int64_t ldd, in
  * Hiera-B+.  *band = 0 (no band: compute the whole grid) when that count is the whole grid or more, when block 0 is global or no
  * block is, and when nw < 4 * grid (padding on the right: columns are not cut).  Pure host arithmetic: no HIP call. */
 int lmx_h_hiera_band(const int* window, const int* q_stride, int n_blocks, int grid, int nh, int nw, int* band);
+/* The same band sized per block, not once for the trunk (arguments as lmx_h_hiera_band).  rows[i], i < n_blocks: the token rows, of
+ * the grid block i READS (`grid` halved behind every pooling block), that block i has to run on.  d = min((nh + 2) / 4 + 1, grid)
+ * rows carry a pixel into block 0; a block in front of the first global one runs on d rounded up to whole windows of its own, and to
+ * an even count where it pools — the whole grid of its resolution once that count reaches it — and hands those rows on, halved
+ * behind a pooling block: a block never has fewer rows than the one before it left, and where it has more the constant rows
+ * between the two are joined in front of it (lmx_k_band_join).  From the first global block on rows[i] is the whole grid; so is
+ * every entry where lmx_h_hiera_band answers 0 for want of a place to end: nw < 4 * grid, block 0 global, no global block.
+ * Hiera-B+, 576 x 1024: 152 (blocks 0 - 2) / 76 (3 - 5) / 42 (6 - 11) against lmx_h_hiera_band's 168 / 84 / 42.  Pure host
+ * arithmetic: no HIP call. */
+int lmx_h_hiera_bands(const int* window, const int* q_stride, int n_blocks, int grid, int nh, int nw, int* rows);
 /* out [n][H][W][D] = rows < Hb of each image from band [n][Hb][W][D], rows >= Hb from table [(H - Hb) * W][D], the same for every
  * image: the frame-dependent band of a Hiera token grid (lmx_h_hiera_band) joined with its constant rows.  dtype f16 or f32, dense
  * operands; a row of D elements must be a multiple of 16 bytes and 1 <= Hb <= H - 1. */

@@ -97,6 +97,7 @@ SIGNATURES = {
     "lmx_k_maxpool2": (_I, [_VP, _I64, _VP, _I64, _I, _I, _I, _I, _I, _VP]),
     "lmx_k_cast_f32_f16": (_I, [_VP, _I64, _VP, _I64, _I64, _I, _VP]),
     "lmx_h_hiera_band": (_I, [C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, C.POINTER(C.c_int)]),
+    "lmx_h_hiera_bands": (_I, [C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "lmx_k_band_join": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     "lmx_k_add_bcast":(_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _I, _I64, _I64, _I, _VP]),
     "lmx_h_mask_features": (_I, [_VP, _I, _I, _VP]),

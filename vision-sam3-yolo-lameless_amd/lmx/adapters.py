@@ -229,7 +229,8 @@ class ResizeLongestSide:
 class LmxSamPredictor:
     """`SamPredictor(sam)`: set_image caches the image embedding, predict decodes a prompt against it (the only state kept
     across calls, as in the reference: sam3 main.py:80-88).  `model` may also be any encoder with the HieraEncoder surface
-    paired with a MaskDecoder (`LmxSamPredictor.from_parts`) — BASELINE's Hiera-B+ configuration."""
+    paired with a MaskDecoder (`LmxSamPredictor.from_parts`) — BASELINE's Hiera-B+ configuration; set_image reads
+    outputs="embedding" alone, so build that encoder with band="blocks"."""
 
     def __init__(self, sam_model):
         self.model = sam_model

@@ -238,6 +238,17 @@ def hiera_band(windows, q_strides, grid, nh, nw):
     return band.value
 
 
+def hiera_bands(windows, q_strides, grid, nh, nw):
+    """The same band sized block by block: (rows per block), the token rows of the grid each block reads that it has to run on; the
+    whole grid from the first global block on, and everywhere where there is no band (lmx_h_hiera_bands, include/lmx.h)."""
+    nb = len(windows)
+    if nb != len(q_strides):
+        raise LmxError("hiera_bands: windows and q_strides must be the same length")
+    rows = (C.c_int * nb)()
+    check(_lib.load().lmx_h_hiera_bands((C.c_int * nb)(*windows), (C.c_int * nb)(*q_strides), nb, grid, nh, nw, rows), "lmx_h_hiera_bands")
+    return tuple(rows)
+
+
 def band_join(band, table, H):
     """[n, H, W, D]: rows < Hb of each image from band [n, Hb, W, D], rows >= Hb from table [(H - Hb) * W, D], the same for every
     image (lmx_k_band_join).  f16 or f32, contiguous."""

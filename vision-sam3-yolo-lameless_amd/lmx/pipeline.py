@@ -41,7 +41,8 @@ class FusedExtractor:
         self.yolo = yolo.YoloDetector(ycfg, yolo.synthetic_state_dict(ycfg, weight_seeds[0], bn if os.path.exists(bn) else None),
                                       self.device)
         scfg = sam.hiera_b_plus()
-        self.sam = sam.HieraEncoder(scfg, weights.synth_state_dict(sam.param_spec(scfg), weight_seeds[1]), self.device)
+        # (band="blocks": step() asks for outputs="embedding", whose band is sized block by block)
+        self.sam = sam.HieraEncoder(scfg, weights.synth_state_dict(sam.param_spec(scfg), weight_seeds[1]), self.device, band="blocks")
         self.decoder = sam_decoder.MaskDecoder(sam_decoder.synthetic_state_dict(weight_seeds[1] + 100), self.device)
         dcfg = dino.dinov3_vitl16()
         self.dino = dino.DinoEmbedder(dcfg, weights.synth_state_dict(dino.param_spec(dcfg), weight_seeds[2]), self.device)

@@ -258,13 +258,13 @@ def attn8_ln_inside(i, fused_mlp):
 
 class BlockPlan(NamedTuple):
     """What one Hiera block runs: a record of hiera_plan(), executed by HieraEncoder.trunk()."""
-    H: int             # the token grid going in: rows (the band's while it lasts; behind a join the whole grid's), columns,
+    H: int             # the token grid going in: rows (the band's while it lasts; behind a join the rows joined to), columns,
     W: int
     Hf: int            # and the whole grid's rows at this resolution
     Ho: int            # the same going out (halved where the block pools its queries)
     Wo: int
     Hfo: int
-    join: int          # > 0: the band ends in front of this block; its `join` rows are joined with the table's to H rows
+    join: int          # > 0: the band grows or ends in front of this block; its `join` rows are joined with the table's to H rows
     attn: str          # the attention half: "attn8_ln" (layer_norm1 inside) | "attn8" | "attn_pool" | "attn4" | "launches"
     ln1: str           # layer_norm1's rows come from: "kernel" (attn8_ln) | "prev" (the previous block's MLP kernel) | "launch"
     shortcut: str      # launches only: None | "gemm" | "gemm+maxpool" | "pooled_gemm"
@@ -286,19 +286,29 @@ class BlockPlan(NamedTuple):
 
 def hiera_plan(cfg, n, rows, fused_mlp=True, lowest=0, proj_ln=True):
     """[BlockPlan per block] for n frames whose blocks in front of the first global one run on `rows` stage-1 token rows (a band, or
-    cfg.image // 4: the whole grid).  The one place that chooses kernels, computed per call: the K.*_ok functions read their
-    environment switches every time.  lowest: stage outputs below this index are not kept.  proj_ln=False: no ln_out projections."""
+    cfg.image // 4: the whole grid).  rows may also be a sequence with one entry per block: the token rows, of the grid that block
+    reads, it runs on (K.hiera_bands) — where a block needs more than the block before it left, a join sits in front of it and the
+    band goes on behind it with the rows it needs.  The one place that chooses kernels, computed per call: the K.*_ok functions read
+    their environment switches every time.  lowest: stage outputs below this index are not kept.  proj_ln=False: no ln_out
+    projections."""
     g = cfg.image // 4
     blocks = cfg.block_plan()
     first_global = next((i for i, b in enumerate(blocks) if b[3] == 0), None)
     stage_ends = [e - 1 for e in itertools.accumulate(cfg.blocks)]
-    H, W, Hf = rows, g, g
-    band = rows < g
+    per = None if isinstance(rows, int) else tuple(rows)
+    if per is not None and len(per) != len(blocks):
+        raise ValueError(f"hiera_plan: {len(per)} row counts for {len(blocks)} blocks")
+    H, W, Hf = rows if per is None else per[0], g, g
+    band = H < g
     plan, prev = [], None  # prev: the block before, which learns from this one's attention half whether to emit layer_norm1
     for i, (dim, D, heads, win, qs) in enumerate(blocks):
-        join = H if band and i == first_global else 0  # the band ends: from here every token sees every other
+        # one number: the band ends in front of the first global block, where every token sees every other
+        need = per[i] if per is not None else Hf if band and i == first_global else H
+        if per is not None and not H <= need <= Hf:
+            raise ValueError(f"hiera_plan: block {i} on {need} rows, the block before left {H} of {Hf}")
+        join = H if need > H else 0
         if join:
-            H, band = Hf, False
+            H, band = need, need < Hf
         fused = FUSED_ATTN.get((dim, D, heads, win, qs))
         shortcut = query = None
         if fused == "attn8" and K.hiera_attn8_ok(D, heads, win, H, W, qs):
@@ -345,9 +355,15 @@ class HieraEncoder:
     frame.  The blocks in front of the first global one then run on the top rows alone (K.hiera_band: 168 of 256 stage-1 rows for a
     16:9 frame); the other rows come from a table built once per frame geometry (_band_table) and are joined in front of the first
     global block (K.band_join).  Every kernel computes a row from its window alone, whatever the grid's height, so the result is
-    bit for bit that of band=False (tests/test_gpu_hiera_band.py)."""
+    bit for bit that of band=False (tests/test_gpu_hiera_band.py).
+
+    band="blocks": the band is sized block by block (block_rows: 152 / 76 stage-1 / stage-2 rows for that frame, and 42 of stage 3
+    only where the 14 x 14 windows begin); where a block needs more rows than the one before it left, a join in front of it adds the
+    constant rows between the two and the band goes on behind it (tests/test_gpu_hiera_block_bands.py)."""
 
     def __init__(self, cfg, state_dict, device="cuda", fused_mlp=True, band=True):
+        if band not in (True, False, "blocks"):
+            raise ValueError(f"band {band!r}: expected True, False or 'blocks'")
         self.cfg = cfg
         self.band = band
         self.device = torch.device(device)
@@ -414,7 +430,7 @@ class HieraEncoder:
         self.lut = t32(sam_norm_lut())
         self._tabs = {}
         self.first_global = next((i for i, B in enumerate(self.blocks) if B["win"] == 0), None)
-        self._bands, self._band_tabs, self._band_lock = {}, {}, threading.Lock()
+        self._bands, self._block_bands, self._band_tabs, self._band_lock = {}, {}, {}, threading.Lock()
 
     # ---- preprocessing ------------------------------------------------------------------------------------
     def _tables(self, h, w):
@@ -449,21 +465,56 @@ class HieraEncoder:
             self._bands[(nh, nw)] = K.hiera_band([p[3] for p in plan], [p[4] for p in plan], self.grid0, nh, nw)
         return self._bands[(nh, nw)]
 
+    def block_rows(self, nh, nw, n=1):
+        """band="blocks": the token rows each block runs on for n frames resized to nh x nw, one entry per block at the resolution
+        that block reads (K.hiera_bands); the whole grid from the first global block on, and everywhere where there is no band.
+        The constant rows come from the whole-grid plan's kernels (_band_table), so a block in the band must run the kernel that
+        plan chose: one whose shape check fails on the rule's rows runs on the next count of whole windows that passes — up to
+        the whole grid, where it needs no constant rows — and is never moved to another kernel, whose rounding the table lacks."""
+        return self._settle(nh, nw, n)[0]
+
+    def _settle(self, nh, nw, n, lowest=0):
+        """-> (block_rows(nh, nw, n), the band's plan on them, the whole-grid plan of one frame that builds the table); the plans are
+        None where there is no band."""
+        if (nh, nw) not in self._block_bands:
+            plan = self.cfg.block_plan()
+            self._block_bands[(nh, nw)] = K.hiera_bands([p[3] for p in plan], [p[4] for p in plan], self.grid0, nh, nw)
+        rows = self._block_bands[(nh, nw)]
+        if rows[0] == self.grid0:
+            return rows, None, None
+        whole, blocks = self.plan(1, self.grid0), self.cfg.block_plan()
+        while True:  # (every round adds rows to a block: it ends at the whole grid at the latest)
+            plan = self.plan(n, rows, lowest)
+            bad = next((i for i in range(self.first_global) if plan[i].H < plan[i].Hf and plan[i].choices() != whole[i].choices()), None)
+            if bad is None:
+                return rows, plan, whole
+            rows, d = list(rows), 0
+            for i in range(bad, self.first_global):
+                piece = math.lcm(blocks[i][3], 2 if blocks[i][4] else 1)
+                d = max(d, rows[i] + piece if i == bad else rows[i])
+                rows[i] = d = min(-(-d // piece) * piece, plan[i].Hf)
+                if blocks[i][4]:
+                    d //= 2
+            rows = tuple(rows)
+
     def plan(self, n, rows, lowest=0):
-        """hiera_plan() of this encoder for n frames on `rows` stage-1 token rows in front of the first global block."""
+        """hiera_plan() of this encoder for n frames on `rows` stage-1 token rows in front of the first global block, or on the rows
+        per block of block_rows()."""
         return hiera_plan(self.cfg, n, rows, self.fused_mlp, lowest, self.proj_ln)
 
-    def _table_key(self, nh, nw, band):
-        """The band table's key: the geometry and the kernel choices of the pass that builds it — one frame, the whole grid, the blocks
-        in front of the first global one — so it never depends on a caller's batch size (K.pooled_gemm_ok does)."""
-        return (nh, nw, band, tuple(p.choices() for p in self.plan(1, self.grid0)[:self.first_global]))
+    def _table_key(self, nh, nw, band, whole=None):
+        """The band table's key: the geometry, the band (one number, or the rows per block) and the kernel choices of the pass that
+        builds it — one frame, the whole grid (`whole`: that plan, where the caller has it), the blocks in front of the first global
+        one — so it never depends on a caller's batch size (K.pooled_gemm_ok does)."""
+        return (nh, nw, band, tuple(p.choices() for p in (whole or self.plan(1, self.grid0))[:self.first_global]))
 
-    def _band_table(self, frames, nh, nw, band):
-        """The rows below the band, the same for every frame of this geometry: dict(x = the f32 stream in front of the first global
-        block, stages / stages16 = the stage outputs before it), each [(H_s - band_s) * W_s, D].  Built once per _table_key by
-        the full-grid path on one frame, outside any running launch trace (a trace describes the steady step), and
-        finished with a synchronisation of the building stream: passes on other streams read the table without an event."""
-        key = self._table_key(nh, nw, band)
+    def _band_table(self, frames, nh, nw, band, whole=None):
+        """The rows below the band, the same for every frame of this geometry: dict(x = {block with a join in front: rows [have, need)
+        of the f32 stream entering it}, stages / stages16 = the rows below the band of the stage outputs inside it), each
+        [rows * W_s, D].  Built once per _table_key by the full-grid path on one frame, outside any running launch trace (a trace
+        describes the steady step), and finished with a synchronisation of the building stream: passes on other streams read the
+        table without an event."""
+        key = self._table_key(nh, nw, band, whole)
         tab = self._band_tabs.get(key)
         if tab is not None:
             return tab
@@ -475,14 +526,16 @@ class HieraEncoder:
                 return self._band_tabs[key]
             trace, K.LAUNCH_TRACE = K.LAUNCH_TRACE, None
             try:
-                g = self.grid0
-                x, H, W, stages, stages16 = self.trunk(self.preprocess(frames[:1])[1], 1, until=self.first_global)
+                plan = self.plan(1, band)  # the band's own plan: where its joins sit and how many rows its stage outputs have
+                taps = {i: (P.join, P.H) for i, P in enumerate(plan) if P.join}
+                ends = [P.Ho for P in plan if P.stage_end and P.join_out]
+                stages, stages16 = self.trunk(self.preprocess(frames[:1])[1], 1, taps=taps)
 
-                def below(t, Hs, Ws):  # rows >= the band of a [1, Hs, Ws, D] grid, as a table of its own
-                    return t.reshape(Hs, Ws, -1)[band * Hs // g:].reshape(-1, t.shape[-1]).clone()
+                def below(t, Hb):  # rows >= Hb of a [1, Hs, Ws, D] grid, as a table of its own
+                    return t.reshape(-1, t.shape[-2], t.shape[-1])[Hb:].reshape(-1, t.shape[-1]).clone()
 
-                tab = dict(x=below(x, H, W), stages=[below(s, *s.shape[1:3]) for s in stages],
-                           stages16=[below(s16, *s.shape[1:3]) if s16 is not None else None for s, s16 in zip(stages, stages16)])
+                tab = dict(x=taps, stages=[below(s, Hb) for s, Hb in zip(stages, ends)],
+                           stages16=[below(s16.view(s.shape), Hb) if s16 is not None else None for s, s16, Hb in zip(stages, stages16, ends)])
             finally:
                 K.LAUNCH_TRACE = trace
             torch.cuda.current_stream(self.device).synchronize()
@@ -490,24 +543,29 @@ class HieraEncoder:
         return tab
 
     # ---- network ------------------------------------------------------------------------------------------
-    def trunk(self, patches, n, band=0, table=None, lowest=0, until=None):
-        """patches -> (stages, stages16): executes self.plan(n, band or the whole grid, lowest) block by block.  band > 0: `patches`
-        hold the top `band` stage-1 token rows of each frame; the blocks in front of the first global one run on those rows, and
-        `table` (_band_table) supplies the others where the band ends and in the stage outputs before it.  lowest: stage outputs
-        below this index are not kept (None).  until: stop in front of block `until` and return (x, H, W, stages, stages16) as they
-        stand there."""
+    def trunk(self, patches, n, band=0, table=None, lowest=0, taps=None, plan=None):
+        """patches -> (stages, stages16): executes self.plan(n, band or the whole grid, lowest) block by block.  band > 0, or the rows
+        per block of block_rows(): `patches` hold the band's stage-1 token rows of each frame; the blocks in front of the first
+        global one run on those rows, and `table` (_band_table) supplies the others in front of every block that needs more and
+        in the stage outputs inside the band.  lowest: stage outputs below this index are not kept (None).  taps (one frame, the
+        whole grid) = {block: (have, need)}: each entry is replaced by a copy of rows [have, need) of the stream entering that
+        block, and the trunk stops in front of the last of them.  plan: that plan, where the caller has computed it."""
         cfg = self.cfg
         g = self.grid0
-        H = band or g
+        rows = band or g
+        H = rows if isinstance(rows, int) else rows[0]
         x = K.gemm(patches, self.pe_w, bias=self.pe_b, res=self.pos[:H * g], res_rows=H * g, out_dtype=torch.float32)
         stages, stages16 = [], []
         dev = x.device
         h_next = None
-        for i, (P, B) in enumerate(zip(self.plan(n, H, lowest), self.blocks)):
-            if i == until:
-                return x, P.join or P.H, P.W, stages, stages16
+        for i, (P, B) in enumerate(zip(plan or self.plan(n, rows, lowest), self.blocks)):
+            if taps and i in taps:
+                have, need = taps[i]
+                taps[i] = x.view(P.H, P.W, -1)[have:need].reshape((need - have) * P.W, -1).clone()
+                if i == max(taps):
+                    return stages, stages16
             if P.join:
-                x = K.band_join(x.view(n, P.join, P.W, -1), table["x"], P.H).view(n * P.H * P.W, -1)
+                x = K.band_join(x.view(n, P.join, P.W, -1), table["x"][i], P.H).view(n * P.H * P.W, -1)
             D, heads = B["dim_out"], B["heads"]
             h = None if P.ln1 == "kernel" else h_next if P.ln1 == "prev" else K.layernorm(x, B["g1"], B["b1"], cfg.eps)
             h2 = None
@@ -632,10 +690,15 @@ class HieraEncoder:
         lowest = 2 if outputs == "embedding" else 0
         n, h, w, _ = frames.shape
         nh, nw = self._tables(h, w)[:2]
-        band = self.band_rows(nh, nw) if self.band else 0
-        table = self._band_table(frames, nh, nw, band) if band else None
-        img, patches = self.preprocess(frames, band)
-        stages, stages16 = self.trunk(patches, n, band, table, lowest)
+        plan = whole = None
+        if self.band == "blocks":
+            band, plan, whole = self._settle(nh, nw, n, lowest)
+            band, top = (band, band[0]) if plan else (0, 0)
+        else:
+            band = top = self.band_rows(nh, nw) if self.band else 0
+        table = self._band_table(frames, nh, nw, band, whole) if band else None
+        img, patches = self.preprocess(frames, top)
+        stages, stages16 = self.trunk(patches, n, band, table, lowest, plan=plan)
         return dict(fpn=self.fpn(stages, stages16, lowest), stages=stages, resized=img)
 
 

@@ -183,7 +183,8 @@ class SAM3Pipeline:
 
 class HieraSegmenter:
     """Adapter giving an image encoder (HieraEncoder, or SamVitEncoder for `sam_vit_b/l` checkpoints: main.py:58-65) +
-    MaskDecoder the `segment(frames, boxes)` surface the service needs."""
+    MaskDecoder the `segment(frames, boxes)` surface the service needs.  It reads outputs="embedding" alone: build a HieraEncoder for
+    it with band="blocks" (the band of frame-dependent rows sized block by block)."""
 
     def __init__(self, encoder, decoder):
         self.encoder, self.decoder = encoder, decoder
