@@ -544,13 +544,13 @@ int lmx_h_aa_tables(int in_size, int out_size, int filt, int32_t* bounds_host, f
 int lmx_h_identity_table(int n, int32_t* bounds_host, int32_t* kk_host);
 int lmx_h_segment_cols(const int32_t* bounds_host, int n_out, int tile);
 
-/* ==== MODEL level: DINO embeddings from raw frames (csrc/dino_model.hip, csrc/host_dino_image.cpp) ==================================
+/* ==== MODEL level: DINO embeddings from raw frames (csrc/dino_model.hip, csrc/model_handle.h, csrc/host_dino_image.cpp) =============
  * The whole of services/dinov3-pipeline/app/main.py:98-113 — cvtColor, processor(images=...), model(**inputs), last_hidden_state
  * .mean(dim=1) — behind one call, for a consumer that is not a Python process: the launch sequence of lmx/dino.py's DinoEmbedder
  * (preprocess + hidden_states + token_mean) written in C++ over the lmx_k_* entry points above, with the descriptors lmx/kernels.py
  * fills.  Same launches, same bits as DinoEmbedder.embed_frames (tests/test_gpu_native_dino.py).
  * The model comes from a WEIGHT IMAGE: one little-endian file that lmx.native.write_dino_image(embedder, path) writes from a loaded
- * DinoEmbedder (header, config block, tensor directory, tensors in final device form; layout in csrc/dino_image.h).  Loading
+ * DinoEmbedder (header, config block, tensor directory, tensors in final device form; layout in csrc/image.h, the config block in csrc/dino_image.h).  Loading
  * safetensors / Hugging Face directories stays in Python: export once, then open the image from C.
  * Handle rules: a handle belongs to the device that was current at lmx_dino_open_host; every call with another device current is
  * LMX_EINVAL.  ONE host thread and ONE stream in flight per handle: all calls write the handle's workspace, so a call on another
@@ -602,14 +602,14 @@ int lmx_h_letterbox_geometry(int sh, int sw, int imgsz, int stride, int auto_, l
 int lmx_h_letterbox_tables(int sh, int sw, int rh, int rw, int32_t* xofs_host, int16_t* ialpha_host, int32_t* yofs_host, int16_t* ibeta_host);
 int lmx_h_conv_split_k(int64_t px_per_frame, int N, int K, int cin);
 
-/* ==== MODEL level: YOLOv8 detections from raw frames (csrc/yolo_model.hip, csrc/host_yolo_image.cpp) ================================
+/* ==== MODEL level: YOLOv8 detections from raw frames (csrc/yolo_model.hip, csrc/model_handle.h, csrc/host_yolo_image.cpp) ===========
  * The whole of services/yolo-pipeline/app/main.py:76 — `self.yolo_model(frame, verbose=False, conf=...)`: LetterBox, the fused
  * Conv-BN-SiLU stack, Detect, non_max_suppression, scale_boxes — and, for pose models, of services/tleap-pipeline/app/main.py:150
  * (`result.keypoints`), behind one call: the launch sequence of lmx/yolo.py's YoloDetector written in C++ over the lmx_k_* entry
  * points above, with the descriptors lmx/kernels.py fills.  Same launches, same bits as YoloDetector.detect / detect_pose on both
  * precision plans (tests/test_gpu_native_yolo.py).
  * The model comes from a weight image of kind YOLO that lmx.native.write_yolo_image(detector, path, plans) writes (layout in
- * csrc/yolo_image.h): the stem, and per convolution the packed tensors of the f16 plan and / or the x3 tensors of the exact plan.
+ * csrc/image.h and csrc/yolo_image.h): the stem, and per convolution the packed tensors of the f16 plan and / or the x3 tensors of the exact plan.
  * Handle, image and error conventions as for lmx_dino: the handle belongs to the device current at open; ONE host thread and ONE
  * stream in flight per handle; several handles are independent; LMX_EINVAL / LMX_EHIP with lmx_last_error(). */
 typedef struct lmx_yolo lmx_yolo;

@@ -9,6 +9,8 @@ import struct
 import numpy as np
 import pytest
 
+from imagepatch import entry_offset as _entry_offset
+from imagepatch import patch as _patch
 from lmx import dino, native, weights
 from lmx import resample as R
 
@@ -100,21 +102,6 @@ def test_image_round_trip(images, arch):
         off, nbytes = rest[4:]
         assert raw_name.rstrip(b"\0").decode() == name and rank == a.ndim and tuple(rest[:rank]) == a.shape
         assert off % 64 == 0 and off >= data_off and raw[off:off + nbytes] == a.tobytes()
-
-
-def _entry_offset(raw, name):
-    dir_off, n = struct.unpack_from("<Q", raw, 24)[0], struct.unpack_from("<I", raw, 20)[0]
-    for i in range(n):
-        at = dir_off + i * native.ENTRY_BYTES
-        if raw[at:at + native.NAME_BYTES].rstrip(b"\0") == name.encode():
-            return at
-    raise KeyError(name)
-
-
-def _patch(raw, at, fmt, value):
-    b = bytearray(raw)
-    struct.pack_into(fmt, b, at, value)
-    return bytes(b)
 
 
 def _corruptions(cfg, raw):

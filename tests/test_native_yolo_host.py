@@ -12,6 +12,8 @@ import struct
 import numpy as np
 import pytest
 
+from imagepatch import entry_offset as _entry_offset
+from imagepatch import patch as _patch
 from lmx import dino, native, weights, yolo
 from lmx import kernels as K
 from lmx import letterbox as LB
@@ -188,21 +190,6 @@ def test_layer_table_twin_on_the_other_scales(scale, tmp_path):
     raw = path.read_bytes()
     n = struct.unpack_from("<I", raw, 20)[0]
     assert n == 2 + 2 * (len(det.w) - 1)  # the reader asked for every one of them: none is missing, none has another shape
-
-
-def _entry_offset(raw, name):
-    dir_off, n = struct.unpack_from("<Q", raw, 24)[0], struct.unpack_from("<I", raw, 20)[0]
-    for i in range(n):
-        at = dir_off + i * native.ENTRY_BYTES
-        if raw[at:at + native.NAME_BYTES].rstrip(b"\0") == name.encode():
-            return at
-    raise KeyError(name)
-
-
-def _patch(raw, at, fmt, value):
-    b = bytearray(raw)
-    struct.pack_into(fmt, b, at, value)
-    return bytes(b)
 
 
 def _corruptions(raw):

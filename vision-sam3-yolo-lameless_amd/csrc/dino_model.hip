@@ -1,5 +1,5 @@
-// dino_model.hip — the model-level entry points of the C-ABI for DINO: a handle that owns the weights of one weight image
-// (dino_image.h) and the workspace of one batch, and lmx_dino_embed, the launch sequence of lmx/dino.py's DinoEmbedder
+// dino_model.hip — the model-level entry points of the C-ABI for DINO: a handle (model_handle.h has what every handle owns) with the
+// weights of one weight image (dino_image.h) and the workspace of one batch, and lmx_dino_embed, the launch sequence of lmx/dino.py's DinoEmbedder
 // (preprocess + hidden_states + token_mean; services/dinov3-pipeline/app/main.py:98-113) written as host C++.
 // HOST code only: there is no kernel in this file.  Every launch goes through the same extern "C" lmx_k_* entry point the ctypes
 // binding calls, with the descriptor filled as lmx/kernels.py fills it, so the embedding is the Python plan's bit for bit
@@ -8,18 +8,13 @@
 #include <string.h>
 
 #include <map>
-#include <memory>
 #include <utility>
 #include <vector>
 
-#include "common.h"
 #include "dino_image.h"
+#include "model_handle.h"
 
 namespace {
-
-const int MAX_FRAME_SIZES = 16;  // prepared frame sizes a handle keeps (each owns its resized-frame workspace)
-
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
 
 // what lmx_dino_prepare builds for one frame size: the resize tables and the resized-frame workspace, one device allocation
 struct FrameSize {
@@ -39,12 +34,9 @@ struct Layer {
 
 }  // namespace
 
-struct lmx_dino {
-  int device = -1, max_batch = 0;
+struct lmx_dino : LmxHandleCore {
   LmxDinoCfg cfg;
-  char* weights = nullptr;  // the data section of the image
-  char* work = nullptr;     // the workspace of max_batch frames
-  hipStream_t own = nullptr;  // lmx_dino_embed_host's stream
+  char* work = nullptr;  // the workspace of max_batch frames
   // weights
   const void* pe_w = nullptr;
   const float *pe_b = nullptr, *prefix = nullptr, *pos = nullptr, *rope_cos = nullptr, *rope_sin = nullptr, *gf = nullptr, *bf = nullptr,
@@ -55,54 +47,19 @@ struct lmx_dino {
   float *x = nullptr, *y = nullptr;
   float mean_std[6];
   std::map<std::pair<int, int>, FrameSize> sizes;
-  // lmx_dino_embed_host's staging buffers (grown on demand; that call synchronises anyway)
-  uint8_t* stage_frames = nullptr;
-  size_t stage_bytes = 0;
-  float* stage_emb = nullptr;
 };
 
 namespace {
 
 void destroy(lmx_dino* m) {
-  if (!m) return;
   for (auto& kv : m->sizes) (void)hipFree(kv.second.blob);
-  (void)hipFree(m->stage_frames);
-  (void)hipFree(m->stage_emb);
   (void)hipFree(m->work);
-  (void)hipFree(m->weights);
-  if (m->own) (void)hipStreamDestroy(m->own);
+  lmx_handle_free(m);
   delete m;
 }
 
-int on_device(const lmx_dino* m, const char* fn) {
-  LMX_REQUIRE(m != nullptr, "%s: null handle", fn);
-  int cur = -1;
-  LMX_HIP(hipGetDevice(&cur));
-  LMX_REQUIRE(cur == m->device, "%s: the handle was opened on device %d, the current device is %d", fn, m->device, cur);
-  return LMX_OK;
-}
-
-// the data section of the image into one device allocation, through a bounded host buffer
-int upload_weights(const char* path, const LmxDinoImage& img, char** out) {
-  const uint64_t total = img.file_bytes - img.data_offset;
-  LMX_REQUIRE(total > 0, "lmx_dino_open_host: the image holds no tensor data");
-  FILE* f = fopen(path, "rb");
-  LMX_REQUIRE(f, "lmx_dino_open_host: cannot open '%s'", path);
-  std::unique_ptr<FILE, int (*)(FILE*)> closer(f, fclose);
-  LMX_REQUIRE(fseeko(f, (off_t)img.data_offset, SEEK_SET) == 0, "lmx_dino_open_host: cannot seek to data_offset");
-  LMX_HIP(hipMalloc(reinterpret_cast<void**>(out), (size_t)total));
-  const size_t chunk = (size_t)64 << 20;
-  std::vector<char> buf((size_t)(total < chunk ? total : chunk));
-  for (uint64_t done = 0; done < total;) {
-    const size_t n = (size_t)(total - done < chunk ? total - done : chunk);
-    LMX_REQUIRE(fread(buf.data(), 1, n, f) == n, "lmx_dino_open_host: the file ends inside the tensor data (truncated while reading?)");
-    LMX_HIP(hipMemcpy(*out + done, buf.data(), n, hipMemcpyHostToDevice));
-    done += n;
-  }
-  return LMX_OK;
-}
-
-int open_into(lmx_dino* m, const char* path, int max_batch) {
+int open_into(lmx_dino* m, const char* path) {
+  const int max_batch = m->max_batch;
   LmxDinoImage img;
   LMX_TRY(lmx_dino_image_parse(path, &img));
   const LmxDinoCfg& c = img.cfg;
@@ -111,13 +68,11 @@ int open_into(lmx_dino* m, const char* path, int max_batch) {
               "lmx_dino_open_host: max_batch %d x tokens %d x the widest row %lld does not fit 32-bit element indices", max_batch, c.tokens,
               (long long)widest);
   m->cfg = c;
-  m->max_batch = max_batch;
-  LMX_HIP(hipGetDevice(&m->device));
   for (int i = 0; i < 3; ++i) {
     m->mean_std[i] = (float)c.mean[i];
     m->mean_std[3 + i] = (float)c.std[i];
   }
-  LMX_TRY(upload_weights(path, img, &m->weights));
+  LMX_TRY(lmx_handle_upload_weights(m, "lmx_dino_open_host", path, img.data_offset, img.file_bytes));
   const uint64_t base = img.data_offset;
   auto at = [&](const LmxTensorRef& r) -> const void* { return r.nbytes ? m->weights + (r.offset - base) : nullptr; };
   auto f32 = [&](const LmxTensorRef& r) { return static_cast<const float*>(at(r)); };
@@ -136,26 +91,21 @@ int open_into(lmx_dino* m, const char* path, int max_batch) {
 
   // the workspace of max_batch frames: one allocation, every buffer on a 256-byte boundary
   const size_t B = (size_t)max_batch, T = (size_t)c.tokens, D = (size_t)c.hidden, I = (size_t)c.mlp, np = (size_t)c.grid * c.grid;
-  const size_t sz[8] = {B * np * c.k_pad * 2, B * np * D * 2, B * T * D * 4, B * T * D * 2, B * T * 3 * D * 2, B * T * D * 2, B * T * I * 2, B * T * D * 4};
-  size_t off[8], total = 0;
-  for (int i = 0; i < 8; ++i) {
-    off[i] = total;
-    total += up256(sz[i]);
-  }
-  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->work), total));
+  LmxLayout lay;
+  const size_t patch_bytes = B * np * c.k_pad * 2;
+  const size_t o_patches = lay.add(patch_bytes), o_xp = lay.add(B * np * D * 2), o_x = lay.add(B * T * D * 4), o_h = lay.add(B * T * D * 2),
+               o_qkv = lay.add(B * T * 3 * D * 2), o_a = lay.add(B * T * D * 2), o_u = lay.add(B * T * I * 2), o_y = lay.add(B * T * D * 4);
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->work), lay.total));
   // the patch matrix's columns beyond 3 * patch^2 (k_pad) are never written by a kernel: zero once, as kernels.patchify_norm's torch.zeros
-  LMX_HIP(hipMemset(m->work + off[0], 0, sz[0]));
-  m->patches = m->work + off[0];
-  m->xp = m->work + off[1];
-  m->x = reinterpret_cast<float*>(m->work + off[2]);
-  m->h = m->work + off[3];
-  m->qkv = m->work + off[4];
-  m->a = m->work + off[5];
-  m->u = m->work + off[6];
-  m->y = reinterpret_cast<float*>(m->work + off[7]);
-  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->stage_emb), B * D * 4));
-  LMX_HIP(hipStreamCreate(&m->own));
-  LMX_HIP(hipDeviceSynchronize());
+  LMX_HIP(hipMemset(m->work + o_patches, 0, patch_bytes));
+  m->patches = m->work + o_patches;
+  m->xp = m->work + o_xp;
+  m->x = reinterpret_cast<float*>(m->work + o_x);
+  m->h = m->work + o_h;
+  m->qkv = m->work + o_qkv;
+  m->a = m->work + o_a;
+  m->u = m->work + o_u;
+  m->y = reinterpret_cast<float*>(m->work + o_y);
   return LMX_OK;
 }
 
@@ -180,7 +130,7 @@ int prepare(lmx_dino* m, int h, int w, const FrameSize** out) {
   }
   FrameSize fs;
   LMX_TRY(lmx_dino_resized(c, h, w, &fs.nh, &fs.nw));
-  LMX_REQUIRE((int)m->sizes.size() < MAX_FRAME_SIZES, "lmx_dino_prepare: the handle already holds %d frame sizes; open another for more", MAX_FRAME_SIZES);
+  LMX_REQUIRE((int)m->sizes.size() < LMX_MAX_PREPARED, "lmx_dino_prepare: the handle already holds %d frame sizes; open another for more", LMX_MAX_PREPARED);
   const int nh = fs.nh, nw = fs.nw;
   std::vector<int32_t> bh, bv;
   std::vector<char> kh, kv;  // i32 or f32 bytes
@@ -214,54 +164,22 @@ int prepare(lmx_dino* m, int h, int w, const FrameSize** out) {
     fs.seg_cols = lmx_h_segment_cols(bh.data(), c.image, 256);
     LMX_REQUIRE(fs.seg_cols > 0, "lmx_dino_prepare: empty horizontal table for %d -> %d", w, nw);
   }
-  const size_t sz[6] = {bh.size() * 4, kh.size(), bv.size() * 4, kv.size(), tmp_h, tmp_v};
-  size_t off[6], total = 0;
-  for (int i = 0; i < 6; ++i) {
-    off[i] = total;
-    total += up256(sz[i]);
-  }
-  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&fs.blob), total));
-  const void* src[4] = {bh.data(), kh.data(), bv.data(), kv.data()};
-  for (int i = 0; i < 4; ++i)
-    if (sz[i]) {
-      const hipError_t e = hipMemcpy(fs.blob + off[i], src[i], sz[i], hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        (void)hipFree(fs.blob);
-        LMX_HIP(e);
-      }
-    }
-  fs.bounds_h = reinterpret_cast<int32_t*>(fs.blob + off[0]);
-  fs.kk_h = fs.blob + off[1];
-  fs.bounds_v = sz[2] ? reinterpret_cast<int32_t*>(fs.blob + off[2]) : nullptr;
-  fs.kk_v = sz[3] ? fs.blob + off[3] : nullptr;
-  fs.tmp_h = sz[4] ? reinterpret_cast<uint8_t*>(fs.blob + off[4]) : nullptr;
-  fs.tmp_v = sz[5] ? reinterpret_cast<uint8_t*>(fs.blob + off[5]) : nullptr;
+  LmxLayout lay;
+  const LmxUpload up[4] = {{lay.add(bh.size() * 4), bh.data(), bh.size() * 4},
+                           {lay.add(kh.size()), kh.data(), kh.size()},
+                           {lay.add(bv.size() * 4), bv.data(), bv.size() * 4},
+                           {lay.add(kv.size()), kv.data(), kv.size()}};
+  const size_t o_tmp_h = lay.add(tmp_h), o_tmp_v = lay.add(tmp_v);
+  LMX_TRY(lmx_alloc_and_upload(lay.total, up, 4, &fs.blob));
+  fs.bounds_h = reinterpret_cast<int32_t*>(fs.blob + up[0].at);
+  fs.kk_h = fs.blob + up[1].at;
+  fs.bounds_v = up[2].bytes ? reinterpret_cast<int32_t*>(fs.blob + up[2].at) : nullptr;
+  fs.kk_v = up[3].bytes ? fs.blob + up[3].at : nullptr;
+  fs.tmp_h = tmp_h ? reinterpret_cast<uint8_t*>(fs.blob + o_tmp_h) : nullptr;
+  fs.tmp_v = tmp_v ? reinterpret_cast<uint8_t*>(fs.blob + o_tmp_v) : nullptr;
   const auto ins = m->sizes.emplace(std::make_pair(h, w), fs);
   if (out) *out = &ins.first->second;
   return LMX_OK;
-}
-
-int gemm(const void* A, int64_t lda, const void* W, const float* bias, void* C, int64_t ldc, int out_dtype, int M, int N, int K, int act,
-         const float* scale, const void* res, int64_t ldr, hipStream_t st) {
-  lmx_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.A = A;
-  d.W = W;
-  d.bias = bias;
-  d.scale = scale;
-  d.res = res;
-  d.C = C;
-  d.lda = lda;
-  d.ldc = ldc;
-  d.ldr = res ? ldr : 0;
-  d.M = M;
-  d.N = N;
-  d.K = K;
-  d.act = act;
-  d.out_dtype = out_dtype;
-  d.a_mode = 0;
-  d.a_rep = 1;
-  return lmx_k_gemm(&d, st);
 }
 
 // DinoEmbedder.preprocess + hidden_states + token_mean for n <= max_batch frames
@@ -282,14 +200,14 @@ int embed_chunk(lmx_dino* m, const FrameSize& fs, const uint8_t* frames, int n, 
     LMX_TRY(lmx_k_patchify_norm(img, m->patches, n, fs.nh, fs.nw, (fs.nh - c.image) / 2, (fs.nw - c.image) / 2, c.grid, c.grid, c.patch, c.k_pad,
                                 m->lut, st));
   }
-  LMX_TRY(gemm(m->patches, c.k_pad, m->pe_w, m->pe_b, m->xp, D, LMX_F16, n * np, D, c.k_pad, LMX_ACT_NONE, nullptr, nullptr, 0, st));
+  LMX_TRY(lmx_gemm_dense(m->patches, c.k_pad, m->pe_w, m->pe_b, m->xp, D, LMX_F16, n * np, D, c.k_pad, LMX_ACT_NONE, nullptr, nullptr, 0, st));
   LMX_TRY(lmx_k_assemble_tokens(m->xp, m->prefix, m->pos, m->x, n, np, c.n_prefix, D, st));
   const float scale = (float)pow((double)hd, -0.5), eps = (float)c.eps;
   const int act1 = c.gated ? LMX_ACT_SWIGLU : LMX_ACT_GELU, N1 = c.gated ? 2 * I : I;
   half_t* q = static_cast<half_t*>(m->qkv);
   for (const Layer& L : m->layers) {
     LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, L.g1, L.b1, m->h, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
-    LMX_TRY(gemm(m->h, D, L.wqkv, L.bqkv, m->qkv, 3 * D, LMX_F16, rows, 3 * D, D, LMX_ACT_NONE, nullptr, nullptr, 0, st));
+    LMX_TRY(lmx_gemm_dense(m->h, D, L.wqkv, L.bqkv, m->qkv, 3 * D, LMX_F16, rows, 3 * D, D, LMX_ACT_NONE, nullptr, nullptr, 0, st));
     if (m->rope_cos) {
       LMX_TRY(lmx_k_rope(q, 3 * D, n, T, H, hd, c.n_prefix, m->rope_cos, m->rope_sin, st));
       LMX_TRY(lmx_k_rope(q + D, 3 * D, n, T, H, hd, c.n_prefix, m->rope_cos, m->rope_sin, st));
@@ -309,17 +227,17 @@ int embed_chunk(lmx_dino* m, const FrameSize& fs, const uint8_t* frames, int n, 
     ad.scale = scale;
     ad.mode = 0;
     LMX_TRY(lmx_k_attention(&ad, st));
-    LMX_TRY(gemm(m->a, D, L.wo, L.bo, m->x, D, LMX_F32, rows, D, D, LMX_ACT_NONE, L.ls1, m->x, D, st));
+    LMX_TRY(lmx_gemm_dense(m->a, D, L.wo, L.bo, m->x, D, LMX_F32, rows, D, D, LMX_ACT_NONE, L.ls1, m->x, D, st));
     LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, L.g2, L.b2, m->h, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
-    LMX_TRY(gemm(m->h, D, L.w1, L.bb1, m->u, I, LMX_F16, rows, N1, D, act1, nullptr, nullptr, 0, st));
-    LMX_TRY(gemm(m->u, I, L.w2, L.bb2, m->x, D, LMX_F32, rows, D, I, LMX_ACT_NONE, L.ls2, m->x, D, st));
+    LMX_TRY(lmx_gemm_dense(m->h, D, L.w1, L.bb1, m->u, I, LMX_F16, rows, N1, D, act1, nullptr, nullptr, 0, st));
+    LMX_TRY(lmx_gemm_dense(m->u, I, L.w2, L.bb2, m->x, D, LMX_F32, rows, D, I, LMX_ACT_NONE, L.ls2, m->x, D, st));
   }
   LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, m->gf, m->bf, m->y, LMX_F32, D, rows, D, eps, LMX_ACT_NONE, st));
   return lmx_k_token_mean(m->y, LMX_F32, emb, n, T, D, st);
 }
 
 int check_frames(const lmx_dino* m, const char* fn, const void* frames, int n, int h, int w, const void* emb) {
-  LMX_TRY(on_device(m, fn));
+  LMX_TRY(lmx_handle_on_device(m, fn));
   LMX_REQUIRE(n > 0, "%s: n = %d frames", fn, n);
   LMX_REQUIRE(h > 0 && w > 0, "%s: frame size %d x %d", fn, h, w);
   LMX_REQUIRE(frames && emb, "%s: null pointer", fn);
@@ -329,29 +247,10 @@ int check_frames(const lmx_dino* m, const char* fn, const void* frames, int n, i
 }  // namespace
 
 extern "C" int lmx_dino_open_host(const char* path_host, int max_batch, lmx_dino** out_host) {
-  LMX_REQUIRE(out_host != nullptr, "lmx_dino_open_host: out_host is null");
-  *out_host = nullptr;
-  LMX_REQUIRE(path_host != nullptr, "lmx_dino_open_host: path_host is null");
-  LMX_REQUIRE(max_batch > 0 && max_batch <= 65535, "lmx_dino_open_host: max_batch %d outside 1 .. 65535", max_batch);
-  lmx_dino* m = new lmx_dino();
-  const int rc = open_into(m, path_host, max_batch);
-  if (rc != LMX_OK) {
-    destroy(m);  // everything a failed open allocated; the error text of the failing step stays
-    return rc;
-  }
-  *out_host = m;
-  return LMX_OK;
+  return lmx_handle_open("lmx_dino_open_host", path_host, max_batch, out_host, open_into, destroy);
 }
 
-extern "C" void lmx_dino_close(lmx_dino* m) {
-  if (!m) return;
-  // work that still reads the handle's memory must be done before it is freed; frees follow the handle's device
-  int cur = -1;
-  const bool sw = hipGetDevice(&cur) == hipSuccess && cur != m->device && hipSetDevice(m->device) == hipSuccess;
-  (void)hipDeviceSynchronize();
-  destroy(m);
-  if (sw) (void)hipSetDevice(cur);
-}
+extern "C" void lmx_dino_close(lmx_dino* m) { lmx_handle_close(m, destroy); }
 
 extern "C" int lmx_dino_info(const lmx_dino* m, lmx_dino_info_t* info_host) {
   LMX_REQUIRE(m && info_host, "lmx_dino_info: null argument");
@@ -360,18 +259,16 @@ extern "C" int lmx_dino_info(const lmx_dino* m, lmx_dino_info_t* info_host) {
 }
 
 extern "C" int lmx_dino_prepare(lmx_dino* m, int h, int w) {
-  LMX_TRY(on_device(m, "lmx_dino_prepare"));
+  LMX_TRY(lmx_handle_on_device(m, "lmx_dino_prepare"));
   return prepare(m, h, w, nullptr);
 }
 
 extern "C" int lmx_dino_embed(lmx_dino* m, const uint8_t* frames, int n, int h, int w, int rgb, float* emb, lmx_stream_t stream) {
   LMX_TRY(check_frames(m, "lmx_dino_embed", frames, n, h, w, emb));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LMX_TRY(lmx_handle_stream_on_device(m, "lmx_dino_embed", st));  // before prepare: a refused call allocates nothing
   const FrameSize* fs = nullptr;
   LMX_TRY(prepare(m, h, w, &fs));  // a size seen before: a lookup
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int st_dev = -1;
-  LMX_TRY(lmx_stream_device(st, &st_dev));
-  LMX_REQUIRE(st_dev == m->device, "lmx_dino_embed: the stream belongs to device %d, the handle to device %d", st_dev, m->device);
   const size_t frame_bytes = (size_t)h * w * 3;
   for (int done = 0; done < n; done += m->max_batch) {
     const int nb = n - done < m->max_batch ? n - done : m->max_batch;
@@ -385,20 +282,18 @@ extern "C" int lmx_dino_embed_host(lmx_dino* m, const uint8_t* frames_host, int 
   const FrameSize* fs = nullptr;
   LMX_TRY(prepare(m, h, w, &fs));
   const size_t frame_bytes = (size_t)h * w * 3, D = (size_t)m->cfg.hidden;
-  const size_t need = frame_bytes * (size_t)(n < m->max_batch ? n : m->max_batch);
-  if (need > m->stage_bytes) {
-    LMX_HIP(hipStreamSynchronize(m->own));
-    (void)hipFree(m->stage_frames);
-    m->stage_frames = nullptr;
-    m->stage_bytes = 0;
-    LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->stage_frames), need));
-    m->stage_bytes = need;
-  }
+  // staging of one chunk: frames | embeddings, each on a 256-byte boundary
+  const size_t B = (size_t)(n < m->max_batch ? n : m->max_batch);
+  LmxLayout lay;
+  const size_t o_frames = lay.add(B * frame_bytes), o_emb = lay.add(B * D * sizeof(float));
+  LMX_TRY(lmx_handle_grow_stage(m, lay.total));
+  uint8_t* frames = reinterpret_cast<uint8_t*>(m->stage + o_frames);
+  float* emb = reinterpret_cast<float*>(m->stage + o_emb);
   for (int done = 0; done < n; done += m->max_batch) {
     const int nb = n - done < m->max_batch ? n - done : m->max_batch;
-    LMX_HIP(hipMemcpyAsync(m->stage_frames, frames_host + (size_t)done * frame_bytes, nb * frame_bytes, hipMemcpyHostToDevice, m->own));
-    LMX_TRY(embed_chunk(m, *fs, m->stage_frames, nb, h, w, rgb, m->stage_emb, m->own));
-    LMX_HIP(hipMemcpyAsync(emb_host + (size_t)done * D, m->stage_emb, nb * D * sizeof(float), hipMemcpyDeviceToHost, m->own));
+    LMX_HIP(hipMemcpyAsync(frames, frames_host + (size_t)done * frame_bytes, nb * frame_bytes, hipMemcpyHostToDevice, m->own));
+    LMX_TRY(embed_chunk(m, *fs, frames, nb, h, w, rgb, emb, m->own));
+    LMX_HIP(hipMemcpyAsync(emb_host + (size_t)done * D, emb, nb * D * sizeof(float), hipMemcpyDeviceToHost, m->own));
     LMX_HIP(hipStreamSynchronize(m->own));
   }
   return LMX_OK;

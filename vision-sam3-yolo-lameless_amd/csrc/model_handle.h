@@ -1,0 +1,180 @@
+// model_handle.h — what every model-level handle of the C-ABI (dino_model.hip, yolo_model.hip) owns and does the same way: the device
+// it was opened on, the weights of its image in one allocation, a stream of its own for the *_host entry points, one staging blob,
+// and the open / close / device-check protocol around them.  HOST code, header-only: a plain struct and free functions; the model's
+// handle derives from the struct and keeps its plan, its workspace and its prepared entries to itself.
+// Each function that can refuse takes the calling entry point's name (`fn`) for its message.
+#pragma once
+#include <stdio.h>
+#include <string.h>
+
+#include <memory>
+#include <vector>
+
+#include "common.h"
+
+const int LMX_MAX_PREPARED = 16;  // prepared entries (a frame size, or a frame size and a plan) a handle keeps; each owns its workspace
+
+struct LmxHandleCore {
+  int device = -1, max_batch = 0;
+  char* weights = nullptr;    // the data section of the image
+  hipStream_t own = nullptr;  // the *_host entry points' stream
+  // the *_host entry points' staging blob (grown on demand; those calls synchronise anyway)
+  char* stage = nullptr;
+  size_t stage_bytes = 0;
+};
+
+inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+
+// offsets inside one allocation: every buffer on a 256-byte boundary
+struct LmxLayout {
+  size_t total = 0;
+  size_t add(size_t bytes) {
+    const size_t at = total;
+    total += up256(bytes);
+    return at;
+  }
+};
+
+// one host table bound for offset `at` of a blob (bytes 0: nothing to copy)
+struct LmxUpload {
+  size_t at;
+  const void* src;
+  size_t bytes;
+};
+
+// One device allocation of `total` bytes with the `n` host tables copied in, complete when the call returns (the prepare calls are
+// documented SYNCHRONOUS).  On failure nothing stays allocated and *blob is null.
+inline int lmx_alloc_and_upload(size_t total, const LmxUpload* up, int n, char** blob) {
+  *blob = nullptr;
+  char* b = nullptr;
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&b), total));
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < n && e == hipSuccess; ++i)
+    if (up[i].bytes) e = hipMemcpy(b + up[i].at, up[i].src, up[i].bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    (void)hipFree(b);
+    LMX_HIP(e);
+  }
+  *blob = b;
+  return LMX_OK;
+}
+
+inline int lmx_handle_on_device(const LmxHandleCore* m, const char* fn) {
+  LMX_REQUIRE(m != nullptr, "%s: null handle", fn);
+  int cur = -1;
+  LMX_HIP(hipGetDevice(&cur));
+  LMX_REQUIRE(cur == m->device, "%s: the handle was opened on device %d, the current device is %d", fn, m->device, cur);
+  return LMX_OK;
+}
+
+// a caller's stream must belong to the handle's device.  Check it BEFORE preparing anything: a refused call allocates nothing
+inline int lmx_handle_stream_on_device(const LmxHandleCore* m, const char* fn, hipStream_t st) {
+  int st_dev = -1;
+  LMX_TRY(lmx_stream_device(st, &st_dev));
+  LMX_REQUIRE(st_dev == m->device, "%s: the stream belongs to device %d, the handle to device %d", fn, st_dev, m->device);
+  return LMX_OK;
+}
+
+// the handle takes the current device, and the data section [data_offset, file_bytes) of the image into one device allocation
+// through a bounded host buffer
+inline int lmx_handle_upload_weights(LmxHandleCore* m, const char* fn, const char* path, uint64_t data_offset, uint64_t file_bytes) {
+  const uint64_t total = file_bytes - data_offset;
+  LMX_REQUIRE(total > 0, "%s: the image holds no tensor data", fn);
+  LMX_HIP(hipGetDevice(&m->device));
+  FILE* f = fopen(path, "rb");
+  LMX_REQUIRE(f, "%s: cannot open '%s'", fn, path);
+  std::unique_ptr<FILE, int (*)(FILE*)> closer(f, fclose);
+  LMX_REQUIRE(fseeko(f, (off_t)data_offset, SEEK_SET) == 0, "%s: cannot seek to data_offset", fn);
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->weights), (size_t)total));
+  const size_t chunk = (size_t)64 << 20;
+  std::vector<char> buf((size_t)(total < chunk ? total : chunk));
+  for (uint64_t done = 0; done < total;) {
+    const size_t n = (size_t)(total - done < chunk ? total - done : chunk);
+    LMX_REQUIRE(fread(buf.data(), 1, n, f) == n, "%s: the file ends inside the tensor data (truncated while reading?)", fn);
+    LMX_HIP(hipMemcpy(m->weights + done, buf.data(), n, hipMemcpyHostToDevice));
+    done += n;
+  }
+  return LMX_OK;
+}
+
+// at least `need` bytes of staging (the old blob is idle once the handle's stream has drained)
+inline int lmx_handle_grow_stage(LmxHandleCore* m, size_t need) {
+  if (need <= m->stage_bytes) return LMX_OK;
+  LMX_HIP(hipStreamSynchronize(m->own));
+  (void)hipFree(m->stage);
+  m->stage = nullptr;
+  m->stage_bytes = 0;
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->stage), need));
+  m->stage_bytes = need;
+  return LMX_OK;
+}
+
+// what the core owns; the model's destroy frees its own allocations, calls this, and deletes the handle
+inline void lmx_handle_free(LmxHandleCore* m) {
+  (void)hipFree(m->stage);
+  (void)hipFree(m->weights);
+  if (m->own) (void)hipStreamDestroy(m->own);
+}
+
+// the last steps of an open: the handle's own stream, and everything the open enqueued is done
+inline int lmx_handle_finish_open(LmxHandleCore* m) {
+  LMX_HIP(hipStreamCreate(&m->own));
+  LMX_HIP(hipDeviceSynchronize());
+  return LMX_OK;
+}
+
+// lmx_<model>_open_host: `open_into` parses the image, uploads the weights (lmx_handle_upload_weights) and builds the model's own
+// state in a fresh handle.  On any failure the handle is destroyed, *out_host stays NULL and the failing step's error text stays.
+template <class H>
+int lmx_handle_open(const char* fn, const char* path_host, int max_batch, H** out_host, int (*open_into)(H*, const char*), void (*destroy)(H*)) {
+  LMX_REQUIRE(out_host != nullptr, "%s: out_host is null", fn);
+  *out_host = nullptr;
+  LMX_REQUIRE(path_host != nullptr, "%s: path_host is null", fn);
+  LMX_REQUIRE(max_batch > 0 && max_batch <= 65535, "%s: max_batch %d outside 1 .. 65535", fn, max_batch);
+  H* m = new H();
+  m->max_batch = max_batch;
+  int rc = open_into(m, path_host);
+  if (rc == LMX_OK) rc = lmx_handle_finish_open(m);
+  if (rc != LMX_OK) {
+    destroy(m);
+    return rc;
+  }
+  *out_host = m;
+  return LMX_OK;
+}
+
+// lmx_<model>_close: work that still reads the handle's memory must be done before it is freed; frees follow the handle's device
+template <class H>
+void lmx_handle_close(H* m, void (*destroy)(H*)) {
+  if (!m) return;
+  int cur = -1;
+  const bool sw = hipGetDevice(&cur) == hipSuccess && cur != m->device && hipSetDevice(m->device) == hipSuccess;
+  (void)hipDeviceSynchronize();
+  destroy(m);
+  if (sw) (void)hipSetDevice(cur);
+}
+
+// a dense GEMM C = act(A W^T + bias) (* scale) (+ res) as lmx/kernels.py's gemm fills its descriptor
+inline int lmx_gemm_dense(const void* A, int64_t lda, const void* W, const float* bias, void* C, int64_t ldc, int out_dtype, int M, int N, int K, int act,
+                          const float* scale, const void* res, int64_t ldr, hipStream_t st) {
+  lmx_gemm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.A = A;
+  d.W = W;
+  d.bias = bias;
+  d.scale = scale;
+  d.res = res;
+  d.C = C;
+  d.lda = lda;
+  d.ldc = ldc;
+  d.ldr = res ? ldr : 0;
+  d.M = M;
+  d.N = N;
+  d.K = K;
+  d.act = act;
+  d.out_dtype = out_dtype;
+  d.a_mode = 0;
+  d.a_rep = 1;
+  return lmx_k_gemm(&d, st);
+}

@@ -1,7 +1,7 @@
 // yolo_image.h — the weight image of a YOLOv8 detector (written by lmx/native.py write_yolo_image, read by host_yolo_image.cpp) as the
 // model handle (yolo_model.hip) sees it.  Host code only: nothing here needs HIP.
 //
-// The container is dino_image.h's (header, config block, directory of 88-byte entries, 64-byte aligned data, version 1), kind YOLO:
+// The container is image.h's (header, config block, directory of 88-byte entries, 64-byte aligned data, version 1), kind YOLO:
 //   config  at 48      10 x i32 (LmxYoloCfg's integers in declaration order), then the names blob: n_names NUL-terminated UTF-8 strings
 //                      in class order, names_bytes long, zero-padded to a multiple of 8
 //   tensors            stem.w f32 [3][3][3][C0] (ky, kx, c, co), stem.b f32 [C0];
@@ -17,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "dino_image.h"
+#include "image.h"
 
 enum { LMX_YOLO_CONFIG_INTS = 10 };
 

@@ -1,7 +1,7 @@
-// yolo_model.hip — the model-level entry points of the C-ABI for YOLOv8: a handle that owns the weights of one weight image
-// (yolo_image.h) and, per prepared (frame size, plan), the workspace of one batch; lmx_yolo_predict / lmx_yolo_detect are the launch
-// sequence of lmx/yolo.py's YoloDetector (preprocess + forward_letterboxed + nms + scale_boxes (+ pose_gather);
-// services/yolo-pipeline/app/main.py:76, services/tleap-pipeline/app/main.py:150) written as host C++.
+// yolo_model.hip — the model-level entry points of the C-ABI for YOLOv8: a handle (model_handle.h has what every handle owns) with the
+// weights of one weight image (yolo_image.h) and, per prepared (frame size, plan), the workspace of one batch; lmx_yolo_predict /
+// lmx_yolo_detect are the launch sequence of lmx/yolo.py's YoloDetector (preprocess + forward_letterboxed + nms + scale_boxes
+// (+ pose_gather); services/yolo-pipeline/app/main.py:76, services/tleap-pipeline/app/main.py:150) written as host C++.
 // HOST code only: there is no kernel in this file.  Every launch goes through the same extern "C" lmx_k_* entry point the ctypes
 // binding calls, with the descriptor filled as lmx/kernels.py fills it, so the outputs are the Python plan's bit for bit on both
 // precision plans (tests/test_gpu_native_yolo.py).
@@ -11,24 +11,20 @@
 #include <string.h>
 
 #include <map>
-#include <memory>
 #include <string>
 #include <tuple>
 #include <vector>
 
-#include "common.h"
+#include "model_handle.h"
 #include "yolo_image.h"
 
 namespace {
 
-const int MAX_PREPARED = 16;                // prepared (frame size, plan) pairs a handle keeps (each owns its workspace)
 // The GEMM kernels walk an operand with 32-bit byte offsets.  lmx_k_gemm itself checks "smaller than 2 GB" for pooled rows (a_mode 2)
 // only; for the dense and convolution launches this plan makes (a_mode 0 / 1) NOTHING in the launcher checks it, so the guard in
 // Run::alloc / need_scratch is the only one: it is not redundant.
 const int64_t MAX_BUFFER_BYTES = 0x7fffffffll;
 const float NMS_MAX_WH = 7680.f;
-
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
 
 // one convolution's operands under one plan
 struct ConvW {
@@ -67,17 +63,11 @@ struct Prepared {
 
 }  // namespace
 
-struct lmx_yolo {
-  int device = -1, max_batch = 0;
+struct lmx_yolo : LmxHandleCore {
   LmxYoloImage img;
-  char* weights = nullptr;    // the data section of the image
-  hipStream_t own = nullptr;  // lmx_yolo_detect_host's stream
   const float *stem_w = nullptr, *stem_b = nullptr;
   std::map<std::string, ConvW> conv[2];  // per plan (LMX_YOLO_F16, LMX_YOLO_EXACT)
   std::map<std::tuple<int, int, int>, Prepared> prepared;
-  // lmx_yolo_detect_host's staging buffer (grown on demand; that call synchronises anyway)
-  char* stage = nullptr;
-  size_t stage_bytes = 0;
 };
 
 namespace {
@@ -130,23 +120,7 @@ struct Run {
 int gemm1(Run& r, const Act& x, const ConvW& w, int act, const float* scale, void* C, int64_t ldc, int out_dtype) {
   LMX_REQUIRE(w.K == x.C, "lmx_yolo: a 1 x 1 convolution with %d weight columns reads %d channels", w.K, x.C);
   if (!r.launch) return LMX_OK;
-  lmx_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.A = r.at(x);
-  d.W = w.w;
-  d.bias = w.b;
-  d.scale = scale;
-  d.C = C;
-  d.lda = x.ps;
-  d.ldc = ldc;
-  d.M = r.n * x.H * x.W;
-  d.N = w.cout;
-  d.K = x.C;
-  d.act = act;
-  d.out_dtype = out_dtype;
-  d.a_mode = 0;
-  d.a_rep = 1;
-  return lmx_k_gemm(&d, r.st);
+  return lmx_gemm_dense(r.at(x), x.ps, w.w, w.b, C, ldc, out_dtype, r.n * x.H * x.W, w.cout, x.C, act, scale, nullptr, 0, r.st);
 }
 
 // K.conv3x3: 3 x 3 / pad 1 as implicit GEMM
@@ -356,47 +330,14 @@ int forward(Run& r, const uint8_t* boxed, int H, int W, float* pred, Act kraw[3]
 }
 
 void destroy(lmx_yolo* m) {
-  if (!m) return;
   for (auto& kv : m->prepared) (void)hipFree(kv.second.blob);
-  (void)hipFree(m->stage);
-  (void)hipFree(m->weights);
-  if (m->own) (void)hipStreamDestroy(m->own);
+  lmx_handle_free(m);
   delete m;
 }
 
-int on_device(const lmx_yolo* m, const char* fn) {
-  LMX_REQUIRE(m != nullptr, "%s: null handle", fn);
-  int cur = -1;
-  LMX_HIP(hipGetDevice(&cur));
-  LMX_REQUIRE(cur == m->device, "%s: the handle was opened on device %d, the current device is %d", fn, m->device, cur);
-  return LMX_OK;
-}
-
-// the data section of the image into one device allocation, through a bounded host buffer
-int upload_weights(const char* path, const LmxYoloImage& img, char** out) {
-  const uint64_t total = img.file_bytes - img.data_offset;
-  LMX_REQUIRE(total > 0, "lmx_yolo_open_host: the image holds no tensor data");
-  FILE* f = fopen(path, "rb");
-  LMX_REQUIRE(f, "lmx_yolo_open_host: cannot open '%s'", path);
-  std::unique_ptr<FILE, int (*)(FILE*)> closer(f, fclose);
-  LMX_REQUIRE(fseeko(f, (off_t)img.data_offset, SEEK_SET) == 0, "lmx_yolo_open_host: cannot seek to data_offset");
-  LMX_HIP(hipMalloc(reinterpret_cast<void**>(out), (size_t)total));
-  const size_t chunk = (size_t)64 << 20;
-  std::vector<char> buf((size_t)(total < chunk ? total : chunk));
-  for (uint64_t done = 0; done < total;) {
-    const size_t n = (size_t)(total - done < chunk ? total - done : chunk);
-    LMX_REQUIRE(fread(buf.data(), 1, n, f) == n, "lmx_yolo_open_host: the file ends inside the tensor data (truncated while reading?)");
-    LMX_HIP(hipMemcpy(*out + done, buf.data(), n, hipMemcpyHostToDevice));
-    done += n;
-  }
-  return LMX_OK;
-}
-
-int open_into(lmx_yolo* m, const char* path, int max_batch) {
+int open_into(lmx_yolo* m, const char* path) {
   LMX_TRY(lmx_yolo_image_parse(path, &m->img));
-  m->max_batch = max_batch;
-  LMX_HIP(hipGetDevice(&m->device));
-  LMX_TRY(upload_weights(path, m->img, &m->weights));
+  LMX_TRY(lmx_handle_upload_weights(m, "lmx_yolo_open_host", path, m->img.data_offset, m->img.file_bytes));
   const uint64_t base = m->img.data_offset;
   auto at = [&](const LmxTensorRef& r) -> const void* { return r.nbytes ? m->weights + (r.offset - base) : nullptr; };
   auto f32 = [&](const LmxTensorRef& r) { return static_cast<const float*>(at(r)); };
@@ -407,8 +348,6 @@ int open_into(lmx_yolo* m, const char* path, int max_batch) {
     if (c.w.nbytes) m->conv[LMX_YOLO_F16][c.name] = ConvW{at(c.w), f32(c.b), nullptr, c.cout, K};
     if (c.xw.nbytes) m->conv[LMX_YOLO_EXACT][c.name] = ConvW{at(c.xw), f32(c.xb), f32(c.xs), c.cout, 3 * K};
   }
-  LMX_HIP(hipStreamCreate(&m->own));
-  LMX_HIP(hipDeviceSynchronize());
   return LMX_OK;
 }
 
@@ -436,8 +375,8 @@ int prepare(lmx_yolo* m, int h, int w, int precision, const Prepared** out) {
   LMX_TRY(check_precision(m, "lmx_yolo_prepare", precision));
   Prepared P;
   LMX_TRY(geometry(m, h, w, &P.geo, &P.A));
-  LMX_REQUIRE((int)m->prepared.size() < MAX_PREPARED, "lmx_yolo_prepare: the handle already holds %d (frame size, plan) pairs; open another for more",
-              MAX_PREPARED);
+  LMX_REQUIRE((int)m->prepared.size() < LMX_MAX_PREPARED,
+              "lmx_yolo_prepare: the handle already holds %d (frame size, plan) pairs; open another for more", LMX_MAX_PREPARED);
   const lmx_letterbox_geo_t& g = P.geo;
   const bool resize = g.rh != h || g.rw != w;
   std::vector<int32_t> xofs, yofs;
@@ -462,40 +401,25 @@ int prepare(lmx_yolo* m, int h, int w, int precision, const Prepared** out) {
               boxed_bytes < MAX_BUFFER_BYTES ? "pred" : "letterboxed frames", (long long)(boxed_bytes < MAX_BUFFER_BYTES ? pred_bytes : boxed_bytes),
               m->max_batch);
   LMX_REQUIRE(nms_bytes > 0, "lmx_yolo_prepare: lmx_nms_workspace_bytes(%d, %d) = %lld", m->max_batch, P.A, (long long)nms_bytes);
-  const size_t sz[9] = {xofs.size() * 4, ialpha.size() * 2, yofs.size() * 4, ibeta.size() * 2, (size_t)boxed_bytes, (size_t)pred_bytes, (size_t)nms_bytes,
-                        P.plan_bytes, P.scratch_bytes};
-  size_t off[9], total = 0;
-  for (int i = 0; i < 9; ++i) {
-    off[i] = total;
-    total += up256(sz[i]);
-  }
-  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&P.blob), total));
-  const void* src[4] = {xofs.data(), ialpha.data(), yofs.data(), ibeta.data()};
-  for (int i = 0; i < 4; ++i)
-    if (sz[i]) {
-      const hipError_t e = hipMemcpy(P.blob + off[i], src[i], sz[i], hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        (void)hipFree(P.blob);
-        LMX_HIP(e);
-      }
-    }
+  LmxLayout lay;
+  const LmxUpload up[4] = {{lay.add(xofs.size() * 4), xofs.data(), xofs.size() * 4},
+                           {lay.add(ialpha.size() * 2), ialpha.data(), ialpha.size() * 2},
+                           {lay.add(yofs.size() * 4), yofs.data(), yofs.size() * 4},
+                           {lay.add(ibeta.size() * 2), ibeta.data(), ibeta.size() * 2}};
+  const size_t o_boxed = lay.add((size_t)boxed_bytes), o_pred = lay.add((size_t)pred_bytes), o_nms = lay.add((size_t)nms_bytes),
+               o_plan = lay.add(P.plan_bytes);
+  lay.add(P.scratch_bytes);  // the plan's f32 scratch, right behind its buffers
+  LMX_TRY(lmx_alloc_and_upload(lay.total, up, 4, &P.blob));
   if (resize) {
-    P.xofs = reinterpret_cast<int32_t*>(P.blob + off[0]);
-    P.ialpha = reinterpret_cast<int16_t*>(P.blob + off[1]);
-    P.yofs = reinterpret_cast<int32_t*>(P.blob + off[2]);
-    P.ibeta = reinterpret_cast<int16_t*>(P.blob + off[3]);
+    P.xofs = reinterpret_cast<int32_t*>(P.blob + up[0].at);
+    P.ialpha = reinterpret_cast<int16_t*>(P.blob + up[1].at);
+    P.yofs = reinterpret_cast<int32_t*>(P.blob + up[2].at);
+    P.ibeta = reinterpret_cast<int16_t*>(P.blob + up[3].at);
   }
-  P.boxed = reinterpret_cast<uint8_t*>(P.blob + off[4]);
-  P.pred = reinterpret_cast<float*>(P.blob + off[5]);
-  P.nms_ws = P.blob + off[6];
-  P.plan = P.blob + off[7];
-  {
-    const hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-      (void)hipFree(P.blob);
-      LMX_HIP(e);
-    }
-  }
+  P.boxed = reinterpret_cast<uint8_t*>(P.blob + o_boxed);
+  P.pred = reinterpret_cast<float*>(P.blob + o_pred);
+  P.nms_ws = P.blob + o_nms;
+  P.plan = P.blob + o_plan;
   const auto ins = m->prepared.emplace(key, P);
   if (out) *out = &ins.first->second;
   return LMX_OK;
@@ -540,7 +464,7 @@ int detect_chunk(const lmx_yolo* m, const Prepared& P, int precision, const uint
 }
 
 int check_frames(const lmx_yolo* m, const char* fn, const void* frames, int n, int h, int w, int precision) {
-  LMX_TRY(on_device(m, fn));
+  LMX_TRY(lmx_handle_on_device(m, fn));
   LMX_REQUIRE(n > 0, "%s: n = %d frames", fn, n);
   LMX_REQUIRE(h > 0 && w > 0, "%s: frame size %d x %d", fn, h, w);
   LMX_REQUIRE(frames != nullptr, "%s: null pointer (frames)", fn);
@@ -557,39 +481,13 @@ int check_detect(const lmx_yolo* m, const char* fn, const void* frames, int n, i
   return LMX_OK;
 }
 
-int stream_on_device(const lmx_yolo* m, const char* fn, hipStream_t st) {
-  int st_dev = -1;
-  LMX_TRY(lmx_stream_device(st, &st_dev));
-  LMX_REQUIRE(st_dev == m->device, "%s: the stream belongs to device %d, the handle to device %d", fn, st_dev, m->device);
-  return LMX_OK;
-}
-
 }  // namespace
 
 extern "C" int lmx_yolo_open_host(const char* path_host, int max_batch, lmx_yolo** out_host) {
-  LMX_REQUIRE(out_host != nullptr, "lmx_yolo_open_host: out_host is null");
-  *out_host = nullptr;
-  LMX_REQUIRE(path_host != nullptr, "lmx_yolo_open_host: path_host is null");
-  LMX_REQUIRE(max_batch > 0 && max_batch <= 65535, "lmx_yolo_open_host: max_batch %d outside 1 .. 65535", max_batch);
-  lmx_yolo* m = new lmx_yolo();
-  const int rc = open_into(m, path_host, max_batch);
-  if (rc != LMX_OK) {
-    destroy(m);  // everything a failed open allocated; the error text of the failing step stays
-    return rc;
-  }
-  *out_host = m;
-  return LMX_OK;
+  return lmx_handle_open("lmx_yolo_open_host", path_host, max_batch, out_host, open_into, destroy);
 }
 
-extern "C" void lmx_yolo_close(lmx_yolo* m) {
-  if (!m) return;
-  // work that still reads the handle's memory must be done before it is freed; frees follow the handle's device
-  int cur = -1;
-  const bool sw = hipGetDevice(&cur) == hipSuccess && cur != m->device && hipSetDevice(m->device) == hipSuccess;
-  (void)hipDeviceSynchronize();
-  destroy(m);
-  if (sw) (void)hipSetDevice(cur);
-}
+extern "C" void lmx_yolo_close(lmx_yolo* m) { lmx_handle_close(m, destroy); }
 
 extern "C" int lmx_yolo_info(const lmx_yolo* m, lmx_yolo_info_t* info_host) {
   LMX_REQUIRE(m && info_host, "lmx_yolo_info: null argument");
@@ -603,7 +501,7 @@ extern "C" const char* lmx_yolo_class_name(const lmx_yolo* m, int cls) {
 }
 
 extern "C" int lmx_yolo_prepare(lmx_yolo* m, int h, int w, int precision) {
-  LMX_TRY(on_device(m, "lmx_yolo_prepare"));
+  LMX_TRY(lmx_handle_on_device(m, "lmx_yolo_prepare"));
   return prepare(m, h, w, precision, nullptr);
 }
 
@@ -620,7 +518,7 @@ extern "C" int lmx_yolo_predict(lmx_yolo* m, const uint8_t* frames, int n, int h
   LMX_TRY(check_frames(m, "lmx_yolo_predict", frames, n, h, w, precision));
   LMX_REQUIRE(pred != nullptr, "lmx_yolo_predict: null pointer (pred)");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LMX_TRY(stream_on_device(m, "lmx_yolo_predict", st));  // before prepare: a refused call allocates nothing
+  LMX_TRY(lmx_handle_stream_on_device(m, "lmx_yolo_predict", st));  // before prepare: a refused call allocates nothing
   const Prepared* P = nullptr;
   LMX_TRY(prepare(m, h, w, precision, &P));  // a pair seen before: a lookup
   const size_t frame_bytes = (size_t)h * w * 3, pred_row = (size_t)P->A * (4 + m->img.cfg.nc);
@@ -636,7 +534,7 @@ extern "C" int lmx_yolo_detect(lmx_yolo* m, const uint8_t* frames, int n, int h,
                                float* boxes, float* scores, int32_t* cls, int32_t* src, int32_t* counts, float* kpts, lmx_stream_t stream) {
   LMX_TRY(check_detect(m, "lmx_yolo_detect", frames, n, h, w, precision, max_det, boxes, scores, cls, src, counts, kpts));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LMX_TRY(stream_on_device(m, "lmx_yolo_detect", st));  // before prepare: a refused call allocates nothing
+  LMX_TRY(lmx_handle_stream_on_device(m, "lmx_yolo_detect", st));  // before prepare: a refused call allocates nothing
   const Prepared* P = nullptr;
   LMX_TRY(prepare(m, h, w, precision, &P));
   const size_t frame_bytes = (size_t)h * w * 3, md = (size_t)max_det, kp = md * m->img.cfg.kpt_k * m->img.cfg.kpt_ndim;
@@ -659,24 +557,15 @@ extern "C" int lmx_yolo_detect_host(lmx_yolo* m, const uint8_t* frames_host, int
   // staging of one chunk: frames | boxes | scores | cls | src | counts | kpts, each on a 256-byte boundary
   const size_t B = (size_t)(n < m->max_batch ? n : m->max_batch), frame_bytes = (size_t)h * w * 3, md = (size_t)max_det;
   const size_t kp = md * m->img.cfg.kpt_k * m->img.cfg.kpt_ndim;
-  const size_t sz[7] = {B * frame_bytes, B * md * 16, B * md * 4, B * md * 4, B * md * 4, B * 4, B * kp * 4};
-  size_t off[7], need = 0;
-  for (int i = 0; i < 7; ++i) {
-    off[i] = need;
-    need += up256(sz[i]);
-  }
-  if (need > m->stage_bytes) {
-    LMX_HIP(hipStreamSynchronize(m->own));
-    (void)hipFree(m->stage);
-    m->stage = nullptr;
-    m->stage_bytes = 0;
-    LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->stage), need));
-    m->stage_bytes = need;
-  }
+  LmxLayout lay;
+  lay.add(B * frame_bytes);  // the frames, at the blob's start
+  const size_t o_boxes = lay.add(B * md * 16), o_scores = lay.add(B * md * 4), o_cls = lay.add(B * md * 4), o_src = lay.add(B * md * 4),
+               o_counts = lay.add(B * 4), o_kpts = lay.add(B * kp * 4);
+  LMX_TRY(lmx_handle_grow_stage(m, lay.total));
   char* s = m->stage;
-  float *boxes = reinterpret_cast<float*>(s + off[1]), *scores = reinterpret_cast<float*>(s + off[2]);
-  int32_t *cls = reinterpret_cast<int32_t*>(s + off[3]), *src = reinterpret_cast<int32_t*>(s + off[4]), *counts = reinterpret_cast<int32_t*>(s + off[5]);
-  float* kpts = kpts_host ? reinterpret_cast<float*>(s + off[6]) : nullptr;
+  float *boxes = reinterpret_cast<float*>(s + o_boxes), *scores = reinterpret_cast<float*>(s + o_scores);
+  int32_t *cls = reinterpret_cast<int32_t*>(s + o_cls), *src = reinterpret_cast<int32_t*>(s + o_src), *counts = reinterpret_cast<int32_t*>(s + o_counts);
+  float* kpts = kpts_host ? reinterpret_cast<float*>(s + o_kpts) : nullptr;
   for (int done = 0; done < n; done += m->max_batch) {
     const size_t nb = (size_t)(n - done < m->max_batch ? n - done : m->max_batch), d = (size_t)done;
     LMX_HIP(hipMemcpyAsync(s, frames_host + d * frame_bytes, nb * frame_bytes, hipMemcpyHostToDevice, m->own));

@@ -1,8 +1,9 @@
-"""The model-level C entry points (include/lmx.h, "MODEL level"; csrc/dino_model.hip) seen from Python.
+"""The model-level C entry points (include/lmx.h, "MODEL level"; csrc/dino_model.hip, csrc/yolo_model.hip) seen from Python.
 
-``write_dino_image`` exports a loaded ``DinoEmbedder`` as a weight image: one little-endian file holding the embedder's tensors
-bit for bit in their final device form (csrc/dino_image.h has the layout).  A C program opens it with ``lmx_dino_open_host`` and
-asks ``lmx_dino_embed`` / ``lmx_dino_embed_host`` for embeddings without Python (examples/dino_embed.c).
+``write_image`` writes the weight-image container (csrc/image.h has the layout): one little-endian file holding a model's config
+block and its tensors bit for bit in their final device form.  ``write_dino_image`` exports a loaded ``DinoEmbedder`` that way
+(csrc/dino_image.h has its config block).  A C program opens it with ``lmx_dino_open_host`` and asks ``lmx_dino_embed`` /
+``lmx_dino_embed_host`` for embeddings without Python (examples/dino_embed.c).
 
 ``NativeDino`` is the thin binding of that handle.  No plan logic lives here: the launch sequence is C++, and it is the launch
 sequence of ``DinoEmbedder.embed_frames`` — same entry points, same descriptors, same bits (tests/test_gpu_native_dino.py).
@@ -12,7 +13,8 @@ lmx/resample.py.
 ``write_yolo_image`` / ``NativeYolo`` are the same for a ``YoloDetector`` (csrc/yolo_model.hip, csrc/yolo_image.h,
 examples/yolo_detect.c): the launch sequence of ``YoloDetector.detect`` / ``detect_pose`` on either precision plan, with the twins of
 lmx/letterbox.py and ``kernels.split_k_for`` (``lmx_h_letterbox_geometry``, ``lmx_h_letterbox_tables``, ``lmx_h_conv_split_k``)
-bound for the tests (tests/test_native_yolo_host.py, tests/test_gpu_native_yolo.py)."""
+bound for the tests (tests/test_native_yolo_host.py, tests/test_gpu_native_yolo.py).  What the two handles share on the C side
+(csrc/model_handle.h) they share here: ``_NativeHandle``."""
 import ctypes as C
 import struct
 
@@ -34,6 +36,11 @@ PLANS = {"f16": 0, "exact": 1}  # LMX_YOLO_F16, LMX_YOLO_EXACT; an image's plan 
 LAYER_TENSORS = ("g1", "b1", "wqkv", "bqkv", "wo", "bo", "ls1", "g2", "b2", "w1", "bb1", "w2", "bb2", "ls2")
 
 
+def host(t):
+    """A tensor of any device as the contiguous numpy array an image stores."""
+    return np.ascontiguousarray(t.detach().cpu().numpy())
+
+
 def dino_config_block(embedder):
     """The fixed config block of a DINO image: 20 int32 then 8 float64 (LmxDinoCfg, csrc/dino_image.h)."""
     cfg, rc = embedder.cfg, embedder.recipe
@@ -46,9 +53,6 @@ def dino_config_block(embedder):
 
 def dino_tensors(embedder):
     """Ordered {name: numpy array}: exactly the tensors the embedder holds, in its dtypes."""
-    def host(t):
-        return np.ascontiguousarray(t.detach().cpu().numpy())
-
     e = embedder
     out = {"pe_w": host(e.pe_w), "pe_b": host(e.pe_b), "prefix": host(e.prefix)}
     if e.pos is not None:
@@ -134,9 +138,6 @@ def yolo_config_block(detector, plans):
 def yolo_tensors(detector, plans):
     """Ordered {name: numpy array}: the stem, then per convolution of detector.w the f16 plan's (w, b) and / or the exact plan's
     (x3 weight, ldexp'd bias, row scale) — exactly the tensors the detector's plans hold, in their dtypes."""
-    def host(t):
-        return np.ascontiguousarray(t.detach().cpu().numpy())
-
     out = {"stem.w": host(detector.w["model.0"][0]), "stem.b": host(detector.w["model.0"][1])}
     groups = yolo_conv_groups(detector)
     exact = detector._plan("exact") if "exact" in plans else None
@@ -225,63 +226,54 @@ def segment_cols(bounds, tile=256):
     return r
 
 
-# ---- the model handle ------------------------------------------------------------------------------------------------------
-class NativeDino:
-    """lmx_dino_open_host(path, max_batch) on `device` (default: torch's current device)."""
+# ---- the model handles ----------------------------------------------------------------------------------------------------
+class _NativeHandle:
+    """What NativeDino and NativeYolo do alike: lmx_<model>_open_host(path, max_batch) on `device` (default: torch's current
+    device), lmx_<model>_info, lmx_<model>_close, and the checks of a batch of frames.  A subclass names its entry points' prefix
+    and its info struct."""
+    _PREFIX = None  # "lmx_dino_"
+    _INFO = None    # DinoInfo
 
     def __init__(self, path, max_batch, device=None):
         self._lib = _lib.load()
         self._h = None
         self.device = torch.device("cuda") if device is None else torch.device(device)
         if self.device.type != "cuda":
-            raise LmxError(f"NativeDino: {self.device} is not a GPU")
+            raise LmxError(f"{type(self).__name__}: {self.device} is not a GPU")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         h = C.c_void_p(0)
         with torch.cuda.device(self.device):
-            check(self._lib.lmx_dino_open_host(str(path).encode(), int(max_batch), C.byref(h)), "lmx_dino_open_host")
+            check(self._fn("open_host")(str(path).encode(), int(max_batch), C.byref(h)), self._PREFIX + "open_host")
         self._h = h
-        self.info = DinoInfo()
-        check(self._lib.lmx_dino_info(self._h, C.byref(self.info)), "lmx_dino_info")
+        self.info = self._INFO()
+        check(self._fn("info")(self._h, C.byref(self.info)), self._PREFIX + "info")
+
+    def _fn(self, name):
+        return getattr(self._lib, self._PREFIX + name)
 
     def _handle(self):
         if self._h is None:
-            raise LmxError("NativeDino: the handle is closed")
+            raise LmxError(f"{type(self).__name__}: the handle is closed")
         return self._h
 
-    def prepare(self, h, w):
-        """lmx_dino_prepare: tables and workspace of one frame size (synchronous); embed() of that size then only enqueues."""
-        with torch.cuda.device(self.device):
-            check(self._lib.lmx_dino_prepare(self._handle(), int(h), int(w)), "lmx_dino_prepare")
-
-    def embed(self, frames, rgb=False):
-        """u8 [n,h,w,3] device tensor (BGR; rgb=True: RGB) -> f32 [n, hidden] on torch's current stream of that device."""
+    def _device_frames(self, frames, what):
+        """(n, h, w) of a contiguous u8 [n,h,w,3] tensor on the handle's device"""
         if not (frames.is_cuda and frames.device == self.device and frames.dtype == torch.uint8 and frames.dim() == 4
                 and frames.shape[3] == 3 and frames.is_contiguous()):
-            raise LmxError(f"NativeDino.embed: frames must be a contiguous uint8 [n,h,w,3] tensor on {self.device}")
-        n, h, w, _ = frames.shape
-        emb = torch.empty((n, self.info.hidden), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            check(self._lib.lmx_dino_embed(self._handle(), C.c_void_p(frames.data_ptr()), n, h, w, 1 if rgb else 0,
-                                           C.c_void_p(emb.data_ptr()), st), "lmx_dino_embed")
-        return emb
+            raise LmxError(f"{type(self).__name__}.{what}: frames must be a contiguous uint8 [n,h,w,3] tensor on {self.device}")
+        return frames.shape[:3]
 
-    def embed_host(self, frames, rgb=False):
-        """u8 [n,h,w,3] numpy array -> f32 [n, hidden] numpy array (lmx_dino_embed_host: uploads, embeds, downloads, synchronises)."""
+    def _host_frames(self, frames, what):
+        """(the frames as a contiguous u8 [n,h,w,3] numpy array, n, h, w)"""
         a = np.ascontiguousarray(frames)
         if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
-            raise LmxError("NativeDino.embed_host: frames must be a uint8 [n,h,w,3] array")
-        n, h, w, _ = a.shape
-        emb = np.empty((n, self.info.hidden), np.float32)
-        with torch.cuda.device(self.device):
-            check(self._lib.lmx_dino_embed_host(self._handle(), a.ctypes.data, n, h, w, 1 if rgb else 0, emb.ctypes.data),
-                  "lmx_dino_embed_host")
-        return emb
+            raise LmxError(f"{type(self).__name__}.{what}: frames must be a uint8 [n,h,w,3] array")
+        return (a,) + a.shape[:3]
 
     def close(self):
         if self._h is not None:
-            self._lib.lmx_dino_close(self._h)
+            self._fn("close")(self._h)
             self._h = None
 
     def __enter__(self):
@@ -297,28 +289,37 @@ class NativeDino:
             pass
 
 
-class NativeYolo:
-    """lmx_yolo_open_host(path, max_batch) on `device` (default: torch's current device).  `precision`: "f16" or "exact"."""
+class NativeDino(_NativeHandle):
+    """lmx_dino_open_host(path, max_batch) on `device` (default: torch's current device)."""
+    _PREFIX, _INFO = "lmx_dino_", DinoInfo
 
-    def __init__(self, path, max_batch, device=None):
-        self._lib = _lib.load()
-        self._h = None
-        self.device = torch.device("cuda") if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise LmxError(f"NativeYolo: {self.device} is not a GPU")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        h = C.c_void_p(0)
+    def prepare(self, h, w):
+        """lmx_dino_prepare: tables and workspace of one frame size (synchronous); embed() of that size then only enqueues."""
         with torch.cuda.device(self.device):
-            check(self._lib.lmx_yolo_open_host(str(path).encode(), int(max_batch), C.byref(h)), "lmx_yolo_open_host")
-        self._h = h
-        self.info = YoloInfo()
-        check(self._lib.lmx_yolo_info(self._h, C.byref(self.info)), "lmx_yolo_info")
+            check(self._lib.lmx_dino_prepare(self._handle(), int(h), int(w)), "lmx_dino_prepare")
 
-    def _handle(self):
-        if self._h is None:
-            raise LmxError("NativeYolo: the handle is closed")
-        return self._h
+    def embed(self, frames, rgb=False):
+        """u8 [n,h,w,3] device tensor (BGR; rgb=True: RGB) -> f32 [n, hidden] on torch's current stream of that device."""
+        n, h, w = self._device_frames(frames, "embed")
+        emb = torch.empty((n, self.info.hidden), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_dino_embed(self._handle(), C.c_void_p(frames.data_ptr()), n, h, w, 1 if rgb else 0,
+                                           C.c_void_p(emb.data_ptr()), st), "lmx_dino_embed")
+        return emb
+
+    def embed_host(self, frames, rgb=False):
+        """u8 [n,h,w,3] numpy array -> f32 [n, hidden] numpy array (lmx_dino_embed_host: uploads, embeds, downloads, synchronises)."""
+        a, n, h, w = self._host_frames(frames, "embed_host")
+        emb = np.empty((n, self.info.hidden), np.float32)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_dino_embed_host(self._handle(), a.ctypes.data, n, h, w, 1 if rgb else 0, emb.ctypes.data),
+                  "lmx_dino_embed_host")
+        return emb
+
+class NativeYolo(_NativeHandle):
+    """lmx_yolo_open_host(path, max_batch) on `device` (default: torch's current device).  `precision`: "f16" or "exact"."""
+    _PREFIX, _INFO = "lmx_yolo_", YoloInfo
 
     @property
     def pose(self):
@@ -341,15 +342,9 @@ class NativeYolo:
         check(self._lib.lmx_yolo_anchors(self._handle(), int(h), int(w), C.byref(oh), C.byref(ow), C.byref(A)), "lmx_yolo_anchors")
         return oh.value, ow.value, A.value
 
-    def _frames(self, frames, what):
-        if not (frames.is_cuda and frames.device == self.device and frames.dtype == torch.uint8 and frames.dim() == 4
-                and frames.shape[3] == 3 and frames.is_contiguous()):
-            raise LmxError(f"NativeYolo.{what}: frames must be a contiguous uint8 [n,h,w,3] tensor on {self.device}")
-        return frames.shape[:3]
-
     def predict(self, frames, precision):
         """u8 BGR [n,h,w,3] device tensor -> pred f32 [n, A, 4+nc] on torch's current stream of that device (lmx_yolo_predict)."""
-        n, h, w = self._frames(frames, "predict")
+        n, h, w = self._device_frames(frames, "predict")
         A = self.anchors(h, w)[2]
         pred = torch.empty((n, A, 4 + self.info.nc), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
@@ -361,7 +356,7 @@ class NativeYolo:
     def detect(self, frames, precision, conf=0.25, iou=0.7, max_det=300):
         """u8 BGR [n,h,w,3] device tensor -> (boxes [n,max_det,4], scores, cls, src, counts), plus kpts [n,max_det,K,ndim] for a pose
         image, on torch's current stream of that device (lmx_yolo_detect; the outputs are initialised by the call)."""
-        n, h, w = self._frames(frames, "detect")
+        n, h, w = self._device_frames(frames, "detect")
         md = max(int(max_det), 0)
         dev = self.device
         boxes = torch.empty((n, md, 4), dtype=torch.float32, device=dev)
@@ -379,10 +374,7 @@ class NativeYolo:
     def detect_host(self, frames, precision, conf=0.25, iou=0.7, max_det=300):
         """u8 BGR [n,h,w,3] numpy array -> the same outputs as numpy arrays (lmx_yolo_detect_host: uploads, detects, downloads,
         synchronises)."""
-        a = np.ascontiguousarray(frames)
-        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
-            raise LmxError("NativeYolo.detect_host: frames must be a uint8 [n,h,w,3] array")
-        n, h, w, _ = a.shape
+        a, n, h, w = self._host_frames(frames, "detect_host")
         md = max(int(max_det), 0)
         boxes, scores = np.empty((n, md, 4), np.float32), np.empty((n, md), np.float32)
         cls, src, counts = np.empty((n, md), np.int32), np.empty((n, md), np.int32), np.empty((n,), np.int32)
@@ -392,20 +384,3 @@ class NativeYolo:
                                                  *(t.ctypes.data for t in (boxes, scores, cls, src, counts)),
                                                  kpts.ctypes.data if kpts is not None else None), "lmx_yolo_detect_host")
         return (boxes, scores, cls, src, counts) + ((kpts,) if kpts is not None else ())
-
-    def close(self):
-        if self._h is not None:
-            self._lib.lmx_yolo_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
