@@ -654,6 +654,74 @@ int lmx_yolo_detect_host(lmx_yolo* m, const uint8_t* frames_host, int n, int h, 
                          float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* src_host, int32_t* counts_host,
                          float* kpts_host);
 
+/* ==== MODEL level: SAM masks from raw frames and boxes (csrc/sam_model.hip, csrc/model_handle.h, csrc/host_sam_image.cpp) ===========
+ * The whole of services/sam3-pipeline/app/main.py:74-92 — `predictor.set_image(frame)`, `predictor.predict(box=..., multimask_output=
+ * False)` — behind one call: ResizeLongestSide, the SAM v1 ViT image encoder, the prompt encoder for one box per frame, the mask
+ * decoder, Sam.postprocess_masks and the threshold, and what the service then takes from the mask (packed bits, statistics, contour
+ * features).  It is the launch sequence of lmx/sam.py's SamVitEncoder.encode and lmx/sam_decoder.py's MaskDecoder.predict written in
+ * C++ over the lmx_k_* entry points above, with the descriptors lmx/kernels.py fills.  Same launches, same bits as the Python classes
+ * on both precision plans (tests/test_gpu_native_sam.py).
+ * The model comes from a weight image of kind SAM that lmx.native.write_sam_image(encoder, decoder, path, plans) writes (layout in
+ * csrc/image.h and csrc/sam_image.h): every tensor in final device form, per plan the image holds.
+ * OUT OF SCOPE, each refused or absent rather than approximated: the Hiera-B+ encoder (the image's config block carries an `encoder`
+ * field so that it can be added without a format break; any kind but LMX_SAM_ENC_VIT is LMX_EINVAL), point prompts, mask-input
+ * prompts and multimask output (lmx/sam_decoder.py MaskDecoder.decode serves them from Python), SamAutomaticMaskGenerator
+ * (lmx/amg.py), and HIP graph capture of these calls.
+ * Handle, image and error conventions as for lmx_yolo: the handle belongs to the device current at open; ONE host thread and ONE
+ * stream in flight per handle; several handles are independent; LMX_EINVAL / LMX_EHIP with lmx_last_error(). */
+typedef struct lmx_sam lmx_sam;
+enum { LMX_SAM_F16 = 0, LMX_SAM_EXACT = 1 }; /* `precision`; lmx_sam_info_t.plans has bit (1 << precision) for each plan the image holds */
+enum { LMX_SAM_ENC_VIT = 0 };                /* lmx_sam_info_t.encoder */
+typedef struct { int32_t encoder, hidden, heads, layers, mlp, window, patch, image, plans, max_batch; } lmx_sam_info_t;
+/* HOST only, touches no GPU (`sam_model_registry[...](checkpoint=...)` behind services/sam3-pipeline/app/main.py:74-92, the checking
+ * half): parse and validate an image — magic, version, kind, sizes against the real file, the config block, every tensor the
+ * configuration and the plan mask call for with its dtype and shape, a head dim the attention kernels serve, and for an image that
+ * holds the exact plan the shapes at which every encoder Linear is ONE launch (hidden, mlp and 3 * patch^2 multiples of 64, every N at
+ * least 96).  LMX_EINVAL names the offending field or tensor.  info_host (may be NULL) receives the configuration, max_batch 0. */
+int lmx_sam_image_check_host(const char* path_host, lmx_sam_info_t* info_host);
+/* SYNCHRONOUS (`SamPredictor(sam.to(device))` behind services/sam3-pipeline/app/main.py:74-92): validate as above, then upload the
+ * weights to the CURRENT device.  Workspaces come with lmx_sam_prepare.  *out_host is NULL after any failure, with nothing left
+ * allocated. */
+int lmx_sam_open_host(const char* path_host, int max_batch, lmx_sam** out_host);
+/* the end of the model of services/sam3-pipeline/app/main.py:74-92: waits for the device, then frees everything the handle owns; NULL
+ * is allowed */
+void lmx_sam_close(lmx_sam* m);
+/* the configuration of the model behind services/sam3-pipeline/app/main.py:74-92 and the handle's max_batch */
+int lmx_sam_info(const lmx_sam* m, lmx_sam_info_t* info_host);
+/* host arithmetic of `set_image` (services/sam3-pipeline/app/main.py:74-92): ResizeLongestSide.get_preprocess_shape of an h x w frame,
+ * int(x * image / max(h, w) + 0.5) per side */
+int lmx_sam_resized(const lmx_sam* m, int h, int w, int* nh_host, int* nw_host);
+/* SYNCHRONOUS (what `set_image` and `predict` of services/sam3-pipeline/app/main.py:74-92 derive from the frame size): the resize
+ * tables of an h x w frame and ONE workspace of max_batch frames under `precision` — the resized frame, the patch matrix, every
+ * activation of the encoder and of the decoder, the relative-position tables, the token buffer with its constant output-token rows,
+ * lmx_k_mask_post's intermediate, the outputs a caller may leave NULL and the contour workspace.  A pair already prepared is a lookup.
+ * LMX_EINVAL for a plan the image does not hold, for a buffer of 2 GB or more (named), and beyond 16 (size, plan) pairs per handle. */
+int lmx_sam_prepare(lmx_sam* m, int h, int w, int precision);
+/* `predictor.set_image(frame)` of services/sam3-pipeline/app/main.py:74-92 for n frames: frames u8 [n][h][w][3], consumed in the
+ * channel order given (the service hands over its BGR frame; no swap) -> emb [n][G][G][out_ch], G = image / patch: f16 under
+ * LMX_SAM_F16, f32 under LMX_SAM_EXACT = SamVitEncoder.encode(frames, precision)["fpn"][2].  Enqueue-only after lmx_sam_prepare, as
+ * lmx_sam_segment. */
+int lmx_sam_encode(lmx_sam* m, const uint8_t* frames, int n, int h, int w, int precision, void* emb, lmx_stream_t stream);
+/* `predictor.predict(box=..., multimask_output=False)` of services/sam3-pipeline/app/main.py:74-92 on n embeddings of lmx_sam_encode
+ * under the same precision: boxes f32 [n][4] xyxy in FRAME pixels (one per frame; an all-zero box stands for "no detection") ->
+ * mask u8 [n][h][w] (0 / 1), stats int64 [n][8] (lmx_k_mask_post's), iou f32 [n], lowres f32 [n][4G][4G] =
+ * MaskDecoder.predict(emb, boxes, (h, w), resized, precision); and, where asked for, mask_bits u8 [n][h][ceil(w/8)]
+ * (lmx_k_pack_bits) and contour int64 [n][8] (lmx_k_contour_features: frames of 2 x 2 up to 2^21 - 1 pixels).  mask, mask_bits,
+ * contour and lowres may each be NULL (what the decoder needs of them lives in the workspace); stats and iou may not. */
+int lmx_sam_decode(lmx_sam* m, const void* emb, int n, int h, int w, const float* boxes, int precision, uint8_t* mask, uint8_t* mask_bits,
+                   int64_t* stats, int64_t* contour, float* iou, float* lowres, lmx_stream_t stream);
+/* services/sam3-pipeline/app/main.py:74-92 for n frames: lmx_sam_encode into the handle's workspace, then lmx_sam_decode.  For a
+ * (size, precision) already prepared the call ONLY ENQUEUES on `stream`: no allocation, no synchronisation; the first call for a new
+ * pair runs lmx_sam_prepare itself, and THAT call synchronises.  n > max_batch runs in chunks of max_batch, each writing its slice of
+ * the outputs. */
+int lmx_sam_segment(lmx_sam* m, const uint8_t* frames, int n, int h, int w, const float* boxes, int precision, uint8_t* mask,
+                    uint8_t* mask_bits, int64_t* stats, int64_t* contour, float* iou, float* lowres, lmx_stream_t stream);
+/* services/sam3-pipeline/app/main.py:74-92 for a caller with no HIP code of its own: every pointer is HOST memory; uploads, segments,
+ * downloads and synchronises (examples/sam_segment.c). */
+int lmx_sam_segment_host(lmx_sam* m, const uint8_t* frames_host, int n, int h, int w, const float* boxes_host, int precision,
+                         uint8_t* mask_host, uint8_t* mask_bits_host, int64_t* stats_host, int64_t* contour_host, float* iou_host,
+                         float* lowres_host);
+
 #ifdef __cplusplus
 }
 #endif

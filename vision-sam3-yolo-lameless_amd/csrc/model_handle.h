@@ -1,4 +1,4 @@
-// model_handle.h — what every model-level handle of the C-ABI (dino_model.hip, yolo_model.hip) owns and does the same way: the device
+// model_handle.h — what every model-level handle of the C-ABI (dino_model.hip, yolo_model.hip, sam_model.hip) owns and does the same way: the device
 // it was opened on, the weights of its image in one allocation, a stream of its own for the *_host entry points, one staging blob,
 // and the open / close / device-check protocol around them.  HOST code, header-only: a plain struct and free functions; the model's
 // handle derives from the struct and keeps its plan, its workspace and its prepared entries to itself.
@@ -155,9 +155,11 @@ void lmx_handle_close(H* m, void (*destroy)(H*)) {
   if (sw) (void)hipSetDevice(cur);
 }
 
-// a dense GEMM C = act(A W^T + bias) (* scale) (+ res) as lmx/kernels.py's gemm fills its descriptor
-inline int lmx_gemm_dense(const void* A, int64_t lda, const void* W, const float* bias, void* C, int64_t ldc, int out_dtype, int M, int N, int K, int act,
-                          const float* scale, const void* res, int64_t ldr, hipStream_t st) {
+// a dense GEMM C = act(A W^T + bias) (* scale) (+ res) as lmx/kernels.py's gemm fills its descriptor.  a_rep = 2: W is [N, 2 K'] =
+// [whi | wlo] and A's K' = K / 2 columns are walked twice (K counts W's columns); res_rows > 0: res is a [res_rows, N] table
+// broadcast over the rows
+inline int lmx_gemm_dense_rep(const void* A, int64_t lda, const void* W, const float* bias, void* C, int64_t ldc, int out_dtype, int M, int N, int K,
+                              int act, const float* scale, const void* res, int64_t ldr, int res_rows, int a_rep, hipStream_t st) {
   lmx_gemm_desc d;
   memset(&d, 0, sizeof(d));
   d.A = A;
@@ -175,6 +177,12 @@ inline int lmx_gemm_dense(const void* A, int64_t lda, const void* W, const float
   d.act = act;
   d.out_dtype = out_dtype;
   d.a_mode = 0;
-  d.a_rep = 1;
+  d.res_rows = res_rows;
+  d.a_rep = a_rep;
   return lmx_k_gemm(&d, st);
+}
+
+inline int lmx_gemm_dense(const void* A, int64_t lda, const void* W, const float* bias, void* C, int64_t ldc, int out_dtype, int M, int N, int K, int act,
+                          const float* scale, const void* res, int64_t ldr, hipStream_t st) {
+  return lmx_gemm_dense_rep(A, lda, W, bias, C, ldc, out_dtype, M, N, K, act, scale, res, ldr, 0, 1, st);
 }

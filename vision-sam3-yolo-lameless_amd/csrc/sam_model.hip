@@ -1,0 +1,788 @@
+// sam_model.hip — the model-level entry points of the C-ABI for SAM v1: a handle (model_handle.h has what every handle owns) with the
+// weights of one weight image (sam_image.h) and, per prepared (frame size, plan), the workspace of one batch.  lmx_sam_encode is the
+// launch sequence of lmx/sam.py's SamVitEncoder.encode, lmx_sam_decode that of lmx/sam_decoder.py's MaskDecoder.predict followed by the
+// lmx_k_pack_bits / lmx_k_contour_features of lmx/pipeline.py (services/sam3-pipeline/app/main.py:74-92), written as host C++.
+// HOST code only: there is no kernel in this file and no arithmetic of its own beyond the resize tables (lmx_h_pil_tables).  Every
+// launch goes through the same extern "C" lmx_k_* entry point the ctypes binding calls, with the descriptor filled as lmx/kernels.py
+// fills it, in the Python plan's order, so the outputs are the Python plan's bit for bit on both precision plans
+// (tests/test_gpu_native_sam.py).  What is torch glue in Python — torch.cat of the output tokens with the sparse prompt, the q / k / v
+// slices of qkv, q3[:, k].contiguous(), iou[:, 0] — is a leading dimension or a strided copy on the call's stream here.
+// OUT OF SCOPE: the Hiera-B+ encoder (the image's `encoder` field leaves room for it), point and mask-input prompts, multimask
+// output, SamAutomaticMaskGenerator, HIP graph capture.
+#include <math.h>
+#include <string.h>
+
+#include <map>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "model_handle.h"
+#include "sam_image.h"
+
+namespace {
+
+// The GEMM kernels walk an operand with 32-bit byte offsets, and for the dense and convolution launches of this plan nothing in the
+// launcher checks it: the guard in prepare is the only one.
+const int64_t MAX_BUFFER_BYTES = 0x7fffffffll;
+const int DD = LMX_SAM_DEC_D, DH = LMX_SAM_DEC_HEADS, DT = LMX_SAM_OUT_TOKENS + 2;  // the decoder's width, heads and tokens (5 + 2 box corners)
+
+// a Linear's operands under one plan.  K: the columns of the ACTIVATION (f16 plan: w [N][K]; encoder exact: [N][2K]; decoder exact: [N][3K])
+struct Lin {
+  const void* w = nullptr;
+  const float *b = nullptr, *s = nullptr;
+  int N = 0, K = 0;
+};
+
+struct Norm {
+  const float *g = nullptr, *b = nullptr;
+};
+
+struct EncLayer {
+  bool glob = false;
+  const float *g1, *b1, *rh, *rw, *g2, *b2;
+  const half_t* padkv;
+  Lin qkv[2], proj[2], fc1[2], fc2[2];  // per plan
+};
+
+// the decoder's Linears by role, per plan
+struct DecAttn {
+  Lin q, k, v, o;
+};
+struct DecLayer {
+  DecAttn sa, t2i, i2t;
+  Lin lin1, lin2;
+  Norm ln[4];
+};
+struct DecPlan {
+  DecLayer L[2];
+  DecAttn fin;
+  Lin up1, up2, hyp[3], iou[3];
+};
+
+// what lmx_sam_prepare builds for one (frame size, plan): the resize tables and the workspace of max_batch frames, one allocation
+struct Prepared {
+  int nh = 0, nw = 0;
+  char* blob = nullptr;
+  int32_t *bounds_h = nullptr, *kk_h = nullptr, *bounds_v = nullptr, *kk_v = nullptr;  // null: that pass is skipped (size kept)
+  int ksize_h = 0, ksize_v = 0;
+  uint8_t *tmp_h = nullptr, *tmp_v = nullptr;
+  // encoder
+  void *patches, *h, *qkv, *a, *u, *rel, *y16, *acc, *emb;
+  float *x, *y32;
+  // decoder
+  float *tokens, *sparse, *qa, *qb, *keys_a, *keys_b, *u1, *hyper, *iou4, *logits, *post;
+  void *qq, *kk, *qc16, *kc16, *tok16, *pq, *pk, *pv, *pa, *hh, *u1n, *u2, *t1, *t2, *x3;
+  uint8_t* mask;
+  void* contour_ws;  // null: the frame size is outside lmx_k_contour_features' range
+};
+
+}  // namespace
+
+struct lmx_sam : LmxHandleCore {
+  LmxSamCfg cfg;
+  Lin pe[2], n1[2];
+  const void *n2_w = nullptr, *n2_hi = nullptr, *n2_lo = nullptr;
+  const float *pos = nullptr, *lut = nullptr;
+  Norm n1_ln, n2_ln;
+  std::vector<EncLayer> layers;
+  const float *gauss = nullptr, *corner = nullptr, *key_pe = nullptr, *no_mask = nullptr, *out_tokens = nullptr;
+  DecPlan dec[2];
+  Norm ln_final, up_ln;
+  std::map<std::tuple<int, int, int>, Prepared> prepared;
+};
+
+namespace {
+
+void destroy(lmx_sam* m) {
+  for (auto& kv : m->prepared) (void)hipFree(kv.second.blob);
+  lmx_handle_free(m);
+  delete m;
+}
+
+int open_into(lmx_sam* m, const char* path) {
+  LmxSamImage img;
+  LMX_TRY(lmx_sam_image_parse(path, &img));
+  m->cfg = img.cfg;
+  const LmxSamCfg& c = m->cfg;
+  LMX_TRY(lmx_handle_upload_weights(m, "lmx_sam_open_host", path, img.data_offset, img.file_bytes));
+  const uint64_t base = img.data_offset;
+  auto at = [&](const LmxTensorRef& r) -> const void* { return r.nbytes ? m->weights + (r.offset - base) : nullptr; };
+  auto f32 = [&](const LmxTensorRef& r) { return static_cast<const float*>(at(r)); };
+  auto norm = [&](const LmxSamNorm& n) { return Norm{f32(n.g), f32(n.b)}; };
+  const int D = c.hidden, I = c.mlp, Kp = c.patch * c.patch * 3, C = c.out_ch;
+  m->pe[LMX_SAM_F16] = Lin{at(img.pe_w), f32(img.pe_b), nullptr, D, Kp};
+  m->pe[LMX_SAM_EXACT] = Lin{at(img.x_pe), f32(img.pe_b), nullptr, D, Kp};
+  m->n1[LMX_SAM_F16] = Lin{at(img.n1_w), nullptr, nullptr, C, D};
+  m->n1[LMX_SAM_EXACT] = Lin{at(img.x_n1), nullptr, nullptr, C, D};
+  m->n2_w = at(img.n2_w);
+  m->n2_hi = at(img.x_n2_hi);
+  m->n2_lo = at(img.x_n2_lo);
+  m->pos = f32(img.pos);
+  m->lut = f32(img.lut);
+  m->n1_ln = Norm{f32(img.n1_g), f32(img.n1_b)};
+  m->n2_ln = Norm{f32(img.n2_g), f32(img.n2_b)};
+  for (int i = 0; i < c.layers; ++i) {
+    const LmxSamLayerRefs& r = img.layers[(size_t)i];
+    EncLayer L;
+    L.glob = c.is_global(i);
+    L.g1 = f32(r.g1);
+    L.b1 = f32(r.b1);
+    L.rh = f32(r.rh);
+    L.rw = f32(r.rw);
+    L.g2 = f32(r.g2);
+    L.b2 = f32(r.b2);
+    L.padkv = static_cast<const half_t*>(at(r.padkv));
+    L.qkv[LMX_SAM_F16] = Lin{at(r.wqkv), f32(r.bqkv), nullptr, 3 * D, D};
+    L.qkv[LMX_SAM_EXACT] = Lin{at(r.xqkv), f32(r.bqkv), nullptr, 3 * D, D};
+    L.proj[LMX_SAM_F16] = Lin{at(r.wo), f32(r.bo), nullptr, D, D};
+    L.proj[LMX_SAM_EXACT] = Lin{at(r.xproj), f32(r.bo), nullptr, D, D};
+    L.fc1[LMX_SAM_F16] = Lin{at(r.w1), f32(r.bb1), nullptr, I, D};
+    L.fc1[LMX_SAM_EXACT] = Lin{at(r.xfc1), f32(r.bb1), nullptr, I, D};
+    L.fc2[LMX_SAM_F16] = Lin{at(r.w2), f32(r.bb2), nullptr, D, I};
+    L.fc2[LMX_SAM_EXACT] = Lin{at(r.xfc2), f32(r.bb2), nullptr, D, I};
+    m->layers.push_back(L);
+  }
+  m->gauss = f32(img.gauss);
+  m->corner = f32(img.corner);
+  m->key_pe = f32(img.key_pe);
+  m->no_mask = f32(img.no_mask);
+  m->out_tokens = f32(img.out_tokens);
+  m->ln_final = norm(img.ln_final);
+  m->up_ln = norm(img.up_ln);
+  // the decoder's Linears: lmx_sam_linears()'s order, walked once per plan
+  for (int plan = 0; plan < 2; ++plan) {
+    size_t at_lin = 0;
+    auto next = [&]() {
+      const LmxSamLinear& l = img.linears[at_lin++];
+      return plan == LMX_SAM_F16 ? Lin{at(l.w), f32(l.b), nullptr, l.N, l.K} : Lin{at(l.xw), f32(l.xb), f32(l.xs), l.N, l.K};
+    };
+    auto attn = [&](DecAttn* a) {
+      a->q = next();
+      a->k = next();
+      a->v = next();
+      a->o = next();
+    };
+    DecPlan& P = m->dec[plan];
+    for (int i = 0; i < 2; ++i) {
+      attn(&P.L[i].sa);
+      attn(&P.L[i].t2i);
+      P.L[i].lin1 = next();
+      P.L[i].lin2 = next();
+      attn(&P.L[i].i2t);
+      for (int j = 0; j < 4; ++j) P.L[i].ln[j] = norm(img.dec_ln[i][j]);
+    }
+    attn(&P.fin);
+    P.up1 = next();
+    P.up2 = next();
+    for (int j = 0; j < 3; ++j) P.hyp[j] = next();
+    for (int j = 0; j < 3; ++j) P.iou[j] = next();
+    LMX_REQUIRE(at_lin == img.linears.size(), "lmx_sam_open_host: the decoder's plan reads %d Linears, the image lists %d", (int)at_lin,
+                (int)img.linears.size());
+  }
+  return LMX_OK;
+}
+
+int check_precision(const lmx_sam* m, const char* fn, int precision) {
+  LMX_REQUIRE(precision == LMX_SAM_F16 || precision == LMX_SAM_EXACT, "%s: precision %d is neither LMX_SAM_F16 (0) nor LMX_SAM_EXACT (1)", fn, precision);
+  LMX_REQUIRE(m->cfg.plans & (1 << precision), "%s: the image does not hold the %s plan (plans mask %d)", fn, precision == LMX_SAM_F16 ? "f16" : "exact",
+              m->cfg.plans);
+  return LMX_OK;
+}
+
+// one axis of ResizeLongestSide's PIL bilinear resize (lmx/sam.py _tables: resample.coeff_tables); nothing where the size is kept
+int pil_axis(int in_size, int out_size, std::vector<int32_t>* bounds, std::vector<int32_t>* kk, int* ksize) {
+  if (in_size == out_size) return LMX_OK;
+  LMX_TRY(lmx_h_pil_tables(in_size, out_size, LMX_FILT_BILINEAR, nullptr, nullptr, 0, ksize));
+  bounds->resize((size_t)out_size * 2);
+  kk->resize((size_t)out_size * *ksize);
+  return lmx_h_pil_tables(in_size, out_size, LMX_FILT_BILINEAR, bounds->data(), kk->data(), (int64_t)kk->size(), ksize);
+}
+
+// offsets inside the workspace, each buffer refused by name from 2 GB on
+struct Sizer {
+  LmxLayout lay;
+  int max_batch;
+  int add(const char* what, int64_t bytes, size_t* at) {
+    LMX_REQUIRE(bytes >= 0 && bytes < MAX_BUFFER_BYTES, "lmx_sam_prepare: buffer '%s' has %lld bytes for max_batch %d, the kernels index below 2 GB", what,
+                (long long)bytes, max_batch);
+    *at = lay.add((size_t)bytes);
+    return LMX_OK;
+  }
+};
+
+int prepare(lmx_sam* m, int h, int w, int precision, const Prepared** out) {
+  const auto key = std::make_tuple(h, w, precision);
+  const auto it = m->prepared.find(key);
+  if (it != m->prepared.end()) {
+    if (out) *out = &it->second;
+    return LMX_OK;
+  }
+  LMX_TRY(check_precision(m, "lmx_sam_prepare", precision));
+  const LmxSamCfg& c = m->cfg;
+  Prepared P;
+  memset(&P, 0, sizeof(P));
+  lmx_sam_resized_hw(c.image, h, w, &P.nh, &P.nw);
+  LMX_REQUIRE(P.nh >= 1 && P.nw >= 1 && P.nh <= c.image && P.nw <= c.image, "lmx_sam_prepare: a %d x %d frame resizes to %d x %d", h, w, P.nh, P.nw);
+  LMX_REQUIRE((int)m->prepared.size() < LMX_MAX_PREPARED, "lmx_sam_prepare: the handle already holds %d (frame size, plan) pairs; open another for more",
+              LMX_MAX_PREPARED);
+  const int nh = P.nh, nw = P.nw;
+  std::vector<int32_t> bh, kh, bv, kv;
+  LMX_TRY(pil_axis(w, nw, &bh, &kh, &P.ksize_h));
+  LMX_TRY(pil_axis(h, nh, &bv, &kv, &P.ksize_v));
+
+  const bool exact = precision == LMX_SAM_EXACT;
+  const int64_t B = m->max_batch, D = c.hidden, I = c.mlp, H = c.heads, g = c.grid(), gg = g * g, Kp = c.patch * c.patch * 3, C = c.out_ch, ws = c.window;
+  const int64_t nW = ((g + ws - 1) / ws) * ((g + ws - 1) / ws), e = exact ? 4 : 2, L = 4 * g;
+  int64_t rel = 0;
+  for (const EncLayer& l : m->layers) {
+    const int64_t r = l.glob ? B * H * gg * 2 * g * 2 : B * nW * H * ws * ws * 2 * ws * 2;
+    if (r > rel) rel = r;
+  }
+  int64_t x3 = 0;
+  if (exact) {  // the widest x3 operand of MaskDecoder._lin: rows x 3 K halves
+    const int64_t cand[3] = {B * gg * 3 * DD, B * gg * 4 * 3 * 64, B * DT * 3 * LMX_SAM_DEC_MLP};
+    for (int64_t v : cand) x3 = v * 2 > x3 ? v * 2 : x3;
+  }
+  int64_t contour = 0;
+  if (h > 1 && w > 1 && (int64_t)h * w <= 0x1fffff && B * h < 0x7fffffffll && B <= 65535) contour = lmx_contour_workspace_bytes((int)B, h, w);
+
+  Sizer z;
+  z.max_batch = m->max_batch;
+  size_t o_bh, o_kh, o_bv, o_kv;
+  LMX_TRY(z.add("resize table", (int64_t)bh.size() * 4, &o_bh));
+  LMX_TRY(z.add("resize table", (int64_t)kh.size() * 4, &o_kh));
+  LMX_TRY(z.add("resize table", (int64_t)bv.size() * 4, &o_bv));
+  LMX_TRY(z.add("resize table", (int64_t)kv.size() * 4, &o_kv));
+  const LmxUpload up[4] = {{o_bh, bh.data(), bh.size() * 4}, {o_kh, kh.data(), kh.size() * 4}, {o_bv, bv.data(), bv.size() * 4}, {o_kv, kv.data(), kv.size() * 4}};
+  struct Want {
+    void** ptr;
+    const char* what;
+    int64_t bytes;
+  };
+  auto vp = [](auto** p) { return reinterpret_cast<void**>(p); };
+  const std::vector<Want> wants = {
+      {vp(&P.tmp_h), "frame after the horizontal resize", nw != w ? B * h * nw * 3 : 0},
+      {vp(&P.tmp_v), "resized frame", nh != h ? B * nh * nw * 3 : 0},
+      {vp(&P.patches), "patches", B * gg * Kp * 2},
+      {vp(&P.x), "residual stream", B * gg * D * 4},
+      {vp(&P.h), "LayerNorm rows", B * gg * D * 2},
+      {vp(&P.qkv), "qkv", B * gg * 3 * D * 2},
+      {vp(&P.a), "attention output", B * gg * D * 2},
+      {vp(&P.u), "MLP hidden", B * gg * I * 2},
+      {vp(&P.rel), "relative-position tables", rel},
+      {vp(&P.y32), "neck 1x1 output", B * gg * C * 4},
+      {vp(&P.y16), "neck LayerNorm rows", B * gg * C * 2},
+      {vp(&P.acc), "neck 3x3 output", B * gg * C * 4},
+      {vp(&P.emb), "image embedding", B * gg * C * e},
+      {vp(&P.tokens), "tokens", B * DT * DD * 4},
+      {vp(&P.sparse), "sparse prompt", B * 2 * DD * 4},
+      {vp(&P.qa), "queries", B * DT * DD * 4},
+      {vp(&P.qb), "queries", B * DT * DD * 4},
+      {vp(&P.keys_a), "keys", B * gg * DD * 4},
+      {vp(&P.keys_b), "keys", B * gg * DD * 4},
+      {vp(&P.qq), "queries + position", B * DT * DD * e},
+      {vp(&P.kk), "keys + position", B * gg * DD * e},
+      {vp(&P.qc16), "queries f16", exact ? 0 : B * DT * DD * 2},
+      {vp(&P.kc16), "keys f16", exact ? 0 : B * gg * DD * 2},
+      {vp(&P.tok16), "token f16", exact ? 0 : B * DD * 2},
+      {vp(&P.pq), "q projection", B * gg * DD * e},
+      {vp(&P.pk), "k projection", B * gg * DD * e},
+      {vp(&P.pv), "v projection", B * gg * DD * e},
+      {vp(&P.pa), "decoder attention output", B * gg * DD * e},
+      {vp(&P.hh), "decoder MLP hidden", B * DT * LMX_SAM_DEC_MLP * e},
+      {vp(&P.u1), "upscaler 1", B * gg * DD * 4},
+      {vp(&P.u1n), "upscaler LayerNorm rows", B * gg * DD * e},
+      {vp(&P.u2), "upscaler 2", B * gg * 4 * 128 * e},
+      {vp(&P.t1), "hyper MLP", B * DD * e},
+      {vp(&P.t2), "hyper MLP", B * DD * e},
+      {vp(&P.x3), "x3 operand", x3},
+      {vp(&P.hyper), "hyper", B * 32 * 4},
+      {vp(&P.iou4), "iou head", B * 4 * 4},
+      {vp(&P.logits), "low-resolution logits", B * L * L * 4},
+      {vp(&P.post), "mask_post intermediate", B * nh * nw * 4},
+      {vp(&P.mask), "mask", B * h * w},
+      {vp(&P.contour_ws), "contour workspace", contour},
+  };
+  std::vector<size_t> offs(wants.size());
+  for (size_t i = 0; i < wants.size(); ++i) LMX_TRY(z.add(wants[i].what, wants[i].bytes, &offs[i]));
+  LMX_TRY(lmx_alloc_and_upload(z.lay.total, up, 4, &P.blob));
+  for (size_t i = 0; i < wants.size(); ++i) *wants[i].ptr = wants[i].bytes ? P.blob + offs[i] : nullptr;
+  if (nw != w) {
+    P.bounds_h = reinterpret_cast<int32_t*>(P.blob + o_bh);
+    P.kk_h = reinterpret_cast<int32_t*>(P.blob + o_kh);
+  }
+  if (nh != h) {
+    P.bounds_v = reinterpret_cast<int32_t*>(P.blob + o_bv);
+    P.kk_v = reinterpret_cast<int32_t*>(P.blob + o_kv);
+  }
+  // the constant rows of the token buffer: [iou token | 4 mask tokens] in front of every frame's two box corners
+  hipError_t err = hipSuccess;
+  for (int64_t b = 0; b < B && err == hipSuccess; ++b)
+    err = hipMemcpy(P.tokens + b * DT * DD, m->out_tokens, (size_t)LMX_SAM_OUT_TOKENS * DD * 4, hipMemcpyDeviceToDevice);
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  if (err != hipSuccess) {
+    (void)hipFree(P.blob);
+    LMX_HIP(err);
+  }
+  const auto ins = m->prepared.emplace(key, P);
+  if (out) *out = &ins.first->second;
+  return LMX_OK;
+}
+
+// SamVitEncoder.embed's `lin`: one launch either way — f16 weights, or a_rep = 2 over [whi | wlo]
+int enc_lin(int precision, const void* a, const Lin& l, void* C, int out_dtype, int M, int act, const void* res, int res_rows, hipStream_t st) {
+  const int rep = precision == LMX_SAM_EXACT ? 2 : 1;
+  return lmx_gemm_dense_rep(a, l.K, l.w, l.b, C, l.N, out_dtype, M, l.N, rep * l.K, act, nullptr, res, l.N, res_rows, rep, st);
+}
+
+// K.conv3x3 of the neck: [n, g, g, C] -> [n, g, g, C], no bias, no activation
+int neck_conv(const void* x, const void* w, void* out, int out_dtype, const void* res, int n, int g, int C, hipStream_t st) {
+  lmx_gemm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.A = x;
+  d.W = w;
+  d.C = out;
+  d.res = res;
+  d.lda = C;
+  d.ldc = C;
+  d.ldr = res ? C : 0;
+  d.M = n * g * g;
+  d.N = C;
+  d.K = 9 * C;
+  d.act = LMX_ACT_NONE;
+  d.out_dtype = out_dtype;
+  d.a_mode = 1;
+  d.H = g;
+  d.W_ = g;
+  d.Cin = C;
+  d.conv_stride = 1;
+  d.Ho = g;
+  d.Wo = g;
+  return lmx_k_gemm(&d, st);
+}
+
+// SamVitEncoder.preprocess + embed for n <= max_batch frames: emb f16 (f16 plan) / f32 (exact plan) [n, g, g, out_ch]
+int encode_chunk(const lmx_sam* m, const Prepared& P, int precision, const uint8_t* frames, int n, int h, int w, void* emb, hipStream_t st) {
+  const LmxSamCfg& c = m->cfg;
+  const int D = c.hidden, H = c.heads, hd = D / H, g = c.grid(), gg = g * g, rows = n * gg, Kp = c.patch * c.patch * 3, C = c.out_ch, ws = c.window;
+  const int nW = ((g + ws - 1) / ws) * ((g + ws - 1) / ws);
+  const float eps = (float)c.eps, scale = (float)pow((double)hd, -0.5);
+  const uint8_t* img = frames;
+  if (P.kk_h) {
+    LMX_TRY(lmx_k_pil_resize_h(img, P.tmp_h, n, h, w, P.nw, P.bounds_h, P.kk_h, P.ksize_h, 0, st));
+    img = P.tmp_h;
+  }
+  if (P.kk_v) {
+    LMX_TRY(lmx_k_pil_resize_v(img, P.tmp_v, n, h, P.nh, P.nw, P.bounds_v, P.kk_v, P.ksize_v, st));
+    img = P.tmp_v;
+  }
+  LMX_TRY(lmx_k_im2col_u8(img, m->lut, P.patches, n, P.nh, P.nw, c.image, c.image, c.patch, c.patch, c.patch, 0, Kp, st));
+  LMX_TRY(enc_lin(precision, P.patches, m->pe[precision], P.x, LMX_F32, rows, LMX_ACT_NONE, m->pos, gg, st));
+  half_t* qkv = static_cast<half_t*>(P.qkv);
+  for (const EncLayer& L : m->layers) {
+    LMX_TRY(lmx_k_layernorm(P.x, LMX_F32, D, L.g1, L.b1, P.h, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
+    LMX_TRY(enc_lin(precision, P.h, L.qkv[precision], P.qkv, LMX_F16, rows, LMX_ACT_NONE, nullptr, 0, st));
+    lmx_attn_desc ad;
+    memset(&ad, 0, sizeof(ad));
+    ad.Q = qkv;
+    ad.K = qkv + D;
+    ad.V = qkv + 2 * D;
+    ad.O = P.a;
+    ad.ldq = ad.ldk = ad.ldv = 3 * D;
+    ad.ldo = D;
+    ad.H = H;
+    ad.hd = hd;
+    ad.scale = scale;
+    int S;
+    if (L.glob) {
+      ad.B = n;
+      ad.Tq = ad.Tk = gg;
+      ad.mode = 0;
+      S = g;
+    } else {
+      ad.B = n * nW;
+      ad.Tq = ad.Tk = ws * ws;
+      ad.mode = 1;
+      ad.Gh = ad.Gw = g;
+      ad.ws = ws;
+      ad.q_stride = 1;
+      ad.pad_k = L.padkv + D;
+      ad.pad_v = L.padkv + 2 * D;
+      S = ws;
+    }
+    LMX_TRY(lmx_k_relpos_tables(&ad, L.rh, L.rw, S, P.rel, st));
+    ad.rel = P.rel;
+    ad.rel_S = S;
+    LMX_TRY(lmx_k_attention(&ad, st));
+    LMX_TRY(enc_lin(precision, P.a, L.proj[precision], P.x, LMX_F32, rows, LMX_ACT_NONE, P.x, 0, st));
+    LMX_TRY(lmx_k_layernorm(P.x, LMX_F32, D, L.g2, L.b2, P.h, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
+    LMX_TRY(enc_lin(precision, P.h, L.fc1[precision], P.u, LMX_F16, rows, LMX_ACT_GELU, nullptr, 0, st));
+    LMX_TRY(enc_lin(precision, P.u, L.fc2[precision], P.x, LMX_F32, rows, LMX_ACT_NONE, P.x, 0, st));
+  }
+  // neck: 1x1 (no bias) -> LayerNorm2d -> 3x3 (no bias) -> LayerNorm2d
+  LMX_TRY(lmx_k_cast_f32_f16(P.x, D, P.h, D, rows, D, st));
+  LMX_TRY(enc_lin(precision, P.h, m->n1[precision], P.y32, LMX_F32, rows, LMX_ACT_NONE, nullptr, 0, st));
+  LMX_TRY(lmx_k_layernorm(P.y32, LMX_F32, C, m->n1_ln.g, m->n1_ln.b, P.y16, LMX_F16, C, rows, C, 1e-6f, LMX_ACT_NONE, st));
+  if (precision == LMX_SAM_EXACT) {  // two accumulating launches of the implicit GEMM (whi, then + wlo), f32 output, f32 embedding
+    LMX_TRY(neck_conv(P.y16, m->n2_hi, P.acc, LMX_F32, nullptr, n, g, C, st));
+    LMX_TRY(neck_conv(P.y16, m->n2_lo, P.acc, LMX_F32, P.acc, n, g, C, st));
+    return lmx_k_layernorm(P.acc, LMX_F32, C, m->n2_ln.g, m->n2_ln.b, emb, LMX_F32, C, rows, C, 1e-6f, LMX_ACT_NONE, st);
+  }
+  LMX_TRY(neck_conv(P.y16, m->n2_w, P.acc, LMX_F16, nullptr, n, g, C, st));
+  return lmx_k_layernorm(P.acc, LMX_F16, C, m->n2_ln.g, m->n2_ln.b, emb, LMX_F16, C, rows, C, 1e-6f, LMX_ACT_NONE, st);
+}
+
+// ---- the mask decoder: one launch sequence per precision plan, as MaskDecoder.lowres / lowres_exact --------------------------------
+struct Dec {
+  const lmx_sam* m;
+  const Prepared& P;
+  int n;
+  hipStream_t st;
+
+  int ln(const float* x, const Norm& g, float eps, void* y, int out_dtype, int rows, int D, int act) const {
+    return lmx_k_layernorm(x, LMX_F32, D, g.g, g.b, y, out_dtype, D, rows, D, eps, act, st);
+  }
+  int add(const void* a, int a_dtype, const float* b, int b_rows, void* out, int out_dtype, int64_t rows) const {
+    return lmx_k_add_bcast(a, a_dtype, DD, b, DD, b_rows, out, out_dtype, DD, rows, DD, st);
+  }
+  int cast(const float* x, int64_t ldx, void* out, int64_t rows) const { return lmx_k_cast_f32_f16(x, ldx, out, DD, rows, DD, st); }
+  // K.gemm of the f16 plan
+  int gemm(const void* a, const Lin& l, void* C, int out_dtype, int M, int act, const void* res) const {
+    return lmx_gemm_dense(a, l.K, l.w, l.b, C, l.N, out_dtype, M, l.N, l.K, act, nullptr, res, l.N, st);
+  }
+  // MaskDecoder._attn
+  int attn16(const DecAttn& W, const void* q16, const void* k16, const void* v16, int tq, int tk, const float* res, float* out) const {
+    const int inner = W.q.N, hd = inner / DH;
+    LMX_TRY(gemm(q16, W.q, P.pq, LMX_F16, n * tq, LMX_ACT_NONE, nullptr));
+    LMX_TRY(gemm(k16, W.k, P.pk, LMX_F16, n * tk, LMX_ACT_NONE, nullptr));
+    LMX_TRY(gemm(v16, W.v, P.pv, LMX_F16, n * tk, LMX_ACT_NONE, nullptr));
+    lmx_attn_desc ad;
+    memset(&ad, 0, sizeof(ad));
+    ad.Q = P.pq;
+    ad.K = P.pk;
+    ad.V = P.pv;
+    ad.O = P.pa;
+    ad.ldq = ad.ldk = ad.ldv = ad.ldo = inner;
+    ad.B = n;
+    ad.H = DH;
+    ad.Tq = tq;
+    ad.Tk = tk;
+    ad.hd = hd;
+    ad.scale = (float)pow((double)hd, -0.5);
+    ad.mode = 0;
+    LMX_TRY(lmx_k_attention(&ad, st));
+    return gemm(P.pa, W.o, out, LMX_F32, n * tq, LMX_ACT_NONE, res);
+  }
+  // MaskDecoder._ffn
+  int ffn16(const Lin* l, const void* x16, float* out) const {
+    LMX_TRY(gemm(x16, l[0], P.t1, LMX_F16, n, LMX_ACT_RELU, nullptr));
+    LMX_TRY(gemm(P.t1, l[1], P.t2, LMX_F16, n, LMX_ACT_RELU, nullptr));
+    return gemm(P.t2, l[2], out, LMX_F32, n, LMX_ACT_NONE, nullptr);
+  }
+  // MaskDecoder._lin: x3 rows of act_in(x), then ONE GEMM over 3 K with the row scale
+  int lin3(const float* x, int64_t ldx, int64_t rows, const Lin& l, int act_in, int act, const float* res, float* out) const {
+    LMX_TRY(lmx_k_split3(x, ldx, act_in, nullptr, 0, P.x3, 3 * l.K, rows, l.K, l.K, 1, 0, st));
+    return lmx_gemm_dense(P.x3, 3 * l.K, l.w, l.b, out, l.N, LMX_F32, (int)rows, l.N, 3 * l.K, act, l.s, res, l.N, st);
+  }
+  // MaskDecoder._attn_exact
+  int attn32(const DecAttn& W, const float* q_in, const float* k_in, const float* v_in, int tq, int tk, const float* res, float* out) const {
+    const int inner = W.q.N, hd = inner / DH;
+    float *q = static_cast<float*>(P.pq), *k = static_cast<float*>(P.pk), *v = static_cast<float*>(P.pv), *a = static_cast<float*>(P.pa);
+    LMX_TRY(lin3(q_in, DD, (int64_t)n * tq, W.q, LMX_ACT_NONE, LMX_ACT_NONE, nullptr, q));
+    LMX_TRY(lin3(k_in, DD, (int64_t)n * tk, W.k, LMX_ACT_NONE, LMX_ACT_NONE, nullptr, k));
+    LMX_TRY(lin3(v_in, DD, (int64_t)n * tk, W.v, LMX_ACT_NONE, LMX_ACT_NONE, nullptr, v));
+    LMX_TRY(lmx_k_attention_f32(q, inner, k, inner, v, inner, a, inner, n, DH, tq, tk, hd, (float)pow((double)hd, -0.5), st));
+    return lin3(a, inner, (int64_t)n * tq, W.o, LMX_ACT_NONE, LMX_ACT_NONE, res, out);
+  }
+  // MaskDecoder._ffn_exact
+  int ffn32(const Lin* l, const float* x, int64_t ldx, float* out) const {
+    float *t1 = static_cast<float*>(P.t1), *t2 = static_cast<float*>(P.t2);
+    LMX_TRY(lin3(x, ldx, n, l[0], LMX_ACT_NONE, LMX_ACT_RELU, nullptr, t1));
+    LMX_TRY(lin3(t1, DD, n, l[1], LMX_ACT_NONE, LMX_ACT_RELU, nullptr, t2));
+    return lin3(t2, DD, n, l[2], LMX_ACT_NONE, LMX_ACT_NONE, nullptr, out);
+  }
+
+  // MaskDecoder.lowres: emb f16 [n * G * G, 256] -> logits f32 [n, 4G, 4G], P.iou4 f32 [n, 4]
+  int lowres16(const void* emb, float* logits) const {
+    const LmxSamCfg& c = m->cfg;
+    const DecPlan& W = m->dec[LMX_SAM_F16];
+    const int G = c.grid(), Pn = G * G, T = DT;
+    const int64_t nT = (int64_t)n * T, nP = (int64_t)n * Pn;
+    const float eps = 1e-6f;
+    const float* qpe = P.tokens;
+    float *queries = P.qa, *spare = P.qb, *keys = P.keys_a, *kspare = P.keys_b;
+    auto flip = [](float*& a, float*& b) {
+      float* t = a;
+      a = b;
+      b = t;
+    };
+    LMX_TRY(add(emb, LMX_F16, m->no_mask, 1, keys, LMX_F32, nP));
+    for (int i = 0; i < 2; ++i) {
+      const DecLayer& L = W.L[i];
+      if (i == 0) {
+        LMX_TRY(cast(P.tokens, DD, P.qq, nT));
+        LMX_TRY(attn16(L.sa, P.qq, P.qq, P.qq, T, T, nullptr, queries));
+      } else {
+        LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, P.qq, LMX_F16, nT));
+        LMX_TRY(cast(queries, DD, P.qc16, nT));
+        LMX_TRY(attn16(L.sa, P.qq, P.qq, P.qc16, T, T, queries, spare));
+        flip(queries, spare);
+      }
+      LMX_TRY(ln(queries, L.ln[0], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+      flip(queries, spare);
+      LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, P.qq, LMX_F16, nT));
+      LMX_TRY(add(keys, LMX_F32, m->key_pe, Pn, P.kk, LMX_F16, nP));
+      LMX_TRY(cast(keys, DD, P.kc16, nP));
+      LMX_TRY(attn16(L.t2i, P.qq, P.kk, P.kc16, T, Pn, queries, spare));
+      flip(queries, spare);
+      LMX_TRY(ln(queries, L.ln[1], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+      flip(queries, spare);
+      LMX_TRY(cast(queries, DD, P.qc16, nT));
+      LMX_TRY(gemm(P.qc16, L.lin1, P.hh, LMX_F16, (int)nT, LMX_ACT_RELU, nullptr));
+      LMX_TRY(gemm(P.hh, L.lin2, spare, LMX_F32, (int)nT, LMX_ACT_NONE, queries));
+      flip(queries, spare);
+      LMX_TRY(ln(queries, L.ln[2], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+      flip(queries, spare);
+      LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, P.qq, LMX_F16, nT));
+      // (keys have not changed since the token-to-image attention above: P.kk is still keys + key_pe)
+      LMX_TRY(cast(queries, DD, P.qc16, nT));
+      LMX_TRY(attn16(L.i2t, P.kk, P.qq, P.qc16, Pn, T, keys, kspare));
+      flip(keys, kspare);
+      LMX_TRY(ln(keys, L.ln[3], eps, kspare, LMX_F32, (int)nP, DD, LMX_ACT_NONE));
+      flip(keys, kspare);
+    }
+    LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, P.qq, LMX_F16, nT));
+    LMX_TRY(add(keys, LMX_F32, m->key_pe, Pn, P.kk, LMX_F16, nP));
+    LMX_TRY(cast(keys, DD, P.kc16, nP));  // the final attention's values and the upscaler's input
+    LMX_TRY(attn16(W.fin, P.qq, P.kk, P.kc16, T, Pn, queries, spare));
+    flip(queries, spare);
+    LMX_TRY(ln(queries, m->ln_final, 1e-5f, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+    flip(queries, spare);
+    LMX_TRY(cast(queries, (int64_t)T * DD, P.tok16, n));  // q3[:, 0]: the iou token
+    // upscaler: per-pixel GEMMs, LayerNorm2d + GELU row-wise on the [.., quadrant, 64] view, pixel shuffle deferred
+    LMX_TRY(gemm(P.kc16, W.up1, P.u1, LMX_F32, (int)nP, LMX_ACT_NONE, nullptr));
+    LMX_TRY(ln(P.u1, m->up_ln, eps, P.u1n, LMX_F16, (int)(nP * 4), 64, LMX_ACT_GELU));
+    LMX_TRY(gemm(P.u1n, W.up2, P.u2, LMX_F16, (int)(nP * 4), LMX_ACT_GELU, nullptr));
+    LMX_TRY(cast(queries + DD, (int64_t)T * DD, P.qc16, n));  // q3[:, 1]: mask token 0
+    LMX_TRY(ffn16(W.hyp, P.qc16, P.hyper));
+    LMX_TRY(lmx_k_hyper_mask_multi(P.u2, P.hyper, logits, n, 1, G, 32, st));
+    return ffn16(W.iou, P.tok16, P.iou4);
+  }
+
+  // MaskDecoder.lowres_exact: emb f32
+  int lowres32(const void* emb, float* logits) const {
+    const LmxSamCfg& c = m->cfg;
+    const DecPlan& W = m->dec[LMX_SAM_EXACT];
+    const int G = c.grid(), Pn = G * G, T = DT;
+    const int64_t nT = (int64_t)n * T, nP = (int64_t)n * Pn;
+    const float eps = 1e-6f;
+    const float* qpe = P.tokens;
+    float *queries = P.qa, *spare = P.qb, *keys = P.keys_a, *kspare = P.keys_b;
+    float *qq = static_cast<float*>(P.qq), *kk = static_cast<float*>(P.kk), *hh = static_cast<float*>(P.hh);
+    auto flip = [](float*& a, float*& b) {
+      float* t = a;
+      a = b;
+      b = t;
+    };
+    LMX_TRY(add(emb, LMX_F32, m->no_mask, 1, keys, LMX_F32, nP));
+    for (int i = 0; i < 2; ++i) {
+      const DecLayer& L = W.L[i];
+      if (i == 0) {
+        LMX_TRY(attn32(L.sa, P.tokens, P.tokens, P.tokens, T, T, nullptr, queries));
+      } else {
+        LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, qq, LMX_F32, nT));
+        LMX_TRY(attn32(L.sa, qq, qq, queries, T, T, queries, spare));
+        flip(queries, spare);
+      }
+      LMX_TRY(ln(queries, L.ln[0], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+      flip(queries, spare);
+      LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, qq, LMX_F32, nT));
+      LMX_TRY(add(keys, LMX_F32, m->key_pe, Pn, kk, LMX_F32, nP));
+      LMX_TRY(attn32(L.t2i, qq, kk, keys, T, Pn, queries, spare));
+      flip(queries, spare);
+      LMX_TRY(ln(queries, L.ln[1], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+      flip(queries, spare);
+      LMX_TRY(lin3(queries, DD, nT, L.lin1, LMX_ACT_NONE, LMX_ACT_RELU, nullptr, hh));
+      LMX_TRY(lin3(hh, LMX_SAM_DEC_MLP, nT, L.lin2, LMX_ACT_NONE, LMX_ACT_NONE, queries, spare));
+      flip(queries, spare);
+      LMX_TRY(ln(queries, L.ln[2], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+      flip(queries, spare);
+      LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, qq, LMX_F32, nT));
+      LMX_TRY(attn32(L.i2t, kk, qq, queries, Pn, T, keys, kspare));
+      flip(keys, kspare);
+      LMX_TRY(ln(keys, L.ln[3], eps, kspare, LMX_F32, (int)nP, DD, LMX_ACT_NONE));
+      flip(keys, kspare);
+    }
+    LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, qq, LMX_F32, nT));
+    LMX_TRY(add(keys, LMX_F32, m->key_pe, Pn, kk, LMX_F32, nP));
+    LMX_TRY(attn32(W.fin, qq, kk, keys, T, Pn, queries, spare));
+    flip(queries, spare);
+    LMX_TRY(ln(queries, m->ln_final, 1e-5f, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+    flip(queries, spare);
+    // upscaler: ConvTranspose2d(k2, s2) as per-pixel GEMMs, LayerNorm2d row-wise on the [.., quadrant, 64] view, exact GELUs folded
+    // into the next split / the final dot product
+    float *u1n = static_cast<float*>(P.u1n), *u2 = static_cast<float*>(P.u2);
+    LMX_TRY(lin3(keys, DD, nP, W.up1, LMX_ACT_NONE, LMX_ACT_NONE, nullptr, P.u1));
+    LMX_TRY(ln(P.u1, m->up_ln, eps, u1n, LMX_F32, (int)(nP * 4), 64, LMX_ACT_NONE));
+    LMX_TRY(lin3(u1n, 64, nP * 4, W.up2, LMX_ACT_GELU, LMX_ACT_NONE, nullptr, u2));
+    LMX_TRY(ffn32(W.hyp, queries + DD, (int64_t)T * DD, P.hyper));  // q3[:, 1]: mask token 0
+    LMX_TRY(lmx_k_hyper_mask_multi_f32(u2, P.hyper, logits, n, 1, G, 32, LMX_ACT_GELU, st));
+    return ffn32(W.iou, queries, (int64_t)T * DD, P.iou4);  // q3[:, 0]: the iou token
+  }
+};
+
+// MaskDecoder.predict (+ pack_bits, contour_features) for n <= max_batch frames, writing the chunk's rows of the outputs
+int decode_chunk(const lmx_sam* m, const Prepared& P, int precision, const void* emb, int n, int h, int w, const float* boxes, uint8_t* mask,
+                 uint8_t* mask_bits, int64_t* stats, int64_t* contour, float* iou, float* lowres, hipStream_t st) {
+  const LmxSamCfg& c = m->cfg;
+  const int L = 4 * c.grid();
+  uint8_t* mk = mask ? mask : P.mask;
+  float* logits = lowres ? lowres : P.logits;
+  LMX_TRY(lmx_k_prompt_box(boxes, 4, P.sparse, n, (double)P.nw / (double)w, (double)P.nh / (double)h, (float)c.image, m->gauss, m->corner, DD / 2, st));
+  // torch.cat([out_tokens, sparse], 1): the output-token rows are in place since prepare
+  LMX_HIP(hipMemcpy2DAsync(P.tokens + LMX_SAM_OUT_TOKENS * DD, (size_t)DT * DD * 4, P.sparse, (size_t)2 * DD * 4, (size_t)2 * DD * 4, (size_t)n,
+                           hipMemcpyDeviceToDevice, st));
+  const Dec d{m, P, n, st};
+  LMX_TRY(precision == LMX_SAM_EXACT ? d.lowres32(emb, logits) : d.lowres16(emb, logits));
+  LMX_TRY(lmx_k_mask_post(logits, n, L, c.image, P.nh, P.nw, h, w, mk, stats, P.post, st));
+  LMX_HIP(hipMemcpy2DAsync(iou, 4, P.iou4, 16, 4, (size_t)n, hipMemcpyDeviceToDevice, st));  // iou[:, 0]
+  if (mask_bits) LMX_TRY(lmx_k_pack_bits(mk, (int64_t)n * h, w, mask_bits, st));
+  if (contour) LMX_TRY(lmx_k_contour_features(mk, n, h, w, contour, P.contour_ws, st));
+  return LMX_OK;
+}
+
+int check_call(const lmx_sam* m, const char* fn, int n, int h, int w, int precision) {
+  LMX_TRY(lmx_handle_on_device(m, fn));
+  LMX_REQUIRE(n > 0, "%s: n = %d frames", fn, n);
+  LMX_REQUIRE(h > 0 && w > 0, "%s: frame size %d x %d", fn, h, w);
+  return check_precision(m, fn, precision);
+}
+
+int check_decode(const lmx_sam* m, const char* fn, const void* in, const char* in_name, int n, int h, int w, const void* boxes, int precision,
+                 const void* stats, const void* contour, const void* iou) {
+  LMX_TRY(check_call(m, fn, n, h, w, precision));
+  LMX_REQUIRE(in != nullptr, "%s: null pointer (%s)", fn, in_name);
+  LMX_REQUIRE(boxes != nullptr, "%s: null pointer (boxes)", fn);
+  LMX_REQUIRE(stats != nullptr, "%s: null pointer (stats: mask, mask_bits, contour and lowres may be NULL, stats and iou may not)", fn);
+  LMX_REQUIRE(iou != nullptr, "%s: null pointer (iou: mask, mask_bits, contour and lowres may be NULL, stats and iou may not)", fn);
+  LMX_REQUIRE(!contour || (h > 1 && w > 1 && (int64_t)h * w <= 0x1fffff),
+              "%s: contour features are served for frames of 2 x 2 up to 2^21 - 1 pixels, not %d x %d (pass contour = NULL)", fn, h, w);
+  return LMX_OK;
+}
+
+}  // namespace
+
+extern "C" int lmx_sam_open_host(const char* path_host, int max_batch, lmx_sam** out_host) {
+  return lmx_handle_open("lmx_sam_open_host", path_host, max_batch, out_host, open_into, destroy);
+}
+
+extern "C" void lmx_sam_close(lmx_sam* m) { lmx_handle_close(m, destroy); }
+
+extern "C" int lmx_sam_info(const lmx_sam* m, lmx_sam_info_t* info_host) {
+  LMX_REQUIRE(m && info_host, "lmx_sam_info: null argument");
+  lmx_sam_fill_info(m->cfg, m->max_batch, info_host);
+  return LMX_OK;
+}
+
+extern "C" int lmx_sam_resized(const lmx_sam* m, int h, int w, int* nh_host, int* nw_host) {
+  LMX_REQUIRE(m && nh_host && nw_host, "lmx_sam_resized: null argument");
+  LMX_REQUIRE(h > 0 && w > 0, "lmx_sam_resized: frame size %d x %d", h, w);
+  lmx_sam_resized_hw(m->cfg.image, h, w, nh_host, nw_host);
+  return LMX_OK;
+}
+
+extern "C" int lmx_sam_prepare(lmx_sam* m, int h, int w, int precision) {
+  LMX_TRY(lmx_handle_on_device(m, "lmx_sam_prepare"));
+  LMX_REQUIRE(h > 0 && w > 0, "lmx_sam_prepare: frame size %d x %d", h, w);
+  return prepare(m, h, w, precision, nullptr);
+}
+
+extern "C" int lmx_sam_encode(lmx_sam* m, const uint8_t* frames, int n, int h, int w, int precision, void* emb, lmx_stream_t stream) {
+  LMX_TRY(check_call(m, "lmx_sam_encode", n, h, w, precision));
+  LMX_REQUIRE(frames != nullptr, "lmx_sam_encode: null pointer (frames)");
+  LMX_REQUIRE(emb != nullptr, "lmx_sam_encode: null pointer (emb)");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LMX_TRY(lmx_handle_stream_on_device(m, "lmx_sam_encode", st));  // before prepare: a refused call allocates nothing
+  const Prepared* P = nullptr;
+  LMX_TRY(prepare(m, h, w, precision, &P));  // a pair seen before: a lookup
+  const size_t frame_bytes = (size_t)h * w * 3, g = (size_t)m->cfg.grid();
+  const size_t emb_bytes = g * g * m->cfg.out_ch * (precision == LMX_SAM_EXACT ? 4 : 2);
+  for (int done = 0; done < n; done += m->max_batch) {
+    const int nb = n - done < m->max_batch ? n - done : m->max_batch;
+    LMX_TRY(encode_chunk(m, *P, precision, frames + (size_t)done * frame_bytes, nb, h, w, static_cast<char*>(emb) + (size_t)done * emb_bytes, st));
+  }
+  return LMX_OK;
+}
+
+// the chunk loop of lmx_sam_decode (frames == nullptr: emb_or_null holds the embeddings) and lmx_sam_segment (encode into the workspace first)
+static int run(lmx_sam* m, const Prepared& P, const uint8_t* frames, const void* emb, int n, int h, int w, const float* boxes, int precision,
+               uint8_t* mask, uint8_t* mask_bits, int64_t* stats, int64_t* contour, float* iou, float* lowres, hipStream_t st) {
+  const size_t frame_bytes = (size_t)h * w * 3, g = (size_t)m->cfg.grid(), px = (size_t)h * w, wb = (size_t)(w + 7) / 8, LL = 16 * g * g;
+  const size_t emb_bytes = g * g * m->cfg.out_ch * (precision == LMX_SAM_EXACT ? 4 : 2);
+  for (int done = 0; done < n; done += m->max_batch) {
+    const int nb = n - done < m->max_batch ? n - done : m->max_batch;
+    const size_t d = (size_t)done;
+    const void* e = emb ? static_cast<const char*>(emb) + d * emb_bytes : P.emb;
+    if (frames) LMX_TRY(encode_chunk(m, P, precision, frames + d * frame_bytes, nb, h, w, P.emb, st));
+    LMX_TRY(decode_chunk(m, P, precision, e, nb, h, w, boxes + d * 4, mask ? mask + d * px : nullptr, mask_bits ? mask_bits + d * h * wb : nullptr,
+                         stats + d * 8, contour ? contour + d * 8 : nullptr, iou + d, lowres ? lowres + d * LL : nullptr, st));
+  }
+  return LMX_OK;
+}
+
+extern "C" int lmx_sam_decode(lmx_sam* m, const void* emb, int n, int h, int w, const float* boxes, int precision, uint8_t* mask, uint8_t* mask_bits,
+                              int64_t* stats, int64_t* contour, float* iou, float* lowres, lmx_stream_t stream) {
+  LMX_TRY(check_decode(m, "lmx_sam_decode", emb, "emb", n, h, w, boxes, precision, stats, contour, iou));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LMX_TRY(lmx_handle_stream_on_device(m, "lmx_sam_decode", st));
+  const Prepared* P = nullptr;
+  LMX_TRY(prepare(m, h, w, precision, &P));
+  return run(m, *P, nullptr, emb, n, h, w, boxes, precision, mask, mask_bits, stats, contour, iou, lowres, st);
+}
+
+extern "C" int lmx_sam_segment(lmx_sam* m, const uint8_t* frames, int n, int h, int w, const float* boxes, int precision, uint8_t* mask,
+                               uint8_t* mask_bits, int64_t* stats, int64_t* contour, float* iou, float* lowres, lmx_stream_t stream) {
+  LMX_TRY(check_decode(m, "lmx_sam_segment", frames, "frames", n, h, w, boxes, precision, stats, contour, iou));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LMX_TRY(lmx_handle_stream_on_device(m, "lmx_sam_segment", st));  // before prepare: a refused call allocates nothing
+  const Prepared* P = nullptr;
+  LMX_TRY(prepare(m, h, w, precision, &P));
+  return run(m, *P, frames, nullptr, n, h, w, boxes, precision, mask, mask_bits, stats, contour, iou, lowres, st);
+}
+
+extern "C" int lmx_sam_segment_host(lmx_sam* m, const uint8_t* frames_host, int n, int h, int w, const float* boxes_host, int precision,
+                                    uint8_t* mask_host, uint8_t* mask_bits_host, int64_t* stats_host, int64_t* contour_host, float* iou_host,
+                                    float* lowres_host) {
+  LMX_TRY(check_decode(m, "lmx_sam_segment_host", frames_host, "frames", n, h, w, boxes_host, precision, stats_host, contour_host, iou_host));
+  const Prepared* P = nullptr;
+  LMX_TRY(prepare(m, h, w, precision, &P));
+  // staging of one chunk: frames | boxes | mask | mask_bits | stats | contour | iou | lowres, each on a 256-byte boundary
+  const size_t B = (size_t)(n < m->max_batch ? n : m->max_batch), frame_bytes = (size_t)h * w * 3, px = (size_t)h * w, wb = (size_t)(w + 7) / 8;
+  const size_t g = (size_t)m->cfg.grid(), LL = 16 * g * g;
+  LmxLayout lay;
+  lay.add(B * frame_bytes);  // the frames, at the blob's start
+  const size_t o_boxes = lay.add(B * 16), o_mask = lay.add(mask_host ? B * px : 0), o_bits = lay.add(mask_bits_host ? B * h * wb : 0),
+               o_stats = lay.add(B * 64), o_contour = lay.add(contour_host ? B * 64 : 0), o_iou = lay.add(B * 4),
+               o_lowres = lay.add(lowres_host ? B * LL * 4 : 0);
+  LMX_TRY(lmx_handle_grow_stage(m, lay.total));
+  char* s = m->stage;
+  float* boxes = reinterpret_cast<float*>(s + o_boxes);
+  uint8_t *mask = mask_host ? reinterpret_cast<uint8_t*>(s + o_mask) : nullptr, *bits = mask_bits_host ? reinterpret_cast<uint8_t*>(s + o_bits) : nullptr;
+  int64_t *stats = reinterpret_cast<int64_t*>(s + o_stats), *contour = contour_host ? reinterpret_cast<int64_t*>(s + o_contour) : nullptr;
+  float *iou = reinterpret_cast<float*>(s + o_iou), *lowres = lowres_host ? reinterpret_cast<float*>(s + o_lowres) : nullptr;
+  for (int done = 0; done < n; done += m->max_batch) {
+    const size_t nb = (size_t)(n - done < m->max_batch ? n - done : m->max_batch), d = (size_t)done;
+    LMX_HIP(hipMemcpyAsync(s, frames_host + d * frame_bytes, nb * frame_bytes, hipMemcpyHostToDevice, m->own));
+    LMX_HIP(hipMemcpyAsync(boxes, boxes_host + d * 4, nb * 16, hipMemcpyHostToDevice, m->own));
+    LMX_TRY(run(m, *P, reinterpret_cast<const uint8_t*>(s), nullptr, (int)nb, h, w, boxes, precision, mask, bits, stats, contour, iou, lowres, m->own));
+    if (mask) LMX_HIP(hipMemcpyAsync(mask_host + d * px, mask, nb * px, hipMemcpyDeviceToHost, m->own));
+    if (bits) LMX_HIP(hipMemcpyAsync(mask_bits_host + d * h * wb, bits, nb * h * wb, hipMemcpyDeviceToHost, m->own));
+    LMX_HIP(hipMemcpyAsync(stats_host + d * 8, stats, nb * 64, hipMemcpyDeviceToHost, m->own));
+    if (contour) LMX_HIP(hipMemcpyAsync(contour_host + d * 8, contour, nb * 64, hipMemcpyDeviceToHost, m->own));
+    LMX_HIP(hipMemcpyAsync(iou_host + d, iou, nb * 4, hipMemcpyDeviceToHost, m->own));
+    if (lowres) LMX_HIP(hipMemcpyAsync(lowres_host + d * LL, lowres, nb * LL * 4, hipMemcpyDeviceToHost, m->own));
+    LMX_HIP(hipStreamSynchronize(m->own));
+  }
+  return LMX_OK;
+}

@@ -35,6 +35,10 @@ class YoloInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("scale", "nc", "imgsz", "kpt_k", "kpt_ndim", "plans", "max_batch")]
 
 
+class SamInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("encoder", "hidden", "heads", "layers", "mlp", "window", "patch", "image", "plans", "max_batch")]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -139,6 +143,16 @@ SIGNATURES = {
     "lmx_yolo_predict": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP]),
     "lmx_yolo_detect": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _D, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lmx_yolo_detect_host": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _D, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_sam_image_check_host": (_I, [C.c_char_p, C.POINTER(SamInfo)]),
+    "lmx_sam_open_host": (_I, [C.c_char_p, _I, C.POINTER(_VP)]),
+    "lmx_sam_close": (None, [_VP]),
+    "lmx_sam_info": (_I, [_VP, C.POINTER(SamInfo)]),
+    "lmx_sam_resized": (_I, [_VP, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lmx_sam_prepare": (_I, [_VP, _I, _I, _I]),
+    "lmx_sam_encode": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP]),
+    "lmx_sam_decode": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_sam_segment": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_sam_segment_host": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

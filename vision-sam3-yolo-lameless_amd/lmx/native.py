@@ -13,8 +13,12 @@ lmx/resample.py.
 ``write_yolo_image`` / ``NativeYolo`` are the same for a ``YoloDetector`` (csrc/yolo_model.hip, csrc/yolo_image.h,
 examples/yolo_detect.c): the launch sequence of ``YoloDetector.detect`` / ``detect_pose`` on either precision plan, with the twins of
 lmx/letterbox.py and ``kernels.split_k_for`` (``lmx_h_letterbox_geometry``, ``lmx_h_letterbox_tables``, ``lmx_h_conv_split_k``)
-bound for the tests (tests/test_native_yolo_host.py, tests/test_gpu_native_yolo.py).  What the two handles share on the C side
-(csrc/model_handle.h) they share here: ``_NativeHandle``."""
+bound for the tests (tests/test_native_yolo_host.py, tests/test_gpu_native_yolo.py).
+
+``write_sam_image`` / ``NativeSam`` are the same for a ``SamVitEncoder`` with a ``MaskDecoder`` (csrc/sam_model.hip, csrc/sam_image.h,
+examples/sam_segment.c): the launch sequence of ``SamVitEncoder.encode`` and ``MaskDecoder.predict`` for one box per frame on either
+precision plan, followed by ``kernels.pack_bits`` / ``kernels.contour_features`` where asked for (tests/test_native_sam_host.py,
+tests/test_gpu_native_sam.py).  What the handles share on the C side (csrc/model_handle.h) they share here: ``_NativeHandle``."""
 import ctypes as C
 import struct
 
@@ -22,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, letterbox, resample
-from ._lib import DinoInfo, LetterboxGeo, LmxError, YoloInfo, check
+from ._lib import DinoInfo, LetterboxGeo, LmxError, SamInfo, YoloInfo, check
 
 MAGIC = b"LMXIMAGE"
 VERSION = 1
@@ -165,6 +169,149 @@ def check_yolo_image(path):
     """lmx_yolo_image_check_host: validate an image on the host (no GPU) -> YoloInfo; LmxError names the offending field or tensor."""
     info = YoloInfo()
     check(_lib.load().lmx_yolo_image_check_host(str(path).encode(), C.byref(info)), "lmx_yolo_image_check_host")
+    return info
+
+
+# ---- the SAM weight image (csrc/sam_image.h) -------------------------------------------------------------------------------
+SAM_ENC_VIT = 0  # LMX_SAM_ENC_VIT: the config block's `encoder` field (the Hiera encoder has no image yet)
+_SAM_ATTN = {"sa": "self_attn", "t2i": "cross_attn_token_to_image", "i2t": "cross_attn_image_to_token"}
+_SAM_PROJ = {"q": "q_proj", "k": "k_proj", "v": "v_proj", "o": "out_proj"}
+_SAM_FFN = {"in": "proj_in", "mid": "layers.0", "out": "proj_out"}
+
+
+def sam_decoder_linears():
+    """Ordered {short name in the image: parameter prefix in the state dict}: every Linear MaskDecoder.lowres / lowres_exact touches
+    for a box prompt with one mask (mask token 0), in the order of csrc/host_sam_image.cpp lmx_sam_linears().  up1 / up2 are the two
+    ConvTranspose2d re-laid as per-pixel GEMMs."""
+    out = {}
+    t = "mask_decoder.transformer."
+    for i in range(2):
+        p = f"{t}layers.{i}."
+        for a in ("sa", "t2i"):
+            for k, v in _SAM_PROJ.items():
+                out[f"L{i}.{a}.{k}"] = f"{p}{_SAM_ATTN[a]}.{v}"
+        out[f"L{i}.lin1"], out[f"L{i}.lin2"] = p + "mlp.lin1", p + "mlp.lin2"
+        for k, v in _SAM_PROJ.items():
+            out[f"L{i}.i2t.{k}"] = f"{p}{_SAM_ATTN['i2t']}.{v}"
+    for k, v in _SAM_PROJ.items():
+        out[f"fin.{k}"] = f"{t}final_attn_token_to_image.{v}"
+    out["up1"], out["up2"] = "mask_decoder.upscale_conv1", "mask_decoder.upscale_conv2"
+    for k, v in _SAM_FFN.items():
+        out[f"hyp0.{k}"] = f"mask_decoder.output_hypernetworks_mlps.0.{v}"
+    for k, v in _SAM_FFN.items():
+        out[f"iou.{k}"] = f"mask_decoder.iou_prediction_head.{v}"
+    return out
+
+
+def _sam_decoder_f16(decoder, short):
+    """(w f16, b f32) of the f16 plan's Linear `short`, as MaskDecoder.__init__ uploaded them"""
+    parts = short.split(".")
+    if parts[0] in ("L0", "L1"):
+        L = decoder.layers[int(parts[0][1])]
+        return L["w1" if parts[1] == "lin1" else "w2"] if len(parts) == 2 else L[parts[1]][_SAM_PROJ[parts[2]]]
+    if parts[0] == "fin":
+        return decoder.final[_SAM_PROJ[parts[1]]]
+    if parts[0] in ("up1", "up2"):
+        return getattr(decoder, parts[0])
+    return (decoder.hypers[0] if parts[0] == "hyp0" else decoder.iou_head)[list(_SAM_FFN).index(parts[1])]
+
+
+def _sam_decoder_x3(decoder, prefix):
+    """(x3 weight f16 [N, 3K], shifted bias f32 [N], row scale f32 [N]) of the exact plan's Linear `prefix`: what MaskDecoder._lin
+    builds on its first use, built here from the same float32 parameters with the same expressions (an entry _lin has cached already
+    is taken as it is)."""
+    from .exact import split_rows_x3
+
+    if prefix in decoder._wx:
+        return tuple(host(t) for t in decoder._wx[prefix])
+    w, b = decoder._sd[prefix + ".weight"], decoder._sd[prefix + ".bias"]
+    if prefix.startswith("mask_decoder.upscale_conv"):  # ConvTranspose2d(k2, s2) as a per-pixel GEMM, as lowres_exact re-lays it
+        w, b = np.transpose(w, (2, 3, 1, 0)).reshape(4 * w.shape[1], w.shape[0]), np.tile(b, 4)
+    x3, sc, e = split_rows_x3(w, [w.shape[1]])
+    return x3, np.ldexp(b.astype(np.float32), e).astype(np.float32), sc
+
+
+def _sam_plans(plans, who):
+    plans = tuple(plans)
+    if not plans or any(p not in PLANS for p in plans):
+        raise LmxError(f"{who}: plans {plans!r}: a non-empty subset of {tuple(PLANS)}")
+    return plans
+
+
+def sam_config_block(encoder, plans=("f16", "exact")):
+    """12 int32 (LmxSamCfg, csrc/sam_image.h), eps as float64, then the global-attention layer indices as int32, zero-padded to 8 bytes."""
+    cfg = encoder.cfg
+    gidx = sorted(int(i) for i in cfg.global_idx)
+    mask = sum(1 << PLANS[p] for p in set(_sam_plans(plans, "sam_config_block")))
+    ints = (SAM_ENC_VIT, cfg.hidden, cfg.heads, cfg.layers, cfg.mlp, cfg.window, cfg.patch, cfg.image, cfg.out_ch, mask, len(gidx), 0)
+    tail = struct.pack(f"<{len(gidx)}i", *gidx)
+    return struct.pack("<12id", *ints, float(cfg.eps)) + tail + b"\0" * (-len(tail) % 8)
+
+
+def sam_tensors(encoder, decoder, plans=("f16", "exact")):
+    """Ordered {name: numpy array}: what SamVitEncoder and MaskDecoder hold on the device, in final device form, for `plans`.  The
+    tensors both build lazily under the exact plan — the encoder's [whi | wlo] weights (_split2) with the two halves of the neck's
+    3 x 3, the decoder's x3 weight / shifted bias / scale triples (_lin) — are built here eagerly, for every layer of
+    sam_decoder_linears()."""
+    plans = _sam_plans(plans, "sam_tensors")
+    e, d = encoder, decoder
+    out = {"enc.pe_b": host(e.pe_b), "enc.pos": host(e.pos), "enc.lut": host(e.lut)}
+    if "f16" in plans:
+        out["enc.pe_w"] = host(e.pe_w)
+    if "exact" in plans:
+        out["enc.x2.pe"] = host(e._split2("pe"))
+    for i, L in enumerate(e.layers):
+        p = f"enc.L{i}."
+        for n in ("g1", "b1", "bqkv", "padkv", "rh", "rw", "bo", "g2", "b2", "bb1", "bb2"):
+            out[p + n] = host(L[n])
+        if "f16" in plans:
+            for n in ("wqkv", "wo", "w1", "w2"):
+                out[p + n] = host(L[n])
+        if "exact" in plans:
+            for n in ("qkv", "proj", "fc1", "fc2"):
+                out[f"enc.x2.L{i}.{n}"] = host(e._split2(f"{i}.{n}"))
+    out["enc.n1.g"], out["enc.n1.b"] = host(e.n1_ln[0]), host(e.n1_ln[1])
+    out["enc.n2.g"], out["enc.n2.b"] = host(e.n2_ln[0]), host(e.n2_ln[1])
+    if "f16" in plans:
+        out["enc.n1.w"], out["enc.n2.w"] = host(e.n1_w), host(e.n2_w)
+    if "exact" in plans:
+        out["enc.x2.n1"] = host(e._split2("n1"))
+        w2 = host(e._split2("n2"))
+        kc = w2.shape[1] // 2
+        out["enc.x2.n2.hi"], out["enc.x2.n2.lo"] = np.ascontiguousarray(w2[:, :kc]), np.ascontiguousarray(w2[:, kc:])
+    out.update({"dec.gauss": host(d.gauss), "dec.corner": host(d.corner), "dec.key_pe": host(d.key_pe), "dec.no_mask": host(d.no_mask),
+                "dec.out_tokens": host(d.out_tokens), "dec.point_embed": host(d.point_embed), "dec.not_a_point": host(d.not_a_point)})
+    if d.mask_params is not None:
+        out["dec.mask_params"] = host(d.mask_params)
+    for i, L in enumerate(d.layers):
+        for j in range(1, 5):
+            out[f"dec.L{i}.ln{j}.g"], out[f"dec.L{i}.ln{j}.b"] = host(L[f"ln{j}"][0]), host(L[f"ln{j}"][1])
+    out["dec.ln_final.g"], out["dec.ln_final.b"] = host(d.ln_final[0]), host(d.ln_final[1])
+    out["dec.up_ln.g"], out["dec.up_ln.b"] = host(d.up_ln[0]), host(d.up_ln[1])
+    for short, prefix in sam_decoder_linears().items():
+        if "f16" in plans:
+            w, b = _sam_decoder_f16(d, short)
+            out[f"dec.f16.{short}.w"], out[f"dec.f16.{short}.b"] = host(w), host(b)
+        if "exact" in plans:
+            out[f"dec.x3.{short}.w"], out[f"dec.x3.{short}.b"], out[f"dec.x3.{short}.s"] = _sam_decoder_x3(d, prefix)
+    return out
+
+
+def write_sam_image(encoder, decoder, path, plans=("f16", "exact")):
+    """Export a SamVitEncoder with its MaskDecoder (any device) as the weight image lmx_sam_open_host reads, with the tensors of
+    `plans`.  Returns the file's size in bytes."""
+    plans = _sam_plans(plans, "write_sam_image")
+    cfg = encoder.cfg
+    if (decoder.S, decoder.G) != (cfg.image, cfg.grid) or cfg.out_ch != 256:
+        raise LmxError(f"write_sam_image: a decoder for image {decoder.S} / grid {decoder.G} does not read the {cfg.out_ch}-channel embedding "
+                       f"of an encoder with image {cfg.image} / grid {cfg.grid}")
+    return write_image(path, KIND_SAM, sam_config_block(encoder, plans), sam_tensors(encoder, decoder, plans))
+
+
+def check_sam_image(path):
+    """lmx_sam_image_check_host: validate an image on the host (no GPU) -> SamInfo; LmxError names the offending field or tensor."""
+    info = SamInfo()
+    check(_lib.load().lmx_sam_image_check_host(str(path).encode(), C.byref(info)), "lmx_sam_image_check_host")
     return info
 
 
@@ -384,3 +531,96 @@ class NativeYolo(_NativeHandle):
                                                  *(t.ctypes.data for t in (boxes, scores, cls, src, counts)),
                                                  kpts.ctypes.data if kpts is not None else None), "lmx_yolo_detect_host")
         return (boxes, scores, cls, src, counts) + ((kpts,) if kpts is not None else ())
+
+
+class NativeSam(_NativeHandle):
+    """lmx_sam_open_host(path, max_batch) on `device` (default: torch's current device).  `precision`: "f16" or "exact"."""
+    _PREFIX, _INFO = "lmx_sam_", SamInfo
+    OUTPUTS = ("mask", "mask_bits", "contour", "lowres")  # what a caller may leave out (NULL in C); stats and iou always come
+
+    @property
+    def grid(self):
+        return self.info.image // self.info.patch
+
+    def prepare(self, h, w, precision):
+        """lmx_sam_prepare: tables and workspace of one (frame size, plan) (synchronous); encode() / decode() / segment() of that pair
+        then only enqueue."""
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_sam_prepare(self._handle(), int(h), int(w), PLANS[precision]), "lmx_sam_prepare")
+
+    def resized(self, h, w):
+        """lmx_sam_resized: ResizeLongestSide.get_preprocess_shape of an h x w frame -> (nh, nw)."""
+        nh, nw = C.c_int(0), C.c_int(0)
+        check(self._lib.lmx_sam_resized(self._handle(), int(h), int(w), C.byref(nh), C.byref(nw)), "lmx_sam_resized")
+        return nh.value, nw.value
+
+    def _emb_dtype(self, precision):
+        return torch.float32 if precision == "exact" else torch.float16
+
+    def encode(self, frames, precision):
+        """u8 [n,h,w,3] device tensor, channel order as given -> emb [n,G,G,256], f16 ("f16") / f32 ("exact"), on torch's current
+        stream of that device (lmx_sam_encode)."""
+        n, h, w = self._device_frames(frames, "encode")
+        g = self.grid
+        emb = torch.empty((n, g, g, 256), dtype=self._emb_dtype(precision), device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_sam_encode(self._handle(), C.c_void_p(frames.data_ptr()), n, h, w, PLANS[precision], C.c_void_p(emb.data_ptr()), st),
+                  "lmx_sam_encode")
+        return emb
+
+    def _outputs(self, n, h, w, outputs, empty):
+        """the output arrays of one call (`empty(shape, dtype name)`), None for those of OUTPUTS the caller leaves out"""
+        unknown = set(outputs) - set(self.OUTPUTS)
+        if unknown:
+            raise LmxError(f"{type(self).__name__}: outputs {sorted(unknown)}: a subset of {self.OUTPUTS}")
+        L = 4 * self.grid
+        shapes = dict(mask=((n, h, w), "uint8"), mask_bits=((n, h, (w + 7) // 8), "uint8"), stats=((n, 8), "int64"), contour=((n, 8), "int64"),
+                      iou=((n,), "float32"), lowres=((n, L, L), "float32"))
+        return {k: (empty(*v) if k in outputs or k in ("stats", "iou") else None) for k, v in shapes.items()}
+
+    def _device_boxes(self, boxes, n, what):
+        if not (boxes.is_cuda and boxes.device == self.device and boxes.dtype == torch.float32 and tuple(boxes.shape) == (n, 4) and boxes.is_contiguous()):
+            raise LmxError(f"{type(self).__name__}.{what}: boxes must be a contiguous float32 [{n},4] tensor on {self.device}")
+        return C.c_void_p(boxes.data_ptr())
+
+    def _device_call(self, fn, name, src, n, h, w, boxes, precision, outputs):
+        dev = self.device
+        out = self._outputs(n, h, w, outputs, lambda shape, dt: torch.empty(shape, dtype=getattr(torch, dt), device=dev))
+        ptr = {k: (C.c_void_p(t.data_ptr()) if t is not None else None) for k, t in out.items()}
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            check(fn(self._handle(), C.c_void_p(src.data_ptr()), n, h, w, self._device_boxes(boxes, n, name), PLANS[precision], ptr["mask"],
+                     ptr["mask_bits"], ptr["stats"], ptr["contour"], ptr["iou"], ptr["lowres"], st), "lmx_sam_" + name)
+        return {k: t for k, t in out.items() if t is not None}
+
+    def decode(self, emb, boxes, frame_hw, precision, outputs=OUTPUTS):
+        """emb [n,G,G,256] of encode() under the same precision, boxes f32 [n,4] xyxy in frame pixels -> dict(stats int64 [n,8], iou
+        f32 [n], and of `outputs`: mask u8 [n,h,w], mask_bits u8 [n,h,ceil(w/8)], contour int64 [n,8], lowres f32 [n,4G,4G])
+        (lmx_sam_decode)."""
+        g = self.grid
+        if not (emb.is_cuda and emb.device == self.device and emb.dtype == self._emb_dtype(precision) and emb.dim() == 4
+                and tuple(emb.shape[1:]) == (g, g, 256) and emb.is_contiguous()):
+            raise LmxError(f"NativeSam.decode: emb must be a contiguous {self._emb_dtype(precision)} [n,{g},{g},256] tensor on {self.device}")
+        h, w = frame_hw
+        return self._device_call(self._lib.lmx_sam_decode, "decode", emb, emb.shape[0], int(h), int(w), boxes, precision, outputs)
+
+    def segment(self, frames, boxes, precision, outputs=OUTPUTS):
+        """u8 [n,h,w,3] device tensor and boxes f32 [n,4] -> the dict of decode() (lmx_sam_segment: encode into the handle's workspace,
+        then decode)."""
+        n, h, w = self._device_frames(frames, "segment")
+        return self._device_call(self._lib.lmx_sam_segment, "segment", frames, n, h, w, boxes, precision, outputs)
+
+    def segment_host(self, frames, boxes, precision, outputs=OUTPUTS):
+        """u8 [n,h,w,3] and f32 [n,4] numpy arrays -> the same dict of numpy arrays (lmx_sam_segment_host: uploads, segments, downloads,
+        synchronises)."""
+        a, n, h, w = self._host_frames(frames, "segment_host")
+        b = np.ascontiguousarray(boxes, dtype=np.float32)
+        if b.shape != (n, 4):
+            raise LmxError(f"NativeSam.segment_host: boxes must be a float32 [{n},4] array")
+        out = self._outputs(n, h, w, outputs, lambda shape, dt: np.empty(shape, getattr(np, dt)))
+        ptr = {k: (t.ctypes.data if t is not None else None) for k, t in out.items()}
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_sam_segment_host(self._handle(), a.ctypes.data, n, h, w, b.ctypes.data, PLANS[precision], ptr["mask"], ptr["mask_bits"],
+                                                 ptr["stats"], ptr["contour"], ptr["iou"], ptr["lowres"]), "lmx_sam_segment_host")
+        return {k: t for k, t in out.items() if t is not None}
