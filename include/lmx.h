@@ -421,6 +421,45 @@ int lmx_h_hiera_bands(const int* window, const int* q_stride, int n_blocks, int 
  * operands; a row of D elements must be a multiple of 16 bytes and 1 <= Hb <= H - 1. */
 int lmx_k_band_join(const void* band, const void* table, void* out, int dtype, int n, int H, int Hb, int W, int D,
                     lmx_stream_t stream);
+/* The Hiera encoder's block plan on the host: WHICH kernels each block runs, on which rows, and what happens at a stage end — what
+ * lmx/sam.py's hiera_plan() and HieraEncoder._settle() compute per call, for an encoder built the default way (fused MLP, ln_out
+ * projections).  These functions read no environment variable: they are the Python plan with none of the LMX_* development
+ * switches set.  Pure host arithmetic: no HIP call (csrc/host_hiera_plan.cpp; tests/test_hiera_plan_c_host.py holds every field to
+ * Python's).
+ * lmx_hiera_config_t: lmx.sam.HieraConfig — per stage s < n_stages: blocks[s], dims[s], heads[s], windows[s]; global_blocks[i],
+ * i < n_global: block indices with global attention; the first q_pool_stages stages behind stage 0 open with a pooling block.
+ * hidden, pos_bkg, fpn_dim, fpn_top_down (n_top_down entries) and eps do not enter the plan; they make the structure the whole
+ * configuration.
+ * lmx_hiera_block_t: lmx.sam.BlockPlan, field for field, the strings as the enums below (a field hiera_plan leaves None is
+ * LMX_HIERA_SHORTCUT_NONE / LMX_HIERA_QUERY_NONE), the booleans as 0 / 1. */
+enum { LMX_HIERA_MAX_STAGES = 8, LMX_HIERA_MAX_GLOBAL = 32, LMX_HIERA_MAX_BLOCKS = 256 };
+typedef struct {
+  int32_t hidden, n_stages, blocks[LMX_HIERA_MAX_STAGES], dims[LMX_HIERA_MAX_STAGES], heads[LMX_HIERA_MAX_STAGES],
+      windows[LMX_HIERA_MAX_STAGES], n_global, global_blocks[LMX_HIERA_MAX_GLOBAL], pos_bkg[2], q_pool_stages, fpn_dim, n_top_down,
+      fpn_top_down[LMX_HIERA_MAX_STAGES], image;
+  double eps;
+} lmx_hiera_config_t;
+enum { LMX_HIERA_ATTN8_LN = 0, LMX_HIERA_ATTN8 = 1, LMX_HIERA_ATTN_POOL = 2, LMX_HIERA_ATTN4 = 3, LMX_HIERA_LAUNCHES = 4 }; /* attn */
+enum { LMX_HIERA_LN1_KERNEL = 0, LMX_HIERA_LN1_PREV = 1, LMX_HIERA_LN1_LAUNCH = 2 };                                         /* ln1 */
+enum { LMX_HIERA_SHORTCUT_NONE = 0, LMX_HIERA_SHORTCUT_GEMM = 1, LMX_HIERA_SHORTCUT_GEMM_MAXPOOL = 2, LMX_HIERA_SHORTCUT_POOLED_GEMM = 3 };
+enum { LMX_HIERA_QUERY_NONE = 0, LMX_HIERA_QUERY_QKV = 1, LMX_HIERA_QUERY_QKV_MAXPOOL = 2, LMX_HIERA_QUERY_POOLED_Q_KV = 3 };
+enum { LMX_HIERA_MLP_IMG = 0, LMX_HIERA_MLP_FUSED = 1, LMX_HIERA_MLP_LAUNCHES = 2 }; /* mlp (FUSED: never chosen without a switch) */
+typedef struct {
+  int32_t H, W, Hf, Ho, Wo, Hfo, join, attn, ln1, shortcut, query, window, ln_out, mlp, emit_ln1, stage_end, keep, x16, join_out, clone;
+} lmx_hiera_block_t;
+/* *n_blocks_host = the number of blocks of `config` (the sum of blocks[s]): the length of the arrays below.  LMX_EINVAL, with the
+ * field named, for a configuration outside the limits above. */
+int lmx_h_hiera_blocks(const lmx_hiera_config_t* config, int* n_blocks_host);
+/* hiera_plan(config, n, rows, lowest): records_host[i] for n frames with block i on rows_in_host[i] token rows of the grid it reads
+ * (lmx_h_hiera_bands, or the whole grid everywhere).  Where a block has more rows than the one before it left, a join sits in front
+ * of it; fewer, or more than its grid has, is LMX_EINVAL.  lowest: stage outputs below this index are not kept. */
+int lmx_h_hiera_plan_rows(const lmx_hiera_config_t* config, int n, const int* rows_in_host, int lowest, lmx_hiera_block_t* records_host);
+/* HieraEncoder(band="blocks")._settle(nh, nw, n, lowest) for n frames resized to nh x nw: rows_host[i] = lmx_h_hiera_bands' rows,
+ * settled — the rows below the band come from the whole-grid plan of one frame, so a block in the band must run the kernels that
+ * plan chose, and one whose shape check fails on the rule's rows gets whole windows added until it passes — and records_host = the
+ * plan on those rows; where there is no band, the whole grid and its plan.  Computed per chunk from that chunk's n (the pooled
+ * GEMM's rule sees n * H * W). */
+int lmx_h_hiera_plan(const lmx_hiera_config_t* config, int n, int nh, int nw, int lowest, lmx_hiera_block_t* records_host, int* rows_host);
 
 /* ---- SAM mask decoder glue (TF:models/sam/modeling_sam.py:432-543; K18/K19) --------------------------------------- */
 /* out[r][:] = a[r][:] + b[r % b_rows][:]  (a, b f32; out f32 or f16): queries + point embeddings, keys + image PE,
@@ -663,15 +702,22 @@ int lmx_yolo_detect_host(lmx_yolo* m, const uint8_t* frames_host, int n, int h, 
  * on both precision plans (tests/test_gpu_native_sam.py).
  * The model comes from a weight image of kind SAM that lmx.native.write_sam_image(encoder, decoder, path, plans) writes (layout in
  * csrc/image.h and csrc/sam_image.h): every tensor in final device form, per plan the image holds.
- * OUT OF SCOPE, each refused or absent rather than approximated: the Hiera-B+ encoder (the image's config block carries an `encoder`
- * field so that it can be added without a format break; any kind but LMX_SAM_ENC_VIT is LMX_EINVAL), point prompts, mask-input
- * prompts and multimask output (lmx/sam_decoder.py MaskDecoder.decode serves them from Python), SamAutomaticMaskGenerator
- * (lmx/amg.py), and HIP graph capture of these calls.
+ * A weight image whose encoder is Hiera (write_sam_image on a lmx.sam.HieraEncoder; Hiera-B+ is BASELINE's headline configuration) is
+ * served by the same calls (csrc/sam_hiera_model.h): lmx_sam_encode is then the launch sequence of HieraEncoder(band="blocks").encode(
+ * frames, outputs="embedding")["fpn"][2] over the block plan lmx_h_hiera_plan computes per chunk, the embedding is f16 under BOTH
+ * precisions (the trunk has one plan; `precision` selects the decoder plan and is checked against the image's plans mask), and
+ * lmx_sam_prepare also builds, once per resized geometry and shared by both plans, the table of the token rows below the band that
+ * depends on the frame (tests/test_gpu_native_sam_hiera.py).  lmx_sam_info_t of a Hiera image: encoder LMX_SAM_ENC_HIERA, hidden =
+ * dims[0], heads = heads[0], layers = the number of blocks, mlp = 0, window = windows[0], patch = 16 (so that G = image / patch), image,
+ * plans, max_batch.
+ * OUT OF SCOPE, each refused or absent rather than approximated: point prompts, mask-input prompts and multimask output
+ * (lmx/sam_decoder.py MaskDecoder.decode serves them from Python), SamAutomaticMaskGenerator (lmx/amg.py), outputs="all" of the Hiera
+ * encoder (the high-resolution FPN levels and the stage outputs), and HIP graph capture of these calls.
  * Handle, image and error conventions as for lmx_yolo: the handle belongs to the device current at open; ONE host thread and ONE
  * stream in flight per handle; several handles are independent; LMX_EINVAL / LMX_EHIP with lmx_last_error(). */
 typedef struct lmx_sam lmx_sam;
 enum { LMX_SAM_F16 = 0, LMX_SAM_EXACT = 1 }; /* `precision`; lmx_sam_info_t.plans has bit (1 << precision) for each plan the image holds */
-enum { LMX_SAM_ENC_VIT = 0 };                /* lmx_sam_info_t.encoder */
+enum { LMX_SAM_ENC_VIT = 0, LMX_SAM_ENC_HIERA = 2 }; /* lmx_sam_info_t.encoder (1 is no encoder's and is refused) */
 typedef struct { int32_t encoder, hidden, heads, layers, mlp, window, patch, image, plans, max_batch; } lmx_sam_info_t;
 /* HOST only, touches no GPU (`sam_model_registry[...](checkpoint=...)` behind services/sam3-pipeline/app/main.py:74-92, the checking
  * half): parse and validate an image — magic, version, kind, sizes against the real file, the config block, every tensor the
@@ -699,7 +745,7 @@ int lmx_sam_resized(const lmx_sam* m, int h, int w, int* nh_host, int* nw_host);
 int lmx_sam_prepare(lmx_sam* m, int h, int w, int precision);
 /* `predictor.set_image(frame)` of services/sam3-pipeline/app/main.py:74-92 for n frames: frames u8 [n][h][w][3], consumed in the
  * channel order given (the service hands over its BGR frame; no swap) -> emb [n][G][G][out_ch], G = image / patch: f16 under
- * LMX_SAM_F16, f32 under LMX_SAM_EXACT = SamVitEncoder.encode(frames, precision)["fpn"][2].  Enqueue-only after lmx_sam_prepare, as
+ * LMX_SAM_F16, f32 under LMX_SAM_EXACT = SamVitEncoder.encode(frames, precision)["fpn"][2]; f16 under both for a Hiera image.  Enqueue-only after lmx_sam_prepare, as
  * lmx_sam_segment. */
 int lmx_sam_encode(lmx_sam* m, const uint8_t* frames, int n, int h, int w, int precision, void* emb, lmx_stream_t stream);
 /* `predictor.predict(box=..., multimask_output=False)` of services/sam3-pipeline/app/main.py:74-92 on n embeddings of lmx_sam_encode

@@ -1,6 +1,7 @@
 // sam.hip — SAM / Hiera pieces that are not GEMM- or attention-shaped (SURVEY.md K9, K10 im2col, K15 Q-pool).
 // HBM-bound element work, one pass, 16-byte stores.
 #include "common.h"
+#include "hiera_bands.h"
 
 namespace {
 
@@ -435,37 +436,16 @@ extern "C" int lmx_h_hiera_band(const int* window, const int* q_stride, int n_bl
   return LMX_OK;
 }
 
-// The same band sized block by block (include/lmx.h): `d` rows of the grid block i reads carry a pixel's influence; the block runs
-// on the whole windows (and whole pooled pairs) that cover them and hands those rows on, halved where it pools.  Host arithmetic only.
+// The same band sized block by block (include/lmx.h); the arithmetic is hiera_bands.h's, which the block plan shares
+// (host_hiera_plan.cpp).  Host arithmetic only.
 extern "C" int lmx_h_hiera_bands(const int* window, const int* q_stride, int n_blocks, int grid, int nh, int nw, int* rows) {
   LMX_REQUIRE(window && q_stride && rows, "lmx_h_hiera_bands: null pointer");
   LMX_REQUIRE(n_blocks > 0 && grid > 0 && grid <= (1 << 20) && nh > 0 && nw > 0 && nh <= 4 * grid && nw <= 4 * grid,
               "lmx_h_hiera_bands: n_blocks=%d grid=%d nh=%d nw=%d", n_blocks, grid, nh, nw);
-  int first_global = -1;
-  for (int i = 0; i < n_blocks; ++i) {
+  for (int i = 0; i < n_blocks; ++i)
     LMX_REQUIRE(window[i] >= 0 && window[i] <= (1 << 20) && (q_stride[i] == 0 || q_stride[i] == 1 || q_stride[i] == 2),
                 "lmx_h_hiera_bands: block %d: window=%d q_stride=%d", i, window[i], q_stride[i]);
-    if (window[i] == 0 && first_global < 0) first_global = i;
-  }
-  // padding on the right, block 0 global, or no global block: no band (lmx_h_hiera_band's cases of 0)
-  const bool whole = nw < 4 * grid || first_global <= 0;
-  int64_t g = grid;                                         // rows of the grid block i reads
-  int64_t d = (nh + 2) / 4 + 1 < g ? (nh + 2) / 4 + 1 : g;  // token row r reads pixel rows 4 r - 3 .. 4 r + 3
-  for (int i = 0; i < n_blocks; ++i) {
-    const bool pools = q_stride[i] == 2;
-    if (whole || i >= first_global) {
-      d = g;
-    } else {
-      const int64_t piece = window[i] % 2 == 0 || !pools ? window[i] : 2 * (int64_t)window[i];  // whole windows, an even count where it pools
-      d = (d + piece - 1) / piece * piece;
-      if (d >= g) d = g;
-    }
-    rows[i] = (int)d;
-    if (pools) {
-      d /= 2;
-      g /= 2;
-    }
-  }
+  lmx_hiera_bands_rows(window, q_stride, n_blocks, grid, nh, nw, rows);
   return LMX_OK;
 }
 

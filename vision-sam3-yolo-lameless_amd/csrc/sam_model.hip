@@ -7,8 +7,10 @@
 // fills it, in the Python plan's order, so the outputs are the Python plan's bit for bit on both precision plans
 // (tests/test_gpu_native_sam.py).  What is torch glue in Python — torch.cat of the output tokens with the sparse prompt, the q / k / v
 // slices of qkv, q3[:, k].contiguous(), iou[:, 0] — is a leading dimension or a strided copy on the call's stream here.
-// OUT OF SCOPE: the Hiera-B+ encoder (the image's `encoder` field leaves room for it), point and mask-input prompts, multimask
-// output, SamAutomaticMaskGenerator, HIP graph capture.
+// An image whose encoder is Hiera runs sam_hiera_model.h's launch plan in place of the ViT's (encode_chunk branches after the resize);
+// its embedding is f16 under both plans, which the exact decoder's first lmx_k_add_bcast takes as such.
+// OUT OF SCOPE: point and mask-input prompts, multimask output, SamAutomaticMaskGenerator, outputs="all" of the Hiera encoder, HIP
+// graph capture.
 #include <math.h>
 #include <string.h>
 
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "model_handle.h"
+#include "sam_hiera_model.h"
 #include "sam_image.h"
 
 namespace {
@@ -75,6 +78,10 @@ struct Prepared {
   void *qq, *kk, *qc16, *kc16, *tok16, *pq, *pk, *pv, *pa, *hh, *u1n, *u2, *t1, *t2, *x3;
   uint8_t* mask;
   void* contour_ws;  // null: the frame size is outside lmx_k_contour_features' range
+  // encoder Hiera: the two arenas of HieraRun with their sizes, and the geometry's band table (null: no band)
+  char *h_stream, *h_scratch;
+  size_t h_stream_cap, h_scratch_cap;
+  const HieraBandTable* table;
 };
 
 }  // namespace
@@ -90,12 +97,16 @@ struct lmx_sam : LmxHandleCore {
   DecPlan dec[2];
   Norm ln_final, up_ln;
   std::map<std::tuple<int, int, int>, Prepared> prepared;
+  HieraW hiera;                                                // encoder Hiera
+  std::map<std::pair<int, int>, HieraBandTable> band_tables;  // ... per resized geometry (nh, nw), shared by both plans
+  bool is_hiera() const { return cfg.encoder == LMX_SAM_ENC_HIERA; }
 };
 
 namespace {
 
 void destroy(lmx_sam* m) {
   for (auto& kv : m->prepared) (void)hipFree(kv.second.blob);
+  for (auto& kv : m->band_tables) (void)hipFree(kv.second.blob);
   lmx_handle_free(m);
   delete m;
 }
@@ -111,6 +122,30 @@ int open_into(lmx_sam* m, const char* path) {
   auto f32 = [&](const LmxTensorRef& r) { return static_cast<const float*>(at(r)); };
   auto norm = [&](const LmxSamNorm& n) { return Norm{f32(n.g), f32(n.b)}; };
   const int D = c.hidden, I = c.mlp, Kp = c.patch * c.patch * 3, C = c.out_ch;
+  m->lut = f32(img.lut);
+  if (m->is_hiera()) {
+    HieraW& W = m->hiera;
+    W.cfg = c.hiera;
+    W.n_blocks = (int)img.hiera_blocks.size();
+    W.pe_w = at(img.pe_w);
+    W.pe_b = f32(img.pe_b);
+    W.pos = f32(img.pos);
+    auto f16 = [&](const LmxTensorRef& r) { return static_cast<const half_t*>(at(r)); };
+    for (int i = 0; i < W.n_blocks; ++i) {
+      const LmxHieraBlockRefs& r = img.hiera_blocks[(size_t)i];
+      HieraBlockW B;
+      B.shape = r.shape;
+      B.fused = r.fused;
+      if (r.shape.win == 0 && W.first_global < 0) W.first_global = i;
+      B.g1 = f32(r.g1), B.b1 = f32(r.b1), B.bqkv = f32(r.bqkv), B.bo = f32(r.bo), B.g2 = f32(r.g2), B.b2 = f32(r.b2), B.bb1 = f32(r.bb1), B.bb2 = f32(r.bb2);
+      B.bp = f32(r.bp);
+      B.wqkv = f16(r.wqkv), B.padkv = f16(r.padkv), B.wo = f16(r.wo), B.w1 = f16(r.w1), B.w2 = f16(r.w2), B.wp = f16(r.wp);
+      for (int j = 0; j < 4; ++j) B.attn[j] = at(r.attn[j]);
+      for (int j = 0; j < 2; ++j) B.mlp_img[j] = at(r.mlp_img[j]);
+      W.blocks.push_back(B);
+    }
+    for (int s = 0; s < LMX_HIERA_MAX_STAGES; ++s) W.neck_w[s] = at(img.neck_w[s]), W.neck_b[s] = f32(img.neck_b[s]);
+  }
   m->pe[LMX_SAM_F16] = Lin{at(img.pe_w), f32(img.pe_b), nullptr, D, Kp};
   m->pe[LMX_SAM_EXACT] = Lin{at(img.x_pe), f32(img.pe_b), nullptr, D, Kp};
   m->n1[LMX_SAM_F16] = Lin{at(img.n1_w), nullptr, nullptr, C, D};
@@ -122,7 +157,7 @@ int open_into(lmx_sam* m, const char* path) {
   m->lut = f32(img.lut);
   m->n1_ln = Norm{f32(img.n1_g), f32(img.n1_b)};
   m->n2_ln = Norm{f32(img.n2_g), f32(img.n2_b)};
-  for (int i = 0; i < c.layers; ++i) {
+  for (int i = 0; i < (m->is_hiera() ? 0 : c.layers); ++i) {
     const LmxSamLayerRefs& r = img.layers[(size_t)i];
     EncLayer L;
     L.glob = c.is_global(i);
@@ -211,6 +246,128 @@ struct Sizer {
   }
 };
 
+// ---- encoder Hiera ---------------------------------------------------------------------------------------------------------------
+// the plan of a chunk of n frames resized to nh x nw, as HieraEncoder(band="blocks").encode(outputs="embedding") computes it
+int hiera_plan_of(const lmx_sam* m, const char* fn, int n, int nh, int nw, std::vector<lmx_hiera_block_t>* plan, std::vector<int>* rows) {
+  const HieraW& W = m->hiera;
+  plan->assign((size_t)W.n_blocks, lmx_hiera_block_t());
+  rows->assign((size_t)W.n_blocks, 0);
+  LMX_TRY(lmx_h_hiera_plan(&W.cfg, n, nh, nw, 2, plan->data(), rows->data()));
+  for (int i = 0; i < W.n_blocks; ++i)
+    LMX_REQUIRE(!(*plan)[(size_t)i].join_out, "%s: block %d ends a kept stage inside the band (the first global block lies behind the embedding's stage): not served",
+                fn, i);
+  return LMX_OK;
+}
+
+// one counting pass: the arenas' peaks for a plan
+int hiera_count(const lmx_sam* m, const char* fn, const lmx_hiera_block_t* plan, int n, const HieraBandTable* table, int stop_at, const int* have,
+                const int* need, size_t* stream, size_t* scratch) {
+  HieraRun R;
+  R.fn = fn;
+  LMX_TRY(hiera_trunk(R, m->hiera, plan, nullptr, n, table, nullptr, stop_at, have, need, nullptr));
+  if (R.stream.peak > *stream) *stream = R.stream.peak;
+  if (R.scratch.peak > *scratch) *scratch = R.scratch.peak;
+  return LMX_OK;
+}
+
+// HieraEncoder._band_table for the rows `rows` of a geometry: ONE whole-grid pass of one frame up to the last block with a join in
+// front, keeping rows [have, need) of the stream entering each such block.  The rows it keeps do not depend on the frame's content
+// (no pixel reaches them), so the frame is all zeros.  The pass has buffers of its own, freed when it is done.  SYNCHRONOUS.
+int hiera_build_table(lmx_sam* m, int nh, int nw, const std::vector<lmx_hiera_block_t>& band, const std::vector<int>& rows, HieraBandTable* T) {
+  const HieraW& W = m->hiera;
+  const int nb = W.n_blocks, g = W.cfg.image / 4;
+  std::vector<int> whole_rows((size_t)nb), have((size_t)nb, 0), need((size_t)nb, 0);
+  std::vector<lmx_hiera_block_t> whole((size_t)nb);
+  for (int i = 0, r = g; i < nb; ++i) {
+    whole_rows[(size_t)i] = r;
+    if (W.blocks[(size_t)i].shape.qs) r /= 2;
+  }
+  LMX_TRY(lmx_h_hiera_plan_rows(&W.cfg, 1, whole_rows.data(), 2, whole.data()));
+  int stop_at = -1;
+  LmxLayout lay;
+  std::vector<size_t> offs((size_t)nb, 0);
+  for (int i = 0; i < nb; ++i)
+    if (band[(size_t)i].join) {
+      have[(size_t)i] = band[(size_t)i].join;
+      need[(size_t)i] = band[(size_t)i].H;
+      offs[(size_t)i] = lay.add((size_t)(need[(size_t)i] - have[(size_t)i]) * band[(size_t)i].W * W.blocks[(size_t)i].shape.dim * 4);
+      stop_at = i;
+    }
+  LMX_REQUIRE(stop_at >= 0, "lmx_sam_prepare: a band without a join");
+  size_t stream = 0, scratch = 0;
+  LMX_TRY(hiera_count(m, "lmx_sam_prepare", whole.data(), 1, nullptr, stop_at, have.data(), need.data(), &stream, &scratch));
+  const int64_t patch_bytes = (int64_t)g * g * HIERA_KPAD_COLS * 2;
+  LMX_REQUIRE(patch_bytes < MAX_BUFFER_BYTES, "lmx_sam_prepare: buffer 'patches of the table pass' has %lld bytes, the kernels index below 2 GB",
+              (long long)patch_bytes);
+  LmxLayout tmp;
+  const size_t o_frame = tmp.add((size_t)nh * nw * 3), o_patches = tmp.add((size_t)patch_bytes), o_stream = tmp.add(stream), o_scratch = tmp.add(scratch);
+  char *work = nullptr, *blob = nullptr;
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&blob), lay.total));
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&work), tmp.total);
+  int rc = LMX_OK;
+  if (e == hipSuccess) e = hipMemset(work + o_frame, 0, (size_t)nh * nw * 3);
+  if (e == hipSuccess) {
+    std::vector<float*> taps((size_t)nb, nullptr);
+    for (int i = 0; i < nb; ++i)
+      if (need[(size_t)i]) taps[(size_t)i] = reinterpret_cast<float*>(blob + offs[(size_t)i]);
+    HieraRun R;
+    R.launch = true;
+    R.fn = "lmx_sam_prepare";
+    R.stream.base = work + o_stream, R.stream.cap = stream;
+    R.scratch.base = work + o_scratch, R.scratch.cap = scratch;
+    R.st = nullptr;
+    rc = lmx_k_im2col_u8(reinterpret_cast<const uint8_t*>(work + o_frame), m->lut, work + o_patches, 1, nh, nw, W.cfg.image, W.cfg.image, 7, 7, 4, 3,
+                         HIERA_KPAD_COLS, nullptr);
+    if (rc == LMX_OK) rc = hiera_trunk(R, W, whole.data(), work + o_patches, 1, nullptr, nullptr, stop_at, have.data(), need.data(), taps.data());
+    e = hipDeviceSynchronize();
+  }
+  (void)hipFree(work);
+  if (e != hipSuccess || rc != LMX_OK) {
+    (void)hipFree(blob);
+    if (rc != LMX_OK) return rc;
+    LMX_HIP(e);
+  }
+  T->blob = blob;
+  T->rows = rows;
+  T->x.assign((size_t)nb, nullptr);
+  for (int i = 0; i < nb; ++i)
+    if (need[(size_t)i]) T->x[(size_t)i] = reinterpret_cast<const float*>(blob + offs[(size_t)i]);
+  return LMX_OK;
+}
+
+// what lmx_sam_prepare adds for a Hiera handle: P->table, the arenas' sizes, and the bytes of the patch matrix
+int hiera_prepare(lmx_sam* m, int nh, int nw, Prepared* P, int64_t* patch_bytes) {
+  const HieraW& W = m->hiera;
+  const int g = W.cfg.image / 4;
+  std::vector<lmx_hiera_block_t> plan;
+  std::vector<int> rows;
+  LMX_TRY(hiera_plan_of(m, "lmx_sam_prepare", m->max_batch, nh, nw, &plan, &rows));
+  *patch_bytes = (int64_t)m->max_batch * rows[0] * g * HIERA_KPAD_COLS * 2;
+  size_t stream = 0, scratch = 0;
+  LMX_TRY(hiera_count(m, "lmx_sam_prepare", plan.data(), m->max_batch, nullptr, -1, nullptr, nullptr, &stream, &scratch));
+  if (m->max_batch > 1) {  // the last chunk of a call may be any size; the pooled GEMM's rule sees it
+    std::vector<int> rows1;
+    LMX_TRY(hiera_plan_of(m, "lmx_sam_prepare", 1, nh, nw, &plan, &rows1));
+    LMX_REQUIRE(rows1 == rows, "lmx_sam_prepare: the band's rows depend on the batch size for a %d x %d frame: not served", nh, nw);
+    LMX_TRY(hiera_count(m, "lmx_sam_prepare", plan.data(), 1, nullptr, -1, nullptr, nullptr, &stream, &scratch));
+  }
+  P->h_stream_cap = stream;
+  P->h_scratch_cap = scratch;
+  // (the table last: a workspace refused above costs no pass on the device)
+  P->table = nullptr;
+  if (rows[0] < g) {
+    const auto key = std::make_pair(nh, nw);
+    auto it = m->band_tables.find(key);
+    if (it == m->band_tables.end()) {  // (a geometry seen under the other plan: a lookup)
+      HieraBandTable T;
+      LMX_TRY(hiera_build_table(m, nh, nw, plan, rows, &T));
+      it = m->band_tables.emplace(key, T).first;
+    }
+    P->table = &it->second;
+  }
+  return LMX_OK;
+}
+
 int prepare(lmx_sam* m, int h, int w, int precision, const Prepared** out) {
   const auto key = std::make_tuple(h, w, precision);
   const auto it = m->prepared.find(key);
@@ -231,9 +388,14 @@ int prepare(lmx_sam* m, int h, int w, int precision, const Prepared** out) {
   LMX_TRY(pil_axis(w, nw, &bh, &kh, &P.ksize_h));
   LMX_TRY(pil_axis(h, nh, &bv, &kv, &P.ksize_v));
 
-  const bool exact = precision == LMX_SAM_EXACT;
+  const bool exact = precision == LMX_SAM_EXACT, hiera = m->is_hiera();
+  // encoder Hiera: the band table of this geometry (built once, shared by both plans), the patches of the band's top rows and the
+  // two arenas of the trunk, counted over the plans of a full chunk and of a single frame
+  int64_t h_patches = 0;
+  if (hiera) LMX_TRY(hiera_prepare(m, nh, nw, &P, &h_patches));
   const int64_t B = m->max_batch, D = c.hidden, I = c.mlp, H = c.heads, g = c.grid(), gg = g * g, Kp = c.patch * c.patch * 3, C = c.out_ch, ws = c.window;
   const int64_t nW = ((g + ws - 1) / ws) * ((g + ws - 1) / ws), e = exact ? 4 : 2, L = 4 * g;
+  const int64_t v = hiera ? 0 : 1;  // the ViT encoder's buffers: none for Hiera, whose embedding is f16 under both plans
   int64_t rel = 0;
   for (const EncLayer& l : m->layers) {
     const int64_t r = l.glob ? B * H * gg * 2 * g * 2 : B * nW * H * ws * ws * 2 * ws * 2;
@@ -264,17 +426,17 @@ int prepare(lmx_sam* m, int h, int w, int precision, const Prepared** out) {
   const std::vector<Want> wants = {
       {vp(&P.tmp_h), "frame after the horizontal resize", nw != w ? B * h * nw * 3 : 0},
       {vp(&P.tmp_v), "resized frame", nh != h ? B * nh * nw * 3 : 0},
-      {vp(&P.patches), "patches", B * gg * Kp * 2},
-      {vp(&P.x), "residual stream", B * gg * D * 4},
-      {vp(&P.h), "LayerNorm rows", B * gg * D * 2},
-      {vp(&P.qkv), "qkv", B * gg * 3 * D * 2},
-      {vp(&P.a), "attention output", B * gg * D * 2},
-      {vp(&P.u), "MLP hidden", B * gg * I * 2},
-      {vp(&P.rel), "relative-position tables", rel},
-      {vp(&P.y32), "neck 1x1 output", B * gg * C * 4},
-      {vp(&P.y16), "neck LayerNorm rows", B * gg * C * 2},
-      {vp(&P.acc), "neck 3x3 output", B * gg * C * 4},
-      {vp(&P.emb), "image embedding", B * gg * C * e},
+      {vp(&P.patches), "patches", hiera ? h_patches : B * gg * Kp * 2},
+      {vp(&P.x), "residual stream", v * B * gg * D * 4},
+      {vp(&P.h), "LayerNorm rows", v * B * gg * D * 2},
+      {vp(&P.qkv), "qkv", v * B * gg * 3 * D * 2},
+      {vp(&P.a), "attention output", v * B * gg * D * 2},
+      {vp(&P.u), "MLP hidden", v * B * gg * I * 2},
+      {vp(&P.rel), "relative-position tables", v * rel},
+      {vp(&P.y32), "neck 1x1 output", v * B * gg * C * 4},
+      {vp(&P.y16), "neck LayerNorm rows", v * B * gg * C * 2},
+      {vp(&P.acc), "neck 3x3 output", v * B * gg * C * 4},
+      {vp(&P.emb), "image embedding", B * gg * C * (hiera ? 2 : e)},
       {vp(&P.tokens), "tokens", B * DT * DD * 4},
       {vp(&P.sparse), "sparse prompt", B * 2 * DD * 4},
       {vp(&P.qa), "queries", B * DT * DD * 4},
@@ -306,7 +468,11 @@ int prepare(lmx_sam* m, int h, int w, int precision, const Prepared** out) {
   };
   std::vector<size_t> offs(wants.size());
   for (size_t i = 0; i < wants.size(); ++i) LMX_TRY(z.add(wants[i].what, wants[i].bytes, &offs[i]));
+  // (the arenas hold many buffers, each checked against 2 GB where it is taken: HieraRun)
+  const size_t o_stream = z.lay.add(P.h_stream_cap), o_scratch = z.lay.add(P.h_scratch_cap);
   LMX_TRY(lmx_alloc_and_upload(z.lay.total, up, 4, &P.blob));
+  P.h_stream = P.blob + o_stream;
+  P.h_scratch = P.blob + o_scratch;
   for (size_t i = 0; i < wants.size(); ++i) *wants[i].ptr = wants[i].bytes ? P.blob + offs[i] : nullptr;
   if (nw != w) {
     P.bounds_h = reinterpret_cast<int32_t*>(P.blob + o_bh);
@@ -362,6 +528,25 @@ int neck_conv(const void* x, const void* w, void* out, int out_dtype, const void
   return lmx_k_gemm(&d, st);
 }
 
+// HieraEncoder(band="blocks").encode(frames, outputs="embedding")["fpn"][2] for n <= max_batch frames: emb f16 [n, 64, 64, fpn_dim]
+int hiera_encode_chunk(const lmx_sam* m, const Prepared& P, const uint8_t* img, int n, void* emb, hipStream_t st) {
+  const HieraW& W = m->hiera;
+  const int S = W.cfg.image, g = S / 4;
+  std::vector<lmx_hiera_block_t> plan;
+  std::vector<int> rows;
+  LMX_TRY(hiera_plan_of(m, "lmx_sam_encode", n, P.nh, P.nw, &plan, &rows));
+  const bool band = rows[0] < g;
+  LMX_REQUIRE(!band || (P.table && P.table->rows == rows), "lmx_sam_encode: the band's rows for %d frames are not those the table was prepared for", n);
+  LMX_TRY(lmx_k_im2col_u8(img, m->lut, P.patches, n, P.nh, P.nw, band ? 4 * rows[0] : S, S, 7, 7, 4, 3, HIERA_KPAD_COLS, st));
+  HieraRun R;
+  R.launch = true;
+  R.fn = "lmx_sam_encode";
+  R.stream.base = P.h_stream, R.stream.cap = P.h_stream_cap;
+  R.scratch.base = P.h_scratch, R.scratch.cap = P.h_scratch_cap;
+  R.st = st;
+  return hiera_trunk(R, W, plan.data(), P.patches, n, band ? P.table : nullptr, emb, -1, nullptr, nullptr, nullptr);
+}
+
 // SamVitEncoder.preprocess + embed for n <= max_batch frames: emb f16 (f16 plan) / f32 (exact plan) [n, g, g, out_ch]
 int encode_chunk(const lmx_sam* m, const Prepared& P, int precision, const uint8_t* frames, int n, int h, int w, void* emb, hipStream_t st) {
   const LmxSamCfg& c = m->cfg;
@@ -377,6 +562,7 @@ int encode_chunk(const lmx_sam* m, const Prepared& P, int precision, const uint8
     LMX_TRY(lmx_k_pil_resize_v(img, P.tmp_v, n, h, P.nh, P.nw, P.bounds_v, P.kk_v, P.ksize_v, st));
     img = P.tmp_v;
   }
+  if (m->is_hiera()) return hiera_encode_chunk(m, P, img, n, emb, st);
   LMX_TRY(lmx_k_im2col_u8(img, m->lut, P.patches, n, P.nh, P.nw, c.image, c.image, c.patch, c.patch, c.patch, 0, Kp, st));
   LMX_TRY(enc_lin(precision, P.patches, m->pe[precision], P.x, LMX_F32, rows, LMX_ACT_NONE, m->pos, gg, st));
   half_t* qkv = static_cast<half_t*>(P.qkv);
@@ -585,7 +771,7 @@ struct Dec {
       a = b;
       b = t;
     };
-    LMX_TRY(add(emb, LMX_F32, m->no_mask, 1, keys, LMX_F32, nP));
+    LMX_TRY(add(emb, m->is_hiera() ? LMX_F16 : LMX_F32, m->no_mask, 1, keys, LMX_F32, nP));  // (a Hiera embedding is f16 under both plans)
     for (int i = 0; i < 2; ++i) {
       const DecLayer& L = W.L[i];
       if (i == 0) {
@@ -707,7 +893,7 @@ extern "C" int lmx_sam_encode(lmx_sam* m, const uint8_t* frames, int n, int h, i
   const Prepared* P = nullptr;
   LMX_TRY(prepare(m, h, w, precision, &P));  // a pair seen before: a lookup
   const size_t frame_bytes = (size_t)h * w * 3, g = (size_t)m->cfg.grid();
-  const size_t emb_bytes = g * g * m->cfg.out_ch * (precision == LMX_SAM_EXACT ? 4 : 2);
+  const size_t emb_bytes = g * g * m->cfg.out_ch * (precision == LMX_SAM_EXACT && !m->is_hiera() ? 4 : 2);
   for (int done = 0; done < n; done += m->max_batch) {
     const int nb = n - done < m->max_batch ? n - done : m->max_batch;
     LMX_TRY(encode_chunk(m, *P, precision, frames + (size_t)done * frame_bytes, nb, h, w, static_cast<char*>(emb) + (size_t)done * emb_bytes, st));
@@ -719,7 +905,7 @@ extern "C" int lmx_sam_encode(lmx_sam* m, const uint8_t* frames, int n, int h, i
 static int run(lmx_sam* m, const Prepared& P, const uint8_t* frames, const void* emb, int n, int h, int w, const float* boxes, int precision,
                uint8_t* mask, uint8_t* mask_bits, int64_t* stats, int64_t* contour, float* iou, float* lowres, hipStream_t st) {
   const size_t frame_bytes = (size_t)h * w * 3, g = (size_t)m->cfg.grid(), px = (size_t)h * w, wb = (size_t)(w + 7) / 8, LL = 16 * g * g;
-  const size_t emb_bytes = g * g * m->cfg.out_ch * (precision == LMX_SAM_EXACT ? 4 : 2);
+  const size_t emb_bytes = g * g * m->cfg.out_ch * (precision == LMX_SAM_EXACT && !m->is_hiera() ? 4 : 2);
   for (int done = 0; done < n; done += m->max_batch) {
     const int nb = n - done < m->max_batch ? n - done : m->max_batch;
     const size_t d = (size_t)done;

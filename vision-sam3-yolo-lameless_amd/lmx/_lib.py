@@ -39,6 +39,19 @@ class SamInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("encoder", "hidden", "heads", "layers", "mlp", "window", "patch", "image", "plans", "max_batch")]
 
 
+class HieraConfig(C.Structure):  # lmx_hiera_config_t
+    MAX_STAGES, MAX_GLOBAL, MAX_BLOCKS = 8, 32, 256
+    _fields_ = [("hidden", C.c_int32), ("n_stages", C.c_int32), ("blocks", C.c_int32 * 8), ("dims", C.c_int32 * 8), ("heads", C.c_int32 * 8),
+                ("windows", C.c_int32 * 8), ("n_global", C.c_int32), ("global_blocks", C.c_int32 * 32), ("pos_bkg", C.c_int32 * 2),
+                ("q_pool_stages", C.c_int32), ("fpn_dim", C.c_int32), ("n_top_down", C.c_int32), ("fpn_top_down", C.c_int32 * 8),
+                ("image", C.c_int32), ("eps", C.c_double)]
+
+
+class HieraBlock(C.Structure):  # lmx_hiera_block_t: lmx.sam.BlockPlan's fields in its order
+    _fields_ = [(n, C.c_int32) for n in ("H", "W", "Hf", "Ho", "Wo", "Hfo", "join", "attn", "ln1", "shortcut", "query", "window", "ln_out", "mlp",
+                                         "emit_ln1", "stage_end", "keep", "x16", "join_out", "clone")]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -103,6 +116,9 @@ SIGNATURES = {
     "lmx_h_hiera_band": (_I, [C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "lmx_h_hiera_bands": (_I, [C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "lmx_k_band_join": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
+    "lmx_h_hiera_blocks": (_I, [C.POINTER(HieraConfig), C.POINTER(C.c_int)]),
+    "lmx_h_hiera_plan_rows": (_I, [C.POINTER(HieraConfig), _I, C.POINTER(C.c_int), _I, C.POINTER(HieraBlock)]),
+    "lmx_h_hiera_plan": (_I, [C.POINTER(HieraConfig), _I, _I, _I, _I, C.POINTER(HieraBlock), C.POINTER(C.c_int)]),
     "lmx_k_add_bcast":(_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _I, _I64, _I64, _I, _VP]),
     "lmx_h_mask_features": (_I, [_VP, _I, _I, _VP]),
     "lmx_h_iou_matrix": (_I, [_VP, _I, _VP, _I, _VP]),

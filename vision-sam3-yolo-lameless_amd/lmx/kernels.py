@@ -249,6 +249,49 @@ def hiera_bands(windows, q_strides, grid, nh, nw):
     return tuple(rows)
 
 
+def _hiera_config(cfg):
+    """lmx.sam.HieraConfig -> lmx_hiera_config_t."""
+    c = _lib.HieraConfig()
+    ns = len(cfg.blocks)
+    if not (len(cfg.dims) == len(cfg.heads) == len(cfg.windows) == ns) or ns > c.MAX_STAGES or len(cfg.global_blocks) > c.MAX_GLOBAL \
+            or len(cfg.fpn_top_down) > c.MAX_STAGES or len(cfg.pos_bkg) != 2:
+        raise LmxError(f"hiera plan: a configuration of {ns} stages, {len(cfg.global_blocks)} global blocks does not fit lmx_hiera_config_t")
+    c.hidden, c.n_stages, c.n_global, c.q_pool_stages, c.fpn_dim, c.n_top_down, c.image, c.eps = \
+        cfg.hidden, ns, len(cfg.global_blocks), cfg.q_pool_stages, cfg.fpn_dim, len(cfg.fpn_top_down), cfg.image, cfg.eps
+    for name in ("blocks", "dims", "heads", "windows", "global_blocks", "pos_bkg", "fpn_top_down"):
+        for i, v in enumerate(getattr(cfg, name)):
+            getattr(c, name)[i] = v
+    return c
+
+
+def _hiera_records(recs):
+    return [tuple(getattr(r, f) for f, _ in _lib.HieraBlock._fields_) for r in recs]
+
+
+def hiera_plan_rows_host(cfg, n, rows, lowest=0):
+    """lmx_h_hiera_plan_rows (include/lmx.h): lmx.sam.hiera_plan(cfg, n, rows, lowest=lowest) of the default encoder as computed in C,
+    one tuple of integers per block in lmx.sam.BlockPlan's field order (lmx.sam.native_plan turns them into BlockPlans)."""
+    c = _hiera_config(cfg)
+    nb = C.c_int(0)
+    check(_lib.load().lmx_h_hiera_blocks(C.byref(c), C.byref(nb)), "lmx_h_hiera_blocks")
+    if len(rows) != nb.value:
+        raise LmxError(f"hiera_plan_rows_host: {len(rows)} row counts for {nb.value} blocks")
+    recs = (_lib.HieraBlock * nb.value)()
+    check(_lib.load().lmx_h_hiera_plan_rows(C.byref(c), n, (C.c_int * nb.value)(*rows), lowest, recs), "lmx_h_hiera_plan_rows")
+    return _hiera_records(recs)
+
+
+def hiera_plan_host(cfg, n, nh, nw, lowest=0):
+    """lmx_h_hiera_plan (include/lmx.h): (the settled rows per block for n frames resized to nh x nw, the plan on them as tuples of
+    integers as in hiera_plan_rows_host) — what HieraEncoder(band="blocks")._settle computes, in C."""
+    c = _hiera_config(cfg)
+    nb = C.c_int(0)
+    check(_lib.load().lmx_h_hiera_blocks(C.byref(c), C.byref(nb)), "lmx_h_hiera_blocks")
+    recs, rows = (_lib.HieraBlock * nb.value)(), (C.c_int * nb.value)()
+    check(_lib.load().lmx_h_hiera_plan(C.byref(c), n, nh, nw, lowest, recs, rows), "lmx_h_hiera_plan")
+    return tuple(rows), _hiera_records(recs)
+
+
 def band_join(band, table, H):
     """[n, H, W, D]: rows < Hb of each image from band [n, Hb, W, D], rows >= Hb from table [(H - Hb) * W, D], the same for every
     image (lmx_k_band_join).  f16 or f32, contiguous."""

@@ -173,7 +173,7 @@ def check_yolo_image(path):
 
 
 # ---- the SAM weight image (csrc/sam_image.h) -------------------------------------------------------------------------------
-SAM_ENC_VIT = 0  # LMX_SAM_ENC_VIT: the config block's `encoder` field (the Hiera encoder has no image yet)
+SAM_ENC_VIT, SAM_ENC_HIERA = 0, 2  # LMX_SAM_ENC_*: the config block's `encoder` field (1 is no encoder's)
 _SAM_ATTN = {"sa": "self_attn", "t2i": "cross_attn_token_to_image", "i2t": "cross_attn_image_to_token"}
 _SAM_PROJ = {"q": "q_proj", "k": "k_proj", "v": "v_proj", "o": "out_proj"}
 _SAM_FFN = {"in": "proj_in", "mid": "layers.0", "out": "proj_out"}
@@ -248,6 +248,85 @@ def sam_config_block(encoder, plans=("f16", "exact")):
     return struct.pack("<12id", *ints, float(cfg.eps)) + tail + b"\0" * (-len(tail) % 8)
 
 
+def _sam_decoder_tensors(d, plans):
+    """The prompt encoder's and the mask decoder's entries of a SAM image, the same behind either encoder."""
+    out = {}
+    out.update({"dec.gauss": host(d.gauss), "dec.corner": host(d.corner), "dec.key_pe": host(d.key_pe), "dec.no_mask": host(d.no_mask),
+                "dec.out_tokens": host(d.out_tokens), "dec.point_embed": host(d.point_embed), "dec.not_a_point": host(d.not_a_point)})
+    if d.mask_params is not None:
+        out["dec.mask_params"] = host(d.mask_params)
+    for i, L in enumerate(d.layers):
+        for j in range(1, 5):
+            out[f"dec.L{i}.ln{j}.g"], out[f"dec.L{i}.ln{j}.b"] = host(L[f"ln{j}"][0]), host(L[f"ln{j}"][1])
+    out["dec.ln_final.g"], out["dec.ln_final.b"] = host(d.ln_final[0]), host(d.ln_final[1])
+    out["dec.up_ln.g"], out["dec.up_ln.b"] = host(d.up_ln[0]), host(d.up_ln[1])
+    for short, prefix in sam_decoder_linears().items():
+        if "f16" in plans:
+            w, b = _sam_decoder_f16(d, short)
+            out[f"dec.f16.{short}.w"], out[f"dec.f16.{short}.b"] = host(w), host(b)
+        if "exact" in plans:
+            out[f"dec.x3.{short}.w"], out[f"dec.x3.{short}.b"], out[f"dec.x3.{short}.s"] = _sam_decoder_x3(d, prefix)
+    return out
+
+
+def _is_hiera(encoder):
+    from .sam import HieraEncoder
+
+    return isinstance(encoder, HieraEncoder)
+
+
+def _hiera_exportable(encoder, who):
+    """The C side plans and runs the default encoder only: the packed operands depend on these choices."""
+    from . import kernels as K
+
+    if not encoder.fused_mlp:
+        raise ValueError(f"{who}: the encoder was built with fused_mlp false (or LMX_NO_FUSED_MLP): its blocks hold no packed MLP images and its "
+                         "attn8 operands are packed for another kernel form; the C plan is the default encoder's")
+    if not encoder.proj_ln:
+        raise ValueError(f"{who}: the encoder has proj_ln false; the C plan is the default encoder's, whose stage-3 projections write layer_norm2")
+    if tuple(K.FUSED_MLP_WIDTHS) != (112, 224):
+        raise ValueError(f"{who}: FUSED_MLP_WIDTHS is {tuple(K.FUSED_MLP_WIDTHS)} (LMX_MLP448 is set); the C plan is the default encoder's, (112, 224)")
+
+
+def sam_hiera_config_block(encoder, plans=("f16", "exact")):
+    """The config block of a SAM image whose encoder is Hiera (csrc/sam_image.h): 12 int32, eps as float64, then blocks / dims / heads /
+    windows per stage, the global blocks (ascending) and fpn_top_down as int32, zero-padded to 8 bytes — all of HieraConfig."""
+    cfg = encoder.cfg
+    mask = sum(1 << PLANS[p] for p in set(_sam_plans(plans, "sam_hiera_config_block")))
+    ns = len(cfg.blocks)
+    if not len(cfg.dims) == len(cfg.heads) == len(cfg.windows) == ns or len(cfg.pos_bkg) != 2:
+        raise LmxError(f"sam_hiera_config_block: blocks, dims, heads and windows of {cfg!r} are not one entry per stage")
+    gb = sorted(int(i) for i in cfg.global_blocks)
+    ints = (SAM_ENC_HIERA, cfg.hidden, ns, sum(cfg.blocks), len(gb), len(cfg.fpn_top_down), cfg.q_pool_stages, cfg.image, cfg.fpn_dim, mask, *cfg.pos_bkg)
+    tail = (*cfg.blocks, *cfg.dims, *cfg.heads, *cfg.windows, *gb, *cfg.fpn_top_down)
+    raw = struct.pack(f"<{len(tail)}i", *(int(v) for v in tail))
+    return struct.pack("<12id", *(int(v) for v in ints), float(cfg.eps)) + raw + b"\0" * (-len(raw) % 8)
+
+
+HIERA_BLOCK_TENSORS = ("g1", "b1", "wqkv", "bqkv", "padkv", "wo", "bo", "g2", "b2", "w1", "bb1", "w2", "bb2")
+
+
+def sam_hiera_tensors(encoder, decoder, plans=("f16", "exact")):
+    """Ordered {name: numpy array}: what a HieraEncoder holds on the device, as it holds it — the packed attention and MLP images
+    included, so that no packing is restated in C++ — with the neck levels outputs="embedding" reads, then the decoder's entries for
+    `plans` (the trunk has one plan)."""
+    plans = _sam_plans(plans, "sam_hiera_tensors")
+    e = encoder
+    _hiera_exportable(e, "sam_hiera_tensors")
+    out = {"enc.pe_w": host(e.pe_w), "enc.pe_b": host(e.pe_b), "enc.pos": host(e.pos), "enc.lut": host(e.lut)}
+    for i, B in enumerate(e.blocks):
+        p = f"enc.B{i}."
+        for n in HIERA_BLOCK_TENSORS + (("wp", "bp") if "wp" in B else ()):
+            out[p + n] = host(B[n])
+        for key in ("attn", "mlp_img"):
+            for j, t in enumerate(B.get(key, ())):
+                out[f"{p}{key}.{j}"] = host(t)
+    for s in range(2, len(e.neck)):
+        out[f"enc.neck.{s}.w"], out[f"enc.neck.{s}.b"] = host(e.neck[s][0]), host(e.neck[s][1])
+    out.update(_sam_decoder_tensors(decoder, plans))
+    return out
+
+
 def sam_tensors(encoder, decoder, plans=("f16", "exact")):
     """Ordered {name: numpy array}: what SamVitEncoder and MaskDecoder hold on the device, in final device form, for `plans`.  The
     tensors both build lazily under the exact plan — the encoder's [whi | wlo] weights (_split2) with the two halves of the neck's
@@ -279,29 +358,24 @@ def sam_tensors(encoder, decoder, plans=("f16", "exact")):
         w2 = host(e._split2("n2"))
         kc = w2.shape[1] // 2
         out["enc.x2.n2.hi"], out["enc.x2.n2.lo"] = np.ascontiguousarray(w2[:, :kc]), np.ascontiguousarray(w2[:, kc:])
-    out.update({"dec.gauss": host(d.gauss), "dec.corner": host(d.corner), "dec.key_pe": host(d.key_pe), "dec.no_mask": host(d.no_mask),
-                "dec.out_tokens": host(d.out_tokens), "dec.point_embed": host(d.point_embed), "dec.not_a_point": host(d.not_a_point)})
-    if d.mask_params is not None:
-        out["dec.mask_params"] = host(d.mask_params)
-    for i, L in enumerate(d.layers):
-        for j in range(1, 5):
-            out[f"dec.L{i}.ln{j}.g"], out[f"dec.L{i}.ln{j}.b"] = host(L[f"ln{j}"][0]), host(L[f"ln{j}"][1])
-    out["dec.ln_final.g"], out["dec.ln_final.b"] = host(d.ln_final[0]), host(d.ln_final[1])
-    out["dec.up_ln.g"], out["dec.up_ln.b"] = host(d.up_ln[0]), host(d.up_ln[1])
-    for short, prefix in sam_decoder_linears().items():
-        if "f16" in plans:
-            w, b = _sam_decoder_f16(d, short)
-            out[f"dec.f16.{short}.w"], out[f"dec.f16.{short}.b"] = host(w), host(b)
-        if "exact" in plans:
-            out[f"dec.x3.{short}.w"], out[f"dec.x3.{short}.b"], out[f"dec.x3.{short}.s"] = _sam_decoder_x3(d, prefix)
+    out.update(_sam_decoder_tensors(d, plans))
     return out
 
 
 def write_sam_image(encoder, decoder, path, plans=("f16", "exact")):
     """Export a SamVitEncoder with its MaskDecoder (any device) as the weight image lmx_sam_open_host reads, with the tensors of
-    `plans`.  Returns the file's size in bytes."""
+    `plans`.  Returns the file's size in bytes.
+    A HieraEncoder is exported too (csrc/sam_image.h; `plans` then names the decoder plans, the trunk has one); ValueError for an
+    encoder not built the default way (fused_mlp,
+    proj_ln, FUSED_MLP_WIDTHS), whatever its `band` setting, which changes no bit and is not recorded."""
     plans = _sam_plans(plans, "write_sam_image")
     cfg = encoder.cfg
+    if _is_hiera(encoder):
+        _hiera_exportable(encoder, "write_sam_image")
+        if (decoder.S, decoder.G) != (cfg.image, cfg.image // 16) or cfg.fpn_dim != 256:
+            raise LmxError(f"write_sam_image: a decoder for image {decoder.S} / grid {decoder.G} does not read the {cfg.fpn_dim}-channel embedding "
+                           f"of a Hiera encoder with image {cfg.image} / grid {cfg.image // 16}")
+        return write_image(path, KIND_SAM, sam_hiera_config_block(encoder, plans), sam_hiera_tensors(encoder, decoder, plans))
     if (decoder.S, decoder.G) != (cfg.image, cfg.grid) or cfg.out_ch != 256:
         raise LmxError(f"write_sam_image: a decoder for image {decoder.S} / grid {decoder.G} does not read the {cfg.out_ch}-channel embedding "
                        f"of an encoder with image {cfg.image} / grid {cfg.grid}")
@@ -555,7 +629,8 @@ class NativeSam(_NativeHandle):
         return nh.value, nw.value
 
     def _emb_dtype(self, precision):
-        return torch.float32 if precision == "exact" else torch.float16
+        """(a Hiera embedding is f16 under both decoder plans: the trunk has one plan)"""
+        return torch.float32 if precision == "exact" and self.info.encoder != SAM_ENC_HIERA else torch.float16
 
     def encode(self, frames, precision):
         """u8 [n,h,w,3] device tensor, channel order as given -> emb [n,G,G,256], f16 ("f16") / f32 ("exact"), on torch's current

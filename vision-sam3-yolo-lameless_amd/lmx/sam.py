@@ -343,6 +343,33 @@ def hiera_plan(cfg, n, rows, fused_mlp=True, lowest=0, proj_ln=True):
     return plan + [prev]
 
 
+# lmx_hiera_block_t's enums (include/lmx.h) -> BlockPlan's strings
+_ATTN = ("attn8_ln", "attn8", "attn_pool", "attn4", "launches")
+_LN1 = ("kernel", "prev", "launch")
+_SHORTCUT = (None, "gemm", "gemm+maxpool", "pooled_gemm")
+_QUERY = (None, "qkv", "qkv+maxpool", "pooled_q+kv")
+_MLP = ("img", "fused", "launches")
+
+
+def _block_plan_of(rec):
+    H, W, Hf, Ho, Wo, Hfo, join, attn, ln1, shortcut, query, window, ln_out, mlp, emit_ln1, stage_end, keep, x16, join_out, clone = rec
+    return BlockPlan(H, W, Hf, Ho, Wo, Hfo, join, _ATTN[attn], _LN1[ln1], _SHORTCUT[shortcut], _QUERY[query], window, bool(ln_out), _MLP[mlp],
+                     bool(emit_ln1), bool(stage_end), bool(keep), bool(x16), bool(join_out), bool(clone))
+
+
+def native_plan(cfg, n, nh, nw, lowest=0):
+    """(rows per block, [BlockPlan per block]) for n frames resized to nh x nw as the C side computes them (lmx_h_hiera_plan): what
+    HieraEncoder(band="blocks")._settle and hiera_plan give for an encoder built the default way with no LMX_* switch set — the plan
+    a caller without Python runs (tests/test_hiera_plan_c_host.py holds the two equal)."""
+    rows, recs = K.hiera_plan_host(cfg, n, nh, nw, lowest)
+    return rows, [_block_plan_of(r) for r in recs]
+
+
+def native_plan_rows(cfg, n, rows, lowest=0):
+    """[BlockPlan per block] = hiera_plan(cfg, n, rows, lowest=lowest) as the C side computes it (lmx_h_hiera_plan_rows)."""
+    return [_block_plan_of(r) for r in K.hiera_plan_rows_host(cfg, n, rows, lowest)]
+
+
 class HieraEncoder:
     """Device-resident Hiera trunk + FPN.  ``encode(frames)`` -> dict(fpn=[3 NHWC f16 levels, high->low res],
     stages=[4 f32 stage outputs]).  Token grids are [n, H, W, C] row-major throughout (no partition copies).
