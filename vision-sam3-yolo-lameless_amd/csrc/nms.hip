@@ -8,8 +8,8 @@
 //     argsort(descending=True) leaves tie order unspecified; this is the stable-sort answer).
 //
 // Kernels
-//   nms_filter_kernel : one thread per anchor: max/argmax over nc class scores (first max wins, as torch.max),
-//                       conf test, atomic append of a 64-bit key (score bits << 32 | ~anchor) to the image's list.
+//   nms_filter_kernel : max over the nc class scores of every anchor with coalesced loads along the rows, conf test, per-wave
+//                       append of a 64-bit key (score bits << 32 | ~anchor) to the image's list.
 //   nms_boxes_kernel  : torchvision.ops.nms on plain xyxy boxes and scores of any sign (lmx_k_nms_boxes): its own keys,
 //                       then the same sort and greedy block suppression (bitonic_sort_desc, greedy_blocks).
 //   nms_greedy_kernel : one 1024-thread workgroup per image: bitonic sort of the keys in LDS (<=16384 keys =
@@ -23,25 +23,62 @@ namespace {
 
 constexpr int MAX_A = 16384;
 
+// Lanes of a wave share rows: a row is read in pieces (16 bytes where VEC, one float otherwise) by L = min(pieces, 64)
+// neighbouring lanes, 64 / L rows per wave pass, so a wave's loads run along the rows (for nc = 80: 21 lanes a row, three rows
+// a wave).  The row maximum — all the filter needs; nms_greedy_kernel finds the class of a candidate — is reduced over the L
+// lanes with shuffles; the keys of a wave are appended with one atomicAdd per image present in it.
+template <bool VEC>
 __global__ __launch_bounds__(256) void nms_filter_kernel(const float* __restrict__ pred, int n, int A, int nc,
                                                          float conf, unsigned long long* __restrict__ keys,
                                                          int* __restrict__ counts) {
   const int64_t total = (int64_t)n * A;
   const int row_len = 4 + nc;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int img = (int)(i / A);
-    const int a = (int)(i - (int64_t)img * A);
-    const float* row = pred + i * row_len + 4;
-    float best = row[0];
-    for (int c = 1; c < nc; ++c) {
-      const float v = row[c];
-      best = v > best ? v : best;
+  const int pieces = VEC ? row_len / 4 : row_len;
+  const int L = pieces < 64 ? pieces : 64;
+  const int rpw = 64 / L;  // rows per wave pass
+  const int lane = threadIdx.x & 63;
+  const int r = lane / L, q = lane - r * L;
+  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int64_t step = (int64_t)gridDim.x * (blockDim.x >> 6) * rpw;
+  for (int64_t base = wave * rpw; base < total; base += step) {  // wave-uniform: every lane takes part in the shuffles
+    const int64_t i = base + r;
+    const bool live = r < rpw && i < total;
+    const int img = live ? (int)(i / A) : 0;
+    float best = -__builtin_inff();
+    if (live) {
+      const float* row = pred + i * row_len;
+      if (VEC) {
+        for (int u = q > 0 ? q : L; u < pieces; u += L) {  // piece 0 is the box
+          const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * u);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) best = v[e] > best ? v[e] : best;
+        }
+      } else {
+        for (int u = q; u < pieces; u += L) {
+          const float v = row[u];
+          best = (u >= 4 && v > best) ? v : best;
+        }
+      }
     }
-    if (best > conf) {
-      const int slot = atomicAdd(&counts[img], 1);
-      const unsigned long long key =
-          ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)a);
-      keys[(int64_t)img * A + slot] = key;
+    // after the step `off` lane q holds the maximum of lanes q .. q + 2 * off - 1 of its row
+    for (int off = 1; off < L; off <<= 1) {
+      const float o = __shfl_down(best, off, 64);
+      best = (q + off < L && o > best) ? o : best;
+    }
+    const bool pass = live && q == 0 && best > conf;
+    const unsigned long long key =
+        ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(i - (int64_t)img * A));
+    unsigned long long todo = __ballot(pass);
+    while (todo) {  // one round per image among the passing rows
+      const int lead = __ffsll((long long)todo) - 1;
+      const int img_l = __shfl(img, lead, 64);
+      const bool mine = pass && img == img_l;
+      const unsigned long long m = __ballot(mine);
+      int slot = 0;
+      if (lane == lead) slot = atomicAdd(&counts[img_l], __popcll(m));
+      slot = __shfl(slot, lead, 64) + __popcll(m & ((1ull << lane) - 1ull));
+      if (mine) keys[(int64_t)img * A + slot] = key;
+      todo &= ~m;
     }
   }
 }
@@ -325,9 +362,16 @@ extern "C" int lmx_k_nms(const float* pred, int n, int A, int nc, float conf, do
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + cnt_bytes);
   float* sbox = reinterpret_cast<float*>(ws + cnt_bytes + (int64_t)n * A * 8);
   LMX_HIP(hipMemsetAsync(cand_counts, 0, (size_t)n * 4, st));
-  int64_t g = ((int64_t)n * A + 255) / 256;
+  // 16-byte pieces where every row starts on a 16-byte address; one 256-thread workgroup takes 4 * (64 / L) rows a pass
+  const bool vec = (4 + nc) % 4 == 0 && (((uintptr_t)pred) & 15) == 0;
+  const int pieces = vec ? (4 + nc) / 4 : 4 + nc;
+  const int rows_wg = 4 * (64 / (pieces < 64 ? pieces : 64));
+  int64_t g = ((int64_t)n * A + rows_wg - 1) / rows_wg;
   if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(nms_filter_kernel, dim3((unsigned)g), dim3(256), 0, st, pred, n, A, nc, conf, keys, cand_counts);
+  if (vec)
+    hipLaunchKernelGGL(nms_filter_kernel<true>, dim3((unsigned)g), dim3(256), 0, st, pred, n, A, nc, conf, keys, cand_counts);
+  else
+    hipLaunchKernelGGL(nms_filter_kernel<false>, dim3((unsigned)g), dim3(256), 0, st, pred, n, A, nc, conf, keys, cand_counts);
   int rc = lmx_launch_check("nms_filter_kernel");
   if (rc) return rc;
   int npow2 = 64;

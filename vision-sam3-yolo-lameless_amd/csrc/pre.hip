@@ -12,68 +12,109 @@ namespace {
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
 
+// clip8(v >> PRECISION_BITS) of the C code (an arithmetic shift, then the clamp to 0..255), written as the clamp of the
+// accumulator followed by a logical shift.  The values are the same; the form is not: from shift-then-clamp of two bytes that
+// are packed side by side hipcc selects v_ashr_pk_u8_i32 and ORs the other bytes into its result as if the upper 16 bits were
+// zero, and on gfx950 they keep what the register held before (seen as wrong bytes 2 of the 16-byte vertical pass).
 __device__ __forceinline__ uint8_t clip8(int v) {
-  v >>= PRECISION_BITS;  // arithmetic shift, like the C code's signed >>
-  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+  const int top = (256 << PRECISION_BITS) - 1;
+  v = v < 0 ? 0 : (v > top ? top : v);
+  return (uint8_t)((unsigned)v >> PRECISION_BITS);
 }
 
-// workgroup = one source row: the row (sw*3 bytes, 5760 for 1080p) is staged into LDS with 16-byte coalesced loads, then
-// every thread produces output pixels of that row from LDS.  (One thread per output pixel reading its taps straight from
-// global memory issued 3 byte loads per tap on overlapping 12..24-byte windows: 0.4 TB/s.)
-constexpr int RESIZE_H_MAX_ROW = 16384;  // bytes of LDS for one source row (sw <= 5461)
+// One tap of the 8bpc passes: byte * coefficient.  Pillow's coefficients are round(w * 2^22) with normalised weights |w| < 2, so
+// both operands fit 24 signed bits and the 24-bit multiply returns the bits of the 32-bit one at the full VALU rate.
+__device__ __forceinline__ int tap(unsigned byte, int coef) { return __mul24((int)byte, coef); }
+
+// workgroup = a group of consecutive source rows (they are contiguous in memory, across frames too): the group's bytes are
+// staged into LDS as ONE span with 16-byte coalesced loads, LDS index = global address modulo 16 + offset in the span, so that
+// every 16-byte global block lands on a 16-byte LDS slot whatever the rows' alignment.  One barrier pair covers the group.
+// thread = one output pixel of RESIZE_H_ROWS staged rows: a coefficient is loaded once for the four rows.  The 12 output bytes
+// of four neighbouring pixels leave as three dword stores of three of the four lanes, which take the next lane's bytes by a
+// shuffle.  Measured and not kept: the tap's three bytes as one dword read at the pixel's own (unaligned) LDS address, 2.1 x
+// slower; four pixels per thread with a 12-byte store each, 110 against 128 us on SAM's 30-frame pass and 951 against 930 us on
+// DINO's 150-frame bicubic pass, the same in sum; four coefficient loads issued ahead of their taps, no change.  (One row per
+// workgroup pass, three byte stores per pixel and a coefficient load per tap and row took 152 and 1010 us; one thread per output
+// pixel reading its taps straight from global memory ran at 0.4 TB/s.)
+// Integer adds: any tap order gives Pillow's bits.
+constexpr int RESIZE_H_MAX_ROW = 16384;             // longest source row staged, bytes (sw <= 5461)
+constexpr int RESIZE_H_LDS = 2 * RESIZE_H_MAX_ROW;  // the staging buffer: 15 bytes of misalignment + the group's rows
+constexpr int RESIZE_H_ROWS = 4;
+
+// rows per staging group: what the buffer holds, at most 8 (narrow frames keep enough workgroups), whole thread tasks above 4
+inline int resize_h_group(int rowb) {
+  int r = (RESIZE_H_LDS - 16) / rowb;
+  r = r > 8 ? 8 : r;
+  return r >= RESIZE_H_ROWS ? r / RESIZE_H_ROWS * RESIZE_H_ROWS : r;
+}
+
 __global__ __launch_bounds__(256) void pil_resize_h_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                           int n, int sh, int sw, int dw,
+                                                           int n, int sh, int sw, int dw, int group,
                                                            const int32_t* __restrict__ bounds,
                                                            const int32_t* __restrict__ kk, int ksize, int swap_rb) {
-  __shared__ __attribute__((aligned(16))) uint8_t rowbuf[RESIZE_H_MAX_ROW];
+  __shared__ __attribute__((aligned(16))) uint8_t buf[RESIZE_H_LDS];
   const int rowb = sw * 3;
-  for (int64_t row = blockIdx.x; row < (int64_t)n * sh; row += gridDim.x) {
-    const uint8_t* srow = src + row * rowb;
-    // rows start at arbitrary byte offsets: align the 16-byte loads on the global address, not on the row
-    const int mis = (int)(reinterpret_cast<uintptr_t>(srow) & 15);
-    const int head = mis ? 16 - mis : 0;
-    for (int i = threadIdx.x; i < head && i < rowb; i += blockDim.x) rowbuf[i] = srow[i];
-    const int nvec = (rowb - head) > 0 ? (rowb - head) / 16 : 0;
-    for (int v = threadIdx.x; v < nvec; v += blockDim.x) {
-      const u32x4 x = *reinterpret_cast<const u32x4*>(srow + head + v * 16);
-      // LDS destination head + 16v is 16-byte aligned only when head == 0: store as four dwords when it is not
-      uint8_t* d = rowbuf + head + v * 16;
-      if ((head & 3) == 0) {
-        reinterpret_cast<unsigned*>(d)[0] = x[0];
-        reinterpret_cast<unsigned*>(d)[1] = x[1];
-        reinterpret_cast<unsigned*>(d)[2] = x[2];
-        reinterpret_cast<unsigned*>(d)[3] = x[3];
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) d[e] = (uint8_t)(x[e >> 2] >> (8 * (e & 3)));
-      }
-    }
-    for (int i = head + nvec * 16 + threadIdx.x; i < rowb; i += blockDim.x) rowbuf[i] = srow[i];
+  const int64_t rows = (int64_t)n * sh;
+  const int dwq = (dw + 3) & ~3;  // whole quads of pixels: a quad lies in one wave (256 and dwq are multiples of 4)
+  for (int64_t row0 = (int64_t)blockIdx.x * group; row0 < rows; row0 += (int64_t)gridDim.x * group) {
+    const int nr = rows - row0 < group ? (int)(rows - row0) : group;
+    const uint8_t* s0 = src + row0 * rowb;
+    const int span = nr * rowb;
+    const int mis = (int)(reinterpret_cast<uintptr_t>(s0) & 15);
+    int head = mis ? 16 - mis : 0;
+    head = head > span ? span : head;
+    for (int i = threadIdx.x; i < head; i += blockDim.x) buf[mis + i] = s0[i];
+    const int nvec = (span - head) / 16;  // mis + head is 0 or 16: aligned on both sides
+    for (int v = threadIdx.x; v < nvec; v += blockDim.x)
+      *reinterpret_cast<u32x4*>(buf + mis + head + v * 16) = *reinterpret_cast<const u32x4*>(s0 + head + v * 16);
+    for (int i = head + nvec * 16 + threadIdx.x; i < span; i += blockDim.x) buf[mis + i] = s0[i];
     __syncthreads();
-    uint8_t* drow = dst + row * dw * 3;
-    for (int xo = threadIdx.x; xo < dw; xo += blockDim.x) {
+    const int ntask = dwq * ((nr + RESIZE_H_ROWS - 1) / RESIZE_H_ROWS);
+    for (int t0 = 0; t0 < ntask; t0 += blockDim.x) {  // workgroup-uniform: every lane of a wave reaches the shuffle
+      const int t = t0 + threadIdx.x;
+      const int rg = t / dwq, xq = t - rg * dwq;
+      const int r0 = rg * RESIZE_H_ROWS;
+      const bool live = t < ntask && xq < dw;
+      // lanes past the row's last pixel and rows past the group's last compute on the last valid one and store nothing
+      const int xo = xq < dw ? xq : dw - 1;
+      int rb[RESIZE_H_ROWS];
+#pragma unroll
+      for (int r = 0; r < RESIZE_H_ROWS; ++r) rb[r] = mis + (r0 + r < nr ? r0 + r : nr - 1) * rowb;
       const int xmin = bounds[2 * xo], cnt = bounds[2 * xo + 1];
       const int32_t* k = kk + (int64_t)xo * ksize;
-      const uint8_t* s = rowbuf + xmin * 3;
-      int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+      int a[RESIZE_H_ROWS][3];
+#pragma unroll
+      for (int r = 0; r < RESIZE_H_ROWS; ++r) a[r][0] = a[r][1] = a[r][2] = 1 << (PRECISION_BITS - 1);
       for (int x = 0; x < cnt; ++x) {
         const int c = k[x];
-        a0 += (int)s[3 * x + 0] * c;
-        a1 += (int)s[3 * x + 1] * c;
-        a2 += (int)s[3 * x + 2] * c;
+        const int off = (xmin + x) * 3;
+#pragma unroll
+        for (int r = 0; r < RESIZE_H_ROWS; ++r) {
+          const uint8_t* s = buf + rb[r] + off;
+          a[r][0] += tap(s[0], c);
+          a[r][1] += tap(s[1], c);
+          a[r][2] += tap(s[2], c);
+        }
       }
-      uint8_t* d = drow + xo * 3;
-      if (swap_rb) {
-        d[0] = clip8(a2);
-        d[1] = clip8(a1);
-        d[2] = clip8(a0);
-      } else {
-        d[0] = clip8(a0);
-        d[1] = clip8(a1);
-        d[2] = clip8(a2);
+      const int j = xq & 3;  // place in the quad; the quad's 12 bytes are dwords 0..2 of lanes j = 0..2
+      const bool quad = xq - j + 4 <= dw;
+#pragma unroll
+      for (int r = 0; r < RESIZE_H_ROWS; ++r) {
+        const unsigned b0 = clip8(swap_rb ? a[r][2] : a[r][0]), b1 = clip8(a[r][1]), b2 = clip8(swap_rb ? a[r][0] : a[r][2]);
+        const unsigned px = b0 | (b1 << 8) | (b2 << 16);
+        const unsigned nx = __shfl_down(px, 1, 64);  // the next pixel's bytes (unused by j = 3)
+        if (!live || r0 + r >= nr) continue;
+        uint8_t* d = dst + (row0 + r0 + r) * dw * 3 + xq * 3;  // this pixel's bytes; the quad's start with d - 3 * j
+        if (quad && ((reinterpret_cast<uintptr_t>(d) - 3 * j) & 3) == 0) {
+          if (j < 3) *reinterpret_cast<unsigned*>(d - 3 * j + 4 * j) = (px >> (8 * j)) | (nx << (24 - 8 * j));
+        } else {  // the row's last pixels, or an output row that is not dword-aligned
+          d[0] = (uint8_t)b0;
+          d[1] = (uint8_t)b1;
+          d[2] = (uint8_t)b2;
+        }
       }
     }
-    __syncthreads();  // the next row overwrites rowbuf
+    __syncthreads();  // the next group overwrites buf
   }
 }
 
@@ -93,17 +134,23 @@ __global__ __launch_bounds__(256) void pil_resize_v_kernel(const uint8_t* __rest
     const int32_t* k = kk + (int64_t)yo * ksize;
     const uint8_t* s = src + ((int64_t)img * sh + ymin) * rowb + xb;
     int a = 1 << (PRECISION_BITS - 1);
-    for (int y = 0; y < cnt; ++y) a += (int)s[(int64_t)y * rowb] * k[y];
+    for (int y = 0; y < cnt; ++y) a += tap(s[(int64_t)y * rowb], k[y]);
     dst[i] = clip8(a);
   }
 }
 
-// the same pass with FOUR consecutive bytes per thread (row length a multiple of 4 bytes, 4-byte aligned images): one dword load
-// per tap row and one dword store instead of four byte loads and four byte stores — identical integer arithmetic per byte
-__global__ __launch_bounds__(256) void pil_resize_v4_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int sh,
+// the same pass with 4 * DW consecutive bytes per thread: one load of DW dwords per tap row and one store instead of byte loads
+// and byte stores, identical integer arithmetic per byte.  DW = 4 (16 bytes) where the row length is a multiple of 16 bytes and
+// the images are 16-byte aligned.  DW = 1 for every other row of 4 bytes or more: dword loads and stores at the bytes' own
+// addresses, aligned or not (rows of 1365 bytes, DINO's 455 columns, have every alignment), and where the row length is no
+// multiple of 4 the row's last piece is moved back to end with the row: the bytes it shares with its neighbour are computed
+// twice, to the same values.
+template <int DW>
+__global__ __launch_bounds__(256) void pil_resize_vw_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int sh,
                                                             int dh, int w, const int32_t* __restrict__ bounds,
                                                             const int32_t* __restrict__ kk, int ksize) {
-  const int rowb = w * 3, roww = rowb / 4;
+  typedef unsigned vec_t __attribute__((ext_vector_type(DW)));
+  const int rowb = w * 3, roww = (rowb + 4 * DW - 1) / (4 * DW);
   const int64_t total = (int64_t)n * dh * roww;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int xw = (int)(i % roww);
@@ -112,18 +159,35 @@ __global__ __launch_bounds__(256) void pil_resize_v4_kernel(const uint8_t* __res
     const int img = (int)(r / dh);
     const int ymin = bounds[2 * yo], cnt = bounds[2 * yo + 1];
     const int32_t* k = kk + (int64_t)yo * ksize;
-    const uint8_t* s = src + ((int64_t)img * sh + ymin) * rowb + xw * 4;
-    int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
+    const int xb = xw * (4 * DW) + 4 * DW <= rowb ? xw * (4 * DW) : rowb - 4 * DW;
+    const uint8_t* s = src + ((int64_t)img * sh + ymin) * rowb + xb;
+    int a[4 * DW];
+#pragma unroll
+    for (int e = 0; e < 4 * DW; ++e) a[e] = 1 << (PRECISION_BITS - 1);
     for (int y = 0; y < cnt; ++y) {
-      const unsigned v = *reinterpret_cast<const unsigned*>(s + (int64_t)y * rowb);
+      vec_t v;
+      if (DW == 4)
+        v = *reinterpret_cast<const vec_t*>(s + (int64_t)y * rowb);
+      else
+        __builtin_memcpy(&v, s + (int64_t)y * rowb, sizeof(v));
       const int c = k[y];
-      a0 += (int)(v & 255u) * c;
-      a1 += (int)((v >> 8) & 255u) * c;
-      a2 += (int)((v >> 16) & 255u) * c;
-      a3 += (int)(v >> 24) * c;
+#pragma unroll
+      for (int q = 0; q < DW; ++q) {
+        a[4 * q + 0] += tap(v[q] & 255u, c);
+        a[4 * q + 1] += tap((v[q] >> 8) & 255u, c);
+        a[4 * q + 2] += tap((v[q] >> 16) & 255u, c);
+        a[4 * q + 3] += tap(v[q] >> 24, c);
+      }
     }
-    *reinterpret_cast<unsigned*>(dst + r * rowb + xw * 4) =
-        (unsigned)clip8(a0) | ((unsigned)clip8(a1) << 8) | ((unsigned)clip8(a2) << 16) | ((unsigned)clip8(a3) << 24);
+    vec_t o;
+#pragma unroll
+    for (int q = 0; q < DW; ++q)
+      o[q] = (unsigned)clip8(a[4 * q]) | ((unsigned)clip8(a[4 * q + 1]) << 8) | ((unsigned)clip8(a[4 * q + 2]) << 16) |
+             ((unsigned)clip8(a[4 * q + 3]) << 24);
+    if (DW == 4)
+      *reinterpret_cast<vec_t*>(dst + r * rowb + xb) = o;
+    else
+      __builtin_memcpy(dst + r * rowb + xb, &o, sizeof(o));
   }
 }
 
@@ -294,9 +358,10 @@ extern "C" int lmx_k_pil_resize_h(const uint8_t* src, uint8_t* dst, int n, int s
   LMX_REQUIRE(src && dst && bounds && kk, "lmx_k_pil_resize_h: null pointer");
   LMX_REQUIRE(n > 0 && sh > 0 && sw > 0 && dw > 0 && ksize > 0, "lmx_k_pil_resize_h: shape");
   LMX_REQUIRE(sw * 3 <= RESIZE_H_MAX_ROW, "lmx_k_pil_resize_h: source rows wider than %d pixels are not staged", RESIZE_H_MAX_ROW / 3);
-  int64_t rows = (int64_t)n * sh;
-  hipLaunchKernelGGL(pil_resize_h_kernel, dim3((unsigned)(rows < 256 * 16 ? rows : 256 * 16)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), src, dst, n, sh, sw, dw, bounds, kk, ksize, swap_rb);
+  const int group = resize_h_group(sw * 3);
+  const int64_t groups = ((int64_t)n * sh + group - 1) / group;
+  hipLaunchKernelGGL(pil_resize_h_kernel, dim3((unsigned)(groups < 256 * 16 ? groups : 256 * 16)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), src, dst, n, sh, sw, dw, group, bounds, kk, ksize, swap_rb);
   return lmx_launch_check("pil_resize_h_kernel");
 }
 
@@ -304,10 +369,16 @@ extern "C" int lmx_k_pil_resize_v(const uint8_t* src, uint8_t* dst, int n, int s
                                   const int32_t* kk, int ksize, lmx_stream_t stream) {
   LMX_REQUIRE(src && dst && bounds && kk, "lmx_k_pil_resize_v: null pointer");
   LMX_REQUIRE(n > 0 && sh > 0 && dh > 0 && w > 0 && ksize > 0, "lmx_k_pil_resize_v: shape");
-  if ((w * 3) % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 3) == 0) {  // four bytes per thread
-    hipLaunchKernelGGL(pil_resize_v4_kernel, dim3(grid_for((int64_t)n * dh * (w * 3 / 4))), dim3(256), 0,
+  const uintptr_t al = (uintptr_t)src | (uintptr_t)dst | (uintptr_t)(w * 3);
+  if ((al & 15) == 0) {  // sixteen bytes per thread
+    hipLaunchKernelGGL(pil_resize_vw_kernel<4>, dim3(grid_for((int64_t)n * dh * (w * 3 / 16))), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), src, dst, n, sh, dh, w, bounds, kk, ksize);
-    return lmx_launch_check("pil_resize_v4_kernel");
+    return lmx_launch_check("pil_resize_vw_kernel<4>");
+  }
+  if (w * 3 >= 4) {  // four bytes per thread
+    hipLaunchKernelGGL(pil_resize_vw_kernel<1>, dim3(grid_for((int64_t)n * dh * ((w * 3 + 3) / 4))), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), src, dst, n, sh, dh, w, bounds, kk, ksize);
+    return lmx_launch_check("pil_resize_vw_kernel<1>");
   }
   hipLaunchKernelGGL(pil_resize_v_kernel, dim3(grid_for((int64_t)n * dh * w * 3)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), src, dst, n, sh, dh, w, bounds, kk, ksize);

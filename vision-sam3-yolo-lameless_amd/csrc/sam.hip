@@ -12,8 +12,114 @@ inline int grid_for(int64_t total, int block = 256) {
   return (int)g;
 }
 
-// thread = one 8-column chunk of one output row (token); builds the 8 normalised values and stores 16 bytes.
-// KW_T > 0: the kernel width as a compile-time constant (7: Hiera's patch embedding, 16: the SAM ViT's) — the two divisions per
+// Hiera's patch embedding (7 x 7, stride 4, pad 3): neighbouring tokens share three of their seven columns and rows, so a
+// workgroup takes a run of P7_T tokens of one output row and stages the seven input rows under it ONCE, as f16: dword loads
+// on the global address (all of a thread's loads are issued before the first is used), the look-up applied once per input byte
+// (the table is converted with (half_t) when it is staged: the same values), zeros outside the rh x rw image.  Within one ky a
+// token's 21 values are contiguous in the staged row (at 12 * token), so the patch rows then leave as consecutive 16-byte
+// chunks built from LDS alone: a thread keeps one chunk column and its eight staged offsets, and walks the tokens.
+// (Eight single-byte global loads and look-ups per 16-byte store gave 1.4 TB/s of output.)
+constexpr int P7_T = 64;                                  // tokens per run
+constexpr int P7_ROW = (4 * P7_T + 3) * 3;                // staged values per input row
+constexpr int P7_NDW = (P7_ROW + 3 + 3) / 4 + 1;          // aligned dwords that can hold one row's bytes, at any misalignment
+constexpr int P7_LOADS = (7 * P7_NDW + 255) / 256;        // dwords per thread and run
+__global__ __launch_bounds__(256) void im2col_p7_kernel(const uint8_t* __restrict__ img, const float* __restrict__ lut,
+                                                        half_t* __restrict__ out, int n, int rh, int rw, int OH, int OW, int64_t ldo) {
+  __shared__ half_t lut_s[768];
+  __shared__ half_t st[7 * P7_ROW];
+  for (int i = threadIdx.x; i < 768; i += blockDim.x) lut_s[i] = (half_t)lut[i];
+  __syncthreads();
+  const int tid = threadIdx.x;
+  const int chunks = (int)(ldo / 8);  // <= 256 (checked by the launcher)
+  const int tpp = 256 / chunks;       // tokens per pass of the workgroup
+  const int tl = tid / chunks, ck = tid - tl * chunks;
+  int offs[8];                        // staged offset of this chunk's values for token 0; columns from K on are zeros
+  unsigned zeros = 0u;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int k = ck * 8 + e, ky = k / 21;
+    offs[e] = k < 147 ? ky * P7_ROW + (k - ky * 21) : 0;
+    zeros |= k < 147 ? 0u : 1u << e;
+  }
+  const int runs = (OW + P7_T - 1) / P7_T;
+  const int64_t jobs = (int64_t)n * OH * runs;
+  for (int64_t job = blockIdx.x; job < jobs; job += gridDim.x) {
+    const int run = (int)(job % runs);
+    const int64_t r = job / runs;
+    const int oy = (int)(r % OH);
+    const int b = (int)(r / OH);
+    const int ox0 = run * P7_T;
+    const int tc = OW - ox0 < P7_T ? OW - ox0 : P7_T;  // tokens of this run
+    const int x_lo = ox0 * 4 - 3;                      // image column of staged element 0
+    const int nst = (4 * tc + 3) * 3;                  // staged values per row that the run reads
+    const int xa = x_lo > 0 ? x_lo : 0;                // image columns [xa, xb) are inside the frame
+    const int xb = x_lo + 4 * tc + 3 < rw ? x_lo + 4 * tc + 3 : rw;
+    const int lo = (xa - x_lo) * 3, len = (xb - xa) * 3;  // staged [lo, lo + len) of a row inside the frame comes from it
+    const uint8_t* ib = img + (int64_t)b * rh * rw * 3;
+    for (int ky = 0; ky < 7; ++ky) {  // the zeros
+      const bool in = (unsigned)(oy * 4 - 3 + ky) < (unsigned)rh && len > 0;
+      half_t* srow = st + ky * P7_ROW;
+      for (int i = tid; i < (in ? lo : nst); i += blockDim.x) srow[i] = (half_t)0.f;
+      for (int i = (in ? lo + len : nst) + tid; i < nst; i += blockDim.x) srow[i] = (half_t)0.f;
+    }
+    // the frame's bytes: unit u = aligned dword d of row ky; v holds its bytes, j0 the offset of its first byte from staged
+    // element lo (-3 .. len - 1; bytes at offsets outside 0 .. len - 1 belong to other columns and are neither read nor used)
+    unsigned v[P7_LOADS], units = 0u;
+    int j0[P7_LOADS], at[P7_LOADS];
+#pragma unroll
+    for (int it = 0; it < P7_LOADS; ++it) {
+      const int u = tid + it * 256;
+      const int ky = u / P7_NDW, d = u - ky * P7_NDW;
+      const int y = oy * 4 - 3 + ky;
+      v[it] = 0u;
+      j0[it] = at[it] = 0;
+      if (ky < 7 && (unsigned)y < (unsigned)rh && len > 0) {
+        const uint8_t* g = ib + (y * rw + xa) * 3;  // the byte of staged element lo (channel 0: lo % 3 == 0)
+        const int mis = (int)(reinterpret_cast<uintptr_t>(g) & 3);
+        const int j = d * 4 - mis;
+        if (j < len) {
+          units |= 1u << it;
+          j0[it] = j;
+          at[it] = ky * P7_ROW + lo + j;
+          if (j >= 0 && j + 4 <= len) {
+            v[it] = *reinterpret_cast<const unsigned*>(g + j);
+          } else {  // the dwords that hold the row's first and last bytes
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (j + e >= 0 && j + e < len) v[it] |= (unsigned)g[j + e] << (8 * e);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < P7_LOADS; ++it) {
+      if (!((units >> it) & 1u)) continue;
+      int c = (j0[it] + 3) % 3;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (j0[it] + e >= 0 && j0[it] + e < len) st[at[it] + e] = lut_s[c * 256 + ((v[it] >> (8 * e)) & 255u)];
+        c = c == 2 ? 0 : c + 1;
+      }
+    }
+    __syncthreads();
+    half_t* orow = out + (((int64_t)b * OH + oy) * OW + ox0) * ldo + ck * 8;
+    if (tl < tpp) {
+      for (int t = tl; t < tc; t += tpp) {
+        half8_t o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const half_t val = st[offs[e] + t * 12];
+          o[e] = (zeros >> e) & 1u ? (half_t)0.f : val;
+        }
+        *reinterpret_cast<half8_t*>(orow + (int64_t)t * ldo) = o;
+      }
+    }
+    __syncthreads();  // the next run overwrites st
+  }
+}
+
+// Every other geometry.  thread = one 8-column chunk of one output row (token); builds the 8 normalised values and stores 16 bytes.
+// KW_T > 0: the kernel width as a compile-time constant (16: the SAM ViT's patch embedding) — the two divisions per
 // VALUE by run-time widths made this kernel ALU-bound at 1.3 TB/s of output; the look-up table sits in LDS.
 template <int KW_T>
 __global__ __launch_bounds__(256) void im2col_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ lut,
@@ -359,9 +465,12 @@ extern "C" int lmx_k_im2col_u8(const uint8_t* img, const float* lut, void* out, 
   const dim3 grid(grid_for((int64_t)n * OH * OW * (ldo / 8)));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   half_t* o16 = reinterpret_cast<half_t*>(out);
-  if (KW == 7)
-    hipLaunchKernelGGL((im2col_u8_kernel<7>), grid, dim3(256), 0, st, img, lut, o16, n, rh, rw, OH, OW, KH, KW, stride, pad, ldo);
-  else if (KW == 16)
+  if (KH == 7 && KW == 7 && stride == 4 && pad == 3 && ldo <= 8 * 256) {
+    const int64_t jobs = (int64_t)n * OH * ((OW + P7_T - 1) / P7_T);
+    hipLaunchKernelGGL(im2col_p7_kernel, dim3(grid_for(jobs * 256)), dim3(256), 0, st, img, lut, o16, n, rh, rw, OH, OW, ldo);
+    return lmx_launch_check("im2col_p7_kernel");
+  }
+  if (KW == 16)
     hipLaunchKernelGGL((im2col_u8_kernel<16>), grid, dim3(256), 0, st, img, lut, o16, n, rh, rw, OH, OW, KH, KW, stride, pad, ldo);
   else
     hipLaunchKernelGGL((im2col_u8_kernel<0>), grid, dim3(256), 0, st, img, lut, o16, n, rh, rw, OH, OW, KH, KW, stride, pad, ldo);

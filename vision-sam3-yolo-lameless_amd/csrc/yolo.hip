@@ -228,10 +228,25 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(const float* __restr
       prow[2] = (x2 - x1) * stride;
       prow[3] = (y2 - y1) * stride;
     }
-    for (int c = side; c < nc; c += 4) {
-      const float v = hrow[64 + c];
-      prow[4 + c] = 1.0f / (1.0f + expf(-v));
+    // the anchor's 4 lanes take the class scores in 16-byte pieces in turn (64 contiguous bytes per pass), stored as one
+    // piece where the pred row is 16-byte aligned (nc % 4 == 0); the nc % 4 last scores go one per lane
+    const float* hc = hrow + 64;
+    float* pc = prow + 4;
+    const bool al = (reinterpret_cast<uintptr_t>(pc) & 15) == 0;
+    const int nc4 = nc & ~3;
+    for (int c = side * 4; c < nc4; c += 16) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(hc + c);
+      f32x4 s;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = 1.0f / (1.0f + expf(-v[e]));
+      if (al) {
+        *reinterpret_cast<f32x4*>(pc + c) = s;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pc[c + e] = s[e];
+      }
     }
+    for (int c = nc4 + side; c < nc; c += 4) pc[c] = 1.0f / (1.0f + expf(-hc[c]));
   }
 }
 
