@@ -14,6 +14,7 @@ from lmx import kernels as K
 from lmx import yolo
 
 F16, F32 = torch.float16, torch.float32
+CU_COUNTS = (64, 104, 256, 304)  # for the table rows that are functions of the device's CU count
 
 
 # ------------------------------------------------------------------------------------------------ GEMM and convolution tables
@@ -49,7 +50,8 @@ def test_gemm_tables_reach_every_route_they_claim():
 # ------------------------------------------------------------------------------------------------ attention tables
 @pytest.mark.parametrize("sid,fam,shape,rel_S,kinds,route", GA.SHAPES, ids=[s[0] for s in GA.SHAPES])
 def test_attention_table(sid, fam, shape, rel_S, kinds, route):
-    assert GA.shape_route(shape, rel_S) == route
+    for cu in (CU_COUNTS if callable(shape) else (None,)):  # rows that grow with the CU count: the same route at every count
+        assert GA.shape_route(shape, rel_S, cu) == route
     # the id and the family say what the route says
     word = {"small": "small", "sp": "sp_qb2_", "spp": "spp_", "gp": "gp4_", "kernel": "tiled_", "wide": "tiled_q1_dot2_hd96", "rel": "_rel_"}[fam]
     assert word in route
@@ -58,6 +60,19 @@ def test_attention_table(sid, fam, shape, rel_S, kinds, route):
     for sums in ("ones", "dot2"):
         assert f" {sums} " not in sid or f"_{sums}" in route
     assert ("wide" in sid) == route.endswith("_hd96")
+
+
+def test_many_item_rows_sample_a_whole_walk():
+    """The rows that grow with the CU count: at every count each workgroup of the persistent kernel walks three or four items, and the
+    row sample holds the items at positions 0, 1, 2 and last of one workgroup (GA.walked_sample asserts both)."""
+    many = [s for s in GA.SHAPES if callable(s[2])]
+    assert len(many) == 2
+    for cu in CU_COUNTS:
+        for sid, _, shape, *_ in many:
+            geo = GA._geo(shape(cu))
+            assert 3 * cu < geo.B * geo.H <= 3 * cu + 16, sid
+            rows, _ = GA.walked_sample(geo, cu)
+            assert len(rows) < geo.q_rows // 20
 
 
 def test_attention_table_reaches_every_route_it_claims():
@@ -70,8 +85,11 @@ def test_attention_table_reaches_every_route_it_claims():
 @pytest.mark.parametrize("label,H,B,sizes,hd,window,routes", GD.ATTN_CASES, ids=[c[0] for c in GD.ATTN_CASES])
 def test_batch_independence_attention_table(label, H, B, sizes, hd, window, routes):
     T = 201 if window is None else 196
-    for i, b in enumerate(GD.attn_case_batches(B, sizes, window)):
-        assert K.attention_route(b, H, T, T, hd, window=window, pad=window is not None, ld=3 * H * hd) == routes[min(i, 1)], f"B = {b}"
+    for cu in (CU_COUNTS if callable(B) else (None,)):
+        batches = GD.attn_case_batches(B, sizes, window, cu)
+        assert sum(batches[1:]) == batches[0]
+        for i, b in enumerate(batches):
+            assert K.attention_route(b, H, T, T, hd, window=window, pad=window is not None, ld=3 * H * hd) == routes[min(i, 1)], f"B = {b}"
 
 
 def test_attention_edges():

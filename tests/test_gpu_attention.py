@@ -8,13 +8,18 @@ kernel the dispatch picks for it and each row of SHAPES ends with that kernel's 
 the test asserts of the library's own selection before it launches (tests/test_dispatch_routes_host.py does so without a GPU).
 q / k / v are views with ld > H * hd inside NaN-filled buffers (gap columns and the rows after
 the last described row), `out` a strided view of a sentinel-filled buffer: every result must be finite and every cell outside
-the described output must keep the sentinel.  The tests print each case's ratio as a power of two."""
+the described output must keep the sentinel.  The tests print each case's ratio as a power of two.
+
+Two spp rows hold more items than the device has CUs (3 CU + 6 / 3 CU + 8: a function of the CU count, resolved in the test), so that a
+workgroup of the persistent kernel walks three or four items and hands its double-buffered LDS image over between them; the test
+asserts through hieraref.walk that the sampled rows hold the items at positions 0, 1, 2 and last of one workgroup's walk."""
 import math
 
 import pytest
 import torch
 
 import attnref as A
+import hieraref
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +36,23 @@ def _win(Gh, ws, qs=1):
     return dict(Gh=Gh, Gw=Gh, ws=ws, q_stride=qs)
 
 
-# (id naming the branch, family, (B, H, Tq, Tk, hd, window), rel_S, stresses, route)
+def _multi_flat(cu):
+    """B x H = 3 CU + 6 items of T 201 (B rounded up to whole batch elements of 2 heads)."""
+    return (-(-(3 * cu + 6) // 2), 2, 201, 201, 64, None)
+
+
+def _multi_win(cu):
+    """images x 4 windows x 2 heads = 3 CU + 8 items (rounded up to whole images): the four 14 x 14 windows of a 20 x 20 image have
+    four different padding patterns, so consecutive items of a workgroup alternate edge and interior DMA plans over one LDS image."""
+    return (4 * -(-(3 * cu + 8) // 8), 2, 196, 196, 56, _win(20, 14))
+
+
+def resolve(shape, cu):
+    """A row's shape: a tuple, or a function of the device's CU count."""
+    return shape(cu) if callable(shape) else shape
+
+
+# (id naming the branch, family, (B, H, Tq, Tk, hd, window) or a function of the CU count giving it, rel_S, stresses, route)
 SHAPES = [
     ("small 7x7 hd32 items15", "small", (3, 5, 7, 7, 32, None), None, ALL, "small"),
     ("small Tq16 Tk1 hd64", "small", (2, 3, 16, 1, 64, None), None, ("benign", "late_max"), "small"),
@@ -68,6 +89,8 @@ SHAPES = [
     ("spp dot2 win14 padded 20x20 hd64", "spp", (16, 4, 196, 196, 64, _win(20, 14)), None, WIN, "spp_dot2"),
     ("sp dot2 items63 T201", "sp", (63, 1, 201, 201, 64, None), None, BL, "sp_qb2_dot2"),
     ("spp dot2 items64 T201", "spp", (64, 1, 201, 201, 64, None), None, BL, "spp_dot2"),
+    ("spp dot2 T201 hd64 items 3CU+6", "spp", _multi_flat, None, ("benign", "large"), "spp_dot2"),
+    ("spp ones win14 padded 20x20 hd56 items 3CU+8", "spp", _multi_win, None, ("late_max", "pad_heavy"), "spp_ones"),
     ("gp ones T256 hd56", "gp", (1, 2, 256, 256, 56, None), None, ALL, "gp4_ones"),
     ("gp dot2 T256 hd64", "gp", (1, 2, 256, 256, 64, None), None, ALL, "gp4_dot2"),
     ("gp ones T257 hd56", "gp", (2, 2, 257, 257, 56, None), None, ALL, "gp4_ones"),
@@ -90,11 +113,12 @@ CASES = [(sid, fam, shape, rel_S, kind, route) for sid, fam, shape, rel_S, kinds
 VIEW_COL0, VIEW_GAP = 8, 16  # _view: q / k / v / out are views with ld = 8 + H * hd + 16
 
 
-def shape_route(shape, rel_S):
-    """The route lmx_k_attention takes for a row of SHAPES as run_attention launches it (windows with both pad vectors)."""
+def shape_route(shape, rel_S, cu=None):
+    """The route lmx_k_attention takes for a row of SHAPES as run_attention launches it (windows with both pad vectors); cu: the
+    CU count for the rows that depend on it."""
     from lmx import kernels as K_
 
-    B, H, Tq, Tk, hd, win = shape
+    B, H, Tq, Tk, hd, win = resolve(shape, cu)
     return K_.attention_route(B, H, Tq, Tk, hd, window=win, pad=win is not None, rel_S=rel_S or 0, ld=VIEW_COL0 + H * hd + VIEW_GAP)
 
 
@@ -135,6 +159,29 @@ def run_attention(inp, geo, cuda, pads=True, Tk=None):
     return out.cpu()
 
 
+def walked_sample(geo, cu):
+    """The row sample of a many-items spp case: rows_sample plus the first and last two query rows of every item the first
+    longest-walking workgroup of the persistent kernel visits (item = b * H + h; an output row holds every head of its batch
+    element | window).  Asserts that the sample holds that workgroup's items at positions 0, 1, 2 and last -> (rows, a line)."""
+    items = geo.B * geo.H
+    assert items > 3 * cu, "every workgroup must walk at least three items"
+    by_wg = {}
+    for item, (wg, p, _) in enumerate(hieraref.walk("attn_spp", items, cu)):
+        by_wg.setdefault(wg, {})[p] = item
+    lens = sorted({len(v) for v in by_wg.values()})
+    assert lens[0] >= 3 and lens[-1] >= 4, lens
+    wg, its = next((w, v) for w, v in sorted(by_wg.items()) if len(v) == lens[-1])
+    of_b = {}
+    for r in range(geo.q_rows):
+        of_b.setdefault(geo.locate(r)[0], []).append(r)
+    extra = [r for it in its.values() for r in of_b[it // geo.H][:2] + of_b[it // geo.H][-2:]]
+    rows = torch.tensor(sorted(set(A.rows_sample(geo.q_rows).tolist()) | set(extra)), dtype=torch.long)
+    sampled = {geo.locate(r)[0] * geo.H + h for r in rows.tolist() for h in range(geo.H)}
+    last = len(its) - 1
+    assert last >= 3 and all(its[p] in sampled for p in (0, 1, 2, last))
+    return rows, f"workgroups walk {lens} items; workgroup {wg} walks items {[its[p] for p in range(last + 1)]}, all sampled"
+
+
 def _check_stress(kind, ref, geo):
     s, p = ref[3]["s"], ref[1]
     if kind == "large":
@@ -151,11 +198,17 @@ def _check_stress(kind, ref, geo):
 
 @pytest.mark.parametrize("sid,fam,shape,rel_S,kind,route", CASES, ids=[f"{c[0]}-{c[4]}" for c in CASES])
 def test_attention_matches_float64(cuda, sid, fam, shape, rel_S, kind, route):
+    cu = torch.cuda.get_device_properties(cuda).multi_processor_count
+    multi = callable(shape)
+    shape = resolve(shape, cu)
     assert shape_route(shape, rel_S) == route, sid
     geo = _geo(shape)
+    rows = A.rows_sample(geo.q_rows)
+    if multi:
+        rows, line = walked_sample(geo, cu)
+        print(f"attention [{fam}] {sid}: {cu} CUs, {line}")
     inp = A.make_inputs(kind, geo, seed=sum(shape[:5]) + A.STRESSES.index(kind), rel_S=rel_S)
     got = run_attention(inp, geo, cuda)
-    rows = A.rows_sample(geo.q_rows)
     r, ref = A.evaluate(inp, geo, got[rows], rows=rows)
     extra = _check_stress(kind, ref, geo)
     print(f"attention [{fam}] {sid} {kind}: max ratio {A.lg(r)} (bound {A.lg(C_ATTN)}){extra}")

@@ -250,11 +250,27 @@ ATTN_CASES = [
     ("flat T201 hd64 H16", 16, 8, [3, 1, 2, 2], 64, None, ("spp_dot2", "sp_qb2_dot2")),
     ("win14 28x28 pad vectors hd56 H2", 2, 8 * 4, [3, 1, 4], 56, dict(Gh=28, Gw=28, ws=14, q_stride=1), ("spp_ones", "sp_qb2_ones")),
     ("win14 20x20 pad vectors hd64 H2", 2, 8 * 4, [7, 1], 64, dict(Gh=20, Gw=20, ws=14, q_stride=1), ("spp_dot2", "sp_qb2_dot2")),
+    # more items than CUs (B and the chunk sizes are functions of the CU count): every workgroup of the persistent kernel walks three
+    # or four items and hands its LDS image over between them — the geometries of the two many-items rows of tests/test_gpu_attention.py
+    ("flat T201 hd64 H2 items 3CU+6", 2, lambda cu: -(-(3 * cu + 6) // 2), lambda cu: _cut(-(-(3 * cu + 6) // 2), (31, 17, 25, 9)), 64, None,
+     ("spp_dot2", "sp_qb2_dot2")),
+    ("win14 20x20 pad vectors hd56 H2 items 3CU+8", 2, lambda cu: 4 * -(-(3 * cu + 8) // 8), lambda cu: _cut(-(-(3 * cu + 8) // 8), (7, 3, 5, 1)), 56,
+     dict(Gh=20, Gw=20, ws=14, q_stride=1), ("spp_ones", "sp_qb2_ones")),
 ]
 
 
-def attn_case_batches(B, sizes, window):
-    """B of the whole problem, then of every chunk of a case of ATTN_CASES, as lmx_k_attention counts it (windows: 4 per image)."""
+def _cut(n, pattern):
+    """n batch elements in chunks whose sizes cycle through `pattern`."""
+    out = []
+    while sum(out) < n:
+        out.append(min(pattern[len(out) % len(pattern)], n - sum(out)))
+    return out
+
+
+def attn_case_batches(B, sizes, window, cu=None):
+    """B of the whole problem, then of every chunk of a case of ATTN_CASES, as lmx_k_attention counts it (windows: 4 per image);
+    cu: the CU count, for the cases whose B and sizes are functions of it."""
+    B, sizes = (B(cu), sizes(cu)) if callable(B) else (B, sizes)
     return [B] + [s * (1 if window is None else 4) for s in sizes]
 
 
@@ -263,6 +279,10 @@ def test_attention_rows_are_independent_of_the_batch(cuda, label, H, B, sizes, h
     """sizes in batch elements (frames | windows); for windows a chunk is whole images (4 windows of 14 x 14 each)."""
     from lmx import kernels as K_
 
+    if callable(B):
+        cu = torch.cuda.get_device_properties(cuda).multi_processor_count
+        B, sizes = B(cu), sizes(cu)
+        assert B * H > 3 * cu, "every workgroup must walk at least three items"
     T = 201 if window is None else 196
     g = torch.Generator(device=cuda).manual_seed(hd + B)
     heads, per = H, (1 if window is None else 4)

@@ -532,7 +532,8 @@ def test_hiera_attn8_fused_block(cuda, n, Gh, Gw, ln_inside):
 def test_hiera_attn4_fused_block(cuda, n, Gh, Gw):
     """lmx_k_hiera_attn4 (csrc/hiera.hip): x += proj(window attention(qkv(h))) for 4 x 4-token windows at D = 224 (4 heads), weights
     streamed through LDS; against the fp32 definition and the three launches it replaces.  The grids cover a partial last group of
-    16 windows, a single window, and several groups per workgroup."""
+    16 windows and a single window, with at most 8 groups: on a device with that many CUs every workgroup runs ONE group.  Several
+    groups per workgroup (later ring phases, a partial group on a late pass) are tests/test_gpu_persistent.py's."""
     from lmx import kernels as Kk
     from lmx import sam
 
@@ -572,7 +573,9 @@ def test_hiera_attn_pool_fused_block(cuda, Din, D, heads, ws, n, Gh, Gw):
     """lmx_k_hiera_attn_pool (csrc/hiera.hip): the attention half of the blocks that open Hiera stages 2 and 3 — pool(proj(h)) +
     attn_proj(window attention(pool(q), k, v)): 112 -> 224 channels on 8 x 8 windows, 224 -> 448 on 4 x 4 windows, 2 x 2 max-pooled
     queries and shortcut — against the fp32 definition (TF sam2 Sam2MultiScaleBlock / Sam2MultiScaleAttention with q_stride) and the
-    five launches it replaces.  The grids cover single windows, partial last groups and several groups per workgroup."""
+    five launches it replaces.  The grids cover single windows and partial last groups, with at most 16 (112 -> 224) / 8 (224 -> 448)
+    groups: on a device with that many CUs every workgroup runs ONE group.  Several groups per workgroup (ring start slots other
+    than 0, a partial group on a late pass) are tests/test_gpu_persistent.py's."""
     from lmx import kernels as Kk
     from lmx import sam
 
