@@ -534,6 +534,45 @@ int lmx_k_nms_boxes(const float* boxes, int64_t ldb, const float* scores, const 
  * (services/sam3-pipeline/app/main.py:83-89 returns a bool[H,W] mask; SURVEY.md §8b `mask_bits [n, h, ceil(w/8)]`):
  * 8x less D2H and xGMI traffic than the byte mask. */
 int lmx_k_pack_bits(const uint8_t* src, int64_t rows, int w, uint8_t* dst, lmx_stream_t stream);
+/* The per-frame record matrix in ONE launch (csrc/records.hip): what lmx.dist.pack_records builds with a torch.zeros and one strided
+ * copy per field, and FusedExtractor.step's reference schedule with an index_copy_ per field on top (lmx/pipeline.py; SURVEY.md §8b
+ * `lmx_allgather_results`, §8e: one fixed-stride byte row per frame is what the gather moves).  out u8 [n_rows][stride]:
+ *   out[r][0:8]   int64 1 for r < n_valid, else 0 (the `valid` word; rows from n_valid on are padding: zeros throughout);
+ *   field f of row r < n_valid = the row_bytes bytes of source row s of fields_host[f].src at out[r][offset ...], where s = r under
+ *                 the identity map (map = -1) and s = row_maps_host[map][r] otherwise; zeros where s < 0 or s >= the field's n_src;
+ *   every other byte of the row is zero, the padding behind each field up to the next 8-byte boundary included.
+ * Every byte of out is stored exactly once, whatever it held: no memset in front, no atomics.
+ * fields_host: HOST array of n_fields <= LMX_RECORD_MAX_FIELDS descriptors, read during the call (they travel as kernel arguments);
+ * src is DEVICE memory [n_src][row_bytes], dense rows, any byte alignment; offset >= 8, a multiple of 8, the fields ascending and
+ * disjoint with offset + row_bytes <= stride.  row_maps_host: HOST array of n_maps <= LMX_RECORD_MAX_MAPS DEVICE pointers, each int32
+ * [n_valid]: no map is read for a padding row (NULL with n_maps = 0).  stride: a multiple of 8; out: 8-byte aligned.  n_rows = 0 is legal and launches nothing.
+ * (n_src lives in the field, not in the call: a scheduled step gathers n_det rows of one network and n_emb of the other.) */
+enum { LMX_RECORD_MAX_FIELDS = 16, LMX_RECORD_MAX_MAPS = 4 };
+typedef struct { const void* src; int64_t row_bytes, offset; int32_t map, n_src; } lmx_record_field_t;
+int lmx_k_pack_records(const lmx_record_field_t* fields_host, int n_fields, const int32_t* const* row_maps_host, int n_maps, int64_t n_valid,
+                       int64_t n_rows, int64_t stride, uint8_t* out, lmx_stream_t stream);
+
+/* ---- HOST functions: the fused record (csrc/host_records.cpp; all pointers are HOST memory) ----
+ * lmx_h_record_layout: lmx.dist.record_layout of the dict FusedExtractor.step returns for h x w frames (lmx/pipeline.py; the record of
+ *                   SURVEY.md §8b): the fields in sorted name order — boxes f32 [max_det][4], cls i32 [max_det], counts i32,
+ *                   embedding f32 [hidden], mask_bits u8 [h][ceil(w/8)], mask_contour i64 [8], mask_iou f32, mask_stats i64 [8],
+ *                   scores f32 [max_det], and with scheduled != 0 ran_det i32, ran_emb i32 between mask_stats and scores — each at
+ *                   the next multiple of 8 bytes behind the 8-byte `valid` word; stride = the end of the last one.
+ * lmx_h_stream_plan: lmx.pipeline.stream_plan(n_chunks, max_streams, layout): *pool_host = max(3, min(2 + n_chunks, max_streams))
+ *                   streams, YOLO on *det_host = 0, DINO on *emb_host = 1, sam_host int32 [n_chunks] = the stream of each SAM pass
+ *                   (LMX_STREAMS_LANES: dealt over streams 2 .. pool - 1; LMX_STREAMS_RR: round-robin over all of them, from 2).
+ * lmx_h_row_map:    the row scatter of FusedExtractor.step's reference schedule (`out[k].index_copy_(0, idx, part[k])`,
+ *                   `ran.index_fill_(0, idx, 1)`; yolo main.py:74, dinov3 main.py:127) as a gather: map_host int32 [n] = j where
+ *                   idx_host[j] = r, else -1; ran_host int32 [n] (may be NULL) = 1 there, else 0.  idx_host int32 [n_idx] must
+ *                   ascend strictly inside 0 .. n - 1: LMX_EINVAL names the first index that is out of range, repeated or out of
+ *                   order (`what`: the list's name for the message). */
+enum { LMX_REC_U8 = 0, LMX_REC_I32 = 1, LMX_REC_I64 = 2, LMX_REC_F32 = 3 }; /* lmx_record_field_layout_t.dtype */
+enum { LMX_STREAMS_LANES = 0, LMX_STREAMS_RR = 1 };                          /* lmx_h_stream_plan's layout */
+typedef struct { char name[16]; int32_t dtype, ndim; int64_t shape[2], offset, nbytes; } lmx_record_field_layout_t;
+typedef struct { int32_t n_fields, reserved; int64_t stride; lmx_record_field_layout_t fields[LMX_RECORD_MAX_FIELDS]; } lmx_record_layout_t;
+int lmx_h_record_layout(int h, int w, int hidden, int max_det, int scheduled, lmx_record_layout_t* out_host);
+int lmx_h_stream_plan(int n_chunks, int max_streams, int layout, int* pool_host, int* det_host, int* emb_host, int32_t* sam_host);
+int lmx_h_row_map(int n, const int32_t* idx_host, int n_idx, const char* what, int32_t* map_host, int32_t* ran_host);
 
 /* ---- contour features ON THE DEVICE ---------------------------------------------------------
  * The cv2 part of extract_segmentation_features (sam3 main.py:118-135): findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE),
@@ -767,6 +806,70 @@ int lmx_sam_segment(lmx_sam* m, const uint8_t* frames, int n, int h, int w, cons
 int lmx_sam_segment_host(lmx_sam* m, const uint8_t* frames_host, int n, int h, int w, const float* boxes_host, int precision,
                          uint8_t* mask_host, uint8_t* mask_bits_host, int64_t* stats_host, int64_t* contour_host, float* iou_host,
                          float* lowres_host);
+
+/* ==== MODEL level: the fused per-frame path, frames to records (csrc/fused_model.hip, csrc/sam_lanes.h, csrc/records.hip) ===========
+ * What a consumer of all three services does per frame — yolo main.py:74-76 (detect), sam3 main.py:199-206 (the first, highest-
+ * confidence detection is SAM's box prompt) and :74-92 (mask), :118-135 (its statistics and contour features), dinov3 main.py:98-113
+ * (embedding) — behind ONE handle and one call: the launch sequence of lmx/pipeline.py's FusedExtractor.step (BASELINE cfg#5) written in
+ * C++ over the three model handles above, ending in the fixed-stride record of lmx.dist.pack_records (SURVEY.md §8b `lmx_init ..
+ * lmx_allgather_results`: one context, frames in, per-frame results out).  Same launches on the same kind of streams, same bytes as
+ * dist.pack_records(FusedExtractor.step(...)) without the byte masks, on both precision plans (tests/test_gpu_native_fused.py).
+ * Streams: lmx_fused_step enqueues on internal streams of the handle, laid out as lmx_h_stream_plan(passes, min(max_streams,
+ * 2 + sam_lanes), LMX_STREAMS_LANES): YOLO on one, DINO on one, the SAM passes of sam_chunk frames dealt over the rest.  Every internal
+ * stream first waits for an event recorded on the caller's `stream`; a SAM pass runs its encoder at once and waits for YOLO's event in
+ * front of its decoder, which reads each frame's top box straight from YOLO's boxes; `stream` then waits for every internal stream and
+ * runs lmx_k_pack_records into `records`.  Each stream of SAM passes has a workspace lane of its own over ONE weight upload, so sam_lanes
+ * passes are in flight together.  Streams and events are created at open (events without timing); a step creates nothing.
+ * The record: lmx_fused_layout — the int64 `valid` word, then boxes f32 [300][4], cls i32 [300], counts i32, embedding f32 [hidden],
+ * mask_bits u8 [h][ceil(w/8)], mask_contour i64 [8], mask_iou f32, mask_stats i64 [8], (scheduled: ran_det i32, ran_emb i32,) scores
+ * f32 [300], each at the next multiple of 8 bytes.  max_det = 300 and the NMS IoU 0.7 are YoloDetector.detect's defaults.
+ * Handle rules as for the model handles: the handle belongs to the device current at lmx_fused_open_host; ONE host thread and ONE STEP
+ * in flight per handle — the previous lmx_fused_step must have FINISHED on the device (not merely been enqueued) before the next call,
+ * lmx_fused_schedule or lmx_fused_prepare: all steps write the handle's workspaces.  Errors: LMX_EINVAL / LMX_EHIP with lmx_last_error().
+ * OUT OF SCOPE: the byte masks, pose keypoints in the record (a Pose image is refused at open), point or mask prompts, RCCL inside the
+ * library (the records are what a caller's gather moves), HIP graph capture of a step. */
+typedef struct lmx_fused lmx_fused;
+typedef struct { lmx_yolo_info_t yolo; lmx_sam_info_t sam; lmx_dino_info_t dino; int32_t hidden, max_det, max_frames, sam_chunk, sam_lanes, max_streams; } lmx_fused_info_t;
+/* SYNCHRONOUS (the three `from_pretrained` / `YOLO(path)` / `sam_model_registry` loads behind yolo main.py:76, sam3 main.py:74-92 and
+ * dinov3 main.py:34-36): validate and upload the three weight images on the CURRENT device (YOLO and DINO for max_frames frames a call,
+ * SAM for passes of sam_chunk frames), create 2 + sam_lanes streams and their events.  sam_lanes 1 .. 16; max_streams 1 .. 64 bounds
+ * the streams a step uses (FusedExtractor's LMX_MAX_STREAMS; at least 3 are used).  *out_host is NULL after any failure, with nothing
+ * left allocated. */
+int lmx_fused_open_host(const char* yolo_image, const char* sam_image, const char* dino_image, int max_frames, int sam_chunk, int sam_lanes,
+                        int max_streams, lmx_fused** out_host);
+/* the end of the models behind yolo main.py:76, sam3 main.py:74-92 and dinov3 main.py:98-113: waits for the device, then frees
+ * everything the handle owns, the three model handles included; NULL is allowed */
+void lmx_fused_close(lmx_fused* m);
+/* the configurations of the three models (yolo main.py:76, sam3 main.py:74-92, dinov3 main.py:77 for hidden), max_det = 300 and the
+ * handle's max_frames, sam_chunk, sam_lanes, max_streams */
+int lmx_fused_info(const lmx_fused* m, lmx_fused_info_t* info_host);
+/* host arithmetic only (the result rows the services return per frame: yolo main.py:74-76, sam3 main.py:83-89 and :118-135, dinov3
+ * main.py:113): lmx_h_record_layout for this handle's hidden and max_det */
+int lmx_fused_layout(const lmx_fused* m, int h, int w, int scheduled, lmx_record_layout_t* out_host);
+/* SYNCHRONOUS (what yolo main.py:76, sam3 main.py:74-92 and dinov3 main.py:107 derive from the frame size): lmx_yolo_prepare,
+ * lmx_dino_prepare, lmx_sam_prepare for EVERY lane, and the step's output buffers of max_frames rows.  LMX_EINVAL for a plan either
+ * image does not hold (checked before anything is allocated), for frames outside 2 x 2 .. 2^21 - 1 pixels (the contour features' range),
+ * and for what the three prepares refuse. */
+int lmx_fused_prepare(lmx_fused* m, int h, int w, int precision);
+/* SYNCHRONOUS (the reference schedule: yolo main.py:74 runs YOLO + SAM, dinov3 main.py:127 runs DINO, each on a subset of the sampled
+ * frames): later steps of n frames gather the frames det_idx_host int32 [n_det] / emb_idx_host [n_emb] name, run the dense sequence on
+ * them and scatter the rows back through row maps (lmx_h_row_map builds them here, this call uploads them); the record gains ran_det /
+ * ran_emb, and a frame in neither list is a zero row with valid = 1, as in FusedExtractor.step.  A count of -1 leaves that list out
+ * (every frame, read in place); n_det = n_emb = -1 clears the schedule: dense steps again.  LMX_EINVAL names an index that is out of
+ * range, repeated or out of order. */
+int lmx_fused_schedule(lmx_fused* m, int n, const int32_t* det_idx_host, int n_det, const int32_t* emb_idx_host, int n_emb);
+/* yolo main.py:74-76, sam3 main.py:199-206, :74-92 and :118-135, dinov3 main.py:98-113 for n <= max_frames frames: frames u8
+ * [n][h][w][3] BGR on the device -> records u8 [n_rows][stride] on the device, row r = frame r; n_rows >= n, the rows from n on are
+ * padding (valid = 0, zeros: what a shard of a multi-GPU gather pads with); n = 0 writes padding only.  conf: YOLO's confidence
+ * threshold; a frame without a detection is decoded against an all-zero box and has counts = 0.  For a (size, precision) already
+ * prepared the call ONLY ENQUEUES (on `stream` and the internal streams): no allocation, no synchronisation; the first call for a new
+ * pair runs lmx_fused_prepare itself, and THAT call synchronises.  `records` needs no clearing.  ONE step in flight per handle (above). */
+int lmx_fused_step(lmx_fused* m, const uint8_t* frames, int n, int h, int w, int precision, float conf, uint8_t* records, int64_t n_rows,
+                   lmx_stream_t stream);
+/* the same (yolo main.py:74-76, sam3 main.py:74-92, dinov3 main.py:98-113) for a caller with no HIP code of its own: frames_host and
+ * records_host are HOST memory; uploads, steps, downloads the records in ONE copy and synchronises (examples/fused_extract.c). */
+int lmx_fused_step_host(lmx_fused* m, const uint8_t* frames_host, int n, int h, int w, int precision, float conf, uint8_t* records_host,
+                        int64_t n_rows);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,8 @@
 // slices of qkv, q3[:, k].contiguous(), iou[:, 0] — is a leading dimension or a strided copy on the call's stream here.
 // An image whose encoder is Hiera runs sam_hiera_model.h's launch plan in place of the ViT's (encode_chunk branches after the resize);
 // its embedding is f16 under both plans, which the exact decoder's first lmx_k_add_bcast takes as such.
+// The fused handle (fused_model.hip) keeps several passes in flight on one handle: sam_lanes.h, at the end of this file, gives it further
+// workspaces (lanes) over the same weights and the two halves of a pass; the public calls keep lane 0 and their one-stream rule.
 // OUT OF SCOPE: point and mask-input prompts, multimask output, SamAutomaticMaskGenerator, outputs="all" of the Hiera encoder, HIP
 // graph capture.
 #include <math.h>
@@ -22,6 +24,7 @@
 #include "model_handle.h"
 #include "sam_hiera_model.h"
 #include "sam_image.h"
+#include "sam_lanes.h"
 
 namespace {
 
@@ -96,7 +99,8 @@ struct lmx_sam : LmxHandleCore {
   const float *gauss = nullptr, *corner = nullptr, *key_pe = nullptr, *no_mask = nullptr, *out_tokens = nullptr;
   DecPlan dec[2];
   Norm ln_final, up_ln;
-  std::map<std::tuple<int, int, int>, Prepared> prepared;
+  std::map<std::tuple<int, int, int>, Prepared> prepared;               // lane 0: the workspace of the public lmx_sam_* calls
+  std::map<std::tuple<int, int, int>, std::vector<Prepared>> more_lanes;  // lanes 1 ..: further workspaces over the same weights (sam_lanes.h)
   HieraW hiera;                                                // encoder Hiera
   std::map<std::pair<int, int>, HieraBandTable> band_tables;  // ... per resized geometry (nh, nw), shared by both plans
   bool is_hiera() const { return cfg.encoder == LMX_SAM_ENC_HIERA; }
@@ -106,6 +110,8 @@ namespace {
 
 void destroy(lmx_sam* m) {
   for (auto& kv : m->prepared) (void)hipFree(kv.second.blob);
+  for (auto& kv : m->more_lanes)
+    for (Prepared& P : kv.second) (void)hipFree(P.blob);
   for (auto& kv : m->band_tables) (void)hipFree(kv.second.blob);
   lmx_handle_free(m);
   delete m;
@@ -368,21 +374,13 @@ int hiera_prepare(lmx_sam* m, int nh, int nw, Prepared* P, int64_t* patch_bytes)
   return LMX_OK;
 }
 
-int prepare(lmx_sam* m, int h, int w, int precision, const Prepared** out) {
-  const auto key = std::make_tuple(h, w, precision);
-  const auto it = m->prepared.find(key);
-  if (it != m->prepared.end()) {
-    if (out) *out = &it->second;
-    return LMX_OK;
-  }
-  LMX_TRY(check_precision(m, "lmx_sam_prepare", precision));
+// one workspace of max_batch frames for (h, w, precision): what lmx_sam_prepare keeps as lane 0 and lmx_sam_lanes_prepare as every further lane
+int build(lmx_sam* m, int h, int w, int precision, Prepared* built) {
   const LmxSamCfg& c = m->cfg;
   Prepared P;
   memset(&P, 0, sizeof(P));
   lmx_sam_resized_hw(c.image, h, w, &P.nh, &P.nw);
   LMX_REQUIRE(P.nh >= 1 && P.nw >= 1 && P.nh <= c.image && P.nw <= c.image, "lmx_sam_prepare: a %d x %d frame resizes to %d x %d", h, w, P.nh, P.nw);
-  LMX_REQUIRE((int)m->prepared.size() < LMX_MAX_PREPARED, "lmx_sam_prepare: the handle already holds %d (frame size, plan) pairs; open another for more",
-              LMX_MAX_PREPARED);
   const int nh = P.nh, nw = P.nw;
   std::vector<int32_t> bh, kh, bv, kv;
   LMX_TRY(pil_axis(w, nw, &bh, &kh, &P.ksize_h));
@@ -491,6 +489,22 @@ int prepare(lmx_sam* m, int h, int w, int precision, const Prepared** out) {
     (void)hipFree(P.blob);
     LMX_HIP(err);
   }
+  *built = P;
+  return LMX_OK;
+}
+
+int prepare(lmx_sam* m, int h, int w, int precision, const Prepared** out) {
+  const auto key = std::make_tuple(h, w, precision);
+  const auto it = m->prepared.find(key);
+  if (it != m->prepared.end()) {
+    if (out) *out = &it->second;
+    return LMX_OK;
+  }
+  LMX_TRY(check_precision(m, "lmx_sam_prepare", precision));
+  LMX_REQUIRE((int)m->prepared.size() < LMX_MAX_PREPARED, "lmx_sam_prepare: the handle already holds %d (frame size, plan) pairs; open another for more",
+              LMX_MAX_PREPARED);
+  Prepared P;
+  LMX_TRY(build(m, h, w, precision, &P));
   const auto ins = m->prepared.emplace(key, P);
   if (out) *out = &ins.first->second;
   return LMX_OK;
@@ -819,13 +833,13 @@ struct Dec {
 };
 
 // MaskDecoder.predict (+ pack_bits, contour_features) for n <= max_batch frames, writing the chunk's rows of the outputs
-int decode_chunk(const lmx_sam* m, const Prepared& P, int precision, const void* emb, int n, int h, int w, const float* boxes, uint8_t* mask,
+int decode_chunk(const lmx_sam* m, const Prepared& P, int precision, const void* emb, int n, int h, int w, const float* boxes, int64_t ldb, uint8_t* mask,
                  uint8_t* mask_bits, int64_t* stats, int64_t* contour, float* iou, float* lowres, hipStream_t st) {
   const LmxSamCfg& c = m->cfg;
   const int L = 4 * c.grid();
   uint8_t* mk = mask ? mask : P.mask;
   float* logits = lowres ? lowres : P.logits;
-  LMX_TRY(lmx_k_prompt_box(boxes, 4, P.sparse, n, (double)P.nw / (double)w, (double)P.nh / (double)h, (float)c.image, m->gauss, m->corner, DD / 2, st));
+  LMX_TRY(lmx_k_prompt_box(boxes, ldb, P.sparse, n, (double)P.nw / (double)w, (double)P.nh / (double)h, (float)c.image, m->gauss, m->corner, DD / 2, st));
   // torch.cat([out_tokens, sparse], 1): the output-token rows are in place since prepare
   LMX_HIP(hipMemcpy2DAsync(P.tokens + LMX_SAM_OUT_TOKENS * DD, (size_t)DT * DD * 4, P.sparse, (size_t)2 * DD * 4, (size_t)2 * DD * 4, (size_t)n,
                            hipMemcpyDeviceToDevice, st));
@@ -857,7 +871,63 @@ int check_decode(const lmx_sam* m, const char* fn, const void* in, const char* i
   return LMX_OK;
 }
 
+// the workspace of `lane` for a prepared (size, plan): a lookup, never an allocation
+int lane_of(const lmx_sam* m, const char* fn, int lane, int h, int w, int precision, const Prepared** out) {
+  const auto key = std::make_tuple(h, w, precision);
+  if (lane == 0) {
+    const auto it = m->prepared.find(key);
+    LMX_REQUIRE(it != m->prepared.end(), "%s: lane 0 of a %d x %d frame under precision %d is not prepared", fn, h, w, precision);
+    *out = &it->second;
+    return LMX_OK;
+  }
+  const auto it = m->more_lanes.find(key);
+  LMX_REQUIRE(it != m->more_lanes.end() && lane >= 1 && lane <= (int)it->second.size(), "%s: lane %d of a %d x %d frame under precision %d is not prepared", fn,
+              lane, h, w, precision);
+  *out = &it->second[(size_t)lane - 1];
+  return LMX_OK;
+}
+
 }  // namespace
+
+// ---- sam_lanes.h: several passes in flight over one weight upload ------------------------------------------------------------------
+int lmx_sam_lanes_ready(const lmx_sam* m, int h, int w, int precision, int lanes) {
+  const auto key = std::make_tuple(h, w, precision);
+  if (!m->prepared.count(key)) return 0;
+  if (lanes <= 1) return 1;
+  const auto it = m->more_lanes.find(key);
+  return it != m->more_lanes.end() && (int)it->second.size() >= lanes - 1;
+}
+
+int lmx_sam_lanes_prepare(lmx_sam* m, int h, int w, int precision, int lanes) {
+  LMX_TRY(lmx_handle_on_device(m, "lmx_sam_lanes_prepare"));
+  LMX_REQUIRE(h > 0 && w > 0, "lmx_sam_lanes_prepare: frame size %d x %d", h, w);
+  LMX_REQUIRE(lanes >= 1 && lanes <= LMX_SAM_MAX_LANES, "lmx_sam_lanes_prepare: %d lanes outside 1 .. %d", lanes, LMX_SAM_MAX_LANES);
+  LMX_TRY(prepare(m, h, w, precision, nullptr));  // lane 0, with every check of lmx_sam_prepare
+  std::vector<Prepared>& more = m->more_lanes[std::make_tuple(h, w, precision)];
+  while ((int)more.size() < lanes - 1) {
+    Prepared P;
+    LMX_TRY(build(m, h, w, precision, &P));
+    more.push_back(P);
+  }
+  return LMX_OK;
+}
+
+int lmx_sam_lane_encode(lmx_sam* m, int lane, const uint8_t* frames, int n, int h, int w, int precision, hipStream_t st) {
+  const Prepared* P = nullptr;
+  LMX_TRY(lane_of(m, "lmx_sam_lane_encode", lane, h, w, precision, &P));
+  LMX_REQUIRE(frames != nullptr && n > 0 && n <= m->max_batch, "lmx_sam_lane_encode: %d frames at %p for a lane of %d", n, (const void*)frames, m->max_batch);
+  return encode_chunk(m, *P, precision, frames, n, h, w, P->emb, st);
+}
+
+int lmx_sam_lane_decode(lmx_sam* m, int lane, int n, int h, int w, const float* boxes, int64_t ldb, int precision, uint8_t* mask_bits, int64_t* stats,
+                        int64_t* contour, float* iou, hipStream_t st) {
+  const Prepared* P = nullptr;
+  LMX_TRY(lane_of(m, "lmx_sam_lane_decode", lane, h, w, precision, &P));
+  LMX_REQUIRE(n > 0 && n <= m->max_batch, "lmx_sam_lane_decode: %d frames for a lane of %d", n, m->max_batch);
+  LMX_REQUIRE(boxes && ldb >= 4 && stats && iou, "lmx_sam_lane_decode: null pointer, or a box row stride of %lld floats", (long long)ldb);
+  LMX_REQUIRE(!contour || P->contour_ws, "lmx_sam_lane_decode: contour features are served for frames of 2 x 2 up to 2^21 - 1 pixels, not %d x %d", h, w);
+  return decode_chunk(m, *P, precision, P->emb, n, h, w, boxes, ldb, nullptr, mask_bits, stats, contour, iou, nullptr, st);
+}
 
 extern "C" int lmx_sam_open_host(const char* path_host, int max_batch, lmx_sam** out_host) {
   return lmx_handle_open("lmx_sam_open_host", path_host, max_batch, out_host, open_into, destroy);
@@ -911,7 +981,7 @@ static int run(lmx_sam* m, const Prepared& P, const uint8_t* frames, const void*
     const size_t d = (size_t)done;
     const void* e = emb ? static_cast<const char*>(emb) + d * emb_bytes : P.emb;
     if (frames) LMX_TRY(encode_chunk(m, P, precision, frames + d * frame_bytes, nb, h, w, P.emb, st));
-    LMX_TRY(decode_chunk(m, P, precision, e, nb, h, w, boxes + d * 4, mask ? mask + d * px : nullptr, mask_bits ? mask_bits + d * h * wb : nullptr,
+    LMX_TRY(decode_chunk(m, P, precision, e, nb, h, w, boxes + d * 4, 4, mask ? mask + d * px : nullptr, mask_bits ? mask_bits + d * h * wb : nullptr,
                          stats + d * 8, contour ? contour + d * 8 : nullptr, iou + d, lowres ? lowres + d * LL : nullptr, st));
   }
   return LMX_OK;

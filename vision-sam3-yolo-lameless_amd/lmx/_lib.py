@@ -39,6 +39,11 @@ class SamInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("encoder", "hidden", "heads", "layers", "mlp", "window", "patch", "image", "plans", "max_batch")]
 
 
+class FusedInfo(C.Structure):  # lmx_fused_info_t
+    _fields_ = [("yolo", YoloInfo), ("sam", SamInfo), ("dino", DinoInfo)] + [(n, C.c_int32) for n in ("hidden", "max_det", "max_frames", "sam_chunk",
+                                                                                                        "sam_lanes", "max_streams")]
+
+
 class HieraConfig(C.Structure):  # lmx_hiera_config_t
     MAX_STAGES, MAX_GLOBAL, MAX_BLOCKS = 8, 32, 256
     _fields_ = [("hidden", C.c_int32), ("n_stages", C.c_int32), ("blocks", C.c_int32 * 8), ("dims", C.c_int32 * 8), ("heads", C.c_int32 * 8),
@@ -50,6 +55,20 @@ class HieraConfig(C.Structure):  # lmx_hiera_config_t
 class HieraBlock(C.Structure):  # lmx_hiera_block_t: lmx.sam.BlockPlan's fields in its order
     _fields_ = [(n, C.c_int32) for n in ("H", "W", "Hf", "Ho", "Wo", "Hfo", "join", "attn", "ln1", "shortcut", "query", "window", "ln_out", "mlp",
                                          "emit_ln1", "stage_end", "keep", "x16", "join_out", "clone")]
+
+
+class RecordField(C.Structure):  # lmx_record_field_t
+    _fields_ = [("src", C.c_void_p), ("row_bytes", C.c_int64), ("offset", C.c_int64), ("map", C.c_int32), ("n_src", C.c_int32)]
+
+
+class RecordFieldLayout(C.Structure):  # lmx_record_field_layout_t
+    _fields_ = [("name", C.c_char * 16), ("dtype", C.c_int32), ("ndim", C.c_int32), ("shape", C.c_int64 * 2), ("offset", C.c_int64),
+                ("nbytes", C.c_int64)]
+
+
+class RecordLayout(C.Structure):  # lmx_record_layout_t
+    MAX_FIELDS, MAX_MAPS = 16, 4
+    _fields_ = [("n_fields", C.c_int32), ("reserved", C.c_int32), ("stride", C.c_int64), ("fields", RecordFieldLayout * 16)]
 
 
 class LetterboxGeo(C.Structure):
@@ -81,6 +100,10 @@ SIGNATURES = {
     "lmx_h_layernorm_route": (_I, [_I, _I, _I, _I, _I, C.c_char_p, _I]),
     "lmx_k_pose_gather": (_I, [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _F, _F, _F, _F, _F, _VP, _VP]),
     "lmx_k_pack_bits": (_I, [_VP, _I64, _I, _VP, _VP]),
+    "lmx_k_pack_records": (_I, [C.POINTER(RecordField), _I, C.POINTER(_VP), _I, _I64, _I64, _I64, _VP, _VP]),
+    "lmx_h_record_layout": (_I, [_I, _I, _I, _I, _I, C.POINTER(RecordLayout)]),
+    "lmx_h_stream_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
+    "lmx_h_row_map": (_I, [_I, C.POINTER(C.c_int32), _I, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lmx_k_ln_mlp": (_I, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _F, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lmx_k_hiera_attn8": (_I, [_VP, _VP, _I64, _VP, _VP, _F, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _VP]),
     "lmx_k_hiera_attn4": (_I, [_VP, _VP, _I64, _VP, _VP, _I, _I, _I, _I, _I, _F, _VP]),
@@ -169,6 +192,14 @@ SIGNATURES = {
     "lmx_sam_decode": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lmx_sam_segment": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lmx_sam_segment_host": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_fused_open_host": (_I, [C.c_char_p, C.c_char_p, C.c_char_p, _I, _I, _I, _I, C.POINTER(_VP)]),
+    "lmx_fused_close": (None, [_VP]),
+    "lmx_fused_info": (_I, [_VP, C.POINTER(FusedInfo)]),
+    "lmx_fused_layout": (_I, [_VP, _I, _I, _I, C.POINTER(RecordLayout)]),
+    "lmx_fused_prepare": (_I, [_VP, _I, _I, _I]),
+    "lmx_fused_schedule": (_I, [_VP, _I, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), _I]),
+    "lmx_fused_step": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP, _I64, _VP]),
+    "lmx_fused_step_host": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP, _I64]),
 }
 
 _lib = None

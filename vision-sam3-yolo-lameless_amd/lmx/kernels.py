@@ -417,6 +417,98 @@ def pack_bits(mask):
     return out
 
 
+def pack_records(rec, n_rows=None, row_maps=(), field_map=None, n_valid=None, out=None):
+    """dict of per-frame tensors [n_k, ...] on one device -> (uint8 [n_rows, stride], layout): lmx.dist.pack_records' bytes from ONE
+    launch that stores every byte of the matrix once (csrc/records.hip); `out` (uint8 [n_rows, stride], contiguous) needs no clearing.
+    Without maps every field has the same n rows, record row r is row r of each field and n_rows - n padding rows follow.
+    row_maps: int32 [n_valid] device tensors, entry r = the source row of record row r or -1 (zeros); field_map: {name: index into
+    row_maps} for the fields that follow one (the others keep the identity and give zeros past their last row); n_valid: rows whose
+    `valid` word is 1 (default: the fields' row count without maps, n_rows with them); the rows behind them are padding, all zeros."""
+    from . import dist
+
+    names = sorted(rec)
+    dev = _dev(*[rec[k] for k in names], *row_maps)
+    field_map = dict(field_map or {})
+    rows = {k: int(rec[k].shape[0]) for k in names}
+    n = max(rows.values()) if not row_maps else None
+    if n_rows is None:
+        if n is None:
+            raise LmxError("pack_records: n_rows is needed with row maps")
+        n_rows = n
+    n_rows = int(n_rows)
+    if n_valid is None:
+        n_valid = n if n is not None else n_rows
+    layout, stride = dist.record_layout(rec)
+    if len(layout) > _lib.RecordLayout.MAX_FIELDS or len(row_maps) > _lib.RecordLayout.MAX_MAPS:
+        raise LmxError(f"pack_records: {len(layout)} fields and {len(row_maps)} maps; at most {_lib.RecordLayout.MAX_FIELDS} and {_lib.RecordLayout.MAX_MAPS}")
+    if not row_maps:
+        for k in names:
+            if rows[k] != n:
+                raise LmxError(f"pack_records: field {k} has {rows[k]} rows, expected {n}")
+        if n_rows < n:
+            raise LmxError(f"pack_records: {n} records do not fit {n_rows} rows")
+    for m in row_maps:
+        if m.dtype != torch.int32 or m.dim() != 1 or int(m.shape[0]) != n_valid or not m.is_contiguous():
+            raise LmxError(f"pack_records: a row map is a contiguous int32 [{n_valid}] tensor (one entry per valid row)")
+    keep = []  # the dense views the launch reads
+    fields = (_lib.RecordField * max(1, len(layout)))()
+    for f, (name, dtype, tail, off, nb) in zip(fields, layout):
+        src = rec[name].contiguous()
+        keep.append(src)
+        which = field_map.pop(name, -1)
+        if not -1 <= which < len(row_maps):
+            raise LmxError(f"pack_records: field {name} follows map {which} of {len(row_maps)}")
+        if nb == 0:
+            raise LmxError(f"pack_records: field {name} has empty rows")
+        f.src, f.row_bytes, f.offset, f.map, f.n_src = src.data_ptr() if rows[name] else None, nb, off, which, rows[name]
+    if field_map:
+        raise LmxError(f"pack_records: field_map names {sorted(field_map)}, which the record does not hold")
+    if out is None:
+        out = torch.empty((n_rows, stride), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n_rows, stride) or not out.is_contiguous() or out.device != dev:
+        raise LmxError(f"pack_records: out must be a contiguous uint8 [{n_rows}, {stride}] tensor on {dev}")
+    maps = (C.c_void_p * max(1, len(row_maps)))(*[m.data_ptr() for m in row_maps])
+    check(_lib.load().lmx_k_pack_records(fields, len(layout), maps, len(row_maps), n_valid, n_rows, stride, _ptr(out), _stream(dev)),
+          "lmx_k_pack_records")
+    return out, layout
+
+
+_REC_DTYPES = (torch.uint8, torch.int32, torch.int64, torch.float32)  # LMX_REC_*
+
+
+def layout_of(lay):
+    """a lmx_record_layout_t as lmx.dist.record_layout gives it: ([(name, dtype, tail shape, byte offset, bytes)], stride)"""
+    fields = [lay.fields[i] for i in range(lay.n_fields)]
+    return [(f.name.decode(), _REC_DTYPES[f.dtype], tuple(int(f.shape[d]) for d in range(f.ndim)), int(f.offset), int(f.nbytes)) for f in fields], int(lay.stride)
+
+
+def record_layout(h, w, hidden, max_det=300, scheduled=False):
+    """lmx_h_record_layout: (layout, stride) of the fused step's record in lmx.dist.record_layout's form, computed by the library."""
+    lay = _lib.RecordLayout()
+    check(_lib.load().lmx_h_record_layout(int(h), int(w), int(hidden), int(max_det), int(bool(scheduled)), C.byref(lay)), "lmx_h_record_layout")
+    return layout_of(lay)
+
+
+def stream_plan(n_chunks, max_streams=4, layout="lanes"):
+    """lmx_h_stream_plan: lmx.pipeline.stream_plan computed by the library."""
+    if layout not in ("lanes", "rr"):
+        raise ValueError(f"stream layout {layout!r}: expected 'lanes' or 'rr'")
+    pool, det, emb = C.c_int(0), C.c_int(0), C.c_int(0)
+    sam = (C.c_int32 * max(1, n_chunks))()
+    check(_lib.load().lmx_h_stream_plan(int(n_chunks), int(max_streams), ("lanes", "rr").index(layout), C.byref(pool), C.byref(det), C.byref(emb), sam),
+          "lmx_h_stream_plan")
+    return pool.value, det.value, emb.value, list(sam)[:n_chunks]
+
+
+def row_map(n, idx, what="idx"):
+    """lmx_h_row_map: (map, ran) int32 lists of n entries for the ascending frame indices `idx` (LmxError names a bad index)."""
+    idx = [int(i) for i in idx]
+    arr = (C.c_int32 * max(1, len(idx)))(*idx)
+    m, ran = (C.c_int32 * max(1, n))(), (C.c_int32 * max(1, n))()
+    check(_lib.load().lmx_h_row_map(int(n), arr, len(idx), what.encode(), m, ran), "lmx_h_row_map")
+    return list(m)[:n], list(ran)[:n]
+
+
 FUSED_MLP_WIDTHS = (112, 224)  # (448 exists as a development configuration: no faster than the unfused launches, csrc/mlp.hip)
 if os.environ.get("LMX_MLP448"):  # development A/B only
     FUSED_MLP_WIDTHS = (112, 224, 448)

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, letterbox, resample
-from ._lib import DinoInfo, LetterboxGeo, LmxError, SamInfo, YoloInfo, check
+from ._lib import DinoInfo, FusedInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, YoloInfo, check
 
 MAGIC = b"LMXIMAGE"
 VERSION = 1
@@ -699,3 +699,84 @@ class NativeSam(_NativeHandle):
             check(self._lib.lmx_sam_segment_host(self._handle(), a.ctypes.data, n, h, w, b.ctypes.data, PLANS[precision], ptr["mask"], ptr["mask_bits"],
                                                  ptr["stats"], ptr["contour"], ptr["iou"], ptr["lowres"]), "lmx_sam_segment_host")
         return {k: t for k, t in out.items() if t is not None}
+
+
+
+class NativeFused(_NativeHandle):
+    """lmx_fused_open_host: the fused per-frame path (lmx.pipeline.FusedExtractor.step + lmx.dist.pack_records) behind one handle over
+    a YOLO, a SAM and a DINO weight image, on `device` (default: torch's current device).  Steps of up to max_frames frames; SAM runs
+    in passes of sam_chunk frames, sam_lanes of them in flight.  `precision`: "f16" or "exact".  Every step gives (records uint8
+    [rows, stride], layout) with the layout in the form lmx.dist.unpack_records takes.  ONE step in flight per handle: synchronise the
+    stream of a step before the next step, schedule() or prepare()."""
+    _PREFIX, _INFO = "lmx_fused_", FusedInfo
+
+    def __init__(self, yolo_path, sam_path, dino_path, max_frames, sam_chunk, sam_lanes=2, max_streams=7, device=None):
+        self._lib = _lib.load()
+        self._h = None
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise LmxError(f"NativeFused: {self.device} is not a GPU")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        h = C.c_void_p(0)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_fused_open_host(str(yolo_path).encode(), str(sam_path).encode(), str(dino_path).encode(), int(max_frames), int(sam_chunk),
+                                                int(sam_lanes), int(max_streams), C.byref(h)), "lmx_fused_open_host")
+        self._h = h
+        self.info = FusedInfo()
+        check(self._lib.lmx_fused_info(self._h, C.byref(self.info)), "lmx_fused_info")
+        self.scheduled = False
+
+    def layout(self, h, w, scheduled=None):
+        """lmx_fused_layout -> (layout, stride): the record of an h x w frame (scheduled: None = as the handle's schedule stands)."""
+        from . import kernels as K
+
+        lay = RecordLayout()
+        sch = self.scheduled if scheduled is None else bool(scheduled)
+        check(self._lib.lmx_fused_layout(self._handle(), int(h), int(w), int(sch), C.byref(lay)), "lmx_fused_layout")
+        return K.layout_of(lay)
+
+    def prepare(self, h, w, precision):
+        """lmx_fused_prepare: the three models' tables and workspaces, every SAM lane and the step's buffers for one (frame size, plan)
+        (synchronous); step() of that pair then only enqueues."""
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_fused_prepare(self._handle(), int(h), int(w), PLANS[precision]), "lmx_fused_prepare")
+
+    def schedule(self, n, det_idx=None, emb_idx=None):
+        """lmx_fused_schedule: the reference schedule for later steps of n frames (FusedExtractor.step's det_idx / emb_idx; None: every
+        frame); both None clears it (dense steps).  Synchronous."""
+        def arr(idx):
+            if idx is None:
+                return None, -1
+            idx = [int(i) for i in idx]
+            return (C.c_int32 * max(1, len(idx)))(*idx), len(idx)
+
+        (d, nd), (e, ne) = arr(det_idx), arr(emb_idx)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_fused_schedule(self._handle(), int(n), d, nd, e, ne), "lmx_fused_schedule")
+        self.scheduled = not (det_idx is None and emb_idx is None)
+
+    def step(self, frames, precision, conf=0.5, n_rows=None):
+        """u8 BGR [n,h,w,3] device tensor -> (records uint8 [n_rows, stride] on the device, layout), enqueued on torch's current stream
+        of that device (lmx_fused_step); n_rows (default n) >= n, the rows from n on are padding."""
+        n, h, w = self._device_frames(frames, "step")
+        n_rows = n if n_rows is None else int(n_rows)
+        layout, stride = self.layout(h, w)
+        records = torch.empty((max(n_rows, 0), stride), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_fused_step(self._handle(), C.c_void_p(frames.data_ptr()), n, h, w, PLANS[precision], float(conf),
+                                           C.c_void_p(records.data_ptr()), n_rows, st), "lmx_fused_step")
+        return records, layout
+
+    def step_host(self, frames, precision, conf=0.5, n_rows=None):
+        """u8 BGR [n,h,w,3] numpy array -> (records uint8 [n_rows, stride] numpy array, layout) (lmx_fused_step_host: uploads, steps,
+        downloads the records in one copy, synchronises)."""
+        a, n, h, w = self._host_frames(frames, "step_host")
+        n_rows = n if n_rows is None else int(n_rows)
+        layout, stride = self.layout(h, w)
+        records = np.empty((max(n_rows, 0), stride), np.uint8)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_fused_step_host(self._handle(), a.ctypes.data, n, h, w, PLANS[precision], float(conf), records.ctypes.data, n_rows),
+                  "lmx_fused_step_host")
+        return records, layout
