@@ -292,6 +292,32 @@ int lmx_k_float_resize_patchify(const uint8_t* src, void* out, int n, int sh, in
                                 const float* kk_v, int ksize_v, int seg_cols, float rescale, const float* mean_std,
                                 int swap_rb, lmx_stream_t stream);
 
+/* ---- frames from a decoder: YUV 4:2:0 (NV12 / I420) -> packed BGR u8 [n][h][w][3], the format every entry point here takes ------
+ * Replaces the colour conversion `cv2.VideoCapture.read()` hides in front of yolo main.py:76, sam3 main.py:80 and dinov3 main.py:98-99:
+ * a software H.264 decoder leaves planar I420, a hardware decoder (VCN through rocDecode or VA-API) a pitched NV12 surface.  The
+ * arithmetic is the public integer form of cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420) — limited range, 20-bit fixed point, nearest
+ * chroma — and is defined HERE (cv2 is not installed: PARITY UNPINNED against real OpenCV and swscale).  For pixel (x, y), h and w even:
+ *   Y = y[y * pitch_y + x];  NV12: U = u[(y >> 1) * pitch_c + 2 * (x >> 1)], V = the byte after it;
+ *                            I420: U = u[(y >> 1) * pitch_c + (x >> 1)],     V = v[the same offset]
+ *   yy = max(0, Y - 16) * CY;  B = sat8((yy + CUB * (U - 128) + 2^19) >> 20)                      (signed 32-bit, arithmetic shift)
+ *   G = sat8((yy + CUG * (U - 128) + CVG * (V - 128) + 2^19) >> 20);  R = sat8((yy + CVR * (V - 128) + 2^19) >> 20);  out = (B, G, R)
+ *   CY, CUB, CUG, CVG, CVR = round(c * 2^20) of 1.164, 2.018, -0.391, -0.813, 1.596 (LMX_YUV_BT601, cv2's constants: 1220542, 2116026,
+ *   -409993, -852492, 1673527) or of 1.164, 2.112, -0.213, -0.533, 1.793 (LMX_YUV_BT709: 1220542, 2214593, -223347, -558891, 1880097).
+ * Frame i of a plane starts stride_y (y) / stride_c (u, v) bytes behind frame i - 1.  Any pointer alignment and any pitch; where a
+ * 2-row x 16-column block's addresses are 16-byte aligned it moves as 16-byte loads and stores (csrc/yuv.hip), the same bytes either
+ * way.  The descriptor is HOST memory, read during the call; the pointers in it are device memory (lmx_k_) or host memory (lmx_h_,
+ * csrc/host_yuv.cpp: the plain C++ restatement).  n = 0 launches nothing.  Refused with LMX_EINVAL, never approximated: odd sizes or
+ * sizes below 2, a pitch below the row, a layout or matrix outside the enums (full range, NV21, 4:2:2 and 10-bit have no value here),
+ * NV12 with v != NULL, I420 with v == NULL. */
+enum { LMX_YUV_NV12 = 0, LMX_YUV_I420 = 1 };
+enum { LMX_YUV_BT601 = 0, LMX_YUV_BT709 = 1 };
+typedef struct { const uint8_t *y, *u, *v;      /* NV12: u = the interleaved plane, v = NULL */
+                 int64_t pitch_y, pitch_c;      /* bytes per row; >= w, and >= w (NV12) or w/2 (I420) */
+                 int64_t stride_y, stride_c;    /* bytes from frame i to frame i+1 in each allocation */
+                 int32_t layout, matrix; } lmx_yuv_frames_t;
+int lmx_k_yuv420_to_bgr(const lmx_yuv_frames_t* frames_host, int n, int h, int w, uint8_t* bgr /* [n][h][w][3] */, lmx_stream_t stream);
+int lmx_h_yuv420_to_bgr(const lmx_yuv_frames_t* frames_host, int n, int h, int w, uint8_t* bgr_host /* [n][h][w][3] */);
+
 /* tokens: out[b][0..n_prefix) = prefix[t][:] (+pos), out[b][n_prefix + p] = patch[b*np + p][:] + pos[n_prefix+p]
  * (f32 residual stream; pos may be NULL — DINOv3 has no learned position table). */
 int lmx_k_assemble_tokens(const void* patch_f16, const float* prefix, const float* pos, float* out, int B, int np,
@@ -870,6 +896,21 @@ int lmx_fused_step(lmx_fused* m, const uint8_t* frames, int n, int h, int w, int
  * records_host are HOST memory; uploads, steps, downloads the records in ONE copy and synchronises (examples/fused_extract.c). */
 int lmx_fused_step_host(lmx_fused* m, const uint8_t* frames_host, int n, int h, int w, int precision, float conf, uint8_t* records_host,
                         int64_t n_rows);
+/* the same step (yolo main.py:74-76, sam3 main.py:74-92, dinov3 main.py:98-113) on frames as a decoder leaves them: frames_host
+ * describes n NV12 / I420 frames on the device (lmx_k_yuv420_to_bgr's descriptor and checks).  The call converts them on `stream` into
+ * a BGR buffer the handle owns — max_frames frames of this size — and then does exactly what lmx_fused_step does on that buffer, the
+ * schedule of lmx_fused_schedule included: the records are those of lmx_k_yuv420_to_bgr followed by lmx_fused_step, byte for byte, on
+ * both precision plans.  The buffer is allocated by the first _yuv call for a frame size (THAT call synchronises, as the first call
+ * for a new size does anyway), freed at close and when a _yuv call brings another size; lmx_fused_prepare, lmx_fused_step and lmx_fused_step_host never allocate it.  The
+ * three single-model handles have no _yuv twin: run lmx_k_yuv420_to_bgr in front of them. */
+int lmx_fused_step_yuv(lmx_fused* m, const lmx_yuv_frames_t* frames_host, int n, int h, int w, int precision, float conf,
+                       uint8_t* records, int64_t n_rows, lmx_stream_t stream);
+/* the same (yolo main.py:74-76, sam3 main.py:74-92, dinov3 main.py:98-113) for a caller with no HIP code of its own: yuv_host is n
+ * frames of tightly packed rawvideo in HOST memory, u8 [n][h * 3 / 2][w] — `nv12` (h luma rows, then h / 2 rows of interleaved U V) or
+ * `yuv420p` (h luma rows, the U plane, the V plane; LMX_YUV_I420).  Uploads the blob in ONE copy (1.5 bytes per pixel against
+ * lmx_fused_step_host's 3), converts, steps, downloads the records in ONE copy and synchronises (examples/fused_extract_nv12.c). */
+int lmx_fused_step_yuv_host(lmx_fused* m, const uint8_t* yuv_host /* [n][h*3/2][w], rawvideo nv12 / yuv420p */, int layout, int matrix,
+                            int n, int h, int w, int precision, float conf, uint8_t* records_host, int64_t n_rows);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@
 // SAM passes of sam_chunk frames dealt over the rest as lmx_h_stream_plan says, each pass's decoder behind YOLO's event, the caller's
 // stream behind all of them, then the record kernel.  HOST code only: there is no kernel in this file and no arithmetic of its own, so
 // the records are the bytes lmx.dist.pack_records makes of FusedExtractor.step's dict (tests/test_gpu_native_fused.py).
+// lmx_fused_step_yuv / _yuv_host take the frames as a decoder leaves them (NV12 / I420): lmx_k_yuv420_to_bgr (yuv.hip) into a BGR buffer of
+// the handle's, on the caller's stream, then the same sequence on that buffer (tests/test_gpu_native_fused_yuv.py).
 // OUT OF SCOPE: the byte masks (keep_byte_masks), pose keypoints in the record, point or mask prompts, RCCL, HIP graph capture.
 #include <string.h>
 
@@ -14,6 +16,7 @@
 
 #include "model_handle.h"
 #include "sam_lanes.h"
+#include "yuv.h"
 
 namespace {
 
@@ -50,6 +53,9 @@ struct lmx_fused : LmxHandleCore {
   int sched_n = 0;
   std::vector<int32_t> det_idx, emb_idx;
   int32_t* maps = nullptr;
+  // lmx_fused_step_yuv's converted frames: max_batch BGR frames of yuv_h x yuv_w, there from the first _yuv call for that size on
+  uint8_t* yuv_bgr = nullptr;
+  int yuv_h = 0, yuv_w = 0;
 };
 
 namespace {
@@ -60,6 +66,7 @@ void destroy(lmx_fused* m) {
     (void)hipFree(kv.second.gather);
   }
   (void)hipFree(m->maps);
+  (void)hipFree(m->yuv_bgr);
   for (hipEvent_t e : m->done) (void)hipEventDestroy(e);
   if (m->start) (void)hipEventDestroy(m->start);
   if (m->det) (void)hipEventDestroy(m->det);
@@ -160,6 +167,20 @@ int prepare(lmx_fused* m, int h, int w, int precision, Work** out) {
   if (m->scheduled) LMX_TRY(ensure_gather(m, h, w, &it->second));
   LMX_HIP(hipDeviceSynchronize());
   if (out) *out = &it->second;
+  return LMX_OK;
+}
+
+// the BGR frames of the _yuv entry points: one buffer per handle, of the size the last _yuv call brought.  Only these calls come here:
+// a handle that steps on BGR never holds it
+int ensure_yuv(lmx_fused* m, int h, int w) {
+  if (m->yuv_bgr && m->yuv_h == h && m->yuv_w == w) return LMX_OK;
+  LMX_HIP(hipDeviceSynchronize());  // a step on the old size has finished (the handle rule); its buffer is idle
+  (void)hipFree(m->yuv_bgr);
+  m->yuv_bgr = nullptr;
+  m->yuv_h = m->yuv_w = 0;
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->yuv_bgr), (size_t)m->max_batch * h * w * 3));
+  m->yuv_h = h;
+  m->yuv_w = w;
   return LMX_OK;
 }
 
@@ -378,6 +399,55 @@ extern "C" int lmx_fused_step_host(lmx_fused* m, const uint8_t* frames_host, int
   uint8_t* s = reinterpret_cast<uint8_t*>(m->stage);
   if (n > 0) LMX_HIP(hipMemcpyAsync(s, frames_host, (size_t)n * frame_bytes, hipMemcpyHostToDevice, m->own));
   LMX_TRY(enqueue(m, m->work[std::make_pair(h, w)], s, n, h, w, precision, conf, s + o_rec, n_rows, m->own));
+  if (rec_bytes) LMX_HIP(hipMemcpyAsync(records_host, s + o_rec, rec_bytes, hipMemcpyDeviceToHost, m->own));  // the records in ONE copy
+  LMX_HIP(hipStreamSynchronize(m->own));
+  return LMX_OK;
+}
+
+extern "C" int lmx_fused_step_yuv(lmx_fused* m, const lmx_yuv_frames_t* frames_host, int n, int h, int w, int precision, float conf, uint8_t* records,
+                                  int64_t n_rows, lmx_stream_t stream) {
+  const char* fn = "lmx_fused_step_yuv";
+  LMX_TRY(check_step(m, fn, frames_host, n, h, w, precision, records, n_rows));
+  LMX_TRY(lmx_yuv_check(fn, frames_host, n, h, w));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LMX_TRY(lmx_handle_stream_on_device(m, fn, st));  // before anything is allocated
+  if (!prepared(m, h, w, precision)) LMX_TRY(prepare(m, h, w, precision, nullptr));
+  LMX_TRY(ensure_yuv(m, h, w));
+  LMX_TRY(lmx_k_yuv420_to_bgr(frames_host, n, h, w, m->yuv_bgr, st));  // on the caller's stream: the step's start event is recorded behind it
+  return enqueue(m, m->work[std::make_pair(h, w)], m->yuv_bgr, n, h, w, precision, conf, records, n_rows, st);
+}
+
+extern "C" int lmx_fused_step_yuv_host(lmx_fused* m, const uint8_t* yuv_host, int layout, int matrix, int n, int h, int w, int precision, float conf,
+                                       uint8_t* records_host, int64_t n_rows) {
+  const char* fn = "lmx_fused_step_yuv_host";
+  LMX_TRY(check_step(m, fn, yuv_host, n, h, w, precision, records_host, n_rows));
+  LMX_TRY(lmx_yuv_check_format(fn, layout, matrix, n, h, w));
+  if (!prepared(m, h, w, precision)) LMX_TRY(prepare(m, h, w, precision, nullptr));
+  LMX_TRY(ensure_yuv(m, h, w));
+  lmx_record_layout_t lay;
+  LMX_TRY(lmx_h_record_layout(h, w, m->di.hidden, MAX_DET, m->scheduled ? 1 : 0, &lay));
+  // staging: the rawvideo blob | records, each on a 256-byte boundary
+  const size_t luma = (size_t)h * w, frame_bytes = luma + luma / 2, rec_bytes = (size_t)n_rows * (size_t)lay.stride;
+  LmxLayout z;
+  z.add((size_t)n * frame_bytes);  // the frames, at the blob's start
+  const size_t o_rec = z.add(rec_bytes);
+  if (z.total == 0) return LMX_OK;
+  LMX_TRY(lmx_handle_grow_stage(m, z.total));
+  uint8_t* s = reinterpret_cast<uint8_t*>(m->stage);
+  if (n > 0) LMX_HIP(hipMemcpyAsync(s, yuv_host, (size_t)n * frame_bytes, hipMemcpyHostToDevice, m->own));  // 1.5 bytes per pixel in ONE copy
+  // a rawvideo frame: h luma rows of w bytes, then (nv12) h / 2 rows of w interleaved bytes or (yuv420p) the U and the V plane of h / 2 x w / 2
+  lmx_yuv_frames_t f;
+  memset(&f, 0, sizeof(f));
+  f.y = s;
+  f.u = s + luma;
+  f.v = layout == LMX_YUV_I420 ? s + luma + luma / 4 : nullptr;
+  f.pitch_y = w;
+  f.pitch_c = layout == LMX_YUV_I420 ? w / 2 : w;
+  f.stride_y = f.stride_c = (int64_t)frame_bytes;
+  f.layout = layout;
+  f.matrix = matrix;
+  LMX_TRY(lmx_k_yuv420_to_bgr(&f, n, h, w, m->yuv_bgr, m->own));
+  LMX_TRY(enqueue(m, m->work[std::make_pair(h, w)], m->yuv_bgr, n, h, w, precision, conf, s + o_rec, n_rows, m->own));
   if (rec_bytes) LMX_HIP(hipMemcpyAsync(records_host, s + o_rec, rec_bytes, hipMemcpyDeviceToHost, m->own));  // the records in ONE copy
   LMX_HIP(hipStreamSynchronize(m->own));
   return LMX_OK;

@@ -71,6 +71,11 @@ class RecordLayout(C.Structure):  # lmx_record_layout_t
     _fields_ = [("n_fields", C.c_int32), ("reserved", C.c_int32), ("stride", C.c_int64), ("fields", RecordFieldLayout * 16)]
 
 
+class YuvFrames(C.Structure):  # lmx_yuv_frames_t
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("pitch_y", C.c_int64), ("pitch_c", C.c_int64), ("stride_y", C.c_int64),
+                ("stride_c", C.c_int64), ("layout", C.c_int32), ("matrix", C.c_int32)]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -117,6 +122,8 @@ SIGNATURES = {
     "lmx_k_pil_resize_v": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _I, _VP]),
     "lmx_k_patchify_norm": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I64, _VP, _VP]),
     "lmx_k_float_resize_patchify": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I64, _VP, _VP, _I, _VP, _VP, _I, _I, _F, _VP, _I, _VP]),
+    "lmx_k_yuv420_to_bgr": (_I, [C.POINTER(YuvFrames), _I, _I, _I, _VP, _VP]),
+    "lmx_h_yuv420_to_bgr": (_I, [C.POINTER(YuvFrames), _I, _I, _I, _VP]),
     "lmx_k_assemble_tokens": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "lmx_k_token_mean": (_I, [_VP, _I, _VP, _I, _I, _I, _VP]),
     "lmx_k_swiglu": (_I, [_VP, _I64, _VP, _I64, _I, _I, _VP]),
@@ -200,6 +207,8 @@ SIGNATURES = {
     "lmx_fused_schedule": (_I, [_VP, _I, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), _I]),
     "lmx_fused_step": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP, _I64, _VP]),
     "lmx_fused_step_host": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP, _I64]),
+    "lmx_fused_step_yuv": (_I, [_VP, C.POINTER(YuvFrames), _I, _I, _I, _I, _F, _VP, _I64, _VP]),
+    "lmx_fused_step_yuv_host": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _F, _VP, _I64]),
 }
 
 _lib = None

@@ -417,6 +417,53 @@ def pack_bits(mask):
     return out
 
 
+YUV_LAYOUTS = {"nv12": 0, "i420": 1}  # LMX_YUV_NV12, LMX_YUV_I420
+YUV_MATRICES = {"bt601": 0, "bt709": 1}  # LMX_YUV_BT601, LMX_YUV_BT709
+
+
+def yuv_frames(y, c, h, w, layout="nv12", matrix="bt601", v=None):
+    """(lmx_yuv_frames_t, n, device) of decoder frames held in uint8 device tensors, pitches and frame strides taken from the
+    tensors' strides: y [n, >= h, >= w] (or [rows, cols]: one frame), c the interleaved U V plane [n, >= h/2, >= w] (nv12) or the U
+    plane [n, >= h/2, >= w/2] with `v` the V plane of the same strides (i420).  Rows are contiguous; everything else is free: a
+    pitched surface is a slice of a wider tensor, a plane at any address a slice of a byte buffer."""
+    if layout not in YUV_LAYOUTS or matrix not in YUV_MATRICES:
+        raise LmxError(f"yuv_frames: layout {layout!r} / matrix {matrix!r}: one of {tuple(YUV_LAYOUTS)} and one of {tuple(YUV_MATRICES)}")
+    planes = [("y", y, h, w), ("c", c, h // 2, w if layout == "nv12" else w // 2)]
+    if (v is not None) != (layout == "i420"):
+        raise LmxError("yuv_frames: i420 takes the V plane in v, nv12 takes none")
+    if v is not None:
+        planes.append(("v", v, h // 2, w // 2))
+    dev = _dev(y, c, v)
+    views = []
+    for name, t, rows, cols in planes:
+        t = t.unsqueeze(0) if t.dim() == 2 else t
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[1] < rows or t.shape[2] < cols or (t.shape[2] > 1 and t.stride(2) != 1):
+            raise LmxError(f"yuv_frames: {name} must be uint8 [n, >= {rows}, >= {cols}] with contiguous rows, got {tuple(t.shape)} strides {t.stride()}")
+        views.append(t)
+    n = views[0].shape[0]
+    if any(t.shape[0] != n for t in views):
+        raise LmxError("yuv_frames: the planes hold different numbers of frames")
+    if v is not None and views[1].stride() != views[2].stride():
+        raise LmxError("yuv_frames: the U and the V plane must have the same pitch and frame stride")
+    # an empty tensor has no address; n = 0 follows no pointer, and the V plane's says "there is one"
+    ptrs = [_ptr(t) if t.numel() else C.c_void_p(_ROUTE_PTR) for t in views]
+    f = _lib.YuvFrames(ptrs[0], ptrs[1], ptrs[2] if v is not None else None, views[0].stride(1), views[1].stride(1),
+                       views[0].stride(0), views[1].stride(0), YUV_LAYOUTS[layout], YUV_MATRICES[matrix])
+    return f, n, dev
+
+
+def yuv420_to_bgr(y, c, h, w, layout="nv12", matrix="bt601", v=None, out=None):
+    """NV12 / I420 frames (yuv_frames' tensors) -> BGR u8 [n,h,w,3] (lmx_k_yuv420_to_bgr, csrc/yuv.hip): limited range, 20-bit fixed
+    point, nearest chroma.  `out`: a contiguous uint8 [n,h,w,3] tensor at any address."""
+    f, n, dev = yuv_frames(y, c, h, w, layout, matrix, v)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous() or out.device != dev:
+        raise LmxError(f"yuv420_to_bgr: out must be a contiguous uint8 [{n},{h},{w},3] tensor on {dev}")
+    check(_lib.load().lmx_k_yuv420_to_bgr(C.byref(f), n, int(h), int(w), _ptr(out), _stream(dev)), "lmx_k_yuv420_to_bgr")
+    return out
+
+
 def pack_records(rec, n_rows=None, row_maps=(), field_map=None, n_valid=None, out=None):
     """dict of per-frame tensors [n_k, ...] on one device -> (uint8 [n_rows, stride], layout): lmx.dist.pack_records' bytes from ONE
     launch that stores every byte of the matrix once (csrc/records.hip); `out` (uint8 [n_rows, stride], contiguous) needs no clearing.

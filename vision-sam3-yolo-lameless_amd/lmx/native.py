@@ -780,3 +780,41 @@ class NativeFused(_NativeHandle):
             check(self._lib.lmx_fused_step_host(self._handle(), a.ctypes.data, n, h, w, PLANS[precision], float(conf), records.ctypes.data, n_rows),
                   "lmx_fused_step_host")
         return records, layout
+
+    def step_yuv(self, y, c, h, w, precision, layout="nv12", matrix="bt601", v=None, conf=0.5, n_rows=None):
+        """NV12 / I420 frames as a decoder leaves them on the device (lmx.kernels.yuv_frames' tensors: pitches and frame strides come
+        from the tensors' strides) -> (records, layout) as step(): lmx_fused_step_yuv converts into a BGR buffer the handle owns, then
+        steps on it.  The records are those of step(lmx.kernels.yuv420_to_bgr(...)), byte for byte."""
+        from . import kernels as K
+
+        f, n, dev = K.yuv_frames(y, c, int(h), int(w), layout, matrix, v)
+        if dev != self.device:
+            raise LmxError(f"NativeFused.step_yuv: the planes are on {dev}, the handle on {self.device}")
+        n_rows = n if n_rows is None else int(n_rows)
+        rec_layout, stride = self.layout(h, w)
+        records = torch.empty((max(n_rows, 0), stride), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_fused_step_yuv(self._handle(), C.byref(f), n, int(h), int(w), PLANS[precision], float(conf),
+                                               C.c_void_p(records.data_ptr()), n_rows, st), "lmx_fused_step_yuv")
+        return records, rec_layout
+
+    def step_yuv_host(self, yuv, precision, layout="nv12", matrix="bt601", conf=0.5, n_rows=None):
+        """rawvideo frames in host memory, uint8 numpy [n, h * 3 / 2, w] tightly packed (`nv12`, or `yuv420p` as layout "i420") ->
+        (records uint8 [n_rows, stride] numpy array, layout) (lmx_fused_step_yuv_host: uploads 1.5 bytes per pixel in one copy,
+        converts, steps, downloads the records in one copy, synchronises)."""
+        from . import kernels as K
+
+        a = np.ascontiguousarray(yuv)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[1] % 3 != 0:
+            raise LmxError("NativeFused.step_yuv_host: yuv must be a uint8 [n, h * 3 / 2, w] array")
+        if layout not in K.YUV_LAYOUTS or matrix not in K.YUV_MATRICES:
+            raise LmxError(f"NativeFused.step_yuv_host: layout {layout!r} / matrix {matrix!r}: one of {tuple(K.YUV_LAYOUTS)} and one of {tuple(K.YUV_MATRICES)}")
+        n, h, w = a.shape[0], a.shape[1] // 3 * 2, a.shape[2]
+        n_rows = n if n_rows is None else int(n_rows)
+        rec_layout, stride = self.layout(h, w)
+        records = np.empty((max(n_rows, 0), stride), np.uint8)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_fused_step_yuv_host(self._handle(), a.ctypes.data, K.YUV_LAYOUTS[layout], K.YUV_MATRICES[matrix], n, h, w,
+                                                    PLANS[precision], float(conf), records.ctypes.data, n_rows), "lmx_fused_step_yuv_host")
+        return records, rec_layout
