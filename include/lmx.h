@@ -318,6 +318,30 @@ typedef struct { const uint8_t *y, *u, *v;      /* NV12: u = the interleaved pla
 int lmx_k_yuv420_to_bgr(const lmx_yuv_frames_t* frames_host, int n, int h, int w, uint8_t* bgr /* [n][h][w][3] */, lmx_stream_t stream);
 int lmx_h_yuv420_to_bgr(const lmx_yuv_frames_t* frames_host, int n, int h, int w, uint8_t* bgr_host /* [n][h][w][3] */);
 
+/* ---- per-frame blur and brightness sums: BGR u8 [n][h][w][3] -> int64 [n][4] ------------------------------------------------------
+ * Replaces what clip-curation's compute_blur_score and compute_brightness_score (main.py:276-289) compute per sampled frame —
+ * cv2.cvtColor(BGR2GRAY), cv2.Laplacian(gray, CV_64F).var() and np.mean(gray) — by one pass over every frame at the memory rate; the
+ * scores themselves are host arithmetic on the four sums (lmx.services.curation.visual_scores).  The arithmetic is defined HERE (cv2 is
+ * not installed: PARITY UNPINNED against real OpenCV).  For pixel (x, y) of a frame with bytes B, G, R:
+ *   g(x, y)   = (3735 * B + 19235 * G + 9798 * R + 16384) >> 15          OpenCV 4's 8-bit BGR2GRAY: round(2^15 * 0.114 / 0.587 / 0.299),
+ *                                                                        rounded descale; 0 .. 255
+ *   lap(x, y) = g(x-1, y) + g(x+1, y) + g(x, y-1) + g(x, y+1) - 4 * g(x, y)      cv2.Laplacian, ksize 1; |lap| <= 1020
+ *   an index outside the frame is reflected without repeating the edge sample: -1 -> 1, w -> w - 2, -1 -> 1, h -> h - 2
+ *   (BORDER_REFLECT_101, cv2's BORDER_DEFAULT)
+ *   out[i] = { sum g, sum lap, sum lap^2, h * w } over frame i: exact 64-bit integer sums, so the result depends neither on the launch
+ *   geometry nor on n nor on the order of any partial sum.
+ * Frames are contiguous and may start at ANY byte address (h * w * 3 is odd for odd sizes); where a thread's run of 16 columns is
+ * 16-byte aligned it moves as three 16-byte loads (csrc/quality.hip), the same values either way.  `out` is 8-byte aligned and needs no
+ * clearing: the call zeroes it on `stream` and every one of its 4 n words is defined when the call completes there.  `workspace`:
+ * lmx_frame_quality_workspace_bytes(n, h, w) bytes, which is 0 — the partial sums meet in `out` through 64-bit integer atomics — so it
+ * may be NULL.  n = 0 launches nothing.  Refused with LMX_EINVAL before anything is read, written or launched: n < 0, h or w below 2
+ * (the reflection needs two samples) or above 32768, a null bgr or out with n > 0.  lmx_h_frame_quality is the plain C++ restatement on
+ * HOST memory (csrc/host_quality.cpp). */
+int64_t lmx_frame_quality_workspace_bytes(int n, int h, int w);
+int lmx_k_frame_quality(const uint8_t* bgr /* [n][h][w][3] */, int n, int h, int w, int64_t* out /* [n][4] */, void* workspace,
+                        lmx_stream_t stream);
+int lmx_h_frame_quality(const uint8_t* bgr_host /* [n][h][w][3] */, int n, int h, int w, int64_t* out_host /* [n][4] */);
+
 /* tokens: out[b][0..n_prefix) = prefix[t][:] (+pos), out[b][n_prefix + p] = patch[b*np + p][:] + pos[n_prefix+p]
  * (f32 residual stream; pos may be NULL — DINOv3 has no learned position table). */
 int lmx_k_assemble_tokens(const void* patch_f16, const float* prefix, const float* pos, float* out, int B, int np,

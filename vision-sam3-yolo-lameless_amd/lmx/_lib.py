@@ -124,6 +124,9 @@ SIGNATURES = {
     "lmx_k_float_resize_patchify": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I64, _VP, _VP, _I, _VP, _VP, _I, _I, _F, _VP, _I, _VP]),
     "lmx_k_yuv420_to_bgr": (_I, [C.POINTER(YuvFrames), _I, _I, _I, _VP, _VP]),
     "lmx_h_yuv420_to_bgr": (_I, [C.POINTER(YuvFrames), _I, _I, _I, _VP]),
+    "lmx_frame_quality_workspace_bytes": (_I64, [_I, _I, _I]),
+    "lmx_k_frame_quality": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP]),
+    "lmx_h_frame_quality": (_I, [_VP, _I, _I, _I, _VP]),
     "lmx_k_assemble_tokens": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "lmx_k_token_mean": (_I, [_VP, _I, _VP, _I, _I, _I, _VP]),
     "lmx_k_swiglu": (_I, [_VP, _I64, _VP, _I64, _I, _I, _VP]),

@@ -464,6 +464,26 @@ def yuv420_to_bgr(y, c, h, w, layout="nv12", matrix="bt601", v=None, out=None):
     return out
 
 
+def frame_quality(frames, out=None):
+    """BGR u8 [n,h,w,3] -> int64 [n,4] = per frame (Σ g, Σ lap, Σ lap², h * w) of the 8-bit gray image and its ksize-1 Laplacian under
+    BORDER_REFLECT_101 (lmx_k_frame_quality, csrc/quality.hip): exact integer sums, what lmx.services.curation.visual_scores turns into
+    the blur and brightness scores of clip-curation main.py:276-289.  `frames` is contiguous and may start at any byte address (a view
+    into a byte buffer); `out`: a contiguous int64 [n,4] tensor, which needs no clearing."""
+    dev = _dev(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise LmxError(f"frame_quality: frames must be contiguous uint8 [n,h,w,3], got {frames.dtype} {tuple(frames.shape)} strides {frames.stride()}")
+    n, h, w, _ = frames.shape
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (n, 4) or not out.is_contiguous() or out.device != dev:
+        raise LmxError(f"frame_quality: out must be a contiguous int64 [{n},4] tensor on {dev}")
+    lib = _lib.load()
+    nws = int(lib.lmx_frame_quality_workspace_bytes(n, h, w))
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev) if nws > 0 else None
+    check(lib.lmx_k_frame_quality(_ptr(frames), n, h, w, _ptr(out), _ptr(ws), _stream(dev)), "lmx_k_frame_quality")
+    return out
+
+
 def pack_records(rec, n_rows=None, row_maps=(), field_map=None, n_valid=None, out=None):
     """dict of per-frame tensors [n_k, ...] on one device -> (uint8 [n_rows, stride], layout): lmx.dist.pack_records' bytes from ONE
     launch that stores every byte of the matrix once (csrc/records.hip); `out` (uint8 [n_rows, stride], contiguous) needs no clearing.

@@ -8,5 +8,5 @@ from .fused import FusedFeatureService  # noqa: F401
 from .sam3_pipeline import SAM3Pipeline  # noqa: F401
 from .yolo_pipeline import YOLOPipeline  # noqa: F401
 from .pose import PoseEstimator  # noqa: F401
-from .curation import CowTracker  # noqa: F401
+from .curation import ClipCurator, CowTracker  # noqa: F401
 from .tracking import TrackingService  # noqa: F401
