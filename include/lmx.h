@@ -318,6 +318,62 @@ typedef struct { const uint8_t *y, *u, *v;      /* NV12: u = the interleaved pla
 int lmx_k_yuv420_to_bgr(const lmx_yuv_frames_t* frames_host, int n, int h, int w, uint8_t* bgr /* [n][h][w][3] */, lmx_stream_t stream);
 int lmx_h_yuv420_to_bgr(const lmx_yuv_frames_t* frames_host, int n, int h, int w, uint8_t* bgr_host /* [n][h][w][3] */);
 
+/* ---- the crop window: a part of every frame of a 4:2:0 clip -> packed BGR u8 [n][roi.h][roi.w][3] ---------------------------------
+ * What video-preprocessing main.py:112-119 (moviepy's crop) cuts out of the decode, without its libx264 re-encode and second decode:
+ * the pipelines run on the window of the ORIGINAL frames.  A window is lmx_rect_t {x, y, w, h} inside the h x w source frame; output
+ * pixel (i, j) of the window is EXACTLY pixel (x + i, y + j) of the text above, its chroma taken from ((y + j) >> 1, (x + i) >> 1) of
+ * the source.  x, y, w and h may have any parity; the source frame still has even sizes.  The window that covers the whole frame
+ * gives the bytes of lmx_k_yuv420_to_bgr.  PARITY UNPINNED against real OpenCV and swscale, as above.  The kernel lays its 2-row x
+ * 16-column blocks on the source's chroma grid (columns at multiples of 16 of the source, row pairs 2k and 2k + 1), so the loads of an
+ * aligned surface stay 16-byte loads for any window; a block on the window's rim has one live row or starts / ends inside a chroma
+ * pair.  Refused with LMX_EINVAL: everything lmx_k_yuv420_to_bgr refuses, an empty window (w or h below 1) and a window that leaves
+ * the frame (x or y below 0, x + w above the frame's w, y + h above its h).  n = 0 launches nothing. */
+typedef struct { int32_t x, y, w, h; } lmx_rect_t;
+int lmx_k_yuv420_to_bgr_roi(const lmx_yuv_frames_t* frames_host, int n, int h, int w, const lmx_rect_t* roi_host,
+                            uint8_t* bgr /* [n][roi.h][roi.w][3] */, lmx_stream_t stream);
+int lmx_h_yuv420_to_bgr_roi(const lmx_yuv_frames_t* frames_host, int n, int h, int w, const lmx_rect_t* roi_host,
+                            uint8_t* bgr_host /* [n][roi.h][roi.w][3] */);
+
+/* ---- frames to an encoder: packed BGR u8 -> YUV 4:2:0 (NV12 / I420) ---------------------------------------------------------------
+ * What swscale does between a BGR frame and libx264 / a hardware encoder (video-preprocessing main.py:122-127, clip-curation's
+ * writer): limited range, BT.601 or BT.709, 20-bit fixed point, chroma from the 2 x 2 BOX (not the top-left sample).  The arithmetic is
+ * defined HERE (neither cv2 nor swscale is installed: PARITY UNPINNED against both).  h and w are even and at least 2; all arithmetic is
+ * signed 32-bit and >> is an arithmetic shift (floor):
+ *   Y(x, y) = sat8(((YB*B + YG*G + YR*R + 2^19) >> 20) + 16)
+ *   SB, SG, SR = sums of B, G, R over pixels (2i, 2j), (2i+1, 2j), (2i, 2j+1), (2i+1, 2j+1)                       (0 .. 1020)
+ *   U(i, j) = sat8(((UB*SB + UG*SG + UR*SR + 2^21) >> 22) + 128);  V(i, j) = sat8(((VB*SB + VG*SG + VR*SR + 2^21) >> 22) + 128)
+ *   NV12: c[j * pitch_c + 2 * i] = U, the byte after it V;  I420: u[j * pitch_c + i] = U, v[the same offset] = V
+ * Every coefficient is round(c * 2^20) of a three-decimal constant:
+ *   LMX_YUV_BT601  YB, YG, YR = 0.098, 0.504, 0.257 (102760, 528482, 269484);  UB, UG, UR = 0.439, -0.291, -0.148 (460325, -305136,
+ *                  -155189);  VB, VG, VR = -0.071, -0.368, 0.439 (-74449, -385876, 460325)
+ *   LMX_YUV_BT709  YB, YG, YR = 0.062, 0.614, 0.183 (65012, 643826, 191889);  UB, UG, UR = 0.439, -0.338, -0.101 (460325, -354419,
+ *                  -105906);  VB, VG, VR = -0.040, -0.399, 0.439 (-41943, -418382, 460325)
+ * Both chroma rows sum to 0 (a grey 2 x 2 gives U = V = 128), white gives Y = 235, the chroma extremes are 16 and 240, and no sum of
+ * products leaves 32 bits.  The source is PITCHED: row r of frame i starts at bgr + i * stride_bgr + r * pitch_bgr, so a crop needs no
+ * copy — point bgr at byte (y0 * W + x0) * 3 of a frame W pixels wide and pass pitch_bgr = 3 * W.  The output descriptor is
+ * lmx_yuv_frames_t with writable planes: any pointer alignment and any pitch; where a 2-row x 16-column block's pieces are 16-byte
+ * (I420 chroma: 8-byte) aligned they move as vector loads and stores (csrc/yuv.hip), the same bytes either way, and nothing outside
+ * the rows' w (w / 2) bytes is written.  The descriptor is HOST memory, read during the call.  n = 0 launches nothing.  Refused with
+ * LMX_EINVAL, never approximated: odd h or w or sizes below 2, pitch_bgr < 3 * w, an output pitch below its row, a layout or matrix
+ * outside the enums, NV12 with v != NULL, I420 with v == NULL. */
+typedef struct { uint8_t *y, *u, *v;            /* NV12: u = the interleaved plane, v = NULL */
+                 int64_t pitch_y, pitch_c;      /* bytes per row; >= w, and >= w (NV12) or w/2 (I420) */
+                 int64_t stride_y, stride_c;    /* bytes from frame i to frame i+1 in each allocation */
+                 int32_t layout, matrix; } lmx_yuv_out_t;
+int lmx_k_bgr_to_yuv420(const uint8_t* bgr, int64_t pitch_bgr /* bytes per row, >= 3 * w */, int64_t stride_bgr /* bytes per frame */,
+                        int n, int h, int w, const lmx_yuv_out_t* out_host, lmx_stream_t stream);
+int lmx_h_bgr_to_yuv420(const uint8_t* bgr_host, int64_t pitch_bgr, int64_t stride_bgr, int n, int h, int w, const lmx_yuv_out_t* out_host);
+
+/* ---- the crop box of a clip: video-preprocessing main.py:86-110 on the host ---------------------------------------------------------
+ * boxes_host: the k detections (x1, y1, x2, y2 as float32, frame pixels) that passed the caller's confidence rule (the reference: the
+ * model's default 0.25 in the detector, then conf > 0.5) on the first 10 frames of an h x w clip, every class.  Kept: boxes whose
+ * float32 area (x2 - x1) * (y2 - y1) is STRICTLY above w * h * 0.1 (a double).  box_host = (x1, y1, x2, y2): per column the median
+ * of the kept boxes as np.median takes it on float32 (an even count averages the two middle values in float32), truncated towards
+ * zero, x1 / y1 lowered by `pad` and clamped at 0, x2 / y2 raised by `pad` and clamped at w / h (the reference's pad: 50).  No box
+ * kept: (0, 0, w, h), the full frame.  lmx.services.preprocessing.crop_box_of is the same arithmetic in Python.  Refused: k < 0,
+ * h or w below 1, pad < 0, null pointers. */
+int lmx_h_crop_box(const float* boxes_host /* [k][4] xyxy */, int k, int h, int w, int pad, int32_t* box_host /* [4] */);
+
 /* ---- per-frame blur and brightness sums: BGR u8 [n][h][w][3] -> int64 [n][4] ------------------------------------------------------
  * Replaces what clip-curation's compute_blur_score and compute_brightness_score (main.py:276-289) compute per sampled frame —
  * cv2.cvtColor(BGR2GRAY), cv2.Laplacian(gray, CV_64F).var() and np.mean(gray) — by one pass over every frame at the memory rate; the
@@ -935,6 +991,16 @@ int lmx_fused_step_yuv(lmx_fused* m, const lmx_yuv_frames_t* frames_host, int n,
  * lmx_fused_step_host's 3), converts, steps, downloads the records in ONE copy and synchronises (examples/fused_extract_nv12.c). */
 int lmx_fused_step_yuv_host(lmx_fused* m, const uint8_t* yuv_host /* [n][h*3/2][w], rawvideo nv12 / yuv420p */, int layout, int matrix,
                             int n, int h, int w, int precision, float conf, uint8_t* records_host, int64_t n_rows);
+/* the three pipelines on a crop window of the ORIGINAL decode (video-preprocessing main.py:112-127 cuts the window out and re-encodes;
+ * its consumers then decode that file): frames_host describes n NV12 / I420 frames of h x w on the device, roi_host a window inside them
+ * (lmx_k_yuv420_to_bgr_roi's descriptor, window and checks).  The call converts the window on `stream` into the BGR buffer the handle
+ * owns for _yuv calls, sized max_frames x roi.h x roi.w x 3, and then does exactly what lmx_fused_step does on it at roi.h x roi.w: the
+ * records are those of lmx_k_yuv420_to_bgr_roi followed by lmx_fused_step, byte for byte, on both precision plans; the window that
+ * covers the frame gives lmx_fused_step_yuv's.  The buffer follows lmx_fused_step_yuv's rules with the WINDOW's size as its size: the
+ * first call for a size allocates and synchronises, another size replaces it, lmx_fused_prepare(m, roi.h, roi.w, ...) prepares the
+ * rest and never allocates it. */
+int lmx_fused_step_yuv_roi(lmx_fused* m, const lmx_yuv_frames_t* frames_host, int n, int h, int w, const lmx_rect_t* roi_host,
+                           int precision, float conf, uint8_t* records, int64_t n_rows, lmx_stream_t stream);
 
 #ifdef __cplusplus
 }

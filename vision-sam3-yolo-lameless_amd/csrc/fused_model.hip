@@ -417,6 +417,21 @@ extern "C" int lmx_fused_step_yuv(lmx_fused* m, const lmx_yuv_frames_t* frames_h
   return enqueue(m, m->work[std::make_pair(h, w)], m->yuv_bgr, n, h, w, precision, conf, records, n_rows, st);
 }
 
+extern "C" int lmx_fused_step_yuv_roi(lmx_fused* m, const lmx_yuv_frames_t* frames_host, int n, int h, int w, const lmx_rect_t* roi_host, int precision,
+                                      float conf, uint8_t* records, int64_t n_rows, lmx_stream_t stream) {
+  const char* fn = "lmx_fused_step_yuv_roi";
+  LMX_TRY(lmx_yuv_check(fn, frames_host, n, h, w));  // the frame's size is checked here; what the step runs at is the window's
+  LMX_TRY(lmx_yuv_check_roi(fn, roi_host, h, w));
+  const int rh = roi_host->h, rw = roi_host->w;
+  LMX_TRY(check_step(m, fn, frames_host, n, rh, rw, precision, records, n_rows));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  LMX_TRY(lmx_handle_stream_on_device(m, fn, st));  // before anything is allocated
+  if (!prepared(m, rh, rw, precision)) LMX_TRY(prepare(m, rh, rw, precision, nullptr));
+  LMX_TRY(ensure_yuv(m, rh, rw));
+  LMX_TRY(lmx_k_yuv420_to_bgr_roi(frames_host, n, h, w, roi_host, m->yuv_bgr, st));  // on the caller's stream, as lmx_fused_step_yuv
+  return enqueue(m, m->work[std::make_pair(rh, rw)], m->yuv_bgr, n, rh, rw, precision, conf, records, n_rows, st);
+}
+
 extern "C" int lmx_fused_step_yuv_host(lmx_fused* m, const uint8_t* yuv_host, int layout, int matrix, int n, int h, int w, int precision, float conf,
                                        uint8_t* records_host, int64_t n_rows) {
   const char* fn = "lmx_fused_step_yuv_host";

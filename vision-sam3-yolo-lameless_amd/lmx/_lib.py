@@ -76,6 +76,14 @@ class YuvFrames(C.Structure):  # lmx_yuv_frames_t
                 ("stride_c", C.c_int64), ("layout", C.c_int32), ("matrix", C.c_int32)]
 
 
+class YuvOut(C.Structure):  # lmx_yuv_out_t: lmx_yuv_frames_t with writable planes
+    _fields_ = YuvFrames._fields_
+
+
+class Rect(C.Structure):  # lmx_rect_t
+    _fields_ = [(n, C.c_int32) for n in ("x", "y", "w", "h")]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -124,6 +132,11 @@ SIGNATURES = {
     "lmx_k_float_resize_patchify": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I64, _VP, _VP, _I, _VP, _VP, _I, _I, _F, _VP, _I, _VP]),
     "lmx_k_yuv420_to_bgr": (_I, [C.POINTER(YuvFrames), _I, _I, _I, _VP, _VP]),
     "lmx_h_yuv420_to_bgr": (_I, [C.POINTER(YuvFrames), _I, _I, _I, _VP]),
+    "lmx_k_yuv420_to_bgr_roi": (_I, [C.POINTER(YuvFrames), _I, _I, _I, C.POINTER(Rect), _VP, _VP]),
+    "lmx_h_yuv420_to_bgr_roi": (_I, [C.POINTER(YuvFrames), _I, _I, _I, C.POINTER(Rect), _VP]),
+    "lmx_k_bgr_to_yuv420": (_I, [_VP, _I64, _I64, _I, _I, _I, C.POINTER(YuvOut), _VP]),
+    "lmx_h_bgr_to_yuv420": (_I, [_VP, _I64, _I64, _I, _I, _I, C.POINTER(YuvOut)]),
+    "lmx_h_crop_box": (_I, [C.POINTER(C.c_float), _I, _I, _I, _I, C.POINTER(C.c_int32)]),
     "lmx_frame_quality_workspace_bytes": (_I64, [_I, _I, _I]),
     "lmx_k_frame_quality": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP]),
     "lmx_h_frame_quality": (_I, [_VP, _I, _I, _I, _VP]),
@@ -211,6 +224,7 @@ SIGNATURES = {
     "lmx_fused_step": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP, _I64, _VP]),
     "lmx_fused_step_host": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP, _I64]),
     "lmx_fused_step_yuv": (_I, [_VP, C.POINTER(YuvFrames), _I, _I, _I, _I, _F, _VP, _I64, _VP]),
+    "lmx_fused_step_yuv_roi": (_I, [_VP, C.POINTER(YuvFrames), _I, _I, _I, C.POINTER(Rect), _I, _F, _VP, _I64, _VP]),
     "lmx_fused_step_yuv_host": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _F, _VP, _I64]),
 }
 

@@ -464,6 +464,52 @@ def yuv420_to_bgr(y, c, h, w, layout="nv12", matrix="bt601", v=None, out=None):
     return out
 
 
+def yuv420_to_bgr_roi(y, c, h, w, roi, layout="nv12", matrix="bt601", v=None, out=None):
+    """The window roi = (x, y, w, h) of NV12 / I420 frames of h x w (yuv_frames' tensors) -> BGR u8 [n, roi h, roi w, 3]
+    (lmx_k_yuv420_to_bgr_roi, csrc/yuv.hip): pixel (i, j) of the window is pixel (x + i, y + j) of yuv420_to_bgr, at any parity of the
+    window; the full-frame window gives yuv420_to_bgr's bytes.  `out`: a contiguous uint8 [n, roi h, roi w, 3] tensor at any address."""
+    f, n, dev = yuv_frames(y, c, h, w, layout, matrix, v)
+    rx, ry, rw, rh = (int(t) for t in roi)
+    rect = _lib.Rect(rx, ry, rw, rh)
+    shape = (n, max(rh, 0), max(rw, 0), 3)  # an empty or outside window is refused by the call, with its message
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise LmxError(f"yuv420_to_bgr_roi: out must be a contiguous uint8 {list(shape)} tensor on {dev}")
+    check(_lib.load().lmx_k_yuv420_to_bgr_roi(C.byref(f), n, int(h), int(w), C.byref(rect), _ptr(out) if out.numel() else C.c_void_p(_ROUTE_PTR),
+                                              _stream(dev)), "lmx_k_yuv420_to_bgr_roi")
+    return out
+
+
+def bgr_to_yuv420(frames, layout="nv12", matrix="bt601", out=None):
+    """BGR u8 [n,h,w,3] -> what an encoder takes (lmx_k_bgr_to_yuv420, csrc/yuv.hip): (y [n,h,w], c [n,h/2,w]) for nv12, (y, u, v) with
+    u, v [n,h/2,w/2] for i420; limited range, 20-bit fixed point, chroma from the 2 x 2 sums.  The source's row pitch and frame stride
+    are the tensor's strides, so a window `frames[:, y0:y1, x0:x1]` of larger frames is converted where it lies, without a copy; pixels
+    are packed (strides 3 and 1).  `out`: the planes to write, uint8 with contiguous rows and any pitch, stride and address (u and v with
+    the same strides); h and w are even."""
+    if layout not in YUV_LAYOUTS or matrix not in YUV_MATRICES:
+        raise LmxError(f"bgr_to_yuv420: layout {layout!r} / matrix {matrix!r}: one of {tuple(YUV_LAYOUTS)} and one of {tuple(YUV_MATRICES)}")
+    dev = _dev(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or (frames.numel() and (frames.stride(3) != 1 or frames.stride(2) != 3)):
+        raise LmxError(f"bgr_to_yuv420: frames must be uint8 [n,h,w,3] with packed pixels, got {frames.dtype} {tuple(frames.shape)} strides {frames.stride()}")
+    n, h, w, _ = frames.shape
+    shapes = [(n, h, w), (n, h // 2, w)] if layout == "nv12" else [(n, h, w), (n, h // 2, w // 2), (n, h // 2, w // 2)]
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.uint8, device=dev) for s in shapes)
+    out = tuple(out)
+    if len(out) != len(shapes) or any(t.dtype != torch.uint8 or tuple(t.shape) != s or t.device != dev or (t.shape[2] > 1 and t.stride(2) != 1)
+                                      for t, s in zip(out, shapes)):
+        raise LmxError(f"bgr_to_yuv420: out must be {len(shapes)} uint8 planes {shapes} with contiguous rows on {dev}")
+    if layout == "i420" and out[1].stride() != out[2].stride():
+        raise LmxError("bgr_to_yuv420: the U and the V plane must have the same pitch and frame stride")
+    ptrs = [_ptr(t) if t.numel() else C.c_void_p(_ROUTE_PTR) for t in out]
+    o = _lib.YuvOut(ptrs[0], ptrs[1], ptrs[2] if layout == "i420" else None, out[0].stride(1), out[1].stride(1), out[0].stride(0), out[1].stride(0),
+                    YUV_LAYOUTS[layout], YUV_MATRICES[matrix])
+    src = _ptr(frames) if frames.numel() else C.c_void_p(_ROUTE_PTR)
+    check(_lib.load().lmx_k_bgr_to_yuv420(src, frames.stride(1), frames.stride(0), n, h, w, C.byref(o), _stream(dev)), "lmx_k_bgr_to_yuv420")
+    return out
+
+
 def frame_quality(frames, out=None):
     """BGR u8 [n,h,w,3] -> int64 [n,4] = per frame (Σ g, Σ lap, Σ lap², h * w) of the 8-bit gray image and its ksize-1 Laplacian under
     BORDER_REFLECT_101 (lmx_k_frame_quality, csrc/quality.hip): exact integer sums, what lmx.services.curation.visual_scores turns into

@@ -799,6 +799,27 @@ class NativeFused(_NativeHandle):
                                                C.c_void_p(records.data_ptr()), n_rows, st), "lmx_fused_step_yuv")
         return records, rec_layout
 
+    def step_yuv_roi(self, y, c, h, w, roi, precision, layout="nv12", matrix="bt601", v=None, conf=0.5, n_rows=None):
+        """step_yuv on the window roi = (x, y, w, h) of the frames (lmx_fused_step_yuv_roi): the window is converted into the handle's
+        BGR buffer and the step runs at the window's size — the records (and their layout) are those of
+        step(lmx.kernels.yuv420_to_bgr_roi(...)), byte for byte; prepare(roi h, roi w, precision) is what prepares it."""
+        from . import kernels as K
+
+        f, n, dev = K.yuv_frames(y, c, int(h), int(w), layout, matrix, v)
+        if dev != self.device:
+            raise LmxError(f"NativeFused.step_yuv_roi: the planes are on {dev}, the handle on {self.device}")
+        rect = _lib.Rect(*(int(t) for t in roi))
+        if rect.w < 1 or rect.h < 1:
+            raise LmxError(f"NativeFused.step_yuv_roi: roi is empty: w = {rect.w}, h = {rect.h}")
+        n_rows = n if n_rows is None else int(n_rows)
+        rec_layout, stride = self.layout(rect.h, rect.w)
+        records = torch.empty((max(n_rows, 0), stride), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_fused_step_yuv_roi(self._handle(), C.byref(f), n, int(h), int(w), C.byref(rect), PLANS[precision], float(conf),
+                                                   C.c_void_p(records.data_ptr()), n_rows, st), "lmx_fused_step_yuv_roi")
+        return records, rec_layout
+
     def step_yuv_host(self, yuv, precision, layout="nv12", matrix="bt601", conf=0.5, n_rows=None):
         """rawvideo frames in host memory, uint8 numpy [n, h * 3 / 2, w] tightly packed (`nv12`, or `yuv420p` as layout "i420") ->
         (records uint8 [n_rows, stride] numpy array, layout) (lmx_fused_step_yuv_host: uploads 1.5 bytes per pixel in one copy,

@@ -10,3 +10,4 @@ from .yolo_pipeline import YOLOPipeline  # noqa: F401
 from .pose import PoseEstimator  # noqa: F401
 from .curation import ClipCurator, CowTracker  # noqa: F401
 from .tracking import TrackingService  # noqa: F401
+from .preprocessing import VideoPreprocessor  # noqa: F401
