@@ -1002,6 +1002,92 @@ int lmx_fused_step_yuv_host(lmx_fused* m, const uint8_t* yuv_host /* [n][h*3/2][
 int lmx_fused_step_yuv_roi(lmx_fused* m, const lmx_yuv_frames_t* frames_host, int n, int h, int w, const lmx_rect_t* roi_host,
                            int precision, float conf, uint8_t* records, int64_t n_rows, lmx_stream_t stream);
 
+/* ==== The TCN gait model: a lameness severity score with an MC-dropout spread from a pose series (csrc/tcn.hip, csrc/host_tcn.cpp) ====
+ * Replaces services/tcn-pipeline/app/main.py:22-195, the temporal convolutional network over the pose series and its
+ * predict_with_uncertainty (ten train-mode forwards at batch 1, about 45 launches each), by ONE launch for n clips and S samples: one
+ * workgroup per (clip, sample), the activations resident in LDS from the input series to the sigmoid.
+ * The network (batch-free, x [T][F]): block i = 0 .. n_blocks - 1 has dilation d = 2^i and channels[i] outputs;
+ *   h   = drop_{2i}  ( relu( conv1(x) ) )          conv(x)[t][o] = b[o] + sum_{j < k, c} W[o][c][j] * x[t - (k - 1 - j) * d][c], x[t < 0] = 0
+ *   y   = drop_{2i+1}( relu( conv2(h) ) )
+ *   x'  = relu( y + res(x) )                       res = a 1 x 1 convolution where the channel count changes, the identity otherwise
+ * then pooled[c] = mean over the T steps, hid = drop_{2 n_blocks}( relu( fc1 pooled + b ) ), pred = 1 / (1 + expf(-(fc2 hid + b))).
+ * All arithmetic is f32 with f32 accumulation (the exact f32-input MFMA on the device), so the device, lmx_h_tcn_forward and torch in
+ * float32 differ by summation order only.  The weights are the FOLDED weight-norm weights g * v / ||v|| (lmx.checkpoints.tcn_from_state_dict).
+ *
+ * MC dropout.  Torch's generator cannot be reproduced, so the keep decision is pinned HERE as integer arithmetic; each clip carries
+ * its own 64-bit seed.
+ *   Dropout sites are numbered 0 .. 2 * n_blocks (n_sites = 2 * n_blocks + 1): site 2i follows conv1 of block i, site 2i + 1 follows
+ *   conv2 of block i, the last site is the head.
+ *   Element u = c * T + t inside a block (torch's [C, T] order); in the head u = j.
+ *   stream = sample * n_sites + site.
+ *   Arithmetic mod 2^64:
+ *     z = seed + 0x9E3779B97F4A7C15 * ((stream << 32) + u + 1)
+ *     z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;
+ *     z ^= z >> 27;  z *= 0x94D049BB133111EB;
+ *     z ^= z >> 31;                                                                      (the splitmix64 finaliser)
+ *   The element is kept iff (z >> 32) >= thr, thr = floor(p * 2^32) computed from the double p.
+ *   Kept values are multiplied by float(1.0 / (1.0 - p)), dropped ones are 0.
+ *   A clip's bits depend on its own seed, the sample, the site and the element, never on the clip's position in the batch.
+ * lmx_h_tcn_keep_bits writes keep_host[u] = 0 / 1 for u = 0 .. count - 1 of one (seed, sample, site), on the host.
+ *
+ * lmx_tcn_weights_t describes one network to both forwards: DEVICE pointers for lmx_k_tcn_forward, HOST pointers for lmx_h_tcn_forward.
+ *   conv_w[i][s]  convolution s (0: conv1, 1: conv2) of block i in the MFMA B-operand order, f32 [k * Q][N / 16][64][4], 16-byte aligned:
+ *                 entry [j * Q + q][nt][l][e] = W[16 nt + (l & 15)][16 q + 4 (l >> 4) + e][j], 0 where that input channel is >= Cin;
+ *                 Q = ceil(Cin / 16), N = channels[i], Cin = input_dim (block 0, conv1), channels[i - 1] (conv1) or channels[i] (conv2)
+ *   conv_b[i][s]  f32 [N]
+ *   res_w[i]      the 1 x 1 residual convolution in the same order with k = 1, NULL exactly where Cin == N;  res_b[i] f32 [N]
+ *   fc1_w f32 [head][channels[n_blocks - 1]] (16-byte aligned), fc1_b [head], fc2_w [head], fc2_b [1]
+ * Accepted: n_blocks 1 .. 8, channels multiples of 16 up to 64, input_dim 1 .. 64, k 2 or 3, head 1 .. 64, T 1 .. 256, one output class.
+ *
+ * lmx_k_tcn_forward: x f32 [n][T][input_dim] on the device; seeds_host u64 [n] on the HOST (may be NULL when S == 0), copied into
+ * `workspace` (lmx_tcn_workspace_bytes(n) bytes on the device, 8-byte aligned; may be NULL when S == 0) on `stream`.  S >= 2: train mode, S
+ * predictions per clip with dropout probability p in [0, 1); S == 0: eval mode, no dropout, ONE prediction per clip; S == 1 is refused
+ * (its standard deviation is undefined).  pred f32 [n][max(S, 1)]; stats f32 [n][2] = the f32 mean of the clip's row of pred in sample
+ * order and its two-pass unbiased (n - 1) f32 standard deviation ({pred, 0} when S == 0), written by a second kernel on the same
+ * stream, so it cannot depend on which workgroup finished first; trunk (may be NULL; for tests) receives the last block's output
+ * f32 [n][max(S, 1)][T][channels[last]].  Nothing else between the series and the prediction touches HBM.  Refused with LMX_EINVAL before
+ * anything is launched: a configuration outside the list above (the field named), T or S out of range, tiles that do not fit the LDS
+ * (the bytes in the message), null or misaligned pointers.  n = 0 launches nothing.
+ * lmx_h_tcn_forward is the same network in plain C++ on HOST pointers with the same keep bits: f32, sequential sums. */
+#define LMX_TCN_MAX_BLOCKS 8
+typedef struct { int32_t input_dim, n_blocks, k, head; int32_t channels[LMX_TCN_MAX_BLOCKS];
+                 const float* conv_w[LMX_TCN_MAX_BLOCKS][2]; const float* conv_b[LMX_TCN_MAX_BLOCKS][2];
+                 const float* res_w[LMX_TCN_MAX_BLOCKS]; const float* res_b[LMX_TCN_MAX_BLOCKS];
+                 const float *fc1_w, *fc1_b, *fc2_w, *fc2_b; } lmx_tcn_weights_t;
+int lmx_h_tcn_keep_bits(uint64_t seed, int sample, int site, int n_sites, int64_t count, double p, uint8_t* keep_host);
+int64_t lmx_tcn_workspace_bytes(int n);
+int lmx_k_tcn_forward(const lmx_tcn_weights_t* w_host, const float* x /* [n][T][input_dim] */, const uint64_t* seeds_host /* [n] */,
+                      int n, int T, int S, double p, float* pred /* [n][max(S,1)] */, float* stats /* [n][2] */,
+                      float* trunk /* NULL or [n][max(S,1)][T][C] */, void* workspace, lmx_stream_t stream);
+int lmx_h_tcn_forward(const lmx_tcn_weights_t* w_host, const float* x_host, const uint64_t* seeds_host, int n, int T, int S, double p,
+                      float* pred_host, float* stats_host, float* trunk_host);
+/* The feature arithmetic of services/tcn-pipeline/app/main.py:255-328 for one clip of T0 >= 1 pose frames, on the host: per frame
+ * 20 keypoints as (x - bbox_x) / max(bbox_w, 1) and (y - bbox_y) / max(bbox_h, 1) with bbox = (x0, y0, x1, y1), bbox_w = x1 - x0,
+ * bbox_h = y1 - y0, computed in doubles and cast to f32 (keypoints at and beyond n_kp_host[t] are 0); then (x0 + x1) / 2 / 1280,
+ * (y0 + y1) / 2 / 720, bbox_w * bbox_h / (1280 * 720), and a velocity that is the difference of the FLOAT32 centroid-x column
+ * (0 at the first step).  The series is then cropped at its centre (start = (T0 - target) / 2) or zero-padded at its centre
+ * (pad_before = (target - T0) / 2, integer divisions) to `target` steps. */
+int lmx_h_tcn_features(const double* keypoints_host /* [T0][20][2] */, const int* n_kp_host /* [T0] */, const double* bbox_host /* [T0][4] */,
+                       int T0, int target, float* out_host /* [target][44] */);
+
+/* ==== MODEL level: gait scores from pose series (csrc/tcn_model.hip, csrc/tcn_image.h, csrc/host_tcn_image.cpp) =======================
+ * services/tcn-pipeline/app/main.py:230-253 and :357-364 behind a handle: the model comes from a WEIGHT IMAGE (kind 4) that
+ * lmx.native.write_tcn_image writes from the folded weights (csrc/tcn_image.h has the config block and the tensors); handle rules as for
+ * lmx_dino.  lmx_tcn_score: x f32 [n][T][input_dim] on the device, seeds_host u64 [n] on the host -> pred f32 [n][max(S, 1)] and stats
+ * f32 [n][2] on the device, lmx_k_tcn_forward with the image's dropout probability; it only enqueues on `stream`.  n <= max_clips,
+ * S <= max_samples.  lmx_tcn_score_host takes and returns HOST memory, and synchronises (examples/tcn_score.c). */
+typedef struct lmx_tcn lmx_tcn;
+typedef struct { int32_t input_dim, n_blocks, k, head, receptive_field, max_clips, max_samples; int32_t channels[LMX_TCN_MAX_BLOCKS];
+                 double p; } lmx_tcn_info_t;
+int lmx_tcn_image_check_host(const char* path_host, lmx_tcn_info_t* info_host);
+int lmx_tcn_open_host(const char* path_host, int max_clips, int max_samples, lmx_tcn** out_host);
+void lmx_tcn_close(lmx_tcn* m);
+int lmx_tcn_info(const lmx_tcn* m, lmx_tcn_info_t* info_host);
+int lmx_tcn_score(lmx_tcn* m, const float* x, const uint64_t* seeds_host, int n, int T, int S, float* pred, float* stats,
+                  lmx_stream_t stream);
+int lmx_tcn_score_host(lmx_tcn* m, const float* x_host, const uint64_t* seeds_host, int n, int T, int S, float* pred_host,
+                       float* stats_host);
+
 #ifdef __cplusplus
 }
 #endif

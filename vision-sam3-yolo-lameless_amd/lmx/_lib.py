@@ -84,6 +84,18 @@ class Rect(C.Structure):  # lmx_rect_t
     _fields_ = [(n, C.c_int32) for n in ("x", "y", "w", "h")]
 
 
+class TcnWeights(C.Structure):  # lmx_tcn_weights_t: device pointers for lmx_k_tcn_forward, host pointers for lmx_h_tcn_forward
+    MAX_BLOCKS = 8
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "n_blocks", "k", "head")] + [
+        ("channels", C.c_int32 * 8), ("conv_w", (C.c_void_p * 2) * 8), ("conv_b", (C.c_void_p * 2) * 8), ("res_w", C.c_void_p * 8),
+        ("res_b", C.c_void_p * 8), ("fc1_w", C.c_void_p), ("fc1_b", C.c_void_p), ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
+
+
+class TcnInfo(C.Structure):  # lmx_tcn_info_t
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "n_blocks", "k", "head", "receptive_field", "max_clips", "max_samples")] + [
+        ("channels", C.c_int32 * 8), ("p", C.c_double)]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -226,6 +238,17 @@ SIGNATURES = {
     "lmx_fused_step_yuv": (_I, [_VP, C.POINTER(YuvFrames), _I, _I, _I, _I, _F, _VP, _I64, _VP]),
     "lmx_fused_step_yuv_roi": (_I, [_VP, C.POINTER(YuvFrames), _I, _I, _I, C.POINTER(Rect), _I, _F, _VP, _I64, _VP]),
     "lmx_fused_step_yuv_host": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _F, _VP, _I64]),
+    "lmx_h_tcn_keep_bits": (_I, [C.c_uint64, _I, _I, _I, _I64, _D, _VP]),
+    "lmx_tcn_workspace_bytes": (_I64, [_I]),
+    "lmx_k_tcn_forward": (_I, [C.POINTER(TcnWeights), _VP, _VP, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_h_tcn_forward": (_I, [C.POINTER(TcnWeights), _VP, _VP, _I, _I, _I, _D, _VP, _VP, _VP]),
+    "lmx_h_tcn_features": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
+    "lmx_tcn_image_check_host": (_I, [C.c_char_p, C.POINTER(TcnInfo)]),
+    "lmx_tcn_open_host": (_I, [C.c_char_p, _I, _I, C.POINTER(_VP)]),
+    "lmx_tcn_close": (None, [_VP]),
+    "lmx_tcn_info": (_I, [_VP, C.POINTER(TcnInfo)]),
+    "lmx_tcn_score": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
+    "lmx_tcn_score_host": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP]),
 }
 
 _lib = None

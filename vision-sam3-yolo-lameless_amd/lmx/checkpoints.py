@@ -373,3 +373,60 @@ def load_dino_dir(model_dir):
     if missing:
         raise RuntimeError(f"{d}: {len(missing)} tensors missing, e.g. {missing[:3]}")
     return cfg, {k: np.asarray(v, np.float32) for k, v in sd.items()}
+
+
+# ---- the TCN gait model (services/tcn-pipeline/app/main.py:242-250: `tcn_lameness.pt`, a plain state_dict) --------------------------
+def tcn_from_state_dict(sd, dropout=0.2):
+    """A TCN state_dict under the reference's key names -> (lmx.tcn.TcnConfig, folded weights).  The convolutions are weight-normalised:
+    `network.{i}.conv{1,2}.conv.parametrizations.weight.original0` (g, [Cout, 1, 1]) and `.original1` (v, [Cout, Cin, k]), or
+    `...conv.weight_g` / `...conv.weight_v` as older torch writes them.  They are folded HERE, by torch's own `_weight_norm` — what both
+    the parametrisation and the old hook evaluate — so the folded bits are the ones torch would convolve with.  The configuration is
+    inferred from the shapes (the dropout probability is not in a state_dict); what the kernel refuses is refused here with the field
+    named.  Folded keys: block.{i}.conv{1,2}.{weight,bias}, block.{i}.res.{weight,bias}, head.fc{1,2}.{weight,bias}, all float32."""
+    import torch
+
+    from . import tcn
+    from ._lib import LmxError
+
+    def conv(prefix):
+        for g, v in ((f"{prefix}.parametrizations.weight.original0", f"{prefix}.parametrizations.weight.original1"),
+                     (f"{prefix}.weight_g", f"{prefix}.weight_v")):
+            if g in sd and v in sd:
+                return torch._weight_norm(sd[v].detach().float().cpu(), sd[g].detach().float().cpu(), 0).contiguous()
+        if f"{prefix}.weight" in sd:  # a convolution saved without weight norm
+            return sd[f"{prefix}.weight"].detach().float().cpu().contiguous()
+        raise LmxError(f"tcn_from_state_dict: no weights under {prefix} (neither parametrizations.weight.original0/1 nor weight_g/weight_v)")
+
+    def plain(key):
+        if key not in sd:
+            raise LmxError(f"tcn_from_state_dict: {key} is missing")
+        return sd[key].detach().float().cpu().contiguous()
+
+    n_blocks = 0
+    while any(k.startswith(f"network.{n_blocks}.conv1.") for k in sd):
+        n_blocks += 1
+    if n_blocks == 0:
+        raise LmxError("tcn_from_state_dict: no network.0.conv1.* keys: not a TCN state_dict")
+    folded, channels = {}, []
+    for i in range(n_blocks):
+        w1, w2 = conv(f"network.{i}.conv1.conv"), conv(f"network.{i}.conv2.conv")
+        folded[f"block.{i}.conv1.weight"], folded[f"block.{i}.conv1.bias"] = w1, plain(f"network.{i}.conv1.conv.bias")
+        folded[f"block.{i}.conv2.weight"], folded[f"block.{i}.conv2.bias"] = w2, plain(f"network.{i}.conv2.conv.bias")
+        channels.append(int(w1.shape[0]))
+        if f"network.{i}.residual.weight" in sd:
+            folded[f"block.{i}.res.weight"] = plain(f"network.{i}.residual.weight")
+            folded[f"block.{i}.res.bias"] = plain(f"network.{i}.residual.bias")
+    folded["head.fc1.weight"], folded["head.fc1.bias"] = plain("classifier.2.weight"), plain("classifier.2.bias")
+    folded["head.fc2.weight"], folded["head.fc2.bias"] = plain("classifier.5.weight"), plain("classifier.5.bias")
+    w0 = folded["block.0.conv1.weight"]
+    if folded["head.fc2.weight"].shape[0] != 1:
+        raise LmxError(f"tcn_from_state_dict: num_classes {folded['head.fc2.weight'].shape[0]}: one output class is supported")
+    cfg = tcn.TcnConfig(input_dim=int(w0.shape[1]), channels=tuple(channels), kernel_size=int(w0.shape[2]), dropout=float(dropout),
+                        head=int(folded["head.fc1.weight"].shape[0])).validate("tcn_from_state_dict")
+    for i, n in enumerate(channels):
+        has = f"block.{i}.res.weight" in folded
+        if has != (cfg.block_inputs(i) != n):
+            raise LmxError(f"tcn_from_state_dict: network.{i} has {cfg.block_inputs(i)} inputs and {n} outputs, and "
+                           f"{'a' if has else 'no'} residual convolution")
+    tcn.pack_tensors(cfg, folded)  # every shape against the configuration
+    return cfg, folded

@@ -530,6 +530,138 @@ def frame_quality(frames, out=None):
     return out
 
 
+# ---- the TCN gait model (include/lmx.h "The TCN gait model"; csrc/tcn.hip, csrc/host_tcn.cpp) ---------------------------------------
+TCN_MAX_T = 256
+
+
+def tcn_keep_bits(seed, sample, site, n_sites, count, p):
+    """uint8 numpy [count]: the keep decisions of MC dropout for one (seed, sample, site) as include/lmx.h pins them
+    (lmx_h_tcn_keep_bits; host arithmetic, no GPU)."""
+    import numpy as np
+
+    keep = np.empty((int(count),), np.uint8)
+    check(_lib.load().lmx_h_tcn_keep_bits(int(seed) & (2 ** 64 - 1), int(sample), int(site), int(n_sites), int(count), float(p),
+                                           keep.ctypes.data), "lmx_h_tcn_keep_bits")
+    return keep
+
+
+def tcn_weights(input_dim, channels, k, head, tensors):
+    """lmx_tcn_weights_t over the packed f32 tensors of lmx.tcn.pack_tensors (all on one GPU for tcn_forward, all on the CPU for
+    tcn_forward_host).  The struct keeps the tensors alive.  Configurations outside the list of include/lmx.h are refused here with
+    the field named, as the library refuses them."""
+    if not 1 <= len(channels) <= 8:
+        raise LmxError(f"tcn_weights: n_blocks {len(channels)} outside 1 .. 8")
+    if not 1 <= input_dim <= 64:
+        raise LmxError(f"tcn_weights: input_dim {input_dim} outside 1 .. 64")
+    if k not in (2, 3):
+        raise LmxError(f"tcn_weights: k {k} is neither 2 nor 3")
+    if not 1 <= head <= 64:
+        raise LmxError(f"tcn_weights: head {head} outside 1 .. 64")
+    for i, c in enumerate(channels):
+        if c % 16 or not 16 <= c <= 64:
+            raise LmxError(f"tcn_weights: channels[{i}] = {c} is not a multiple of 16 up to 64")
+    devs = {t.device for t in tensors.values()}
+    if len(devs) != 1:
+        raise LmxError(f"tcn_weights: tensors on different devices ({sorted(map(str, devs))})")
+    w = _lib.TcnWeights()
+    w.input_dim, w.n_blocks, w.k, w.head = input_dim, len(channels), k, head
+
+    def take(name, shape):
+        t = tensors.get(name)
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise LmxError(f"tcn_weights: {name} must be a contiguous float32 tensor of shape {shape}, got "
+                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
+        return t.data_ptr()
+
+    for i, n in enumerate(channels):
+        w.channels[i] = n
+        cin = channels[i - 1] if i else input_dim
+        for s, c_in in ((0, cin), (1, n)):
+            w.conv_w[i][s] = take(f"block.{i}.conv{s + 1}.w", (k * ((c_in + 15) // 16), n // 16, 64, 4))
+            w.conv_b[i][s] = take(f"block.{i}.conv{s + 1}.b", (n,))
+        if cin != n:
+            w.res_w[i] = take(f"block.{i}.res.w", ((cin + 15) // 16, n // 16, 64, 4))
+            w.res_b[i] = take(f"block.{i}.res.b", (n,))
+    w.fc1_w, w.fc1_b = take("head.fc1.w", (head, channels[-1])), take("head.fc1.b", (head,))
+    w.fc2_w, w.fc2_b = take("head.fc2.w", (head,)), take("head.fc2.b", (1,))
+    w._tensors, w._device = dict(tensors), devs.pop()
+    return w
+
+
+def _tcn_args(who, w, x, seeds, n_samples, p):
+    """(n, T, S, the seeds as a uint64 numpy array or None) after the checks both forwards share."""
+    import numpy as np
+
+    if x.dtype != torch.float32 or x.dim() != 3 or x.shape[2] != w.input_dim or not x.is_contiguous():
+        raise LmxError(f"{who}: x must be a contiguous float32 [n, T, {w.input_dim}] tensor, got {x.dtype} {tuple(x.shape)} strides {x.stride()}")
+    n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
+    if not 1 <= T <= TCN_MAX_T:
+        raise LmxError(f"{who}: T {T} outside 1 .. {TCN_MAX_T}")
+    if S == 1 or S < 0 or S > 65535:
+        raise LmxError(f"{who}: S {S} (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)")
+    if S and not 0.0 <= p < 1.0:
+        raise LmxError(f"{who}: p {p} outside [0, 1)")
+    if S == 0:
+        return n, T, S, None
+    if seeds is None:
+        raise LmxError(f"{who}: S = {S} needs one seed per clip")
+    if isinstance(seeds, torch.Tensor):
+        if seeds.is_cuda or seeds.dtype != torch.int64:
+            raise LmxError(f"{who}: seeds are HOST memory: a CPU int64 tensor, a numpy uint64 array or a list of ints")
+        seeds = seeds.numpy().view(np.uint64)
+    sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64) if isinstance(seeds, (list, tuple)) else seeds)
+    if sd.dtype != np.uint64 or sd.shape != (n,):
+        raise LmxError(f"{who}: seeds must be {n} 64-bit values, got {sd.dtype} {sd.shape}")
+    return n, T, S, sd
+
+
+def tcn_forward(w, x, seeds, n_samples, p, trunk=False):
+    """The whole TCN for n clips and S samples in ONE launch (lmx_k_tcn_forward, csrc/tcn.hip): x f32 [n, T, input_dim] on the device,
+    seeds: n 64-bit values on the host -> (pred f32 [n, max(S, 1)], stats f32 [n, 2] = mean and unbiased std, trunk f32
+    [n, max(S, 1), T, C] or None).  S = 0 is eval mode; S = 1 is refused.  `w`: tcn_weights over device tensors."""
+    dev = _dev(x)
+    if w._device != dev:
+        raise LmxError(f"tcn_forward: the weights are on {w._device}, x is on {dev}")
+    n, T, S, sd = _tcn_args("tcn_forward", w, x, seeds, n_samples, p)
+    smax = max(S, 1)
+    pred = torch.empty((n, smax), dtype=torch.float32, device=dev)
+    stats = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    tr = torch.empty((n, smax, T, w.channels[w.n_blocks - 1]), dtype=torch.float32, device=dev) if trunk else None
+    lib = _lib.load()
+    ws = torch.empty((max(int(lib.lmx_tcn_workspace_bytes(n)), 8) // 8,), dtype=torch.int64, device=dev)
+    check(lib.lmx_k_tcn_forward(C.byref(w), _ptr(x), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p), _ptr(pred),
+                                _ptr(stats), _ptr(tr), _ptr(ws), _stream(dev)), "lmx_k_tcn_forward")
+    return pred, stats, tr
+
+
+def tcn_forward_host(w, x, seeds, n_samples, p, trunk=False):
+    """lmx_h_tcn_forward: the same network in plain C++ on CPU tensors, with the same keep bits (no GPU).  `w`: tcn_weights over CPU
+    tensors; returns CPU tensors."""
+    if x.is_cuda or w._device.type != "cpu":
+        raise LmxError("tcn_forward_host takes CPU tensors and CPU weights")
+    n, T, S, sd = _tcn_args("tcn_forward_host", w, x, seeds, n_samples, p)
+    smax = max(S, 1)
+    pred = torch.empty((n, smax), dtype=torch.float32)
+    stats = torch.empty((n, 2), dtype=torch.float32)
+    tr = torch.empty((n, smax, T, w.channels[w.n_blocks - 1]), dtype=torch.float32) if trunk else None
+    check(_lib.load().lmx_h_tcn_forward(C.byref(w), _ptr(x), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p), _ptr(pred),
+                                        _ptr(stats), _ptr(tr)), "lmx_h_tcn_forward")
+    return pred, stats, tr
+
+
+def tcn_features(keypoints, n_kp, bbox, target=125):
+    """lmx_h_tcn_features: keypoints f64 [T0, 20, 2], n_kp int32 [T0], bbox f64 [T0, 4] (numpy) -> f32 numpy [target, 44]."""
+    import numpy as np
+
+    kp, nk, bb = (np.ascontiguousarray(keypoints, np.float64), np.ascontiguousarray(n_kp, np.int32), np.ascontiguousarray(bbox, np.float64))
+    T0 = len(nk)
+    if kp.shape != (T0, 20, 2) or bb.shape != (T0, 4):
+        raise LmxError(f"tcn_features: keypoints {kp.shape} / bbox {bb.shape} for {T0} frames")
+    out = np.empty((int(target), 44), np.float32)
+    check(_lib.load().lmx_h_tcn_features(kp.ctypes.data, nk.ctypes.data, bb.ctypes.data, T0, int(target), out.ctypes.data), "lmx_h_tcn_features")
+    return out
+
+
 def pack_records(rec, n_rows=None, row_maps=(), field_map=None, n_valid=None, out=None):
     """dict of per-frame tensors [n_k, ...] on one device -> (uint8 [n_rows, stride], layout): lmx.dist.pack_records' bytes from ONE
     launch that stores every byte of the matrix once (csrc/records.hip); `out` (uint8 [n_rows, stride], contiguous) needs no clearing.

@@ -26,11 +26,11 @@ import numpy as np
 import torch
 
 from . import _lib, letterbox, resample
-from ._lib import DinoInfo, FusedInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, YoloInfo, check
+from ._lib import DinoInfo, FusedInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, TcnInfo, YoloInfo, check
 
 MAGIC = b"LMXIMAGE"
 VERSION = 1
-KIND_DINO, KIND_YOLO, KIND_SAM = 1, 2, 3
+KIND_DINO, KIND_YOLO, KIND_SAM, KIND_TCN = 1, 2, 3, 4
 HEADER_BYTES, ENTRY_BYTES, NAME_BYTES = 48, 88, 48
 ARCH = {"dinov2": 0, "dinov3": 1}
 RECIPE = {"pil": 0, "float": 1}
@@ -104,6 +104,28 @@ def check_dino_image(path):
     """lmx_dino_image_check_host: validate an image on the host (no GPU) -> DinoInfo; LmxError names the offending field."""
     info = DinoInfo()
     check(_lib.load().lmx_dino_image_check_host(str(path).encode(), C.byref(info)), "lmx_dino_image_check_host")
+    return info
+
+
+# ---- the TCN weight image (csrc/tcn_image.h) ----------------------------------------------------------------------------------
+def tcn_config_block(cfg):
+    """12 int32 (input_dim, n_blocks, k, head, channels[8]) then the dropout probability as one float64."""
+    ch = tuple(cfg.channels) + (0,) * (8 - len(cfg.channels))
+    return struct.pack("<12id", cfg.input_dim, len(cfg.channels), cfg.kernel_size, cfg.head, *ch, cfg.dropout)
+
+
+def write_tcn_image(cfg, folded, path):
+    """Export a TCN (lmx.checkpoints.tcn_from_state_dict's configuration and folded weights) as the weight image lmx_tcn_open_host
+    reads: the tensors in the kernel's operand order (lmx.tcn.pack_tensors).  Returns the file's size in bytes."""
+    from . import tcn
+
+    return write_image(path, KIND_TCN, tcn_config_block(cfg.validate("write_tcn_image")), tcn.pack_tensors(cfg, folded))
+
+
+def check_tcn_image(path):
+    """lmx_tcn_image_check_host: validate an image on the host (no GPU) -> TcnInfo; LmxError names the offending field."""
+    info = TcnInfo()
+    check(_lib.load().lmx_tcn_image_check_host(str(path).encode(), C.byref(info)), "lmx_tcn_image_check_host")
     return info
 
 
@@ -465,13 +487,17 @@ class _NativeHandle:
             self.device = torch.device("cuda", torch.cuda.current_device())
         h = C.c_void_p(0)
         with torch.cuda.device(self.device):
-            check(self._fn("open_host")(str(path).encode(), int(max_batch), C.byref(h)), self._PREFIX + "open_host")
+            check(self._fn("open_host")(str(path).encode(), *self._open_args(max_batch), C.byref(h)), self._PREFIX + "open_host")
         self._h = h
         self.info = self._INFO()
         check(self._fn("info")(self._h, C.byref(self.info)), self._PREFIX + "info")
 
     def _fn(self, name):
         return getattr(self._lib, self._PREFIX + name)
+
+    def _open_args(self, max_batch):
+        """what lmx_<model>_open_host takes between the path and the handle"""
+        return (int(max_batch),)
 
     def _handle(self):
         if self._h is None:
@@ -839,3 +865,53 @@ class NativeFused(_NativeHandle):
             check(self._lib.lmx_fused_step_yuv_host(self._handle(), a.ctypes.data, K.YUV_LAYOUTS[layout], K.YUV_MATRICES[matrix], n, h, w,
                                                     PLANS[precision], float(conf), records.ctypes.data, n_rows), "lmx_fused_step_yuv_host")
         return records, rec_layout
+
+
+class NativeTcn(_NativeHandle):
+    """lmx_tcn_open_host(path, max_clips, max_samples) on `device` (default: torch's current device): the TCN gait model from its
+    weight image.  score / score_host give the bits of lmx.tcn.TcnScorer.score (tests/test_gpu_tcn.py)."""
+    _PREFIX, _INFO = "lmx_tcn_", TcnInfo
+
+    def __init__(self, path, max_clips, max_samples=10, device=None):
+        self._max_samples = int(max_samples)
+        super().__init__(path, max_clips, device)
+
+    def _open_args(self, max_batch):
+        return (int(max_batch), self._max_samples)
+
+    @staticmethod
+    def _seeds(seeds, n, S, what):
+        if S == 0:
+            return None
+        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
+        if sd.shape != (n,):
+            raise LmxError(f"NativeTcn.{what}: {n} clips need {n} seeds, got {sd.shape}")
+        return sd
+
+    def score(self, x, seeds, n_samples=10):
+        """f32 [n, T, input_dim] device tensor, n host seeds -> (mean [n], std [n], pred [n, max(S, 1)]) on torch's current stream."""
+        if not (x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.info.input_dim
+                and x.is_contiguous()):
+            raise LmxError(f"NativeTcn.score: x must be a contiguous float32 [n, T, {self.info.input_dim}] tensor on {self.device}")
+        n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
+        sd = self._seeds(seeds, n, S, "score")
+        pred = torch.empty((n, max(S, 1)), dtype=torch.float32, device=self.device)
+        stats = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_tcn_score(self._handle(), C.c_void_p(x.data_ptr()), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S,
+                                          C.c_void_p(pred.data_ptr()), C.c_void_p(stats.data_ptr()), st), "lmx_tcn_score")
+        return stats[:, 0], stats[:, 1], pred
+
+    def score_host(self, x, seeds, n_samples=10):
+        """f32 [n, T, input_dim] numpy array -> numpy (mean, std, pred) (lmx_tcn_score_host: uploads, scores, downloads, synchronises)."""
+        a = np.ascontiguousarray(x, np.float32)
+        if a.ndim != 3 or a.shape[2] != self.info.input_dim:
+            raise LmxError(f"NativeTcn.score_host: x must be a float32 [n, T, {self.info.input_dim}] array")
+        n, T, S = a.shape[0], a.shape[1], int(n_samples)
+        sd = self._seeds(seeds, n, S, "score_host")
+        pred, stats = np.empty((n, max(S, 1)), np.float32), np.empty((n, 2), np.float32)
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_tcn_score_host(self._handle(), a.ctypes.data, sd.ctypes.data if sd is not None else None, n, T, S,
+                                               pred.ctypes.data, stats.ctypes.data), "lmx_tcn_score_host")
+        return stats[:, 0], stats[:, 1], pred

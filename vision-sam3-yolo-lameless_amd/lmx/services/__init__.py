@@ -11,3 +11,4 @@ from .pose import PoseEstimator  # noqa: F401
 from .curation import ClipCurator, CowTracker  # noqa: F401
 from .tracking import TrackingService  # noqa: F401
 from .preprocessing import VideoPreprocessor  # noqa: F401
+from .tcn_pipeline import TCNPipeline  # noqa: F401
