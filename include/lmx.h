@@ -1088,6 +1088,98 @@ int lmx_tcn_score(lmx_tcn* m, const float* x, const uint64_t* seeds_host, int n,
 int lmx_tcn_score_host(lmx_tcn* m, const float* x_host, const uint64_t* seeds_host, int n, int T, int S, float* pred_host,
                        float* stats_host);
 
+/* ==== The gait transformer: score, MC-dropout spread and temporal saliency from a pose series (csrc/xfm.hip, csrc/host_xfm.cpp) ========
+ * Replaces services/transformer-pipeline/app/main.py:24-237, the encoder-only pre-norm transformer over the TCN's 44 features per
+ * frame, its predict_with_uncertainty (ten train-mode forwards at batch 1) and its get_attention_weights (an eleventh forward), by ONE
+ * launch for n clips and S samples: one workgroup per (clip, sample), the residual stream resident in LDS from the series to the sigmoid.
+ * The network (batch-free, x [T][F], T <= max_len; D = d_model, H = n_heads, dh = D / H, L = n_layers, FF = ff):
+ *   h  = drop_0( x W_in^T + b_in + pe[t] )                                   pe: the table f32 [max_len][D] of the weights
+ *   layer l = 0 .. L-1:
+ *     a  = LN(h; g1, b1)                       eps 1e-5, biased variance, two passes (mean, then the squared deviations), 1.0f / sqrtf
+ *     q, k, v = a Wq^T + bq, ...               rows 0..D-1, D..2D-1, 2D..3D-1 of in_proj_weight; head i = channels i*dh .. (i+1)*dh-1
+ *     s[i][t][u] = (q_i[t] * c) . k_i[u]       c = float(1 / sqrt(dh)): 0.25 for dh 16, the rounded 0.17677669 for dh 32, applied to q
+ *                                              after its bias; s = -inf where key u is masked
+ *     P = drop_{1+4l}( softmax_u(s) )          max-subtracted, the accurate expf, ONE DIVISION PER ELEMENT by the row's sum
+ *     o[t] = concat_i( P_i[t] . v_i )
+ *     h  = h + drop_{2+4l}( o Wo^T + bo )
+ *     a  = LN(h; g2, b2)
+ *     h  = h + drop_{4+4l}( drop_{3+4l}( gelu( a W1^T + b1 ) ) W2^T + b2 )   gelu exact: 0.5 x (1 + erff(x * 0.70710678f))
+ *   trunk = LN(h; gf, bf)
+ *   pooled = sum over UNMASKED t of trunk[t] / max(count, 1)                 without a mask: the mean over T
+ *   pred = 1 / (1 + expf(-( fc2 drop_{4L+1}( relu( fc1 pooled + b ) ) + b )))
+ *   saliency[u] = sum_t (1/H) sum_i P_i[t][u]  of the LAST layer, eval mode only: the column sums of the head-averaged attention weights
+ * All arithmetic is f32 with f32 accumulation (the exact f32-input MFMA on the device), so the device, lmx_h_xfm_forward and torch in
+ * float32 differ in summation order and in the last places of expf and erff only.
+ * Masking (mask u8 [n][T], nonzero = masked, NULL = none): a masked step is computed as a QUERY like any other (torch does, and trunk
+ * shows it), it is never a key and never pooled.  A clip with NO unmasked step has no defined softmax: its pred is NaN, on the device
+ * and on the host, as torch's is; lmx.services.TransformerPipeline refuses such a clip.
+ * MC dropout: the keep decision of the TCN section above (the same mix, thr and scale), stream = sample * n_sites + site with
+ * n_sites = 4 L + 2.  Element numbers follow torch's memory order:
+ *   site 0 (after the positional table)         u = t * D + c
+ *   site 1 + 4l (attention probabilities)       u = (i * T + t) * T + u_key
+ *   sites 2 + 4l, 4 + 4l (out_proj, FFN output) u = t * D + c
+ *   site 3 + 4l (FFN hidden)                    u = t * FF + j
+ *   site 4L + 1 (classifier hidden)             u = j
+ * lmx_h_tcn_keep_bits serves these sites as it takes n_sites.  Parity with torch's generator is statistical only.
+ *
+ * lmx_xfm_weights_t describes one network to both forwards: DEVICE pointers for lmx_k_xfm_forward, HOST pointers for lmx_h_xfm_forward.
+ * A linear layer W [N][K] is stored as the TCN stores a convolution with one tap: f32 [Q][N / 16][64][4], Q = ceil(K / 16), entry
+ * [q][nt][l][e] = W[16 nt + (l & 15)][16 q + 4 (l >> 4) + e], 0 where that input is >= K; 16-byte aligned.
+ *   in_w [F -> D], in_b [D], pe [max_len][D]
+ *   per layer: ln1_g, ln1_b [D]; qkv_w: H linear layers [D -> 3 dh] one after the other, layer i with the rows q_i | k_i | v_i of
+ *   in_proj_weight; qkv_b [H][3 dh] in the same order; out_w [D -> D], out_b [D]; ln2_g, ln2_b [D]; ff1_w [D -> FF], ff1_b [FF];
+ *   ff2_w [FF -> D], ff2_b [D]
+ *   lnf_g, lnf_b [D]; fc1_w plain [head][D] (16-byte aligned), fc1_b [head], fc2_w [head], fc2_b [1]
+ * Accepted: input_dim 1 .. 64, d_model in {16, 32, 48, 64}, d_model / n_heads in {16, 32}, n_layers 1 .. 8, ff a multiple of 16 up to
+ * 256, head 1 .. 64, max_len 1 .. 160, T 1 .. max_len, S = 0 or 2 .. 65535, p in [0, 1).
+ *
+ * lmx_k_xfm_forward: x f32 [n][T][input_dim] and mask on the device, seeds_host u64 [n] on the HOST (NULL allowed when S == 0), copied
+ * into `workspace` (lmx_xfm_workspace_bytes(n) bytes on the device, 8-byte aligned; NULL allowed when S == 0) on `stream`.  S as for the
+ * TCN: S >= 2 train mode, S == 0 eval mode with one prediction per clip, S == 1 refused.  pred f32 [n][max(S, 1)]; stats f32 [n][2] = mean
+ * and unbiased standard deviation of the clip's row of pred, by a second kernel; saliency (NULL or f32 [n][T]) only when S == 0, summed
+ * without floating-point atomics in a fixed order; trunk (NULL or f32 [n][max(S, 1)][T][D]; for tests) the final LayerNorm's output.
+ * Refused with LMX_EINVAL before anything is launched: a configuration outside the list (the field named), T or S out of range,
+ * saliency with S > 0, tiles that do not fit the LDS (the bytes in the message), null or misaligned pointers.  n = 0 launches nothing.
+ * lmx_h_xfm_forward is the same network in plain C++ on HOST pointers with the same keep bits: f32, sequential sums. */
+#define LMX_XFM_MAX_LAYERS 8
+typedef struct { int32_t input_dim, d_model, n_heads, n_layers, ff, head, max_len, reserved;
+                 const float *in_w, *in_b, *pe;
+                 const float *ln1_g[LMX_XFM_MAX_LAYERS], *ln1_b[LMX_XFM_MAX_LAYERS], *qkv_w[LMX_XFM_MAX_LAYERS], *qkv_b[LMX_XFM_MAX_LAYERS];
+                 const float *out_w[LMX_XFM_MAX_LAYERS], *out_b[LMX_XFM_MAX_LAYERS], *ln2_g[LMX_XFM_MAX_LAYERS], *ln2_b[LMX_XFM_MAX_LAYERS];
+                 const float *ff1_w[LMX_XFM_MAX_LAYERS], *ff1_b[LMX_XFM_MAX_LAYERS], *ff2_w[LMX_XFM_MAX_LAYERS], *ff2_b[LMX_XFM_MAX_LAYERS];
+                 const float *lnf_g, *lnf_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b; } lmx_xfm_weights_t;
+int64_t lmx_xfm_workspace_bytes(int n);
+int lmx_k_xfm_forward(const lmx_xfm_weights_t* w_host, const float* x /* [n][T][input_dim] */, const uint8_t* mask /* NULL or [n][T] */,
+                      const uint64_t* seeds_host /* [n] */, int n, int T, int S, double p, float* pred /* [n][max(S,1)] */,
+                      float* stats /* [n][2] */, float* saliency /* NULL or [n][T], S == 0 only */,
+                      float* trunk /* NULL or [n][max(S,1)][T][D] */, void* workspace, lmx_stream_t stream);
+int lmx_h_xfm_forward(const lmx_xfm_weights_t* w_host, const float* x_host, const uint8_t* mask_host, const uint64_t* seeds_host, int n,
+                      int T, int S, double p, float* pred_host, float* stats_host, float* saliency_host, float* trunk_host);
+/* The key-padding mask of services/transformer-pipeline/app/main.py:303-392 for one clip of T0 >= 1 pose frames, on the host: per frame
+ * the 20 keypoint confidences (those at and beyond n_kp_host[t] count as 0) are added in index order in doubles, divided by 20,
+ * multiplied by the detection confidence, cast to f32 and compared < 0.3f (1 = masked).  The mask is then cropped at its centre or padded
+ * at its centre with 1 to `target` steps, with the integer divisions of lmx_h_tcn_features.  numpy's own np.mean may add in another order
+ * and differ in the last place of the double: that matters only for a confidence within one such place of the threshold. */
+int lmx_h_xfm_mask(const double* kp_conf_host /* [T0][20] */, const int* n_kp_host /* [T0] */, const double* det_conf_host /* [T0] */,
+                   int T0, int target, uint8_t* mask_host /* [target] */);
+
+/* ==== MODEL level: transformer gait scores from pose series (csrc/xfm_model.hip, csrc/xfm_image.h, csrc/host_xfm_image.cpp) ============
+ * services/transformer-pipeline/app/main.py:272-301 and :421-441 behind a handle: the model comes from a WEIGHT IMAGE (kind 5) that
+ * lmx.native.write_xfm_image writes (csrc/xfm_image.h has the config block and the tensors); handle rules as for lmx_tcn.
+ * lmx_xfm_score: x and mask (may be NULL) on the device, seeds_host on the host -> pred, stats and, when S == 0 and it is not NULL,
+ * saliency f32 [n][T] on the device: lmx_k_xfm_forward with the image's dropout probability; it only enqueues on `stream`.
+ * n <= max_clips, S <= max_samples.  lmx_xfm_score_host takes and returns HOST memory, and synchronises (examples/xfm_score.c). */
+typedef struct lmx_xfm lmx_xfm;
+typedef struct { int32_t input_dim, d_model, n_heads, n_layers, ff, head, max_len, max_clips, max_samples, reserved; double p; } lmx_xfm_info_t;
+int lmx_xfm_image_check_host(const char* path_host, lmx_xfm_info_t* info_host);
+int lmx_xfm_open_host(const char* path_host, int max_clips, int max_samples, lmx_xfm** out_host);
+void lmx_xfm_close(lmx_xfm* m);
+int lmx_xfm_info(const lmx_xfm* m, lmx_xfm_info_t* info_host);
+int lmx_xfm_score(lmx_xfm* m, const float* x, const uint8_t* mask, const uint64_t* seeds_host, int n, int T, int S, float* pred,
+                  float* stats, float* saliency, lmx_stream_t stream);
+int lmx_xfm_score_host(lmx_xfm* m, const float* x_host, const uint8_t* mask_host, const uint64_t* seeds_host, int n, int T, int S,
+                       float* pred_host, float* stats_host, float* saliency_host);
+
 #ifdef __cplusplus
 }
 #endif

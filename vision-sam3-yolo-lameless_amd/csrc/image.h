@@ -5,7 +5,7 @@
 // File layout, little-endian, every offset from the start of the file:
 //   header  48 bytes   magic "LMXIMAGE" | u32 version | u32 kind | u32 config_bytes | u32 n_tensors | u64 dir_offset |
 //                      u64 data_offset | u64 file_bytes
-//   config  at 48      config_bytes of the kind's own block (dino_image.h, yolo_image.h, sam_image.h, tcn_image.h)
+//   config  at 48      config_bytes of the kind's own block (dino_image.h, yolo_image.h, sam_image.h, tcn_image.h, xfm_image.h)
 //   directory          n_tensors entries of 88 bytes: char name[48] (NUL padded) | u32 dtype | u32 rank | i32 shape[4] |
 //                      u64 offset (a multiple of 64, >= data_offset) | u64 nbytes (= elements * element size)
 //   data               the tensors, each bit for bit what the Python model holds on the device
@@ -20,7 +20,7 @@
 #include "../../include/lmx.h"
 
 #define LMX_IMAGE_VERSION 1u
-enum { LMX_IMAGE_DINO = 1, LMX_IMAGE_YOLO = 2, LMX_IMAGE_SAM = 3, LMX_IMAGE_TCN = 4 };  // kinds
+enum { LMX_IMAGE_DINO = 1, LMX_IMAGE_YOLO = 2, LMX_IMAGE_SAM = 3, LMX_IMAGE_TCN = 4, LMX_IMAGE_XFM = 5 };  // kinds
 enum { LMX_IMG_F16 = 0, LMX_IMG_F32 = 1, LMX_IMG_I32 = 2 };          // directory dtypes (F16 / F32 as LMX_F16 / LMX_F32)
 enum { LMX_IMAGE_HEADER_BYTES = 48, LMX_IMAGE_ENTRY_BYTES = 88, LMX_IMAGE_NAME_BYTES = 48, LMX_IMAGE_MAX_CONFIG_BYTES = 1 << 20 };
 

@@ -231,6 +231,12 @@ int launch(const TcnArgs& a, unsigned grid, int lds_bytes, int dev, hipStream_t 
 
 }  // namespace
 
+// the stats kernel on `st`; the gait transformer (xfm.hip) writes its stats with it too
+int lmx_tcn_stats_launch(const float* pred, float* stats, int n, int S, hipStream_t st) {
+  hipLaunchKernelGGL(tcn_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pred, stats, n, S);
+  return lmx_launch_check("tcn_stats_kernel");
+}
+
 extern "C" int64_t lmx_tcn_workspace_bytes(int n) { return n > 0 ? (int64_t)n * 8 : 0; }
 
 extern "C" int lmx_k_tcn_forward(const lmx_tcn_weights_t* w, const float* x, const uint64_t* seeds_host, int n, int T, int S, double p, float* pred,
@@ -273,6 +279,5 @@ extern "C" int lmx_k_tcn_forward(const lmx_tcn_weights_t* w, const float* x, con
     LMX_TRY(launch<2>(a, grid, lds_bytes, dev, st));
   else
     LMX_TRY(launch<4>(a, grid, lds_bytes, dev, st));
-  hipLaunchKernelGGL(tcn_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pred, stats, n, S);
-  return lmx_launch_check("tcn_stats_kernel");
+  return lmx_tcn_stats_launch(pred, stats, n, S, st);
 }

@@ -96,6 +96,19 @@ class TcnInfo(C.Structure):  # lmx_tcn_info_t
         ("channels", C.c_int32 * 8), ("p", C.c_double)]
 
 
+class XfmWeights(C.Structure):  # lmx_xfm_weights_t: device pointers for lmx_k_xfm_forward, host pointers for lmx_h_xfm_forward
+    MAX_LAYERS = 8
+    LAYER_FIELDS = ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_g", "ln2_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b")
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "n_layers", "ff", "head", "max_len", "reserved")] + [
+        (n, C.c_void_p) for n in ("in_w", "in_b", "pe")] + [(n, C.c_void_p * 8) for n in LAYER_FIELDS] + [
+        (n, C.c_void_p) for n in ("lnf_g", "lnf_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
+class XfmInfo(C.Structure):  # lmx_xfm_info_t
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "n_layers", "ff", "head", "max_len", "max_clips", "max_samples",
+                                         "reserved")] + [("p", C.c_double)]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -249,6 +262,16 @@ SIGNATURES = {
     "lmx_tcn_info": (_I, [_VP, C.POINTER(TcnInfo)]),
     "lmx_tcn_score": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
     "lmx_tcn_score_host": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP]),
+    "lmx_xfm_workspace_bytes": (_I64, [_I]),
+    "lmx_k_xfm_forward": (_I, [C.POINTER(XfmWeights), _VP, _VP, _VP, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_h_xfm_forward": (_I, [C.POINTER(XfmWeights), _VP, _VP, _VP, _I, _I, _I, _D, _VP, _VP, _VP, _VP]),
+    "lmx_h_xfm_mask": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
+    "lmx_xfm_image_check_host": (_I, [C.c_char_p, C.POINTER(XfmInfo)]),
+    "lmx_xfm_open_host": (_I, [C.c_char_p, _I, _I, C.POINTER(_VP)]),
+    "lmx_xfm_close": (None, [_VP]),
+    "lmx_xfm_info": (_I, [_VP, C.POINTER(XfmInfo)]),
+    "lmx_xfm_score": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "lmx_xfm_score_host": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
 }
 
 _lib = None

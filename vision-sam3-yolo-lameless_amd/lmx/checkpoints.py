@@ -430,3 +430,72 @@ def tcn_from_state_dict(sd, dropout=0.2):
                            f"{'a' if has else 'no'} residual convolution")
     tcn.pack_tensors(cfg, folded)  # every shape against the configuration
     return cfg, folded
+
+
+# ---- the gait transformer (services/transformer-pipeline/app/main.py:272-295: `transformer_lameness.pt`, a plain state_dict) ----------
+def xfm_positional_table(max_len, d_model):
+    """The sinusoidal table of main.py:32-37, computed once in torch float32 exactly as the reference's module builds it: f32 [max_len, D]."""
+    import math
+
+    import torch
+
+    pe = torch.zeros(max_len, d_model)
+    position = torch.arange(0, max_len, dtype=torch.float).unsqueeze(1)
+    div_term = torch.exp(torch.arange(0, d_model, 2).float() * (-math.log(10000.0) / d_model))
+    pe[:, 0::2] = torch.sin(position * div_term)
+    pe[:, 1::2] = torch.cos(position * div_term)
+    return pe
+
+
+def xfm_from_state_dict(sd, n_heads=4, dropout=0.1, max_len=150):
+    """A GaitTransformer state_dict under the reference's key names -> (lmx.xfm.XfmConfig, weights).  Keys read: `input_projection.*`,
+    `pos_encoder.pe` ([1, max_len, D]; where it is absent the table is computed once by the formula of main.py:32-37 for `max_len`
+    rows), `encoder_layers.{i}.self_attn.in_proj_weight` / `in_proj_bias` / `out_proj.*`, `.ffn.0.*`, `.ffn.3.*`, `.norm1.*`, `.norm2.*`,
+    `final_norm.*`, `classifier.0.*` and `classifier.3.*`.  The shape is inferred from the tensors; the number of heads and the dropout
+    probability are not in a state_dict.  What the kernel refuses is refused here with the field named.  Weights' keys: in.*, pe,
+    layer.{i}.{ln1,qkv,out,ln2,ff1,ff2}.{weight,bias}, lnf.*, head.fc{1,2}.*, all float32 in torch's layouts."""
+    from . import xfm
+    from ._lib import LmxError
+
+    def plain(key):
+        if key not in sd:
+            raise LmxError(f"xfm_from_state_dict: {key} is missing")
+        return sd[key].detach().float().cpu().contiguous()
+
+    n_layers = 0
+    while any(k.startswith(f"encoder_layers.{n_layers}.") for k in sd):
+        n_layers += 1
+    if n_layers == 0 or "input_projection.weight" not in sd:
+        raise LmxError("xfm_from_state_dict: no input_projection.weight or encoder_layers.0.* keys: not a GaitTransformer state_dict")
+    w = {"in.weight": plain("input_projection.weight"), "in.bias": plain("input_projection.bias")}
+    names = (("ln1", "norm1"), ("qkv", None), ("out", "self_attn.out_proj"), ("ln2", "norm2"), ("ff1", "ffn.0"), ("ff2", "ffn.3"))
+    for i in range(n_layers):
+        for ours, theirs in names:
+            if theirs is None:
+                w[f"layer.{i}.qkv.weight"] = plain(f"encoder_layers.{i}.self_attn.in_proj_weight")
+                w[f"layer.{i}.qkv.bias"] = plain(f"encoder_layers.{i}.self_attn.in_proj_bias")
+            else:
+                w[f"layer.{i}.{ours}.weight"] = plain(f"encoder_layers.{i}.{theirs}.weight")
+                w[f"layer.{i}.{ours}.bias"] = plain(f"encoder_layers.{i}.{theirs}.bias")
+    w["lnf.weight"], w["lnf.bias"] = plain("final_norm.weight"), plain("final_norm.bias")
+    w["head.fc1.weight"], w["head.fc1.bias"] = plain("classifier.0.weight"), plain("classifier.0.bias")
+    w["head.fc2.weight"], w["head.fc2.bias"] = plain("classifier.3.weight"), plain("classifier.3.bias")
+    if w["in.weight"].dim() != 2 or w["layer.0.ff1.weight"].dim() != 2 or w["head.fc1.weight"].dim() != 2 or w["head.fc2.weight"].dim() != 2:
+        raise LmxError("xfm_from_state_dict: a linear layer's weight is not a matrix")
+    if w["head.fc2.weight"].shape[0] != 1:
+        raise LmxError(f"xfm_from_state_dict: num_classes {w['head.fc2.weight'].shape[0]}: one output class is supported")
+    d_model = int(w["in.weight"].shape[0])
+    if "pos_encoder.pe" in sd:
+        pe = plain("pos_encoder.pe")
+        pe = pe.reshape(-1, pe.shape[-1]).contiguous()
+        max_len = int(pe.shape[0])
+    else:
+        if not 1 <= int(max_len) <= 160 or d_model % 2:
+            raise LmxError(f"xfm_from_state_dict: no pos_encoder.pe, and max_len {max_len} / d_model {d_model} give no table")
+        pe = xfm_positional_table(int(max_len), d_model)
+    w["pe"] = pe
+    cfg = xfm.XfmConfig(input_dim=int(w["in.weight"].shape[1]), d_model=d_model, n_heads=int(n_heads), n_layers=n_layers,
+                        ff=int(w["layer.0.ff1.weight"].shape[0]), head=int(w["head.fc1.weight"].shape[0]), dropout=float(dropout),
+                        max_len=int(max_len)).validate("xfm_from_state_dict")
+    xfm.pack_tensors(cfg, w)  # every shape against the configuration
+    return cfg, w

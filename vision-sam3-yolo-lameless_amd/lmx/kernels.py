@@ -662,6 +662,130 @@ def tcn_features(keypoints, n_kp, bbox, target=125):
     return out
 
 
+# ---- the gait transformer (include/lmx.h "The gait transformer"; csrc/xfm.hip, csrc/host_xfm.cpp) -------------------------------------
+XFM_MAX_LEN = 160
+
+
+def xfm_check_config(who, input_dim, d_model, n_heads, n_layers, ff, head, max_len):
+    """The list of include/lmx.h, refused as the library refuses it: LmxError names the field."""
+    if not 1 <= input_dim <= 64:
+        raise LmxError(f"{who}: input_dim {input_dim} outside 1 .. 64")
+    if d_model not in (16, 32, 48, 64):
+        raise LmxError(f"{who}: d_model {d_model} is not 16, 32, 48 or 64")
+    if n_heads < 1 or d_model % n_heads or d_model // n_heads not in (16, 32):
+        raise LmxError(f"{who}: n_heads {n_heads} gives d_model {d_model} a head_dim that is neither 16 nor 32")
+    if not 1 <= n_layers <= 8:
+        raise LmxError(f"{who}: n_layers {n_layers} outside 1 .. 8")
+    if ff % 16 or not 16 <= ff <= 256:
+        raise LmxError(f"{who}: ff {ff} is not a multiple of 16 up to 256")
+    if not 1 <= head <= 64:
+        raise LmxError(f"{who}: head {head} outside 1 .. 64")
+    if not 1 <= max_len <= XFM_MAX_LEN:
+        raise LmxError(f"{who}: max_len {max_len} outside 1 .. {XFM_MAX_LEN}")
+
+
+def xfm_tensor_shapes(input_dim, d_model, n_heads, n_layers, ff, head, max_len):
+    """Ordered {tensor name: shape} of one network: the names of the weight image (csrc/xfm_image.h) and of lmx.xfm.pack_tensors."""
+    D, qd, dh = d_model, d_model // 16, d_model // n_heads
+    out = {"in.w": ((input_dim + 15) // 16, qd, 64, 4), "in.b": (D,), "pe": (max_len, D)}
+    for l in range(n_layers):
+        out.update({f"layer.{l}.ln1.g": (D,), f"layer.{l}.ln1.b": (D,), f"layer.{l}.qkv.w": (n_heads * qd, 3 * dh // 16, 64, 4),
+                    f"layer.{l}.qkv.b": (n_heads, 3 * dh), f"layer.{l}.out.w": (qd, qd, 64, 4), f"layer.{l}.out.b": (D,),
+                    f"layer.{l}.ln2.g": (D,), f"layer.{l}.ln2.b": (D,), f"layer.{l}.ff1.w": (qd, ff // 16, 64, 4), f"layer.{l}.ff1.b": (ff,),
+                    f"layer.{l}.ff2.w": (ff // 16, qd, 64, 4), f"layer.{l}.ff2.b": (D,)})
+    out.update({"lnf.g": (D,), "lnf.b": (D,), "head.fc1.w": (head, D), "head.fc1.b": (head,), "head.fc2.w": (head,), "head.fc2.b": (1,)})
+    return out
+
+
+def xfm_weights(input_dim, d_model, n_heads, n_layers, ff, head, max_len, tensors):
+    """lmx_xfm_weights_t over the packed f32 tensors of lmx.xfm.pack_tensors (all on one GPU for xfm_forward, all on the CPU for
+    xfm_forward_host).  The struct keeps the tensors alive.  Configurations outside the list of include/lmx.h are refused here with
+    the field named, as the library refuses them."""
+    xfm_check_config("xfm_weights", input_dim, d_model, n_heads, n_layers, ff, head, max_len)
+    devs = {t.device for t in tensors.values()}
+    if len(devs) != 1:
+        raise LmxError(f"xfm_weights: tensors on different devices ({sorted(map(str, devs))})")
+    w = _lib.XfmWeights()
+    w.input_dim, w.d_model, w.n_heads, w.n_layers, w.ff, w.head, w.max_len = input_dim, d_model, n_heads, n_layers, ff, head, max_len
+    for name, shape in xfm_tensor_shapes(input_dim, d_model, n_heads, n_layers, ff, head, max_len).items():
+        t = tensors.get(name)
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise LmxError(f"xfm_weights: {name} must be a contiguous float32 tensor of shape {shape}, got "
+                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
+        parts = name.split(".")
+        if parts[0] == "layer":
+            getattr(w, f"{parts[2]}_{parts[3]}")[int(parts[1])] = t.data_ptr()
+        else:
+            setattr(w, "_".join(parts[1:] if parts[0] == "head" else parts), t.data_ptr())
+    w._tensors, w._device = dict(tensors), devs.pop()
+    return w
+
+
+def _xfm_args(who, w, x, mask, seeds, n_samples, p, saliency):
+    """(n, T, S, the seeds as a uint64 numpy array or None) after the checks both forwards share."""
+    if x.dtype != torch.float32 or x.dim() != 3 or x.shape[2] != w.input_dim or not x.is_contiguous():
+        raise LmxError(f"{who}: x must be a contiguous float32 [n, T, {w.input_dim}] tensor, got {x.dtype} {tuple(x.shape)} strides {x.stride()}")
+    n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
+    if not 1 <= T <= w.max_len:
+        raise LmxError(f"{who}: T {T} outside 1 .. max_len {w.max_len}")
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (n, T) or not mask.is_contiguous() or mask.device != x.device):
+        raise LmxError(f"{who}: mask must be a contiguous uint8 [{n}, {T}] tensor on {x.device} (nonzero = masked), got {mask.dtype} "
+                       f"{tuple(mask.shape)} on {mask.device}")
+    if saliency and S:
+        raise LmxError(f"{who}: saliency is read in eval mode only, S = {S}")
+    return _tcn_args(who, w, x, seeds, S, p)
+
+
+def xfm_forward(w, x, mask, seeds, n_samples, p, saliency=False, trunk=False):
+    """The whole gait transformer for n clips and S samples in ONE launch (lmx_k_xfm_forward, csrc/xfm.hip): x f32 [n, T, input_dim] and
+    mask (None or uint8 [n, T], nonzero = masked) on the device, seeds: n 64-bit values on the host -> (pred f32 [n, max(S, 1)], stats f32
+    [n, 2] = mean and unbiased std, saliency f32 [n, T] or None (S = 0 only), trunk f32 [n, max(S, 1), T, D] or None)."""
+    dev = _dev(x)
+    if w._device != dev:
+        raise LmxError(f"xfm_forward: the weights are on {w._device}, x is on {dev}")
+    n, T, S, sd = _xfm_args("xfm_forward", w, x, mask, seeds, n_samples, p, saliency)
+    smax = max(S, 1)
+    pred = torch.empty((n, smax), dtype=torch.float32, device=dev)
+    stats = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    sal = torch.empty((n, T), dtype=torch.float32, device=dev) if saliency else None
+    tr = torch.empty((n, smax, T, w.d_model), dtype=torch.float32, device=dev) if trunk else None
+    lib = _lib.load()
+    ws = torch.empty((max(int(lib.lmx_xfm_workspace_bytes(n)), 8) // 8,), dtype=torch.int64, device=dev)
+    check(lib.lmx_k_xfm_forward(C.byref(w), _ptr(x), _ptr(mask), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p),
+                                _ptr(pred), _ptr(stats), _ptr(sal), _ptr(tr), _ptr(ws), _stream(dev)), "lmx_k_xfm_forward")
+    return pred, stats, sal, tr
+
+
+def xfm_forward_host(w, x, mask, seeds, n_samples, p, saliency=False, trunk=False):
+    """lmx_h_xfm_forward: the same network in plain C++ on CPU tensors, with the same keep bits (no GPU).  `w`: xfm_weights over CPU
+    tensors; returns CPU tensors."""
+    if x.is_cuda or w._device.type != "cpu":
+        raise LmxError("xfm_forward_host takes CPU tensors and CPU weights")
+    n, T, S, sd = _xfm_args("xfm_forward_host", w, x, mask, seeds, n_samples, p, saliency)
+    smax = max(S, 1)
+    pred = torch.empty((n, smax), dtype=torch.float32)
+    stats = torch.empty((n, 2), dtype=torch.float32)
+    sal = torch.empty((n, T), dtype=torch.float32) if saliency else None
+    tr = torch.empty((n, smax, T, w.d_model), dtype=torch.float32) if trunk else None
+    check(_lib.load().lmx_h_xfm_forward(C.byref(w), _ptr(x), _ptr(mask), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p),
+                                        _ptr(pred), _ptr(stats), _ptr(sal), _ptr(tr)), "lmx_h_xfm_forward")
+    return pred, stats, sal, tr
+
+
+def xfm_mask(kp_conf, n_kp, det_conf, target=125):
+    """lmx_h_xfm_mask: keypoint confidences f64 [T0, 20], n_kp int32 [T0], detection confidences f64 [T0] (numpy) -> uint8 numpy [target],
+    1 = masked."""
+    import numpy as np
+
+    kc, nk, dc = (np.ascontiguousarray(kp_conf, np.float64), np.ascontiguousarray(n_kp, np.int32), np.ascontiguousarray(det_conf, np.float64))
+    T0 = len(nk)
+    if kc.shape != (T0, 20) or dc.shape != (T0,):
+        raise LmxError(f"xfm_mask: confidences {kc.shape} / detection confidences {dc.shape} for {T0} frames")
+    out = np.empty((int(target),), np.uint8)
+    check(_lib.load().lmx_h_xfm_mask(kc.ctypes.data, nk.ctypes.data, dc.ctypes.data, T0, int(target), out.ctypes.data), "lmx_h_xfm_mask")
+    return out
+
+
 def pack_records(rec, n_rows=None, row_maps=(), field_map=None, n_valid=None, out=None):
     """dict of per-frame tensors [n_k, ...] on one device -> (uint8 [n_rows, stride], layout): lmx.dist.pack_records' bytes from ONE
     launch that stores every byte of the matrix once (csrc/records.hip); `out` (uint8 [n_rows, stride], contiguous) needs no clearing.

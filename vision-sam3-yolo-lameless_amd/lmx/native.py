@@ -26,11 +26,11 @@ import numpy as np
 import torch
 
 from . import _lib, letterbox, resample
-from ._lib import DinoInfo, FusedInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, TcnInfo, YoloInfo, check
+from ._lib import DinoInfo, FusedInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, TcnInfo, XfmInfo, YoloInfo, check
 
 MAGIC = b"LMXIMAGE"
 VERSION = 1
-KIND_DINO, KIND_YOLO, KIND_SAM, KIND_TCN = 1, 2, 3, 4
+KIND_DINO, KIND_YOLO, KIND_SAM, KIND_TCN, KIND_XFM = 1, 2, 3, 4, 5
 HEADER_BYTES, ENTRY_BYTES, NAME_BYTES = 48, 88, 48
 ARCH = {"dinov2": 0, "dinov3": 1}
 RECIPE = {"pil": 0, "float": 1}
@@ -126,6 +126,27 @@ def check_tcn_image(path):
     """lmx_tcn_image_check_host: validate an image on the host (no GPU) -> TcnInfo; LmxError names the offending field."""
     info = TcnInfo()
     check(_lib.load().lmx_tcn_image_check_host(str(path).encode(), C.byref(info)), "lmx_tcn_image_check_host")
+    return info
+
+
+# ---- the gait transformer's weight image (csrc/xfm_image.h) ------------------------------------------------------------------------
+def xfm_config_block(cfg):
+    """8 int32 (input_dim, d_model, n_heads, n_layers, ff, head, max_len, 0) then the dropout probability as one float64."""
+    return struct.pack("<8id", cfg.input_dim, cfg.d_model, cfg.n_heads, cfg.n_layers, cfg.ff, cfg.head, cfg.max_len, 0, cfg.dropout)
+
+
+def write_xfm_image(cfg, weights, path):
+    """Export a gait transformer (lmx.checkpoints.xfm_from_state_dict's configuration and weights) as the weight image
+    lmx_xfm_open_host reads: the tensors in the kernel's operand order (lmx.xfm.pack_tensors).  Returns the file's size in bytes."""
+    from . import xfm
+
+    return write_image(path, KIND_XFM, xfm_config_block(cfg.validate("write_xfm_image")), xfm.pack_tensors(cfg, weights))
+
+
+def check_xfm_image(path):
+    """lmx_xfm_image_check_host: validate an image on the host (no GPU) -> XfmInfo; LmxError names the offending field."""
+    info = XfmInfo()
+    check(_lib.load().lmx_xfm_image_check_host(str(path).encode(), C.byref(info)), "lmx_xfm_image_check_host")
     return info
 
 
@@ -915,3 +936,64 @@ class NativeTcn(_NativeHandle):
             check(self._lib.lmx_tcn_score_host(self._handle(), a.ctypes.data, sd.ctypes.data if sd is not None else None, n, T, S,
                                                pred.ctypes.data, stats.ctypes.data), "lmx_tcn_score_host")
         return stats[:, 0], stats[:, 1], pred
+
+
+class NativeXfm(_NativeHandle):
+    """lmx_xfm_open_host(path, max_clips, max_samples) on `device` (default: torch's current device): the gait transformer from its
+    weight image.  score / score_host give the bits of lmx.xfm.XfmScorer (tests/test_gpu_xfm.py)."""
+    _PREFIX, _INFO = "lmx_xfm_", XfmInfo
+
+    def __init__(self, path, max_clips, max_samples=10, device=None):
+        self._max_samples = int(max_samples)
+        super().__init__(path, max_clips, device)
+
+    def _open_args(self, max_batch):
+        return (int(max_batch), self._max_samples)
+
+    @staticmethod
+    def _seeds(seeds, n, S, what):
+        if S == 0:
+            return None
+        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
+        if sd.shape != (n,):
+            raise LmxError(f"NativeXfm.{what}: {n} clips need {n} seeds, got {sd.shape}")
+        return sd
+
+    def score(self, x, mask=None, seeds=None, n_samples=10, saliency=False):
+        """f32 [n, T, input_dim] and uint8 [n, T] (or None) device tensors, n host seeds -> (mean [n], std [n], pred [n, max(S, 1)],
+        saliency [n, T] or None) on torch's current stream."""
+        if not (x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.info.input_dim
+                and x.is_contiguous()):
+            raise LmxError(f"NativeXfm.score: x must be a contiguous float32 [n, T, {self.info.input_dim}] tensor on {self.device}")
+        n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
+        if mask is not None and not (mask.device == self.device and mask.dtype == torch.uint8 and tuple(mask.shape) == (n, T) and mask.is_contiguous()):
+            raise LmxError(f"NativeXfm.score: mask must be a contiguous uint8 [{n}, {T}] tensor on {self.device}")
+        sd = self._seeds(seeds, n, S, "score")
+        pred = torch.empty((n, max(S, 1)), dtype=torch.float32, device=self.device)
+        stats = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        sal = torch.empty((n, T), dtype=torch.float32, device=self.device) if saliency else None
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.lmx_xfm_score(self._handle(), C.c_void_p(x.data_ptr()), C.c_void_p(mask.data_ptr() if mask is not None else 0),
+                                          C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, C.c_void_p(pred.data_ptr()),
+                                          C.c_void_p(stats.data_ptr()), C.c_void_p(sal.data_ptr() if sal is not None else 0), st), "lmx_xfm_score")
+        return stats[:, 0], stats[:, 1], pred, sal
+
+    def score_host(self, x, mask=None, seeds=None, n_samples=10, saliency=False):
+        """numpy f32 [n, T, input_dim] and uint8 [n, T] (or None) -> numpy (mean, std, pred, saliency or None) (lmx_xfm_score_host:
+        uploads, scores, downloads, synchronises)."""
+        a = np.ascontiguousarray(x, np.float32)
+        if a.ndim != 3 or a.shape[2] != self.info.input_dim:
+            raise LmxError(f"NativeXfm.score_host: x must be a float32 [n, T, {self.info.input_dim}] array")
+        n, T, S = a.shape[0], a.shape[1], int(n_samples)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if mk is not None and mk.shape != (n, T):
+            raise LmxError(f"NativeXfm.score_host: mask must be a uint8 [{n}, {T}] array")
+        sd = self._seeds(seeds, n, S, "score_host")
+        pred, stats = np.empty((n, max(S, 1)), np.float32), np.empty((n, 2), np.float32)
+        sal = np.empty((n, T), np.float32) if saliency else None
+        with torch.cuda.device(self.device):
+            check(self._lib.lmx_xfm_score_host(self._handle(), a.ctypes.data, mk.ctypes.data if mk is not None else None,
+                                               sd.ctypes.data if sd is not None else None, n, T, S, pred.ctypes.data, stats.ctypes.data,
+                                               sal.ctypes.data if sal is not None else None), "lmx_xfm_score_host")
+        return stats[:, 0], stats[:, 1], pred, sal
