@@ -1070,7 +1070,7 @@ int lmx_h_tcn_forward(const lmx_tcn_weights_t* w_host, const float* x_host, cons
 int lmx_h_tcn_features(const double* keypoints_host /* [T0][20][2] */, const int* n_kp_host /* [T0] */, const double* bbox_host /* [T0][4] */,
                        int T0, int target, float* out_host /* [target][44] */);
 
-/* ==== MODEL level: gait scores from pose series (csrc/tcn_model.hip, csrc/tcn_image.h, csrc/host_tcn_image.cpp) =======================
+/* ==== MODEL level: gait scores from pose series (csrc/gait_model.hip, csrc/tcn_image.h, csrc/host_tcn_image.cpp) =======================
  * services/tcn-pipeline/app/main.py:230-253 and :357-364 behind a handle: the model comes from a WEIGHT IMAGE (kind 4) that
  * lmx.native.write_tcn_image writes from the folded weights (csrc/tcn_image.h has the config block and the tensors); handle rules as for
  * lmx_dino.  lmx_tcn_score: x f32 [n][T][input_dim] on the device, seeds_host u64 [n] on the host -> pred f32 [n][max(S, 1)] and stats
@@ -1163,7 +1163,7 @@ int lmx_h_xfm_forward(const lmx_xfm_weights_t* w_host, const float* x_host, cons
 int lmx_h_xfm_mask(const double* kp_conf_host /* [T0][20] */, const int* n_kp_host /* [T0] */, const double* det_conf_host /* [T0] */,
                    int T0, int target, uint8_t* mask_host /* [target] */);
 
-/* ==== MODEL level: transformer gait scores from pose series (csrc/xfm_model.hip, csrc/xfm_image.h, csrc/host_xfm_image.cpp) ============
+/* ==== MODEL level: transformer gait scores from pose series (csrc/gait_model.hip, csrc/xfm_image.h, csrc/host_xfm_image.cpp) ============
  * services/transformer-pipeline/app/main.py:272-301 and :421-441 behind a handle: the model comes from a WEIGHT IMAGE (kind 5) that
  * lmx.native.write_xfm_image writes (csrc/xfm_image.h has the config block and the tensors); handle rules as for lmx_tcn.
  * lmx_xfm_score: x and mask (may be NULL) on the device, seeds_host on the host -> pred, stats and, when S == 0 and it is not NULL,

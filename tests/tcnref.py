@@ -163,3 +163,15 @@ def check_case(case, trunk, pred, tol_trunk, tol_pred, what):
     assert dt <= tol_trunk * scale, (what, case.name, dt, tol_trunk * scale)
     assert dp <= tol_pred, (what, case.name, dp, tol_pred)
     return rt, rp
+
+
+def check_stats(pred, stats, S):
+    """stats is the float64 mean and unbiased standard deviation of the pred row it read, to a few f32 spacings of the value"""
+    p, s = pred.double().cpu(), stats.double().cpu()
+    if S == 0:
+        assert torch.equal(stats[:, 0], pred[:, 0]) and not stats[:, 1].any()
+        return
+    mean, std = p.mean(1), p.std(1)  # unbiased
+    assert (s[:, 0] - mean).abs().max() <= 4 * 2.0 ** -24, (s[:, 0], mean)       # the mean lies in (0, 1): spacing <= 2^-24
+    # the deviations are differences of values in (0, 1) known to 2^-24 each: their root mean square is known to a few 2^-24 as well
+    assert (s[:, 1] - std).abs().max() <= 8 * 2.0 ** -24, (s[:, 1], std)

@@ -1,4 +1,4 @@
-"""The TCN gait model on the GPU (csrc/tcn.hip, csrc/tcn_model.hip; include/lmx.h "The TCN gait model"): one launch for n clips and S
+"""The TCN gait model on the GPU (csrc/tcn.hip, csrc/gait_model.hip; include/lmx.h "The TCN gait model"): one launch for n clips and S
 MC-dropout samples, against tcnref in float64 with the same keep bits under the tolerance rule of tcnref.tolerances, and the properties
 that need no reference — causality, no leak from padding, independence of the batch and of S, stats from pred, untouched guard words."""
 import ctypes as C
@@ -46,20 +46,8 @@ def test_device_and_host_forward_against_float64(cuda, models, cases):
         for who, t, p in (("device", trunk, pred), ("host", htrunk, hpred)):
             rt, rp = tcnref.check_case(case, t, p, tol_trunk, tol_pred, who)
             worst[who] = [max(worst[who][0], rt), max(worst[who][1], rp)]
-        _check_stats(pred, stats, case.S)
+        tcnref.check_stats(pred, stats, case.S)
     print("worst error / bound:", worst)
-
-
-def _check_stats(pred, stats, S):
-    """stats is the float64 mean and unbiased standard deviation of the pred row it read, to a few f32 spacings of the value"""
-    p, s = pred.double().cpu(), stats.double().cpu()
-    if S == 0:
-        assert torch.equal(stats[:, 0], pred[:, 0]) and not stats[:, 1].any()
-        return
-    mean, std = p.mean(1), p.std(1)  # unbiased
-    assert (s[:, 0] - mean).abs().max() <= 4 * 2.0 ** -24, (s[:, 0], mean)       # the mean lies in (0, 1): spacing <= 2^-24
-    # the deviations are differences of values in (0, 1) known to 2^-24 each: their root mean square is known to a few 2^-24 as well
-    assert (s[:, 1] - std).abs().max() <= 8 * 2.0 ** -24, (s[:, 1], std)
 
 
 def _clip(cfg, T, seed, n=1):

@@ -1,4 +1,4 @@
-"""The gait transformer on the GPU (csrc/xfm.hip, csrc/xfm_model.hip; include/lmx.h "The gait transformer"): one launch for n clips and
+"""The gait transformer on the GPU (csrc/xfm.hip, csrc/gait_model.hip; include/lmx.h "The gait transformer"): one launch for n clips and
 S MC-dropout samples, against xfmref in float64 with the same keep bits under the tolerance rule of xfmref.tolerances, and the
 properties that need no reference — the saliency's sum, masked steps that reach nothing, independence of the batch and of S, stats from
 pred, untouched guard words."""
@@ -11,7 +11,7 @@ import torch
 import xfmref
 from lmx import checkpoints, native, xfm
 from lmx import kernels as K
-from test_gpu_tcn import _check_stats
+from tcnref import check_stats
 
 pytestmark = pytest.mark.gpu
 
@@ -52,7 +52,7 @@ def test_device_and_host_forward_against_float64(cuda, models, cases):
         for who, t, p, sl in (("device", trunk, pred, s), ("host", htrunk, hpred, hs)):
             ratios = xfmref.check_case(case, t, p, sl, tols, who)
             worst[who] = [max(a, b) for a, b in zip(worst[who], ratios)]
-        _check_stats(pred, stats, case.S)
+        check_stats(pred, stats, case.S)
     print("worst error / bound (trunk, pred, saliency):", worst)
 
 

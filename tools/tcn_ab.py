@@ -6,24 +6,17 @@ HIP-event times; every shape is warmed up first; the two sides alternate inside 
 rounds with the spread.  FLOPs are counted from the shapes (2 T K N per convolution with K = taps x inputs, and the head).
 
     python tools/tcn_ab.py [--rounds 7] [--out profiles/tcn_ab.txt]"""
-import argparse
-import os
 import statistics
-import sys
 
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "vision-sam3-yolo-lameless_amd"), ROOT):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import gait_ab as G
 
 import tcnref  # noqa: E402
 from lmx import checkpoints, tcn  # noqa: E402
 
 T, S = 125, 10
-F32_MFMA_FLOP_PER_CLK_PER_CU = 256  # 64 per SIMD (v_mfma_f32_16x16x4_f32: 2048 FLOP per 32 cycles), 4 SIMDs
 
 
 def flops_per_pass(cfg, steps):
@@ -34,22 +27,8 @@ def flops_per_pass(cfg, steps):
     return total + 2 * cfg.channels[-1] * cfg.head + 2 * cfg.head
 
 
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / iters  # ms per call
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tcn_ab.txt"))
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), "tcn_ab needs a GPU"
+    args = G.parse_args("tcn_ab")
     dev = torch.device("cuda:0")
     cfg = tcnref.SHIPPED
     _, folded = checkpoints.tcn_from_state_dict(tcnref.state_dict(cfg, 1), cfg.dropout)
@@ -67,46 +46,24 @@ def main():
     for n, iters_lmx, iters_torch in ((1, 200, 10), (256, 50, 10)):
         x = torch.randn((n, T, cfg.input_dim), generator=torch.Generator().manual_seed(n)).to(dev)
         seeds = list(range(1, n + 1))
-        lmx_fn, torch_fn = (lambda: scorer.score(x, seeds, S)), (lambda: torch_score(x))
-        for fn in (lmx_fn, torch_fn):  # warm-up of both sides at this shape
-            for _ in range(3):
-                fn()
-        torch.cuda.synchronize()
-        a, b = [], []
-        for _ in range(args.rounds):
-            a.append(timed(lmx_fn, iters_lmx))
-            b.append(timed(torch_fn, iters_torch))
-        rows[n] = (a, b)
+        rows[n] = G.alternate([(lambda: scorer.score(x, seeds, S), iters_lmx), (lambda: torch_score(x), iters_torch)], args.rounds)
 
     # the same grid of 2560 workgroups in eval mode: what the launch costs without the keep bits
     xe = torch.randn((256 * S, T, cfg.input_dim), generator=torch.Generator().manual_seed(3)).to(dev)
-    eval_fn = lambda: scorer.score(xe, None, 0)  # noqa: E731
-    for _ in range(3):
-        eval_fn()
-    torch.cuda.synchronize()
-    ev = [timed(eval_fn, 50) for _ in range(args.rounds)]
+    ev, = G.alternate([(lambda: scorer.score(xe, None, 0), 50)], args.rounds)
 
-    props = torch.cuda.get_device_properties(dev)
-    cus, mhz = props.multi_processor_count, getattr(props, "clock_rate", 2400000) / 1e3
+    cus, mhz, where = G.device(dev, args.rounds)
     fl = flops_per_pass(cfg, T)
-    lines = [f"TCN gait model, shipped configuration (44 -> 4 x 64, k = 3, head 32), clips of {T} steps, S = {S} samples; {props.name}, "
-             f"{cus} CUs at up to {mhz:.0f} MHz; {args.rounds} alternating rounds, HIP events, median [min .. max]",
+    lines = [f"TCN gait model, shipped configuration (44 -> 4 x 64, k = 3, head 32), clips of {T} steps, S = {S} samples; {where}",
              f"FLOPs per (clip, sample): {fl / 1e6:.2f} M",
              f"{'n':>4}  {'lmx one launch, ms':>28}  {'torch eager 10 forwards, ms':>30}  {'ratio':>7}  {'lmx clips/s':>12}  {'lmx TFLOP/s':>11}"]
     for n, (a, b) in rows.items():
         ma, mb = statistics.median(a), statistics.median(b)
-        lines.append(f"{n:>4}  {ma:>10.4f} [{min(a):.4f} .. {max(a):.4f}]  {mb:>10.3f} [{min(b):.3f} .. {max(b):.3f}]  {mb / ma:>7.1f}  "
-                     f"{n / ma * 1e3:>12.0f}  {n * S * fl / ma / 1e9:>11.2f}")
-    bound_ms = 256 * S * fl / (cus * F32_MFMA_FLOP_PER_CLK_PER_CU * mhz * 1e6) * 1e3
-    lines.append(f"f32 MFMA bound for n = 256: {256 * S * fl / 1e9:.1f} GFLOP at {cus} CUs x {F32_MFMA_FLOP_PER_CLK_PER_CU} FLOP/clk x {mhz:.0f} MHz "
-                 f"= {bound_ms:.3f} ms; measured / bound = {statistics.median(rows[256][0]) / bound_ms:.2f}")
-    lines.append(f"eval mode, n = {256 * S} (the same {256 * S} workgroups, no keep bits): {statistics.median(ev):.4f} ms [{min(ev):.4f} .. {max(ev):.4f}]; "
-                 f"/ bound = {statistics.median(ev) / bound_ms:.2f}")
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text)
+        lines.append(f"{n:>4}  {G.cell(a, 10, 4)}  {G.cell(b, 10, 3)}  {mb / ma:>7.1f}  {n / ma * 1e3:>12.0f}  {n * S * fl / ma / 1e9:>11.2f}")
+    bound_ms, derivation = G.bound(256 * S * fl, cus, mhz)
+    lines.append(f"f32 MFMA bound for n = 256: {derivation}; measured / bound = {statistics.median(rows[256][0]) / bound_ms:.2f}")
+    lines.append(f"eval mode, n = {256 * S} (the same {256 * S} workgroups, no keep bits): {statistics.median(ev):.4f} ms [{min(ev):.4f} .. {max(ev):.4f}]; / bound = {statistics.median(ev) / bound_ms:.2f}")
+    G.write(args.out, lines)
 
 
 if __name__ == "__main__":

@@ -32,13 +32,13 @@ int lmx_tcn_image_parse(const char* path, LmxTcnImage* img) {
   for (int i = 0; i < c.n_blocks; ++i) {
     const int cin = lmx_tcn_cin(c, i), N = c.channels[i];
     const std::string b = "block." + std::to_string(i) + ".";
-    IMG_TAKE(file, b + "conv1.w", &img->conv_w[i][0], "k, the block's inputs, channels", LMX_IMG_F32, 4, c.k * lmx_tcn_groups(cin), N / 16, 64, 4);
+    IMG_TAKE(file, b + "conv1.w", &img->conv_w[i][0], "k, the block's inputs, channels", LMX_IMG_F32, 4, c.k * lmx_gait_groups(cin), N / 16, 64, 4);
     IMG_TAKE(file, b + "conv1.b", &img->conv_b[i][0], "channels", LMX_IMG_F32, 1, N);
-    IMG_TAKE(file, b + "conv2.w", &img->conv_w[i][1], "k, channels", LMX_IMG_F32, 4, c.k * lmx_tcn_groups(N), N / 16, 64, 4);
+    IMG_TAKE(file, b + "conv2.w", &img->conv_w[i][1], "k, channels", LMX_IMG_F32, 4, c.k * lmx_gait_groups(N), N / 16, 64, 4);
     IMG_TAKE(file, b + "conv2.b", &img->conv_b[i][1], "channels", LMX_IMG_F32, 1, N);
     img->res_w[i] = img->res_b[i] = LmxTensorRef();
     if (cin != N) {
-      IMG_TAKE(file, b + "res.w", &img->res_w[i], "the block's inputs, channels", LMX_IMG_F32, 4, lmx_tcn_groups(cin), N / 16, 64, 4);
+      IMG_TAKE(file, b + "res.w", &img->res_w[i], "the block's inputs, channels", LMX_IMG_F32, 4, lmx_gait_groups(cin), N / 16, 64, 4);
       IMG_TAKE(file, b + "res.b", &img->res_b[i], "channels", LMX_IMG_F32, 1, N);
     }
   }

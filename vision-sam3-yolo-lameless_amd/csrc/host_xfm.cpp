@@ -1,6 +1,6 @@
 // host_xfm.cpp — the gait transformer on the HOST (include/lmx.h "The gait transformer"): the configuration check both forwards share,
 // the whole forward in plain C++ (f32, sequential sums, no contraction: the Makefile builds this file with -ffp-contract=off) with the
-// TCN's keep bits, and the key-padding mask of services/transformer-pipeline/app/main.py:303-392.  No HIP here: it makes the service
+// keep bits and the head of gait.h, and the key-padding mask of services/transformer-pipeline/app/main.py:303-392.  No HIP here: it makes the service
 // testable without a GPU and is what the stand-alone sanitizer program (tests/xfm_check_main.cpp) runs.  The device forward is
 // csrc/xfm.hip; both read the packed weights of xfm.h.
 #include <string.h>
@@ -11,61 +11,32 @@
 
 #include "xfm.h"
 
-void lmx_set_error(const char* fmt, ...);  // api.hip
-
-#define XFM_REQUIRE(cond, ...)    \
-  do {                            \
-    if (!(cond)) {                \
-      lmx_set_error(__VA_ARGS__); \
-      return LMX_EINVAL;          \
-    }                             \
-  } while (0)
-
 int lmx_xfm_check_config(const char* who, const lmx_xfm_weights_t* w, bool pointers) {
-  XFM_REQUIRE(w != nullptr, "%s: null weights", who);
-  XFM_REQUIRE(w->input_dim >= 1 && w->input_dim <= LMX_XFM_MAX_D, "%s: input_dim %d outside 1 .. %d", who, w->input_dim, LMX_XFM_MAX_D);
-  XFM_REQUIRE(w->d_model >= 16 && w->d_model <= LMX_XFM_MAX_D && w->d_model % 16 == 0, "%s: d_model %d is not 16, 32, 48 or 64", who, w->d_model);
-  XFM_REQUIRE(w->n_heads >= 1 && w->d_model % w->n_heads == 0 && (w->d_model / w->n_heads == 16 || w->d_model / w->n_heads == 32),
+  GAIT_REQUIRE(w != nullptr, "%s: null weights", who);
+  GAIT_REQUIRE(w->input_dim >= 1 && w->input_dim <= LMX_XFM_MAX_D, "%s: input_dim %d outside 1 .. %d", who, w->input_dim, LMX_XFM_MAX_D);
+  GAIT_REQUIRE(w->d_model >= 16 && w->d_model <= LMX_XFM_MAX_D && w->d_model % 16 == 0, "%s: d_model %d is not 16, 32, 48 or 64", who, w->d_model);
+  GAIT_REQUIRE(w->n_heads >= 1 && w->d_model % w->n_heads == 0 && (w->d_model / w->n_heads == 16 || w->d_model / w->n_heads == 32),
               "%s: n_heads %d gives d_model %d a head_dim that is neither 16 nor 32", who, w->n_heads, w->d_model);
-  XFM_REQUIRE(w->n_layers >= 1 && w->n_layers <= LMX_XFM_MAX_LAYERS, "%s: n_layers %d outside 1 .. %d", who, w->n_layers, LMX_XFM_MAX_LAYERS);
-  XFM_REQUIRE(w->ff >= 16 && w->ff <= LMX_XFM_MAX_FF && w->ff % 16 == 0, "%s: ff %d is not a multiple of 16 up to %d", who, w->ff, LMX_XFM_MAX_FF);
-  XFM_REQUIRE(w->head >= 1 && w->head <= LMX_XFM_MAX_HEAD, "%s: head %d outside 1 .. %d", who, w->head, LMX_XFM_MAX_HEAD);
-  XFM_REQUIRE(w->max_len >= 1 && w->max_len <= LMX_XFM_MAX_LEN, "%s: max_len %d outside 1 .. %d", who, w->max_len, LMX_XFM_MAX_LEN);
+  GAIT_REQUIRE(w->n_layers >= 1 && w->n_layers <= LMX_XFM_MAX_LAYERS, "%s: n_layers %d outside 1 .. %d", who, w->n_layers, LMX_XFM_MAX_LAYERS);
+  GAIT_REQUIRE(w->ff >= 16 && w->ff <= LMX_XFM_MAX_FF && w->ff % 16 == 0, "%s: ff %d is not a multiple of 16 up to %d", who, w->ff, LMX_XFM_MAX_FF);
+  GAIT_REQUIRE(w->head >= 1 && w->head <= LMX_XFM_MAX_HEAD, "%s: head %d outside 1 .. %d", who, w->head, LMX_XFM_MAX_HEAD);
+  GAIT_REQUIRE(w->max_len >= 1 && w->max_len <= LMX_XFM_MAX_LEN, "%s: max_len %d outside 1 .. %d", who, w->max_len, LMX_XFM_MAX_LEN);
   if (!pointers) return LMX_OK;
-  XFM_REQUIRE(w->in_w && w->in_b && w->pe, "%s: the input projection or the positional table has no weights", who);
-  XFM_REQUIRE(((uintptr_t)w->in_w & 15) == 0, "%s: the input projection is not 16-byte aligned", who);
+  GAIT_REQUIRE(w->in_w && w->in_b && w->pe, "%s: the input projection or the positional table has no weights", who);
+  GAIT_REQUIRE(((uintptr_t)w->in_w & 15) == 0, "%s: the input projection is not 16-byte aligned", who);
   for (int l = 0; l < w->n_layers; ++l) {
-    XFM_REQUIRE(w->ln1_g[l] && w->ln1_b[l] && w->qkv_w[l] && w->qkv_b[l] && w->out_w[l] && w->out_b[l] && w->ln2_g[l] && w->ln2_b[l] &&
+    GAIT_REQUIRE(w->ln1_g[l] && w->ln1_b[l] && w->qkv_w[l] && w->qkv_b[l] && w->out_w[l] && w->out_b[l] && w->ln2_g[l] && w->ln2_b[l] &&
                     w->ff1_w[l] && w->ff1_b[l] && w->ff2_w[l] && w->ff2_b[l],
                 "%s: layer %d lacks a tensor", who, l);
-    XFM_REQUIRE((((uintptr_t)w->qkv_w[l] | (uintptr_t)w->out_w[l] | (uintptr_t)w->ff1_w[l] | (uintptr_t)w->ff2_w[l]) & 15) == 0,
+    GAIT_REQUIRE((((uintptr_t)w->qkv_w[l] | (uintptr_t)w->out_w[l] | (uintptr_t)w->ff1_w[l] | (uintptr_t)w->ff2_w[l]) & 15) == 0,
                 "%s: layer %d has weights that are not 16-byte aligned", who, l);
   }
-  XFM_REQUIRE(w->lnf_g && w->lnf_b && w->fc1_w && w->fc1_b && w->fc2_w && w->fc2_b, "%s: the final norm or the classifier has no weights", who);
-  XFM_REQUIRE(((uintptr_t)w->fc1_w & 15) == 0, "%s: the classifier's fc1 weights are not 16-byte aligned", who);
-  return LMX_OK;
-}
-
-int lmx_xfm_check_call(const char* who, const lmx_xfm_weights_t* w, int n, int T, int S, double p, bool saliency) {
-  XFM_REQUIRE(n >= 0, "%s: n = %d clips", who, n);
-  XFM_REQUIRE(T >= 1 && T <= w->max_len, "%s: T %d outside 1 .. max_len %d", who, T, w->max_len);
-  XFM_REQUIRE(S == 0 || (S >= 2 && S <= 65535), "%s: S %d (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)", who, S);
-  XFM_REQUIRE(S == 0 || (p >= 0.0 && p < 1.0), "%s: p %g outside [0, 1)", who, p);
-  XFM_REQUIRE(!saliency || S == 0, "%s: saliency is read in eval mode only, S = %d", who, S);
+  GAIT_REQUIRE(w->lnf_g && w->lnf_b && w->fc1_w && w->fc1_b && w->fc2_w && w->fc2_b, "%s: the final norm or the classifier has no weights", who);
+  GAIT_REQUIRE(((uintptr_t)w->fc1_w & 15) == 0, "%s: the classifier's fc1 weights are not 16-byte aligned", who);
   return LMX_OK;
 }
 
 namespace {
-
-struct Drop {
-  bool on;
-  uint64_t seed, thr, sample, n_sites;
-  float scale;
-  float operator()(float v, int site, uint64_t u) const {
-    if (!on) return v;
-    return lmx_tcn_keep(seed, sample * n_sites + (uint64_t)site, u, thr) ? v * scale : 0.0f;
-  }
-};
 
 // out[t][o] = b[o] + sum over c (ascending) of W[o][c] * in[t][c]
 void linear(const float* in, int ld_in, int K, float* out, int ld_out, int N, const float* w, const float* b, int T) {
@@ -96,7 +67,7 @@ extern "C" int lmx_h_xfm_forward(const lmx_xfm_weights_t* w, const float* x, con
   if (const int rc = lmx_xfm_check_config("lmx_h_xfm_forward", w, true)) return rc;
   if (const int rc = lmx_xfm_check_call("lmx_h_xfm_forward", w, n, T, S, p, saliency != nullptr)) return rc;
   if (n == 0) return LMX_OK;
-  XFM_REQUIRE(x && pred && stats && (seeds || S == 0), "lmx_h_xfm_forward: null pointer");
+  GAIT_REQUIRE(x && pred && stats && (seeds || S == 0), "lmx_h_xfm_forward: null pointer");
   const int F = w->input_dim, D = w->d_model, H = w->n_heads, dh = D / H, L = w->n_layers, FF = w->ff, HD = w->head, Smax = S > 0 ? S : 1;
   const float qs = lmx_xfm_q_scale(dh), ninf = -std::numeric_limits<float>::infinity();
   const int64_t head_floats = lmx_xfm_qkv_head_floats(*w);
@@ -105,8 +76,7 @@ extern "C" int lmx_h_xfm_forward(const lmx_xfm_weights_t* w, const float* x, con
   for (int i = 0; i < n; ++i) {
     const uint8_t* mk = mask ? mask + (size_t)i * T : nullptr;
     for (int s = 0; s < Smax; ++s) {
-      const Drop drop = {S > 0, S > 0 ? seeds[i] : 0, S > 0 ? lmx_tcn_threshold(p) : 0, (uint64_t)s, (uint64_t)(4 * L + 2),
-                         S > 0 ? lmx_tcn_keep_scale(p) : 1.0f};
+      const LmxGaitDrop drop(S, seeds, i, p, s, 4 * L + 2);
       linear(x + (size_t)i * T * F, F, F, h.data(), D, D, w->in_w, w->in_b, T);
       for (int t = 0; t < T; ++t)
         for (int c = 0; c < D; ++c) h[(size_t)t * D + c] = drop(h[(size_t)t * D + c] + w->pe[(size_t)t * D + c], 0, (uint64_t)t * D + c);
@@ -176,52 +146,32 @@ extern "C" int lmx_h_xfm_forward(const lmx_xfm_weights_t* w, const float* x, con
       if (trunk) memcpy(trunk + ((size_t)i * Smax + s) * T * D, a.data(), (size_t)T * D * sizeof(float));
       int count = 0;
       for (int t = 0; t < T; ++t) count += !(mk && mk[t]);
-      float pooled[LMX_XFM_MAX_D], hd1[LMX_XFM_MAX_HEAD];
+      float pooled[LMX_XFM_MAX_D];
       for (int c = 0; c < D; ++c) {
         float sum = 0.0f;
         for (int t = 0; t < T; ++t)
           if (!(mk && mk[t])) sum += a[(size_t)t * D + c];
         pooled[c] = sum / (float)(count > 0 ? count : 1);
       }
-      for (int j = 0; j < HD; ++j) {
-        float sum = w->fc1_b[j];
-        for (int c = 0; c < D; ++c) sum += w->fc1_w[(size_t)j * D + c] * pooled[c];
-        hd1[j] = drop(fmaxf(sum, 0.0f), 4 * L + 1, (uint64_t)j);
-      }
-      float z = w->fc2_b[0];
-      for (int j = 0; j < HD; ++j) z += w->fc2_w[j] * hd1[j];
+      const float z = lmx_gait_head(pooled, D, HD, w->fc1_w, w->fc1_b, w->fc2_w, w->fc2_b, drop, 4 * L + 1);
       // no unmasked step: every softmax of the clip is NaN and torch's pooling (NaN * 0) keeps it; fmaxf would not, so it is said here
       pred[(size_t)i * Smax + s] = count ? 1.0f / (1.0f + expf(-z)) : std::numeric_limits<float>::quiet_NaN();
     }
-    const float* row = pred + (size_t)i * Smax;
-    if (S == 0) {
-      stats[2 * i] = row[0];
-      stats[2 * i + 1] = 0.0f;
-    } else {
-      float sum = 0.0f, ss = 0.0f;
-      for (int s = 0; s < S; ++s) sum += row[s];
-      const float mean = sum / (float)S;
-      for (int s = 0; s < S; ++s) ss += (row[s] - mean) * (row[s] - mean);
-      stats[2 * i] = mean;
-      stats[2 * i + 1] = sqrtf(ss / (float)(S - 1));
-    }
+    lmx_gait_row_stats(pred + (size_t)i * Smax, S, stats + 2 * i);
   }
   return LMX_OK;
 }
 
 extern "C" int lmx_h_xfm_mask(const double* kp_conf, const int* n_kp, const double* det_conf, int T0, int target, uint8_t* mask) {
-  XFM_REQUIRE(T0 >= 1 && T0 <= (1 << 24), "lmx_h_xfm_mask: T0 = %d frames", T0);
-  XFM_REQUIRE(target >= 1 && target <= (1 << 24), "lmx_h_xfm_mask: target = %d steps", target);
-  XFM_REQUIRE(kp_conf && n_kp && det_conf && mask, "lmx_h_xfm_mask: null pointer");
-  const int K = LMX_XFM_N_KEYPOINTS;
-  for (int t = 0; t < T0; ++t) XFM_REQUIRE(n_kp[t] >= 0 && n_kp[t] <= K, "lmx_h_xfm_mask: n_kp[%d] = %d outside 0 .. %d", t, n_kp[t], K);
-  const int first = T0 >= target ? (T0 - target) / 2 : 0, rows = T0 >= target ? target : T0, at = T0 >= target ? 0 : (target - T0) / 2;
+  if (const int rc = lmx_gait_check_clip("lmx_h_xfm_mask", T0, target, kp_conf && n_kp && det_conf && mask, n_kp)) return rc;
+  const int K = LMX_GAIT_N_KEYPOINTS;
+  const LmxGaitWindow win = lmx_gait_window(T0, target);
   memset(mask, 1, (size_t)target);
-  for (int r = 0; r < rows; ++r) {
-    const int t = first + r;
+  for (int r = 0; r < win.rows; ++r) {
+    const int t = win.first + r;
     double sum = 0.0;
     for (int i = 0; i < n_kp[t]; ++i) sum += kp_conf[(size_t)t * K + i];
-    mask[at + r] = (float)(sum / K * det_conf[t]) < 0.3f ? 1 : 0;
+    mask[win.at + r] = (float)(sum / K * det_conf[t]) < 0.3f ? 1 : 0;
   }
   return LMX_OK;
 }

@@ -32,7 +32,7 @@ int lmx_xfm_image_parse(const char* path, LmxXfmImage* img) {
   img->data_offset = file.data_offset;
   img->file_bytes = file.file_bytes;
   const int F = c.input_dim, D = c.d_model, H = c.n_heads, dh = D / H, FF = c.ff, QD = D / 16;
-  IMG_TAKE(file, "in.w", &img->in_w, "input_dim, d_model", LMX_IMG_F32, 4, lmx_tcn_groups(F), QD, 64, 4);
+  IMG_TAKE(file, "in.w", &img->in_w, "input_dim, d_model", LMX_IMG_F32, 4, lmx_gait_groups(F), QD, 64, 4);
   IMG_TAKE(file, "in.b", &img->in_b, "d_model", LMX_IMG_F32, 1, D);
   IMG_TAKE(file, "pe", &img->pe, "max_len, d_model", LMX_IMG_F32, 2, c.max_len, D);
   for (int l = 0; l < c.n_layers; ++l) {

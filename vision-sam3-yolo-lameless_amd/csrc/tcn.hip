@@ -7,9 +7,9 @@
 // v_mfma_f32_16x16x4_f32: wave w owns the 16-row tiles w, w + 4, ... (MPW of them, the template parameter) and all Cout / 16 column
 // tiles.  For one tap and one group of 16 input channels a lane reads ONE float4 of A from LDS (row t - shift, channels 16q + 4g .. +3,
 // g = lane >> 4) and one float4 of B per column tile straight from the weights in L2, which lmx.native.write_tcn_image stored in exactly
-// that order (tcn.h): element e of both is the operand of MFMA e, whose four k are the channels 16q + 4g + e, g = 0 .. 3.
+// that order (gait.h): element e of both is the operand of MFMA e, whose four k are the channels 16q + 4g + e, g = 0 .. 3.
 // Rows t >= T of the tiles hold finite values that never reach a row < T (the convolutions are causal) and never leave the LDS.
-#include "common.h"
+#include "gait_launch.h"
 #include "tcn.h"
 
 namespace {
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void tcn_forward_kernel(const TcnArgs a) {
             for (int e = 0; e < 4; ++e) {
               const int t = m * 16 + 4 * g + e;
               float v = fmaxf(acc[mi][ni][e] + bias, 0.f);
-              if (drop && t < T) v = lmx_tcn_keep(seed, stream0 + 2 * blk, (uint64_t)(c * T + t), a.thr) ? v * a.scale : 0.f;
+              if (drop && t < T) v = lmx_gait_keep(seed, stream0 + 2 * blk, (uint64_t)(c * T + t), a.thr) ? v * a.scale : 0.f;
               bufB[t * LD + c] = v;
             }
           }
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void tcn_forward_kernel(const TcnArgs a) {
             for (int e = 0; e < 4; ++e) {
               const int t = m * 16 + 4 * g + e;
               float v = fmaxf(acc[mi][ni][e] + bias, 0.f);
-              if (drop && t < T) v = lmx_tcn_keep(seed, stream0 + 2 * blk + 1, (uint64_t)(c * T + t), a.thr) ? v * a.scale : 0.f;
+              if (drop && t < T) v = lmx_gait_keep(seed, stream0 + 2 * blk + 1, (uint64_t)(c * T + t), a.thr) ? v * a.scale : 0.f;
               const float xr = has_res ? res[mi][ni][e] + rbias : bufA[t * LD + c];
               acc[mi][ni][e] = fmaxf(v + xr, 0.f);
             }
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void tcn_forward_kernel(const TcnArgs a) {
         for (int e = 0; e < 4; ++e) s += w1[c4][e] * pooled[4 * c4 + e];
       }
     s = fmaxf(s, 0.f);
-    if (drop) s = lmx_tcn_keep(seed, stream0 + 2 * nb, (uint64_t)tid, a.thr) ? s * a.scale : 0.f;
+    if (drop) s = lmx_gait_keep(seed, stream0 + 2 * nb, (uint64_t)tid, a.thr) ? s * a.scale : 0.f;
     hid[tid] = w2 * s;  // the product of the second linear; thread 0 adds them in order
   }
   __syncthreads();
@@ -231,29 +231,23 @@ int launch(const TcnArgs& a, unsigned grid, int lds_bytes, int dev, hipStream_t 
 
 }  // namespace
 
-// the stats kernel on `st`; the gait transformer (xfm.hip) writes its stats with it too
-int lmx_tcn_stats_launch(const float* pred, float* stats, int n, int S, hipStream_t st) {
+// gait_launch.h: the stats kernel on `st`; the gait transformer (xfm.hip) writes its stats with it too
+int lmx_gait_stats_launch(const float* pred, float* stats, int n, int S, hipStream_t st) {
   hipLaunchKernelGGL(tcn_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pred, stats, n, S);
   return lmx_launch_check("tcn_stats_kernel");
 }
 
-extern "C" int64_t lmx_tcn_workspace_bytes(int n) { return n > 0 ? (int64_t)n * 8 : 0; }
+extern "C" int64_t lmx_tcn_workspace_bytes(int n) { return lmx_gait_workspace_bytes(n); }
 
 extern "C" int lmx_k_tcn_forward(const lmx_tcn_weights_t* w, const float* x, const uint64_t* seeds_host, int n, int T, int S, double p, float* pred,
                                  float* stats, float* trunk, void* workspace, lmx_stream_t stream) {
   LMX_TRY(lmx_tcn_check_config("lmx_k_tcn_forward", w, true));
-  LMX_REQUIRE(n >= 0, "lmx_k_tcn_forward: n = %d clips", n);
-  LMX_REQUIRE(T >= 1 && T <= LMX_TCN_MAX_T, "lmx_k_tcn_forward: T %d outside 1 .. %d", T, LMX_TCN_MAX_T);
-  LMX_REQUIRE(S == 0 || (S >= 2 && S <= 65535),
-              "lmx_k_tcn_forward: S %d (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)", S);
-  LMX_REQUIRE(S == 0 || (p >= 0.0 && p < 1.0), "lmx_k_tcn_forward: p %g outside [0, 1)", p);
+  LMX_TRY(lmx_tcn_check_call("lmx_k_tcn_forward", n, T, S, p));
   if (n == 0) return LMX_OK;
-  const int Smax = S > 0 ? S : 1;
-  LMX_REQUIRE((int64_t)n * Smax <= 0x7fffffff, "lmx_k_tcn_forward: n %d x S %d workgroups do not fit one grid", n, Smax);
-  LMX_REQUIRE(x && pred && stats, "lmx_k_tcn_forward: null pointer");
-  LMX_REQUIRE(S == 0 || (seeds_host && workspace), "lmx_k_tcn_forward: S = %d needs seeds_host and a workspace", S);
-  LMX_REQUIRE((((uintptr_t)x | (uintptr_t)pred | (uintptr_t)stats | (uintptr_t)trunk) & 3) == 0 && ((uintptr_t)workspace & 7) == 0,
-              "lmx_k_tcn_forward: misaligned pointer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  unsigned grid = 0;
+  int dev = -1;
+  LMX_TRY(lmx_gait_launch_prologue("lmx_k_tcn_forward", n, S, x, pred, stats, {trunk}, seeds_host, workspace, st, &grid, &dev));
   TcnArgs a;
   a.w = *w;
   a.x = x;
@@ -263,21 +257,16 @@ extern "C" int lmx_k_tcn_forward(const lmx_tcn_weights_t* w, const float* x, con
   a.T = T;
   a.S = S;
   a.MT = (T + 15) / 16;
-  a.thr = S > 0 ? lmx_tcn_threshold(p) : 0;
-  a.scale = S > 0 ? lmx_tcn_keep_scale(p) : 1.0f;
+  a.thr = S > 0 ? lmx_gait_threshold(p) : 0;
+  a.scale = S > 0 ? lmx_gait_keep_scale(p) : 1.0f;
   const int lds_bytes = (2 * a.MT * 16 * LD + TAIL) * (int)sizeof(float);
   LMX_REQUIRE(lds_bytes <= LDS_LIMIT, "lmx_k_tcn_forward: two tiles of %d x %d f32 and the head need %d bytes of LDS, a workgroup has %d",
               a.MT * 16, LD, lds_bytes, LDS_LIMIT);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int dev = -1;
-  LMX_TRY(lmx_stream_device(st, &dev));
-  if (S > 0) LMX_HIP(hipMemcpyAsync(workspace, seeds_host, (size_t)n * 8, hipMemcpyHostToDevice, st));
-  const unsigned grid = (unsigned)(n * Smax);
   if (a.MT <= 4)
     LMX_TRY(launch<1>(a, grid, lds_bytes, dev, st));
   else if (a.MT <= 8)
     LMX_TRY(launch<2>(a, grid, lds_bytes, dev, st));
   else
     LMX_TRY(launch<4>(a, grid, lds_bytes, dev, st));
-  return lmx_tcn_stats_launch(pred, stats, n, S, st);
+  return lmx_gait_stats_launch(pred, stats, n, S, st);
 }

@@ -1,10 +1,10 @@
 // tcn_image.h — the weight image of the TCN gait model (written by lmx/native.py write_tcn_image, read by host_tcn_image.cpp) as the
-// model handle (tcn_model.hip) sees it.  Host code only: nothing here needs HIP.
+// model handle (gait_model.hip) sees it.  Host code only: nothing here needs HIP.
 //
 // The container is image.h's (header, config block, directory of 88-byte entries, 64-byte aligned data, version 1), kind TCN:
 //   config  at 48      12 x i32 (input_dim, n_blocks, k, head, channels[8]; channels beyond n_blocks are 0) then 1 x f64 (p)
 //   tensors            all f32, the FOLDED weight-norm weights g * v / ||v|| as torch's parametrisation evaluates them, in the order the
-//                      kernel's B operand wants (tcn.h lmx_tcn_packed_index; include/lmx.h lmx_tcn_weights_t):
+//                      kernel's B operand wants (gait.h lmx_gait_packed_index; include/lmx.h lmx_tcn_weights_t):
 //     block.{i}.conv{1,2}.w   [k * Q][N / 16][64][4]    entry [j * Q + q][nt][l][e] = W[16 nt + (l & 15)][16 q + 4 (l >> 4) + e][j]
 //     block.{i}.conv{1,2}.b   [N]
 //     block.{i}.res.w         [Q][N / 16][64][4], block.{i}.res.b [N]      only where the block's channel count changes

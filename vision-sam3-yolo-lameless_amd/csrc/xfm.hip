@@ -12,10 +12,8 @@
 //   FFN: 64 hidden columns at a time through U, fc2 accumulates over the chunks in registers.
 // Rows t >= T: h starts as zeros there and stays finite, they are masked as keys (their score is -inf, so P is exactly 0 where V holds
 // them), never pooled, and never leave the LDS.
-#include "common.h"
+#include "gait_launch.h"
 #include "xfm.h"
-
-int lmx_tcn_stats_launch(const float* pred, float* stats, int n, int S, hipStream_t st);  // tcn.hip
 
 namespace {
 
@@ -192,7 +190,7 @@ __global__ __launch_bounds__(NW * 64) void xfm_forward_kernel(const XfmArgs a) {
             float v = 0.f;
             if (t < T) {
               v = acc[mi][ni][e] + bias + a.w.pe[t * D + c];
-              if (drop) v = lmx_tcn_keep(seed, stream0, (uint64_t)(t * D + c), a.thr) ? v * a.scale : 0.f;
+              if (drop) v = lmx_gait_keep(seed, stream0, (uint64_t)(t * D + c), a.thr) ? v * a.scale : 0.f;
             }
             hb[t * LD + c] = v;
           }
@@ -297,7 +295,7 @@ __global__ __launch_bounds__(NW * 64) void xfm_forward_kernel(const XfmArgs a) {
                 const int t = m * 16 + 4 * g + e;
                 float pv = s[kt][e] / sum[e];
                 if (drop && t < T && key < T)
-                  pv = lmx_tcn_keep(seed, site_p, ((uint64_t)(hd * T + t)) * (uint64_t)T + (uint64_t)key, a.thr) ? pv * a.scale : 0.f;
+                  pv = lmx_gait_keep(seed, site_p, ((uint64_t)(hd * T + t)) * (uint64_t)T + (uint64_t)key, a.thr) ? pv * a.scale : 0.f;
                 if (t < T) col += pv;
                 s[kt][e] = pv;
               }
@@ -346,7 +344,7 @@ __global__ __launch_bounds__(NW * 64) void xfm_forward_kernel(const XfmArgs a) {
             for (int e = 0; e < 4; ++e) {
               const int t = m * 16 + 4 * g + e;
               float v = racc[mi][ni][e] + bias;
-              if (drop && t < T) v = lmx_tcn_keep(seed, stream0 + 2 + 4 * l, (uint64_t)(t * D + c), a.thr) ? v * a.scale : 0.f;
+              if (drop && t < T) v = lmx_gait_keep(seed, stream0 + 2 + 4 * l, (uint64_t)(t * D + c), a.thr) ? v * a.scale : 0.f;
               hb[t * LD + c] += v;
             }
           }
@@ -376,7 +374,7 @@ __global__ __launch_bounds__(NW * 64) void xfm_forward_kernel(const XfmArgs a) {
                 const int t = m * 16 + 4 * g + e;
                 float v = acc[mi][ni][e] + bias;
                 v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-                if (drop && t < T) v = lmx_tcn_keep(seed, stream0 + 3 + 4 * l, (uint64_t)(t * FF + j), a.thr) ? v * a.scale : 0.f;
+                if (drop && t < T) v = lmx_gait_keep(seed, stream0 + 3 + 4 * l, (uint64_t)(t * FF + j), a.thr) ? v * a.scale : 0.f;
                 ub[t * LDU + ni * 16 + r] = v;
               }
             }
@@ -399,7 +397,7 @@ __global__ __launch_bounds__(NW * 64) void xfm_forward_kernel(const XfmArgs a) {
             for (int e = 0; e < 4; ++e) {
               const int t = m * 16 + 4 * g + e;
               float v = racc[mi][ni][e] + bias;
-              if (drop && t < T) v = lmx_tcn_keep(seed, stream0 + 4 + 4 * l, (uint64_t)(t * D + c), a.thr) ? v * a.scale : 0.f;
+              if (drop && t < T) v = lmx_gait_keep(seed, stream0 + 4 + 4 * l, (uint64_t)(t * D + c), a.thr) ? v * a.scale : 0.f;
               hb[t * LD + c] += v;
             }
           }
@@ -458,7 +456,7 @@ __global__ __launch_bounds__(NW * 64) void xfm_forward_kernel(const XfmArgs a) {
         for (int e = 0; e < 4; ++e) s += w1[c4][e] * pooled[4 * c4 + e];
       }
     s = fmaxf(s, 0.f);
-    if (drop) s = lmx_tcn_keep(seed, stream0 + 4 * L + 1, (uint64_t)tid, a.thr) ? s * a.scale : 0.f;
+    if (drop) s = lmx_gait_keep(seed, stream0 + 4 * L + 1, (uint64_t)tid, a.thr) ? s * a.scale : 0.f;
     hid[tid] = w2 * s;  // the product of the second linear; thread 0 adds them in order
   }
   __syncthreads();
@@ -483,19 +481,17 @@ int launch(const XfmArgs& a, unsigned grid, int lds_bytes, int dev, hipStream_t 
 
 }  // namespace
 
-extern "C" int64_t lmx_xfm_workspace_bytes(int n) { return n > 0 ? (int64_t)n * 8 : 0; }
+extern "C" int64_t lmx_xfm_workspace_bytes(int n) { return lmx_gait_workspace_bytes(n); }
 
 extern "C" int lmx_k_xfm_forward(const lmx_xfm_weights_t* w, const float* x, const uint8_t* mask, const uint64_t* seeds_host, int n, int T, int S,
                                  double p, float* pred, float* stats, float* saliency, float* trunk, void* workspace, lmx_stream_t stream) {
   LMX_TRY(lmx_xfm_check_config("lmx_k_xfm_forward", w, true));
   LMX_TRY(lmx_xfm_check_call("lmx_k_xfm_forward", w, n, T, S, p, saliency != nullptr));
   if (n == 0) return LMX_OK;
-  const int Smax = S > 0 ? S : 1;
-  LMX_REQUIRE((int64_t)n * Smax <= 0x7fffffff, "lmx_k_xfm_forward: n %d x S %d workgroups do not fit one grid", n, Smax);
-  LMX_REQUIRE(x && pred && stats, "lmx_k_xfm_forward: null pointer");
-  LMX_REQUIRE(S == 0 || (seeds_host && workspace), "lmx_k_xfm_forward: S = %d needs seeds_host and a workspace", S);
-  LMX_REQUIRE((((uintptr_t)x | (uintptr_t)pred | (uintptr_t)stats | (uintptr_t)trunk | (uintptr_t)saliency) & 3) == 0 && ((uintptr_t)workspace & 7) == 0,
-              "lmx_k_xfm_forward: misaligned pointer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  unsigned grid = 0;
+  int dev = -1;
+  LMX_TRY(lmx_gait_launch_prologue("lmx_k_xfm_forward", n, S, x, pred, stats, {trunk, saliency}, seeds_host, workspace, st, &grid, &dev));
   XfmArgs a;
   a.w = *w;
   a.x = x;
@@ -509,8 +505,8 @@ extern "C" int lmx_k_xfm_forward(const lmx_xfm_weights_t* w, const float* x, con
   a.MT = (T + 15) / 16;
   const int dh = lmx_xfm_head_dim(*w);
   a.LDU = (3 * dh > 64 ? 3 * dh : 64) + 4;
-  a.thr = S > 0 ? lmx_tcn_threshold(p) : 0;
-  a.scale = S > 0 ? lmx_tcn_keep_scale(p) : 1.0f;
+  a.thr = S > 0 ? lmx_gait_threshold(p) : 0;
+  a.scale = S > 0 ? lmx_gait_keep_scale(p) : 1.0f;
   a.qs = lmx_xfm_q_scale(dh);
   // Up to 128 steps: 8 waves with one row tile each, two waves per SIMD; on the shipped shape they take 0.73 of the time of 4 waves with
   // two tiles each.  Beyond: 4 waves with three tiles each, because 8 waves with two spill 548 bytes per lane within
@@ -519,14 +515,9 @@ extern "C" int lmx_k_xfm_forward(const lmx_xfm_weights_t* w, const float* x, con
   const int lds_bytes = lds_floats(nw, a.MT * 16, a.LDU) * (int)sizeof(float);
   LMX_REQUIRE(lds_bytes <= LDS_LIMIT, "lmx_k_xfm_forward: two tiles of %d x %d f32, one of %d x %d and the rest need %d bytes of LDS, a workgroup has %d",
               a.MT * 16, LD, a.MT * 16, a.LDU, lds_bytes, LDS_LIMIT);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int dev = -1;
-  LMX_TRY(lmx_stream_device(st, &dev));
-  if (S > 0) LMX_HIP(hipMemcpyAsync(workspace, seeds_host, (size_t)n * 8, hipMemcpyHostToDevice, st));
-  const unsigned grid = (unsigned)(n * Smax);
   if (nw == 8)
     LMX_TRY((launch<8, 1>(a, grid, lds_bytes, dev, st)));
   else
     LMX_TRY((launch<4, 3>(a, grid, lds_bytes, dev, st)));
-  return lmx_tcn_stats_launch(pred, stats, n, S, st);
+  return lmx_gait_stats_launch(pred, stats, n, S, st);
 }

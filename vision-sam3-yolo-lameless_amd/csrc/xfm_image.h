@@ -1,9 +1,9 @@
 // xfm_image.h — the weight image of the gait transformer (written by lmx/native.py write_xfm_image, read by host_xfm_image.cpp) as
-// the model handle (xfm_model.hip) sees it.  Host code only: nothing here needs HIP.
+// the model handle (gait_model.hip) sees it.  Host code only: nothing here needs HIP.
 //
 // The container is image.h's (header, config block, directory of 88-byte entries, 64-byte aligned data, version 1), kind XFM:
 //   config  at 48      8 x i32 (input_dim, d_model, n_heads, n_layers, ff, head, max_len, 0) then 1 x f64 (p)
-//   tensors            all f32; a linear layer [K -> N] is [Q][N / 16][64][4] in the kernel's B-operand order (xfm.h, tcn.h), Q = ceil(K / 16):
+//   tensors            all f32; a linear layer [K -> N] is [Q][N / 16][64][4] in the kernel's B-operand order (xfm.h, gait.h), Q = ceil(K / 16):
 //     in.w [F -> D], in.b [D], pe [max_len][D]
 //     layer.{l}.ln1.g / ln1.b [D]; qkv.w [H * D / 16][3 dh / 16][64][4]: per head one linear layer [D -> 3 dh] with the rows q_i | k_i | v_i
 //     of in_proj_weight; qkv.b [H][3 dh]; out.w [D -> D], out.b [D]; ln2.g / ln2.b [D]; ff1.w [D -> FF], ff1.b [FF]; ff2.w [FF -> D], ff2.b [D]

@@ -545,21 +545,26 @@ def tcn_keep_bits(seed, sample, site, n_sites, count, p):
     return keep
 
 
+def tcn_check_config(who, input_dim, channels, k, head):
+    """The list of include/lmx.h, refused as the library refuses it: LmxError names the field."""
+    if not 1 <= len(channels) <= 8:
+        raise LmxError(f"{who}: n_blocks {len(channels)} outside 1 .. 8")
+    if not 1 <= input_dim <= 64:
+        raise LmxError(f"{who}: input_dim {input_dim} outside 1 .. 64")
+    if k not in (2, 3):
+        raise LmxError(f"{who}: k {k} is neither 2 nor 3")
+    if not 1 <= head <= 64:
+        raise LmxError(f"{who}: head {head} outside 1 .. 64")
+    for i, c in enumerate(channels):
+        if c % 16 or not 16 <= c <= 64:
+            raise LmxError(f"{who}: channels[{i}] = {c} is not a multiple of 16 up to 64")
+
+
 def tcn_weights(input_dim, channels, k, head, tensors):
     """lmx_tcn_weights_t over the packed f32 tensors of lmx.tcn.pack_tensors (all on one GPU for tcn_forward, all on the CPU for
     tcn_forward_host).  The struct keeps the tensors alive.  Configurations outside the list of include/lmx.h are refused here with
     the field named, as the library refuses them."""
-    if not 1 <= len(channels) <= 8:
-        raise LmxError(f"tcn_weights: n_blocks {len(channels)} outside 1 .. 8")
-    if not 1 <= input_dim <= 64:
-        raise LmxError(f"tcn_weights: input_dim {input_dim} outside 1 .. 64")
-    if k not in (2, 3):
-        raise LmxError(f"tcn_weights: k {k} is neither 2 nor 3")
-    if not 1 <= head <= 64:
-        raise LmxError(f"tcn_weights: head {head} outside 1 .. 64")
-    for i, c in enumerate(channels):
-        if c % 16 or not 16 <= c <= 64:
-            raise LmxError(f"tcn_weights: channels[{i}] = {c} is not a multiple of 16 up to 64")
+    tcn_check_config("tcn_weights", input_dim, channels, k, head)
     devs = {t.device for t in tensors.values()}
     if len(devs) != 1:
         raise LmxError(f"tcn_weights: tensors on different devices ({sorted(map(str, devs))})")
@@ -588,15 +593,21 @@ def tcn_weights(input_dim, channels, k, head, tensors):
     return w
 
 
-def _tcn_args(who, w, x, seeds, n_samples, p):
-    """(n, T, S, the seeds as a uint64 numpy array or None) after the checks both forwards share."""
+def _gait_args(who, w, x, mask, seeds, n_samples, p, saliency, max_T, limit=""):
+    """(n, T, S, the seeds as a uint64 numpy array or None) after the checks every forward of a gait model shares; `limit` words
+    T's bound as the library does."""
     import numpy as np
 
     if x.dtype != torch.float32 or x.dim() != 3 or x.shape[2] != w.input_dim or not x.is_contiguous():
         raise LmxError(f"{who}: x must be a contiguous float32 [n, T, {w.input_dim}] tensor, got {x.dtype} {tuple(x.shape)} strides {x.stride()}")
     n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
-    if not 1 <= T <= TCN_MAX_T:
-        raise LmxError(f"{who}: T {T} outside 1 .. {TCN_MAX_T}")
+    if not 1 <= T <= max_T:
+        raise LmxError(f"{who}: T {T} outside 1 .. {limit}{max_T}")
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (n, T) or not mask.is_contiguous() or mask.device != x.device):
+        raise LmxError(f"{who}: mask must be a contiguous uint8 [{n}, {T}] tensor on {x.device} (nonzero = masked), got {mask.dtype} "
+                       f"{tuple(mask.shape)} on {mask.device}")
+    if saliency and S:
+        raise LmxError(f"{who}: saliency is read in eval mode only, S = {S}")
     if S == 1 or S < 0 or S > 65535:
         raise LmxError(f"{who}: S {S} (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)")
     if S and not 0.0 <= p < 1.0:
@@ -615,37 +626,48 @@ def _tcn_args(who, w, x, seeds, n_samples, p):
     return n, T, S, sd
 
 
+def _gait_forward(model, host, w, x, mask, seeds, n_samples, p, saliency, trunk):
+    """What tcn_forward, tcn_forward_host, xfm_forward and xfm_forward_host share: the checks, pred / stats / saliency / trunk allocated
+    where x lives, and the call of lmx_k_<model>_forward (device: with a seed workspace, on torch's stream) or lmx_h_<model>_forward
+    (host).  Returns (pred, stats, saliency or None, trunk or None); only the transformer takes a mask and gives a saliency."""
+    xfm = model == "xfm"
+    who = f"{model}_forward_host" if host else f"{model}_forward"
+    if host:
+        if x.is_cuda or w._device.type != "cpu":
+            raise LmxError(f"{who} takes CPU tensors and CPU weights")
+        dev = torch.device("cpu")
+    else:
+        dev = _dev(x)
+        if w._device != dev:
+            raise LmxError(f"{who}: the weights are on {w._device}, x is on {dev}")
+    n, T, S, sd = _gait_args(who, w, x, mask, seeds, n_samples, p, saliency, *((w.max_len, "max_len ") if xfm else (TCN_MAX_T,)))
+    smax = max(S, 1)
+    pred = torch.empty((n, smax), dtype=torch.float32, device=dev)
+    stats = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    sal = torch.empty((n, T), dtype=torch.float32, device=dev) if saliency else None
+    tr = torch.empty((n, smax, T, w.d_model if xfm else w.channels[w.n_blocks - 1]), dtype=torch.float32, device=dev) if trunk else None
+    lib, name = _lib.load(), f"lmx_{'h' if host else 'k'}_{model}_forward"
+    args = [C.byref(w), _ptr(x)] + [_ptr(mask)] * xfm + [C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p), _ptr(pred),
+                                                          _ptr(stats)] + [_ptr(sal)] * xfm + [_ptr(tr)]
+    if not host:
+        ws = torch.empty((max(int(getattr(lib, f"lmx_{model}_workspace_bytes")(n)), 8) // 8,), dtype=torch.int64, device=dev)
+        args += [_ptr(ws), _stream(dev)]
+    check(getattr(lib, name)(*args), name)
+    return pred, stats, sal, tr
+
+
 def tcn_forward(w, x, seeds, n_samples, p, trunk=False):
     """The whole TCN for n clips and S samples in ONE launch (lmx_k_tcn_forward, csrc/tcn.hip): x f32 [n, T, input_dim] on the device,
     seeds: n 64-bit values on the host -> (pred f32 [n, max(S, 1)], stats f32 [n, 2] = mean and unbiased std, trunk f32
     [n, max(S, 1), T, C] or None).  S = 0 is eval mode; S = 1 is refused.  `w`: tcn_weights over device tensors."""
-    dev = _dev(x)
-    if w._device != dev:
-        raise LmxError(f"tcn_forward: the weights are on {w._device}, x is on {dev}")
-    n, T, S, sd = _tcn_args("tcn_forward", w, x, seeds, n_samples, p)
-    smax = max(S, 1)
-    pred = torch.empty((n, smax), dtype=torch.float32, device=dev)
-    stats = torch.empty((n, 2), dtype=torch.float32, device=dev)
-    tr = torch.empty((n, smax, T, w.channels[w.n_blocks - 1]), dtype=torch.float32, device=dev) if trunk else None
-    lib = _lib.load()
-    ws = torch.empty((max(int(lib.lmx_tcn_workspace_bytes(n)), 8) // 8,), dtype=torch.int64, device=dev)
-    check(lib.lmx_k_tcn_forward(C.byref(w), _ptr(x), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p), _ptr(pred),
-                                _ptr(stats), _ptr(tr), _ptr(ws), _stream(dev)), "lmx_k_tcn_forward")
+    pred, stats, _, tr = _gait_forward("tcn", False, w, x, None, seeds, n_samples, p, False, trunk)
     return pred, stats, tr
 
 
 def tcn_forward_host(w, x, seeds, n_samples, p, trunk=False):
     """lmx_h_tcn_forward: the same network in plain C++ on CPU tensors, with the same keep bits (no GPU).  `w`: tcn_weights over CPU
     tensors; returns CPU tensors."""
-    if x.is_cuda or w._device.type != "cpu":
-        raise LmxError("tcn_forward_host takes CPU tensors and CPU weights")
-    n, T, S, sd = _tcn_args("tcn_forward_host", w, x, seeds, n_samples, p)
-    smax = max(S, 1)
-    pred = torch.empty((n, smax), dtype=torch.float32)
-    stats = torch.empty((n, 2), dtype=torch.float32)
-    tr = torch.empty((n, smax, T, w.channels[w.n_blocks - 1]), dtype=torch.float32) if trunk else None
-    check(_lib.load().lmx_h_tcn_forward(C.byref(w), _ptr(x), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p), _ptr(pred),
-                                        _ptr(stats), _ptr(tr)), "lmx_h_tcn_forward")
+    pred, stats, _, tr = _gait_forward("tcn", True, w, x, None, seeds, n_samples, p, False, trunk)
     return pred, stats, tr
 
 
@@ -721,55 +743,17 @@ def xfm_weights(input_dim, d_model, n_heads, n_layers, ff, head, max_len, tensor
     return w
 
 
-def _xfm_args(who, w, x, mask, seeds, n_samples, p, saliency):
-    """(n, T, S, the seeds as a uint64 numpy array or None) after the checks both forwards share."""
-    if x.dtype != torch.float32 or x.dim() != 3 or x.shape[2] != w.input_dim or not x.is_contiguous():
-        raise LmxError(f"{who}: x must be a contiguous float32 [n, T, {w.input_dim}] tensor, got {x.dtype} {tuple(x.shape)} strides {x.stride()}")
-    n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
-    if not 1 <= T <= w.max_len:
-        raise LmxError(f"{who}: T {T} outside 1 .. max_len {w.max_len}")
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (n, T) or not mask.is_contiguous() or mask.device != x.device):
-        raise LmxError(f"{who}: mask must be a contiguous uint8 [{n}, {T}] tensor on {x.device} (nonzero = masked), got {mask.dtype} "
-                       f"{tuple(mask.shape)} on {mask.device}")
-    if saliency and S:
-        raise LmxError(f"{who}: saliency is read in eval mode only, S = {S}")
-    return _tcn_args(who, w, x, seeds, S, p)
-
-
 def xfm_forward(w, x, mask, seeds, n_samples, p, saliency=False, trunk=False):
     """The whole gait transformer for n clips and S samples in ONE launch (lmx_k_xfm_forward, csrc/xfm.hip): x f32 [n, T, input_dim] and
     mask (None or uint8 [n, T], nonzero = masked) on the device, seeds: n 64-bit values on the host -> (pred f32 [n, max(S, 1)], stats f32
     [n, 2] = mean and unbiased std, saliency f32 [n, T] or None (S = 0 only), trunk f32 [n, max(S, 1), T, D] or None)."""
-    dev = _dev(x)
-    if w._device != dev:
-        raise LmxError(f"xfm_forward: the weights are on {w._device}, x is on {dev}")
-    n, T, S, sd = _xfm_args("xfm_forward", w, x, mask, seeds, n_samples, p, saliency)
-    smax = max(S, 1)
-    pred = torch.empty((n, smax), dtype=torch.float32, device=dev)
-    stats = torch.empty((n, 2), dtype=torch.float32, device=dev)
-    sal = torch.empty((n, T), dtype=torch.float32, device=dev) if saliency else None
-    tr = torch.empty((n, smax, T, w.d_model), dtype=torch.float32, device=dev) if trunk else None
-    lib = _lib.load()
-    ws = torch.empty((max(int(lib.lmx_xfm_workspace_bytes(n)), 8) // 8,), dtype=torch.int64, device=dev)
-    check(lib.lmx_k_xfm_forward(C.byref(w), _ptr(x), _ptr(mask), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p),
-                                _ptr(pred), _ptr(stats), _ptr(sal), _ptr(tr), _ptr(ws), _stream(dev)), "lmx_k_xfm_forward")
-    return pred, stats, sal, tr
+    return _gait_forward("xfm", False, w, x, mask, seeds, n_samples, p, saliency, trunk)
 
 
 def xfm_forward_host(w, x, mask, seeds, n_samples, p, saliency=False, trunk=False):
     """lmx_h_xfm_forward: the same network in plain C++ on CPU tensors, with the same keep bits (no GPU).  `w`: xfm_weights over CPU
     tensors; returns CPU tensors."""
-    if x.is_cuda or w._device.type != "cpu":
-        raise LmxError("xfm_forward_host takes CPU tensors and CPU weights")
-    n, T, S, sd = _xfm_args("xfm_forward_host", w, x, mask, seeds, n_samples, p, saliency)
-    smax = max(S, 1)
-    pred = torch.empty((n, smax), dtype=torch.float32)
-    stats = torch.empty((n, 2), dtype=torch.float32)
-    sal = torch.empty((n, T), dtype=torch.float32) if saliency else None
-    tr = torch.empty((n, smax, T, w.d_model), dtype=torch.float32) if trunk else None
-    check(_lib.load().lmx_h_xfm_forward(C.byref(w), _ptr(x), _ptr(mask), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, float(p),
-                                        _ptr(pred), _ptr(stats), _ptr(sal), _ptr(tr)), "lmx_h_xfm_forward")
-    return pred, stats, sal, tr
+    return _gait_forward("xfm", True, w, x, mask, seeds, n_samples, p, saliency, trunk)
 
 
 def xfm_mask(kp_conf, n_kp, det_conf, target=125):

@@ -888,112 +888,94 @@ class NativeFused(_NativeHandle):
         return records, rec_layout
 
 
-class NativeTcn(_NativeHandle):
+def _vp(a):
+    """void* of a tensor, of a numpy array or of nothing"""
+    return C.c_void_p(0 if a is None else a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data)
+
+
+class _NativeGait(_NativeHandle):
+    """What NativeTcn and NativeXfm do alike: lmx_<model>_open_host(path, max_clips, max_samples), the checks of a series (and of a
+    mask) on the device and on the host, one seed per clip, and the outputs of a call."""
+
+    def __init__(self, path, max_clips, max_samples=10, device=None):
+        self._max_samples = int(max_samples)
+        super().__init__(path, max_clips, device)
+
+    def _open_args(self, max_batch):
+        return (int(max_batch), self._max_samples)
+
+    def _seeds(self, seeds, n, S, what):
+        if S == 0:
+            return None
+        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
+        if sd.shape != (n,):
+            raise LmxError(f"{type(self).__name__}.{what}: {n} clips need {n} seeds, got {sd.shape}")
+        return sd
+
+    def _args(self, what, x, mask, seeds, n_samples, saliency):
+        """(x, mask, n, T, S, seeds, pred, stats, saliency or None) of one call: tensors on the handle's device for "score", numpy
+        arrays for "score_host"."""
+        name, dev, F, host = type(self).__name__, self.device, self.info.input_dim, what == "score_host"
+        if host:
+            x = np.ascontiguousarray(x, np.float32)
+            if x.ndim != 3 or x.shape[2] != F:
+                raise LmxError(f"{name}.score_host: x must be a float32 [n, T, {F}] array")
+        elif not (x.is_cuda and x.device == dev and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == F and x.is_contiguous()):
+            raise LmxError(f"{name}.score: x must be a contiguous float32 [n, T, {F}] tensor on {dev}")
+        n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
+        if host and mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != (n, T):
+                raise LmxError(f"{name}.score_host: mask must be a uint8 [{n}, {T}] array")
+        elif mask is not None and not (mask.device == dev and mask.dtype == torch.uint8 and tuple(mask.shape) == (n, T) and mask.is_contiguous()):
+            raise LmxError(f"{name}.score: mask must be a contiguous uint8 [{n}, {T}] tensor on {dev}")
+        sd = self._seeds(seeds, n, S, what)
+        empty = (lambda *shape: np.empty(shape, np.float32)) if host else (lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev))
+        return x, mask, n, T, S, sd, empty(n, max(S, 1)), empty(n, 2), empty(n, T) if saliency else None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+
+class NativeTcn(_NativeGait):
     """lmx_tcn_open_host(path, max_clips, max_samples) on `device` (default: torch's current device): the TCN gait model from its
     weight image.  score / score_host give the bits of lmx.tcn.TcnScorer.score (tests/test_gpu_tcn.py)."""
     _PREFIX, _INFO = "lmx_tcn_", TcnInfo
 
-    def __init__(self, path, max_clips, max_samples=10, device=None):
-        self._max_samples = int(max_samples)
-        super().__init__(path, max_clips, device)
-
-    def _open_args(self, max_batch):
-        return (int(max_batch), self._max_samples)
-
-    @staticmethod
-    def _seeds(seeds, n, S, what):
-        if S == 0:
-            return None
-        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
-        if sd.shape != (n,):
-            raise LmxError(f"NativeTcn.{what}: {n} clips need {n} seeds, got {sd.shape}")
-        return sd
-
     def score(self, x, seeds, n_samples=10):
         """f32 [n, T, input_dim] device tensor, n host seeds -> (mean [n], std [n], pred [n, max(S, 1)]) on torch's current stream."""
-        if not (x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.info.input_dim
-                and x.is_contiguous()):
-            raise LmxError(f"NativeTcn.score: x must be a contiguous float32 [n, T, {self.info.input_dim}] tensor on {self.device}")
-        n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
-        sd = self._seeds(seeds, n, S, "score")
-        pred = torch.empty((n, max(S, 1)), dtype=torch.float32, device=self.device)
-        stats = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        x, _, n, T, S, sd, pred, stats, _ = self._args("score", x, None, seeds, n_samples, False)
         with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            check(self._lib.lmx_tcn_score(self._handle(), C.c_void_p(x.data_ptr()), C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S,
-                                          C.c_void_p(pred.data_ptr()), C.c_void_p(stats.data_ptr()), st), "lmx_tcn_score")
+            check(self._lib.lmx_tcn_score(self._handle(), _vp(x), _vp(sd), n, T, S, _vp(pred), _vp(stats), self._stream()), "lmx_tcn_score")
         return stats[:, 0], stats[:, 1], pred
 
     def score_host(self, x, seeds, n_samples=10):
         """f32 [n, T, input_dim] numpy array -> numpy (mean, std, pred) (lmx_tcn_score_host: uploads, scores, downloads, synchronises)."""
-        a = np.ascontiguousarray(x, np.float32)
-        if a.ndim != 3 or a.shape[2] != self.info.input_dim:
-            raise LmxError(f"NativeTcn.score_host: x must be a float32 [n, T, {self.info.input_dim}] array")
-        n, T, S = a.shape[0], a.shape[1], int(n_samples)
-        sd = self._seeds(seeds, n, S, "score_host")
-        pred, stats = np.empty((n, max(S, 1)), np.float32), np.empty((n, 2), np.float32)
+        x, _, n, T, S, sd, pred, stats, _ = self._args("score_host", x, None, seeds, n_samples, False)
         with torch.cuda.device(self.device):
-            check(self._lib.lmx_tcn_score_host(self._handle(), a.ctypes.data, sd.ctypes.data if sd is not None else None, n, T, S,
-                                               pred.ctypes.data, stats.ctypes.data), "lmx_tcn_score_host")
+            check(self._lib.lmx_tcn_score_host(self._handle(), _vp(x), _vp(sd), n, T, S, _vp(pred), _vp(stats)), "lmx_tcn_score_host")
         return stats[:, 0], stats[:, 1], pred
 
 
-class NativeXfm(_NativeHandle):
+class NativeXfm(_NativeGait):
     """lmx_xfm_open_host(path, max_clips, max_samples) on `device` (default: torch's current device): the gait transformer from its
     weight image.  score / score_host give the bits of lmx.xfm.XfmScorer (tests/test_gpu_xfm.py)."""
     _PREFIX, _INFO = "lmx_xfm_", XfmInfo
 
-    def __init__(self, path, max_clips, max_samples=10, device=None):
-        self._max_samples = int(max_samples)
-        super().__init__(path, max_clips, device)
-
-    def _open_args(self, max_batch):
-        return (int(max_batch), self._max_samples)
-
-    @staticmethod
-    def _seeds(seeds, n, S, what):
-        if S == 0:
-            return None
-        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
-        if sd.shape != (n,):
-            raise LmxError(f"NativeXfm.{what}: {n} clips need {n} seeds, got {sd.shape}")
-        return sd
-
     def score(self, x, mask=None, seeds=None, n_samples=10, saliency=False):
         """f32 [n, T, input_dim] and uint8 [n, T] (or None) device tensors, n host seeds -> (mean [n], std [n], pred [n, max(S, 1)],
         saliency [n, T] or None) on torch's current stream."""
-        if not (x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.info.input_dim
-                and x.is_contiguous()):
-            raise LmxError(f"NativeXfm.score: x must be a contiguous float32 [n, T, {self.info.input_dim}] tensor on {self.device}")
-        n, T, S = int(x.shape[0]), int(x.shape[1]), int(n_samples)
-        if mask is not None and not (mask.device == self.device and mask.dtype == torch.uint8 and tuple(mask.shape) == (n, T) and mask.is_contiguous()):
-            raise LmxError(f"NativeXfm.score: mask must be a contiguous uint8 [{n}, {T}] tensor on {self.device}")
-        sd = self._seeds(seeds, n, S, "score")
-        pred = torch.empty((n, max(S, 1)), dtype=torch.float32, device=self.device)
-        stats = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-        sal = torch.empty((n, T), dtype=torch.float32, device=self.device) if saliency else None
+        x, mask, n, T, S, sd, pred, stats, sal = self._args("score", x, mask, seeds, n_samples, saliency)
         with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            check(self._lib.lmx_xfm_score(self._handle(), C.c_void_p(x.data_ptr()), C.c_void_p(mask.data_ptr() if mask is not None else 0),
-                                          C.c_void_p(sd.ctypes.data if sd is not None else 0), n, T, S, C.c_void_p(pred.data_ptr()),
-                                          C.c_void_p(stats.data_ptr()), C.c_void_p(sal.data_ptr() if sal is not None else 0), st), "lmx_xfm_score")
+            check(self._lib.lmx_xfm_score(self._handle(), _vp(x), _vp(mask), _vp(sd), n, T, S, _vp(pred), _vp(stats), _vp(sal), self._stream()),
+                  "lmx_xfm_score")
         return stats[:, 0], stats[:, 1], pred, sal
 
     def score_host(self, x, mask=None, seeds=None, n_samples=10, saliency=False):
         """numpy f32 [n, T, input_dim] and uint8 [n, T] (or None) -> numpy (mean, std, pred, saliency or None) (lmx_xfm_score_host:
         uploads, scores, downloads, synchronises)."""
-        a = np.ascontiguousarray(x, np.float32)
-        if a.ndim != 3 or a.shape[2] != self.info.input_dim:
-            raise LmxError(f"NativeXfm.score_host: x must be a float32 [n, T, {self.info.input_dim}] array")
-        n, T, S = a.shape[0], a.shape[1], int(n_samples)
-        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-        if mk is not None and mk.shape != (n, T):
-            raise LmxError(f"NativeXfm.score_host: mask must be a uint8 [{n}, {T}] array")
-        sd = self._seeds(seeds, n, S, "score_host")
-        pred, stats = np.empty((n, max(S, 1)), np.float32), np.empty((n, 2), np.float32)
-        sal = np.empty((n, T), np.float32) if saliency else None
+        x, mask, n, T, S, sd, pred, stats, sal = self._args("score_host", x, mask, seeds, n_samples, saliency)
         with torch.cuda.device(self.device):
-            check(self._lib.lmx_xfm_score_host(self._handle(), a.ctypes.data, mk.ctypes.data if mk is not None else None,
-                                               sd.ctypes.data if sd is not None else None, n, T, S, pred.ctypes.data, stats.ctypes.data,
-                                               sal.ctypes.data if sal is not None else None), "lmx_xfm_score_host")
+            check(self._lib.lmx_xfm_score_host(self._handle(), _vp(x), _vp(mask), _vp(sd), n, T, S, _vp(pred), _vp(stats), _vp(sal)),
+                  "lmx_xfm_score_host")
         return stats[:, 0], stats[:, 1], pred, sal

@@ -5,13 +5,13 @@ pose series, in ONE launch for a batch of clips (csrc/tcn.hip; include/lmx.h "Th
 tensors the kernel and the weight image hold, ``TcnScorer`` scores clips on the device or, with ``backend="host"``, through the
 plain C++ forward ``lmx_h_tcn_forward`` without a GPU.  There is no torch arithmetic here."""
 import dataclasses
-import hashlib
 
 import numpy as np
 import torch
 
 from . import kernels as K
 from ._lib import LmxError
+from .gait import GaitScorer, clip_seed, pack_conv  # noqa: F401 — the seeds and the operand order are every gait model's
 
 MAX_BLOCKS, MAX_CH, MAX_T, MAX_HEAD = 8, 64, 256, 64
 
@@ -42,32 +42,10 @@ class TcnConfig:
 
     def validate(self, who="TcnConfig"):
         """The list of include/lmx.h; LmxError names the field."""
-        if not 1 <= len(self.channels) <= MAX_BLOCKS:
-            raise LmxError(f"{who}: n_blocks {len(self.channels)} outside 1 .. {MAX_BLOCKS}")
-        if not 1 <= self.input_dim <= MAX_CH:
-            raise LmxError(f"{who}: input_dim {self.input_dim} outside 1 .. {MAX_CH}")
-        if self.kernel_size not in (2, 3):
-            raise LmxError(f"{who}: k {self.kernel_size} is neither 2 nor 3")
-        if not 1 <= self.head <= MAX_HEAD:
-            raise LmxError(f"{who}: head {self.head} outside 1 .. {MAX_HEAD}")
-        for i, c in enumerate(self.channels):
-            if c % 16 or not 16 <= c <= MAX_CH:
-                raise LmxError(f"{who}: channels[{i}] = {c} is not a multiple of 16 up to {MAX_CH}")
+        K.tcn_check_config(who, self.input_dim, self.channels, self.kernel_size, self.head)
         if not 0.0 <= self.dropout < 1.0:
             raise LmxError(f"{who}: p {self.dropout} outside [0, 1)")
         return self
-
-
-def pack_conv(w):
-    """f32 [N, Cin, k] -> f32 [k * Q, N / 16, 64, 4], the MFMA B-operand order of csrc/tcn.h:
-    entry [j * Q + q][nt][l][e] = W[16 nt + (l & 15)][16 q + 4 (l >> 4) + e][j], zeros where the input channel is >= Cin."""
-    w = np.asarray(w, np.float32)
-    n, cin, k = w.shape
-    q = (cin + 15) // 16
-    wp = np.zeros((n, 16 * q, k), np.float32)
-    wp[:, :cin] = w
-    # (nt, r, q, g, e, j) -> (j, q, nt, g, r, e); the lane is l = 16 g + r
-    return np.ascontiguousarray(wp.reshape(n // 16, 16, q, 4, 4, k).transpose(5, 2, 0, 3, 1, 4)).reshape(k * q, n // 16, 64, 4)
 
 
 def pack_tensors(cfg, folded):
@@ -94,21 +72,11 @@ def pack_tensors(cfg, folded):
     return out
 
 
-def clip_seed(video_id):
-    """The seed of a clip: the first 8 bytes of the SHA-256 of its video_id, little-endian."""
-    return int.from_bytes(hashlib.sha256(str(video_id).encode()).digest()[:8], "little")
-
-
-class TcnScorer:
+class TcnScorer(GaitScorer):
     """The network on `device` (backend "device", default) or on the host (backend "host": lmx_h_tcn_forward, no GPU)."""
+    _pack = staticmethod(pack_tensors)
 
-    def __init__(self, cfg, folded, device=None, backend="device"):
-        if backend not in ("device", "host"):
-            raise LmxError(f"TcnScorer: backend {backend!r} is neither 'device' nor 'host'")
-        self.cfg, self.backend = cfg.validate("TcnScorer"), backend
-        self.device = torch.device("cpu") if backend == "host" else torch.device("cuda" if device is None else device)
-        self.tensors = {k: torch.from_numpy(v).to(self.device) for k, v in pack_tensors(cfg, folded).items()}
-        self.weights = K.tcn_weights(cfg.input_dim, cfg.channels, cfg.kernel_size, cfg.head, self.tensors)
+    _weights = staticmethod(lambda cfg, tensors: K.tcn_weights(cfg.input_dim, cfg.channels, cfg.kernel_size, cfg.head, tensors))
 
     def forward(self, x, seeds, n_samples=10, trunk=False):
         """x f32 [n, T, input_dim] -> (pred [n, max(S, 1)], stats [n, 2], trunk [n, max(S, 1), T, C] or None)."""

@@ -12,7 +12,7 @@ import torch
 
 from . import kernels as K
 from ._lib import LmxError
-from .tcn import clip_seed, pack_conv  # noqa: F401 — the seeds and the operand order are the TCN's
+from .gait import GaitScorer, clip_seed, pack_conv  # noqa: F401 — the seeds and the operand order are every gait model's
 
 
 @dataclasses.dataclass(frozen=True)
@@ -47,7 +47,7 @@ class XfmConfig:
 
 
 def pack_linear(w):
-    """f32 [N, K] -> f32 [Q, N / 16, 64, 4]: a convolution with one tap in the TCN's operand order (lmx.tcn.pack_conv)."""
+    """f32 [N, K] -> f32 [Q, N / 16, 64, 4]: a convolution with one tap in the shared operand order (lmx.gait.pack_conv)."""
     w = np.asarray(w, np.float32)
     return pack_conv(w.reshape(w.shape[0], w.shape[1], 1))
 
@@ -83,16 +83,11 @@ def pack_tensors(cfg, weights):
     return {k: np.ascontiguousarray(v, np.float32) for k, v in out.items()}
 
 
-class XfmScorer:
+class XfmScorer(GaitScorer):
     """The network on `device` (backend "device", default) or on the host (backend "host": lmx_h_xfm_forward, no GPU)."""
+    _pack = staticmethod(pack_tensors)
 
-    def __init__(self, cfg, weights, device=None, backend="device"):
-        if backend not in ("device", "host"):
-            raise LmxError(f"XfmScorer: backend {backend!r} is neither 'device' nor 'host'")
-        self.cfg, self.backend = cfg.validate("XfmScorer"), backend
-        self.device = torch.device("cpu") if backend == "host" else torch.device("cuda" if device is None else device)
-        self.tensors = {k: torch.from_numpy(v).to(self.device) for k, v in pack_tensors(cfg, weights).items()}
-        self.weights = K.xfm_weights(*cfg.shape(), self.tensors)
+    _weights = staticmethod(lambda cfg, tensors: K.xfm_weights(*cfg.shape(), tensors))
 
     def forward(self, x, mask=None, seeds=None, n_samples=10, trunk=False, saliency=False):
         """x f32 [n, T, input_dim], mask None or uint8 / bool [n, T] (nonzero = masked) -> (pred [n, max(S, 1)], stats [n, 2],
