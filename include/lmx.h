@@ -1180,6 +1180,159 @@ int lmx_xfm_score(lmx_xfm* m, const float* x, const uint8_t* mask, const uint64_
 int lmx_xfm_score_host(lmx_xfm* m, const float* x_host, const uint8_t* mask_host, const uint64_t* seeds_host, int n, int T, int S,
                        float* pred_host, float* stats_host, float* saliency_host);
 
+/* ==== The graph transformer: a cow's lameness score, its MC-dropout spread, node scores and attention per graph (csrc/gfm.hip,
+ * csrc/host_gfm.cpp) ====
+ * Replaces services/graph-transformer-pipeline/app/model/{graphormer,encodings,attention,layers}.py: CowLamenessGraphormer over one
+ * graph per cow (a node per video), its predict_with_uncertainty (ten train-mode forwards of several hundred launches each) and the
+ * eleventh eval-mode forward for node scores and attention, each of which recomputes all-pairs shortest paths on the host.  Here the
+ * graph is prepared ONCE on the host (lmx_h_gfm_graph), the attention bias ONCE per graph on the device, and n graphs x S samples run in
+ * ONE launch: one workgroup per (graph, sample), the residual stream resident in LDS from the node features to the sigmoid.
+ * The network (batch-free, x [N][F]; D = d_model, H = n_heads, dh = D / H, L = n_layers, FF = ff):
+ *   h  = drop_0( LN( x W_in^T + b_in ) ) + enc                     the encoding is added AFTER the dropout
+ *   enc[i] = ( deg_in[min(in_deg_i, max_degree)] + deg_out[min(out_deg_i, max_degree)] ) + ( pe_i W_t^T + b_t )
+ *            the time term only when the graph has timestamps: days_i = min((t_i - min t) / 86400, 365) in f32 from f32 timestamps,
+ *            pe_i[2k] = sinf(days_i * div_term[k]), pe_i[2k + 1] = cosf(days_i * div_term[k]); div_term comes from the weights
+ *   bias[head][i][j] = spd[idx(i, j)][head] + edge_mlp(edge_attr[e])[head]    e = the edge i -> j; the edge term is 0 without an edge
+ *            idx = min(spd, max_spd) + 1 over the UNDIRECTED graph; unreachable pairs and pairs beyond max_spd both map to max_spd + 1;
+ *            idx = 1 on the diagonal.  edge_mlp = Linear(3 -> 2H), ReLU, Linear(2H -> H); no dropout touches it, so the bias is the same
+ *            for every sample of a graph.  Where two edges share (src, dst) THE LATER EDGE IN EDGE ORDER WINS (lmx_h_gfm_graph lists
+ *            kNN edges first, so a temporal edge wins).  The reference assigns bias[src, dst] = ... with duplicate indices, which torch
+ *            leaves undefined; the rule is pinned by this text, not by torch.
+ *   layer l = 0 .. L-1:
+ *     a  = LN(h; g1, b1)                       eps 1e-5, biased variance, two passes (mean, then the squared deviations), 1.0f / sqrtf
+ *     q, k, v = a Wq^T + bq, ...               separate q_proj / k_proj / v_proj; head i = channels i*dh .. (i+1)*dh-1
+ *     s[i][t][u] = (q_i[t] . k_i[u]) * c + bias[i][t][u]      c = float(dh^-0.5): 0.25 for dh 16, the rounded 0.17677669 for dh 32
+ *     P = drop_{1+6l}( softmax_u(s) )          max-subtracted, the accurate expf, ONE DIVISION PER ELEMENT by the row's sum
+ *     h  = h + drop_{2+6l}( concat_i( P_i v_i ) Wo^T + bo )
+ *     a  = LN(h; g2, b2)
+ *     h  = h + drop_{4+6l}( drop_{3+6l}( gelu( a W1^T + b1 ) ) W2^T + b2 )    gelu exact: 0.5 x (1 + erff(x * 0.70710678f))
+ *     the virtual-node attention: rows [vn_l ; h], N + 1 of them; vn_l is layer l's OWN parameter, not carried from the layer before.
+ *       The same attention with its own weights, the bias extended by a zero row and a zero column, NO LayerNorm in front and NO
+ *       residual: y = drop_{6+6l}( concat_i( drop_{5+6l}(softmax(s))_i v_i ) Wo^T + bo ), and rows 1 .. N of y REPLACE h.
+ *       vn = LN( gelu( y[0] U1^T + c1 ) U2^T + c2 ) (D -> 2D -> D) is used of the LAST layer only: the earlier ones are dead and are
+ *       not computed.
+ *   trunk = LN(h; gf, bf)
+ *   r  = LN( relu( [ mean_i trunk[i] ; vn ; sum_i a_i trunk[i] ] Wc^T + bc ) )      a = softmax over the nodes of
+ *                                                                                    tanhf( trunk A1^T + a1 ) A2^T + a2  (D -> D/2 -> 1)
+ *   pred = 1 / (1 + expf(-( P3 drop_{6L+2}( relu( P2 drop_{6L+1}( relu( P1 r + p1 ) ) + p2 ) ) + p3 )))       D -> D/2 -> D/4 -> 1
+ *   node_pred[i] = 1 / (1 + expf(-( N2 relu( N1 trunk[i] + n1 ) + n2 )))            eval mode only (site 6L+3 is numbered, never drawn:
+ *                                                                                    the reference discards its train-mode node scores)
+ *   attn_to_target[i] = (1/H) sum_head P_head[i][target]   of the LAST layer's GRAPH attention (not its virtual-node attention), eval
+ *                                                          mode only; the heads are added in ascending order
+ * All arithmetic is f32 with f32 accumulation (the exact f32-input MFMA on the device), LayerNorm in two passes, the accurate expf /
+ * erff / tanhf / sinf / cosf: the device, lmx_h_gfm_forward and torch in float32 differ in summation order and in the last places of
+ * those functions only.
+ * MC dropout: the keep decision of the TCN section above (the same mix, thr and scale), stream = sample * n_sites + site with
+ * n_sites = 6 L + 4.  Element numbers u (i, j count nodes from 0; in the virtual-node attention row / column 0 is the virtual node):
+ *   site 0 (input)                                  u = i * D + c
+ *   site 1 + 6l (attention probabilities)           u = (head * N + i) * N + j
+ *   sites 2 + 6l, 4 + 6l (out_proj, FFN output)     u = i * D + c
+ *   site 3 + 6l (FFN hidden)                        u = i * FF + j
+ *   site 5 + 6l (virtual-node attention probabilities)   u = (head * (N+1) + i) * (N+1) + j
+ *   site 6 + 6l (virtual-node out_proj)             u = i * D + c over N + 1 rows
+ *   sites 6L + 1, 6L + 2 (the graph head's hidden layers)   u = j
+ *   site 6L + 3 (the node head)                     numbered but never drawn
+ * lmx_h_tcn_keep_bits serves these sites unchanged.  Parity with torch's generator is statistical only.
+ *
+ * The graph a caller hands over is prepared by lmx_h_gfm_graph on the HOST from f32 embeddings [N][E], optional f32 timestamps [N] and k
+ * (GraphormerGraphBuilder); N 1 .. LMX_GFM_MAX_NODES.  The rules are pinned HERE where numpy's cannot be:
+ *   kNN edges first: cosine similarity in DOUBLE from the f32 embeddings (each row divided by its norm + 1e-8, the products added in
+ *   ascending channel order); k = min(k, N - 1); the neighbours of i are the k most similar j != i, listed as edges i -> j in ASCENDING
+ *   similarity (the reference's argsort[-k:]), EXACT TIES GOING TO THE LOWER INDEX FIRST; weight = max(0, sim) rounded to f32;
+ *   attributes (weight, 1, 0).
+ *   Temporal edges then, only with timestamps and N > 1: the nodes in ascending timestamp, STABLE IN INDEX for equal timestamps (the
+ *   service defaults a missing one to 0.0); consecutive nodes a, b are joined a -> b, then b -> a; weight = exp(-|t_b - t_a| / 86400)
+ *   in double from the f32 timestamps, rounded to f32; attributes (weight, 0, 1).
+ *   deg_in / deg_out: incoming / outgoing edges counted with duplicates, clamped to max_degree.  win[i][j] = the LAST edge i -> j in
+ *   edge order, or -1.  idx[i][j] as above, by a breadth-first search per node over the symmetrised edge set.
+ *   Unpinned against numpy: the BLAS summation order and float32 products of its similarity matrix, its f32 exp, and argsort on ties
+ *   (an unstable quicksort); a graph without similarity ties and with distinct timestamps comes out the same.
+ * edges_host must hold N * min(k, N-1) + 2 * (N-1) pairs (src, dst), edge_attr_host as many triples.
+ *
+ * lmx_gfm_graphs_t describes n graphs of differing N to both forwards, nodes, edges and matrices concatenated in graph order:
+ *   node_off_host, edge_off_host  i32 [n + 1] on the HOST, ascending from 0: graph g has N_g = node_off[g+1] - node_off[g] nodes and its
+ *                                 edges are edge_off[g] .. edge_off[g+1] - 1
+ *   x f32 [sum N][input_dim]; timestamps NULL or f32 [sum N]; has_time NULL (no graph has timestamps) or u8 [n];
+ *   deg_in, deg_out u8 [sum N]; idx u8 [sum N^2] and win i32 [sum N^2] (graph g's [N_g][N_g] matrix starts at sum_{g' < g} N_g'^2; win
+ *   counts from the graph's first edge); edge_attr f32 [sum E][3]; target NULL or i32 [n] (the node whose attention column is read)
+ *   DEVICE pointers for lmx_k_gfm_forward, HOST pointers for lmx_h_gfm_forward (the two offset arrays are on the host for both).
+ *   node_off_host, edge_off_host and seeds_host are copied to the device asynchronously: they must stay valid and unchanged until the
+ *   work enqueued on `stream` has run (for a caller that frees or reuses them at once: until the stream is synchronised).  The device
+ *   arrays must live on the stream's device.
+ * lmx_gfm_weights_t describes one network to both forwards likewise.  A linear layer marked "packed" is stored as the gait transformer
+ * stores one (f32 [Q][N / 16][64][4], 16-byte aligned); one marked "transposed" is the plain W^T, f32 [K][N].
+ *   in_w packed [F -> D], in_b, in_g, in_beta [D]; deg_in, deg_out [max_degree + 1][D]; time_w packed [D -> D], time_b [D],
+ *   div_term [D / 2]; spd [max_spd + 2][H]; e1_w plain [2H][3], e1_b [2H], e2_w plain [H][2H], e2_b [H]
+ *   per layer: ln1_g, ln1_b; qkv_w: H packed layers [D -> 3 dh] one after the other (rows q_i | k_i | v_i), qkv_b [H][3 dh]; out_w packed
+ *   [D -> D], out_b; ln2_g, ln2_b; ff1_w packed [D -> FF], ff1_b; ff2_w packed [FF -> D], ff2_b; vn [D]; vqkv_w, vqkv_b, vout_w, vout_b
+ *   the virtual-node attention's, as qkv / out
+ *   vu1_w transposed [D][2D], vu1_b [2D], vu2_w transposed [2D][D], vu2_b, vu_g, vu_beta [D]: vn_update of the LAST layer
+ *   lnf_g, lnf_b; pool1_w packed [D -> PD], pool1_b [PD], pool2_w [PD], pool2_b [1], PD = D / 2 rounded up to 16 with zeros;
+ *   comb_w transposed [3D][D], comb_b, comb_g, comb_beta [D]; ph1_w transposed [D][D/2], ph1_b; ph2_w transposed [D/2][D/4], ph2_b;
+ *   ph3_w [D/4], ph3_b [1]; nh1_w packed [D -> PD], nh1_b [PD], nh2_w [PD], nh2_b [1]
+ * Accepted: d_model a multiple of 16 up to 128; d_model / n_heads 16 or 32; n_layers 1 .. 8; ff a multiple of 16 up to 512; input_dim
+ * 1 .. 64; edge_dim 3; max_degree 0 .. 255; max_spd >= 0 with max_spd + 2 <= 32; N 1 .. LMX_GFM_MAX_NODES per graph; S = 0 or
+ * 2 .. 65535; p in [0, 1).  LMX_GFM_MAX_NODES = 95: with the virtual node 96 rows of the residual stream, the LayerNorm output (132
+ * floats each) and the work tile (100 floats for a head width of 32) plus the waves' patches and the readout's vectors are 154,624 of
+ * the 163,840 bytes of LDS; 112 rows would need 178 KB.
+ *
+ * lmx_k_gfm_forward: seeds_host u64 [n] on the HOST (NULL allowed when S == 0).  `workspace`: lmx_gfm_workspace_bytes(n, cells, H) bytes
+ * on the device, 16-byte aligned, cells = sum N^2; it receives the seeds, the two offset arrays and bias f32 [H][N][N] per graph, filled
+ * by a small kernel in front of the forward on the same stream.  pred f32 [n][max(S, 1)]; stats f32 [n][2] as for the TCN; with S == 0
+ * only: node_pred f32 [sum N] and attn_to_target f32 [sum N] (NULL allowed; the latter needs target), summed in a fixed order without
+ * floating-point atomics; for tests: trunk f32, graph g's [max(S, 1)][N_g][D] starting at node_off[g] * max(S, 1) * D, and vn f32
+ * [n][max(S, 1)][D] (NULL allowed).  Rows beyond a graph's N stay finite, are never keys, are never pooled and never leave the LDS.
+ * Refused with LMX_EINVAL before anything is launched: a configuration outside the list (the field named), offsets that do not ascend
+ * from 0, an N outside 1 .. LMX_GFM_MAX_NODES, S or p out of range, node_pred / attn_to_target with S > 0, null or misaligned
+ * pointers.  n = 0 launches nothing.
+ * lmx_h_gfm_forward is the same network in plain C++ on HOST pointers with the same keep bits: f32, sequential sums. */
+#define LMX_GFM_MAX_LAYERS 8
+#define LMX_GFM_MAX_NODES 95
+typedef struct { int32_t input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd;
+                 const float *in_w, *in_b, *in_g, *in_beta, *deg_in, *deg_out, *time_w, *time_b, *div_term, *spd, *e1_w, *e1_b, *e2_w, *e2_b;
+                 const float *ln1_g[LMX_GFM_MAX_LAYERS], *ln1_b[LMX_GFM_MAX_LAYERS], *qkv_w[LMX_GFM_MAX_LAYERS], *qkv_b[LMX_GFM_MAX_LAYERS];
+                 const float *out_w[LMX_GFM_MAX_LAYERS], *out_b[LMX_GFM_MAX_LAYERS], *ln2_g[LMX_GFM_MAX_LAYERS], *ln2_b[LMX_GFM_MAX_LAYERS];
+                 const float *ff1_w[LMX_GFM_MAX_LAYERS], *ff1_b[LMX_GFM_MAX_LAYERS], *ff2_w[LMX_GFM_MAX_LAYERS], *ff2_b[LMX_GFM_MAX_LAYERS];
+                 const float *vn[LMX_GFM_MAX_LAYERS], *vqkv_w[LMX_GFM_MAX_LAYERS], *vqkv_b[LMX_GFM_MAX_LAYERS], *vout_w[LMX_GFM_MAX_LAYERS];
+                 const float *vout_b[LMX_GFM_MAX_LAYERS];
+                 const float *vu1_w, *vu1_b, *vu2_w, *vu2_b, *vu_g, *vu_beta, *lnf_g, *lnf_b, *pool1_w, *pool1_b, *pool2_w, *pool2_b;
+                 const float *comb_w, *comb_b, *comb_g, *comb_beta, *ph1_w, *ph1_b, *ph2_w, *ph2_b, *ph3_w, *ph3_b;
+                 const float *nh1_w, *nh1_b, *nh2_w, *nh2_b; } lmx_gfm_weights_t;
+typedef struct { int32_t n, reserved; const int32_t *node_off_host, *edge_off_host; const float *x, *timestamps; const uint8_t* has_time;
+                 const uint8_t *deg_in, *deg_out, *idx; const int32_t* win; const float* edge_attr; const int32_t* target; } lmx_gfm_graphs_t;
+int lmx_h_gfm_graph(const float* emb_host /* [N][E] */, const float* timestamps_host /* NULL or [N] */, int N, int E, int k, int max_degree,
+                    int max_spd, int32_t* edges_host /* [cap][2] */, float* edge_attr_host /* [cap][3] */, int32_t* n_edges_host,
+                    uint8_t* deg_in_host /* [N] */, uint8_t* deg_out_host /* [N] */, uint8_t* idx_host /* [N][N] */,
+                    int32_t* win_host /* [N][N] */);
+int64_t lmx_gfm_workspace_bytes(int n, int64_t cells, int n_heads);
+int lmx_k_gfm_forward(const lmx_gfm_weights_t* w_host, const lmx_gfm_graphs_t* graphs_host, const uint64_t* seeds_host /* [n] */, int S,
+                      double p, float* pred /* [n][max(S,1)] */, float* stats /* [n][2] */, float* node_pred /* NULL or [sum N], S == 0 */,
+                      float* attn_to_target /* NULL or [sum N], S == 0 */, float* trunk /* NULL or [sum N][max(S,1)][D] */,
+                      float* vn /* NULL or [n][max(S,1)][D] */, void* workspace, lmx_stream_t stream);
+int lmx_h_gfm_forward(const lmx_gfm_weights_t* w_host, const lmx_gfm_graphs_t* graphs_host, const uint64_t* seeds_host, int S, double p,
+                      float* pred_host, float* stats_host, float* node_pred_host, float* attn_to_target_host, float* trunk_host,
+                      float* vn_host);
+
+/* ==== MODEL level: graph scores from prepared graphs (csrc/gait_model.hip, csrc/gfm_image.h, csrc/host_gfm_image.cpp) =================
+ * services/graph-transformer-pipeline/app/main.py behind a handle: the model comes from a WEIGHT IMAGE (kind 6) that
+ * lmx.native.write_gfm_image writes (csrc/gfm_image.h has the config block and the tensors); handle rules as for lmx_tcn.  The handle
+ * owns the workspace for max_graphs graphs of max_nodes_total nodes in all.  lmx_gfm_score: the graphs as for lmx_k_gfm_forward (DEVICE
+ * arrays, the two offset arrays on the host), seeds_host on the host -> pred, stats and, when S == 0 and they are not NULL, node_pred and
+ * attn_to_target on the device: lmx_k_gfm_forward with the image's dropout probability; it only enqueues on `stream`.  n <= max_graphs,
+ * sum N <= max_nodes_total, S <= max_samples.  lmx_gfm_score_host takes the graphs' arrays and returns the outputs in HOST memory, and
+ * synchronises (examples/gfm_score.c). */
+typedef struct lmx_gfm lmx_gfm;
+typedef struct { int32_t input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd, max_nodes, max_graphs, max_nodes_total,
+                 max_samples; double p; } lmx_gfm_info_t;
+int lmx_gfm_image_check_host(const char* path_host, lmx_gfm_info_t* info_host);
+int lmx_gfm_open_host(const char* path_host, int max_graphs, int max_nodes_total, int max_samples, lmx_gfm** out_host);
+void lmx_gfm_close(lmx_gfm* m);
+int lmx_gfm_info(const lmx_gfm* m, lmx_gfm_info_t* info_host);
+int lmx_gfm_score(lmx_gfm* m, const lmx_gfm_graphs_t* graphs_host, const uint64_t* seeds_host, int S, float* pred, float* stats,
+                  float* node_pred, float* attn_to_target, lmx_stream_t stream);
+int lmx_gfm_score_host(lmx_gfm* m, const lmx_gfm_graphs_t* graphs_host, const uint64_t* seeds_host, int S, float* pred_host,
+                       float* stats_host, float* node_pred_host, float* attn_to_target_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,27 @@ class XfmInfo(C.Structure):  # lmx_xfm_info_t
                                          "reserved")] + [("p", C.c_double)]
 
 
+class GfmWeights(C.Structure):  # lmx_gfm_weights_t: device pointers for lmx_k_gfm_forward, host pointers for lmx_h_gfm_forward
+    MAX_LAYERS = 8
+    HEAD_FIELDS = ("in_w", "in_b", "in_g", "in_beta", "deg_in", "deg_out", "time_w", "time_b", "div_term", "spd", "e1_w", "e1_b", "e2_w", "e2_b")
+    LAYER_FIELDS = ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_g", "ln2_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b", "vn", "vqkv_w",
+                    "vqkv_b", "vout_w", "vout_b")
+    TAIL_FIELDS = ("vu1_w", "vu1_b", "vu2_w", "vu2_b", "vu_g", "vu_beta", "lnf_g", "lnf_b", "pool1_w", "pool1_b", "pool2_w", "pool2_b", "comb_w",
+                   "comb_b", "comb_g", "comb_beta", "ph1_w", "ph1_b", "ph2_w", "ph2_b", "ph3_w", "ph3_b", "nh1_w", "nh1_b", "nh2_w", "nh2_b")
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "n_layers", "ff", "edge_dim", "max_degree", "max_spd")] + [
+        (n, C.c_void_p) for n in HEAD_FIELDS] + [(n, C.c_void_p * 8) for n in LAYER_FIELDS] + [(n, C.c_void_p) for n in TAIL_FIELDS]
+
+
+class GfmGraphs(C.Structure):  # lmx_gfm_graphs_t: the two offset arrays on the host, the rest where the forward runs
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "node_off_host", "edge_off_host", "x", "timestamps", "has_time", "deg_in", "deg_out", "idx", "win", "edge_attr", "target")]
+
+
+class GfmInfo(C.Structure):  # lmx_gfm_info_t
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "n_layers", "ff", "edge_dim", "max_degree", "max_spd", "max_nodes",
+                                         "max_graphs", "max_nodes_total", "max_samples")] + [("p", C.c_double)]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -272,6 +293,16 @@ SIGNATURES = {
     "lmx_xfm_info": (_I, [_VP, C.POINTER(XfmInfo)]),
     "lmx_xfm_score": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "lmx_xfm_score_host": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
+    "lmx_h_gfm_graph": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_gfm_workspace_bytes": (_I64, [_I, _I64, _I]),
+    "lmx_k_gfm_forward": (_I, [C.POINTER(GfmWeights), C.POINTER(GfmGraphs), _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_h_gfm_forward": (_I, [C.POINTER(GfmWeights), C.POINTER(GfmGraphs), _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_gfm_image_check_host": (_I, [C.c_char_p, C.POINTER(GfmInfo)]),
+    "lmx_gfm_open_host": (_I, [C.c_char_p, _I, _I, _I, C.POINTER(_VP)]),
+    "lmx_gfm_close": (None, [_VP]),
+    "lmx_gfm_info": (_I, [_VP, C.POINTER(GfmInfo)]),
+    "lmx_gfm_score": (_I, [_VP, C.POINTER(GfmGraphs), _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_gfm_score_host": (_I, [_VP, C.POINTER(GfmGraphs), _VP, _I, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -499,3 +499,61 @@ def xfm_from_state_dict(sd, n_heads=4, dropout=0.1, max_len=150):
                         max_len=int(max_len)).validate("xfm_from_state_dict")
     xfm.pack_tensors(cfg, w)  # every shape against the configuration
     return cfg, w
+
+
+# the reference's module paths of CowLamenessGraphormer -> the names of lmx.gfm's weights ({i}: the layer)
+GFM_KEYS = (("input_proj.0", "in"), ("input_proj.1", "in_norm"), ("encodings.temporal_enc.time_proj", "time"),
+            ("encodings.edge_enc.edge_proj.0", "edge1"), ("encodings.edge_enc.edge_proj.2", "edge2"), ("encoder.final_norm", "lnf"),
+            ("readout.attention_pool.0", "pool1"), ("readout.attention_pool.2", "pool2"), ("readout.combine.0", "comb"),
+            ("readout.combine.2", "comb_norm"), ("pred_head.0", "ph1"), ("pred_head.3", "ph2"), ("pred_head.6", "ph3"), ("node_pred.0", "nh1"),
+            ("node_pred.3", "nh2"))
+GFM_LAYER_KEYS = (("layers.{i}.norm1", "ln1"), ("layers.{i}.self_attn.q_proj", "q"), ("layers.{i}.self_attn.k_proj", "k"),
+                  ("layers.{i}.self_attn.v_proj", "v"), ("layers.{i}.self_attn.out_proj", "out"), ("layers.{i}.norm2", "ln2"),
+                  ("layers.{i}.ffn.0", "ff1"), ("layers.{i}.ffn.3", "ff2"), ("virtual_node_layers.{i}.vn_attention.q_proj", "vq"),
+                  ("virtual_node_layers.{i}.vn_attention.k_proj", "vk"), ("virtual_node_layers.{i}.vn_attention.v_proj", "vv"),
+                  ("virtual_node_layers.{i}.vn_attention.out_proj", "vout"), ("virtual_node_layers.{i}.vn_update.0", "vu1"),
+                  ("virtual_node_layers.{i}.vn_update.2", "vu2"), ("virtual_node_layers.{i}.vn_update.3", "vu_norm"))
+
+
+def gfm_from_state_dict(sd, num_heads=8, dropout=0.1):
+    """A CowLamenessGraphormer state_dict under the reference's key names (220 of them for six layers: `input_proj.0.weight` ...
+    `node_pred.3.bias`, the buffer `encodings.temporal_enc.div_term` included) -> (lmx.gfm.GfmConfig, weights).  The shape is inferred
+    from the tensors; the number of heads and the dropout probability are not in a state_dict.  What the kernel refuses is refused
+    here with the field named.  Weights' keys: the second names of GFM_KEYS with .weight / .bias, deg_in, deg_out, spd, div_term,
+    layer.{i}.<second names of GFM_LAYER_KEYS>.{weight,bias} and layer.{i}.vn, all float32 in torch's layouts."""
+    from . import gfm
+    from ._lib import LmxError
+
+    def plain(key):
+        if key not in sd:
+            raise LmxError(f"gfm_from_state_dict: {key} is missing")
+        return sd[key].detach().float().cpu().contiguous()
+
+    n_layers = 0
+    while any(k.startswith(f"encoder.layers.{n_layers}.") for k in sd):
+        n_layers += 1
+    if n_layers == 0 or "input_proj.0.weight" not in sd:
+        raise LmxError("gfm_from_state_dict: no input_proj.0.weight or encoder.layers.0.* keys: not a CowLamenessGraphormer state_dict")
+    w = {}
+    for theirs, ours in GFM_KEYS:
+        w[f"{ours}.weight"], w[f"{ours}.bias"] = plain(f"{theirs}.weight"), plain(f"{theirs}.bias")
+    w["deg_in"] = plain("encodings.centrality_enc.degree_encoder.weight")
+    w["deg_out"] = plain("encodings.centrality_enc.out_degree_encoder.weight")
+    w["spd"] = plain("encodings.spatial_enc.spd_bias.weight")
+    w["div_term"] = plain("encodings.temporal_enc.div_term")
+    for i in range(n_layers):
+        for theirs, ours in GFM_LAYER_KEYS:
+            key = "encoder." + theirs.format(i=i)
+            w[f"layer.{i}.{ours}.weight"], w[f"layer.{i}.{ours}.bias"] = plain(key + ".weight"), plain(key + ".bias")
+        w[f"layer.{i}.vn"] = plain(f"encoder.virtual_node_layers.{i}.virtual_node").reshape(-1)
+    for name in ("in.weight", "layer.0.ff1.weight", "edge1.weight", "spd", "deg_in", "ph3.weight"):
+        if w[name].dim() != 2:
+            raise LmxError(f"gfm_from_state_dict: {name} is not a matrix")
+    if w["ph3.weight"].shape[0] != 1:
+        raise LmxError(f"gfm_from_state_dict: {w['ph3.weight'].shape[0]} outputs of the graph head: one is supported")
+    cfg = gfm.GfmConfig(input_dim=int(w["in.weight"].shape[1]), d_model=int(w["in.weight"].shape[0]), n_heads=int(num_heads), n_layers=n_layers,
+                        ff=int(w["layer.0.ff1.weight"].shape[0]), edge_dim=int(w["edge1.weight"].shape[1]),
+                        max_degree=int(w["deg_in"].shape[0]) - 1, max_spd=int(w["spd"].shape[0]) - 2,
+                        dropout=float(dropout)).validate("gfm_from_state_dict")
+    gfm.pack_tensors(cfg, w)  # every shape against the configuration
+    return cfg, w

@@ -770,6 +770,225 @@ def xfm_mask(kp_conf, n_kp, det_conf, target=125):
     return out
 
 
+# ---- the graph transformer (include/lmx.h "The graph transformer"; csrc/gfm.hip, csrc/host_gfm.cpp) -----------------------------------
+GFM_MAX_NODES = 95
+
+
+def gfm_check_config(who, input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd):
+    """The list of include/lmx.h, refused as the library refuses it: LmxError names the field."""
+    if not 1 <= input_dim <= 64:
+        raise LmxError(f"{who}: input_dim {input_dim} outside 1 .. 64")
+    if d_model % 16 or not 16 <= d_model <= 128:
+        raise LmxError(f"{who}: d_model {d_model} is not a multiple of 16 up to 128")
+    if n_heads < 1 or d_model % n_heads or d_model // n_heads not in (16, 32):
+        raise LmxError(f"{who}: n_heads {n_heads} gives d_model {d_model} a head_dim that is neither 16 nor 32")
+    if not 1 <= n_layers <= 8:
+        raise LmxError(f"{who}: n_layers {n_layers} outside 1 .. 8")
+    if ff % 16 or not 16 <= ff <= 512:
+        raise LmxError(f"{who}: ff {ff} is not a multiple of 16 up to 512")
+    if edge_dim != 3:
+        raise LmxError(f"{who}: edge_dim {edge_dim} is not 3")
+    if not 0 <= max_degree <= 255:
+        raise LmxError(f"{who}: max_degree {max_degree} outside 0 .. 255")
+    if not 2 <= max_spd + 2 <= 32:
+        raise LmxError(f"{who}: max_spd {max_spd}: max_spd + 2 outside 2 .. 32")
+
+
+def gfm_tensor_shapes(input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd):
+    """Ordered {tensor name: shape} of one network: the fields of lmx_gfm_weights_t (`layer.{l}.<field>` for the per-layer ones), the
+    names of lmx.gfm.pack_tensors."""
+    D, qd, dh, H, pd = d_model, d_model // 16, d_model // n_heads, n_heads, (d_model // 2 + 15) // 16 * 16
+    out = {"in_w": ((input_dim + 15) // 16, qd, 64, 4), "in_b": (D,), "in_g": (D,), "in_beta": (D,), "deg_in": (max_degree + 1, D),
+           "deg_out": (max_degree + 1, D), "time_w": (qd, qd, 64, 4), "time_b": (D,), "div_term": (D // 2,), "spd": (max_spd + 2, H),
+           "e1_w": (2 * H, 3), "e1_b": (2 * H,), "e2_w": (H, 2 * H), "e2_b": (H,)}
+    for l in range(n_layers):
+        p = f"layer.{l}."
+        out.update({p + "ln1_g": (D,), p + "ln1_b": (D,), p + "qkv_w": (H * qd, 3 * dh // 16, 64, 4), p + "qkv_b": (H, 3 * dh),
+                    p + "out_w": (qd, qd, 64, 4), p + "out_b": (D,), p + "ln2_g": (D,), p + "ln2_b": (D,), p + "ff1_w": (qd, ff // 16, 64, 4),
+                    p + "ff1_b": (ff,), p + "ff2_w": (ff // 16, qd, 64, 4), p + "ff2_b": (D,), p + "vn": (D,),
+                    p + "vqkv_w": (H * qd, 3 * dh // 16, 64, 4), p + "vqkv_b": (H, 3 * dh), p + "vout_w": (qd, qd, 64, 4), p + "vout_b": (D,)})
+    out.update({"vu1_w": (D, 2 * D), "vu1_b": (2 * D,), "vu2_w": (2 * D, D), "vu2_b": (D,), "vu_g": (D,), "vu_beta": (D,), "lnf_g": (D,),
+                "lnf_b": (D,), "pool1_w": (qd, pd // 16, 64, 4), "pool1_b": (pd,), "pool2_w": (pd,), "pool2_b": (1,), "comb_w": (3 * D, D),
+                "comb_b": (D,), "comb_g": (D,), "comb_beta": (D,), "ph1_w": (D, D // 2), "ph1_b": (D // 2,), "ph2_w": (D // 2, D // 4),
+                "ph2_b": (D // 4,), "ph3_w": (D // 4,), "ph3_b": (1,), "nh1_w": (qd, pd // 16, 64, 4), "nh1_b": (pd,), "nh2_w": (pd,),
+                "nh2_b": (1,)})
+    return out
+
+
+def gfm_weights(input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd, tensors):
+    """lmx_gfm_weights_t over the f32 tensors of lmx.gfm.pack_tensors (all on one GPU for gfm_forward, all on the CPU for
+    gfm_forward_host).  The struct keeps the tensors alive.  Configurations outside the list of include/lmx.h are refused here with
+    the field named, as the library refuses them."""
+    shape = (input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd)
+    gfm_check_config("gfm_weights", *shape)
+    devs = {t.device for t in tensors.values()}
+    if len(devs) != 1:
+        raise LmxError(f"gfm_weights: tensors on different devices ({sorted(map(str, devs))})")
+    w = _lib.GfmWeights()
+    w.input_dim, w.d_model, w.n_heads, w.n_layers, w.ff, w.edge_dim, w.max_degree, w.max_spd = shape
+    for name, shp in gfm_tensor_shapes(*shape).items():
+        t = tensors.get(name)
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous():
+            raise LmxError(f"gfm_weights: {name} must be a contiguous float32 tensor of shape {shp}, got "
+                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
+        parts = name.split(".")
+        if parts[0] == "layer":
+            getattr(w, parts[2])[int(parts[1])] = t.data_ptr()
+        else:
+            setattr(w, name, t.data_ptr())
+    w._tensors, w._device = dict(tensors), devs.pop()
+    return w
+
+
+def gfm_graph(embeddings, timestamps, k, max_degree, max_spd):
+    """lmx_h_gfm_graph: f32 embeddings [N, E], None or f32 timestamps [N] (numpy) -> dict of numpy arrays: edges int32 [E, 2] (src, dst),
+    edge_attr f32 [E, 3], deg_in / deg_out uint8 [N], idx uint8 [N, N], win int32 [N, N] (host arithmetic, no GPU)."""
+    import numpy as np
+
+    emb = np.ascontiguousarray(embeddings, np.float32)
+    if emb.ndim != 2 or emb.shape[0] < 1 or emb.shape[1] < 1:
+        raise LmxError(f"gfm_graph: embeddings must be [N, E], got {emb.shape}")
+    N, E = emb.shape
+    if N > GFM_MAX_NODES:
+        raise LmxError(f"gfm_graph: N {N} outside 1 .. {GFM_MAX_NODES}")
+    ts = None if timestamps is None else np.ascontiguousarray(timestamps, np.float32)
+    if ts is not None and ts.shape != (N,):
+        raise LmxError(f"gfm_graph: timestamps {ts.shape} for {N} nodes")
+    cap = max(N * min(max(int(k), 0), N - 1) + 2 * (N - 1), 1)
+    edges, attr, ne = np.zeros((cap, 2), np.int32), np.zeros((cap, 3), np.float32), np.zeros((1,), np.int32)
+    din, dout, idx, win = np.zeros((N,), np.uint8), np.zeros((N,), np.uint8), np.zeros((N, N), np.uint8), np.zeros((N, N), np.int32)
+    check(_lib.load().lmx_h_gfm_graph(emb.ctypes.data, ts.ctypes.data if ts is not None else None, N, E, int(k), int(max_degree), int(max_spd),
+                                      edges.ctypes.data, attr.ctypes.data, ne.ctypes.data, din.ctypes.data, dout.ctypes.data, idx.ctypes.data,
+                                      win.ctypes.data), "lmx_h_gfm_graph")
+    n = int(ne[0])
+    return {"edges": edges[:n].copy(), "edge_attr": attr[:n].copy(), "deg_in": din, "deg_out": dout, "idx": idx, "win": win}
+
+
+class GfmBatch:
+    """n graphs of differing N as lmx_gfm_graphs_t wants them: nodes, edges and matrices concatenated on `device`, the two offset arrays
+    on the host.  graphs: dicts with x f32 [N, F], timestamps None or f32 [N], and gfm_graph's arrays; targets: None or one node per graph."""
+
+    def __init__(self, graphs, device, targets=None):
+        import numpy as np
+
+        self.n, self.device = len(graphs), torch.device(device)
+        self.sizes = [int(np.asarray(g["x"]).shape[0]) for g in graphs]
+        self.node_off = np.zeros((self.n + 1,), np.int32)
+        self.edge_off = np.zeros((self.n + 1,), np.int32)
+        self.node_off[1:] = np.cumsum(self.sizes)
+        self.edge_off[1:] = np.cumsum([len(g["edges"]) for g in graphs])
+        self.nodes, self.cells = int(self.node_off[-1]), int(sum(s * s for s in self.sizes))
+
+        def cat(key, dtype, tail=()):
+            parts = [np.ascontiguousarray(g[key], dtype).reshape((-1,) + tail) for g in graphs]
+            a = np.concatenate(parts, 0) if parts else np.zeros((0,) + tail, dtype)
+            if a.shape[0] == 0:
+                a = np.zeros((1,) + tail, dtype)  # a pointer the library may look at, never follow
+            return torch.from_numpy(a).to(self.device)
+
+        F = int(np.asarray(graphs[0]["x"]).shape[1]) if graphs else 1
+        self.input_dim = F
+        if any(np.asarray(g["x"]).ndim != 2 or np.asarray(g["x"]).shape[1] != F for g in graphs):
+            raise LmxError("GfmBatch: every x must be [N, input_dim] with one input_dim")
+        self.x = cat("x", np.float32, (F,))
+        timed = [g.get("timestamps") is not None for g in graphs]
+        self.has_time = torch.from_numpy(np.array(timed + [False], np.uint8)).to(self.device) if any(timed) else None
+        self.timestamps = None
+        if any(timed):
+            ts = [np.ascontiguousarray(g["timestamps"], np.float32) if t else np.zeros((s,), np.float32) for g, t, s in zip(graphs, timed, self.sizes)]
+            self.timestamps = torch.from_numpy(np.concatenate(ts)).to(self.device)
+        self.deg_in, self.deg_out = cat("deg_in", np.uint8), cat("deg_out", np.uint8)
+        self.idx, self.win = cat("idx", np.uint8), cat("win", np.int32)
+        self.edge_attr = cat("edge_attr", np.float32, (3,))
+        for key, want in (("deg_in", self.nodes), ("deg_out", self.nodes), ("idx", self.cells), ("win", self.cells)):
+            if max(want, 1) != getattr(self, key).shape[0]:
+                raise LmxError(f"GfmBatch: {key} has {getattr(self, key).shape[0]} entries, the graphs call for {want}")
+        self.target = None
+        if targets is not None:
+            if len(targets) != self.n:
+                raise LmxError(f"GfmBatch: {len(targets)} targets for {self.n} graphs")
+            self.target = torch.from_numpy(np.array(list(targets) + [0], np.int32)).to(self.device)
+
+    def struct(self):
+        g = _lib.GfmGraphs()
+        g.n = self.n
+        g.node_off_host, g.edge_off_host = self.node_off.ctypes.data, self.edge_off.ctypes.data
+        for name in ("x", "timestamps", "has_time", "deg_in", "deg_out", "idx", "win", "edge_attr", "target"):
+            t = getattr(self, name)
+            setattr(g, name, t.data_ptr() if t is not None else None)
+        return g
+
+
+def _gfm_forward(host, w, batch, seeds, n_samples, p, node, attn, trunk, vn):
+    import numpy as np
+
+    who = "gfm_forward_host" if host else "gfm_forward"
+    if not isinstance(batch, GfmBatch):
+        raise LmxError(f"{who}: the graphs come as a GfmBatch")
+    if host:
+        if batch.device.type != "cpu" or w._device.type != "cpu":
+            raise LmxError(f"{who} takes CPU tensors and CPU weights")
+        dev = torch.device("cpu")
+    else:
+        dev = _dev(batch.x)
+        if w._device != dev:
+            raise LmxError(f"{who}: the weights are on {w._device}, the graphs are on {dev}")
+    n, S = batch.n, int(n_samples)
+    if batch.n and batch.input_dim != w.input_dim:
+        raise LmxError(f"{who}: x has {batch.input_dim} features, the network takes {w.input_dim}")
+    for i, s in enumerate(batch.sizes):
+        if not 1 <= s <= GFM_MAX_NODES:
+            raise LmxError(f"{who}: graph {i} has N = {s} nodes, outside 1 .. {GFM_MAX_NODES}")
+    if S == 1 or S < 0 or S > 65535:
+        raise LmxError(f"{who}: S {S} (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)")
+    if S and not 0.0 <= p < 1.0:
+        raise LmxError(f"{who}: p {p} outside [0, 1)")
+    if (node or attn) and S:
+        raise LmxError(f"{who}: node_pred and attn_to_target are read in eval mode only, S = {S}")
+    if attn and batch.target is None:
+        raise LmxError(f"{who}: attn_to_target without targets")
+    sd = None
+    if S:
+        if seeds is None:
+            raise LmxError(f"{who}: S = {S} needs one seed per graph")
+        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
+        if sd.shape != (n,):
+            raise LmxError(f"{who}: seeds must be {n} 64-bit values, got {sd.shape}")
+    smax, D = max(S, 1), w.d_model
+
+    def buf(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+
+    pred, stats = buf(n, smax), buf(n, 2)
+    npred, at = (buf(batch.nodes) if node else None), (buf(batch.nodes) if attn else None)
+    tr, vv = (buf(batch.nodes * smax, D) if trunk else None), (buf(n, smax, D) if vn else None)
+    lib, g = _lib.load(), batch.struct()
+    args = [C.byref(w), C.byref(g), C.c_void_p(sd.ctypes.data if sd is not None else 0), S, float(p), _ptr(pred), _ptr(stats), _ptr(npred), _ptr(at),
+            _ptr(tr), _ptr(vv)]
+    if host:
+        check(lib.lmx_h_gfm_forward(*args), "lmx_h_gfm_forward")
+    else:
+        ws = torch.empty((max(int(lib.lmx_gfm_workspace_bytes(n, batch.cells, w.n_heads)), 16) // 16 + 1, 2), dtype=torch.int64, device=dev)
+        check(lib.lmx_k_gfm_forward(*args, _ptr(ws), _stream(dev)), "lmx_k_gfm_forward")
+    trunks = None
+    if trunk:  # graph g's [max(S, 1), N_g, D]
+        trunks = [tr[int(batch.node_off[i]) * smax:int(batch.node_off[i + 1]) * smax].reshape(smax, batch.sizes[i], D) for i in range(n)]
+    return pred, stats, npred, at, trunks, vv
+
+
+def gfm_forward(w, batch, seeds, n_samples, p, node=False, attn=False, trunk=False, vn=False):
+    """The whole graph transformer for n graphs and S samples in ONE launch behind the bias kernel (lmx_k_gfm_forward, csrc/gfm.hip):
+    batch a GfmBatch on the device, seeds: n 64-bit values on the host -> (pred f32 [n, max(S, 1)], stats f32 [n, 2], node_pred f32
+    [sum N] or None, attn_to_target f32 [sum N] or None (both S = 0 only), trunk: a list of [max(S, 1), N_g, D] views or None, vn f32
+    [n, max(S, 1), D] or None)."""
+    return _gfm_forward(False, w, batch, seeds, n_samples, p, node, attn, trunk, vn)
+
+
+def gfm_forward_host(w, batch, seeds, n_samples, p, node=False, attn=False, trunk=False, vn=False):
+    """lmx_h_gfm_forward: the same network in plain C++ on a CPU GfmBatch, with the same keep bits (no GPU)."""
+    return _gfm_forward(True, w, batch, seeds, n_samples, p, node, attn, trunk, vn)
+
+
 def pack_records(rec, n_rows=None, row_maps=(), field_map=None, n_valid=None, out=None):
     """dict of per-frame tensors [n_k, ...] on one device -> (uint8 [n_rows, stride], layout): lmx.dist.pack_records' bytes from ONE
     launch that stores every byte of the matrix once (csrc/records.hip); `out` (uint8 [n_rows, stride], contiguous) needs no clearing.

@@ -26,11 +26,11 @@ import numpy as np
 import torch
 
 from . import _lib, letterbox, resample
-from ._lib import DinoInfo, FusedInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, TcnInfo, XfmInfo, YoloInfo, check
+from ._lib import DinoInfo, FusedInfo, GfmInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, TcnInfo, XfmInfo, YoloInfo, check
 
 MAGIC = b"LMXIMAGE"
 VERSION = 1
-KIND_DINO, KIND_YOLO, KIND_SAM, KIND_TCN, KIND_XFM = 1, 2, 3, 4, 5
+KIND_DINO, KIND_YOLO, KIND_SAM, KIND_TCN, KIND_XFM, KIND_GFM = 1, 2, 3, 4, 5, 6
 HEADER_BYTES, ENTRY_BYTES, NAME_BYTES = 48, 88, 48
 ARCH = {"dinov2": 0, "dinov3": 1}
 RECIPE = {"pil": 0, "float": 1}
@@ -147,6 +147,27 @@ def check_xfm_image(path):
     """lmx_xfm_image_check_host: validate an image on the host (no GPU) -> XfmInfo; LmxError names the offending field."""
     info = XfmInfo()
     check(_lib.load().lmx_xfm_image_check_host(str(path).encode(), C.byref(info)), "lmx_xfm_image_check_host")
+    return info
+
+
+# ---- the graph transformer's weight image (csrc/gfm_image.h) -----------------------------------------------------------------------
+def gfm_config_block(cfg):
+    """8 int32 (input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd) then the dropout probability as one float64."""
+    return struct.pack("<8id", *cfg.shape(), cfg.dropout)
+
+
+def write_gfm_image(cfg, weights, path):
+    """Export a graph transformer (lmx.checkpoints.gfm_from_state_dict's configuration and weights) as the weight image
+    lmx_gfm_open_host reads: the tensors of lmx.gfm.pack_tensors under the names of lmx_gfm_weights_t's fields.  Returns the file's size."""
+    from . import gfm
+
+    return write_image(path, KIND_GFM, gfm_config_block(cfg.validate("write_gfm_image")), gfm.pack_tensors(cfg, weights))
+
+
+def check_gfm_image(path):
+    """lmx_gfm_image_check_host: validate an image on the host (no GPU) -> GfmInfo; LmxError names the offending field."""
+    info = GfmInfo()
+    check(_lib.load().lmx_gfm_image_check_host(str(path).encode(), C.byref(info)), "lmx_gfm_image_check_host")
     return info
 
 
@@ -979,3 +1000,51 @@ class NativeXfm(_NativeGait):
             check(self._lib.lmx_xfm_score_host(self._handle(), _vp(x), _vp(mask), _vp(sd), n, T, S, _vp(pred), _vp(stats), _vp(sal)),
                   "lmx_xfm_score_host")
         return stats[:, 0], stats[:, 1], pred, sal
+
+
+class NativeGfm(_NativeHandle):
+    """lmx_gfm_open_host(path, max_graphs, max_nodes_total, max_samples) on `device` (default: torch's current device): the graph
+    transformer from its weight image.  score / score_host give the bits of lmx.gfm.GfmScorer (tests/test_gpu_gfm.py)."""
+    _PREFIX, _INFO = "lmx_gfm_", GfmInfo
+
+    def __init__(self, path, max_graphs, max_nodes_total, max_samples=10, device=None):
+        self._extra = (int(max_nodes_total), int(max_samples))
+        super().__init__(path, max_graphs, device)
+
+    def _open_args(self, max_batch):
+        return (int(max_batch),) + self._extra
+
+    def _call(self, what, graphs, seeds, n_samples, targets, node):
+        from . import kernels as K
+
+        host = what == "score_host"
+        b = graphs if isinstance(graphs, K.GfmBatch) else K.GfmBatch(graphs, "cpu" if host else self.device, targets)
+        if b.device != (torch.device("cpu") if host else self.device):
+            raise LmxError(f"NativeGfm.{what}: the graphs are on {b.device}")
+        n, S = b.n, int(n_samples)
+        sd = None
+        if S:
+            sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
+            if sd.shape != (n,):
+                raise LmxError(f"NativeGfm.{what}: {n} graphs need {n} seeds, got {sd.shape}")
+        empty = lambda *shape: torch.empty(shape, dtype=torch.float32, device=b.device)  # noqa: E731
+        pred, stats = empty(n, max(S, 1)), empty(n, 2)
+        npred = empty(b.nodes) if node else None
+        attn = empty(b.nodes) if (b.target is not None and S == 0) else None
+        g = b.struct()
+        args = [self._handle(), C.byref(g), _vp(sd), S, _vp(pred), _vp(stats), _vp(npred), _vp(attn)]
+        with torch.cuda.device(self.device):
+            if host:
+                check(self._lib.lmx_gfm_score_host(*args), "lmx_gfm_score_host")
+            else:
+                check(self._lib.lmx_gfm_score(*args, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "lmx_gfm_score")
+        return stats[:, 0], stats[:, 1], pred, npred, attn
+
+    def score(self, graphs, seeds=None, n_samples=10, targets=None, node=False):
+        """graphs: lmx.gfm.build_graph's dicts (or a GfmBatch on the handle's device), n host seeds -> (mean [n], std [n], pred
+        [n, max(S, 1)], node_pred [sum N] or None, attn_to_target [sum N] or None: with targets, S = 0) on torch's current stream."""
+        return self._call("score", graphs, seeds, n_samples, targets, node)
+
+    def score_host(self, graphs, seeds=None, n_samples=10, targets=None, node=False):
+        """The same from and to HOST memory (CPU tensors): lmx_gfm_score_host uploads, scores, downloads, synchronises."""
+        return self._call("score_host", graphs, seeds, n_samples, targets, node)

@@ -12,4 +12,5 @@ from .curation import ClipCurator, CowTracker  # noqa: F401
 from .tracking import TrackingService  # noqa: F401
 from .preprocessing import VideoPreprocessor  # noqa: F401
 from .tcn_pipeline import TCNPipeline  # noqa: F401
+from .graph_transformer_pipeline import GraphTransformerPipeline  # noqa: F401
 from .transformer_pipeline import TransformerPipeline  # noqa: F401
