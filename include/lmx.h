@@ -1333,6 +1333,154 @@ int lmx_gfm_score(lmx_gfm* m, const lmx_gfm_graphs_t* graphs_host, const uint64_
 int lmx_gfm_score_host(lmx_gfm* m, const lmx_gfm_graphs_t* graphs_host, const uint64_t* seeds_host, int S, float* pred_host,
                        float* stats_host, float* node_pred_host, float* attn_to_target_host);
 
+/* ==== GraphGPS: node scores, their MC-dropout spread and a cow score per graph (csrc/gnn.hip, csrc/host_gnn.cpp) ======================
+ * Replaces EnhancedGraphGPS of services/gnn-pipeline/app/main.py: its predict_with_uncertainty (ten train-mode forwards, each of which
+ * rebuilds a sparse Laplacian, runs an eigensolver and 16 dense matrix powers on the host) and the eleventh eval-mode forward.  Here
+ * the graph and both raw encodings are prepared ONCE on the host (lmx_h_gnn_graph) and n graphs x S samples run in ONE launch, one
+ * workgroup per (graph, sample), the residual stream resident in LDS.
+ * ONLY THE LIVE NETWORK IS BUILT.  forward() returns pred_head(final_norm(h)) with h taken after pre_pool_layers (num_layers / 2 of
+ * them); pool_layer, post_pool_layers and multi_scale_readout feed scale_representations, which nothing reads, and the e_new of the
+ * last pre-pool layer (edge_update, bn_edge) feeds only that branch.  n_layers below counts the LIVE layers.
+ * The network (x [N][F]; D = d_model, P = pe_dim, H = n_heads, dh = D / H, L = n_layers, FF = ff; edges e = (src, dst), E of them):
+ *   h  = [ x W_in^T + b_in | LN_P( relu(|lap| L1^T) L2^T ) | LN_P( relu(rw R1^T) R2^T ) ]      D - 2P | P | P columns, biases as usual;
+ *        lap f32 [N][8] and rw f32 [N][16] are the RAW encodings of lmx_h_gnn_graph (the absolute value is taken there)
+ *   ea = LN_D( relu(attr W_e1^T + b_e1) W_e2^T + b_e2 )                     3 -> D/2 -> D, per edge; no dropout touches h or ea
+ *   layer l = 0 .. L-1:
+ *     a  = LN(h; norm1)                     eps 1e-5, biased variance, two passes, 1.0f / sqrtf everywhere
+ *     Ax | Bx | Dx | Ex = a [A;B;D;E]^T + b
+ *     Ce = ea C^T + c;  sigma = 1 / (1 + expf(-((Ce + Dx[dst]) + Ex[src])));  message = sigma * Bx[src]
+ *     agg[i] = ( sum of the messages of the edges INTO i, IN EDGE ORDER, one running f32 sum ) / max(indeg_i, 1)
+ *     l < L-1 only:  ea = BN_edge( relu( [Dx[dst] | Ex[src] | Ce] U1^T + u1 ) U2^T + u2 )
+ *     h  = h + drop_{5l}( relu( BN_node( Ax + agg ) ) )
+ *     a  = LN(h; norm2);  q | k | v = a Wqkv^T + b        nn.MultiheadAttention's in_proj rows: q, then k, then v; head i = channels
+ *                                                          i dh .. (i+1) dh - 1 of each
+ *     P  = drop_{5l+1}( softmax_u( (q_i[t] . k_i[u]) * c ) )     c = float(dh^-0.5); max-subtracted, ONE DIVISION PER ELEMENT
+ *     g  = LN( a + drop_{5l+2}( concat_i(P_i v_i) Wo^T + bo ); global_attn.norm );   h = h + (g - a)
+ *     a  = LN(h; norm3);  h = h + drop_{5l+4}( drop_{5l+3}( gelu(a W1^T + b1) ) W2^T + b2 )        gelu exact (erff)
+ *   t  = LN(h; final_norm)
+ *   node_pred[i] = 1 / (1 + expf(-( N2 drop_{5L}( relu(N1 t[i] + n1) ) + n2 )))                    D -> D/2 -> 1
+ *   eval mode only: w = softmax over the nodes of ( tanhf(t A1^T + a1) A2^T + a2 ) (max-subtracted, e_i / sum) = attention_weights;
+ *   graph_pred = 1 / (1 + expf(-( K3 relu( K2 relu( K1 [ mean_i t[i] | sum_i w_i t[i] ] + k1 ) + k2 ) + k3 )))   2D -> D -> D/2 -> 1;
+ *   the sums over the nodes in ascending order.  The classifier's two dropout sites are never drawn: graph_pred is read in eval mode.
+ * BatchNorm (eps 1e-5).  S > 0 is predict_with_uncertainty, which calls train(): bn_node normalises with the mean and BIASED variance
+ * over the graph's N nodes, bn_edge over its E edges (two passes).  S = 0 normalises with the checkpoint's running_mean / running_var.
+ * The reference's running statistics drift with every video it scores (momentum 0.1); that drift is NOT reproduced: a graph scores
+ * to the same bytes whatever was scored before.  A graph of one node has no batch statistics: N < 2 (and, with L > 1, E < 2) is
+ * refused with S > 0, as torch raises and the reference writes no result.
+ * MC dropout: the keep decision of the TCN section (same mix, thr, scale), stream = sample * n_sites + site, n_sites = 5 L + 1, seeded
+ * per graph.  Element numbers u (i, j count nodes from 0):
+ *   site 5l (message passing), 5l+2 (out_proj), 5l+4 (FFN output)   u = i * D + c
+ *   site 5l+1 (attention probabilities)                             u = (head * N + i) * N + j
+ *   site 5l+3 (FFN hidden)                                          u = i * FF + j
+ *   site 5L (node head)                                             u = i * (D / 2) + j
+ * No floating-point atomics anywhere: every sum has a fixed order, so a graph gives the same bytes on every run, at every batch
+ * position and for every S (sample s depends on (seed, s) only).
+ *
+ * lmx_h_gnn_graph prepares a graph on the HOST from f32 embeddings [N][E], optional f64 timestamps [N] (the reference keeps them as
+ * Python floats) and k (GraphBuilder):
+ *   kNN edges first: cosine similarity in DOUBLE (each row divided by its norm + 1e-8, products added in ascending channel order);
+ *   k = max(1, N - 1) where N <= k; the neighbours of i are the k most similar j != i, edges i -> j in ASCENDING similarity, EXACT
+ *   TIES TO THE LOWER INDEX FIRST; weight = the RAW cosine rounded to f32 (not clamped); attributes (weight, 1, 0).  N = 1: no edge.
+ *   Temporal edges then, only with timestamps (a known cow) and N > 1: nodes in ascending timestamp, STABLE in index; consecutive a, b
+ *   give a -> b then b -> a with weight tanh(|t_b - t_a| / 86400) in double, rounded to f32; (weight, 0, 1).
+ *   Multi-edges stay multi-edges.  csr_ptr i32 [N + 1], csr_edge i32 [E]: the edges by DESTINATION, those of one destination in edge
+ *   order.  deg i32 [N]: the in-degree, clamped to at least 1.
+ *   RWPE: A counts multiplicities and carries one self-loop per node; P = D^-1 A in double (row sums); rw[i][k-1] = (P^k)[i][i] for
+ *   k = 1 .. 16, every inner product summed in ascending index order, then rounded to f32.
+ *   LapPE: the same A; deg its row sums; L = I - D^-1/2 A D^-1/2 in double (A is NOT symmetric: kNN edges are directed), then L IS
+ *   SYMMETRISED FROM ITS LOWER TRIANGLE (what numpy's eigh reads); a cyclic Jacobi eigendecomposition in double runs until the
+ *   off-diagonal Frobenius norm is <= 1e-14 times the matrix's (at most 64 sweeps); eigenvalues ascending, TIES BY THE LOWER ORIGINAL
+ *   COLUMN; lap = |columns 1 .. 8|, zero columns where N <= 8, rounded to f32.  This equals the reference's np.linalg.eigh branch
+ *   (N <= 9) wherever the spectrum is simple.  For N > 9 the reference runs eigsh(which='SM', tol=1e-3) from a random start vector on
+ *   the non-symmetric matrix: parity there is unpinned and unattainable.
+ *   Unpinned against numpy, as for the graph transformer: the BLAS order of its similarity matrix and tanh in the last place.
+ * edges_host holds N * min(max(k, 1), N - 1) + 2 (N - 1) pairs at most.  LMX_GNN_MAX_NODES = 95 and E <= LMX_GNN_MAX_EDGES =
+ * 5 * 95 + 2 * 94 = 663 per graph, the graph transformer's cows.  LDS at the limit: three tiles of 96 rows x 132 floats (residual
+ * stream, LayerNorm output / aggregation, work tile) and 1,664 floats of vectors are 158,720 of 163,840 bytes.
+ *
+ * lmx_gnn_graphs_t: n graphs concatenated in graph order; node_off_host / edge_off_host i32 [n + 1] on the HOST, ascending from 0;
+ *   x f32 [sum N][input_dim]; lap f32 [sum N][8]; rw f32 [sum N][16]; edge_src, edge_dst i32 [sum E] (nodes counted within the graph);
+ *   edge_attr f32 [sum E][3]; csr_ptr i32 [sum N + n] (graph g's N_g + 1 entries start at node_off[g] + g); csr_edge i32 [sum E] (edges
+ *   counted within the graph); deg i32 [sum N].  DEVICE pointers for lmx_k_gnn_forward, HOST pointers for lmx_h_gnn_forward.  The
+ *   device forward clamps every index it reads into its graph; the host forward refuses an index outside.
+ * lmx_gnn_weights_t: "packed" and "transposed" as for the graph transformer.
+ *   in_w packed [F -> D - 2P], in_b; lap1_w plain [2P][8], lap1_b, lap2_w plain [P][2P], lap2_b, lap_g, lap_beta [P]; rw1_w plain
+ *   [2P][16], rw1_b, rw2_w, rw2_b, rw_g, rw_beta likewise; ee1_w plain [D/2][3], ee1_b, ee2_w packed [D/2 -> D], ee2_b, ee_g, ee_beta
+ *   per layer: ln1_g, ln1_b; abde_w packed [D -> 4D] (rows A | B | D | E), abde_b [4D]; c_w packed [D -> D], c_b; eu1_w packed
+ *   [3D -> D], eu1_b, eu2_w packed [D -> D], eu2_b, bne_g, bne_b, bne_mean, bne_var (these eight NULL in the last layer); bnn_g, bnn_b,
+ *   bnn_mean, bnn_var; ln2_g, ln2_b; qkv_w: H packed layers [D -> 3 dh] (rows q_i | k_i | v_i), qkv_b [H][3 dh]; out_w packed, out_b;
+ *   lna_g, lna_b (global_attn.norm); ln3_g, ln3_b; ff1_w packed [D -> FF], ff1_b; ff2_w packed [FF -> D], ff2_b
+ *   lnf_g, lnf_b; nh1_w packed [D -> D/2], nh1_b, nh2_w [D/2], nh2_b [1]; na1_w packed [D -> D/2], na1_b, na2_w [D/2], na2_b [1];
+ *   cl1_w transposed [2D][D], cl1_b; cl2_w transposed [D][D/2], cl2_b; cl3_w [D/2], cl3_b [1]
+ * Accepted: d_model a multiple of 32 up to 128; d_model / n_heads 16 or 32; pe_dim a multiple of 8 with 2 pe_dim < d_model; n_layers
+ * 1 .. 4; ff a multiple of 16 up to 512; input_dim 1 .. 64; edge_dim 3; N 1 .. LMX_GNN_MAX_NODES and E 0 .. LMX_GNN_MAX_EDGES per
+ * graph; S = 0 or 2 .. 65535; p in [0, 1).
+ * lmx_k_gnn_forward: `workspace`: lmx_gnn_workspace_bytes(n, S, max N, max E, D, L) bytes on the device, 16-byte aligned: the seeds,
+ * the offsets, and one slice per workgroup for Bx | Dx | Ex [N][3D] and, with L > 1, the first layers' ea [E][D] (written once, read
+ * once; its batch statistics in a pass of their own): n x max(S, 1) x (max N x 3D + max E x D) x 4 bytes, 485,376 bytes per
+ * (graph, sample) for the shipped network at the limits, 310 MB for 64 such graphs x 10 samples.  S > 0: node_mc f32 [sum N][S] and stats f32 [sum N][2] (mean, unbiased std).
+ * S = 0: graph_pred f32 [n], node_pred f32 [sum N], attn_weights f32 [sum N].  The outputs of the other mode must be NULL.  trunk
+ * (NULL allowed, for tests): t of graph g as [max(S,1)][N_g][D] starting at node_off[g] * max(S,1) * D.  n = 0 launches nothing.
+ * lmx_h_gnn_forward is the same network in plain C++ on HOST pointers with the same keep bits: f32, sequential sums. */
+#define LMX_GNN_MAX_LAYERS 4
+#define LMX_GNN_MAX_NODES 95
+#define LMX_GNN_MAX_EDGES 663
+#define LMX_GNN_LAP_K 8
+#define LMX_GNN_RW_K 16
+typedef struct { int32_t input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim, reserved;
+                 const float *in_w, *in_b, *lap1_w, *lap1_b, *lap2_w, *lap2_b, *lap_g, *lap_beta, *rw1_w, *rw1_b, *rw2_w, *rw2_b, *rw_g, *rw_beta;
+                 const float *ee1_w, *ee1_b, *ee2_w, *ee2_b, *ee_g, *ee_beta;
+                 const float *ln1_g[LMX_GNN_MAX_LAYERS], *ln1_b[LMX_GNN_MAX_LAYERS], *abde_w[LMX_GNN_MAX_LAYERS], *abde_b[LMX_GNN_MAX_LAYERS];
+                 const float *c_w[LMX_GNN_MAX_LAYERS], *c_b[LMX_GNN_MAX_LAYERS], *eu1_w[LMX_GNN_MAX_LAYERS], *eu1_b[LMX_GNN_MAX_LAYERS];
+                 const float *eu2_w[LMX_GNN_MAX_LAYERS], *eu2_b[LMX_GNN_MAX_LAYERS], *bne_g[LMX_GNN_MAX_LAYERS], *bne_b[LMX_GNN_MAX_LAYERS];
+                 const float *bne_mean[LMX_GNN_MAX_LAYERS], *bne_var[LMX_GNN_MAX_LAYERS], *bnn_g[LMX_GNN_MAX_LAYERS], *bnn_b[LMX_GNN_MAX_LAYERS];
+                 const float *bnn_mean[LMX_GNN_MAX_LAYERS], *bnn_var[LMX_GNN_MAX_LAYERS], *ln2_g[LMX_GNN_MAX_LAYERS], *ln2_b[LMX_GNN_MAX_LAYERS];
+                 const float *qkv_w[LMX_GNN_MAX_LAYERS], *qkv_b[LMX_GNN_MAX_LAYERS], *out_w[LMX_GNN_MAX_LAYERS], *out_b[LMX_GNN_MAX_LAYERS];
+                 const float *lna_g[LMX_GNN_MAX_LAYERS], *lna_b[LMX_GNN_MAX_LAYERS], *ln3_g[LMX_GNN_MAX_LAYERS], *ln3_b[LMX_GNN_MAX_LAYERS];
+                 const float *ff1_w[LMX_GNN_MAX_LAYERS], *ff1_b[LMX_GNN_MAX_LAYERS], *ff2_w[LMX_GNN_MAX_LAYERS], *ff2_b[LMX_GNN_MAX_LAYERS];
+                 const float *lnf_g, *lnf_b, *nh1_w, *nh1_b, *nh2_w, *nh2_b, *na1_w, *na1_b, *na2_w, *na2_b;
+                 const float *cl1_w, *cl1_b, *cl2_w, *cl2_b, *cl3_w, *cl3_b; } lmx_gnn_weights_t;
+typedef struct { int32_t n, reserved; const int32_t *node_off_host, *edge_off_host; const float *x, *lap, *rw; const int32_t *edge_src, *edge_dst;
+                 const float* edge_attr; const int32_t *csr_ptr, *csr_edge, *deg; } lmx_gnn_graphs_t;
+int lmx_h_gnn_graph(const float* emb_host /* [N][E] */, const double* timestamps_host /* NULL or [N] */, int N, int E, int k,
+                    int32_t* edges_host /* [cap][2] */, float* edge_attr_host /* [cap][3] */, int32_t* n_edges_host,
+                    int32_t* csr_ptr_host /* [N + 1] */, int32_t* csr_edge_host /* [cap] */, int32_t* deg_host /* [N] */,
+                    float* lap_host /* [N][8] */, float* rw_host /* [N][16] */);
+/* the eigendecomposition behind lap, in double: eigenvalues ascending (ties by the lower original column), column c of eigenvectors
+ * [N][N] belongs to eigenvalue c; lap[i][c] = (float)|eigenvectors[i][c + 1]| */
+int lmx_h_gnn_laplacian(const int32_t* edges_host /* [E][2] */, int n_edges, int N, double* eigenvalues_host /* [N] */,
+                        double* eigenvectors_host /* [N][N] */);
+int64_t lmx_gnn_workspace_bytes(int n, int S, int max_nodes, int max_edges, int d_model, int n_layers);
+int lmx_k_gnn_forward(const lmx_gnn_weights_t* w_host, const lmx_gnn_graphs_t* graphs_host, const uint64_t* seeds_host /* [n] */, int S,
+                      double p, float* node_mc /* [sum N][S], S > 0 */, float* stats /* [sum N][2], S > 0 */, float* graph_pred /* [n], S == 0 */,
+                      float* node_pred /* [sum N], S == 0 */, float* attn_weights /* [sum N], S == 0 */,
+                      float* trunk /* NULL or [sum N][max(S,1)][D] */, void* workspace, lmx_stream_t stream);
+int lmx_h_gnn_forward(const lmx_gnn_weights_t* w_host, const lmx_gnn_graphs_t* graphs_host, const uint64_t* seeds_host, int S, double p,
+                      float* node_mc_host, float* stats_host, float* graph_pred_host, float* node_pred_host, float* attn_weights_host,
+                      float* trunk_host);
+
+/* ==== MODEL level: GraphGPS scores from prepared graphs (csrc/gait_model.hip, csrc/gnn_image.h, csrc/host_gnn_image.cpp) ================
+ * services/gnn-pipeline/app/main.py's model behind a handle: the weights come from a WEIGHT IMAGE (kind 7) that
+ * lmx.native.write_gnn_image writes (csrc/gnn_image.h has the config block and the tensors; the last live layer's edge update is not in
+ * it); handle rules as for lmx_tcn.  The handle owns the workspace: lmx_gnn_workspace_bytes(max_graphs, max_samples, min(95,
+ * max_nodes_total), min(663, max_edges_total), D, L), i.e. up to 485,376 bytes per (graph, sample) for the shipped network — 310 MB for
+ * 64 graphs x 10 samples; open with the limits the caller will really use.  lmx_gnn_score: the graphs as for lmx_k_gnn_forward (DEVICE
+ * arrays, the two offset arrays on the host), seeds_host on the host -> with S > 0 node_mc and stats, with S == 0 graph_pred, node_pred
+ * and attn_weights, on the device (the outputs of the other mode NULL): lmx_k_gnn_forward with the image's dropout probability; it only
+ * enqueues on `stream`.  n <= max_graphs, sum N <= max_nodes_total, sum E <= max_edges_total, S <= max_samples.  lmx_gnn_score_host takes
+ * the graphs' arrays and returns the outputs in HOST memory, and synchronises (examples/gnn_score.c). */
+typedef struct lmx_gnn lmx_gnn;
+typedef struct { int32_t input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim, max_nodes, max_edges, max_graphs, max_nodes_total,
+                 max_edges_total, max_samples, reserved; double p; } lmx_gnn_info_t;
+int lmx_gnn_image_check_host(const char* path_host, lmx_gnn_info_t* info_host);
+int lmx_gnn_open_host(const char* path_host, int max_graphs, int max_nodes_total, int max_edges_total, int max_samples, lmx_gnn** out_host);
+void lmx_gnn_close(lmx_gnn* m);
+int lmx_gnn_info(const lmx_gnn* m, lmx_gnn_info_t* info_host);
+int lmx_gnn_score(lmx_gnn* m, const lmx_gnn_graphs_t* graphs_host, const uint64_t* seeds_host, int S, float* node_mc, float* stats,
+                  float* graph_pred, float* node_pred, float* attn_weights, lmx_stream_t stream);
+int lmx_gnn_score_host(lmx_gnn* m, const lmx_gnn_graphs_t* graphs_host, const uint64_t* seeds_host, int S, float* node_mc_host,
+                       float* stats_host, float* graph_pred_host, float* node_pred_host, float* attn_weights_host);
+
 #ifdef __cplusplus
 }
 #endif

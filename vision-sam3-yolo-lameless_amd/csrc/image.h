@@ -20,7 +20,7 @@
 #include "../../include/lmx.h"
 
 #define LMX_IMAGE_VERSION 1u
-enum { LMX_IMAGE_DINO = 1, LMX_IMAGE_YOLO = 2, LMX_IMAGE_SAM = 3, LMX_IMAGE_TCN = 4, LMX_IMAGE_XFM = 5, LMX_IMAGE_GFM = 6 };  // kinds
+enum { LMX_IMAGE_DINO = 1, LMX_IMAGE_YOLO = 2, LMX_IMAGE_SAM = 3, LMX_IMAGE_TCN = 4, LMX_IMAGE_XFM = 5, LMX_IMAGE_GFM = 6, LMX_IMAGE_GNN = 7 };  // kinds
 enum { LMX_IMG_F16 = 0, LMX_IMG_F32 = 1, LMX_IMG_I32 = 2 };          // directory dtypes (F16 / F32 as LMX_F16 / LMX_F32)
 enum { LMX_IMAGE_HEADER_BYTES = 48, LMX_IMAGE_ENTRY_BYTES = 88, LMX_IMAGE_NAME_BYTES = 48, LMX_IMAGE_MAX_CONFIG_BYTES = 1 << 20 };
 

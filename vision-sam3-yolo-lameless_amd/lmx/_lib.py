@@ -130,6 +130,29 @@ class GfmInfo(C.Structure):  # lmx_gfm_info_t
                                          "max_graphs", "max_nodes_total", "max_samples")] + [("p", C.c_double)]
 
 
+class GnnWeights(C.Structure):  # lmx_gnn_weights_t: device pointers for lmx_k_gnn_forward, host pointers for lmx_h_gnn_forward
+    MAX_LAYERS = 4
+    HEAD_FIELDS = ("in_w", "in_b", "lap1_w", "lap1_b", "lap2_w", "lap2_b", "lap_g", "lap_beta", "rw1_w", "rw1_b", "rw2_w", "rw2_b", "rw_g", "rw_beta",
+                   "ee1_w", "ee1_b", "ee2_w", "ee2_b", "ee_g", "ee_beta")
+    LAYER_FIELDS = ("ln1_g", "ln1_b", "abde_w", "abde_b", "c_w", "c_b", "eu1_w", "eu1_b", "eu2_w", "eu2_b", "bne_g", "bne_b", "bne_mean", "bne_var",
+                    "bnn_g", "bnn_b", "bnn_mean", "bnn_var", "ln2_g", "ln2_b", "qkv_w", "qkv_b", "out_w", "out_b", "lna_g", "lna_b", "ln3_g", "ln3_b",
+                    "ff1_w", "ff1_b", "ff2_w", "ff2_b")
+    TAIL_FIELDS = ("lnf_g", "lnf_b", "nh1_w", "nh1_b", "nh2_w", "nh2_b", "na1_w", "na1_b", "na2_w", "na2_b", "cl1_w", "cl1_b", "cl2_w", "cl2_b",
+                   "cl3_w", "cl3_b")
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "n_layers", "pe_dim", "ff", "edge_dim", "reserved")] + [
+        (n, C.c_void_p) for n in HEAD_FIELDS] + [(n, C.c_void_p * 4) for n in LAYER_FIELDS] + [(n, C.c_void_p) for n in TAIL_FIELDS]
+
+
+class GnnGraphs(C.Structure):  # lmx_gnn_graphs_t: the two offset arrays on the host, the rest where the forward runs
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "node_off_host", "edge_off_host", "x", "lap", "rw", "edge_src", "edge_dst", "edge_attr", "csr_ptr", "csr_edge", "deg")]
+
+
+class GnnInfo(C.Structure):  # lmx_gnn_info_t
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "n_layers", "pe_dim", "ff", "edge_dim", "max_nodes", "max_edges",
+                                         "max_graphs", "max_nodes_total", "max_edges_total", "max_samples", "reserved")] + [("p", C.c_double)]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -303,6 +326,17 @@ SIGNATURES = {
     "lmx_gfm_info": (_I, [_VP, C.POINTER(GfmInfo)]),
     "lmx_gfm_score": (_I, [_VP, C.POINTER(GfmGraphs), _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "lmx_gfm_score_host": (_I, [_VP, C.POINTER(GfmGraphs), _VP, _I, _VP, _VP, _VP, _VP]),
+    "lmx_h_gnn_graph": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_h_gnn_laplacian": (_I, [_VP, _I, _I, _VP, _VP]),
+    "lmx_gnn_workspace_bytes": (_I64, [_I, _I, _I, _I, _I, _I]),
+    "lmx_k_gnn_forward": (_I, [C.POINTER(GnnWeights), C.POINTER(GnnGraphs), _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_h_gnn_forward": (_I, [C.POINTER(GnnWeights), C.POINTER(GnnGraphs), _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_gnn_image_check_host": (_I, [C.c_char_p, C.POINTER(GnnInfo)]),
+    "lmx_gnn_open_host": (_I, [C.c_char_p, _I, _I, _I, _I, C.POINTER(_VP)]),
+    "lmx_gnn_close": (None, [_VP]),
+    "lmx_gnn_info": (_I, [_VP, C.POINTER(GnnInfo)]),
+    "lmx_gnn_score": (_I, [_VP, C.POINTER(GnnGraphs), _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_gnn_score_host": (_I, [_VP, C.POINTER(GnnGraphs), _VP, _I, _VP, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

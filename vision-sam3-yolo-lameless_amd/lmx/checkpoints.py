@@ -557,3 +557,75 @@ def gfm_from_state_dict(sd, num_heads=8, dropout=0.1):
                         dropout=float(dropout)).validate("gfm_from_state_dict")
     gfm.pack_tensors(cfg, w)  # every shape against the configuration
     return cfg, w
+
+
+# EnhancedGraphGPS (services/gnn-pipeline/app/main.py): the reference's module paths and the names lmx.gnn.pack_tensors reads
+GNN_KEYS = (("input_proj", "in"), ("lap_pe.transform.0", "lap1"), ("lap_pe.transform.2", "lap2"), ("lap_pe.transform.3", "lap_norm"),
+            ("rw_pe.transform.0", "rw1"), ("rw_pe.transform.2", "rw2"), ("rw_pe.transform.3", "rw_norm"), ("edge_encoder.encoder.0", "ee1"),
+            ("edge_encoder.encoder.2", "ee2"), ("edge_encoder.encoder.3", "ee_norm"), ("final_norm", "lnf"),
+            ("pred_head.node_classifier.0", "nh1"), ("pred_head.node_classifier.3", "nh2"), ("pred_head.node_attention.0", "na1"),
+            ("pred_head.node_attention.2", "na2"), ("pred_head.classifier.0", "cl1"), ("pred_head.classifier.3", "cl2"),
+            ("pred_head.classifier.6", "cl3"))
+GNN_LAYER_KEYS = (("norm1", "ln1"), ("local_conv.A", "A"), ("local_conv.B", "B"), ("local_conv.D", "D"), ("local_conv.E", "E"),
+                  ("local_conv.C", "C"), ("norm2", "ln2"), ("global_attn.attention.out_proj", "out"), ("global_attn.norm", "lna"),
+                  ("norm3", "ln3"), ("ffn.0", "ff1"), ("ffn.3", "ff2"))
+GNN_EDGE_KEYS = (("local_conv.edge_update.0", "eu1"), ("local_conv.edge_update.2", "eu2"))
+# what never reaches an output of forward(): dropped BY PREFIX, whatever lies below (SAGPooling's inner names are torch_geometric's)
+GNN_DEAD_PREFIXES = ("pool_layer.", "post_pool_layers.", "multi_scale_readout.")
+
+
+def gnn_from_state_dict(sd, num_heads=8, dropout=0.1):
+    """An EnhancedGraphGPS state_dict under the reference's key names -> (lmx.gnn.GnnConfig, weights) of the LIVE network: input_proj,
+    edge_encoder, the transform MLPs of lap_pe / rw_pe, pre_pool_layers (the last one without its edge update), final_norm, pred_head.
+    pool_layer.*, post_pool_layers.*, multi_scale_readout.*, the last live layer's local_conv.edge_update.* / local_conv.bn_edge.* and
+    every global_attn.pe_bias.* (a parameter forward never applies) are accepted and dropped by prefix; num_batches_tracked likewise.
+    Any other key that is not read is refused by name, and so is the legacy GraphGPS class.  The shape is inferred from the tensors;
+    the number of heads and the dropout probability are not in a state_dict.  BatchNorm's running statistics must be there: the eval
+    launch normalises with them."""
+    from . import gnn
+    from ._lib import LmxError
+
+    who = "gnn_from_state_dict"
+    if any(k.startswith("layers.") for k in sd) or "pred_head.0.weight" in sd:
+        raise LmxError(f"{who}: a GraphGPS state_dict (layers.*, pred_head.0): the legacy class is not served, only EnhancedGraphGPS")
+    n_layers = 0
+    while any(k.startswith(f"pre_pool_layers.{n_layers}.") for k in sd):
+        n_layers += 1
+    if n_layers == 0 or "input_proj.weight" not in sd:
+        raise LmxError(f"{who}: no input_proj.weight or pre_pool_layers.0.* keys: not an EnhancedGraphGPS state_dict")
+    used = set()
+
+    def plain(key):
+        if key not in sd:
+            raise LmxError(f"{who}: {key} is missing")
+        used.add(key)
+        return sd[key].detach().float().cpu().contiguous()
+
+    w = {}
+    for theirs, ours in GNN_KEYS:
+        w[f"{ours}.weight"], w[f"{ours}.bias"] = plain(f"{theirs}.weight"), plain(f"{theirs}.bias")
+    for i in range(n_layers):
+        p, q = f"pre_pool_layers.{i}.", f"layer.{i}."
+        for theirs, ours in GNN_LAYER_KEYS + (GNN_EDGE_KEYS if i < n_layers - 1 else ()):
+            w[f"{q}{ours}.weight"], w[f"{q}{ours}.bias"] = plain(f"{p}{theirs}.weight"), plain(f"{p}{theirs}.bias")
+        for theirs, ours in (("local_conv.bn_node", "bnn"),) + ((("local_conv.bn_edge", "bne"),) if i < n_layers - 1 else ()):
+            for field in ("weight", "bias", "running_mean", "running_var"):
+                w[f"{q}{ours}.{field}"] = plain(f"{p}{theirs}.{field}")
+        w[q + "in_proj.weight"], w[q + "in_proj.bias"] = plain(p + "global_attn.attention.in_proj_weight"), plain(p + "global_attn.attention.in_proj_bias")
+    last = f"pre_pool_layers.{n_layers - 1}.local_conv."
+    dead = GNN_DEAD_PREFIXES + (last + "edge_update.", last + "bn_edge.")
+    for k in sd:
+        if k in used or k.startswith(dead) or ".global_attn.pe_bias." in k or k.endswith(".num_batches_tracked"):
+            continue
+        raise LmxError(f"{who}: {k} is neither read nor one of the keys that reach no output")
+    for name in ("in.weight", "lap1.weight", "layer.0.ff1.weight", "ee1.weight", "cl3.weight", "nh2.weight"):
+        if w[name].dim() != 2:
+            raise LmxError(f"{who}: {name} is not a matrix")
+    if w["cl3.weight"].shape[0] != 1 or w["nh2.weight"].shape[0] != 1:
+        raise LmxError(f"{who}: {w['cl3.weight'].shape[0]} outputs of the graph head, {w['nh2.weight'].shape[0]} of the node head: one is supported")
+    pe_dim = int(w["lap2.weight"].shape[0])
+    cfg = gnn.GnnConfig(input_dim=int(w["in.weight"].shape[1]), d_model=int(w["in.weight"].shape[0]) + 2 * pe_dim, n_heads=int(num_heads),
+                        n_layers=n_layers, pe_dim=pe_dim, ff=int(w["layer.0.ff1.weight"].shape[0]), edge_dim=int(w["ee1.weight"].shape[1]),
+                        dropout=float(dropout)).validate(who)
+    gnn.pack_tensors(cfg, w)  # every shape against the configuration
+    return cfg, w

@@ -989,6 +989,239 @@ def gfm_forward_host(w, batch, seeds, n_samples, p, node=False, attn=False, trun
     return _gfm_forward(True, w, batch, seeds, n_samples, p, node, attn, trunk, vn)
 
 
+# ---- GraphGPS (include/lmx.h "GraphGPS"; csrc/gnn.hip, csrc/host_gnn.cpp) ---------------------------------------------------------------
+GNN_MAX_NODES = 95
+GNN_MAX_EDGES = 663
+GNN_MAX_LAYERS = 4
+GNN_LAP_K = 8
+GNN_RW_K = 16
+
+
+def gnn_check_config(who, input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim):
+    """The list of include/lmx.h, refused as the library refuses it: LmxError names the field."""
+    if not 1 <= input_dim <= 64:
+        raise LmxError(f"{who}: input_dim {input_dim} outside 1 .. 64")
+    if d_model % 32 or not 32 <= d_model <= 128:
+        raise LmxError(f"{who}: d_model {d_model} is not a multiple of 32 up to 128")
+    if n_heads < 1 or d_model % n_heads or d_model // n_heads not in (16, 32):
+        raise LmxError(f"{who}: n_heads {n_heads} gives d_model {d_model} a head_dim that is neither 16 nor 32")
+    if not 1 <= n_layers <= GNN_MAX_LAYERS:
+        raise LmxError(f"{who}: n_layers {n_layers} outside 1 .. {GNN_MAX_LAYERS} live layers")
+    if pe_dim < 8 or pe_dim % 8 or 2 * pe_dim >= d_model:
+        raise LmxError(f"{who}: pe_dim {pe_dim} is not a multiple of 8 with 2 pe_dim < d_model {d_model}")
+    if ff % 16 or not 16 <= ff <= 512:
+        raise LmxError(f"{who}: ff {ff} is not a multiple of 16 up to 512")
+    if edge_dim != 3:
+        raise LmxError(f"{who}: edge_dim {edge_dim} is not 3")
+
+
+def gnn_tensor_shapes(input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim):
+    """Ordered {tensor name: shape} of one network: the fields of lmx_gnn_weights_t (`layer.{l}.<field>` for the per-layer ones; the
+    last layer has no edge update), the names of lmx.gnn.pack_tensors."""
+    D, qd, dh, H, P = d_model, d_model // 16, d_model // n_heads, n_heads, pe_dim
+    out = {"in_w": ((input_dim + 15) // 16, (D - 2 * P) // 16, 64, 4), "in_b": (D - 2 * P,)}
+    for enc, k in (("lap", GNN_LAP_K), ("rw", GNN_RW_K)):
+        out.update({f"{enc}1_w": (2 * P, k), f"{enc}1_b": (2 * P,), f"{enc}2_w": (P, 2 * P), f"{enc}2_b": (P,), f"{enc}_g": (P,), f"{enc}_beta": (P,)})
+    out.update({"ee1_w": (D // 2, 3), "ee1_b": (D // 2,), "ee2_w": (D // 32, qd, 64, 4), "ee2_b": (D,), "ee_g": (D,), "ee_beta": (D,)})
+    for l in range(n_layers):
+        p = f"layer.{l}."
+        out.update({p + "ln1_g": (D,), p + "ln1_b": (D,), p + "abde_w": (qd, 4 * qd, 64, 4), p + "abde_b": (4 * D,), p + "c_w": (qd, qd, 64, 4),
+                    p + "c_b": (D,)})
+        if l < n_layers - 1:
+            out.update({p + "eu1_w": (3 * qd, qd, 64, 4), p + "eu1_b": (D,), p + "eu2_w": (qd, qd, 64, 4), p + "eu2_b": (D,), p + "bne_g": (D,),
+                        p + "bne_b": (D,), p + "bne_mean": (D,), p + "bne_var": (D,)})
+        out.update({p + "bnn_g": (D,), p + "bnn_b": (D,), p + "bnn_mean": (D,), p + "bnn_var": (D,), p + "ln2_g": (D,), p + "ln2_b": (D,),
+                    p + "qkv_w": (H * qd, 3 * dh // 16, 64, 4), p + "qkv_b": (H, 3 * dh), p + "out_w": (qd, qd, 64, 4), p + "out_b": (D,),
+                    p + "lna_g": (D,), p + "lna_b": (D,), p + "ln3_g": (D,), p + "ln3_b": (D,), p + "ff1_w": (qd, ff // 16, 64, 4), p + "ff1_b": (ff,),
+                    p + "ff2_w": (ff // 16, qd, 64, 4), p + "ff2_b": (D,)})
+    out.update({"lnf_g": (D,), "lnf_b": (D,), "nh1_w": (qd, D // 32, 64, 4), "nh1_b": (D // 2,), "nh2_w": (D // 2,), "nh2_b": (1,),
+                "na1_w": (qd, D // 32, 64, 4), "na1_b": (D // 2,), "na2_w": (D // 2,), "na2_b": (1,), "cl1_w": (2 * D, D), "cl1_b": (D,),
+                "cl2_w": (D, D // 2), "cl2_b": (D // 2,), "cl3_w": (D // 2,), "cl3_b": (1,)})
+    return out
+
+
+def gnn_weights(input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim, tensors):
+    """lmx_gnn_weights_t over the f32 tensors of lmx.gnn.pack_tensors (all on one GPU for gnn_forward, all on the CPU for
+    gnn_forward_host).  The struct keeps the tensors alive."""
+    shape = (input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim)
+    gnn_check_config("gnn_weights", *shape)
+    devs = {t.device for t in tensors.values()}
+    if len(devs) != 1:
+        raise LmxError(f"gnn_weights: tensors on different devices ({sorted(map(str, devs))})")
+    w = _lib.GnnWeights()
+    w.input_dim, w.d_model, w.n_heads, w.n_layers, w.pe_dim, w.ff, w.edge_dim = shape
+    for name, shp in gnn_tensor_shapes(*shape).items():
+        t = tensors.get(name)
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous():
+            raise LmxError(f"gnn_weights: {name} must be a contiguous float32 tensor of shape {shp}, got "
+                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
+        parts = name.split(".")
+        if parts[0] == "layer":
+            getattr(w, parts[2])[int(parts[1])] = t.data_ptr()
+        else:
+            setattr(w, name, t.data_ptr())
+    w._tensors, w._device = dict(tensors), devs.pop()
+    return w
+
+
+def gnn_graph(embeddings, timestamps, k):
+    """lmx_h_gnn_graph: f32 embeddings [N, E], None or f64 timestamps [N] (numpy) -> dict of numpy arrays: edges int32 [E, 2] (src, dst),
+    edge_attr f32 [E, 3], csr_ptr int32 [N + 1], csr_edge int32 [E], deg int32 [N], lap f32 [N, 8], rw f32 [N, 16] (host arithmetic)."""
+    import numpy as np
+
+    emb = np.ascontiguousarray(embeddings, np.float32)
+    if emb.ndim != 2 or emb.shape[0] < 1 or emb.shape[1] < 1:
+        raise LmxError(f"gnn_graph: embeddings must be [N, E], got {emb.shape}")
+    N, E = emb.shape
+    if N > GNN_MAX_NODES:
+        raise LmxError(f"gnn_graph: N {N} outside 1 .. {GNN_MAX_NODES}")
+    ts = None if timestamps is None else np.ascontiguousarray(timestamps, np.float64)
+    if ts is not None and ts.shape != (N,):
+        raise LmxError(f"gnn_graph: timestamps {ts.shape} for {N} nodes")
+    cap = max(N * min(max(int(k), 1), max(N - 1, 1)) + 2 * (N - 1), 1)
+    edges, attr, ne = np.zeros((cap, 2), np.int32), np.zeros((cap, 3), np.float32), np.zeros((1,), np.int32)
+    ptr, cse, deg = np.zeros((N + 1,), np.int32), np.zeros((cap,), np.int32), np.zeros((N,), np.int32)
+    lap, rw = np.zeros((N, GNN_LAP_K), np.float32), np.zeros((N, GNN_RW_K), np.float32)
+    check(_lib.load().lmx_h_gnn_graph(emb.ctypes.data, ts.ctypes.data if ts is not None else None, N, E, int(k), edges.ctypes.data, attr.ctypes.data,
+                                      ne.ctypes.data, ptr.ctypes.data, cse.ctypes.data, deg.ctypes.data, lap.ctypes.data, rw.ctypes.data),
+          "lmx_h_gnn_graph")
+    n = int(ne[0])
+    return {"edges": edges[:n].copy(), "edge_attr": attr[:n].copy(), "csr_ptr": ptr, "csr_edge": cse[:n].copy(), "deg": deg, "lap": lap, "rw": rw}
+
+
+def gnn_laplacian(edges, N):
+    """lmx_h_gnn_laplacian: the double-precision eigendecomposition behind the Laplacian encoding of an edge list int32 [E, 2] over N
+    nodes -> (eigenvalues f64 [N] ascending, eigenvectors f64 [N, N], column c for eigenvalue c)."""
+    import numpy as np
+
+    e = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+    lam, vec = np.zeros((int(N),), np.float64), np.zeros((int(N), int(N)), np.float64)
+    check(_lib.load().lmx_h_gnn_laplacian(e.ctypes.data if len(e) else None, len(e), int(N), lam.ctypes.data, vec.ctypes.data), "lmx_h_gnn_laplacian")
+    return lam, vec
+
+
+class GnnBatch:
+    """n graphs of differing N as lmx_gnn_graphs_t wants them: nodes and edges concatenated on `device`, the two offset arrays on the
+    host.  graphs: dicts with x f32 [N, F] and gnn_graph's arrays."""
+
+    def __init__(self, graphs, device):
+        import numpy as np
+
+        self.n, self.device = len(graphs), torch.device(device)
+        self.sizes = [int(np.asarray(g["x"]).shape[0]) for g in graphs]
+        self.n_edges = [len(g["edges"]) for g in graphs]
+        self.node_off = np.zeros((self.n + 1,), np.int32)
+        self.edge_off = np.zeros((self.n + 1,), np.int32)
+        self.node_off[1:] = np.cumsum(self.sizes)
+        self.edge_off[1:] = np.cumsum(self.n_edges)
+        self.nodes, self.edges = int(self.node_off[-1]), int(self.edge_off[-1])
+        self.max_n, self.max_e = max(self.sizes, default=0), max(self.n_edges, default=0)
+        F = int(np.asarray(graphs[0]["x"]).shape[1]) if graphs else 1
+        self.input_dim = F
+        if any(np.asarray(g["x"]).ndim != 2 or np.asarray(g["x"]).shape[1] != F for g in graphs):
+            raise LmxError("GnnBatch: every x must be [N, input_dim] with one input_dim")
+
+        def cat(parts, dtype, tail=()):
+            parts = [np.ascontiguousarray(p, dtype).reshape((-1,) + tail) for p in parts]
+            a = np.concatenate(parts, 0) if parts else np.zeros((0,) + tail, dtype)
+            if a.shape[0] == 0:
+                a = np.zeros((1,) + tail, dtype)  # a pointer the library may look at, never follow
+            return torch.from_numpy(a).to(self.device)
+
+        self.x = cat([g["x"] for g in graphs], np.float32, (F,))
+        self.lap = cat([g["lap"] for g in graphs], np.float32, (GNN_LAP_K,))
+        self.rw = cat([g["rw"] for g in graphs], np.float32, (GNN_RW_K,))
+        self.edge_src = cat([np.asarray(g["edges"], np.int32).reshape(-1, 2)[:, 0] for g in graphs], np.int32)
+        self.edge_dst = cat([np.asarray(g["edges"], np.int32).reshape(-1, 2)[:, 1] for g in graphs], np.int32)
+        self.edge_attr = cat([g["edge_attr"] for g in graphs], np.float32, (3,))
+        self.csr_ptr = cat([g["csr_ptr"] for g in graphs], np.int32)
+        self.csr_edge = cat([g["csr_edge"] for g in graphs], np.int32)
+        self.deg = cat([g["deg"] for g in graphs], np.int32)
+        for key, want in (("lap", self.nodes), ("rw", self.nodes), ("deg", self.nodes), ("csr_ptr", self.nodes + self.n), ("csr_edge", self.edges),
+                          ("edge_attr", self.edges)):
+            if max(want, 1) != getattr(self, key).shape[0]:
+                raise LmxError(f"GnnBatch: {key} has {getattr(self, key).shape[0]} entries, the graphs call for {want}")
+
+    def struct(self):
+        g = _lib.GnnGraphs()
+        g.n = self.n
+        g.node_off_host, g.edge_off_host = self.node_off.ctypes.data, self.edge_off.ctypes.data
+        for name in ("x", "lap", "rw", "edge_src", "edge_dst", "edge_attr", "csr_ptr", "csr_edge", "deg"):
+            setattr(g, name, getattr(self, name).data_ptr())
+        return g
+
+
+def _gnn_forward(host, w, batch, seeds, n_samples, p, trunk):
+    import numpy as np
+
+    who = "gnn_forward_host" if host else "gnn_forward"
+    if not isinstance(batch, GnnBatch):
+        raise LmxError(f"{who}: the graphs come as a GnnBatch")
+    if host:
+        if batch.device.type != "cpu" or w._device.type != "cpu":
+            raise LmxError(f"{who} takes CPU tensors and CPU weights")
+        dev = torch.device("cpu")
+    else:
+        dev = _dev(batch.x)
+        if w._device != dev:
+            raise LmxError(f"{who}: the weights are on {w._device}, the graphs are on {dev}")
+    n, S = batch.n, int(n_samples)
+    if batch.n and batch.input_dim != w.input_dim:
+        raise LmxError(f"{who}: x has {batch.input_dim} features, the network takes {w.input_dim}")
+    if S == 1 or S < 0 or S > 65535:
+        raise LmxError(f"{who}: S {S} (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)")
+    if S and not 0.0 <= p < 1.0:
+        raise LmxError(f"{who}: p {p} outside [0, 1)")
+    for i, (s, e) in enumerate(zip(batch.sizes, batch.n_edges)):
+        if not 1 <= s <= GNN_MAX_NODES:
+            raise LmxError(f"{who}: graph {i} has N = {s} nodes, outside 1 .. {GNN_MAX_NODES}")
+        if e > GNN_MAX_EDGES:
+            raise LmxError(f"{who}: graph {i} has E = {e} edges, more than {GNN_MAX_EDGES}")
+        if S and s < 2:
+            raise LmxError(f"{who}: graph {i} has N = 1 node: BatchNorm has no batch statistics with S = {S}")
+    sd = None
+    if S:
+        if seeds is None:
+            raise LmxError(f"{who}: S = {S} needs one seed per graph")
+        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
+        if sd.shape != (n,):
+            raise LmxError(f"{who}: seeds must be {n} 64-bit values, got {sd.shape}")
+    smax, D = max(S, 1), w.d_model
+
+    def buf(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+
+    mc, stats = (buf(batch.nodes, S), buf(batch.nodes, 2)) if S else (None, None)
+    gp, npred, attw = (None, None, None) if S else (buf(n), buf(batch.nodes), buf(batch.nodes))
+    tr = buf(batch.nodes * smax, D) if trunk else None
+    lib, g = _lib.load(), batch.struct()
+    args = [C.byref(w), C.byref(g), C.c_void_p(sd.ctypes.data if sd is not None else 0), S, float(p), _ptr(mc), _ptr(stats), _ptr(gp), _ptr(npred),
+            _ptr(attw), _ptr(tr)]
+    if host:
+        check(lib.lmx_h_gnn_forward(*args), "lmx_h_gnn_forward")
+    else:
+        nbytes = int(lib.lmx_gnn_workspace_bytes(n, S, batch.max_n, batch.max_e, w.d_model, w.n_layers))
+        ws = torch.empty((max(nbytes, 16) // 16 + 1, 2), dtype=torch.int64, device=dev)
+        check(lib.lmx_k_gnn_forward(*args, _ptr(ws), _stream(dev)), "lmx_k_gnn_forward")
+    trunks = None
+    if trunk:  # graph g's [max(S, 1), N_g, D]
+        trunks = [tr[int(batch.node_off[i]) * smax:int(batch.node_off[i + 1]) * smax].reshape(smax, batch.sizes[i], D) for i in range(n)]
+    return mc, stats, gp, npred, attw, trunks
+
+
+def gnn_forward(w, batch, seeds, n_samples, p, trunk=False):
+    """The live network of GraphGPS for n graphs and S samples in ONE launch (lmx_k_gnn_forward, csrc/gnn.hip): batch a GnnBatch on the
+    device, seeds: n 64-bit values on the host -> (node_mc f32 [sum N, S], stats f32 [sum N, 2] = mean and unbiased std (both None when
+    S = 0), graph_pred f32 [n], node_pred f32 [sum N], attn_weights f32 [sum N] (all three None when S > 0), trunk: a list of
+    [max(S, 1), N_g, D] views or None)."""
+    return _gnn_forward(False, w, batch, seeds, n_samples, p, trunk)
+
+
+def gnn_forward_host(w, batch, seeds, n_samples, p, trunk=False):
+    """lmx_h_gnn_forward: the same network in plain C++ on a CPU GnnBatch, with the same keep bits (no GPU)."""
+    return _gnn_forward(True, w, batch, seeds, n_samples, p, trunk)
+
+
 def pack_records(rec, n_rows=None, row_maps=(), field_map=None, n_valid=None, out=None):
     """dict of per-frame tensors [n_k, ...] on one device -> (uint8 [n_rows, stride], layout): lmx.dist.pack_records' bytes from ONE
     launch that stores every byte of the matrix once (csrc/records.hip); `out` (uint8 [n_rows, stride], contiguous) needs no clearing.

@@ -26,11 +26,11 @@ import numpy as np
 import torch
 
 from . import _lib, letterbox, resample
-from ._lib import DinoInfo, FusedInfo, GfmInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, TcnInfo, XfmInfo, YoloInfo, check
+from ._lib import DinoInfo, FusedInfo, GfmInfo, GnnInfo, LetterboxGeo, LmxError, RecordLayout, SamInfo, TcnInfo, XfmInfo, YoloInfo, check
 
 MAGIC = b"LMXIMAGE"
 VERSION = 1
-KIND_DINO, KIND_YOLO, KIND_SAM, KIND_TCN, KIND_XFM, KIND_GFM = 1, 2, 3, 4, 5, 6
+KIND_DINO, KIND_YOLO, KIND_SAM, KIND_TCN, KIND_XFM, KIND_GFM, KIND_GNN = 1, 2, 3, 4, 5, 6, 7
 HEADER_BYTES, ENTRY_BYTES, NAME_BYTES = 48, 88, 48
 ARCH = {"dinov2": 0, "dinov3": 1}
 RECIPE = {"pil": 0, "float": 1}
@@ -147,6 +147,27 @@ def check_xfm_image(path):
     """lmx_xfm_image_check_host: validate an image on the host (no GPU) -> XfmInfo; LmxError names the offending field."""
     info = XfmInfo()
     check(_lib.load().lmx_xfm_image_check_host(str(path).encode(), C.byref(info)), "lmx_xfm_image_check_host")
+    return info
+
+
+# ---- GraphGPS' weight image (csrc/gnn_image.h) ---------------------------------------------------------------------------------------
+def gnn_config_block(cfg):
+    """8 int32 (input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim, 0) then the dropout probability as one float64."""
+    return struct.pack("<8id", *cfg.shape(), 0, cfg.dropout)
+
+
+def write_gnn_image(cfg, weights, path):
+    """Export the live network of GraphGPS (lmx.checkpoints.gnn_from_state_dict's configuration and weights) as the weight image
+    lmx_gnn_open_host reads: the tensors of lmx.gnn.pack_tensors under the names of lmx_gnn_weights_t's fields.  Returns the file's size."""
+    from . import gnn
+
+    return write_image(path, KIND_GNN, gnn_config_block(cfg.validate("write_gnn_image")), gnn.pack_tensors(cfg, weights))
+
+
+def check_gnn_image(path):
+    """lmx_gnn_image_check_host: validate an image on the host (no GPU) -> GnnInfo; LmxError names the offending field."""
+    info = GnnInfo()
+    check(_lib.load().lmx_gnn_image_check_host(str(path).encode(), C.byref(info)), "lmx_gnn_image_check_host")
     return info
 
 
@@ -1048,3 +1069,50 @@ class NativeGfm(_NativeHandle):
     def score_host(self, graphs, seeds=None, n_samples=10, targets=None, node=False):
         """The same from and to HOST memory (CPU tensors): lmx_gfm_score_host uploads, scores, downloads, synchronises."""
         return self._call("score_host", graphs, seeds, n_samples, targets, node)
+
+
+class NativeGnn(_NativeHandle):
+    """lmx_gnn_open_host(path, max_graphs, max_nodes_total, max_edges_total, max_samples) on `device` (default: torch's current device):
+    GraphGPS from its weight image.  score / score_host give the bits of lmx.gnn.GnnScorer (tests/test_gpu_gnn.py)."""
+    _PREFIX, _INFO = "lmx_gnn_", GnnInfo
+
+    def __init__(self, path, max_graphs, max_nodes_total, max_edges_total, max_samples=10, device=None):
+        self._extra = (int(max_nodes_total), int(max_edges_total), int(max_samples))
+        super().__init__(path, max_graphs, device)
+
+    def _open_args(self, max_batch):
+        return (int(max_batch),) + self._extra
+
+    def _call(self, what, graphs, seeds, n_samples):
+        from . import kernels as K
+
+        host = what == "score_host"
+        b = graphs if isinstance(graphs, K.GnnBatch) else K.GnnBatch(graphs, "cpu" if host else self.device)
+        if b.device != (torch.device("cpu") if host else self.device):
+            raise LmxError(f"NativeGnn.{what}: the graphs are on {b.device}")
+        n, S = b.n, int(n_samples)
+        sd = None
+        if S:
+            sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
+            if sd.shape != (n,):
+                raise LmxError(f"NativeGnn.{what}: {n} graphs need {n} seeds, got {sd.shape}")
+        empty = lambda *shape: torch.empty(shape, dtype=torch.float32, device=b.device)  # noqa: E731
+        mc, stats = (empty(b.nodes, S), empty(b.nodes, 2)) if S else (None, None)
+        gp, npred, attw = (None, None, None) if S else (empty(n), empty(b.nodes), empty(b.nodes))
+        g = b.struct()
+        args = [self._handle(), C.byref(g), _vp(sd), S, _vp(mc), _vp(stats), _vp(gp), _vp(npred), _vp(attw)]
+        with torch.cuda.device(self.device):
+            if host:
+                check(self._lib.lmx_gnn_score_host(*args), "lmx_gnn_score_host")
+            else:
+                check(self._lib.lmx_gnn_score(*args, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "lmx_gnn_score")
+        return mc, stats, gp, npred, attw
+
+    def score(self, graphs, seeds=None, n_samples=10):
+        """graphs: lmx.gnn.build_graph's dicts (or a GnnBatch on the handle's device), n host seeds -> (node_mc [sum N, S], stats
+        [sum N, 2], graph_pred [n], node_pred [sum N], attn_weights [sum N]) as lmx.gnn.GnnScorer.forward, on torch's current stream."""
+        return self._call("score", graphs, seeds, n_samples)
+
+    def score_host(self, graphs, seeds=None, n_samples=10):
+        """The same from and to HOST memory (CPU tensors): lmx_gnn_score_host uploads, scores, downloads, synchronises."""
+        return self._call("score_host", graphs, seeds, n_samples)
