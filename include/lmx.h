@@ -1313,7 +1313,7 @@ int lmx_h_gfm_forward(const lmx_gfm_weights_t* w_host, const lmx_gfm_graphs_t* g
                       float* pred_host, float* stats_host, float* node_pred_host, float* attn_to_target_host, float* trunk_host,
                       float* vn_host);
 
-/* ==== MODEL level: graph scores from prepared graphs (csrc/gait_model.hip, csrc/gfm_image.h, csrc/host_gfm_image.cpp) =================
+/* ==== MODEL level: graph scores from prepared graphs (csrc/graph_model.hip, csrc/gfm_image.h, csrc/host_gfm_image.cpp) ================
  * services/graph-transformer-pipeline/app/main.py behind a handle: the model comes from a WEIGHT IMAGE (kind 6) that
  * lmx.native.write_gfm_image writes (csrc/gfm_image.h has the config block and the tensors); handle rules as for lmx_tcn.  The handle
  * owns the workspace for max_graphs graphs of max_nodes_total nodes in all.  lmx_gfm_score: the graphs as for lmx_k_gfm_forward (DEVICE
@@ -1459,7 +1459,7 @@ int lmx_h_gnn_forward(const lmx_gnn_weights_t* w_host, const lmx_gnn_graphs_t* g
                       float* node_mc_host, float* stats_host, float* graph_pred_host, float* node_pred_host, float* attn_weights_host,
                       float* trunk_host);
 
-/* ==== MODEL level: GraphGPS scores from prepared graphs (csrc/gait_model.hip, csrc/gnn_image.h, csrc/host_gnn_image.cpp) ================
+/* ==== MODEL level: GraphGPS scores from prepared graphs (csrc/graph_model.hip, csrc/gnn_image.h, csrc/host_gnn_image.cpp) ===============
  * services/gnn-pipeline/app/main.py's model behind a handle: the weights come from a WEIGHT IMAGE (kind 7) that
  * lmx.native.write_gnn_image writes (csrc/gnn_image.h has the config block and the tensors; the last live layer's edge update is not in
  * it); handle rules as for lmx_tcn.  The handle owns the workspace: lmx_gnn_workspace_bytes(max_graphs, max_samples, min(95,

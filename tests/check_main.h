@@ -1,5 +1,6 @@
-// gait_check.h — what tcn_check_main.cpp and xfm_check_main.cpp share: the program's own lmx_set_error (the library's lives in api.hip),
-// the loader of an image's data section, the reader of the pose file's common front, and main's two modes.
+// check_main.h — what the four *_check_main.cpp programs share: the program's own lmx_set_error (the library's lives in api.hip), the
+// loader of an image's data section, the loader of a file of tensors into exactly-sized blocks, main's `check PATH...` mode, and for
+// the two gait programs the reader of the pose file's common front and main's `score` mode.
 #pragma once
 #include <stdarg.h>
 #include <stdint.h>
@@ -33,6 +34,21 @@ static char* load_data(const char* image, uint64_t data_offset, uint64_t file_by
   return data;
 }
 
+// the f32 tensors of `path` with counts[i] floats each, one after the other: each into a block of its own, 16-byte aligned and exactly as
+// long as the tensor; whole_file: the file holds the tensors and nothing more
+static bool load_tensors(const char* path, const std::vector<size_t>& counts, bool whole_file, std::vector<char*>& blocks) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  for (size_t c : counts) {
+    void* p = nullptr;
+    if (posix_memalign(&p, 16, c * 4) || fread(p, 4, c, f) != c) return false;
+    blocks.push_back(static_cast<char*>(p));
+  }
+  if (whole_file && fgetc(f) != EOF) return false;
+  fclose(f);
+  return true;
+}
+
 template <class T>
 static bool read_all(FILE* f, std::vector<T>& v) {
   return fread(v.data(), sizeof(T), v.size(), f) == v.size();
@@ -45,18 +61,23 @@ static FILE* open_pose(const char* pose, int T0, std::vector<double>& kp, std::v
   return f && read_all(f, kp) && read_all(f, bbox) && read_all(f, n_kp) ? f : nullptr;
 }
 
-// check PATH...: one line per file, "<return code>\t<path>\t<error text>"; score IMAGE POSE T0 S SEED
+// check PATH...: one line per file, "<return code>\t<path>\t<error text>"; false if the arguments ask for something else
+template <class Info>
+static bool check_mode(int argc, char** argv, int (*check)(const char*, Info*)) {
+  if (argc < 3 || strcmp(argv[1], "check") != 0) return false;
+  for (int i = 2; i < argc; ++i) {
+    g_error[0] = 0;
+    Info info;
+    const int rc = check(argv[i], &info);
+    printf("%d\t%s\t%s\n", rc, argv[i], g_error);
+  }
+  return true;
+}
+
+// check PATH... | score IMAGE POSE T0 S SEED
 template <class Info>
 static int gait_main(int argc, char** argv, int (*check)(const char*, Info*), int (*score)(const char*, const char*, int, int, uint64_t)) {
-  if (argc >= 3 && strcmp(argv[1], "check") == 0) {
-    for (int i = 2; i < argc; ++i) {
-      g_error[0] = 0;
-      Info info;
-      const int rc = check(argv[i], &info);
-      printf("%d\t%s\t%s\n", rc, argv[i], g_error);
-    }
-    return 0;
-  }
+  if (check_mode(argc, argv, check)) return 0;
   if (argc == 7 && strcmp(argv[1], "score") == 0) return score(argv[2], argv[3], atoi(argv[4]), atoi(argv[5]), strtoull(argv[6], nullptr, 10));
   fprintf(stderr, "usage: %s check PATH... | score IMAGE POSE T0 S SEED\n", argv[0]);
   return 2;

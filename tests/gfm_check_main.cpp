@@ -10,20 +10,12 @@
 // Every buffer is sized exactly, so that a read or a write past an end is the sanitizer's to see.  The library reports through
 // lmx_set_error, which lives in api.hip with the rest of it: this program brings its own.
 #include "../vision-sam3-yolo-lameless_amd/csrc/gfm_image.h"
-#include "gait_check.h"
+#include "check_main.h"
 
 static const float* take(const std::vector<char*>& blocks, size_t& next) { return reinterpret_cast<const float*>(blocks[next++]); }
 
 int main(int argc, char** argv) {
-  if (argc >= 3 && strcmp(argv[1], "check") == 0) {
-    for (int i = 2; i < argc; ++i) {
-      g_error[0] = 0;
-      lmx_gfm_info_t info;
-      const int rc = lmx_gfm_image_check_host(argv[i], &info);
-      printf("%d\t%s\t%s\n", rc, argv[i], g_error);
-    }
-    return 0;
-  }
+  if (check_mode(argc, argv, lmx_gfm_image_check_host)) return 0;
   if (argc != 11) {
     fprintf(stderr, "usage: %s CONFIG WEIGHTS GRAPH N E K TIMED S SEED TARGET\n", argv[0]);
     return 2;
@@ -52,15 +44,8 @@ int main(int argc, char** argv) {
                          (size_t)D * (D / 2), (size_t)D / 2, (size_t)(D / 2) * (D / 4), (size_t)D / 4, (size_t)D / 4, 1,
                          (size_t)Q * (PD / 16) * 256, (size_t)PD, (size_t)PD, 1};
   counts.insert(counts.end(), tail, tail + 26);
-  FILE* f = fopen(argv[2], "rb");
-  if (!f) return 2;
   std::vector<char*> blocks;
-  for (size_t c : counts) {
-    void* p = nullptr;  // 16-byte aligned and exactly as long as the tensor
-    if (posix_memalign(&p, 16, c * 4) || fread(p, 4, c, f) != c) return 2;
-    blocks.push_back(static_cast<char*>(p));
-  }
-  fclose(f);
+  if (!load_tensors(argv[2], counts, false, blocks)) return 2;
   size_t next = 0;
   const float** head[] = {&w.in_w, &w.in_b, &w.in_g, &w.in_beta, &w.deg_in, &w.deg_out, &w.time_w, &w.time_b, &w.div_term, &w.spd, &w.e1_w,
                           &w.e1_b, &w.e2_w, &w.e2_b};
@@ -77,7 +62,7 @@ int main(int argc, char** argv) {
 
   if (N < 1 || N > 4096 || E < 1 || E > 4096 || k < 0) return 2;
   std::vector<float> x((size_t)N * F), emb((size_t)N * E), ts((size_t)(timed ? N : 0));
-  f = fopen(argv[3], "rb");
+  FILE* f = fopen(argv[3], "rb");
   if (!f || !read_all(f, x) || !read_all(f, emb) || (timed && !read_all(f, ts))) return 2;
   fclose(f);
   const int kk = k < N - 1 ? k : N - 1, cap = N * kk + 2 * (N - 1);

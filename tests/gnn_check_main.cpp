@@ -11,20 +11,12 @@
 // Every buffer is sized exactly, so that a read or a write past an end is the sanitizer's to see.  The library reports through
 // lmx_set_error, which lives in api.hip with the rest of it: this program brings its own.
 #include "../vision-sam3-yolo-lameless_amd/csrc/gnn_image.h"
-#include "gait_check.h"
+#include "check_main.h"
 
 static const float* take(const std::vector<char*>& blocks, size_t& next) { return reinterpret_cast<const float*>(blocks[next++]); }
 
 int main(int argc, char** argv) {
-  if (argc >= 3 && strcmp(argv[1], "check") == 0) {
-    for (int i = 2; i < argc; ++i) {
-      g_error[0] = 0;
-      lmx_gnn_info_t info;
-      const int rc = lmx_gnn_image_check_host(argv[i], &info);
-      printf("%d\t%s\t%s\n", rc, argv[i], g_error);
-    }
-    return 0;
-  }
+  if (check_mode(argc, argv, lmx_gnn_image_check_host)) return 0;
   if (argc != 10) {
     fprintf(stderr, "usage: %s CONFIG WEIGHTS GRAPH N E K TIMED S SEED\n", argv[0]);
     return 2;
@@ -61,16 +53,8 @@ int main(int argc, char** argv) {
   const size_t half = (size_t)Q * (D2 / 16) * 256;
   const size_t tail[] = {v, v, half, (size_t)D2, (size_t)D2, 1, half, (size_t)D2, (size_t)D2, 1, 2 * v * v, v, v * D2, (size_t)D2, (size_t)D2, 1};
   counts.insert(counts.end(), tail, tail + 16);
-  FILE* f = fopen(argv[2], "rb");
-  if (!f) return 2;
   std::vector<char*> blocks;
-  for (size_t c : counts) {
-    void* p = nullptr;  // 16-byte aligned and exactly as long as the tensor
-    if (posix_memalign(&p, 16, c * 4) || fread(p, 4, c, f) != c) return 2;
-    blocks.push_back(static_cast<char*>(p));
-  }
-  if (fgetc(f) != EOF) return 2;  // the file holds the tensors and nothing more
-  fclose(f);
+  if (!load_tensors(argv[2], counts, true, blocks)) return 2;
   size_t next = 0;
   const float** head[] = {&w.in_w, &w.in_b, &w.lap1_w, &w.lap1_b, &w.lap2_w, &w.lap2_b, &w.lap_g, &w.lap_beta, &w.rw1_w, &w.rw1_b,
                           &w.rw2_w, &w.rw2_b, &w.rw_g, &w.rw_beta, &w.ee1_w, &w.ee1_b, &w.ee2_w, &w.ee2_b, &w.ee_g, &w.ee_beta};
@@ -93,7 +77,7 @@ int main(int argc, char** argv) {
   if (N < 1 || N > 4096 || E < 1 || E > 4096 || k < 1) return 2;
   std::vector<float> x((size_t)N * F), emb((size_t)N * E);
   std::vector<double> ts((size_t)(timed ? N : 0));
-  f = fopen(argv[3], "rb");
+  FILE* f = fopen(argv[3], "rb");
   if (!f || !read_all(f, x) || !read_all(f, emb) || (timed && !read_all(f, ts))) return 2;
   fclose(f);
   const int kk = N <= k ? (N - 1 > 1 ? N - 1 : 1) : k, cap = N > 1 ? N * kk + (timed ? 2 * (N - 1) : 0) : 0;  // exactly what the rules give

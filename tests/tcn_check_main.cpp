@@ -5,7 +5,7 @@
 //                                                features' and the keep bits' sums, then the predictions, mean and deviation as hex floats
 // The readers report through lmx_set_error, which lives in api.hip with the rest of the library: this program brings its own.
 #include "../vision-sam3-yolo-lameless_amd/csrc/tcn_image.h"
-#include "gait_check.h"
+#include "check_main.h"
 
 static int score(const char* image, const char* pose, int T0, int S, uint64_t seed) {
   LmxTcnImage img;

@@ -14,12 +14,13 @@ import statistics
 import torch
 import torch.nn.functional as F
 
-import gait_ab as G
+import graph_ab as A
+from gait_ab import cell, write
 
 import gnnref  # noqa: E402
 from lmx import checkpoints, gnn  # noqa: E402
 
-S, BACKLOG = 10, 64
+S = A.S
 
 
 def flops_per_pass(cfg, N, E):
@@ -31,37 +32,19 @@ def flops_per_pass(cfg, N, E):
 
 
 def main():
-    args = G.parse_args("gnn_ab")
-    dev = torch.device("cuda:0")
-    cfg = gnnref.SHIPPED
-    _, w = checkpoints.gnn_from_state_dict(gnnref.state_dict(cfg, 1), num_heads=cfg.n_heads, dropout=cfg.dropout)
-    scorer = gnn.GnnScorer(cfg, w, device=dev)
-    dev_w = {k: v.to(dev) for k, v in w.items()}
+    def lmx_sides(scorer, graphs, seeds):
+        b = scorer.batch(graphs)
+        return ((lambda: (scorer.forward(b, seeds, S), scorer.forward(b, None, 0))), (lambda: scorer.forward(b, seeds, S)),
+                (lambda: scorer.forward(b, None, 0)))
 
-    def torch_score(graphs):
-        """per graph: predict_with_uncertainty (ten train-mode forwards, stack, mean, unbiased std), then the eval forward"""
-        out = []
-        with torch.no_grad():
-            for gr in graphs:
-                preds = torch.stack([gnnref.forward(cfg, dev_w, gr, lambda v, site: F.dropout(v, cfg.dropout, True), torch.float32, True, dev)["node_pred"]
-                                     for _ in range(S)], 0)
-                ev = gnnref.forward(cfg, dev_w, gr, None, torch.float32, False, dev)
-                out.append((preds.mean(0), preds.std(0), ev["graph_pred"], ev["node_pred"], ev["attw"]))
-        return out
+    def eval_forward(cfg, w, gr, dev):
+        ev = gnnref.forward(cfg, w, gr, None, torch.float32, False, dev)
+        return ev["graph_pred"], ev["node_pred"], ev["attw"]
 
-    rows, edges = {}, {}
-    for N in (8, gnn.MAX_NODES):
-        for n, iters_lmx, iters_torch in ((1, 50, 2), (BACKLOG, 10, 1)):
-            g = torch.Generator().manual_seed(100 * N + n)
-            graphs = [gnnref.make_graphs(cfg, N, g)[1] for _ in range(n)]
-            edges[N] = len(graphs[0]["edges"])
-            b = scorer.batch(graphs)
-            seeds = list(range(1, n + 1))
-            rows[(N, n)] = G.alternate([(lambda: (scorer.forward(b, seeds, S), scorer.forward(b, None, 0)), iters_lmx),
-                                        (lambda: torch_score(graphs), iters_torch), (lambda: scorer.forward(b, seeds, S), iters_lmx),
-                                        (lambda: scorer.forward(b, None, 0), iters_lmx)], args.rounds)
-
-    cus, mhz, where = G.device(dev, args.rounds)
+    args, cfg, rows, edges, (cus, mhz, where) = A.measure(
+        "gnn_ab", gnn, gnn.GnnScorer, gnnref, checkpoints.gnn_from_state_dict,
+        lambda cfg, w, gr, dev: gnnref.forward(cfg, w, gr, lambda v, site: F.dropout(v, cfg.dropout, True), torch.float32, True, dev)["node_pred"],
+        eval_forward, lmx_sides)
     lines = [f"GraphGPS, shipped configuration (50 -> d_model 128, 8 heads, 2 live layers of num_layers 4, FF 512), graphs with timestamps, k = 5, "
              f"S = {S} samples; {where}",
              f"{'N':>3} {'E':>4} {'n':>4}  {'lmx S = 10 + eval launches, ms':>32}  {'torch eager 10 + 1 forwards per graph, ms':>42}  {'ratio':>7}  "
@@ -70,16 +53,12 @@ def main():
         a, b, c, d = sides
         ma, mb, mc = statistics.median(a), statistics.median(b), statistics.median(c)
         fl = flops_per_pass(cfg, N, edges[N])
-        lines.append(f"{N:>3} {edges[N]:>4} {n:>4}  {G.cell(a, 12, 4)}  {G.cell(b, 12, 3):>42}  {mb / ma:>7.1f}  {G.cell(c, 12, 4)}  {G.cell(d, 12, 4)}  "
+        lines.append(f"{N:>3} {edges[N]:>4} {n:>4}  {cell(a, 12, 4)}  {cell(b, 12, 3):>42}  {mb / ma:>7.1f}  {cell(c, 12, 4)}  {cell(d, 12, 4)}  "
                      f"{n / ma * 1e3:>9.0f}  {n * S * fl / mc / 1e9:>8.2f}")
     N = gnn.MAX_NODES
-    fl = flops_per_pass(cfg, N, edges[N])
-    lines.append(f"FLOPs per (graph, sample): {flops_per_pass(cfg, 8, edges[8]) / 1e6:.2f} M at N = 8, {fl / 1e6:.2f} M at N = {N}")
-    bound_ms, derivation = G.bound(BACKLOG * S * fl, cus, mhz)
-    lines.append(f"f32 MFMA bound for N = {N}, n = {BACKLOG}, S = {S}: {derivation}; S = 10 launch / bound = "
-                 f"{statistics.median(rows[(N, BACKLOG)][2]) / bound_ms:.2f}")
+    lines += A.last_lines(rows, flops_per_pass(cfg, 8, edges[8]), flops_per_pass(cfg, N, edges[N]), N, cus, mhz, "launch")
     lines.append("Not in the torch baseline: the reference's eleven host-side eigendecompositions and matrix powers per video, and its dead post-pool layers.")
-    G.write(args.out, lines)
+    write(args.out, lines)
 
 
 if __name__ == "__main__":

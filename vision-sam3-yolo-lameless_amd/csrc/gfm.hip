@@ -12,19 +12,17 @@
 // output over transposed weights, with the host's sequential sums.
 // Rows beyond N: h starts as zeros there and stays finite, they are masked as keys (their score is -inf, so P is exactly 0 where V
 // holds them), never pooled, and never leave the LDS.
+// graph_tile.h has what this kernel shares with gnn.hip: the workgroup's shape, wave_fence, zero, Keep, layer_norm and mma_cols.
 #include "gait_launch.h"
 #include "gfm.h"
+#include "graph_tile.h"
 
 namespace {
 
-constexpr int NW = 8;             // waves of a workgroup
-constexpr int NTH = NW * 64;
-constexpr int LD = 132;           // floats per row of h and a: rows 16-byte aligned, 16 rows of a float4 column in 16 different slots
 constexpr int PLD = 20;           // floats per row of a wave's 16 x 16 patch
 constexpr int PATCH = 16 * PLD;
 constexpr int KT = (LMX_GFM_MAX_NODES + 1 + 15) / 16;  // key tiles held in registers
 constexpr int TAIL = 3 * LMX_GFM_MAX_D + 2 * LMX_GFM_MAX_D + LMX_GFM_MAX_D + LMX_GFM_MAX_D / 2 + LMX_GFM_MAX_D / 4;  // comb | vnv | gr | h1 | h2
-constexpr int LDS_LIMIT = 160 * 1024;
 
 struct GfmArgs {
   lmx_gfm_weights_t w;
@@ -45,13 +43,6 @@ struct GfmArgs {
 // h | a | U | one patch per wave | pool scores, attention column, pool weights (one per row) | the single-row vectors
 __host__ __device__ constexpr int lds_floats(int TP, int LDU) { return TP * (2 * LD + LDU + 3) + NW * PATCH + TAIL; }
 
-__device__ __forceinline__ void wave_fence() {
-  // orders this wave's LDS stores before its later LDS loads of other lanes' words (the hardware keeps a wave's DS operations in order)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // sum of N^2 over the graphs in front of graph g: where its matrices start.  `red`: nth 64-bit words of LDS; every thread calls.
 __device__ __forceinline__ long long cells_before(const int32_t* node_off, int g, long long* red, int tid, int nth) {
   long long s = 0;
@@ -70,12 +61,6 @@ __device__ __forceinline__ long long cells_before(const int32_t* node_off, int g
   const long long out = red[0];
   __syncthreads();
   return out;
-}
-
-template <int NC>
-__device__ __forceinline__ void zero(f32x4 (&acc)[NC]) {
-#pragma unroll
-  for (int ni = 0; ni < NC; ++ni) acc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 // acc[ni] += rows of tile m of src[.][0 .. 16 nq) x the groups q0 .. q0 + nq - 1 and column tiles n0 .. n0 + nn - 1 (nn <= NC) of the
@@ -117,78 +102,6 @@ __device__ __forceinline__ void mma(f32x4 (&acc)[NC], const float* src, int ld, 
   if (NC == 4) {
 #pragma unroll
     for (int ni = 0; ni < NC; ++ni) acc[ni] += odd[NC == 4 ? ni : 0];
-  }
-}
-
-// racc += one block of a sum over blocks (a head's share of out_proj, an FFN chunk's share of fc2), all NTD <= 8 column tiles: the
-// block's own chains start at zero, four column tiles at a time, which keeps the registers of a second set of eight accumulators free
-__device__ __forceinline__ void mma_block(f32x4 (&racc)[8], const float* src, int ld, const float* __restrict__ W, int q0, int nq, int NTD, int m,
-                                          int lane) {
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int nn = NTD - 4 * half < 4 ? NTD - 4 * half : 4;
-    if (nn > 0) {
-      f32x4 block[4];
-      zero<4>(block);
-      mma<4>(block, src, ld, W, q0, nq, NTD, 4 * half, nn, m, lane);
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) racc[4 * half + ni] += block[ni];
-    }
-  }
-}
-
-struct Keep {
-  bool on;
-  uint64_t seed, stream0, thr;
-  float scale;
-  __device__ __forceinline__ float operator()(float v, int site, uint64_t u) const {
-    if (!on) return v;
-    return lmx_gait_keep(seed, stream0 + (uint64_t)site, u, thr) ? v * scale : 0.f;
-  }
-};
-
-// dst = LN(src) on the 16 rows of tile m (dst may be src): one row per 16-lane group, two passes.  site >= 0: the rows 1 .. N are dropped
-// at that site with u = (t - 1) * D + c.  `out` (global, may be null) receives the rows 1 .. N as [N][D].
-__device__ __forceinline__ void layer_norm(const float* src, float* dst, const float* __restrict__ gam, const float* __restrict__ bet, int D, int N,
-                                           int m, int lane, const Keep& keep, int site, float* out) {
-  const int r = lane & 15, g = lane >> 4;
-  float gg[8], bb[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = r + 16 * j;
-    gg[j] = c < D ? gam[c] : 0.f;
-    bb[j] = c < D ? bet[c] : 0.f;
-  }
-  const float inv = (float)D;
-  for (int rr = 0; rr < 4; ++rr) {
-    const int t = m * 16 + 4 * rr + g;
-    float v[8], sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      v[j] = r + 16 * j < D ? src[t * LD + r + 16 * j] : 0.f;
-      sum += v[j];
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
-    const float mean = sum / inv;
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (r + 16 * j < D) ss += (v[j] - mean) * (v[j] - mean);
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) ss += __shfl_xor(ss, o, 64);
-    const float rstd = 1.0f / sqrtf(ss / inv + 1e-5f);
-    const bool node = t >= 1 && t <= N;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = r + 16 * j;
-      if (c < D) {
-        float y = (v[j] - mean) * rstd * gg[j] + bb[j];
-        if (site >= 0 && node) y = keep(y, site, (uint64_t)((t - 1) * D + c));
-        dst[t * LD + c] = y;
-        if (out && node) out[(size_t)(t - 1) * D + c] = y;
-      }
-    }
   }
 }
 
@@ -315,7 +228,7 @@ __device__ __forceinline__ void attention(f32x4 (&racc)[8], const float* src, fl
         }
     }
     __syncthreads();  // every wave has read K and V of this head
-    if (act) mma_block(racc, ub, LDU, out_w, hd * NQ, NQ, NTD, m, lane);  // the head's share of out_proj as a block of its own
+    if (act) mma_cols<mma<4>>(racc, ub, LDU, out_w, hd * NQ, NQ, NTD, 0, NTD, m, lane);  // the head's share of out_proj as a block of its own
     __syncthreads();  // ... and its own rows of the output, before the next head's q | k | v land in U
   }
 }
@@ -417,7 +330,7 @@ __global__ __launch_bounds__(NTH) void gfm_forward_kernel(const GfmArgs a) {
         }
       }
     wave_fence();
-    layer_norm(hb, hb, a.w.in_g, a.w.in_beta, D, N, m, lane, keep, 0, nullptr);
+    layer_norm<1>(hb, hb, a.w.in_g, a.w.in_beta, D, N, m, lane, keep, 0, nullptr);
     const bool timed = a.has_time != nullptr && a.has_time[gi] != 0;
     if (timed) {
       const float* ts = a.ts + n0;
@@ -459,7 +372,7 @@ __global__ __launch_bounds__(NTH) void gfm_forward_kernel(const GfmArgs a) {
   __syncthreads();
 
   for (int l = 0; l < L; ++l) {
-    if (act) layer_norm(hb, ab, a.w.ln1_g[l], a.w.ln1_b[l], D, N, m, lane, keep, -1, nullptr);
+    if (act) layer_norm<1>(hb, ab, a.w.ln1_g[l], a.w.ln1_b[l], D, N, m, lane, keep, -1, nullptr);
     __syncthreads();
     attention<false>(racc, ab, ub, mypatch, attw, a.w.qkv_w[l], a.w.qkv_b[l], a.w.out_w[l], bias, N, MT, m, act, lane, D, H, dh, LDU, a.cs, keep,
                      1 + 6 * l, l == L - 1 ? tcol : -1);
@@ -479,7 +392,7 @@ __global__ __launch_bounds__(NTH) void gfm_forward_kernel(const GfmArgs a) {
           }
         }
       wave_fence();
-      layer_norm(hb, ab, a.w.ln2_g[l], a.w.ln2_b[l], D, N, m, lane, keep, -1, nullptr);
+      layer_norm<1>(hb, ab, a.w.ln2_g[l], a.w.ln2_b[l], D, N, m, lane, keep, -1, nullptr);
     }
     __syncthreads();
     // the FFN, 64 hidden columns at a time through U; fc2 accumulates over the chunks
@@ -506,7 +419,7 @@ __global__ __launch_bounds__(NTH) void gfm_forward_kernel(const GfmArgs a) {
             }
           }
         wave_fence();  // the chunk is read by the wave that wrote it
-        mma_block(racc, ub, LDU, a.w.ff2_w[l], n0f, nn, NTD, m, lane);
+        mma_cols<mma<4>>(racc, ub, LDU, a.w.ff2_w[l], n0f, nn, NTD, 0, NTD, m, lane);
         wave_fence();
       }
     }
@@ -560,7 +473,7 @@ __global__ __launch_bounds__(NTH) void gfm_forward_kernel(const GfmArgs a) {
     vnv[j] = 0.5f * s * (1.0f + erff(s * 0.70710678118654752440f));
   }
   if (act)
-    layer_norm(hb, ab, a.w.lnf_g, a.w.lnf_b, D, N, m, lane, keep, -1, a.trunk ? a.trunk + ((size_t)n0 * Smax + (size_t)sample * N) * D : nullptr);
+    layer_norm<1>(hb, ab, a.w.lnf_g, a.w.lnf_b, D, N, m, lane, keep, -1, a.trunk ? a.trunk + ((size_t)n0 * Smax + (size_t)sample * N) * D : nullptr);
   __syncthreads();
   if (tid < D) {
     float s = a.w.vu2_b[tid];

@@ -3,7 +3,7 @@
 // LayerNorm's output, then Ax + the aggregated messages) and the work tile U (a wave's 16-edge tiles, then q_i | k_i | v_i of the current
 // head, then 64 columns of the FFN's hidden layer at a time).  Node i sits in row i; wave w owns the 16-row tile w of all three (waves
 // beyond the graph's tiles only keep the barriers).  Every product over node rows or edge rows runs on the exact f32-input MFMA
-// v_mfma_f32_16x16x4_f32 in the operand order of gfm.hip, whose helpers are restated here (gfm.hip stays as it is), except that in a product
+// v_mfma_f32_16x16x4_f32 in the operand order of gfm.hip, with which it shares the helpers of graph_tile.h, except that in a product
 // with weights no MFMA accumulates into its third operand: `mma` says why (the scores and P.V of the attention still chain).
 // Message passing: Bx | Dx | Ex of every node go to the workgroup's slice of the workspace (they are gathered by src and dst of any
 // edge and do not fit beside the three tiles); wave w then walks the edges INTO its own 16 nodes in CSR order, 16 at a time: the edge
@@ -15,19 +15,16 @@
 // Every index read from the graph (src, dst, csr_ptr, csr_edge) is clamped into the graph before it is used as an address.
 #include "gait_launch.h"
 #include "gnn.h"
+#include "graph_tile.h"
 
 namespace {
 
-constexpr int NW = 8;             // waves of a workgroup
-constexpr int NTH = NW * 64;
-constexpr int LD = 132;           // floats per row of the three tiles: rows 16-byte aligned, 16 rows of a float4 column in 16 different slots
 constexpr int PCOL = 100;         // a wave's 16 x 16 patch of attention probabilities: columns 100 .. 115 of its own rows of U (q | k | v end at 96)
 constexpr int ICOL = 128;         // dst, src and the edge of an edge tile's row, as integers in columns 128 .. 130 of U
 constexpr int KT = (LMX_GNN_MAX_NODES + 15) / 16;  // key tiles held in registers
 constexpr int TPMAX = KT * 16;
 // partial sums | node mean, rstd | edge mean, rstd | pool scores, weights | mean and weighted pool | classifier hidden 1, 2
 constexpr int TAIL = NTH + 4 * LMX_GNN_MAX_D + 2 * TPMAX + 2 * LMX_GNN_MAX_D + LMX_GNN_MAX_D + LMX_GNN_MAX_D / 2;
-constexpr int LDS_LIMIT = 160 * 1024;
 
 struct GnnArgs {
   lmx_gnn_weights_t w;
@@ -45,20 +42,7 @@ struct GnnArgs {
 
 __host__ __device__ constexpr int lds_floats(int TP) { return 3 * TP * LD + TAIL; }
 
-__device__ __forceinline__ void wave_fence() {
-  // orders this wave's LDS stores before its later LDS loads of other lanes' words (the hardware keeps a wave's DS operations in order)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-template <int NC>
-__device__ __forceinline__ void zero(f32x4 (&acc)[NC]) {
-#pragma unroll
-  for (int ni = 0; ni < NC; ++ni) acc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
 
 // acc[ni] += rows of tile m of src[.][0 .. 16 nq) x the groups q0 .. q0 + nq - 1 and column tiles n0 .. n0 + nn - 1 (nn <= 4) of the
 // packed linear layer W with NT column tiles; the B operand of the NEXT group is loaded while the MFMAs of this one run.
@@ -95,76 +79,6 @@ __device__ __forceinline__ void mma(f32x4 (&acc)[4], const float* src, int ld, c
   }
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) acc[ni] += low[ni];
-}
-
-// racc[0 .. ncols) += one block of a sum over blocks: the column tiles n0 .. n0 + ncols - 1 (ncols <= 8) of W, four at a time, each with
-// chains of its own that start at zero
-__device__ __forceinline__ void mma_cols(f32x4 (&racc)[8], const float* src, int ld, const float* __restrict__ W, int q0, int nq, int NT, int n0,
-                                         int ncols, int m, int lane) {
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int nn = ncols - 4 * half < 4 ? ncols - 4 * half : 4;
-    if (nn > 0) {
-      f32x4 block[4];
-      zero<4>(block);
-      mma(block, src, ld, W, q0, nq, NT, n0 + 4 * half, nn, m, lane);
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) racc[4 * half + ni] += block[ni];
-    }
-  }
-}
-
-struct Keep {
-  bool on;
-  uint64_t seed, stream0, thr;
-  float scale;
-  __device__ __forceinline__ float operator()(float v, int site, uint64_t u) const {
-    if (!on) return v;
-    return lmx_gait_keep(seed, stream0 + (uint64_t)site, u, thr) ? v * scale : 0.f;
-  }
-};
-
-// dst = LN(src) on the 16 rows of tile m (dst may be src): one row per 16-lane group, two passes.  `out` (global, may be null) receives
-// the rows 0 .. N - 1 as [N][D].
-__device__ __forceinline__ void layer_norm(const float* src, float* dst, const float* __restrict__ gam, const float* __restrict__ bet, int D, int N,
-                                           int m, int lane, float* out) {
-  const int r = lane & 15, g = lane >> 4;
-  float gg[8], bb[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = r + 16 * j;
-    gg[j] = c < D ? gam[c] : 0.f;
-    bb[j] = c < D ? bet[c] : 0.f;
-  }
-  const float inv = (float)D;
-  for (int rr = 0; rr < 4; ++rr) {
-    const int t = m * 16 + 4 * rr + g;
-    float v[8], sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      v[j] = r + 16 * j < D ? src[t * LD + r + 16 * j] : 0.f;
-      sum += v[j];
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
-    const float mean = sum / inv;
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (r + 16 * j < D) ss += (v[j] - mean) * (v[j] - mean);
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) ss += __shfl_xor(ss, o, 64);
-    const float rstd = 1.0f / sqrtf(ss / inv + 1e-5f);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = r + 16 * j;
-      if (c < D) {
-        const float y = (v[j] - mean) * rstd * gg[j] + bb[j];
-        dst[t * LD + c] = y;
-        if (out && t < N) out[(size_t)t * D + c] = y;
-      }
-    }
-  }
 }
 
 // racc = concat_i( drop_site( softmax(s) )_i v_i ) Wo^T over the rows of `src` [.][LD], the bias of out_proj left to the caller; the keys
@@ -277,7 +191,7 @@ __device__ __forceinline__ void attention(f32x4 (&racc)[8], const float* src, fl
         }
     }
     __syncthreads();  // every wave has read K and V of this head
-    if (act) mma_cols(racc, ub, LD, out_w, hd * NQ, NQ, NTD, 0, NTD, m, lane);  // the head's share of out_proj as a block of its own
+    if (act) mma_cols<mma>(racc, ub, LD, out_w, hd * NQ, NQ, NTD, 0, NTD, m, lane);  // the head's share of out_proj as a block of its own
     __syncthreads();  // ... and its own rows of the output, before the next head's q | k | v land in U
   }
 }
@@ -355,7 +269,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
   if (act) {
     const int NTI = DI >> 4;
     zero<8>(racc);
-    mma_cols(racc, ab, LD, a.w.in_w, 0, (F + 15) >> 4, NTI, 0, NTI, m, lane);
+    mma_cols<mma>(racc, ab, LD, a.w.in_w, 0, (F + 15) >> 4, NTI, 0, NTI, m, lane);
 #pragma unroll
     for (int ni = 0; ni < 8; ++ni)
       if (ni < NTI) {
@@ -407,7 +321,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
   for (int l = 0; l < L; ++l) {
     // ---- message passing --------------------------------------------------------------------------------------------------------------
     if (act) {
-      layer_norm(hb, ab, a.w.ln1_g[l], a.w.ln1_b[l], D, N, m, lane, nullptr);
+      layer_norm<0>(hb, ab, a.w.ln1_g[l], a.w.ln1_b[l], D, N, m, lane, keep, -1, nullptr);
       wave_fence();
       // Bx | Dx | Ex of the wave's rows to the slice, then Ax over the rows of a that the products have read
       for (int nc = NTD; nc < 4 * NTD; nc += 4) {
@@ -428,7 +342,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
           }
       }
       zero<8>(racc);
-      mma_cols(racc, ab, LD, a.w.abde_w[l], 0, NTD, 4 * NTD, 0, NTD, m, lane);
+      mma_cols<mma>(racc, ab, LD, a.w.abde_w[l], 0, NTD, 4 * NTD, 0, NTD, m, lane);
       wave_fence();
 #pragma unroll
       for (int ni = 0; ni < 8; ++ni)
@@ -480,7 +394,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
           }
           wave_fence();
           zero<8>(racc);
-          mma_cols(racc, ub, LD, a.w.ee2_w, 0, D2 >> 4, NTD, 0, NTD, m, lane);
+          mma_cols<mma>(racc, ub, LD, a.w.ee2_w, 0, D2 >> 4, NTD, 0, NTD, m, lane);
           wave_fence();
 #pragma unroll
           for (int ni = 0; ni < 8; ++ni)
@@ -491,7 +405,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
               for (int e = 0; e < 4; ++e) ub[(R0 + 4 * g + e) * LD + c] = racc[ni][e] + b;
             }
           wave_fence();
-          layer_norm(ub, ub, a.w.ee_g, a.w.ee_beta, D, 0, m, lane, nullptr);
+          layer_norm<0>(ub, ub, a.w.ee_g, a.w.ee_beta, D, 0, m, lane, keep, -1, nullptr);
         } else {
           for (int i = lane; i < 16 * D; i += 64) {
             const int j = i / D, c = i % D, p = p0 + j;
@@ -501,7 +415,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
         }
         wave_fence();
         zero<8>(racc);
-        mma_cols(racc, ub, LD, a.w.c_w[l], 0, NTD, NTD, 0, NTD, m, lane);  // Ce
+        mma_cols<mma>(racc, ub, LD, a.w.c_w[l], 0, NTD, NTD, 0, NTD, m, lane);  // Ce
         wave_fence();
         // the gate and the messages of the tile
 #pragma unroll
@@ -561,7 +475,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
                 }
             }
             wave_fence();
-            mma_cols(uacc, ub, LD, a.w.eu1_w[l], part * NTD, NTD, NTD, 0, NTD, m, lane);
+            mma_cols<mma>(uacc, ub, LD, a.w.eu1_w[l], part * NTD, NTD, NTD, 0, NTD, m, lane);
           }
           wave_fence();
 #pragma unroll
@@ -574,7 +488,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
             }
           wave_fence();
           zero<8>(racc);
-          mma_cols(racc, ub, LD, a.w.eu2_w[l], 0, NTD, NTD, 0, NTD, m, lane);
+          mma_cols<mma>(racc, ub, LD, a.w.eu2_w[l], 0, NTD, NTD, 0, NTD, m, lane);
 #pragma unroll
           for (int ni = 0; ni < 8; ++ni)
             if (ni < NTD) {
@@ -615,7 +529,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
         }
       }
       wave_fence();
-      layer_norm(hb, ab, a.w.ln2_g[l], a.w.ln2_b[l], D, N, m, lane, nullptr);
+      layer_norm<0>(hb, ab, a.w.ln2_g[l], a.w.ln2_b[l], D, N, m, lane, keep, -1, nullptr);
     }
     __syncthreads();
     // ---- global attention -------------------------------------------------------------------------------------------------------------
@@ -636,14 +550,14 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
           }
         }
       wave_fence();
-      layer_norm(ub, ub, a.w.lna_g[l], a.w.lna_b[l], D, N, m, lane, nullptr);
+      layer_norm<0>(ub, ub, a.w.lna_g[l], a.w.lna_b[l], D, N, m, lane, keep, -1, nullptr);
       wave_fence();
       for (int i = lane; i < 16 * D; i += 64) {
         const int t = R0 + i / D, c = i % D;
         if (t < N) hb[t * LD + c] += ub[t * LD + c] - ab[t * LD + c];
       }
       wave_fence();
-      layer_norm(hb, ab, a.w.ln3_g[l], a.w.ln3_b[l], D, N, m, lane, nullptr);
+      layer_norm<0>(hb, ab, a.w.ln3_g[l], a.w.ln3_b[l], D, N, m, lane, keep, -1, nullptr);
       wave_fence();
       // ---- the FFN, 64 hidden columns at a time through U; fc2 accumulates over the chunks ---------------------------------------------
       zero<8>(racc);
@@ -668,7 +582,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
             }
           }
         wave_fence();  // the chunk is read by the wave that wrote it
-        mma_cols(racc, ub, LD, a.w.ff2_w[l], n0f, nn, NTD, 0, NTD, m, lane);
+        mma_cols<mma>(racc, ub, LD, a.w.ff2_w[l], n0f, nn, NTD, 0, NTD, m, lane);
         wave_fence();
       }
 #pragma unroll
@@ -689,7 +603,7 @@ __global__ __launch_bounds__(NTH) void gnn_forward_kernel(const GnnArgs a) {
 
   // ---- the heads on t = LN(h; final_norm) in tile a --------------------------------------------------------------------------------------
   if (act) {
-    layer_norm(hb, ab, a.w.lnf_g, a.w.lnf_b, D, N, m, lane, a.trunk ? a.trunk + ((size_t)n0 * Smax + (size_t)sample * N) * D : nullptr);
+    layer_norm<0>(hb, ab, a.w.lnf_g, a.w.lnf_b, D, N, m, lane, keep, -1, a.trunk ? a.trunk + ((size_t)n0 * Smax + (size_t)sample * N) * D : nullptr);
     wave_fence();
     const int NTP = D2 >> 4;
     for (int which = train ? 1 : 0; which < 2; ++which) {  // 0: the attention pool's scores (eval mode), 1: the node head

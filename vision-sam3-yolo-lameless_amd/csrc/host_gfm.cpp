@@ -2,7 +2,8 @@
 // temporal edges, degrees, shortest-path indices, the winning edge per pair), the configuration and call checks both forwards share,
 // and the whole forward in plain C++ (f32, sequential sums, no contraction: the Makefile builds this file with -ffp-contract=off) with
 // the keep bits of gait.h.  No HIP here: it makes the service testable without a GPU.  The device forward is csrc/gfm.hip; both read
-// the weights of gfm.h.
+// the weights of gfm.h.  What this file shares with host_gnn.cpp (the batch checks, the kNN and temporal edges, the plain layers) is
+// in graph.h.
 #include <string.h>
 
 #include <algorithm>
@@ -10,6 +11,9 @@
 #include <vector>
 
 #include "gfm.h"
+#include "graph.h"
+
+using namespace lmx_graph;
 
 int lmx_gfm_check_config(const char* who, const lmx_gfm_weights_t* w, bool pointers) {
   GAIT_REQUIRE(w != nullptr, "%s: null weights", who);
@@ -46,28 +50,18 @@ int lmx_gfm_check_config(const char* who, const lmx_gfm_weights_t* w, bool point
 }
 
 int lmx_gfm_check_call(const char* who, const lmx_gfm_graphs_t* g, int S, double p, bool eval_outputs, int64_t* nodes, int64_t* cells, int* max_n) {
-  GAIT_REQUIRE(g != nullptr, "%s: null graphs", who);
-  GAIT_REQUIRE(g->n >= 0, "%s: n = %d graphs", who, g->n);
-  GAIT_REQUIRE(S == 0 || (S >= 2 && S <= 65535), "%s: S %d (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)", who, S);
-  GAIT_REQUIRE(S == 0 || (p >= 0.0 && p < 1.0), "%s: p %g outside [0, 1)", who, p);
-  GAIT_REQUIRE(!eval_outputs || S == 0, "%s: node_pred and attn_to_target are read in eval mode only, S = %d", who, S);
-  *nodes = *cells = 0;
-  *max_n = 0;
-  if (g->n == 0) return LMX_OK;
-  GAIT_REQUIRE(g->node_off_host && g->edge_off_host, "%s: null offsets", who);
-  GAIT_REQUIRE(g->node_off_host[0] == 0 && g->edge_off_host[0] == 0, "%s: offsets start at node_off %d, edge_off %d, not at 0", who,
-               g->node_off_host[0], g->edge_off_host[0]);
-  for (int i = 0; i < g->n; ++i) {
-    const int64_t N = (int64_t)g->node_off_host[i + 1] - g->node_off_host[i];
-    GAIT_REQUIRE(N >= 1 && N <= LMX_GFM_MAX_NODES, "%s: graph %d has N = %lld nodes (node_off %d .. %d), outside 1 .. %d", who, i, (long long)N,
-                 g->node_off_host[i], g->node_off_host[i + 1], LMX_GFM_MAX_NODES);
-    GAIT_REQUIRE(g->edge_off_host[i + 1] >= g->edge_off_host[i], "%s: edge_off descends at graph %d (%d after %d)", who, i, g->edge_off_host[i + 1],
-                 g->edge_off_host[i]);
-    *cells += N * N;
-    if (N > *max_n) *max_n = (int)N;
-  }
-  *nodes = g->node_off_host[g->n];
-  return LMX_OK;
+  *cells = 0;
+  return lmx_graph_check_call(
+      who, g, S, p, LMX_GFM_MAX_NODES,
+      [&] {
+        GAIT_REQUIRE(!eval_outputs || S == 0, "%s: node_pred and attn_to_target are read in eval mode only, S = %d", who, S);
+        return LMX_OK;
+      },
+      [&](int, int64_t N, int64_t) {
+        *cells += N * N;
+        return LMX_OK;
+      },
+      nodes, max_n);
 }
 
 extern "C" int lmx_h_gfm_graph(const float* emb, const float* ts, int N, int E, int k, int max_degree, int max_spd, int32_t* edges, float* edge_attr,
@@ -81,46 +75,9 @@ extern "C" int lmx_h_gfm_graph(const float* emb, const float* ts, int N, int E, 
   k = std::min(k, N - 1);
   const bool no_edges = N * k + (ts ? 2 * (N - 1) : 0) == 0;  // then the two edge arrays may be absent
   GAIT_REQUIRE(emb && ((edges && edge_attr) || no_edges) && n_edges && deg_in && deg_out && idx && win, "%s: null pointer", who);
-  int ne = 0;
-  auto add = [&](int src, int dst, float weight, float knn) {
-    edges[2 * ne] = src, edges[2 * ne + 1] = dst;
-    edge_attr[3 * ne] = weight, edge_attr[3 * ne + 1] = knn, edge_attr[3 * ne + 2] = 1.0f - knn;
-    ++ne;
-  };
-  if (k > 0) {
-    std::vector<double> unit((size_t)N * E), sim((size_t)N);
-    for (int i = 0; i < N; ++i) {
-      double ss = 0.0;
-      for (int c = 0; c < E; ++c) ss += (double)emb[(size_t)i * E + c] * (double)emb[(size_t)i * E + c];
-      const double norm = sqrt(ss) + 1e-8;
-      for (int c = 0; c < E; ++c) unit[(size_t)i * E + c] = (double)emb[(size_t)i * E + c] / norm;
-    }
-    std::vector<int> order((size_t)N - 1);
-    for (int i = 0; i < N; ++i) {
-      int m = 0;
-      for (int j = 0; j < N; ++j) {
-        if (j == i) continue;
-        double s = 0.0;
-        for (int c = 0; c < E; ++c) s += unit[(size_t)i * E + c] * unit[(size_t)j * E + c];
-        sim[j] = s;
-        order[m++] = j;
-      }
-      // ascending similarity, exact ties to the lower index first: the last k are the neighbours
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sim[a] < sim[b]; });
-      for (int q = N - 1 - k; q < N - 1; ++q) add(i, order[q], (float)std::max(0.0, sim[order[q]]), 1.0f);
-    }
-  }
-  if (ts && N > 1) {
-    std::vector<int> order((size_t)N);
-    for (int i = 0; i < N; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ts[a] < ts[b]; });
-    for (int q = 0; q + 1 < N; ++q) {
-      const int a = order[q], b = order[q + 1];
-      const float weight = (float)exp(-fabs((double)ts[b] - (double)ts[a]) / 86400.0);
-      add(a, b, weight, 0.0f);
-      add(b, a, weight, 0.0f);
-    }
-  }
+  // kNN edges weigh max(0, sim), temporal ones exp(-|dt| / a day)
+  const int ne = lmx_graph_edges(
+      emb, ts, N, E, k, [](double sim) { return (float)std::max(0.0, sim); }, [](double dt) { return (float)exp(-dt / 86400.0); }, edges, edge_attr);
   *n_edges = ne;
   std::vector<int> din((size_t)N, 0), dout((size_t)N, 0);
   std::vector<uint8_t> adj((size_t)N * N, 0);
@@ -155,48 +112,6 @@ extern "C" int lmx_h_gfm_graph(const float* emb, const float* ts, int N, int E, 
 }
 
 namespace {
-
-// a packed linear layer [K -> NP] as the plain matrix [N][K]: the forward reads every weight once per row, so it unpacks them once per call
-std::vector<float> unpack(const float* w, int K, int N, int NP) {
-  std::vector<float> out((size_t)N * K);
-  for (int o = 0; o < N; ++o)
-    for (int c = 0; c < K; ++c) out[(size_t)o * K + c] = w[lmx_gfm_packed_index(o, c, K, NP)];
-  return out;
-}
-
-// out[t][o] = b[o] + sum over c (ascending) of W[o][c] * in[t][c], W plain [N][K]
-void linear(const float* in, int ld_in, int K, float* out, int ld_out, int N, const float* w, const float* b, int T) {
-  for (int t = 0; t < T; ++t)
-    for (int o = 0; o < N; ++o) {
-      float s = b[o];
-      const float* wr = w + (size_t)o * K;
-      for (int c = 0; c < K; ++c) s += wr[c] * in[(size_t)t * ld_in + c];
-      out[(size_t)t * ld_out + o] = s;
-    }
-}
-
-// out[o] = b[o] + sum over c (ascending) of Wt[c][o] * in[c]
-void linear_t(const float* in, int K, float* out, int N, const float* wt, const float* b) {
-  for (int o = 0; o < N; ++o) {
-    float s = b[o];
-    for (int c = 0; c < K; ++c) s += wt[(size_t)c * N + o] * in[c];
-    out[o] = s;
-  }
-}
-
-void layer_norm(const float* in, float* out, const float* g, const float* b, int T, int D) {
-  for (int t = 0; t < T; ++t) {
-    const float* x = in + (size_t)t * D;
-    float sum = 0.0f, ss = 0.0f;
-    for (int c = 0; c < D; ++c) sum += x[c];
-    const float mean = sum / (float)D;
-    for (int c = 0; c < D; ++c) ss += (x[c] - mean) * (x[c] - mean);
-    const float rstd = 1.0f / sqrtf(ss / (float)D + 1e-5f);
-    for (int c = 0; c < D; ++c) out[(size_t)t * D + c] = (x[c] - mean) * rstd * g[c] + b[c];
-  }
-}
-
-inline float gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 // One attention (qkv_w: the heads' plain [3 dh][D] matrices one after the other, out_w plain [D][D]) over R rows of `in` (R = N: the graph attention, rows are nodes; R = N + 1: the virtual-node attention, row 0 is the
 // virtual node and the bias has a zero row and column in front).  y = concat_i(drop_site(softmax(s))_i v_i) Wo^T + bo, no dropout on y.
@@ -259,17 +174,17 @@ extern "C" int lmx_h_gfm_forward(const lmx_gfm_weights_t* w, const lmx_gfm_graph
   auto heads = [&](const float* packed) {
     std::vector<float> out;
     for (int hd = 0; hd < H; ++hd) {
-      const std::vector<float> one = unpack(packed + hd * head_floats, D, 3 * dh, 3 * dh);
+      const std::vector<float> one = unpack(packed + hd * head_floats, D, 3 * dh);
       out.insert(out.end(), one.begin(), one.end());
     }
     return out;
   };
-  const std::vector<float> in_w = unpack(w->in_w, F, D, D), time_w = unpack(w->time_w, D, D, D), pool1_w = unpack(w->pool1_w, D, PD, PD),
-                           nh1_w = unpack(w->nh1_w, D, PD, PD);
+  const std::vector<float> in_w = unpack(w->in_w, F, D), time_w = unpack(w->time_w, D, D), pool1_w = unpack(w->pool1_w, D, PD),
+                           nh1_w = unpack(w->nh1_w, D, PD);
   std::vector<std::vector<float>> qkv_w, out_w, ff1_w, ff2_w, vqkv_w, vout_w;
   for (int l = 0; l < L; ++l) {
-    qkv_w.push_back(heads(w->qkv_w[l])), out_w.push_back(unpack(w->out_w[l], D, D, D)), ff1_w.push_back(unpack(w->ff1_w[l], D, FF, FF));
-    ff2_w.push_back(unpack(w->ff2_w[l], FF, D, D)), vqkv_w.push_back(heads(w->vqkv_w[l])), vout_w.push_back(unpack(w->vout_w[l], D, D, D));
+    qkv_w.push_back(heads(w->qkv_w[l])), out_w.push_back(unpack(w->out_w[l], D, D)), ff1_w.push_back(unpack(w->ff1_w[l], D, FF));
+    ff2_w.push_back(unpack(w->ff2_w[l], FF, D)), vqkv_w.push_back(heads(w->vqkv_w[l])), vout_w.push_back(unpack(w->vout_w[l], D, D));
   }
   int64_t moff = 0;
   for (int i = 0; i < g->n; ++i) {
@@ -314,12 +229,12 @@ extern "C" int lmx_h_gfm_forward(const lmx_gfm_weights_t* w, const lmx_gfm_graph
     for (int s = 0; s < Smax; ++s) {
       const LmxGaitDrop drop(S, seeds, i, p, s, lmx_gfm_n_sites(L));
       linear(g->x + (size_t)n0 * F, F, F, y.data(), D, D, in_w.data(), w->in_b, N);
-      layer_norm(y.data(), h.data(), w->in_g, w->in_beta, N, D);
+      layer_norm(y.data(), D, h.data(), D, w->in_g, w->in_beta, N, D);
       for (int t = 0; t < N; ++t)
         for (int c = 0; c < D; ++c) h[(size_t)t * D + c] = drop(h[(size_t)t * D + c], 0, (uint64_t)t * D + c) + enc[(size_t)t * D + c];
       float vnv[LMX_GFM_MAX_D];
       for (int l = 0; l < L; ++l) {
-        layer_norm(h.data(), a.data(), w->ln1_g[l], w->ln1_b[l], N, D);
+        layer_norm(h.data(), D, a.data(), D, w->ln1_g[l], w->ln1_b[l], N, D);
         const bool col = attn && l == L - 1;
         if (col) std::fill(column.begin(), column.end(), 0.0f);
         attention(*w, a.data(), N, N, bias.data(), qkv_w[l].data(), w->qkv_b[l], out_w[l].data(), w->out_b[l], drop, 1 + 6 * l, y.data(),
@@ -328,7 +243,7 @@ extern "C" int lmx_h_gfm_forward(const lmx_gfm_weights_t* w, const lmx_gfm_graph
           for (int t = 0; t < N; ++t) attn[n0 + t] = (g->target[i] >= 0 && g->target[i] < N) ? column[t] / (float)H : 0.0f;
         for (int t = 0; t < N; ++t)
           for (int c = 0; c < D; ++c) h[(size_t)t * D + c] += drop(y[(size_t)t * D + c], 2 + 6 * l, (uint64_t)t * D + c);
-        layer_norm(h.data(), a.data(), w->ln2_g[l], w->ln2_b[l], N, D);
+        layer_norm(h.data(), D, a.data(), D, w->ln2_g[l], w->ln2_b[l], N, D);
         linear(a.data(), D, D, hid.data(), FF, FF, ff1_w[l].data(), w->ff1_b[l], N);
         for (int t = 0; t < N; ++t)
           for (int j = 0; j < FF; ++j) hid[(size_t)t * FF + j] = drop(gelu(hid[(size_t)t * FF + j]), 3 + 6 * l, (uint64_t)t * FF + j);
@@ -348,10 +263,10 @@ extern "C" int lmx_h_gfm_forward(const lmx_gfm_weights_t* w, const lmx_gfm_graph
           linear_t(y.data(), D, u1, 2 * D, w->vu1_w, w->vu1_b);
           for (int j = 0; j < 2 * D; ++j) u1[j] = gelu(u1[j]);
           linear_t(u1, 2 * D, u2, D, w->vu2_w, w->vu2_b);
-          layer_norm(u2, vnv, w->vu_g, w->vu_beta, 1, D);
+          layer_norm(u2, D, vnv, D, w->vu_g, w->vu_beta, 1, D);
         }
       }
-      layer_norm(h.data(), a.data(), w->lnf_g, w->lnf_b, N, D);
+      layer_norm(h.data(), D, a.data(), D, w->lnf_g, w->lnf_b, N, D);
       if (trunk) memcpy(trunk + ((size_t)n0 * Smax + (size_t)s * N) * D, a.data(), (size_t)N * D * sizeof(float));
       if (vn_out) memcpy(vn_out + ((size_t)i * Smax + s) * D, vnv, (size_t)D * sizeof(float));
       // the readout: mean | vn | attention pool
@@ -379,7 +294,7 @@ extern "C" int lmx_h_gfm_forward(const lmx_gfm_weights_t* w, const lmx_gfm_graph
       }
       linear_t(comb, 3 * D, r, D, w->comb_w, w->comb_b);
       for (int c = 0; c < D; ++c) r[c] = fmaxf(r[c], 0.0f);
-      layer_norm(r, rn, w->comb_g, w->comb_beta, 1, D);
+      layer_norm(r, D, rn, D, w->comb_g, w->comb_beta, 1, D);
       linear_t(rn, D, h1, D / 2, w->ph1_w, w->ph1_b);
       for (int j = 0; j < D / 2; ++j) h1[j] = drop(fmaxf(h1[j], 0.0f), 6 * L + 1, (uint64_t)j);
       linear_t(h1, D / 2, h2, D / 4, w->ph2_w, w->ph2_b);

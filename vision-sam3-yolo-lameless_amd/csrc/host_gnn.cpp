@@ -1,7 +1,8 @@
 // host_gnn.cpp — GraphGPS on the HOST (include/lmx.h "GraphGPS"): the graph builder lmx_h_gnn_graph (kNN and temporal edges, the CSR by
 // destination, the raw Laplacian and random-walk encodings in double), the configuration and call checks both forwards share, and the
 // whole live network in plain C++ (f32, sequential sums, no contraction: the Makefile builds this file with -ffp-contract=off) with the
-// keep bits of gait.h.  No HIP here: it makes the service testable without a GPU.  The device forward is csrc/gnn.hip.
+// keep bits of gait.h.  No HIP here: it makes the service testable without a GPU.  The device forward is csrc/gnn.hip.  What
+// this file shares with host_gfm.cpp (the batch checks, the kNN and temporal edges, the plain layers) is in graph.h.
 #include <string.h>
 
 #include <algorithm>
@@ -9,6 +10,9 @@
 #include <vector>
 
 #include "gnn.h"
+#include "graph.h"
+
+using namespace lmx_graph;
 
 int lmx_gnn_check_config(const char* who, const lmx_gnn_weights_t* w, bool pointers) {
   GAIT_REQUIRE(w != nullptr, "%s: null weights", who);
@@ -49,32 +53,23 @@ int lmx_gnn_check_config(const char* who, const lmx_gnn_weights_t* w, bool point
 
 int lmx_gnn_check_call(const char* who, const lmx_gnn_weights_t* w, const lmx_gnn_graphs_t* g, int S, double p, bool mc_outputs, bool eval_outputs,
                        int64_t* nodes, int* max_n, int* max_e) {
-  GAIT_REQUIRE(g != nullptr, "%s: null graphs", who);
-  GAIT_REQUIRE(g->n >= 0, "%s: n = %d graphs", who, g->n);
-  GAIT_REQUIRE(S == 0 || (S >= 2 && S <= 65535), "%s: S %d (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)", who, S);
-  GAIT_REQUIRE(S == 0 || (p >= 0.0 && p < 1.0), "%s: p %g outside [0, 1)", who, p);
-  GAIT_REQUIRE(!eval_outputs || S == 0, "%s: graph_pred, node_pred and attn_weights are read in eval mode only, S = %d", who, S);
-  GAIT_REQUIRE(!mc_outputs || S > 0, "%s: node_mc and stats are written with S > 0 only", who);
-  *nodes = 0;
-  *max_n = *max_e = 0;
-  if (g->n == 0) return LMX_OK;
-  GAIT_REQUIRE(g->node_off_host && g->edge_off_host, "%s: null offsets", who);
-  GAIT_REQUIRE(g->node_off_host[0] == 0 && g->edge_off_host[0] == 0, "%s: offsets start at node_off %d, edge_off %d, not at 0", who,
-               g->node_off_host[0], g->edge_off_host[0]);
-  for (int i = 0; i < g->n; ++i) {
-    const int64_t N = (int64_t)g->node_off_host[i + 1] - g->node_off_host[i], E = (int64_t)g->edge_off_host[i + 1] - g->edge_off_host[i];
-    GAIT_REQUIRE(N >= 1 && N <= LMX_GNN_MAX_NODES, "%s: graph %d has N = %lld nodes (node_off %d .. %d), outside 1 .. %d", who, i, (long long)N,
-                 g->node_off_host[i], g->node_off_host[i + 1], LMX_GNN_MAX_NODES);
-    GAIT_REQUIRE(E >= 0, "%s: edge_off descends at graph %d (%d after %d)", who, i, g->edge_off_host[i + 1], g->edge_off_host[i]);
-    GAIT_REQUIRE(E <= LMX_GNN_MAX_EDGES, "%s: graph %d has E = %lld edges, more than %d", who, i, (long long)E, LMX_GNN_MAX_EDGES);
-    GAIT_REQUIRE(S == 0 || N >= 2, "%s: graph %d has N = 1 node: BatchNorm has no batch statistics with S = %d", who, i, S);
-    GAIT_REQUIRE(S == 0 || w->n_layers == 1 || E >= 2, "%s: graph %d has E = %lld edges: bn_edge has no batch statistics with S = %d", who, i,
-                 (long long)E, S);
-    if (N > *max_n) *max_n = (int)N;
-    if (E > *max_e) *max_e = (int)E;
-  }
-  *nodes = g->node_off_host[g->n];
-  return LMX_OK;
+  *max_e = 0;
+  return lmx_graph_check_call(
+      who, g, S, p, LMX_GNN_MAX_NODES,
+      [&] {
+        GAIT_REQUIRE(!eval_outputs || S == 0, "%s: graph_pred, node_pred and attn_weights are read in eval mode only, S = %d", who, S);
+        GAIT_REQUIRE(!mc_outputs || S > 0, "%s: node_mc and stats are written with S > 0 only", who);
+        return LMX_OK;
+      },
+      [&](int i, int64_t N, int64_t E) {
+        GAIT_REQUIRE(E <= LMX_GNN_MAX_EDGES, "%s: graph %d has E = %lld edges, more than %d", who, i, (long long)E, LMX_GNN_MAX_EDGES);
+        GAIT_REQUIRE(S == 0 || N >= 2, "%s: graph %d has N = 1 node: BatchNorm has no batch statistics with S = %d", who, i, S);
+        GAIT_REQUIRE(S == 0 || w->n_layers == 1 || E >= 2, "%s: graph %d has E = %lld edges: bn_edge has no batch statistics with S = %d", who, i,
+                     (long long)E, S);
+        if (E > *max_e) *max_e = (int)E;
+        return LMX_OK;
+      },
+      nodes, max_n);
 }
 
 namespace {
@@ -172,46 +167,9 @@ extern "C" int lmx_h_gnn_graph(const float* emb, const double* ts, int N, int E,
   GAIT_REQUIRE(k >= 1 && k <= 5, "%s: k = %d neighbours outside 1 .. 5 (E <= 5 N + 2 (N - 1))", who, k);
   if (N <= k) k = std::max(1, N - 1);
   GAIT_REQUIRE(emb && ((edges && edge_attr && csr_edge) || N == 1) && n_edges && csr_ptr && deg && lap && rw, "%s: null pointer", who);
-  int ne = 0;
-  auto add = [&](int src, int dst, float weight, float knn) {
-    edges[2 * ne] = src, edges[2 * ne + 1] = dst;
-    edge_attr[3 * ne] = weight, edge_attr[3 * ne + 1] = knn, edge_attr[3 * ne + 2] = 1.0f - knn;
-    ++ne;
-  };
-  if (N > 1) {
-    std::vector<double> unit((size_t)N * E), sim((size_t)N);
-    for (int i = 0; i < N; ++i) {
-      double ss = 0.0;
-      for (int c = 0; c < E; ++c) ss += (double)emb[(size_t)i * E + c] * (double)emb[(size_t)i * E + c];
-      const double norm = sqrt(ss) + 1e-8;
-      for (int c = 0; c < E; ++c) unit[(size_t)i * E + c] = (double)emb[(size_t)i * E + c] / norm;
-    }
-    std::vector<int> order((size_t)N - 1);
-    for (int i = 0; i < N; ++i) {
-      int m = 0;
-      for (int j = 0; j < N; ++j) {
-        if (j == i) continue;
-        double s = 0.0;
-        for (int c = 0; c < E; ++c) s += unit[(size_t)i * E + c] * unit[(size_t)j * E + c];
-        sim[j] = s;
-        order[m++] = j;
-      }
-      // ascending similarity, exact ties to the lower index first: the last k are the neighbours
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sim[a] < sim[b]; });
-      for (int q = N - 1 - k; q < N - 1; ++q) add(i, order[q], (float)sim[order[q]], 1.0f);
-    }
-  }
-  if (ts && N > 1) {
-    std::vector<int> order((size_t)N);
-    for (int i = 0; i < N; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ts[a] < ts[b]; });
-    for (int q = 0; q + 1 < N; ++q) {
-      const int a = order[q], b = order[q + 1];
-      const float weight = (float)tanh(fabs(ts[b] - ts[a]) / 86400.0);
-      add(a, b, weight, 0.0f);
-      add(b, a, weight, 0.0f);
-    }
-  }
+  // kNN edges weigh the raw similarity, temporal ones tanh(|dt| / a day)
+  const int ne = lmx_graph_edges(
+      emb, ts, N, E, k, [](double sim) { return (float)sim; }, [](double dt) { return (float)tanh(dt / 86400.0); }, edges, edge_attr);
   *n_edges = ne;
   // the edges by destination, those of one destination in edge order
   std::vector<int> din((size_t)N, 0);
@@ -253,46 +211,6 @@ extern "C" int lmx_h_gnn_graph(const float* emb, const double* ts, int N, int E,
 
 namespace {
 
-// a packed linear layer [K -> N] as the plain matrix [N][K]
-std::vector<float> unpack(const float* w, int K, int N) {
-  std::vector<float> out((size_t)N * K);
-  for (int o = 0; o < N; ++o)
-    for (int c = 0; c < K; ++c) out[(size_t)o * K + c] = w[lmx_gnn_packed_index(o, c, K, N)];
-  return out;
-}
-
-// out[t][o] = b[o] + sum over c (ascending) of W[o][c] * in[t][c], W plain [N][K]
-void linear(const float* in, int ld_in, int K, float* out, int ld_out, int N, const float* w, const float* b, int T) {
-  for (int t = 0; t < T; ++t)
-    for (int o = 0; o < N; ++o) {
-      float s = b[o];
-      const float* wr = w + (size_t)o * K;
-      for (int c = 0; c < K; ++c) s += wr[c] * in[(size_t)t * ld_in + c];
-      out[(size_t)t * ld_out + o] = s;
-    }
-}
-
-// out[o] = b[o] + sum over c (ascending) of Wt[c][o] * in[c]
-void linear_t(const float* in, int K, float* out, int N, const float* wt, const float* b) {
-  for (int o = 0; o < N; ++o) {
-    float s = b[o];
-    for (int c = 0; c < K; ++c) s += wt[(size_t)c * N + o] * in[c];
-    out[o] = s;
-  }
-}
-
-void layer_norm(const float* in, int ld_in, float* out, int ld_out, const float* g, const float* b, int T, int D) {
-  for (int t = 0; t < T; ++t) {
-    const float* x = in + (size_t)t * ld_in;
-    float sum = 0.0f, ss = 0.0f;
-    for (int c = 0; c < D; ++c) sum += x[c];
-    const float mean = sum / (float)D;
-    for (int c = 0; c < D; ++c) ss += (x[c] - mean) * (x[c] - mean);
-    const float rstd = 1.0f / sqrtf(ss / (float)D + 1e-5f);
-    for (int c = 0; c < D; ++c) out[(size_t)t * ld_out + c] = (x[c] - mean) * rstd * g[c] + b[c];
-  }
-}
-
 // BatchNorm over the T rows of x [T][D] in place: batch statistics (mean, biased variance, two passes) or the running ones
 void batch_norm(float* x, int T, int D, bool batch, const float* g, const float* b, const float* rmean, const float* rvar) {
   for (int c = 0; c < D; ++c) {
@@ -309,7 +227,6 @@ void batch_norm(float* x, int T, int D, bool batch, const float* g, const float*
   }
 }
 
-inline float gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 inline float sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
 
 // LN_P( relu(in W1^T + b1) W2^T + b2 ) of one encoding: K raw columns -> 2P -> P, into out[t][0 .. P) with row stride ld

@@ -1,5 +1,7 @@
 """What the gait sequence models (``lmx.tcn``, ``lmx.xfm``) have in common on the Python side: the operand order of a packed
-convolution (csrc/gait.h), the seed of a clip, and the scorer that holds a network's packed tensors on the device or on the host."""
+convolution (csrc/gait.h), the seed of a clip, and the scorer that holds a network's packed tensors on the device or on the host; and
+what the two graph models (``lmx.gfm``, ``lmx.gnn``) share on top: the seed of a graph, the weights as checked f32 arrays and the node
+features of a graph."""
 import hashlib
 
 import numpy as np
@@ -23,6 +25,36 @@ def pack_conv(w):
 def clip_seed(video_id):
     """The seed of a clip: the first 8 bytes of the SHA-256 of its video_id, little-endian."""
     return int.from_bytes(hashlib.sha256(str(video_id).encode()).digest()[:8], "little")
+
+
+def graph_seed(video_id):
+    """The seed of a graph: that of a clip, from the video the graph is scored for."""
+    return clip_seed(video_id)
+
+
+def checked_arrays(weights):
+    """take(name, shape) over the weights (torch tensors or arrays): the f32 numpy array of that name, which must have that shape."""
+    f = {k: np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, np.float32) for k, v in weights.items()}
+
+    def take(name, shape):
+        a = f.get(name)
+        if a is None or a.shape != shape:
+            raise LmxError(f"pack_tensors: {name} has shape {None if a is None else a.shape}, the configuration calls for {shape}")
+        return a
+
+    return take
+
+
+def graph_features(cfg, x, embeddings, max_nodes):
+    """The node features of a graph as f32 [N, cfg.input_dim], one embedding per node; more than max_nodes nodes are refused."""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 2 or x.shape[1] != cfg.input_dim:
+        raise LmxError(f"build_graph: x must be [N, {cfg.input_dim}], got {x.shape}")
+    if x.shape[0] > max_nodes:
+        raise LmxError(f"build_graph: a graph of {x.shape[0]} nodes; one workgroup holds at most {max_nodes}")
+    if len(embeddings) != x.shape[0]:
+        raise LmxError(f"build_graph: {len(embeddings)} embeddings for {x.shape[0]} nodes")
+    return x
 
 
 class GaitScorer:

@@ -9,11 +9,10 @@ kernel reads, ``build_graph`` prepares a graph on the host (``lmx_h_gfm_graph``)
 import dataclasses
 
 import numpy as np
-import torch
 
 from . import kernels as K
 from ._lib import LmxError
-from .gait import GaitScorer, clip_seed
+from .gait import GaitScorer, checked_arrays, graph_features, graph_seed  # noqa: F401 (graph_seed: the seed of a graph)
 from .xfm import pack_linear
 
 MAX_NODES = K.GFM_MAX_NODES
@@ -56,22 +55,11 @@ class GfmConfig:
         return self
 
 
-def graph_seed(video_id):
-    """The seed of a graph: that of a clip (lmx.gait.clip_seed), from the video the graph is scored for."""
-    return clip_seed(video_id)
-
-
 def pack_tensors(cfg, weights):
     """Ordered {field of lmx_gfm_weights_t: f32 numpy array} from the weights under gfm_from_state_dict's names (torch's layouts)."""
     cfg.validate("pack_tensors")
-    f = {k: np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, np.float32) for k, v in weights.items()}
+    take = checked_arrays(weights)
     D, H, dh, L, pd = cfg.d_model, cfg.n_heads, cfg.head_dim, cfg.n_layers, cfg.pool_dim
-
-    def take(name, shape):
-        a = f.get(name)
-        if a is None or a.shape != shape:
-            raise LmxError(f"pack_tensors: {name} has shape {None if a is None else a.shape}, the configuration calls for {shape}")
-        return a
 
     def padded(w, b, w2):
         """a D -> D / 2 layer and the D / 2 -> 1 layer behind it, widened to pool_dim outputs with zeros"""
@@ -123,13 +111,7 @@ def build_graph(cfg, x, embeddings, timestamps=None, k=5):
     """A graph as GraphormerGraphBuilder(k).build_graph makes it, by lmx_h_gfm_graph's pinned rules (include/lmx.h): a dict with x f32
     [N, input_dim], timestamps (None or f32 [N]), edges int32 [E, 2], edge_attr f32 [E, 3], deg_in / deg_out uint8 [N] clamped to
     cfg.max_degree, idx uint8 [N, N] and win int32 [N, N].  More than MAX_NODES nodes are refused."""
-    x = np.ascontiguousarray(x, np.float32)
-    if x.ndim != 2 or x.shape[1] != cfg.input_dim:
-        raise LmxError(f"build_graph: x must be [N, {cfg.input_dim}], got {x.shape}")
-    if x.shape[0] > MAX_NODES:
-        raise LmxError(f"build_graph: a graph of {x.shape[0]} nodes; one workgroup holds at most {MAX_NODES}")
-    if len(embeddings) != x.shape[0]:
-        raise LmxError(f"build_graph: {len(embeddings)} embeddings for {x.shape[0]} nodes")
+    x = graph_features(cfg, x, embeddings, MAX_NODES)
     g = K.gfm_graph(embeddings, timestamps, k, cfg.max_degree, cfg.max_spd)
     g["x"] = x
     g["timestamps"] = None if timestamps is None else np.ascontiguousarray(timestamps, np.float32)

@@ -9,11 +9,10 @@ no torch arithmetic here."""
 import dataclasses
 
 import numpy as np
-import torch
 
 from . import kernels as K
 from ._lib import LmxError
-from .gait import GaitScorer, clip_seed
+from .gait import GaitScorer, checked_arrays, graph_features, graph_seed  # noqa: F401 (graph_seed: the seed of a graph)
 from .xfm import pack_linear
 
 MAX_NODES = K.GNN_MAX_NODES
@@ -55,22 +54,11 @@ class GnnConfig:
         return self
 
 
-def graph_seed(video_id):
-    """The seed of a graph: that of a clip (lmx.gait.clip_seed), from the video the graph is scored for."""
-    return clip_seed(video_id)
-
-
 def pack_tensors(cfg, weights):
     """Ordered {field of lmx_gnn_weights_t: f32 numpy array} from the weights under gnn_from_state_dict's names (torch's layouts)."""
     cfg.validate("pack_tensors")
-    f = {k: np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, np.float32) for k, v in weights.items()}
+    take = checked_arrays(weights)
     D, H, dh, L, P = cfg.d_model, cfg.n_heads, cfg.head_dim, cfg.n_layers, cfg.pe_dim
-
-    def take(name, shape):
-        a = f.get(name)
-        if a is None or a.shape != shape:
-            raise LmxError(f"pack_tensors: {name} has shape {None if a is None else a.shape}, the configuration calls for {shape}")
-        return a
 
     out = {"in_w": pack_linear(take("in.weight", (D - 2 * P, cfg.input_dim))), "in_b": take("in.bias", (D - 2 * P,))}
     for enc, k in (("lap", LAP_K), ("rw", RW_K)):
@@ -124,13 +112,7 @@ def build_graph(cfg, x, embeddings, timestamps=None, k=5):
     """A graph as GraphBuilder(k).build_graph makes it, with the two raw encodings, by lmx_h_gnn_graph's pinned rules (include/lmx.h): a
     dict with x f32 [N, input_dim], edges int32 [E, 2], edge_attr f32 [E, 3], csr_ptr, csr_edge, deg, lap f32 [N, 8], rw f32 [N, 16].
     timestamps: those of a known cow in seconds, float64 as the reference keeps them (temporal edges), or None.  More than MAX_NODES nodes are refused."""
-    x = np.ascontiguousarray(x, np.float32)
-    if x.ndim != 2 or x.shape[1] != cfg.input_dim:
-        raise LmxError(f"build_graph: x must be [N, {cfg.input_dim}], got {x.shape}")
-    if x.shape[0] > MAX_NODES:
-        raise LmxError(f"build_graph: a graph of {x.shape[0]} nodes; one workgroup holds at most {MAX_NODES}")
-    if len(embeddings) != x.shape[0]:
-        raise LmxError(f"build_graph: {len(embeddings)} embeddings for {x.shape[0]} nodes")
+    x = graph_features(cfg, x, embeddings, MAX_NODES)
     g = K.gnn_graph(embeddings, timestamps, k)
     g["x"] = x
     return g

@@ -593,6 +593,21 @@ def tcn_weights(input_dim, channels, k, head, tensors):
     return w
 
 
+def _check_samples(who, S, p):
+    """S and p as every MC-dropout forward takes them"""
+    if S == 1 or S < 0 or S > 65535:
+        raise LmxError(f"{who}: S {S} (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)")
+    if S and not 0.0 <= p < 1.0:
+        raise LmxError(f"{who}: p {p} outside [0, 1)")
+
+
+def pack_seeds(seeds):
+    """the low 64 bits of every seed (ints of either sign) as a contiguous uint64 numpy array: HOST memory, as the library reads them"""
+    import numpy as np
+
+    return np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
+
+
 def _gait_args(who, w, x, mask, seeds, n_samples, p, saliency, max_T, limit=""):
     """(n, T, S, the seeds as a uint64 numpy array or None) after the checks every forward of a gait model shares; `limit` words
     T's bound as the library does."""
@@ -608,10 +623,7 @@ def _gait_args(who, w, x, mask, seeds, n_samples, p, saliency, max_T, limit=""):
                        f"{tuple(mask.shape)} on {mask.device}")
     if saliency and S:
         raise LmxError(f"{who}: saliency is read in eval mode only, S = {S}")
-    if S == 1 or S < 0 or S > 65535:
-        raise LmxError(f"{who}: S {S} (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)")
-    if S and not 0.0 <= p < 1.0:
-        raise LmxError(f"{who}: p {p} outside [0, 1)")
+    _check_samples(who, S, p)
     if S == 0:
         return n, T, S, None
     if seeds is None:
@@ -620,7 +632,7 @@ def _gait_args(who, w, x, mask, seeds, n_samples, p, saliency, max_T, limit=""):
         if seeds.is_cuda or seeds.dtype != torch.int64:
             raise LmxError(f"{who}: seeds are HOST memory: a CPU int64 tensor, a numpy uint64 array or a list of ints")
         seeds = seeds.numpy().view(np.uint64)
-    sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64) if isinstance(seeds, (list, tuple)) else seeds)
+    sd = pack_seeds(seeds) if isinstance(seeds, (list, tuple)) else np.ascontiguousarray(seeds)
     if sd.dtype != np.uint64 or sd.shape != (n,):
         raise LmxError(f"{who}: seeds must be {n} 64-bit values, got {sd.dtype} {sd.shape}")
     return n, T, S, sd
@@ -864,67 +876,84 @@ def gfm_graph(embeddings, timestamps, k, max_degree, max_spd):
     return {"edges": edges[:n].copy(), "edge_attr": attr[:n].copy(), "deg_in": din, "deg_out": dout, "idx": idx, "win": win}
 
 
-class GfmBatch:
-    """n graphs of differing N as lmx_gfm_graphs_t wants them: nodes, edges and matrices concatenated on `device`, the two offset arrays
-    on the host.  graphs: dicts with x f32 [N, F], timestamps None or f32 [N], and gfm_graph's arrays; targets: None or one node per graph."""
+class _GraphBatch:
+    """What GfmBatch and GnnBatch share: n graphs of differing N, nodes and edges concatenated on `device`, the two offset arrays on the
+    host, and struct(), which fills _STRUCT's pointers from the attributes named in _FIELDS (None: a null pointer)."""
 
-    def __init__(self, graphs, device, targets=None):
+    def __init__(self, graphs, device):
         import numpy as np
 
         self.n, self.device = len(graphs), torch.device(device)
         self.sizes = [int(np.asarray(g["x"]).shape[0]) for g in graphs]
+        self.n_edges = [len(g["edges"]) for g in graphs]
         self.node_off = np.zeros((self.n + 1,), np.int32)
         self.edge_off = np.zeros((self.n + 1,), np.int32)
         self.node_off[1:] = np.cumsum(self.sizes)
-        self.edge_off[1:] = np.cumsum([len(g["edges"]) for g in graphs])
-        self.nodes, self.cells = int(self.node_off[-1]), int(sum(s * s for s in self.sizes))
-
-        def cat(key, dtype, tail=()):
-            parts = [np.ascontiguousarray(g[key], dtype).reshape((-1,) + tail) for g in graphs]
-            a = np.concatenate(parts, 0) if parts else np.zeros((0,) + tail, dtype)
-            if a.shape[0] == 0:
-                a = np.zeros((1,) + tail, dtype)  # a pointer the library may look at, never follow
-            return torch.from_numpy(a).to(self.device)
-
+        self.edge_off[1:] = np.cumsum(self.n_edges)
+        self.nodes, self.edges = int(self.node_off[-1]), int(self.edge_off[-1])
         F = int(np.asarray(graphs[0]["x"]).shape[1]) if graphs else 1
         self.input_dim = F
         if any(np.asarray(g["x"]).ndim != 2 or np.asarray(g["x"]).shape[1] != F for g in graphs):
-            raise LmxError("GfmBatch: every x must be [N, input_dim] with one input_dim")
-        self.x = cat("x", np.float32, (F,))
+            raise LmxError(f"{type(self).__name__}: every x must be [N, input_dim] with one input_dim")
+        self.x = self._cat([g["x"] for g in graphs], np.float32, (F,))
+
+    def _cat(self, parts, dtype, tail=()):
+        import numpy as np
+
+        parts = [np.ascontiguousarray(p, dtype).reshape((-1,) + tail) for p in parts]
+        a = np.concatenate(parts, 0) if parts else np.zeros((0,) + tail, dtype)
+        if a.shape[0] == 0:
+            a = np.zeros((1,) + tail, dtype)  # a pointer the library may look at, never follow
+        return torch.from_numpy(a).to(self.device)
+
+    def _check_entries(self, wants):
+        for key, want in wants:
+            if max(want, 1) != getattr(self, key).shape[0]:
+                raise LmxError(f"{type(self).__name__}: {key} has {getattr(self, key).shape[0]} entries, the graphs call for {want}")
+
+    def struct(self):
+        g = self._STRUCT()
+        g.n = self.n
+        g.node_off_host, g.edge_off_host = self.node_off.ctypes.data, self.edge_off.ctypes.data
+        for name in self._FIELDS:
+            t = getattr(self, name)
+            setattr(g, name, t.data_ptr() if t is not None else None)
+        return g
+
+
+class GfmBatch(_GraphBatch):
+    """n graphs of differing N as lmx_gfm_graphs_t wants them: nodes, edges and matrices concatenated on `device`, the two offset arrays
+    on the host.  graphs: dicts with x f32 [N, F], timestamps None or f32 [N], and gfm_graph's arrays; targets: None or one node per graph."""
+    _STRUCT, _FIELDS = _lib.GfmGraphs, ("x", "timestamps", "has_time", "deg_in", "deg_out", "idx", "win", "edge_attr", "target")
+
+    def __init__(self, graphs, device, targets=None):
+        import numpy as np
+
+        super().__init__(graphs, device)
+        self.cells = int(sum(s * s for s in self.sizes))
         timed = [g.get("timestamps") is not None for g in graphs]
         self.has_time = torch.from_numpy(np.array(timed + [False], np.uint8)).to(self.device) if any(timed) else None
         self.timestamps = None
         if any(timed):
             ts = [np.ascontiguousarray(g["timestamps"], np.float32) if t else np.zeros((s,), np.float32) for g, t, s in zip(graphs, timed, self.sizes)]
             self.timestamps = torch.from_numpy(np.concatenate(ts)).to(self.device)
-        self.deg_in, self.deg_out = cat("deg_in", np.uint8), cat("deg_out", np.uint8)
-        self.idx, self.win = cat("idx", np.uint8), cat("win", np.int32)
-        self.edge_attr = cat("edge_attr", np.float32, (3,))
-        for key, want in (("deg_in", self.nodes), ("deg_out", self.nodes), ("idx", self.cells), ("win", self.cells)):
-            if max(want, 1) != getattr(self, key).shape[0]:
-                raise LmxError(f"GfmBatch: {key} has {getattr(self, key).shape[0]} entries, the graphs call for {want}")
+        for key, dtype in (("deg_in", np.uint8), ("deg_out", np.uint8), ("idx", np.uint8), ("win", np.int32)):
+            setattr(self, key, self._cat([g[key] for g in graphs], dtype))
+        self.edge_attr = self._cat([g["edge_attr"] for g in graphs], np.float32, (3,))
+        self._check_entries((("deg_in", self.nodes), ("deg_out", self.nodes), ("idx", self.cells), ("win", self.cells)))
         self.target = None
         if targets is not None:
             if len(targets) != self.n:
                 raise LmxError(f"GfmBatch: {len(targets)} targets for {self.n} graphs")
             self.target = torch.from_numpy(np.array(list(targets) + [0], np.int32)).to(self.device)
 
-    def struct(self):
-        g = _lib.GfmGraphs()
-        g.n = self.n
-        g.node_off_host, g.edge_off_host = self.node_off.ctypes.data, self.edge_off.ctypes.data
-        for name in ("x", "timestamps", "has_time", "deg_in", "deg_out", "idx", "win", "edge_attr", "target"):
-            t = getattr(self, name)
-            setattr(g, name, t.data_ptr() if t is not None else None)
-        return g
 
-
-def _gfm_forward(host, w, batch, seeds, n_samples, p, node, attn, trunk, vn):
-    import numpy as np
-
-    who = "gfm_forward_host" if host else "gfm_forward"
-    if not isinstance(batch, GfmBatch):
-        raise LmxError(f"{who}: the graphs come as a GfmBatch")
+def _graph_front(model, host, w, batch, n_samples):
+    """(who, device, S) of a graph model's forward after what both check first: the batch's class, where the batch and the weights
+    live, and the feature count."""
+    who, cls = f"{model}_forward_host" if host else f"{model}_forward", GfmBatch if model == "gfm" else GnnBatch
+    if not isinstance(batch, cls):
+        raise LmxError(f"{who}: the graphs come as a {cls.__name__}")
     if host:
         if batch.device.type != "cpu" or w._device.type != "cpu":
             raise LmxError(f"{who} takes CPU tensors and CPU weights")
@@ -933,47 +962,56 @@ def _gfm_forward(host, w, batch, seeds, n_samples, p, node, attn, trunk, vn):
         dev = _dev(batch.x)
         if w._device != dev:
             raise LmxError(f"{who}: the weights are on {w._device}, the graphs are on {dev}")
-    n, S = batch.n, int(n_samples)
     if batch.n and batch.input_dim != w.input_dim:
         raise LmxError(f"{who}: x has {batch.input_dim} features, the network takes {w.input_dim}")
-    for i, s in enumerate(batch.sizes):
-        if not 1 <= s <= GFM_MAX_NODES:
-            raise LmxError(f"{who}: graph {i} has N = {s} nodes, outside 1 .. {GFM_MAX_NODES}")
-    if S == 1 or S < 0 or S > 65535:
-        raise LmxError(f"{who}: S {S} (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)")
-    if S and not 0.0 <= p < 1.0:
-        raise LmxError(f"{who}: p {p} outside [0, 1)")
-    if (node or attn) and S:
-        raise LmxError(f"{who}: node_pred and attn_to_target are read in eval mode only, S = {S}")
-    if attn and batch.target is None:
-        raise LmxError(f"{who}: attn_to_target without targets")
+    return who, dev, int(n_samples)
+
+
+def _graph_run(model, host, who, dev, w, batch, seeds, S, p, outs, ws_bytes):
+    """The shared back: one seed per graph, then lmx_h_<model>_forward (host) or lmx_k_<model>_forward with a workspace of
+    ws_bytes(lib) bytes on torch's stream; outs: the output tensors (or None) in the order of the C signature."""
     sd = None
     if S:
         if seeds is None:
             raise LmxError(f"{who}: S = {S} needs one seed per graph")
-        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
-        if sd.shape != (n,):
-            raise LmxError(f"{who}: seeds must be {n} 64-bit values, got {sd.shape}")
-    smax, D = max(S, 1), w.d_model
+        sd = pack_seeds(seeds)
+        if sd.shape != (batch.n,):
+            raise LmxError(f"{who}: seeds must be {batch.n} 64-bit values, got {sd.shape}")
+    lib, g, name = _lib.load(), batch.struct(), f"lmx_{'h' if host else 'k'}_{model}_forward"
+    args = [C.byref(w), C.byref(g), C.c_void_p(sd.ctypes.data if sd is not None else 0), S, float(p)] + [_ptr(t) for t in outs]
+    if not host:
+        ws = torch.empty((max(int(ws_bytes(lib)), 16) // 16 + 1, 2), dtype=torch.int64, device=dev)
+        args += [_ptr(ws), _stream(dev)]
+    check(getattr(lib, name)(*args), name)
+
+
+def _trunk_views(tr, batch, smax, D):
+    """graph g's [max(S, 1), N_g, D] of the trunk buffer (None without one)"""
+    if tr is None:
+        return None
+    return [tr[int(batch.node_off[i]) * smax:int(batch.node_off[i + 1]) * smax].reshape(smax, batch.sizes[i], D) for i in range(batch.n)]
+
+
+def _gfm_forward(host, w, batch, seeds, n_samples, p, node, attn, trunk, vn):
+    who, dev, S = _graph_front("gfm", host, w, batch, n_samples)
+    for i, s in enumerate(batch.sizes):
+        if not 1 <= s <= GFM_MAX_NODES:
+            raise LmxError(f"{who}: graph {i} has N = {s} nodes, outside 1 .. {GFM_MAX_NODES}")
+    _check_samples(who, S, p)
+    if (node or attn) and S:
+        raise LmxError(f"{who}: node_pred and attn_to_target are read in eval mode only, S = {S}")
+    if attn and batch.target is None:
+        raise LmxError(f"{who}: attn_to_target without targets")
+    n, nodes, smax, D = batch.n, batch.nodes, max(S, 1), w.d_model
 
     def buf(*shape):
         return torch.empty(shape, dtype=torch.float32, device=dev)
 
-    pred, stats = buf(n, smax), buf(n, 2)
-    npred, at = (buf(batch.nodes) if node else None), (buf(batch.nodes) if attn else None)
-    tr, vv = (buf(batch.nodes * smax, D) if trunk else None), (buf(n, smax, D) if vn else None)
-    lib, g = _lib.load(), batch.struct()
-    args = [C.byref(w), C.byref(g), C.c_void_p(sd.ctypes.data if sd is not None else 0), S, float(p), _ptr(pred), _ptr(stats), _ptr(npred), _ptr(at),
-            _ptr(tr), _ptr(vv)]
-    if host:
-        check(lib.lmx_h_gfm_forward(*args), "lmx_h_gfm_forward")
-    else:
-        ws = torch.empty((max(int(lib.lmx_gfm_workspace_bytes(n, batch.cells, w.n_heads)), 16) // 16 + 1, 2), dtype=torch.int64, device=dev)
-        check(lib.lmx_k_gfm_forward(*args, _ptr(ws), _stream(dev)), "lmx_k_gfm_forward")
-    trunks = None
-    if trunk:  # graph g's [max(S, 1), N_g, D]
-        trunks = [tr[int(batch.node_off[i]) * smax:int(batch.node_off[i + 1]) * smax].reshape(smax, batch.sizes[i], D) for i in range(n)]
-    return pred, stats, npred, at, trunks, vv
+    outs = [buf(n, smax), buf(n, 2), buf(nodes) if node else None, buf(nodes) if attn else None, buf(nodes * smax, D) if trunk else None,
+            buf(n, smax, D) if vn else None]
+    _graph_run("gfm", host, who, dev, w, batch, seeds, S, p, outs, lambda lib: lib.lmx_gfm_workspace_bytes(n, batch.cells, w.n_heads))
+    pred, stats, npred, at, tr, vv = outs
+    return pred, stats, npred, at, _trunk_views(tr, batch, smax, D), vv
 
 
 def gfm_forward(w, batch, seeds, n_samples, p, node=False, attn=False, trunk=False, vn=False):
@@ -1100,78 +1138,30 @@ def gnn_laplacian(edges, N):
     return lam, vec
 
 
-class GnnBatch:
+class GnnBatch(_GraphBatch):
     """n graphs of differing N as lmx_gnn_graphs_t wants them: nodes and edges concatenated on `device`, the two offset arrays on the
     host.  graphs: dicts with x f32 [N, F] and gnn_graph's arrays."""
+    _STRUCT, _FIELDS = _lib.GnnGraphs, ("x", "lap", "rw", "edge_src", "edge_dst", "edge_attr", "csr_ptr", "csr_edge", "deg")
 
     def __init__(self, graphs, device):
         import numpy as np
 
-        self.n, self.device = len(graphs), torch.device(device)
-        self.sizes = [int(np.asarray(g["x"]).shape[0]) for g in graphs]
-        self.n_edges = [len(g["edges"]) for g in graphs]
-        self.node_off = np.zeros((self.n + 1,), np.int32)
-        self.edge_off = np.zeros((self.n + 1,), np.int32)
-        self.node_off[1:] = np.cumsum(self.sizes)
-        self.edge_off[1:] = np.cumsum(self.n_edges)
-        self.nodes, self.edges = int(self.node_off[-1]), int(self.edge_off[-1])
+        super().__init__(graphs, device)
         self.max_n, self.max_e = max(self.sizes, default=0), max(self.n_edges, default=0)
-        F = int(np.asarray(graphs[0]["x"]).shape[1]) if graphs else 1
-        self.input_dim = F
-        if any(np.asarray(g["x"]).ndim != 2 or np.asarray(g["x"]).shape[1] != F for g in graphs):
-            raise LmxError("GnnBatch: every x must be [N, input_dim] with one input_dim")
-
-        def cat(parts, dtype, tail=()):
-            parts = [np.ascontiguousarray(p, dtype).reshape((-1,) + tail) for p in parts]
-            a = np.concatenate(parts, 0) if parts else np.zeros((0,) + tail, dtype)
-            if a.shape[0] == 0:
-                a = np.zeros((1,) + tail, dtype)  # a pointer the library may look at, never follow
-            return torch.from_numpy(a).to(self.device)
-
-        self.x = cat([g["x"] for g in graphs], np.float32, (F,))
-        self.lap = cat([g["lap"] for g in graphs], np.float32, (GNN_LAP_K,))
-        self.rw = cat([g["rw"] for g in graphs], np.float32, (GNN_RW_K,))
-        self.edge_src = cat([np.asarray(g["edges"], np.int32).reshape(-1, 2)[:, 0] for g in graphs], np.int32)
-        self.edge_dst = cat([np.asarray(g["edges"], np.int32).reshape(-1, 2)[:, 1] for g in graphs], np.int32)
-        self.edge_attr = cat([g["edge_attr"] for g in graphs], np.float32, (3,))
-        self.csr_ptr = cat([g["csr_ptr"] for g in graphs], np.int32)
-        self.csr_edge = cat([g["csr_edge"] for g in graphs], np.int32)
-        self.deg = cat([g["deg"] for g in graphs], np.int32)
-        for key, want in (("lap", self.nodes), ("rw", self.nodes), ("deg", self.nodes), ("csr_ptr", self.nodes + self.n), ("csr_edge", self.edges),
-                          ("edge_attr", self.edges)):
-            if max(want, 1) != getattr(self, key).shape[0]:
-                raise LmxError(f"GnnBatch: {key} has {getattr(self, key).shape[0]} entries, the graphs call for {want}")
-
-    def struct(self):
-        g = _lib.GnnGraphs()
-        g.n = self.n
-        g.node_off_host, g.edge_off_host = self.node_off.ctypes.data, self.edge_off.ctypes.data
-        for name in ("x", "lap", "rw", "edge_src", "edge_dst", "edge_attr", "csr_ptr", "csr_edge", "deg"):
-            setattr(g, name, getattr(self, name).data_ptr())
-        return g
+        self.lap = self._cat([g["lap"] for g in graphs], np.float32, (GNN_LAP_K,))
+        self.rw = self._cat([g["rw"] for g in graphs], np.float32, (GNN_RW_K,))
+        self.edge_src = self._cat([np.asarray(g["edges"], np.int32).reshape(-1, 2)[:, 0] for g in graphs], np.int32)
+        self.edge_dst = self._cat([np.asarray(g["edges"], np.int32).reshape(-1, 2)[:, 1] for g in graphs], np.int32)
+        self.edge_attr = self._cat([g["edge_attr"] for g in graphs], np.float32, (3,))
+        for key in ("csr_ptr", "csr_edge", "deg"):
+            setattr(self, key, self._cat([g[key] for g in graphs], np.int32))
+        self._check_entries((("lap", self.nodes), ("rw", self.nodes), ("deg", self.nodes), ("csr_ptr", self.nodes + self.n),
+                             ("csr_edge", self.edges), ("edge_attr", self.edges)))
 
 
 def _gnn_forward(host, w, batch, seeds, n_samples, p, trunk):
-    import numpy as np
-
-    who = "gnn_forward_host" if host else "gnn_forward"
-    if not isinstance(batch, GnnBatch):
-        raise LmxError(f"{who}: the graphs come as a GnnBatch")
-    if host:
-        if batch.device.type != "cpu" or w._device.type != "cpu":
-            raise LmxError(f"{who} takes CPU tensors and CPU weights")
-        dev = torch.device("cpu")
-    else:
-        dev = _dev(batch.x)
-        if w._device != dev:
-            raise LmxError(f"{who}: the weights are on {w._device}, the graphs are on {dev}")
-    n, S = batch.n, int(n_samples)
-    if batch.n and batch.input_dim != w.input_dim:
-        raise LmxError(f"{who}: x has {batch.input_dim} features, the network takes {w.input_dim}")
-    if S == 1 or S < 0 or S > 65535:
-        raise LmxError(f"{who}: S {S} (0: eval mode; 2 .. 65535 samples; the standard deviation of 1 is undefined)")
-    if S and not 0.0 <= p < 1.0:
-        raise LmxError(f"{who}: p {p} outside [0, 1)")
+    who, dev, S = _graph_front("gnn", host, w, batch, n_samples)
+    _check_samples(who, S, p)
     for i, (s, e) in enumerate(zip(batch.sizes, batch.n_edges)):
         if not 1 <= s <= GNN_MAX_NODES:
             raise LmxError(f"{who}: graph {i} has N = {s} nodes, outside 1 .. {GNN_MAX_NODES}")
@@ -1179,34 +1169,16 @@ def _gnn_forward(host, w, batch, seeds, n_samples, p, trunk):
             raise LmxError(f"{who}: graph {i} has E = {e} edges, more than {GNN_MAX_EDGES}")
         if S and s < 2:
             raise LmxError(f"{who}: graph {i} has N = 1 node: BatchNorm has no batch statistics with S = {S}")
-    sd = None
-    if S:
-        if seeds is None:
-            raise LmxError(f"{who}: S = {S} needs one seed per graph")
-        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
-        if sd.shape != (n,):
-            raise LmxError(f"{who}: seeds must be {n} 64-bit values, got {sd.shape}")
-    smax, D = max(S, 1), w.d_model
+    n, nodes, smax, D = batch.n, batch.nodes, max(S, 1), w.d_model
 
     def buf(*shape):
         return torch.empty(shape, dtype=torch.float32, device=dev)
 
-    mc, stats = (buf(batch.nodes, S), buf(batch.nodes, 2)) if S else (None, None)
-    gp, npred, attw = (None, None, None) if S else (buf(n), buf(batch.nodes), buf(batch.nodes))
-    tr = buf(batch.nodes * smax, D) if trunk else None
-    lib, g = _lib.load(), batch.struct()
-    args = [C.byref(w), C.byref(g), C.c_void_p(sd.ctypes.data if sd is not None else 0), S, float(p), _ptr(mc), _ptr(stats), _ptr(gp), _ptr(npred),
-            _ptr(attw), _ptr(tr)]
-    if host:
-        check(lib.lmx_h_gnn_forward(*args), "lmx_h_gnn_forward")
-    else:
-        nbytes = int(lib.lmx_gnn_workspace_bytes(n, S, batch.max_n, batch.max_e, w.d_model, w.n_layers))
-        ws = torch.empty((max(nbytes, 16) // 16 + 1, 2), dtype=torch.int64, device=dev)
-        check(lib.lmx_k_gnn_forward(*args, _ptr(ws), _stream(dev)), "lmx_k_gnn_forward")
-    trunks = None
-    if trunk:  # graph g's [max(S, 1), N_g, D]
-        trunks = [tr[int(batch.node_off[i]) * smax:int(batch.node_off[i + 1]) * smax].reshape(smax, batch.sizes[i], D) for i in range(n)]
-    return mc, stats, gp, npred, attw, trunks
+    outs = ([buf(nodes, S), buf(nodes, 2), None, None, None] if S else [None, None, buf(n), buf(nodes), buf(nodes)]) + \
+        [buf(nodes * smax, D) if trunk else None]
+    _graph_run("gnn", host, who, dev, w, batch, seeds, S, p, outs,
+               lambda lib: lib.lmx_gnn_workspace_bytes(n, S, batch.max_n, batch.max_e, w.d_model, w.n_layers))
+    return (*outs[:5], _trunk_views(outs[5], batch, smax, D))
 
 
 def gnn_forward(w, batch, seeds, n_samples, p, trunk=False):

@@ -935,6 +935,18 @@ def _vp(a):
     return C.c_void_p(0 if a is None else a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data)
 
 
+def _seeds(who, seeds, n, S, items):
+    """one 64-bit seed per clip or graph (`items`) as a uint64 numpy array; None in eval mode"""
+    from . import kernels as K
+
+    if S == 0:
+        return None
+    sd = K.pack_seeds(seeds)
+    if sd.shape != (n,):
+        raise LmxError(f"{who}: {n} {items} need {n} seeds, got {sd.shape}")
+    return sd
+
+
 class _NativeGait(_NativeHandle):
     """What NativeTcn and NativeXfm do alike: lmx_<model>_open_host(path, max_clips, max_samples), the checks of a series (and of a
     mask) on the device and on the host, one seed per clip, and the outputs of a call."""
@@ -947,12 +959,7 @@ class _NativeGait(_NativeHandle):
         return (int(max_batch), self._max_samples)
 
     def _seeds(self, seeds, n, S, what):
-        if S == 0:
-            return None
-        sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
-        if sd.shape != (n,):
-            raise LmxError(f"{type(self).__name__}.{what}: {n} clips need {n} seeds, got {sd.shape}")
-        return sd
+        return _seeds(f"{type(self).__name__}.{what}", seeds, n, S, "clips")
 
     def _args(self, what, x, mask, seeds, n_samples, saliency):
         """(x, mask, n, T, S, seeds, pred, stats, saliency or None) of one call: tensors on the handle's device for "score", numpy
@@ -1023,42 +1030,52 @@ class NativeXfm(_NativeGait):
         return stats[:, 0], stats[:, 1], pred, sal
 
 
-class NativeGfm(_NativeHandle):
-    """lmx_gfm_open_host(path, max_graphs, max_nodes_total, max_samples) on `device` (default: torch's current device): the graph
-    transformer from its weight image.  score / score_host give the bits of lmx.gfm.GfmScorer (tests/test_gpu_gfm.py)."""
-    _PREFIX, _INFO = "lmx_gfm_", GfmInfo
+class _NativeGraph(_NativeHandle):
+    """What NativeGfm and NativeGnn do alike: lmx_<model>_open_host(path, max_graphs, <the model's limits>), the graphs as the
+    model's batch where the call wants them, one seed per graph, and the call with the outputs in the order of the C signature."""
 
-    def __init__(self, path, max_graphs, max_nodes_total, max_samples=10, device=None):
-        self._extra = (int(max_nodes_total), int(max_samples))
+    def __init__(self, path, max_graphs, limits, device=None):
+        self._extra = tuple(int(v) for v in limits)
         super().__init__(path, max_graphs, device)
 
     def _open_args(self, max_batch):
         return (int(max_batch),) + self._extra
 
-    def _call(self, what, graphs, seeds, n_samples, targets, node):
+    def _batch(self, what, graphs, *extra):
+        """the graphs as a batch on the CPU (score_host) or on the handle's device (score)"""
         from . import kernels as K
 
-        host = what == "score_host"
-        b = graphs if isinstance(graphs, K.GfmBatch) else K.GfmBatch(graphs, "cpu" if host else self.device, targets)
-        if b.device != (torch.device("cpu") if host else self.device):
-            raise LmxError(f"NativeGfm.{what}: the graphs are on {b.device}")
-        n, S = b.n, int(n_samples)
-        sd = None
-        if S:
-            sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
-            if sd.shape != (n,):
-                raise LmxError(f"NativeGfm.{what}: {n} graphs need {n} seeds, got {sd.shape}")
+        cls, where = getattr(K, self._BATCH), torch.device("cpu") if what == "score_host" else self.device
+        b = graphs if isinstance(graphs, cls) else cls(graphs, where, *extra)
+        if b.device != where:
+            raise LmxError(f"{type(self).__name__}.{what}: the graphs are on {b.device}")
+        return b
+
+    def _run(self, what, b, seeds, S, outs):
+        sd = _seeds(f"{type(self).__name__}.{what}", seeds, b.n, S, "graphs")
+        g, name = b.struct(), self._PREFIX + what
+        args = [self._handle(), C.byref(g), _vp(sd), S] + [_vp(t) for t in outs]
+        if what == "score":
+            args.append(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        with torch.cuda.device(self.device):
+            check(getattr(self._lib, name)(*args), name)
+
+
+class NativeGfm(_NativeGraph):
+    """lmx_gfm_open_host(path, max_graphs, max_nodes_total, max_samples) on `device` (default: torch's current device): the graph
+    transformer from its weight image.  score / score_host give the bits of lmx.gfm.GfmScorer (tests/test_gpu_gfm.py)."""
+    _PREFIX, _INFO, _BATCH = "lmx_gfm_", GfmInfo, "GfmBatch"
+
+    def __init__(self, path, max_graphs, max_nodes_total, max_samples=10, device=None):
+        super().__init__(path, max_graphs, (max_nodes_total, max_samples), device)
+
+    def _call(self, what, graphs, seeds, n_samples, targets, node):
+        b, S = self._batch(what, graphs, targets), int(n_samples)
         empty = lambda *shape: torch.empty(shape, dtype=torch.float32, device=b.device)  # noqa: E731
-        pred, stats = empty(n, max(S, 1)), empty(n, 2)
+        pred, stats = empty(b.n, max(S, 1)), empty(b.n, 2)
         npred = empty(b.nodes) if node else None
         attn = empty(b.nodes) if (b.target is not None and S == 0) else None
-        g = b.struct()
-        args = [self._handle(), C.byref(g), _vp(sd), S, _vp(pred), _vp(stats), _vp(npred), _vp(attn)]
-        with torch.cuda.device(self.device):
-            if host:
-                check(self._lib.lmx_gfm_score_host(*args), "lmx_gfm_score_host")
-            else:
-                check(self._lib.lmx_gfm_score(*args, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "lmx_gfm_score")
+        self._run(what, b, seeds, S, (pred, stats, npred, attn))
         return stats[:, 0], stats[:, 1], pred, npred, attn
 
     def score(self, graphs, seeds=None, n_samples=10, targets=None, node=False):
@@ -1071,41 +1088,20 @@ class NativeGfm(_NativeHandle):
         return self._call("score_host", graphs, seeds, n_samples, targets, node)
 
 
-class NativeGnn(_NativeHandle):
+class NativeGnn(_NativeGraph):
     """lmx_gnn_open_host(path, max_graphs, max_nodes_total, max_edges_total, max_samples) on `device` (default: torch's current device):
     GraphGPS from its weight image.  score / score_host give the bits of lmx.gnn.GnnScorer (tests/test_gpu_gnn.py)."""
-    _PREFIX, _INFO = "lmx_gnn_", GnnInfo
+    _PREFIX, _INFO, _BATCH = "lmx_gnn_", GnnInfo, "GnnBatch"
 
     def __init__(self, path, max_graphs, max_nodes_total, max_edges_total, max_samples=10, device=None):
-        self._extra = (int(max_nodes_total), int(max_edges_total), int(max_samples))
-        super().__init__(path, max_graphs, device)
-
-    def _open_args(self, max_batch):
-        return (int(max_batch),) + self._extra
+        super().__init__(path, max_graphs, (max_nodes_total, max_edges_total, max_samples), device)
 
     def _call(self, what, graphs, seeds, n_samples):
-        from . import kernels as K
-
-        host = what == "score_host"
-        b = graphs if isinstance(graphs, K.GnnBatch) else K.GnnBatch(graphs, "cpu" if host else self.device)
-        if b.device != (torch.device("cpu") if host else self.device):
-            raise LmxError(f"NativeGnn.{what}: the graphs are on {b.device}")
-        n, S = b.n, int(n_samples)
-        sd = None
-        if S:
-            sd = np.ascontiguousarray(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64))
-            if sd.shape != (n,):
-                raise LmxError(f"NativeGnn.{what}: {n} graphs need {n} seeds, got {sd.shape}")
+        b, S = self._batch(what, graphs), int(n_samples)
         empty = lambda *shape: torch.empty(shape, dtype=torch.float32, device=b.device)  # noqa: E731
         mc, stats = (empty(b.nodes, S), empty(b.nodes, 2)) if S else (None, None)
-        gp, npred, attw = (None, None, None) if S else (empty(n), empty(b.nodes), empty(b.nodes))
-        g = b.struct()
-        args = [self._handle(), C.byref(g), _vp(sd), S, _vp(mc), _vp(stats), _vp(gp), _vp(npred), _vp(attw)]
-        with torch.cuda.device(self.device):
-            if host:
-                check(self._lib.lmx_gnn_score_host(*args), "lmx_gnn_score_host")
-            else:
-                check(self._lib.lmx_gnn_score(*args, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "lmx_gnn_score")
+        gp, npred, attw = (None, None, None) if S else (empty(b.n), empty(b.nodes), empty(b.nodes))
+        self._run(what, b, seeds, S, (mc, stats, gp, npred, attw))
         return mc, stats, gp, npred, attw
 
     def score(self, graphs, seeds=None, n_samples=10):
