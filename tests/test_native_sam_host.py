@@ -1,7 +1,7 @@
 """The host half of the model-level C API for SAM (include/lmx.h "MODEL level: SAM"), without a GPU:
   * the weight image lmx.native.write_sam_image writes from CPU-built SamVitEncoder / MaskDecoder objects, read back by
     lmx_sam_image_check_host (csrc/host_sam_image.cpp): the configuration, and every tensor bit for bit what the plans upload — the
-    lazily built exact-plan tensors (SamVitEncoder._split2, MaskDecoder._lin) recomputed here from the float32 parameters;
+    lazily built exact-plan tensors (SamVitEncoder._split2, MaskDecoder._x3) recomputed here from the float32 parameters;
   * corrupted images: each is LMX_EINVAL with the offending field or tensor named, and the process survives;
   * a DINO image and a YOLO image fed to the SAM reader.
 lmx_sam_resized takes a handle, and a handle needs a device: its five sizes are held to ResizeLongestSide.get_preprocess_shape in
@@ -161,7 +161,7 @@ def test_the_exporter_builds_what_the_plans_build_lazily(models, tmp_path):
     native.write_sam_image(enc, dec, fresh)
     from lmx.exact import split_rows_x3 as split
 
-    name = "mask_decoder.transformer.layers.0.self_attn.q_proj"  # what MaskDecoder._lin caches on its first use
+    name = "mask_decoder.transformer.layers.0.self_attn.q_proj"  # what MaskDecoder._x3 caches on its first use
     import torch
 
     w, b = dec._sd[name + ".weight"], dec._sd[name + ".bias"]

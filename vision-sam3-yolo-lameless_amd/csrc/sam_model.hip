@@ -8,7 +8,7 @@
 // (tests/test_gpu_native_sam.py).  What is torch glue in Python — torch.cat of the output tokens with the sparse prompt, the q / k / v
 // slices of qkv, q3[:, k].contiguous(), iou[:, 0] — is a leading dimension or a strided copy on the call's stream here.
 // An image whose encoder is Hiera runs sam_hiera_model.h's launch plan in place of the ViT's (encode_chunk branches after the resize);
-// its embedding is f16 under both plans, which the exact decoder's first lmx_k_add_bcast takes as such.
+// its embedding is f16 under both plans, which the decoder's first lmx_k_add_bcast takes as such.
 // The fused handle (fused_model.hip) keeps several passes in flight on one handle: sam_lanes.h, at the end of this file, gives it further
 // workspaces (lanes) over the same weights and the two halves of a pass; the public calls keep lane 0 and their one-stream rule.
 // OUT OF SCOPE: point and mask-input prompts, multimask output, SamAutomaticMaskGenerator, outputs="all" of the Hiera encoder, HIP
@@ -400,7 +400,7 @@ int build(lmx_sam* m, int h, int w, int precision, Prepared* built) {
     if (r > rel) rel = r;
   }
   int64_t x3 = 0;
-  if (exact) {  // the widest x3 operand of MaskDecoder._lin: rows x 3 K halves
+  if (exact) {  // the widest x3 operand of Dec::lin: rows x 3 K halves
     const int64_t cand[3] = {B * gg * 3 * DD, B * gg * 4 * 3 * 64, B * DT * 3 * LMX_SAM_DEC_MLP};
     for (int64_t v : cand) x3 = v * 2 > x3 ? v * 2 : x3;
   }
@@ -633,202 +633,159 @@ int encode_chunk(const lmx_sam* m, const Prepared& P, int precision, const uint8
   return lmx_k_layernorm(P.acc, LMX_F16, C, m->n2_ln.g, m->n2_ln.b, emb, LMX_F16, C, rows, C, 1e-6f, LMX_ACT_NONE, st);
 }
 
-// ---- the mask decoder: one launch sequence per precision plan, as MaskDecoder.lowres / lowres_exact --------------------------------
+// ---- the mask decoder: MaskDecoder.lowres, ONE walk.  The precision plan enters in operand / lin / attention / upscale -------------
 struct Dec {
   const lmx_sam* m;
   const Prepared& P;
   int n;
+  bool exact;
   hipStream_t st;
 
-  int ln(const float* x, const Norm& g, float eps, void* y, int out_dtype, int rows, int D, int act) const {
-    return lmx_k_layernorm(x, LMX_F32, D, g.g, g.b, y, out_dtype, D, rows, D, eps, act, st);
+  // an activation as a Linear reads it: f16 rows (f16 plan) or f32 rows (exact plan), ld in elements
+  struct Opd {
+    const void* p;
+    int64_t ld;
+  };
+  int mid() const { return exact ? LMX_F32 : LMX_F16; }  // what travels between two Linears
+
+  int ln(const float* x, const Norm& g, float eps, void* y, int out_dtype, int64_t rows, int D, int act) const {
+    return lmx_k_layernorm(x, LMX_F32, D, g.g, g.b, y, out_dtype, D, (int)rows, D, eps, act, st);
   }
-  int add(const void* a, int a_dtype, const float* b, int b_rows, void* out, int out_dtype, int64_t rows) const {
-    return lmx_k_add_bcast(a, a_dtype, DD, b, DD, b_rows, out, out_dtype, DD, rows, DD, st);
+  int add(const void* a, int a_dtype, const float* b, int64_t b_rows, void* out, int out_dtype, int64_t rows) const {
+    return lmx_k_add_bcast(a, a_dtype, DD, b, DD, (int)b_rows, out, out_dtype, DD, rows, DD, st);
   }
-  int cast(const float* x, int64_t ldx, void* out, int64_t rows) const { return lmx_k_cast_f32_f16(x, ldx, out, DD, rows, DD, st); }
-  // K.gemm of the f16 plan
-  int gemm(const void* a, const Lin& l, void* C, int out_dtype, int M, int act, const void* res) const {
-    return lmx_gemm_dense(a, l.K, l.w, l.b, C, l.N, out_dtype, M, l.N, l.K, act, nullptr, res, l.N, st);
+  // the plans' operand(x, pe): x + pe in `buf`; without pe a cast into `buf` (f16 plan) or x where it lies (exact plan: no launch)
+  int operand(const float* x, int64_t ldx, const float* pe, int64_t pe_rows, void* buf, int64_t rows, Opd* out) const {
+    *out = pe || !exact ? Opd{buf, DD} : Opd{x, ldx};
+    if (pe) return add(x, LMX_F32, pe, pe_rows, buf, mid(), rows);
+    return exact ? LMX_OK : lmx_k_cast_f32_f16(x, ldx, buf, DD, rows, DD, st);
   }
-  // MaskDecoder._attn
-  int attn16(const DecAttn& W, const void* q16, const void* k16, const void* v16, int tq, int tk, const float* res, float* out) const {
-    const int inner = W.q.N, hd = inner / DH;
-    LMX_TRY(gemm(q16, W.q, P.pq, LMX_F16, n * tq, LMX_ACT_NONE, nullptr));
-    LMX_TRY(gemm(k16, W.k, P.pk, LMX_F16, n * tk, LMX_ACT_NONE, nullptr));
-    LMX_TRY(gemm(v16, W.v, P.pv, LMX_F16, n * tk, LMX_ACT_NONE, nullptr));
-    lmx_attn_desc ad;
-    memset(&ad, 0, sizeof(ad));
-    ad.Q = P.pq;
-    ad.K = P.pk;
-    ad.V = P.pv;
-    ad.O = P.pa;
-    ad.ldq = ad.ldk = ad.ldv = ad.ldo = inner;
-    ad.B = n;
-    ad.H = DH;
-    ad.Tq = tq;
-    ad.Tk = tk;
-    ad.hd = hd;
-    ad.scale = (float)pow((double)hd, -0.5);
-    ad.mode = 0;
-    LMX_TRY(lmx_k_attention(&ad, st));
-    return gemm(P.pa, W.o, out, LMX_F32, n * tq, LMX_ACT_NONE, res);
-  }
-  // MaskDecoder._ffn
-  int ffn16(const Lin* l, const void* x16, float* out) const {
-    LMX_TRY(gemm(x16, l[0], P.t1, LMX_F16, n, LMX_ACT_RELU, nullptr));
-    LMX_TRY(gemm(P.t1, l[1], P.t2, LMX_F16, n, LMX_ACT_RELU, nullptr));
-    return gemm(P.t2, l[2], out, LMX_F32, n, LMX_ACT_NONE, nullptr);
-  }
-  // MaskDecoder._lin: x3 rows of act_in(x), then ONE GEMM over 3 K with the row scale
-  int lin3(const float* x, int64_t ldx, int64_t rows, const Lin& l, int act_in, int act, const float* res, float* out) const {
-    LMX_TRY(lmx_k_split3(x, ldx, act_in, nullptr, 0, P.x3, 3 * l.K, rows, l.K, l.K, 1, 0, st));
+  // the plans' linear: K.gemm on (w f16, b), or the x3 rows of act_in(a), then ONE GEMM over 3 K with the row scale and f32 output
+  int lin(Opd a, int64_t rows, const Lin& l, void* out, int out_dtype, int act = LMX_ACT_NONE, const float* res = nullptr, int act_in = LMX_ACT_NONE) const {
+    if (!exact) return lmx_gemm_dense(a.p, l.K, l.w, l.b, out, l.N, out_dtype, (int)rows, l.N, l.K, act, nullptr, res, l.N, st);
+    LMX_TRY(lmx_k_split3(static_cast<const float*>(a.p), a.ld, act_in, nullptr, 0, P.x3, 3 * l.K, rows, l.K, l.K, 1, 0, st));
     return lmx_gemm_dense(P.x3, 3 * l.K, l.w, l.b, out, l.N, LMX_F32, (int)rows, l.N, 3 * l.K, act, l.s, res, l.N, st);
   }
-  // MaskDecoder._attn_exact
-  int attn32(const DecAttn& W, const float* q_in, const float* k_in, const float* v_in, int tq, int tk, const float* res, float* out) const {
+  // MaskDecoder._attn: q / k / v projections, attention over 8 heads, out projection (+ res) in f32
+  int attn(const DecAttn& W, Opd q, Opd k, Opd v, int tq, int tk, const float* res, float* out) const {
     const int inner = W.q.N, hd = inner / DH;
-    float *q = static_cast<float*>(P.pq), *k = static_cast<float*>(P.pk), *v = static_cast<float*>(P.pv), *a = static_cast<float*>(P.pa);
-    LMX_TRY(lin3(q_in, DD, (int64_t)n * tq, W.q, LMX_ACT_NONE, LMX_ACT_NONE, nullptr, q));
-    LMX_TRY(lin3(k_in, DD, (int64_t)n * tk, W.k, LMX_ACT_NONE, LMX_ACT_NONE, nullptr, k));
-    LMX_TRY(lin3(v_in, DD, (int64_t)n * tk, W.v, LMX_ACT_NONE, LMX_ACT_NONE, nullptr, v));
-    LMX_TRY(lmx_k_attention_f32(q, inner, k, inner, v, inner, a, inner, n, DH, tq, tk, hd, (float)pow((double)hd, -0.5), st));
-    return lin3(a, inner, (int64_t)n * tq, W.o, LMX_ACT_NONE, LMX_ACT_NONE, res, out);
+    const float scale = (float)pow((double)hd, -0.5);
+    LMX_TRY(lin(q, (int64_t)n * tq, W.q, P.pq, mid()));
+    LMX_TRY(lin(k, (int64_t)n * tk, W.k, P.pk, mid()));
+    LMX_TRY(lin(v, (int64_t)n * tk, W.v, P.pv, mid()));
+    if (exact) {
+      auto f = [](void* p) { return static_cast<float*>(p); };
+      LMX_TRY(lmx_k_attention_f32(f(P.pq), inner, f(P.pk), inner, f(P.pv), inner, f(P.pa), inner, n, DH, tq, tk, hd, scale, st));
+    } else {
+      lmx_attn_desc ad;
+      memset(&ad, 0, sizeof(ad));
+      ad.Q = P.pq;
+      ad.K = P.pk;
+      ad.V = P.pv;
+      ad.O = P.pa;
+      ad.ldq = ad.ldk = ad.ldv = ad.ldo = inner;
+      ad.B = n;
+      ad.H = DH;
+      ad.Tq = tq;
+      ad.Tk = tk;
+      ad.hd = hd;
+      ad.scale = scale;
+      ad.mode = 0;
+      LMX_TRY(lmx_k_attention(&ad, st));
+    }
+    return lin(Opd{P.pa, inner}, (int64_t)n * tq, W.o, out, LMX_F32, LMX_ACT_NONE, res);
   }
-  // MaskDecoder._ffn_exact
-  int ffn32(const Lin* l, const float* x, int64_t ldx, float* out) const {
-    float *t1 = static_cast<float*>(P.t1), *t2 = static_cast<float*>(P.t2);
-    LMX_TRY(lin3(x, ldx, n, l[0], LMX_ACT_NONE, LMX_ACT_RELU, nullptr, t1));
-    LMX_TRY(lin3(t1, DD, n, l[1], LMX_ACT_NONE, LMX_ACT_RELU, nullptr, t2));
-    return lin3(t2, DD, n, l[2], LMX_ACT_NONE, LMX_ACT_NONE, nullptr, out);
+  // MaskDecoder._ffn
+  int ffn(const Lin* l, Opd x, float* out) const {
+    LMX_TRY(lin(x, n, l[0], P.t1, mid(), LMX_ACT_RELU));
+    LMX_TRY(lin(Opd{P.t1, DD}, n, l[1], P.t2, mid(), LMX_ACT_RELU));
+    return lin(Opd{P.t2, DD}, n, l[2], out, LMX_F32);
+  }
+  // the upscaler of the plans' upscale_and_mask: per-pixel GEMMs, LayerNorm2d row-wise on the [.., quadrant, 64] view, pixel shuffle
+  // deferred.  The two GELUs sit in the epilogues of the LayerNorm and of the second GEMM (f16 plan), or, exact, in the next split and
+  // in the final dot product
+  int upscale(const DecPlan& W, Opd x, int64_t nP) const {
+    const float eps = 1e-6f;
+    LMX_TRY(lin(x, nP, W.up1, P.u1, LMX_F32));
+    if (exact) {
+      LMX_TRY(ln(P.u1, m->up_ln, eps, P.u1n, LMX_F32, nP * 4, 64, LMX_ACT_NONE));
+      return lin(Opd{P.u1n, 64}, nP * 4, W.up2, P.u2, LMX_F32, LMX_ACT_NONE, nullptr, LMX_ACT_GELU);
+    }
+    LMX_TRY(ln(P.u1, m->up_ln, eps, P.u1n, LMX_F16, nP * 4, 64, LMX_ACT_GELU));
+    return lin(Opd{P.u1n, 64}, nP * 4, W.up2, P.u2, LMX_F16, LMX_ACT_GELU);
   }
 
-  // MaskDecoder.lowres: emb f16 [n * G * G, 256] -> logits f32 [n, 4G, 4G], P.iou4 f32 [n, 4]
-  int lowres16(const void* emb, float* logits) const {
-    const LmxSamCfg& c = m->cfg;
-    const DecPlan& W = m->dec[LMX_SAM_F16];
-    const int G = c.grid(), Pn = G * G, T = DT;
+  // MaskDecoder.lowres: emb f16 (f16 plan, Hiera) / f32 [n * G * G, 256] -> logits f32 [n, 4G, 4G], P.iou4 f32 [n, 4]
+  int lowres(const void* emb, float* logits) const {
+    const DecPlan& W = m->dec[exact ? LMX_SAM_EXACT : LMX_SAM_F16];
+    const int G = m->cfg.grid(), Pn = G * G, T = DT;
     const int64_t nT = (int64_t)n * T, nP = (int64_t)n * Pn;
     const float eps = 1e-6f;
-    const float* qpe = P.tokens;
     float *queries = P.qa, *spare = P.qb, *keys = P.keys_a, *kspare = P.keys_b;
+    // x = LayerNorm(y) / x = y: the ping-pong buffers flip behind every launch that writes one
     auto flip = [](float*& a, float*& b) {
       float* t = a;
       a = b;
       b = t;
     };
-    LMX_TRY(add(emb, LMX_F16, m->no_mask, 1, keys, LMX_F32, nP));
-    for (int i = 0; i < 2; ++i) {
-      const DecLayer& L = W.L[i];
-      if (i == 0) {
-        LMX_TRY(cast(P.tokens, DD, P.qq, nT));
-        LMX_TRY(attn16(L.sa, P.qq, P.qq, P.qq, T, T, nullptr, queries));
-      } else {
-        LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, P.qq, LMX_F16, nT));
-        LMX_TRY(cast(queries, DD, P.qc16, nT));
-        LMX_TRY(attn16(L.sa, P.qq, P.qq, P.qc16, T, T, queries, spare));
-        flip(queries, spare);
-      }
-      LMX_TRY(ln(queries, L.ln[0], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
-      flip(queries, spare);
-      LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, P.qq, LMX_F16, nT));
-      LMX_TRY(add(keys, LMX_F32, m->key_pe, Pn, P.kk, LMX_F16, nP));
-      LMX_TRY(cast(keys, DD, P.kc16, nP));
-      LMX_TRY(attn16(L.t2i, P.qq, P.kk, P.kc16, T, Pn, queries, spare));
-      flip(queries, spare);
-      LMX_TRY(ln(queries, L.ln[1], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
-      flip(queries, spare);
-      LMX_TRY(cast(queries, DD, P.qc16, nT));
-      LMX_TRY(gemm(P.qc16, L.lin1, P.hh, LMX_F16, (int)nT, LMX_ACT_RELU, nullptr));
-      LMX_TRY(gemm(P.hh, L.lin2, spare, LMX_F32, (int)nT, LMX_ACT_NONE, queries));
-      flip(queries, spare);
-      LMX_TRY(ln(queries, L.ln[2], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
-      flip(queries, spare);
-      LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, P.qq, LMX_F16, nT));
-      // (keys have not changed since the token-to-image attention above: P.kk is still keys + key_pe)
-      LMX_TRY(cast(queries, DD, P.qc16, nT));
-      LMX_TRY(attn16(L.i2t, P.kk, P.qq, P.qc16, Pn, T, keys, kspare));
-      flip(keys, kspare);
-      LMX_TRY(ln(keys, L.ln[3], eps, kspare, LMX_F32, (int)nP, DD, LMX_ACT_NONE));
-      flip(keys, kspare);
-    }
-    LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, P.qq, LMX_F16, nT));
-    LMX_TRY(add(keys, LMX_F32, m->key_pe, Pn, P.kk, LMX_F16, nP));
-    LMX_TRY(cast(keys, DD, P.kc16, nP));  // the final attention's values and the upscaler's input
-    LMX_TRY(attn16(W.fin, P.qq, P.kk, P.kc16, T, Pn, queries, spare));
-    flip(queries, spare);
-    LMX_TRY(ln(queries, m->ln_final, 1e-5f, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
-    flip(queries, spare);
-    LMX_TRY(cast(queries, (int64_t)T * DD, P.tok16, n));  // q3[:, 0]: the iou token
-    // upscaler: per-pixel GEMMs, LayerNorm2d + GELU row-wise on the [.., quadrant, 64] view, pixel shuffle deferred
-    LMX_TRY(gemm(P.kc16, W.up1, P.u1, LMX_F32, (int)nP, LMX_ACT_NONE, nullptr));
-    LMX_TRY(ln(P.u1, m->up_ln, eps, P.u1n, LMX_F16, (int)(nP * 4), 64, LMX_ACT_GELU));
-    LMX_TRY(gemm(P.u1n, W.up2, P.u2, LMX_F16, (int)(nP * 4), LMX_ACT_GELU, nullptr));
-    LMX_TRY(cast(queries + DD, (int64_t)T * DD, P.qc16, n));  // q3[:, 1]: mask token 0
-    LMX_TRY(ffn16(W.hyp, P.qc16, P.hyper));
-    LMX_TRY(lmx_k_hyper_mask_multi(P.u2, P.hyper, logits, n, 1, G, 32, st));
-    return ffn16(W.iou, P.tok16, P.iou4);
-  }
-
-  // MaskDecoder.lowres_exact: emb f32
-  int lowres32(const void* emb, float* logits) const {
-    const LmxSamCfg& c = m->cfg;
-    const DecPlan& W = m->dec[LMX_SAM_EXACT];
-    const int G = c.grid(), Pn = G * G, T = DT;
-    const int64_t nT = (int64_t)n * T, nP = (int64_t)n * Pn;
-    const float eps = 1e-6f;
-    const float* qpe = P.tokens;
-    float *queries = P.qa, *spare = P.qb, *keys = P.keys_a, *kspare = P.keys_b;
-    float *qq = static_cast<float*>(P.qq), *kk = static_cast<float*>(P.kk), *hh = static_cast<float*>(P.hh);
-    auto flip = [](float*& a, float*& b) {
-      float* t = a;
-      a = b;
-      b = t;
+    auto norm = [&](float*& x, float*& other, const Norm& g, float e, int64_t rows) {
+      LMX_TRY(ln(x, g, e, other, LMX_F32, rows, DD, LMX_ACT_NONE));
+      flip(x, other);
+      return (int)LMX_OK;
     };
-    LMX_TRY(add(emb, m->is_hiera() ? LMX_F16 : LMX_F32, m->no_mask, 1, keys, LMX_F32, nP));  // (a Hiera embedding is f16 under both plans)
+    // queries + qpe, keys + key_pe and the bare queries / keys, each in its own buffer (P.kk is read twice, P.kc16 by the upscaler)
+    auto q_pe = [&](Opd* o) { return operand(queries, DD, P.tokens, nT, P.qq, nT, o); };
+    auto k_pe = [&](Opd* o) { return operand(keys, DD, m->key_pe, Pn, P.kk, nP, o); };
+    auto q_in = [&](Opd* o) { return operand(queries, DD, nullptr, 0, P.qc16, nT, o); };
+    auto k_in = [&](Opd* o) { return operand(keys, DD, nullptr, 0, P.kc16, nP, o); };
+    Opd q, k, v;
+    LMX_TRY(add(emb, exact && !m->is_hiera() ? LMX_F32 : LMX_F16, m->no_mask, 1, keys, LMX_F32, nP));  // (a Hiera embedding is f16 under both plans)
     for (int i = 0; i < 2; ++i) {
       const DecLayer& L = W.L[i];
       if (i == 0) {
-        LMX_TRY(attn32(L.sa, P.tokens, P.tokens, P.tokens, T, T, nullptr, queries));
+        LMX_TRY(operand(P.tokens, DD, nullptr, 0, P.qq, nT, &q));
+        LMX_TRY(attn(L.sa, q, q, q, T, T, nullptr, queries));
       } else {
-        LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, qq, LMX_F32, nT));
-        LMX_TRY(attn32(L.sa, qq, qq, queries, T, T, queries, spare));
+        LMX_TRY(q_pe(&q));
+        LMX_TRY(q_in(&v));
+        LMX_TRY(attn(L.sa, q, q, v, T, T, queries, spare));
         flip(queries, spare);
       }
-      LMX_TRY(ln(queries, L.ln[0], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
+      LMX_TRY(norm(queries, spare, L.ln[0], eps, nT));
+      LMX_TRY(q_pe(&q));
+      LMX_TRY(k_pe(&k));
+      LMX_TRY(k_in(&v));
+      LMX_TRY(attn(L.t2i, q, k, v, T, Pn, queries, spare));
       flip(queries, spare);
-      LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, qq, LMX_F32, nT));
-      LMX_TRY(add(keys, LMX_F32, m->key_pe, Pn, kk, LMX_F32, nP));
-      LMX_TRY(attn32(L.t2i, qq, kk, keys, T, Pn, queries, spare));
+      LMX_TRY(norm(queries, spare, L.ln[1], eps, nT));
+      LMX_TRY(q_in(&v));
+      LMX_TRY(lin(v, nT, L.lin1, P.hh, mid(), LMX_ACT_RELU));
+      LMX_TRY(lin(Opd{P.hh, LMX_SAM_DEC_MLP}, nT, L.lin2, spare, LMX_F32, LMX_ACT_NONE, queries));
       flip(queries, spare);
-      LMX_TRY(ln(queries, L.ln[1], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
-      flip(queries, spare);
-      LMX_TRY(lin3(queries, DD, nT, L.lin1, LMX_ACT_NONE, LMX_ACT_RELU, nullptr, hh));
-      LMX_TRY(lin3(hh, LMX_SAM_DEC_MLP, nT, L.lin2, LMX_ACT_NONE, LMX_ACT_NONE, queries, spare));
-      flip(queries, spare);
-      LMX_TRY(ln(queries, L.ln[2], eps, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
-      flip(queries, spare);
-      LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, qq, LMX_F32, nT));
-      LMX_TRY(attn32(L.i2t, kk, qq, queries, Pn, T, keys, kspare));
+      LMX_TRY(norm(queries, spare, L.ln[2], eps, nT));
+      LMX_TRY(q_pe(&q));
+      // (keys have not changed since the token-to-image attention above: k is still keys + key_pe)
+      LMX_TRY(q_in(&v));
+      LMX_TRY(attn(L.i2t, k, q, v, Pn, T, keys, kspare));
       flip(keys, kspare);
-      LMX_TRY(ln(keys, L.ln[3], eps, kspare, LMX_F32, (int)nP, DD, LMX_ACT_NONE));
-      flip(keys, kspare);
+      LMX_TRY(norm(keys, kspare, L.ln[3], eps, nP));
     }
-    LMX_TRY(add(queries, LMX_F32, qpe, (int)nT, qq, LMX_F32, nT));
-    LMX_TRY(add(keys, LMX_F32, m->key_pe, Pn, kk, LMX_F32, nP));
-    LMX_TRY(attn32(W.fin, qq, kk, keys, T, Pn, queries, spare));
+    LMX_TRY(q_pe(&q));
+    LMX_TRY(k_pe(&k));
+    LMX_TRY(k_in(&v));  // the final attention's values and the upscaler's input
+    LMX_TRY(attn(W.fin, q, k, v, T, Pn, queries, spare));
     flip(queries, spare);
-    LMX_TRY(ln(queries, m->ln_final, 1e-5f, spare, LMX_F32, (int)nT, DD, LMX_ACT_NONE));
-    flip(queries, spare);
-    // upscaler: ConvTranspose2d(k2, s2) as per-pixel GEMMs, LayerNorm2d row-wise on the [.., quadrant, 64] view, exact GELUs folded
-    // into the next split / the final dot product
-    float *u1n = static_cast<float*>(P.u1n), *u2 = static_cast<float*>(P.u2);
-    LMX_TRY(lin3(keys, DD, nP, W.up1, LMX_ACT_NONE, LMX_ACT_NONE, nullptr, P.u1));
-    LMX_TRY(ln(P.u1, m->up_ln, eps, u1n, LMX_F32, (int)(nP * 4), 64, LMX_ACT_NONE));
-    LMX_TRY(lin3(u1n, 64, nP * 4, W.up2, LMX_ACT_GELU, LMX_ACT_NONE, nullptr, u2));
-    LMX_TRY(ffn32(W.hyp, queries + DD, (int64_t)T * DD, P.hyper));  // q3[:, 1]: mask token 0
-    LMX_TRY(lmx_k_hyper_mask_multi_f32(u2, P.hyper, logits, n, 1, G, 32, LMX_ACT_GELU, st));
-    return ffn32(W.iou, queries, (int64_t)T * DD, P.iou4);  // q3[:, 0]: the iou token
+    LMX_TRY(norm(queries, spare, m->ln_final, 1e-5f, nT));
+    Opd iou_tok, mask_tok;
+    LMX_TRY(operand(queries, (int64_t)T * DD, nullptr, 0, P.tok16, n, &iou_tok));  // q3[:, 0]: the iou token, ahead of the upscaler
+    LMX_TRY(upscale(W, v, nP));
+    LMX_TRY(operand(queries + DD, (int64_t)T * DD, nullptr, 0, P.qc16, n, &mask_tok));  // q3[:, 1]: mask token 0, behind it
+    LMX_TRY(ffn(W.hyp, mask_tok, P.hyper));
+    if (exact)
+      LMX_TRY(lmx_k_hyper_mask_multi_f32(static_cast<const float*>(P.u2), P.hyper, logits, n, 1, G, 32, LMX_ACT_GELU, st));
+    else
+      LMX_TRY(lmx_k_hyper_mask_multi(P.u2, P.hyper, logits, n, 1, G, 32, st));
+    return ffn(W.iou, iou_tok, P.iou4);
   }
 };
 
@@ -843,8 +800,7 @@ int decode_chunk(const lmx_sam* m, const Prepared& P, int precision, const void*
   // torch.cat([out_tokens, sparse], 1): the output-token rows are in place since prepare
   LMX_HIP(hipMemcpy2DAsync(P.tokens + LMX_SAM_OUT_TOKENS * DD, (size_t)DT * DD * 4, P.sparse, (size_t)2 * DD * 4, (size_t)2 * DD * 4, (size_t)n,
                            hipMemcpyDeviceToDevice, st));
-  const Dec d{m, P, n, st};
-  LMX_TRY(precision == LMX_SAM_EXACT ? d.lowres32(emb, logits) : d.lowres16(emb, logits));
+  LMX_TRY((Dec{m, P, n, precision == LMX_SAM_EXACT, st}.lowres(emb, logits)));
   LMX_TRY(lmx_k_mask_post(logits, n, L, c.image, P.nh, P.nw, h, w, mk, stats, P.post, st));
   LMX_HIP(hipMemcpy2DAsync(iou, 4, P.iou4, 16, 4, (size_t)n, hipMemcpyDeviceToDevice, st));  // iou[:, 0]
   if (mask_bits) LMX_TRY(lmx_k_pack_bits(mk, (int64_t)n * h, w, mask_bits, st));

@@ -265,7 +265,7 @@ _SAM_FFN = {"in": "proj_in", "mid": "layers.0", "out": "proj_out"}
 
 
 def sam_decoder_linears():
-    """Ordered {short name in the image: parameter prefix in the state dict}: every Linear MaskDecoder.lowres / lowres_exact touches
+    """Ordered {short name in the image: parameter prefix in the state dict}: every Linear MaskDecoder.lowres touches
     for a box prompt with one mask (mask token 0), in the order of csrc/host_sam_image.cpp lmx_sam_linears().  up1 / up2 are the two
     ConvTranspose2d re-laid as per-pixel GEMMs."""
     out = {}
@@ -286,34 +286,6 @@ def sam_decoder_linears():
     for k, v in _SAM_FFN.items():
         out[f"iou.{k}"] = f"mask_decoder.iou_prediction_head.{v}"
     return out
-
-
-def _sam_decoder_f16(decoder, short):
-    """(w f16, b f32) of the f16 plan's Linear `short`, as MaskDecoder.__init__ uploaded them"""
-    parts = short.split(".")
-    if parts[0] in ("L0", "L1"):
-        L = decoder.layers[int(parts[0][1])]
-        return L["w1" if parts[1] == "lin1" else "w2"] if len(parts) == 2 else L[parts[1]][_SAM_PROJ[parts[2]]]
-    if parts[0] == "fin":
-        return decoder.final[_SAM_PROJ[parts[1]]]
-    if parts[0] in ("up1", "up2"):
-        return getattr(decoder, parts[0])
-    return (decoder.hypers[0] if parts[0] == "hyp0" else decoder.iou_head)[list(_SAM_FFN).index(parts[1])]
-
-
-def _sam_decoder_x3(decoder, prefix):
-    """(x3 weight f16 [N, 3K], shifted bias f32 [N], row scale f32 [N]) of the exact plan's Linear `prefix`: what MaskDecoder._lin
-    builds on its first use, built here from the same float32 parameters with the same expressions (an entry _lin has cached already
-    is taken as it is)."""
-    from .exact import split_rows_x3
-
-    if prefix in decoder._wx:
-        return tuple(host(t) for t in decoder._wx[prefix])
-    w, b = decoder._sd[prefix + ".weight"], decoder._sd[prefix + ".bias"]
-    if prefix.startswith("mask_decoder.upscale_conv"):  # ConvTranspose2d(k2, s2) as a per-pixel GEMM, as lowres_exact re-lays it
-        w, b = np.transpose(w, (2, 3, 1, 0)).reshape(4 * w.shape[1], w.shape[0]), np.tile(b, 4)
-    x3, sc, e = split_rows_x3(w, [w.shape[1]])
-    return x3, np.ldexp(b.astype(np.float32), e).astype(np.float32), sc
 
 
 def _sam_plans(plans, who):
@@ -347,10 +319,9 @@ def _sam_decoder_tensors(d, plans):
     out["dec.up_ln.g"], out["dec.up_ln.b"] = host(d.up_ln[0]), host(d.up_ln[1])
     for short, prefix in sam_decoder_linears().items():
         if "f16" in plans:
-            w, b = _sam_decoder_f16(d, short)
-            out[f"dec.f16.{short}.w"], out[f"dec.f16.{short}.b"] = host(w), host(b)
+            out[f"dec.f16.{short}.w"], out[f"dec.f16.{short}.b"] = (host(t) for t in d._w16[prefix])
         if "exact" in plans:
-            out[f"dec.x3.{short}.w"], out[f"dec.x3.{short}.b"], out[f"dec.x3.{short}.s"] = _sam_decoder_x3(d, prefix)
+            out[f"dec.x3.{short}.w"], out[f"dec.x3.{short}.b"], out[f"dec.x3.{short}.s"] = (host(t) for t in d._x3(prefix))
     return out
 
 

@@ -107,6 +107,72 @@ def synthetic_state_dict(seed):
     return sd
 
 
+def linear_f32(sd, prefix):
+    """(w [N, K], b [N]) of the decoder's Linear `prefix` as a GEMM takes them.  The two upscale ConvTranspose2d(k2, s2) are per-pixel
+    GEMMs: Wg[(dy,dx,co), ci] = W[ci,co,dy,dx], the bias repeated per quadrant."""
+    w, b = sd[prefix + ".weight"], sd[prefix + ".bias"]
+    if prefix.startswith("mask_decoder.upscale_conv"):
+        w, b = np.transpose(w, (2, 3, 1, 0)).reshape(4 * w.shape[1], w.shape[0]), np.tile(b, 4)
+    return w, b
+
+
+class _PlanF16:
+    """Throughput plan: f16 GEMM operands, one K.gemm per Linear on the uploaded (w f16, b f32), flash attention in f16."""
+
+    def __init__(self, dec):
+        self.dec, self.w = dec, dec._w16
+
+    def operand(self, x, pe=None):
+        """x (+ pe) f32 in the form linear() takes"""
+        return K.cast_f16(x) if pe is None else K.add_bcast(x, pe, out_dtype=torch.float16)
+
+    def linear(self, a, name, act=K.ACT_NONE, res=None, out_dtype=torch.float16):
+        w, b = self.w[name]
+        return K.gemm(a, w, b, act, None, res, None, out_dtype)  # (positional: this sits in front of every GEMM of the dense schedule)
+
+    def attention(self, q, k, v, n, tq, tk):
+        hd = q.shape[1] // HEADS
+        a = torch.empty((n * tq, q.shape[1]), dtype=torch.float16, device=q.device)
+        K.attention(q, k, v, a, n, HEADS, tq, tk, hd, hd ** -0.5)
+        return a
+
+    def upscale_and_mask(self, x, hyper, n):
+        """GELUs in the epilogues of the LayerNorm and of the second GEMM; hyper() runs behind the upscaler"""
+        dec = self.dec
+        u = self.linear(x, "mask_decoder.upscale_conv1", out_dtype=torch.float32)                        # [n*P, 4*64]
+        u = K.layernorm(u.view(-1, 64), *dec.up_ln, 1e-6, act=K.ACT_GELU)                                # f16 [n*P*4, 64]
+        u = self.linear(u, "mask_decoder.upscale_conv2", act=K.ACT_GELU)                                 # f16 [n*P*4, 4*32]
+        return K.hyper_mask_multi(u, hyper(), n, dec.G, 32)                                              # one pass over u for all M masks
+
+
+class _PlanExact:
+    """Exact plan (csrc/exact.hip): f32 activations, 22-bit GEMM operands (MaskDecoder._x3), f32 attention."""
+
+    def __init__(self, dec):
+        self.dec = dec
+
+    def operand(self, x, pe=None):
+        return x if pe is None else K.add_bcast(x, pe, out_dtype=torch.float32)
+
+    def linear(self, a, name, act=K.ACT_NONE, res=None, out_dtype=torch.float32, act_in=K.ACT_NONE):
+        """y = act(act_in(a) @ W^T + b) (+ res): a f32 [rows, K] is split into x3 rows (after act_in), then ONE lmx_k_gemm launch over
+        3K with f32 output.  act may be NONE or RELU (it commutes with the positive row scale)."""
+        w3, b3, sc = self.dec._x3(name)
+        return K.gemm(K.split3_rows(a, act_in), w3, bias=b3, act=act, scale=sc, res=res, out_dtype=torch.float32)
+
+    def attention(self, q, k, v, n, tq, tk):
+        hd = q.shape[1] // HEADS
+        return K.attention_f32(q, k, v, n, HEADS, tq, tk, hd, hd ** -0.5)
+
+    def upscale_and_mask(self, x, hyper, n):
+        """exact GELUs folded into the next split / the final dot product"""
+        dec = self.dec
+        u = self.linear(x, "mask_decoder.upscale_conv1")                                                  # [n*P, 4*64]
+        u = K.layernorm(u.view(-1, 64), *dec.up_ln, 1e-6, out_dtype=torch.float32)
+        u = self.linear(u, "mask_decoder.upscale_conv2", act_in=K.ACT_GELU)                              # [n*P*4, 4*32], pre-GELU
+        return K.hyper_mask_multi_f32(u, hyper(), n, dec.G, 32, act=K.ACT_GELU)
+
+
 class MaskDecoder:
     """Device-resident SAM prompt encoder + mask decoder.  ``predict(emb, boxes, frame_hw, resized_hw)`` -> dict(mask u8
     [n,h,w], stats int64 [n,8], iou f32 [n], lowres f32 [n,256,256]); ``decode(...)`` serves every prompt of
@@ -116,9 +182,10 @@ class MaskDecoder:
         """precision: the default plan of predict() — "exact" (services, adapters, the reference schedule: f32 activations,
         22-bit GEMM operands, f32 attention; masks within IoU 0.9995 of the fp32 path) or "f16" (the dense throughput
         schedule: f16 GEMM operands)."""
-        if precision not in ("exact", "f16"):
-            raise ValueError(f"precision {precision!r}: expected 'exact' or 'f16'")
+        self._w16 = {}  # state-dict prefix -> (w f16 [N, K], b f32 [N]): the f16 plan's Linears, which the attributes below hold by role
+        self._plans = {"f16": _PlanF16(self), "exact": _PlanExact(self)}
         self.precision = precision
+        self._plan(None)
         self.device = torch.device(device)
         self.S, self.G = image_size, grid
         dev = self.device
@@ -147,8 +214,13 @@ class MaskDecoder:
         self.mask_params = t32(np.concatenate([np.asarray(sd[k], np.float32).ravel() for k in me])) if all(k in sd for k in me) else None
         self.out_tokens = t32(np.concatenate([sd["mask_decoder.iou_token.weight"], sd["mask_decoder.mask_tokens.weight"]], 0))
 
+        def lin(prefix):
+            w, b = linear_f32(self._sd, prefix)
+            self._w16[prefix] = (t16(w), t32(b))
+            return self._w16[prefix]
+
         def attn(p):
-            return {n_: (t16(sd[p + n_ + ".weight"]), t32(sd[p + n_ + ".bias"])) for n_ in ("q_proj", "k_proj", "v_proj", "out_proj")}
+            return {n_: lin(p + n_) for n_ in ("q_proj", "k_proj", "v_proj", "out_proj")}
 
         def ln(p):
             return t32(sd[p + "weight"]), t32(sd[p + "bias"])
@@ -158,127 +230,66 @@ class MaskDecoder:
             p = f"mask_decoder.transformer.layers.{i}."
             self.layers.append(dict(sa=attn(p + "self_attn."), ln1=ln(p + "layer_norm1."),
                                     t2i=attn(p + "cross_attn_token_to_image."), ln2=ln(p + "layer_norm2."),
-                                    w1=(t16(sd[p + "mlp.lin1.weight"]), t32(sd[p + "mlp.lin1.bias"])),
-                                    w2=(t16(sd[p + "mlp.lin2.weight"]), t32(sd[p + "mlp.lin2.bias"])),
+                                    w1=lin(p + "mlp.lin1"), w2=lin(p + "mlp.lin2"),
                                     ln3=ln(p + "layer_norm3."), ln4=ln(p + "layer_norm4."),
                                     i2t=attn(p + "cross_attn_image_to_token.")))
         self.final = attn("mask_decoder.transformer.final_attn_token_to_image.")
         self.ln_final = ln("mask_decoder.transformer.layer_norm_final_attn.")
-        # ConvTranspose2d(k2,s2) as a per-pixel GEMM: Wg[(dy,dx,co), ci] = W[ci,co,dy,dx]; bias repeated per quadrant
-        w1 = sd["mask_decoder.upscale_conv1.weight"]
-        w2 = sd["mask_decoder.upscale_conv2.weight"]
-        self.up1 = (t16(np.transpose(w1, (2, 3, 1, 0)).reshape(4 * w1.shape[1], w1.shape[0])), t32(np.tile(sd["mask_decoder.upscale_conv1.bias"], 4)))
-        self.up2 = (t16(np.transpose(w2, (2, 3, 1, 0)).reshape(4 * w2.shape[1], w2.shape[0])), t32(np.tile(sd["mask_decoder.upscale_conv2.bias"], 4)))
+        self.up1, self.up2 = lin("mask_decoder.upscale_conv1"), lin("mask_decoder.upscale_conv2")
         self.up_ln = ln("mask_decoder.upscale_layer_norm.")
 
         def ffn(p):
-            return [(t16(sd[p + n_ + ".weight"]), t32(sd[p + n_ + ".bias"])) for n_ in ("proj_in", "layers.0", "proj_out")]
+            return [lin(p + n_) for n_ in ("proj_in", "layers.0", "proj_out")]
 
         self.hypers = [ffn(f"mask_decoder.output_hypernetworks_mlps.{m}.") for m in range(4)]
         self.iou_head = ffn("mask_decoder.iou_prediction_head.")
 
     # ---- helpers ---------------------------------------------------------------------------------------------
-    def _attn(self, W, q16, k16, v16, n, tq, tk, res):
-        """SamAttention: q/k/v projections (f16), flash attention over 8 heads, out projection (+res) in f32."""
-        q = K.gemm(q16, *W["q_proj"])
-        k = K.gemm(k16, *W["k_proj"])
-        v = K.gemm(v16, *W["v_proj"])
-        inner = q.shape[1]
-        hd = inner // HEADS
-        a = torch.empty((n * tq, inner), dtype=torch.float16, device=q.device)
-        K.attention(q, k, v, a, n, HEADS, tq, tk, hd, hd ** -0.5)
-        return K.gemm(a, W["out_proj"][0], bias=W["out_proj"][1], res=res, out_dtype=torch.float32)
+    def _plan(self, precision):
+        """the plan object of `precision` (None: this decoder's default)"""
+        precision = precision or self.precision
+        if precision not in self._plans:
+            raise ValueError(f"precision {precision!r}: expected 'exact' or 'f16'")
+        return self._plans[precision]
 
-    @staticmethod
-    def _ffn(layers, x16):
-        h = K.gemm(x16, *layers[0], act=K.ACT_RELU)
-        h = K.gemm(h, *layers[1], act=K.ACT_RELU)
-        return K.gemm(h, *layers[2], out_dtype=torch.float32)
-
-    # ---- forward ---------------------------------------------------------------------------------------------
-    def lowres(self, emb, sparse, keys=None, masks=None):
-        """emb f16/f32 [n*G*G, 256] (NHWC rows), sparse f32 [n,Ns,256] -> (logits f32 [n,4G,4G] of mask 0, iou f32 [n]).
-        keys: f32 [n*G*G,256] = emb + the dense prompt of a mask input (lmx_k_mask_embed); None = emb + the no-mask embedding.
-        masks: a tuple of mask indices to decode -> (logits f32 [n,len(masks),4G,4G], iou f32 [n,4]); None = mask 0 as above."""
-        n = sparse.shape[0]
-        T, P = 5 + sparse.shape[1], self.G * self.G
-        sel = (0,) if masks is None else tuple(masks)
-        eps = 1e-6
-        tokens = torch.cat([self.out_tokens[None].expand(n, -1, -1), sparse], dim=1).reshape(n * T, D).contiguous()
-        if keys is None:
-            keys = K.add_bcast(emb, self.no_mask)             # image embedding + dense no-mask embedding, f32
-        queries, qpe = tokens, tokens
-        for i, L in enumerate(self.layers):
-            if i == 0:
-                q16 = K.cast_f16(queries)
-                queries = self._attn(L["sa"], q16, q16, q16, n, T, T, None)
-            else:
-                q16 = K.add_bcast(queries, qpe, out_dtype=torch.float16)
-                queries = self._attn(L["sa"], q16, q16, K.cast_f16(queries), n, T, T, queries)
-            queries = K.layernorm(queries, *L["ln1"], eps, out_dtype=torch.float32)
-            q16 = K.add_bcast(queries, qpe, out_dtype=torch.float16)
-            k16 = K.add_bcast(keys, self.key_pe, out_dtype=torch.float16)
-            queries = self._attn(L["t2i"], q16, k16, K.cast_f16(keys), n, T, P, queries)
-            queries = K.layernorm(queries, *L["ln2"], eps, out_dtype=torch.float32)
-            h = K.gemm(K.cast_f16(queries), *L["w1"], act=K.ACT_RELU)
-            queries = K.gemm(h, *L["w2"], res=queries, out_dtype=torch.float32)
-            queries = K.layernorm(queries, *L["ln3"], eps, out_dtype=torch.float32)
-            q16 = K.add_bcast(queries, qpe, out_dtype=torch.float16)
-            # (keys have not changed since the token-to-image attention above: k16 is still keys + key_pe)
-            keys = self._attn(L["i2t"], k16, q16, K.cast_f16(queries), n, P, T, keys)
-            keys = K.layernorm(keys, *L["ln4"], eps, out_dtype=torch.float32)
-        q16 = K.add_bcast(queries, qpe, out_dtype=torch.float16)
-        k16 = K.add_bcast(keys, self.key_pe, out_dtype=torch.float16)
-        keys16 = K.cast_f16(keys)  # the final attention's values and the upscaler's input
-        queries = self._attn(self.final, q16, k16, keys16, n, T, P, queries)
-        queries = K.layernorm(queries, *self.ln_final, 1e-5, out_dtype=torch.float32)
-        q3 = queries.view(n, T, D)
-        iou_tok = K.cast_f16(q3[:, 0].contiguous())
-        # upscaler: per-pixel GEMMs, LayerNorm2d+GELU row-wise on the [.., quadrant, 64] view, pixel shuffle deferred
-        u = K.gemm(keys16, *self.up1, out_dtype=torch.float32)                       # [n*P, 4*64]
-        u = K.layernorm(u.view(n * P * 4, 64), *self.up_ln, eps, act=K.ACT_GELU)      # f16 [n*P*4, 64]
-        u = K.gemm(u, *self.up2, act=K.ACT_GELU)                                     # f16 [n*P*4, 4*32]
-        hs = [self._ffn(self.hypers[m], K.cast_f16(q3[:, 1 + m].contiguous())) for m in sel]
-        hyper = hs[0][:, None] if len(hs) == 1 else torch.stack(hs, 1)              # f32 [n,M,32]
-        logits = K.hyper_mask_multi(u, hyper, n, self.G, 32)                         # one pass over u for all M masks
-        iou = self._ffn(self.iou_head, iou_tok)                                      # f32 [n,4]
-        return (logits[:, 0], iou[:, 0]) if masks is None else (logits, iou)
-
-    # ---- exact plan: f32 activations, x3 operands (csrc/exact.hip), f32 attention ---------------------------------------
-    def _lin(self, x, name, act_in=K.ACT_NONE, act=K.ACT_NONE, res=None, w2d=None, bias=None):
-        """y = act(act_in(x) @ W^T + b) (+ res) with 22-bit operands: x f32 [rows, K] is split into x3 rows (after act_in),
-        W into [whi | whi/2048 | wlo] rows pre-scaled by powers of two (lmx.exact.split_rows_x3), ONE lmx_k_gemm launch over
-        3K with f32 output.  act may be NONE or RELU (it commutes with the positive row scale)."""
+    def _x3(self, name):
+        """(x3 weight f16 [N, 3K], shifted bias f32 [N], row scale f32 [N]) of the exact plan's Linear `name`, built on first use: W as
+        [whi | whi/2048 | wlo] rows pre-scaled by powers of two (lmx.exact.split_rows_x3), the bias shifted along."""
         from .exact import split_rows_x3
 
         if name not in self._wx:
-            w = self._sd[name + ".weight"] if w2d is None else w2d
-            b = self._sd[name + ".bias"] if bias is None else bias
+            w, b = linear_f32(self._sd, name)
             x3, sc, e = split_rows_x3(w, [w.shape[1]])
             dev = self.device
             self._wx[name] = (torch.from_numpy(x3).to(dev), torch.from_numpy(np.ldexp(b.astype(np.float32), e).astype(np.float32)).to(dev),
                               torch.from_numpy(sc).to(dev))
-        w3, b3, sc = self._wx[name]
-        return K.gemm(K.split3_rows(x, act_in), w3, bias=b3, act=act, scale=sc, res=res, out_dtype=torch.float32)
+        return self._wx[name]
 
-    def _attn_exact(self, p, q_in, k_in, v_in, n, tq, tk, res):
-        q = self._lin(q_in, p + "q_proj")
-        k = self._lin(k_in, p + "k_proj")
-        v = self._lin(v_in, p + "v_proj")
-        hd = q.shape[1] // HEADS
-        a = K.attention_f32(q, k, v, n, HEADS, tq, tk, hd, hd ** -0.5)
-        return self._lin(a, p + "out_proj", res=res)
+    @staticmethod
+    def _attn(P, p, q_in, k_in, v_in, n, tq, tk, res):
+        """SamAttention: q/k/v projections, attention over 8 heads, out projection (+res) in f32."""
+        q = P.linear(q_in, p + "q_proj")
+        k = P.linear(k_in, p + "k_proj")
+        v = P.linear(v_in, p + "v_proj")
+        return P.linear(P.attention(q, k, v, n, tq, tk), p + "out_proj", res=res, out_dtype=torch.float32)
 
-    def _ffn_exact(self, p, x):
-        h = self._lin(x, p + "proj_in", act=K.ACT_RELU)
-        h = self._lin(h, p + "layers.0", act=K.ACT_RELU)
-        return self._lin(h, p + "proj_out")
+    @staticmethod
+    def _ffn(P, p, x):
+        h = P.linear(x, p + "proj_in", act=K.ACT_RELU)
+        h = P.linear(h, p + "layers.0", act=K.ACT_RELU)
+        return P.linear(h, p + "proj_out", out_dtype=torch.float32)
 
-    def lowres_exact(self, emb, sparse, keys=None, masks=None):
-        """The exact plan of lowres() (same arguments and results): same launch structure, every tensor f32
-        (TF:models/sam/modeling_sam.py:432-543)."""
+    # ---- forward ---------------------------------------------------------------------------------------------
+    def lowres(self, emb, sparse, keys=None, masks=None, precision=None):
+        """emb f16/f32 [n*G*G, 256] (NHWC rows), sparse f32 [n,Ns,256] -> (logits f32 [n,4G,4G] of mask 0, iou f32 [n]).
+        keys: f32 [n*G*G,256] = emb + the dense prompt of a mask input (lmx_k_mask_embed); None = emb + the no-mask embedding.
+        masks: a tuple of mask indices to decode -> (logits f32 [n,len(masks),4G,4G], iou f32 [n,4]); None = mask 0 as above.
+        precision: the plan (constructor docstring; None = this decoder's default).  One walk serves both
+        (TF:models/sam/modeling_sam.py:432-543): a plan says how an activation becomes a GEMM operand and where the upscaler's
+        two GELUs sit."""
+        P = self._plan(precision)
         n = sparse.shape[0]
-        T, P = 5 + sparse.shape[1], self.G * self.G
+        T, Pn = 5 + sparse.shape[1], self.G * self.G
         sel = (0,) if masks is None else tuple(masks)
         eps = 1e-6
         f32 = torch.float32
@@ -286,46 +297,42 @@ class MaskDecoder:
         if keys is None:
             keys = K.add_bcast(emb, self.no_mask)             # image embedding + dense no-mask embedding, f32
         queries, qpe = tokens, tokens
-        for i in range(2):
+        for i, L in enumerate(self.layers):
             p = f"mask_decoder.transformer.layers.{i}."
-            L = self.layers[i]
             if i == 0:
-                queries = self._attn_exact(p + "self_attn.", queries, queries, queries, n, T, T, None)
+                q_ = P.operand(queries)
+                queries = self._attn(P, p + "self_attn.", q_, q_, q_, n, T, T, None)
             else:
-                q_ = K.add_bcast(queries, qpe, out_dtype=f32)
-                queries = self._attn_exact(p + "self_attn.", q_, q_, queries, n, T, T, queries)
+                q_ = P.operand(queries, qpe)
+                queries = self._attn(P, p + "self_attn.", q_, q_, P.operand(queries), n, T, T, queries)
             queries = K.layernorm(queries, *L["ln1"], eps, out_dtype=f32)
-            q_ = K.add_bcast(queries, qpe, out_dtype=f32)
-            k_ = K.add_bcast(keys, self.key_pe, out_dtype=f32)
-            queries = self._attn_exact(p + "cross_attn_token_to_image.", q_, k_, keys, n, T, P, queries)
+            q_ = P.operand(queries, qpe)
+            k_ = P.operand(keys, self.key_pe)
+            queries = self._attn(P, p + "cross_attn_token_to_image.", q_, k_, P.operand(keys), n, T, Pn, queries)
             queries = K.layernorm(queries, *L["ln2"], eps, out_dtype=f32)
-            h = self._lin(queries, p + "mlp.lin1", act=K.ACT_RELU)
-            queries = self._lin(h, p + "mlp.lin2", res=queries)
+            h = P.linear(P.operand(queries), p + "mlp.lin1", act=K.ACT_RELU)
+            queries = P.linear(h, p + "mlp.lin2", res=queries, out_dtype=f32)
             queries = K.layernorm(queries, *L["ln3"], eps, out_dtype=f32)
-            q_ = K.add_bcast(queries, qpe, out_dtype=f32)
-            keys = self._attn_exact(p + "cross_attn_image_to_token.", k_, q_, queries, n, P, T, keys)
+            q_ = P.operand(queries, qpe)
+            # (keys have not changed since the token-to-image attention above: k_ is still keys + key_pe)
+            keys = self._attn(P, p + "cross_attn_image_to_token.", k_, q_, P.operand(queries), n, Pn, T, keys)
             keys = K.layernorm(keys, *L["ln4"], eps, out_dtype=f32)
-        p = "mask_decoder.transformer."
-        q_ = K.add_bcast(queries, qpe, out_dtype=f32)
-        k_ = K.add_bcast(keys, self.key_pe, out_dtype=f32)
-        queries = self._attn_exact(p + "final_attn_token_to_image.", q_, k_, keys, n, T, P, queries)
+        q_ = P.operand(queries, qpe)
+        k_ = P.operand(keys, self.key_pe)
+        v_ = P.operand(keys)  # the final attention's values and the upscaler's input
+        queries = self._attn(P, "mask_decoder.transformer.final_attn_token_to_image.", q_, k_, v_, n, T, Pn, queries)
         queries = K.layernorm(queries, *self.ln_final, 1e-5, out_dtype=f32)
         q3 = queries.view(n, T, D)
-        iou_tok = q3[:, 0].contiguous()
-        # upscaler: ConvTranspose2d(k2, s2) as per-pixel GEMMs (weights re-laid as in __init__), LayerNorm2d row-wise on the
-        # [.., quadrant, 64] view, exact GELUs folded into the next split / the final dot product
-        w1 = self._sd["mask_decoder.upscale_conv1.weight"]
-        w2 = self._sd["mask_decoder.upscale_conv2.weight"]
-        u = self._lin(keys, "mask_decoder.upscale_conv1", w2d=np.transpose(w1, (2, 3, 1, 0)).reshape(4 * w1.shape[1], w1.shape[0]),
-                      bias=np.tile(self._sd["mask_decoder.upscale_conv1.bias"], 4))                    # [n*P, 4*64]
-        u = K.layernorm(u.view(n * P * 4, 64), *self.up_ln, eps, out_dtype=f32)
-        u = self._lin(u, "mask_decoder.upscale_conv2", act_in=K.ACT_GELU,
-                      w2d=np.transpose(w2, (2, 3, 1, 0)).reshape(4 * w2.shape[1], w2.shape[0]),
-                      bias=np.tile(self._sd["mask_decoder.upscale_conv2.bias"], 4))                    # [n*P*4, 4*32], pre-GELU
-        hs = [self._ffn_exact(f"mask_decoder.output_hypernetworks_mlps.{m}.", q3[:, 1 + m].contiguous()) for m in sel]
-        hyper = hs[0][:, None] if len(hs) == 1 else torch.stack(hs, 1)                                 # f32 [n,M,32]
-        logits = K.hyper_mask_multi_f32(u, hyper, n, self.G, 32, act=K.ACT_GELU)
-        iou = self._ffn_exact("mask_decoder.iou_prediction_head.", iou_tok)                             # f32 [n,4]
+        iou_tok = P.operand(q3[:, 0].contiguous())
+
+        def hyper():  # f32 [n,M,32]
+            hs = [self._ffn(P, f"mask_decoder.output_hypernetworks_mlps.{m}.", P.operand(q3[:, 1 + m].contiguous())) for m in sel]
+            return hs[0][:, None] if len(hs) == 1 else torch.stack(hs, 1)
+
+        # upscaler: ConvTranspose2d(k2, s2) as per-pixel GEMMs, LayerNorm2d row-wise on the [.., quadrant, 64] view, the pixel
+        # shuffle deferred to the hyper-network dot product
+        logits = P.upscale_and_mask(v_, hyper, n)
+        iou = self._ffn(P, "mask_decoder.iou_prediction_head.", iou_tok)                                # f32 [n,4]
         return (logits[:, 0], iou[:, 0]) if masks is None else (logits, iou)
 
     def predict(self, emb, boxes, frame_hw, resized_hw, precision=None):
@@ -334,10 +341,7 @@ class MaskDecoder:
         h, w = frame_hw
         nh, nw = resized_hw
         sparse = K.prompt_box(boxes, nw / w, nh / h, float(self.S), self.gauss, self.corner)
-        precision = precision or self.precision
-        if precision not in ("exact", "f16"):
-            raise ValueError(f"precision {precision!r}: expected 'exact' or 'f16'")
-        logits, iou = (self.lowres_exact if precision == "exact" else self.lowres)(emb, sparse)
+        logits, iou = self.lowres(emb, sparse, precision=precision)
         mask, stats = K.mask_post(logits, self.S, nh, nw, h, w)
         return dict(mask=mask, stats=stats, iou=iou, lowres=logits)
 
@@ -354,9 +358,7 @@ class MaskDecoder:
             raise ValueError("decode needs points (with labels) or boxes")
         if (points is None) != (labels is None):
             raise ValueError("points and labels go together")
-        precision = precision or self.precision
-        if precision not in ("exact", "f16"):
-            raise ValueError(f"precision {precision!r}: expected 'exact' or 'f16'")
+        self._plan(precision)
         sx, sy = (1.0, 1.0) if input_frame else (nw / w, nh / h)
         sparse = K.prompt_points(points, labels, boxes, sx, sy, float(self.S), self.gauss, self.point_embed, self.not_a_point,
                                  self.corner)
@@ -372,7 +374,7 @@ class MaskDecoder:
                                  "decoder's state dict does not hold")
             keys = K.mask_embed(mask_input, emb, self.mask_params, self.G)
         sel = (1, 2, 3) if multimask else (0,)
-        logits, iou = (self.lowres_exact if precision == "exact" else self.lowres)(emb, sparse, keys=keys, masks=sel)
+        logits, iou = self.lowres(emb, sparse, keys=keys, masks=sel, precision=precision)
         return logits, iou[:, sel[0]:sel[-1] + 1]
 
     def decode(self, emb, frame_hw, resized_hw, points=None, labels=None, boxes=None, mask_input=None, multimask=False,
