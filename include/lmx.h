@@ -1481,6 +1481,27 @@ int lmx_gnn_score(lmx_gnn* m, const lmx_gnn_graphs_t* graphs_host, const uint64_
 int lmx_gnn_score_host(lmx_gnn* m, const lmx_gnn_graphs_t* graphs_host, const uint64_t* seeds_host, int S, float* node_mc_host,
                        float* stats_host, float* graph_pred_host, float* node_pred_host, float* attn_weights_host);
 
+/* ==== The weight tables of the TCN, the gait transformer, the graph transformer and GraphGPS (csrc/weights_table.h) =====================
+ * Which tensors a configuration calls for, under which names, with which shapes, and which pointer of lmx_<model>_weights_t each one
+ * fills: stated once per model in the library (lmx_<model>_tensor_rows, csrc/host_<model>.cpp), read by the image readers, by the
+ * handles and, through these four, by lmx/kernels.py. */
+#define LMX_MAX_TENSOR_ROWS 256   /* above the largest table any configuration in the lists can ask for (gfm: 14 + 17 * 8 + 26 = 176) */
+typedef struct lmx_tensor_row {
+  char    name[48];     /* NUL padded; the image directory's name width */
+  int32_t rank;         /* 1 .. 4 */
+  int32_t shape[4];     /* unused dimensions 0 */
+  int32_t reserved;     /* 0 */
+  int64_t pointer_at;   /* byte offset, inside the model's lmx_<model>_weights_t, of the const float* this tensor fills */
+} lmx_tensor_row_t;
+/* The tensors the configuration in *config_host calls for (its integers only; its pointers are not read), in the order of the
+ * weight image and of pack_tensors.  The configuration is checked against the model's list first: LMX_EINVAL, the message opened
+ * by `who` and naming the field, exactly as lmx_h_<model>_forward refuses it.  rows_host may be NULL with cap 0 to check and count
+ * only; cap below the count is LMX_EINVAL naming cap and the count.  Host arithmetic, no GPU. */
+int lmx_h_tcn_tensors(const char* who, const lmx_tcn_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host);
+int lmx_h_xfm_tensors(const char* who, const lmx_xfm_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host);
+int lmx_h_gfm_tensors(const char* who, const lmx_gfm_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host);
+int lmx_h_gnn_tensors(const char* who, const lmx_gnn_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host);
+
 #ifdef __cplusplus
 }
 #endif

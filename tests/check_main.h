@@ -1,5 +1,5 @@
 // check_main.h — what the four *_check_main.cpp programs share: the program's own lmx_set_error (the library's lives in api.hip), the
-// loader of an image's data section, the loader of a file of tensors into exactly-sized blocks, main's `check PATH...` mode, and for
+// loader of an image's data section, the loader of a file of tensors into exactly-sized blocks and their binding by a weight table's rows, main's `check PATH...` mode, and for
 // the two gait programs the reader of the pose file's common front and main's `score` mode.
 #pragma once
 #include <stdarg.h>
@@ -47,6 +47,13 @@ static bool load_tensors(const char* path, const std::vector<size_t>& counts, bo
   if (whole_file && fgetc(f) != EOF) return false;
   fclose(f);
   return true;
+}
+
+// blocks[i] becomes the tensor of rows[i]: its address goes into the `const float*` of the weights struct `w` at rows[i].at (Row: LmxTensorRow)
+template <class Weights, class Row>
+static void bind_blocks(const std::vector<Row>& rows, const std::vector<char*>& blocks, Weights* w) {
+  for (size_t i = 0; i < rows.size(); ++i)
+    *reinterpret_cast<const float**>(reinterpret_cast<char*>(w) + rows[i].at) = reinterpret_cast<const float*>(blocks[i]);
 }
 
 template <class T>

@@ -4,15 +4,13 @@
 //                                   and csrc/host_gfm_image.cpp)
 //   gfm_check_main CONFIG WEIGHTS GRAPH N E K TIMED S SEED TARGET
 //     CONFIG   eight decimal integers, comma-separated: input_dim,d_model,n_heads,n_layers,ff,edge_dim,max_degree,max_spd
-//     WEIGHTS  the f32 tensors of lmx.kernels.gfm_tensor_shapes in its order, one after the other
+//     WEIGHTS  the f32 tensors of the weight table (lmx_gfm_tensor_rows, lmx.kernels.gfm_tensor_shapes) in its order, one after the other
 //     GRAPH    N x input_dim f32 node features, N x E f32 embeddings, N f32 timestamps (read only when TIMED is 1)
 //   Prints the edges, the attributes, the degrees, idx and win, then pred, stats and (S = 0) node_pred and attn_to_target, floats as hex.
 // Every buffer is sized exactly, so that a read or a write past an end is the sanitizer's to see.  The library reports through
 // lmx_set_error, which lives in api.hip with the rest of it: this program brings its own.
 #include "../vision-sam3-yolo-lameless_amd/csrc/gfm_image.h"
 #include "check_main.h"
-
-static const float* take(const std::vector<char*>& blocks, size_t& next) { return reinterpret_cast<const float*>(blocks[next++]); }
 
 int main(int argc, char** argv) {
   if (check_mode(argc, argv, lmx_gfm_image_check_host)) return 0;
@@ -27,38 +25,20 @@ int main(int argc, char** argv) {
   if (lmx_gfm_check_config("gfm_check_main", &w, false)) return fail("config");
   const int N = atoi(argv[4]), E = atoi(argv[5]), k = atoi(argv[6]), timed = atoi(argv[7]), S = atoi(argv[8]), target = atoi(argv[10]);
   uint64_t seed = strtoull(argv[9], nullptr, 10);
-  const int F = w.input_dim, D = w.d_model, H = w.n_heads, L = w.n_layers, FF = w.ff, dh = D / H, PD = lmx_gfm_pool_dim(D), Q = D / 16;
+  const int F = w.input_dim, D = w.d_model;
 
-  // the tensors in the order of gfm_tensor_shapes, each in an allocation of its own size
-  std::vector<size_t> counts = {(size_t)lmx_gfm_packed_floats(F, D), (size_t)D, (size_t)D, (size_t)D, (size_t)(w.max_degree + 1) * D,
-                                (size_t)(w.max_degree + 1) * D, (size_t)lmx_gfm_packed_floats(D, D), (size_t)D, (size_t)D / 2,
-                                (size_t)(w.max_spd + 2) * H, (size_t)2 * H * 3, (size_t)2 * H, (size_t)H * 2 * H, (size_t)H};
-  for (int l = 0; l < L; ++l) {
-    const size_t layer[] = {(size_t)D, (size_t)D, (size_t)H * Q * (3 * dh / 16) * 256, (size_t)H * 3 * dh, (size_t)Q * Q * 256, (size_t)D, (size_t)D,
-                            (size_t)D, (size_t)Q * (FF / 16) * 256, (size_t)FF, (size_t)(FF / 16) * Q * 256, (size_t)D, (size_t)D,
-                            (size_t)H * Q * (3 * dh / 16) * 256, (size_t)H * 3 * dh, (size_t)Q * Q * 256, (size_t)D};
-    counts.insert(counts.end(), layer, layer + 17);
+  // the tensors of the weight table in its order, each in an allocation of its own size, its address where the table says
+  std::vector<LmxTensorRow> rows;
+  lmx_gfm_tensor_rows(w, &rows);
+  std::vector<size_t> counts;
+  for (const LmxTensorRow& r : rows) {
+    size_t count = 1;
+    for (int d = 0; d < r.rank; ++d) count *= (size_t)r.shape[d];
+    counts.push_back(count);
   }
-  const size_t tail[] = {(size_t)D * 2 * D, (size_t)2 * D, (size_t)2 * D * D, (size_t)D, (size_t)D, (size_t)D, (size_t)D, (size_t)D,
-                         (size_t)Q * (PD / 16) * 256, (size_t)PD, (size_t)PD, 1, (size_t)3 * D * D, (size_t)D, (size_t)D, (size_t)D,
-                         (size_t)D * (D / 2), (size_t)D / 2, (size_t)(D / 2) * (D / 4), (size_t)D / 4, (size_t)D / 4, 1,
-                         (size_t)Q * (PD / 16) * 256, (size_t)PD, (size_t)PD, 1};
-  counts.insert(counts.end(), tail, tail + 26);
   std::vector<char*> blocks;
   if (!load_tensors(argv[2], counts, false, blocks)) return 2;
-  size_t next = 0;
-  const float** head[] = {&w.in_w, &w.in_b, &w.in_g, &w.in_beta, &w.deg_in, &w.deg_out, &w.time_w, &w.time_b, &w.div_term, &w.spd, &w.e1_w,
-                          &w.e1_b, &w.e2_w, &w.e2_b};
-  for (const float** p : head) *p = take(blocks, next);
-  for (int l = 0; l < L; ++l) {
-    const float** layer[] = {&w.ln1_g[l], &w.ln1_b[l], &w.qkv_w[l], &w.qkv_b[l], &w.out_w[l], &w.out_b[l], &w.ln2_g[l], &w.ln2_b[l], &w.ff1_w[l],
-                             &w.ff1_b[l], &w.ff2_w[l], &w.ff2_b[l], &w.vn[l], &w.vqkv_w[l], &w.vqkv_b[l], &w.vout_w[l], &w.vout_b[l]};
-    for (const float** p : layer) *p = take(blocks, next);
-  }
-  const float** rest[] = {&w.vu1_w, &w.vu1_b, &w.vu2_w, &w.vu2_b, &w.vu_g, &w.vu_beta, &w.lnf_g, &w.lnf_b, &w.pool1_w, &w.pool1_b, &w.pool2_w,
-                          &w.pool2_b, &w.comb_w, &w.comb_b, &w.comb_g, &w.comb_beta, &w.ph1_w, &w.ph1_b, &w.ph2_w, &w.ph2_b, &w.ph3_w, &w.ph3_b,
-                          &w.nh1_w, &w.nh1_b, &w.nh2_w, &w.nh2_b};
-  for (const float** p : rest) *p = take(blocks, next);
+  bind_blocks(rows, blocks, &w);
 
   if (N < 1 || N > 4096 || E < 1 || E > 4096 || k < 0) return 2;
   std::vector<float> x((size_t)N * F), emb((size_t)N * E), ts((size_t)(timed ? N : 0));

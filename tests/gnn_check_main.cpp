@@ -4,7 +4,7 @@
 //                                   and csrc/host_gnn_image.cpp)
 //   gnn_check_main CONFIG WEIGHTS GRAPH N E K TIMED S SEED
 //     CONFIG   seven decimal integers, comma-separated: input_dim,d_model,n_heads,n_layers,pe_dim,ff,edge_dim
-//     WEIGHTS  the f32 tensors of lmx.kernels.gnn_tensor_shapes in its order, one after the other
+//     WEIGHTS  the f32 tensors of the weight table (lmx_gnn_tensor_rows, lmx.kernels.gnn_tensor_shapes) in its order, one after the other
 //     GRAPH    N x input_dim f32 node features, N x E f32 embeddings, N f64 timestamps (read only when TIMED is 1)
 //   Prints the edges, the attributes, the CSR, the degrees, both encodings, then (S > 0) node_mc and stats or (S = 0) graph_pred,
 //   node_pred and attn_weights, floats as hex.
@@ -12,8 +12,6 @@
 // lmx_set_error, which lives in api.hip with the rest of it: this program brings its own.
 #include "../vision-sam3-yolo-lameless_amd/csrc/gnn_image.h"
 #include "check_main.h"
-
-static const float* take(const std::vector<char*>& blocks, size_t& next) { return reinterpret_cast<const float*>(blocks[next++]); }
 
 int main(int argc, char** argv) {
   if (check_mode(argc, argv, lmx_gnn_image_check_host)) return 0;
@@ -27,52 +25,20 @@ int main(int argc, char** argv) {
   if (lmx_gnn_check_config("gnn_check_main", &w, false)) return fail("config");
   const int N = atoi(argv[4]), E = atoi(argv[5]), k = atoi(argv[6]), timed = atoi(argv[7]), S = atoi(argv[8]);
   uint64_t seed = strtoull(argv[9], nullptr, 10);
-  const int F = w.input_dim, D = w.d_model, H = w.n_heads, L = w.n_layers, FF = w.ff, P = w.pe_dim, dh = D / H, Q = D / 16, D2 = D / 2;
+  const int F = w.input_dim, D = w.d_model;
 
-  // the tensors in the order of gnn_tensor_shapes, each in an allocation of its own size
-  std::vector<size_t> counts = {(size_t)lmx_gnn_packed_floats(F, D - 2 * P), (size_t)D - 2 * P};
-  for (int enc = 0; enc < 2; ++enc) {
-    const size_t K = enc ? LMX_GNN_RW_K : LMX_GNN_LAP_K;
-    const size_t one[] = {(size_t)2 * P * K, (size_t)2 * P, (size_t)P * 2 * P, (size_t)P, (size_t)P, (size_t)P};
-    counts.insert(counts.end(), one, one + 6);
+  // the tensors of the weight table in its order, each in an allocation of its own size, its address where the table says
+  std::vector<LmxTensorRow> rows;
+  lmx_gnn_tensor_rows(w, &rows);
+  std::vector<size_t> counts;
+  for (const LmxTensorRow& r : rows) {
+    size_t count = 1;
+    for (int d = 0; d < r.rank; ++d) count *= (size_t)r.shape[d];
+    counts.push_back(count);
   }
-  const size_t edge[] = {(size_t)D2 * 3, (size_t)D2, (size_t)lmx_gnn_packed_floats(D2, D), (size_t)D, (size_t)D, (size_t)D};
-  counts.insert(counts.end(), edge, edge + 6);
-  const size_t sq = (size_t)Q * Q * 256, v = (size_t)D;
-  for (int l = 0; l < L; ++l) {
-    const size_t front[] = {v, v, 4 * sq, 4 * v, sq, v};
-    counts.insert(counts.end(), front, front + 6);
-    if (l < L - 1) {
-      const size_t update[] = {3 * sq, v, sq, v, v, v, v, v};
-      counts.insert(counts.end(), update, update + 8);
-    }
-    const size_t back[] = {v, v, v, v, v, v, (size_t)H * Q * (3 * dh / 16) * 256, (size_t)H * 3 * dh, sq, v, v, v, v, v, (size_t)Q * (FF / 16) * 256,
-                           (size_t)FF, (size_t)(FF / 16) * Q * 256, v};
-    counts.insert(counts.end(), back, back + 18);
-  }
-  const size_t half = (size_t)Q * (D2 / 16) * 256;
-  const size_t tail[] = {v, v, half, (size_t)D2, (size_t)D2, 1, half, (size_t)D2, (size_t)D2, 1, 2 * v * v, v, v * D2, (size_t)D2, (size_t)D2, 1};
-  counts.insert(counts.end(), tail, tail + 16);
   std::vector<char*> blocks;
   if (!load_tensors(argv[2], counts, true, blocks)) return 2;
-  size_t next = 0;
-  const float** head[] = {&w.in_w, &w.in_b, &w.lap1_w, &w.lap1_b, &w.lap2_w, &w.lap2_b, &w.lap_g, &w.lap_beta, &w.rw1_w, &w.rw1_b,
-                          &w.rw2_w, &w.rw2_b, &w.rw_g, &w.rw_beta, &w.ee1_w, &w.ee1_b, &w.ee2_w, &w.ee2_b, &w.ee_g, &w.ee_beta};
-  for (const float** p : head) *p = take(blocks, next);
-  for (int l = 0; l < L; ++l) {
-    const float** front[] = {&w.ln1_g[l], &w.ln1_b[l], &w.abde_w[l], &w.abde_b[l], &w.c_w[l], &w.c_b[l]};
-    for (const float** p : front) *p = take(blocks, next);
-    if (l < L - 1) {
-      const float** update[] = {&w.eu1_w[l], &w.eu1_b[l], &w.eu2_w[l], &w.eu2_b[l], &w.bne_g[l], &w.bne_b[l], &w.bne_mean[l], &w.bne_var[l]};
-      for (const float** p : update) *p = take(blocks, next);
-    }
-    const float** back[] = {&w.bnn_g[l], &w.bnn_b[l], &w.bnn_mean[l], &w.bnn_var[l], &w.ln2_g[l], &w.ln2_b[l], &w.qkv_w[l], &w.qkv_b[l], &w.out_w[l],
-                            &w.out_b[l], &w.lna_g[l], &w.lna_b[l], &w.ln3_g[l], &w.ln3_b[l], &w.ff1_w[l], &w.ff1_b[l], &w.ff2_w[l], &w.ff2_b[l]};
-    for (const float** p : back) *p = take(blocks, next);
-  }
-  const float** rest[] = {&w.lnf_g, &w.lnf_b, &w.nh1_w, &w.nh1_b, &w.nh2_w, &w.nh2_b, &w.na1_w, &w.na1_b, &w.na2_w, &w.na2_b, &w.cl1_w, &w.cl1_b,
-                          &w.cl2_w, &w.cl2_b, &w.cl3_w, &w.cl3_b};
-  for (const float** p : rest) *p = take(blocks, next);
+  bind_blocks(rows, blocks, &w);
 
   if (N < 1 || N > 4096 || E < 1 || E > 4096 || k < 1) return 2;
   std::vector<float> x((size_t)N * F), emb((size_t)N * E);

@@ -2,7 +2,11 @@
 // graph transformer share beyond gait.h (keep decision, packed weight order): the limits, the shapes, the dropout sites and the call
 // checks.  Plain C++ without HIP types.
 #pragma once
+#include <vector>
+
 #include "gait.h"
+
+struct LmxTensorRow;  // weights_table.h
 
 enum {
   LMX_GFM_MAX_D = 128,      // d_model
@@ -26,6 +30,9 @@ inline float lmx_gfm_score_scale(int dh) { return (float)(1.0 / sqrt((double)dh)
 // host_gfm.cpp: the configuration list of include/lmx.h (`who` opens the message; the offending field is named) and, with `pointers`,
 // that every tensor is there and aligned
 int lmx_gfm_check_config(const char* who, const lmx_gfm_weights_t* w, bool pointers);
+// host_gfm.cpp: the weight table, stated once: appends every tensor `cfg` calls for (name, shape and the pointer of lmx_gfm_weights_t it
+// fills) in the order of the weight image and of pack_tensors; `cfg` has passed lmx_gfm_check_config(.., false)
+void lmx_gfm_tensor_rows(const lmx_gfm_weights_t& cfg, std::vector<LmxTensorRow>* rows);
 // host_gfm.cpp: what both forwards check of a call after the configuration: the offsets, every N, S, p, the eval-only outputs.  On
 // success *nodes = sum N, *cells = sum N^2, *max_n = the largest N.
 int lmx_gfm_check_call(const char* who, const lmx_gfm_graphs_t* g, int S, double p, bool eval_outputs, int64_t* nodes, int64_t* cells, int* max_n);

@@ -2,7 +2,11 @@
 // forward) of GraphGPS share beyond gait.h (keep decision, packed weight order): the limits, the dropout sites and the call checks.
 // Plain C++ without HIP types.
 #pragma once
+#include <vector>
+
 #include "gait.h"
+
+struct LmxTensorRow;  // weights_table.h
 
 enum {
   LMX_GNN_MAX_D = 128,   // d_model
@@ -26,6 +30,9 @@ inline int64_t lmx_gnn_slice_floats(int max_nodes, int max_edges, int d_model, i
 // host_gnn.cpp: the configuration list of include/lmx.h (`who` opens the message; the offending field is named) and, with `pointers`,
 // that every tensor is there and aligned
 int lmx_gnn_check_config(const char* who, const lmx_gnn_weights_t* w, bool pointers);
+// host_gnn.cpp: the weight table, stated once: appends every tensor `cfg` calls for (name, shape and the pointer of lmx_gnn_weights_t it
+// fills) in the order of the weight image and of pack_tensors; `cfg` has passed lmx_gnn_check_config(.., false)
+void lmx_gnn_tensor_rows(const lmx_gnn_weights_t& cfg, std::vector<LmxTensorRow>* rows);
 // host_gnn.cpp: what both forwards check of a call after the configuration: the offsets, every N and E, S, p, the outputs of the mode.
 // On success *nodes = sum N, *max_n and *max_e = the largest N and E.
 int lmx_gnn_check_call(const char* who, const lmx_gnn_weights_t* w, const lmx_gnn_graphs_t* g, int S, double p, bool mc_outputs, bool eval_outputs,

@@ -8,10 +8,12 @@
 
 #include <algorithm>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "gfm.h"
 #include "graph.h"
+#include "weights_table.h"
 
 using namespace lmx_graph;
 
@@ -47,6 +49,44 @@ int lmx_gfm_check_config(const char* who, const lmx_gfm_weights_t* w, bool point
                "%s: the virtual node's update, the final norm, the readout or a head has no weights", who);
   GAIT_REQUIRE((((uintptr_t)w->pool1_w | (uintptr_t)w->nh1_w) & 15) == 0, "%s: the attention pool or the node head is not 16-byte aligned", who);
   return LMX_OK;
+}
+
+// The weight table (gfm.h): the tensors of the image and of lmx.gfm.pack_tensors, each named as the field of lmx_gfm_weights_t it
+// fills, the per-layer ones as layer.{l}.<field>
+void lmx_gfm_tensor_rows(const lmx_gfm_weights_t& c, std::vector<LmxTensorRow>* rows) {
+// a tensor is named as the field it fills: ONE for a plain pointer, PER_LAYER (inside the loop over l) for an array of one pointer per layer
+#define ONE(member, field, ...)                                                                        \
+  static_assert(!std::is_array<decltype(lmx_gfm_weights_t::member)>::value, #member " is one pointer"); \
+  LMX_ROW(lmx_gfm_weights_t, member, 0, #member, field, __VA_ARGS__)
+#define PER_LAYER(member, field, ...)                                                                     \
+  static_assert(std::is_array<decltype(lmx_gfm_weights_t::member)>::value, #member " is one pointer per layer"); \
+  LMX_ROW(lmx_gfm_weights_t, member, l, layer + #member, field, __VA_ARGS__)
+  const int F = c.input_dim, D = c.d_model, H = c.n_heads, dh = D / H, FF = c.ff, Q = D / 16, PD = lmx_gfm_pool_dim(D), NI = c.max_spd + 2,
+            ND = c.max_degree + 1;
+  ONE(in_w, "input_dim, d_model", lmx_gait_groups(F), Q, 64, 4); ONE(in_b, "d_model", D); ONE(in_g, "d_model", D); ONE(in_beta, "d_model", D);
+  ONE(deg_in, "max_degree, d_model", ND, D); ONE(deg_out, "max_degree, d_model", ND, D); ONE(time_w, "d_model", Q, Q, 64, 4);
+  ONE(time_b, "d_model", D); ONE(div_term, "d_model", D / 2); ONE(spd, "max_spd, n_heads", NI, H); ONE(e1_w, "n_heads, edge_dim", 2 * H, 3);
+  ONE(e1_b, "n_heads", 2 * H); ONE(e2_w, "n_heads", H, 2 * H); ONE(e2_b, "n_heads", H);
+  for (int l = 0; l < c.n_layers; ++l) {
+    const std::string layer = "layer." + std::to_string(l) + ".";
+    PER_LAYER(ln1_g, "d_model", D); PER_LAYER(ln1_b, "d_model", D); PER_LAYER(qkv_w, "n_heads, d_model", H * Q, 3 * dh / 16, 64, 4);
+    PER_LAYER(qkv_b, "n_heads, d_model", H, 3 * dh); PER_LAYER(out_w, "d_model", Q, Q, 64, 4); PER_LAYER(out_b, "d_model", D); PER_LAYER(ln2_g, "d_model", D);
+    PER_LAYER(ln2_b, "d_model", D); PER_LAYER(ff1_w, "d_model, ff", Q, FF / 16, 64, 4); PER_LAYER(ff1_b, "ff", FF); PER_LAYER(ff2_w, "ff, d_model", FF / 16, Q, 64, 4);
+    PER_LAYER(ff2_b, "d_model", D); PER_LAYER(vn, "d_model", D); PER_LAYER(vqkv_w, "n_heads, d_model", H * Q, 3 * dh / 16, 64, 4);
+    PER_LAYER(vqkv_b, "n_heads, d_model", H, 3 * dh); PER_LAYER(vout_w, "d_model", Q, Q, 64, 4); PER_LAYER(vout_b, "d_model", D);
+  }
+  ONE(vu1_w, "d_model", D, 2 * D); ONE(vu1_b, "d_model", 2 * D); ONE(vu2_w, "d_model", 2 * D, D); ONE(vu2_b, "d_model", D); ONE(vu_g, "d_model", D);
+  ONE(vu_beta, "d_model", D); ONE(lnf_g, "d_model", D); ONE(lnf_b, "d_model", D); ONE(pool1_w, "d_model", Q, PD / 16, 64, 4);
+  ONE(pool1_b, "d_model", PD); ONE(pool2_w, "d_model", PD); ONE(pool2_b, "one score", 1); ONE(comb_w, "d_model", 3 * D, D);
+  ONE(comb_b, "d_model", D); ONE(comb_g, "d_model", D); ONE(comb_beta, "d_model", D); ONE(ph1_w, "d_model", D, D / 2); ONE(ph1_b, "d_model", D / 2);
+  ONE(ph2_w, "d_model", D / 2, D / 4); ONE(ph2_b, "d_model", D / 4); ONE(ph3_w, "d_model", D / 4); ONE(ph3_b, "one class", 1);
+  ONE(nh1_w, "d_model", Q, PD / 16, 64, 4); ONE(nh1_b, "d_model", PD); ONE(nh2_w, "d_model", PD); ONE(nh2_b, "one score", 1);
+#undef ONE
+#undef PER_LAYER
+}
+
+extern "C" int lmx_h_gfm_tensors(const char* who, const lmx_gfm_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host) {
+  return lmx_table_export("lmx_h_gfm_tensors", who, config_host, lmx_gfm_check_config, lmx_gfm_tensor_rows, rows_host, cap, n_host);
 }
 
 int lmx_gfm_check_call(const char* who, const lmx_gfm_graphs_t* g, int S, double p, bool eval_outputs, int64_t* nodes, int64_t* cells, int* max_n) {

@@ -7,10 +7,12 @@
 
 #include <algorithm>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "gnn.h"
 #include "graph.h"
+#include "weights_table.h"
 
 using namespace lmx_graph;
 
@@ -49,6 +51,50 @@ int lmx_gnn_check_config(const char* who, const lmx_gnn_weights_t* w, bool point
                "%s: the final norm or a head has no weights", who);
   GAIT_REQUIRE((((uintptr_t)w->nh1_w | (uintptr_t)w->na1_w) & 15) == 0, "%s: the node head or the attention pool is not 16-byte aligned", who);
   return LMX_OK;
+}
+
+// The weight table (gnn.h): the tensors of the image and of lmx.gnn.pack_tensors, each named as the field of lmx_gnn_weights_t it
+// fills, the per-layer ones as layer.{l}.<field>.  The last live layer's edge update reaches no output and has no tensors.
+void lmx_gnn_tensor_rows(const lmx_gnn_weights_t& c, std::vector<LmxTensorRow>* rows) {
+// a tensor is named as the field it fills: ONE for a plain pointer, PER_LAYER (inside the loop over l) for an array of one pointer per layer
+#define ONE(member, field, ...)                                                                        \
+  static_assert(!std::is_array<decltype(lmx_gnn_weights_t::member)>::value, #member " is one pointer"); \
+  LMX_ROW(lmx_gnn_weights_t, member, 0, #member, field, __VA_ARGS__)
+#define PER_LAYER(member, field, ...)                                                                     \
+  static_assert(std::is_array<decltype(lmx_gnn_weights_t::member)>::value, #member " is one pointer per layer"); \
+  LMX_ROW(lmx_gnn_weights_t, member, l, layer + #member, field, __VA_ARGS__)
+  const int F = c.input_dim, D = c.d_model, H = c.n_heads, dh = D / H, FF = c.ff, Q = D / 16, P = c.pe_dim, D2 = D / 2;
+  ONE(in_w, "input_dim, d_model, pe_dim", lmx_gait_groups(F), (D - 2 * P) / 16, 64, 4); ONE(in_b, "d_model, pe_dim", D - 2 * P);
+  ONE(lap1_w, "pe_dim", 2 * P, LMX_GNN_LAP_K); ONE(lap1_b, "pe_dim", 2 * P); ONE(lap2_w, "pe_dim", P, 2 * P); ONE(lap2_b, "pe_dim", P);
+  ONE(lap_g, "pe_dim", P); ONE(lap_beta, "pe_dim", P);
+  ONE(rw1_w, "pe_dim", 2 * P, LMX_GNN_RW_K); ONE(rw1_b, "pe_dim", 2 * P); ONE(rw2_w, "pe_dim", P, 2 * P); ONE(rw2_b, "pe_dim", P);
+  ONE(rw_g, "pe_dim", P); ONE(rw_beta, "pe_dim", P);
+  ONE(ee1_w, "d_model, edge_dim", D2, 3); ONE(ee1_b, "d_model", D2); ONE(ee2_w, "d_model", D2 / 16, Q, 64, 4); ONE(ee2_b, "d_model", D);
+  ONE(ee_g, "d_model", D); ONE(ee_beta, "d_model", D);
+  for (int l = 0; l < c.n_layers; ++l) {
+    const std::string layer = "layer." + std::to_string(l) + ".";
+    PER_LAYER(ln1_g, "d_model", D); PER_LAYER(ln1_b, "d_model", D); PER_LAYER(abde_w, "d_model", Q, 4 * Q, 64, 4); PER_LAYER(abde_b, "d_model", 4 * D);
+    PER_LAYER(c_w, "d_model", Q, Q, 64, 4); PER_LAYER(c_b, "d_model", D);
+    if (l < c.n_layers - 1) {
+      PER_LAYER(eu1_w, "d_model", 3 * Q, Q, 64, 4); PER_LAYER(eu1_b, "d_model", D); PER_LAYER(eu2_w, "d_model", Q, Q, 64, 4); PER_LAYER(eu2_b, "d_model", D);
+      PER_LAYER(bne_g, "d_model", D); PER_LAYER(bne_b, "d_model", D); PER_LAYER(bne_mean, "d_model", D); PER_LAYER(bne_var, "d_model", D);
+    }
+    PER_LAYER(bnn_g, "d_model", D); PER_LAYER(bnn_b, "d_model", D); PER_LAYER(bnn_mean, "d_model", D); PER_LAYER(bnn_var, "d_model", D);
+    PER_LAYER(ln2_g, "d_model", D); PER_LAYER(ln2_b, "d_model", D); PER_LAYER(qkv_w, "n_heads, d_model", H * Q, 3 * dh / 16, 64, 4);
+    PER_LAYER(qkv_b, "n_heads, d_model", H, 3 * dh); PER_LAYER(out_w, "d_model", Q, Q, 64, 4); PER_LAYER(out_b, "d_model", D);
+    PER_LAYER(lna_g, "d_model", D); PER_LAYER(lna_b, "d_model", D); PER_LAYER(ln3_g, "d_model", D); PER_LAYER(ln3_b, "d_model", D);
+    PER_LAYER(ff1_w, "d_model, ff", Q, FF / 16, 64, 4); PER_LAYER(ff1_b, "ff", FF); PER_LAYER(ff2_w, "ff, d_model", FF / 16, Q, 64, 4); PER_LAYER(ff2_b, "d_model", D);
+  }
+  ONE(lnf_g, "d_model", D); ONE(lnf_b, "d_model", D); ONE(nh1_w, "d_model", Q, D2 / 16, 64, 4); ONE(nh1_b, "d_model", D2); ONE(nh2_w, "d_model", D2);
+  ONE(nh2_b, "one score", 1); ONE(na1_w, "d_model", Q, D2 / 16, 64, 4); ONE(na1_b, "d_model", D2); ONE(na2_w, "d_model", D2);
+  ONE(na2_b, "one score", 1); ONE(cl1_w, "d_model", 2 * D, D); ONE(cl1_b, "d_model", D); ONE(cl2_w, "d_model", D, D2); ONE(cl2_b, "d_model", D2);
+  ONE(cl3_w, "d_model", D2); ONE(cl3_b, "one class", 1);
+#undef ONE
+#undef PER_LAYER
+}
+
+extern "C" int lmx_h_gnn_tensors(const char* who, const lmx_gnn_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host) {
+  return lmx_table_export("lmx_h_gnn_tensors", who, config_host, lmx_gnn_check_config, lmx_gnn_tensor_rows, rows_host, cap, n_host);
 }
 
 int lmx_gnn_check_call(const char* who, const lmx_gnn_weights_t* w, const lmx_gnn_graphs_t* g, int S, double p, bool mc_outputs, bool eval_outputs,

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "tcn.h"
+#include "weights_table.h"
 
 int lmx_tcn_receptive_field(int k, int n_blocks) { return 1 + 2 * (k - 1) * ((1 << n_blocks) - 1); }
 
@@ -34,6 +35,33 @@ int lmx_tcn_check_config(const char* who, const lmx_tcn_weights_t* w, bool point
   GAIT_REQUIRE(w->fc1_w && w->fc1_b && w->fc2_w && w->fc2_b, "%s: the head has no weights", who);
   GAIT_REQUIRE(((uintptr_t)w->fc1_w & 15) == 0, "%s: the head's fc1 weights are not 16-byte aligned", who);
   return LMX_OK;
+}
+
+// The weight table (tcn.h): the tensors of the image and of lmx.tcn.pack_tensors in their order.  A block whose input width equals its
+// channels has no residual convolution.
+void lmx_tcn_tensor_rows(const lmx_tcn_weights_t& c, std::vector<LmxTensorRow>* rows) {
+#define ROW(member, index, name, field, ...) LMX_ROW(lmx_tcn_weights_t, member, index, name, field, __VA_ARGS__)
+  for (int i = 0; i < c.n_blocks; ++i) {
+    const int cin = lmx_tcn_cin(c, i), N = c.channels[i];
+    const std::string b = "block." + std::to_string(i) + ".";
+    ROW(conv_w, 2 * i, b + "conv1.w", "k, the block's inputs, channels", c.k * lmx_gait_groups(cin), N / 16, 64, 4);
+    ROW(conv_b, 2 * i, b + "conv1.b", "channels", N);
+    ROW(conv_w, 2 * i + 1, b + "conv2.w", "k, channels", c.k * lmx_gait_groups(N), N / 16, 64, 4);
+    ROW(conv_b, 2 * i + 1, b + "conv2.b", "channels", N);
+    if (cin != N) {
+      ROW(res_w, i, b + "res.w", "the block's inputs, channels", lmx_gait_groups(cin), N / 16, 64, 4);
+      ROW(res_b, i, b + "res.b", "channels", N);
+    }
+  }
+  ROW(fc1_w, 0, "head.fc1.w", "head, channels", c.head, c.channels[c.n_blocks - 1]);
+  ROW(fc1_b, 0, "head.fc1.b", "head", c.head);
+  ROW(fc2_w, 0, "head.fc2.w", "head", c.head);
+  ROW(fc2_b, 0, "head.fc2.b", "one class", 1);
+#undef ROW
+}
+
+extern "C" int lmx_h_tcn_tensors(const char* who, const lmx_tcn_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host) {
+  return lmx_table_export("lmx_h_tcn_tensors", who, config_host, lmx_tcn_check_config, lmx_tcn_tensor_rows, rows_host, cap, n_host);
 }
 
 extern "C" int lmx_h_tcn_keep_bits(uint64_t seed, int sample, int site, int n_sites, int64_t count, double p, uint8_t* keep_host) {

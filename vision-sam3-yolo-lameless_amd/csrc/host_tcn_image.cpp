@@ -1,7 +1,8 @@
 // host_tcn_image.cpp — reader of the TCN weight image (tcn_image.h has the config block and the tensors; image.h the container;
 // lmx/native.py write_tcn_image writes it).  HOST code without HIP: the container reader (host_image.cpp) checks the header and the
 // directory against the file's real size, this file checks the config block (the list of include/lmx.h, through tcn.h's
-// lmx_tcn_check_config) and asks for every tensor the configuration calls for.  A malformed file is LMX_EINVAL with the field named.
+// lmx_tcn_check_config) and weights_table.h asks for every tensor of the configuration's table (lmx_tcn_tensor_rows, host_tcn.cpp).  A
+// malformed file is LMX_EINVAL with the field named.
 #include <math.h>
 #include <string.h>
 
@@ -26,45 +27,7 @@ int lmx_tcn_image_parse(const char* path, LmxTcnImage* img) {
   for (int i = c.n_blocks; i < LMX_TCN_MAX_BLOCKS; ++i)
     IMG_REQUIRE(c.channels[i] == 0, "tcn image: channels[%d] = %d beyond n_blocks %d", i, c.channels[i], c.n_blocks);
   IMG_REQUIRE(isfinite(img->p) && img->p >= 0.0 && img->p < 1.0, "tcn image: p %g outside [0, 1)", img->p);
-
-  img->data_offset = file.data_offset;
-  img->file_bytes = file.file_bytes;
-  for (int i = 0; i < c.n_blocks; ++i) {
-    const int cin = lmx_tcn_cin(c, i), N = c.channels[i];
-    const std::string b = "block." + std::to_string(i) + ".";
-    IMG_TAKE(file, b + "conv1.w", &img->conv_w[i][0], "k, the block's inputs, channels", LMX_IMG_F32, 4, c.k * lmx_gait_groups(cin), N / 16, 64, 4);
-    IMG_TAKE(file, b + "conv1.b", &img->conv_b[i][0], "channels", LMX_IMG_F32, 1, N);
-    IMG_TAKE(file, b + "conv2.w", &img->conv_w[i][1], "k, channels", LMX_IMG_F32, 4, c.k * lmx_gait_groups(N), N / 16, 64, 4);
-    IMG_TAKE(file, b + "conv2.b", &img->conv_b[i][1], "channels", LMX_IMG_F32, 1, N);
-    img->res_w[i] = img->res_b[i] = LmxTensorRef();
-    if (cin != N) {
-      IMG_TAKE(file, b + "res.w", &img->res_w[i], "the block's inputs, channels", LMX_IMG_F32, 4, lmx_gait_groups(cin), N / 16, 64, 4);
-      IMG_TAKE(file, b + "res.b", &img->res_b[i], "channels", LMX_IMG_F32, 1, N);
-    }
-  }
-  const int C = c.channels[c.n_blocks - 1];
-  IMG_TAKE(file, "head.fc1.w", &img->fc1_w, "head, channels", LMX_IMG_F32, 2, c.head, C);
-  IMG_TAKE(file, "head.fc1.b", &img->fc1_b, "head", LMX_IMG_F32, 1, c.head);
-  IMG_TAKE(file, "head.fc2.w", &img->fc2_w, "head", LMX_IMG_F32, 1, c.head);
-  IMG_TAKE(file, "head.fc2.b", &img->fc2_b, "one class", LMX_IMG_F32, 1, 1);
-  return LMX_OK;
-}
-
-void lmx_tcn_bind(const LmxTcnImage& img, const char* data, lmx_tcn_weights_t* w) {
-  auto at = [&](const LmxTensorRef& r) { return r.nbytes ? reinterpret_cast<const float*>(data + (r.offset - img.data_offset)) : nullptr; };
-  *w = img.cfg;
-  for (int i = 0; i < img.cfg.n_blocks; ++i) {
-    for (int s = 0; s < 2; ++s) {
-      w->conv_w[i][s] = at(img.conv_w[i][s]);
-      w->conv_b[i][s] = at(img.conv_b[i][s]);
-    }
-    w->res_w[i] = at(img.res_w[i]);
-    w->res_b[i] = at(img.res_b[i]);
-  }
-  w->fc1_w = at(img.fc1_w);
-  w->fc1_b = at(img.fc1_b);
-  w->fc2_w = at(img.fc2_w);
-  w->fc2_b = at(img.fc2_b);
+  return lmx_table_take(file, lmx_tcn_tensor_rows, img);
 }
 
 void lmx_tcn_fill_info(const LmxTcnImage& img, int max_clips, int max_samples, lmx_tcn_info_t* info) {

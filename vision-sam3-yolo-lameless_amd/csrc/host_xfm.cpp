@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "xfm.h"
+#include "weights_table.h"
 
 int lmx_xfm_check_config(const char* who, const lmx_xfm_weights_t* w, bool pointers) {
   GAIT_REQUIRE(w != nullptr, "%s: null weights", who);
@@ -34,6 +35,41 @@ int lmx_xfm_check_config(const char* who, const lmx_xfm_weights_t* w, bool point
   GAIT_REQUIRE(w->lnf_g && w->lnf_b && w->fc1_w && w->fc1_b && w->fc2_w && w->fc2_b, "%s: the final norm or the classifier has no weights", who);
   GAIT_REQUIRE(((uintptr_t)w->fc1_w & 15) == 0, "%s: the classifier's fc1 weights are not 16-byte aligned", who);
   return LMX_OK;
+}
+
+// The weight table (xfm.h): the tensors of the image and of lmx.xfm.pack_tensors in their order
+void lmx_xfm_tensor_rows(const lmx_xfm_weights_t& c, std::vector<LmxTensorRow>* rows) {
+#define ROW(member, index, name, field, ...) LMX_ROW(lmx_xfm_weights_t, member, index, name, field, __VA_ARGS__)
+  const int F = c.input_dim, D = c.d_model, H = c.n_heads, dh = D / H, FF = c.ff, QD = D / 16;
+  ROW(in_w, 0, "in.w", "input_dim, d_model", lmx_gait_groups(F), QD, 64, 4);
+  ROW(in_b, 0, "in.b", "d_model", D);
+  ROW(pe, 0, "pe", "max_len, d_model", c.max_len, D);
+  for (int l = 0; l < c.n_layers; ++l) {
+    const std::string b = "layer." + std::to_string(l) + ".";
+    ROW(ln1_g, l, b + "ln1.g", "d_model", D);
+    ROW(ln1_b, l, b + "ln1.b", "d_model", D);
+    ROW(qkv_w, l, b + "qkv.w", "n_heads, d_model", H * QD, 3 * dh / 16, 64, 4);
+    ROW(qkv_b, l, b + "qkv.b", "n_heads, d_model", H, 3 * dh);
+    ROW(out_w, l, b + "out.w", "d_model", QD, QD, 64, 4);
+    ROW(out_b, l, b + "out.b", "d_model", D);
+    ROW(ln2_g, l, b + "ln2.g", "d_model", D);
+    ROW(ln2_b, l, b + "ln2.b", "d_model", D);
+    ROW(ff1_w, l, b + "ff1.w", "d_model, ff", QD, FF / 16, 64, 4);
+    ROW(ff1_b, l, b + "ff1.b", "ff", FF);
+    ROW(ff2_w, l, b + "ff2.w", "ff, d_model", FF / 16, QD, 64, 4);
+    ROW(ff2_b, l, b + "ff2.b", "d_model", D);
+  }
+  ROW(lnf_g, 0, "lnf.g", "d_model", D);
+  ROW(lnf_b, 0, "lnf.b", "d_model", D);
+  ROW(fc1_w, 0, "head.fc1.w", "head, d_model", c.head, D);
+  ROW(fc1_b, 0, "head.fc1.b", "head", c.head);
+  ROW(fc2_w, 0, "head.fc2.w", "head", c.head);
+  ROW(fc2_b, 0, "head.fc2.b", "one class", 1);
+#undef ROW
+}
+
+extern "C" int lmx_h_xfm_tensors(const char* who, const lmx_xfm_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host) {
+  return lmx_table_export("lmx_h_xfm_tensors", who, config_host, lmx_xfm_check_config, lmx_xfm_tensor_rows, rows_host, cap, n_host);
 }
 
 namespace {

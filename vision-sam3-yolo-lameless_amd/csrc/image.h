@@ -1,11 +1,12 @@
 // image.h — the weight-image container every model-level handle reads (written by lmx/native.py write_image, read by host_image.cpp).
-// Host code only: nothing here needs HIP.  The container knows no model: a model's reader (host_dino_image.cpp, host_yolo_image.cpp,
-// host_sam_image.cpp) decodes and validates its own config block, then asks for each tensor the configuration calls for by name, dtype and shape.
+// Host code only: nothing here needs HIP.  The container knows no model: a model's reader (host_<model>_image.cpp for dino, yolo, sam,
+// tcn, xfm, gfm and gnn) decodes and validates its own config block, then asks for each tensor the configuration calls for by name, dtype
+// and shape (the last four through the model's weight table, weights_table.h).
 //
 // File layout, little-endian, every offset from the start of the file:
 //   header  48 bytes   magic "LMXIMAGE" | u32 version | u32 kind | u32 config_bytes | u32 n_tensors | u64 dir_offset |
 //                      u64 data_offset | u64 file_bytes
-//   config  at 48      config_bytes of the kind's own block (dino_image.h, yolo_image.h, sam_image.h, tcn_image.h, xfm_image.h)
+//   config  at 48      config_bytes of the kind's own block (<model>_image.h of the seven kinds)
 //   directory          n_tensors entries of 88 bytes: char name[48] (NUL padded) | u32 dtype | u32 rank | i32 shape[4] |
 //                      u64 offset (a multiple of 64, >= data_offset) | u64 nbytes (= elements * element size)
 //   data               the tensors, each bit for bit what the Python model holds on the device

@@ -13,22 +13,16 @@
 #pragma once
 #include <stdint.h>
 
-#include "image.h"
 #include "tcn.h"
+#include "weights_table.h"
 
 enum { LMX_TCN_CONFIG_BYTES = 12 * 4 + 8 };
 
-struct LmxTcnImage {
-  lmx_tcn_weights_t cfg;  // the integers; its pointers stay null until lmx_tcn_bind
-  double p = 0.0;
-  uint64_t data_offset = 0, file_bytes = 0;
-  LmxTensorRef conv_w[LMX_TCN_MAX_BLOCKS][2], conv_b[LMX_TCN_MAX_BLOCKS][2], res_w[LMX_TCN_MAX_BLOCKS], res_b[LMX_TCN_MAX_BLOCKS];
-  LmxTensorRef fc1_w, fc1_b, fc2_w, fc2_b;
-};
+typedef LmxTableImage<lmx_tcn_weights_t> LmxTcnImage;  // cfg, p, data_offset, file_bytes, rows, refs
 
 // Parse and validate the header, the config block and the directory of `path` (the tensor data is not read).  LMX_EINVAL with
 // the offending field named in lmx_last_error; `img` is complete only on LMX_OK.
 int lmx_tcn_image_parse(const char* path, LmxTcnImage* img);
 // the weights with every pointer into `data`, a copy of the image's data section [data_offset, file_bytes) in host or device memory
-void lmx_tcn_bind(const LmxTcnImage& img, const char* data, lmx_tcn_weights_t* w);
+inline void lmx_tcn_bind(const LmxTcnImage& img, const char* data, lmx_tcn_weights_t* w) { lmx_table_bind(img, data, w); }
 void lmx_tcn_fill_info(const LmxTcnImage& img, int max_clips, int max_samples, lmx_tcn_info_t* info);

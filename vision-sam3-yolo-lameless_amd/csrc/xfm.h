@@ -2,7 +2,11 @@
 // transformer share beyond gait.h (keep decision, packed weight order): the limits, the shapes and the configuration check.  Plain C++
 // without HIP types.
 #pragma once
+#include <vector>
+
 #include "gait.h"
+
+struct LmxTensorRow;  // weights_table.h
 
 enum {
   LMX_XFM_MAX_D = 64,     // d_model and input_dim
@@ -24,6 +28,9 @@ inline float lmx_xfm_q_scale(int dh) { return (float)(1.0 / sqrt((double)dh)); }
 // host_xfm.cpp: the configuration list of include/lmx.h (`who` opens the message; the offending field is named) and, with
 // `pointers`, that every tensor is there and aligned
 int lmx_xfm_check_config(const char* who, const lmx_xfm_weights_t* w, bool pointers);
+// host_xfm.cpp: the weight table, stated once: appends every tensor `cfg` calls for (name, shape and the pointer of lmx_xfm_weights_t it
+// fills) in the order of the weight image and of pack_tensors; `cfg` has passed lmx_xfm_check_config(.., false)
+void lmx_xfm_tensor_rows(const lmx_xfm_weights_t& cfg, std::vector<LmxTensorRow>* rows);
 // the checks both forwards and the handle share after the configuration: n, T, S, p, saliency (LMX_EINVAL with the field named)
 inline int lmx_xfm_check_call(const char* who, const lmx_xfm_weights_t* w, int n, int T, int S, double p, bool saliency) {
   if (const int rc = lmx_gait_check_call(who, n, T, S, p, w->max_len, "max_len ")) return rc;

@@ -11,21 +11,16 @@
 #pragma once
 #include <stdint.h>
 
-#include "image.h"
 #include "xfm.h"
+#include "weights_table.h"
 
 enum { LMX_XFM_CONFIG_BYTES = 8 * 4 + 8 };
 
-struct LmxXfmImage {
-  lmx_xfm_weights_t cfg;  // the integers; its pointers stay null until lmx_xfm_bind
-  double p = 0.0;
-  uint64_t data_offset = 0, file_bytes = 0;
-  LmxTensorRef in_w, in_b, pe, layer[LMX_XFM_MAX_LAYERS][12], lnf_g, lnf_b, fc1_w, fc1_b, fc2_w, fc2_b;
-};
+typedef LmxTableImage<lmx_xfm_weights_t> LmxXfmImage;  // cfg, p, data_offset, file_bytes, rows, refs
 
 // Parse and validate the header, the config block and the directory of `path` (the tensor data is not read).  LMX_EINVAL with
 // the offending field named in lmx_last_error; `img` is complete only on LMX_OK.
 int lmx_xfm_image_parse(const char* path, LmxXfmImage* img);
 // the weights with every pointer into `data`, a copy of the image's data section [data_offset, file_bytes) in host or device memory
-void lmx_xfm_bind(const LmxXfmImage& img, const char* data, lmx_xfm_weights_t* w);
+inline void lmx_xfm_bind(const LmxXfmImage& img, const char* data, lmx_xfm_weights_t* w) { lmx_table_bind(img, data, w); }
 void lmx_xfm_fill_info(const LmxXfmImage& img, int max_clips, int max_samples, lmx_xfm_info_t* info);

@@ -153,6 +153,10 @@ class GnnInfo(C.Structure):  # lmx_gnn_info_t
                                          "max_graphs", "max_nodes_total", "max_edges_total", "max_samples", "reserved")] + [("p", C.c_double)]
 
 
+class TensorRow(C.Structure):  # lmx_tensor_row_t: one row of a model's weight table (lmx_h_<model>_tensors)
+    _fields_ = [("name", C.c_char * 48), ("rank", C.c_int32), ("shape", C.c_int32 * 4), ("reserved", C.c_int32), ("pointer_at", C.c_int64)]
+
+
 class LetterboxGeo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sh", "sw", "rh", "rw", "top", "left", "oh", "ow")] + [(n, C.c_double) for n in ("gain", "pad_x", "pad_y")]
 
@@ -337,6 +341,10 @@ SIGNATURES = {
     "lmx_gnn_info": (_I, [_VP, C.POINTER(GnnInfo)]),
     "lmx_gnn_score": (_I, [_VP, C.POINTER(GnnGraphs), _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lmx_gnn_score_host": (_I, [_VP, C.POINTER(GnnGraphs), _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_h_tcn_tensors": (_I, [C.c_char_p, C.POINTER(TcnWeights), C.POINTER(TensorRow), _I, C.POINTER(_I)]),
+    "lmx_h_xfm_tensors": (_I, [C.c_char_p, C.POINTER(XfmWeights), C.POINTER(TensorRow), _I, C.POINTER(_I)]),
+    "lmx_h_gfm_tensors": (_I, [C.c_char_p, C.POINTER(GfmWeights), C.POINTER(TensorRow), _I, C.POINTER(_I)]),
+    "lmx_h_gnn_tensors": (_I, [C.c_char_p, C.POINTER(GnnWeights), C.POINTER(TensorRow), _I, C.POINTER(_I)]),
 }
 
 _lib = None

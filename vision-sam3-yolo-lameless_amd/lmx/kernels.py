@@ -530,6 +530,68 @@ def frame_quality(frames, out=None):
     return out
 
 
+# ---- the weight tables of the TCN, the gait transformer, the graph transformer and GraphGPS -------------------------------------------
+# Which tensors a configuration calls for, their names, shapes and the pointer of lmx_<model>_weights_t each one fills, and which
+# configurations are accepted at all, are stated once, in the library (include/lmx.h lmx_h_<model>_tensors; csrc/weights_table.h).
+def _model_config(Struct, who, ints):
+    """Struct (a lmx_<model>_weights_t) with the integers of `ints`, {field: an int, or a tuple for an array field}, and null pointers.
+    ctypes cuts a value that does not fit an int32 field without a word, so such a value is refused here; so are more blocks than
+    `channels`, the one array field, has entries."""
+    w = Struct()
+    for name, v in ints.items():
+        if isinstance(v, tuple) and len(v) > len(getattr(w, name)):
+            raise LmxError(f"{who}: n_blocks {len(v)} outside 1 .. {len(getattr(w, name))}")
+        for x in v if isinstance(v, tuple) else (v,):
+            if int(x) != x or not -2 ** 31 <= x < 2 ** 31:
+                raise LmxError(f"{who}: {name} {x} is not an int32")
+        if isinstance(v, tuple):
+            getattr(w, name)[:len(v)] = [int(x) for x in v]
+        else:
+            setattr(w, name, int(v))
+    return w
+
+
+def _ints(Struct, *values):
+    """{field: value} where the arguments come in the order of the struct's leading int32 fields (xfm, gfm, gnn)"""
+    return dict(zip((n for n, _ in Struct._fields_), values))
+
+
+def _model_rows(model, who, w):
+    """lmx_h_<model>_tensors for the configuration in `w`: [(name, shape, pointer_at)] in the order of the weight image and of
+    pack_tensors.  A configuration outside the list of include/lmx.h is refused in the library's words, `who` in front, the field named."""
+    lib, n = _lib.load(), C.c_int(0)
+    fn = getattr(lib, f"lmx_h_{model}_tensors")
+    if fn(who.encode(), C.byref(w), None, 0, C.byref(n)):  # the check and the count
+        raise LmxError(lib.lmx_last_error().decode("utf-8", "replace"))
+    rows = (_lib.TensorRow * n.value)()
+    check(fn(who.encode(), C.byref(w), rows, len(rows), C.byref(n)), f"lmx_h_{model}_tensors")
+    return [(r.name.decode(), tuple(r.shape[:r.rank]), r.pointer_at) for r in rows]
+
+
+def _model_shapes(model, Struct, who, ints):
+    """ordered {tensor name: shape} of one network"""
+    return {name: shape for name, shape, _ in _model_rows(model, who, _model_config(Struct, who, ints))}
+
+
+def _model_weights(model, Struct, who, ints, tensors):
+    """lmx_<model>_weights_t over packed f32 tensors (all on one GPU for the device forward, all on the CPU for the host forward): every
+    tensor of the table must be there, contiguous float32 of the table's shape, and its address goes where the table says.  The
+    struct keeps the tensors alive."""
+    w = _model_config(Struct, who, ints)
+    rows = _model_rows(model, who, w)
+    devs = {t.device for t in tensors.values()}
+    if len(devs) != 1:
+        raise LmxError(f"{who}: tensors on different devices ({sorted(map(str, devs))})")
+    for name, shape, at in rows:
+        t = tensors.get(name)
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise LmxError(f"{who}: {name} must be a contiguous float32 tensor of shape {shape}, got "
+                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
+        C.c_void_p.from_address(C.addressof(w) + at).value = t.data_ptr()
+    w._tensors, w._device = dict(tensors), devs.pop()
+    return w
+
+
 # ---- the TCN gait model (include/lmx.h "The TCN gait model"; csrc/tcn.hip, csrc/host_tcn.cpp) ---------------------------------------
 TCN_MAX_T = 256
 
@@ -545,52 +607,25 @@ def tcn_keep_bits(seed, sample, site, n_sites, count, p):
     return keep
 
 
+def _tcn_ints(input_dim, channels, k, head):
+    return {"input_dim": input_dim, "n_blocks": len(channels), "k": k, "head": head, "channels": tuple(channels)}
+
+
 def tcn_check_config(who, input_dim, channels, k, head):
-    """The list of include/lmx.h, refused as the library refuses it: LmxError names the field."""
-    if not 1 <= len(channels) <= 8:
-        raise LmxError(f"{who}: n_blocks {len(channels)} outside 1 .. 8")
-    if not 1 <= input_dim <= 64:
-        raise LmxError(f"{who}: input_dim {input_dim} outside 1 .. 64")
-    if k not in (2, 3):
-        raise LmxError(f"{who}: k {k} is neither 2 nor 3")
-    if not 1 <= head <= 64:
-        raise LmxError(f"{who}: head {head} outside 1 .. 64")
-    for i, c in enumerate(channels):
-        if c % 16 or not 16 <= c <= 64:
-            raise LmxError(f"{who}: channels[{i}] = {c} is not a multiple of 16 up to 64")
+    """The list of include/lmx.h, refused by the library itself: LmxError names the field."""
+    _model_rows("tcn", who, _model_config(_lib.TcnWeights, who, _tcn_ints(input_dim, channels, k, head)))
+
+
+def tcn_tensor_shapes(input_dim, channels, k, head):
+    """Ordered {tensor name: shape} of one network: the names of the weight image (csrc/tcn_image.h) and of lmx.tcn.pack_tensors."""
+    return _model_shapes("tcn", _lib.TcnWeights, "tcn_tensor_shapes", _tcn_ints(input_dim, channels, k, head))
 
 
 def tcn_weights(input_dim, channels, k, head, tensors):
     """lmx_tcn_weights_t over the packed f32 tensors of lmx.tcn.pack_tensors (all on one GPU for tcn_forward, all on the CPU for
     tcn_forward_host).  The struct keeps the tensors alive.  Configurations outside the list of include/lmx.h are refused here with
     the field named, as the library refuses them."""
-    tcn_check_config("tcn_weights", input_dim, channels, k, head)
-    devs = {t.device for t in tensors.values()}
-    if len(devs) != 1:
-        raise LmxError(f"tcn_weights: tensors on different devices ({sorted(map(str, devs))})")
-    w = _lib.TcnWeights()
-    w.input_dim, w.n_blocks, w.k, w.head = input_dim, len(channels), k, head
-
-    def take(name, shape):
-        t = tensors.get(name)
-        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
-            raise LmxError(f"tcn_weights: {name} must be a contiguous float32 tensor of shape {shape}, got "
-                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
-        return t.data_ptr()
-
-    for i, n in enumerate(channels):
-        w.channels[i] = n
-        cin = channels[i - 1] if i else input_dim
-        for s, c_in in ((0, cin), (1, n)):
-            w.conv_w[i][s] = take(f"block.{i}.conv{s + 1}.w", (k * ((c_in + 15) // 16), n // 16, 64, 4))
-            w.conv_b[i][s] = take(f"block.{i}.conv{s + 1}.b", (n,))
-        if cin != n:
-            w.res_w[i] = take(f"block.{i}.res.w", ((cin + 15) // 16, n // 16, 64, 4))
-            w.res_b[i] = take(f"block.{i}.res.b", (n,))
-    w.fc1_w, w.fc1_b = take("head.fc1.w", (head, channels[-1])), take("head.fc1.b", (head,))
-    w.fc2_w, w.fc2_b = take("head.fc2.w", (head,)), take("head.fc2.b", (1,))
-    w._tensors, w._device = dict(tensors), devs.pop()
-    return w
+    return _model_weights("tcn", _lib.TcnWeights, "tcn_weights", _tcn_ints(input_dim, channels, k, head), tensors)
 
 
 def _check_samples(who, S, p):
@@ -697,62 +732,22 @@ def tcn_features(keypoints, n_kp, bbox, target=125):
 
 
 # ---- the gait transformer (include/lmx.h "The gait transformer"; csrc/xfm.hip, csrc/host_xfm.cpp) -------------------------------------
-XFM_MAX_LEN = 160
-
-
 def xfm_check_config(who, input_dim, d_model, n_heads, n_layers, ff, head, max_len):
-    """The list of include/lmx.h, refused as the library refuses it: LmxError names the field."""
-    if not 1 <= input_dim <= 64:
-        raise LmxError(f"{who}: input_dim {input_dim} outside 1 .. 64")
-    if d_model not in (16, 32, 48, 64):
-        raise LmxError(f"{who}: d_model {d_model} is not 16, 32, 48 or 64")
-    if n_heads < 1 or d_model % n_heads or d_model // n_heads not in (16, 32):
-        raise LmxError(f"{who}: n_heads {n_heads} gives d_model {d_model} a head_dim that is neither 16 nor 32")
-    if not 1 <= n_layers <= 8:
-        raise LmxError(f"{who}: n_layers {n_layers} outside 1 .. 8")
-    if ff % 16 or not 16 <= ff <= 256:
-        raise LmxError(f"{who}: ff {ff} is not a multiple of 16 up to 256")
-    if not 1 <= head <= 64:
-        raise LmxError(f"{who}: head {head} outside 1 .. 64")
-    if not 1 <= max_len <= XFM_MAX_LEN:
-        raise LmxError(f"{who}: max_len {max_len} outside 1 .. {XFM_MAX_LEN}")
+    """The list of include/lmx.h, refused by the library itself: LmxError names the field."""
+    _model_rows("xfm", who, _model_config(_lib.XfmWeights, who, _ints(_lib.XfmWeights, input_dim, d_model, n_heads, n_layers, ff, head, max_len)))
 
 
 def xfm_tensor_shapes(input_dim, d_model, n_heads, n_layers, ff, head, max_len):
     """Ordered {tensor name: shape} of one network: the names of the weight image (csrc/xfm_image.h) and of lmx.xfm.pack_tensors."""
-    D, qd, dh = d_model, d_model // 16, d_model // n_heads
-    out = {"in.w": ((input_dim + 15) // 16, qd, 64, 4), "in.b": (D,), "pe": (max_len, D)}
-    for l in range(n_layers):
-        out.update({f"layer.{l}.ln1.g": (D,), f"layer.{l}.ln1.b": (D,), f"layer.{l}.qkv.w": (n_heads * qd, 3 * dh // 16, 64, 4),
-                    f"layer.{l}.qkv.b": (n_heads, 3 * dh), f"layer.{l}.out.w": (qd, qd, 64, 4), f"layer.{l}.out.b": (D,),
-                    f"layer.{l}.ln2.g": (D,), f"layer.{l}.ln2.b": (D,), f"layer.{l}.ff1.w": (qd, ff // 16, 64, 4), f"layer.{l}.ff1.b": (ff,),
-                    f"layer.{l}.ff2.w": (ff // 16, qd, 64, 4), f"layer.{l}.ff2.b": (D,)})
-    out.update({"lnf.g": (D,), "lnf.b": (D,), "head.fc1.w": (head, D), "head.fc1.b": (head,), "head.fc2.w": (head,), "head.fc2.b": (1,)})
-    return out
+    return _model_shapes("xfm", _lib.XfmWeights, "xfm_tensor_shapes", _ints(_lib.XfmWeights, input_dim, d_model, n_heads, n_layers, ff, head, max_len))
 
 
 def xfm_weights(input_dim, d_model, n_heads, n_layers, ff, head, max_len, tensors):
     """lmx_xfm_weights_t over the packed f32 tensors of lmx.xfm.pack_tensors (all on one GPU for xfm_forward, all on the CPU for
     xfm_forward_host).  The struct keeps the tensors alive.  Configurations outside the list of include/lmx.h are refused here with
     the field named, as the library refuses them."""
-    xfm_check_config("xfm_weights", input_dim, d_model, n_heads, n_layers, ff, head, max_len)
-    devs = {t.device for t in tensors.values()}
-    if len(devs) != 1:
-        raise LmxError(f"xfm_weights: tensors on different devices ({sorted(map(str, devs))})")
-    w = _lib.XfmWeights()
-    w.input_dim, w.d_model, w.n_heads, w.n_layers, w.ff, w.head, w.max_len = input_dim, d_model, n_heads, n_layers, ff, head, max_len
-    for name, shape in xfm_tensor_shapes(input_dim, d_model, n_heads, n_layers, ff, head, max_len).items():
-        t = tensors.get(name)
-        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
-            raise LmxError(f"xfm_weights: {name} must be a contiguous float32 tensor of shape {shape}, got "
-                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
-        parts = name.split(".")
-        if parts[0] == "layer":
-            getattr(w, f"{parts[2]}_{parts[3]}")[int(parts[1])] = t.data_ptr()
-        else:
-            setattr(w, "_".join(parts[1:] if parts[0] == "head" else parts), t.data_ptr())
-    w._tensors, w._device = dict(tensors), devs.pop()
-    return w
+    return _model_weights("xfm", _lib.XfmWeights, "xfm_weights", _ints(_lib.XfmWeights, input_dim, d_model, n_heads, n_layers, ff, head, max_len),
+                          tensors)
 
 
 def xfm_forward(w, x, mask, seeds, n_samples, p, saliency=False, trunk=False):
@@ -787,44 +782,16 @@ GFM_MAX_NODES = 95
 
 
 def gfm_check_config(who, input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd):
-    """The list of include/lmx.h, refused as the library refuses it: LmxError names the field."""
-    if not 1 <= input_dim <= 64:
-        raise LmxError(f"{who}: input_dim {input_dim} outside 1 .. 64")
-    if d_model % 16 or not 16 <= d_model <= 128:
-        raise LmxError(f"{who}: d_model {d_model} is not a multiple of 16 up to 128")
-    if n_heads < 1 or d_model % n_heads or d_model // n_heads not in (16, 32):
-        raise LmxError(f"{who}: n_heads {n_heads} gives d_model {d_model} a head_dim that is neither 16 nor 32")
-    if not 1 <= n_layers <= 8:
-        raise LmxError(f"{who}: n_layers {n_layers} outside 1 .. 8")
-    if ff % 16 or not 16 <= ff <= 512:
-        raise LmxError(f"{who}: ff {ff} is not a multiple of 16 up to 512")
-    if edge_dim != 3:
-        raise LmxError(f"{who}: edge_dim {edge_dim} is not 3")
-    if not 0 <= max_degree <= 255:
-        raise LmxError(f"{who}: max_degree {max_degree} outside 0 .. 255")
-    if not 2 <= max_spd + 2 <= 32:
-        raise LmxError(f"{who}: max_spd {max_spd}: max_spd + 2 outside 2 .. 32")
+    """The list of include/lmx.h, refused by the library itself: LmxError names the field."""
+    shape = (input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd)
+    _model_rows("gfm", who, _model_config(_lib.GfmWeights, who, _ints(_lib.GfmWeights, *shape)))
 
 
 def gfm_tensor_shapes(input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd):
     """Ordered {tensor name: shape} of one network: the fields of lmx_gfm_weights_t (`layer.{l}.<field>` for the per-layer ones), the
     names of lmx.gfm.pack_tensors."""
-    D, qd, dh, H, pd = d_model, d_model // 16, d_model // n_heads, n_heads, (d_model // 2 + 15) // 16 * 16
-    out = {"in_w": ((input_dim + 15) // 16, qd, 64, 4), "in_b": (D,), "in_g": (D,), "in_beta": (D,), "deg_in": (max_degree + 1, D),
-           "deg_out": (max_degree + 1, D), "time_w": (qd, qd, 64, 4), "time_b": (D,), "div_term": (D // 2,), "spd": (max_spd + 2, H),
-           "e1_w": (2 * H, 3), "e1_b": (2 * H,), "e2_w": (H, 2 * H), "e2_b": (H,)}
-    for l in range(n_layers):
-        p = f"layer.{l}."
-        out.update({p + "ln1_g": (D,), p + "ln1_b": (D,), p + "qkv_w": (H * qd, 3 * dh // 16, 64, 4), p + "qkv_b": (H, 3 * dh),
-                    p + "out_w": (qd, qd, 64, 4), p + "out_b": (D,), p + "ln2_g": (D,), p + "ln2_b": (D,), p + "ff1_w": (qd, ff // 16, 64, 4),
-                    p + "ff1_b": (ff,), p + "ff2_w": (ff // 16, qd, 64, 4), p + "ff2_b": (D,), p + "vn": (D,),
-                    p + "vqkv_w": (H * qd, 3 * dh // 16, 64, 4), p + "vqkv_b": (H, 3 * dh), p + "vout_w": (qd, qd, 64, 4), p + "vout_b": (D,)})
-    out.update({"vu1_w": (D, 2 * D), "vu1_b": (2 * D,), "vu2_w": (2 * D, D), "vu2_b": (D,), "vu_g": (D,), "vu_beta": (D,), "lnf_g": (D,),
-                "lnf_b": (D,), "pool1_w": (qd, pd // 16, 64, 4), "pool1_b": (pd,), "pool2_w": (pd,), "pool2_b": (1,), "comb_w": (3 * D, D),
-                "comb_b": (D,), "comb_g": (D,), "comb_beta": (D,), "ph1_w": (D, D // 2), "ph1_b": (D // 2,), "ph2_w": (D // 2, D // 4),
-                "ph2_b": (D // 4,), "ph3_w": (D // 4,), "ph3_b": (1,), "nh1_w": (qd, pd // 16, 64, 4), "nh1_b": (pd,), "nh2_w": (pd,),
-                "nh2_b": (1,)})
-    return out
+    shape = (input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd)
+    return _model_shapes("gfm", _lib.GfmWeights, "gfm_tensor_shapes", _ints(_lib.GfmWeights, *shape))
 
 
 def gfm_weights(input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd, tensors):
@@ -832,24 +799,7 @@ def gfm_weights(input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree,
     gfm_forward_host).  The struct keeps the tensors alive.  Configurations outside the list of include/lmx.h are refused here with
     the field named, as the library refuses them."""
     shape = (input_dim, d_model, n_heads, n_layers, ff, edge_dim, max_degree, max_spd)
-    gfm_check_config("gfm_weights", *shape)
-    devs = {t.device for t in tensors.values()}
-    if len(devs) != 1:
-        raise LmxError(f"gfm_weights: tensors on different devices ({sorted(map(str, devs))})")
-    w = _lib.GfmWeights()
-    w.input_dim, w.d_model, w.n_heads, w.n_layers, w.ff, w.edge_dim, w.max_degree, w.max_spd = shape
-    for name, shp in gfm_tensor_shapes(*shape).items():
-        t = tensors.get(name)
-        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous():
-            raise LmxError(f"gfm_weights: {name} must be a contiguous float32 tensor of shape {shp}, got "
-                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
-        parts = name.split(".")
-        if parts[0] == "layer":
-            getattr(w, parts[2])[int(parts[1])] = t.data_ptr()
-        else:
-            setattr(w, name, t.data_ptr())
-    w._tensors, w._device = dict(tensors), devs.pop()
-    return w
+    return _model_weights("gfm", _lib.GfmWeights, "gfm_weights", _ints(_lib.GfmWeights, *shape), tensors)
 
 
 def gfm_graph(embeddings, timestamps, k, max_degree, max_spd):
@@ -1036,70 +986,23 @@ GNN_RW_K = 16
 
 
 def gnn_check_config(who, input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim):
-    """The list of include/lmx.h, refused as the library refuses it: LmxError names the field."""
-    if not 1 <= input_dim <= 64:
-        raise LmxError(f"{who}: input_dim {input_dim} outside 1 .. 64")
-    if d_model % 32 or not 32 <= d_model <= 128:
-        raise LmxError(f"{who}: d_model {d_model} is not a multiple of 32 up to 128")
-    if n_heads < 1 or d_model % n_heads or d_model // n_heads not in (16, 32):
-        raise LmxError(f"{who}: n_heads {n_heads} gives d_model {d_model} a head_dim that is neither 16 nor 32")
-    if not 1 <= n_layers <= GNN_MAX_LAYERS:
-        raise LmxError(f"{who}: n_layers {n_layers} outside 1 .. {GNN_MAX_LAYERS} live layers")
-    if pe_dim < 8 or pe_dim % 8 or 2 * pe_dim >= d_model:
-        raise LmxError(f"{who}: pe_dim {pe_dim} is not a multiple of 8 with 2 pe_dim < d_model {d_model}")
-    if ff % 16 or not 16 <= ff <= 512:
-        raise LmxError(f"{who}: ff {ff} is not a multiple of 16 up to 512")
-    if edge_dim != 3:
-        raise LmxError(f"{who}: edge_dim {edge_dim} is not 3")
+    """The list of include/lmx.h, refused by the library itself: LmxError names the field."""
+    shape = (input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim)
+    _model_rows("gnn", who, _model_config(_lib.GnnWeights, who, _ints(_lib.GnnWeights, *shape)))
 
 
 def gnn_tensor_shapes(input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim):
     """Ordered {tensor name: shape} of one network: the fields of lmx_gnn_weights_t (`layer.{l}.<field>` for the per-layer ones; the
     last layer has no edge update), the names of lmx.gnn.pack_tensors."""
-    D, qd, dh, H, P = d_model, d_model // 16, d_model // n_heads, n_heads, pe_dim
-    out = {"in_w": ((input_dim + 15) // 16, (D - 2 * P) // 16, 64, 4), "in_b": (D - 2 * P,)}
-    for enc, k in (("lap", GNN_LAP_K), ("rw", GNN_RW_K)):
-        out.update({f"{enc}1_w": (2 * P, k), f"{enc}1_b": (2 * P,), f"{enc}2_w": (P, 2 * P), f"{enc}2_b": (P,), f"{enc}_g": (P,), f"{enc}_beta": (P,)})
-    out.update({"ee1_w": (D // 2, 3), "ee1_b": (D // 2,), "ee2_w": (D // 32, qd, 64, 4), "ee2_b": (D,), "ee_g": (D,), "ee_beta": (D,)})
-    for l in range(n_layers):
-        p = f"layer.{l}."
-        out.update({p + "ln1_g": (D,), p + "ln1_b": (D,), p + "abde_w": (qd, 4 * qd, 64, 4), p + "abde_b": (4 * D,), p + "c_w": (qd, qd, 64, 4),
-                    p + "c_b": (D,)})
-        if l < n_layers - 1:
-            out.update({p + "eu1_w": (3 * qd, qd, 64, 4), p + "eu1_b": (D,), p + "eu2_w": (qd, qd, 64, 4), p + "eu2_b": (D,), p + "bne_g": (D,),
-                        p + "bne_b": (D,), p + "bne_mean": (D,), p + "bne_var": (D,)})
-        out.update({p + "bnn_g": (D,), p + "bnn_b": (D,), p + "bnn_mean": (D,), p + "bnn_var": (D,), p + "ln2_g": (D,), p + "ln2_b": (D,),
-                    p + "qkv_w": (H * qd, 3 * dh // 16, 64, 4), p + "qkv_b": (H, 3 * dh), p + "out_w": (qd, qd, 64, 4), p + "out_b": (D,),
-                    p + "lna_g": (D,), p + "lna_b": (D,), p + "ln3_g": (D,), p + "ln3_b": (D,), p + "ff1_w": (qd, ff // 16, 64, 4), p + "ff1_b": (ff,),
-                    p + "ff2_w": (ff // 16, qd, 64, 4), p + "ff2_b": (D,)})
-    out.update({"lnf_g": (D,), "lnf_b": (D,), "nh1_w": (qd, D // 32, 64, 4), "nh1_b": (D // 2,), "nh2_w": (D // 2,), "nh2_b": (1,),
-                "na1_w": (qd, D // 32, 64, 4), "na1_b": (D // 2,), "na2_w": (D // 2,), "na2_b": (1,), "cl1_w": (2 * D, D), "cl1_b": (D,),
-                "cl2_w": (D, D // 2), "cl2_b": (D // 2,), "cl3_w": (D // 2,), "cl3_b": (1,)})
-    return out
+    shape = (input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim)
+    return _model_shapes("gnn", _lib.GnnWeights, "gnn_tensor_shapes", _ints(_lib.GnnWeights, *shape))
 
 
 def gnn_weights(input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim, tensors):
     """lmx_gnn_weights_t over the f32 tensors of lmx.gnn.pack_tensors (all on one GPU for gnn_forward, all on the CPU for
     gnn_forward_host).  The struct keeps the tensors alive."""
     shape = (input_dim, d_model, n_heads, n_layers, pe_dim, ff, edge_dim)
-    gnn_check_config("gnn_weights", *shape)
-    devs = {t.device for t in tensors.values()}
-    if len(devs) != 1:
-        raise LmxError(f"gnn_weights: tensors on different devices ({sorted(map(str, devs))})")
-    w = _lib.GnnWeights()
-    w.input_dim, w.d_model, w.n_heads, w.n_layers, w.pe_dim, w.ff, w.edge_dim = shape
-    for name, shp in gnn_tensor_shapes(*shape).items():
-        t = tensors.get(name)
-        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous():
-            raise LmxError(f"gnn_weights: {name} must be a contiguous float32 tensor of shape {shp}, got "
-                           f"{None if t is None else (t.dtype, tuple(t.shape))}")
-        parts = name.split(".")
-        if parts[0] == "layer":
-            getattr(w, parts[2])[int(parts[1])] = t.data_ptr()
-        else:
-            setattr(w, name, t.data_ptr())
-    w._tensors, w._device = dict(tensors), devs.pop()
-    return w
+    return _model_weights("gnn", _lib.GnnWeights, "gnn_weights", _ints(_lib.GnnWeights, *shape), tensors)
 
 
 def gnn_graph(embeddings, timestamps, k):

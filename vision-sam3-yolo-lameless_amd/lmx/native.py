@@ -95,6 +95,13 @@ def write_image(path, kind, config_block, tensors):
     return file_bytes
 
 
+def _check_image(Info, fn_name, path):
+    """lmx_<kind>_image_check_host: validate an image on the host (no GPU) -> its info struct; LmxError names the offending field."""
+    info = Info()
+    check(getattr(_lib.load(), fn_name)(str(path).encode(), C.byref(info)), fn_name)
+    return info
+
+
 def write_dino_image(embedder, path):
     """Export a DinoEmbedder (any device) as the weight image lmx_dino_open_host reads.  Returns the file's size in bytes."""
     return write_image(path, KIND_DINO, dino_config_block(embedder), dino_tensors(embedder))
@@ -102,9 +109,7 @@ def write_dino_image(embedder, path):
 
 def check_dino_image(path):
     """lmx_dino_image_check_host: validate an image on the host (no GPU) -> DinoInfo; LmxError names the offending field."""
-    info = DinoInfo()
-    check(_lib.load().lmx_dino_image_check_host(str(path).encode(), C.byref(info)), "lmx_dino_image_check_host")
-    return info
+    return _check_image(DinoInfo, "lmx_dino_image_check_host", path)
 
 
 # ---- the TCN weight image (csrc/tcn_image.h) ----------------------------------------------------------------------------------
@@ -124,9 +129,7 @@ def write_tcn_image(cfg, folded, path):
 
 def check_tcn_image(path):
     """lmx_tcn_image_check_host: validate an image on the host (no GPU) -> TcnInfo; LmxError names the offending field."""
-    info = TcnInfo()
-    check(_lib.load().lmx_tcn_image_check_host(str(path).encode(), C.byref(info)), "lmx_tcn_image_check_host")
-    return info
+    return _check_image(TcnInfo, "lmx_tcn_image_check_host", path)
 
 
 # ---- the gait transformer's weight image (csrc/xfm_image.h) ------------------------------------------------------------------------
@@ -145,9 +148,7 @@ def write_xfm_image(cfg, weights, path):
 
 def check_xfm_image(path):
     """lmx_xfm_image_check_host: validate an image on the host (no GPU) -> XfmInfo; LmxError names the offending field."""
-    info = XfmInfo()
-    check(_lib.load().lmx_xfm_image_check_host(str(path).encode(), C.byref(info)), "lmx_xfm_image_check_host")
-    return info
+    return _check_image(XfmInfo, "lmx_xfm_image_check_host", path)
 
 
 # ---- GraphGPS' weight image (csrc/gnn_image.h) ---------------------------------------------------------------------------------------
@@ -166,9 +167,7 @@ def write_gnn_image(cfg, weights, path):
 
 def check_gnn_image(path):
     """lmx_gnn_image_check_host: validate an image on the host (no GPU) -> GnnInfo; LmxError names the offending field."""
-    info = GnnInfo()
-    check(_lib.load().lmx_gnn_image_check_host(str(path).encode(), C.byref(info)), "lmx_gnn_image_check_host")
-    return info
+    return _check_image(GnnInfo, "lmx_gnn_image_check_host", path)
 
 
 # ---- the graph transformer's weight image (csrc/gfm_image.h) -----------------------------------------------------------------------
@@ -187,9 +186,7 @@ def write_gfm_image(cfg, weights, path):
 
 def check_gfm_image(path):
     """lmx_gfm_image_check_host: validate an image on the host (no GPU) -> GfmInfo; LmxError names the offending field."""
-    info = GfmInfo()
-    check(_lib.load().lmx_gfm_image_check_host(str(path).encode(), C.byref(info)), "lmx_gfm_image_check_host")
-    return info
+    return _check_image(GfmInfo, "lmx_gfm_image_check_host", path)
 
 
 # ---- the YOLO weight image (csrc/yolo_image.h) ------------------------------------------------------------------------------
@@ -252,9 +249,7 @@ def write_yolo_image(detector, path, plans=("f16", "exact")):
 
 def check_yolo_image(path):
     """lmx_yolo_image_check_host: validate an image on the host (no GPU) -> YoloInfo; LmxError names the offending field or tensor."""
-    info = YoloInfo()
-    check(_lib.load().lmx_yolo_image_check_host(str(path).encode(), C.byref(info)), "lmx_yolo_image_check_host")
-    return info
+    return _check_image(YoloInfo, "lmx_yolo_image_check_host", path)
 
 
 # ---- the SAM weight image (csrc/sam_image.h) -------------------------------------------------------------------------------
@@ -440,9 +435,7 @@ def write_sam_image(encoder, decoder, path, plans=("f16", "exact")):
 
 def check_sam_image(path):
     """lmx_sam_image_check_host: validate an image on the host (no GPU) -> SamInfo; LmxError names the offending field or tensor."""
-    info = SamInfo()
-    check(_lib.load().lmx_sam_image_check_host(str(path).encode(), C.byref(info)), "lmx_sam_image_check_host")
-    return info
+    return _check_image(SamInfo, "lmx_sam_image_check_host", path)
 
 
 # ---- the host arithmetic of the YOLO predictor (csrc/host_letterbox.cpp) -------------------------------------------------------
