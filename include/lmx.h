@@ -1180,6 +1180,81 @@ int lmx_xfm_score(lmx_xfm* m, const float* x, const uint8_t* mask, const uint64_
 int lmx_xfm_score_host(lmx_xfm* m, const float* x_host, const uint8_t* mask_host, const uint64_t* seeds_host, int n, int T, int S,
                        float* pred_host, float* stats_host, float* saliency_host);
 
+/* ==== Pose series: the detector's outputs to tleap's pose records, the 125 x 44 series and the key-padding mask (csrc/tleap.hip,
+ * csrc/tleap.h, csrc/host_tleap.cpp) ====
+ * services/tleap-pipeline/app/main.py:173-313 and :479-486 in ONE launch for n clips, one workgroup per clip, on the buffers that
+ * lmx_yolo_detect leaves in HBM: boxes f32 [F][max_det][4], scores f32 [F][max_det], cls i32 [F][max_det], counts i32 [F] (clamped to
+ * 0 .. max_det) and, for a pose model, kpts f32 [F][max_det][K][ndim].  Clip c owns frames clip_first_host[c] .. clip_first_host[c + 1]
+ * of the batch (n + 1 values from 0 to F that ascend strictly: a clip has at least one frame); h x w is the frame size.
+ * ROWS.  pose_sequences holds one row per DETECTION, flattened over the frames (main.py:479-486): frames ascend, within a frame the rows
+ * follow NMS order; row r of a clip comes from an exclusive scan of the per-frame row counts and rows[c] is their total T0.
+ *   LMX_TLEAP_TRAINED (kpts given): every detection is a row; a frame without detections contributes nothing (main.py:152-154).
+ *   LMX_TLEAP_HEURISTIC (kpts NULL): the detections whose class is one of cow_classes_host (at most LMX_TLEAP_MAX_COW_CLASSES ids,
+ *     main.py:282) are rows; a frame with none contributes ONE assumed row (main.py:295-304): box [w * 0.1, h * 0.1, w * (1 - 0.1),
+ *     h * (1 - 0.1)] in doubles, confidence 0.5, detection index -1.
+ * RECORDS.  The caller allocates F * max_det records; clip c's rows start at record clip_first_host[c] * max_det, those at and beyond
+ * rows[c] are not written.  A record holds the frame index RELATIVE to the clip's first frame, the detection index, the box (the four f32
+ * widened to f64, or the assumed box), the detection confidence (f32 widened, or 0.5), n_kp and 20 keypoints (x, y, confidence) in f64,
+ * zero at and beyond n_kp.
+ * HEURISTIC KEYPOINTS (main.py:210-263).  x1, y1, x2, y2 = the box corners truncated toward zero (Python's int); width = x2 - x1,
+ * height = y2 - y1; all arithmetic in doubles, one rounding per operation, in the reference's order: head_x = x1 + width * 0.1,
+ * head_y = y1 + height * 0.3, front_x = x1 + width * 0.25, back_x = x1 + width * 0.75, ground_y = y2 - height * 0.05 are rounded before
+ * they are used.  In slot order, (x; y; confidence):
+ *    0 left_eye   head_x - width*0.02; head_y - height*0.05; 0.7      1 right_eye  head_x + width*0.02; head_y - height*0.05; 0.7
+ *    2 nose       head_x; head_y + height*0.05; 0.8                   3 left_ear   head_x - width*0.05; head_y - height*0.1; 0.6
+ *    4 right_ear  head_x + width*0.05; head_y - height*0.1; 0.6       5 / 6 left / right_front_elbow  front_x -/+ width*0.05; y1 + height*0.4; 0.7
+ *    7 / 8 left / right_back_elbow  back_x -/+ width*0.05; y1 + height*0.4; 0.7
+ *    9 left_front_knee  front_x - width*0.03; y1 + height*0.6; 0.7    10 right_front_knee  front_x + width*0.07; y1 + height*0.6; 0.7
+ *   11 left_back_knee   back_x - width*0.07; y1 + height*0.6; 0.7     12 right_back_knee   back_x + width*0.03; y1 + height*0.6; 0.7
+ *   13 left_front_paw   front_x - width*0.02; ground_y; 0.7           14 right_front_paw   front_x + width*0.08; ground_y; 0.7
+ *   15 left_back_paw    back_x - width*0.08; ground_y; 0.7            16 right_back_paw    back_x + width*0.02; ground_y; 0.7
+ *   17 throat  x1 + width*0.15; y1 + height*0.25; 0.8                 18 withers  x1 + width*0.3; y1 + height*0.15; 0.8
+ *   19 tailbase  x1 + width*0.9; y1 + height*0.25; 0.7
+ * TRAINED BLEND (main.py:177-188).  n_kp = min(K, 20); keypoint i < n_kp is the model's: x and y f32 widened, the confidence f32 widened
+ * or 1.0 when ndim == 2; keypoints beyond 20 are dropped as the reference drops kp_{i}.  The only name the model's list and the heuristic
+ * list share is withers, slot 2 of the model's list: when its widened confidence is not > 0.3 (the double), the heuristic withers
+ * (x1 + width*0.3, y1 + height*0.15, 0.8) replaces it.
+ * SERIES AND MASK.  series f32 [n][target][44] and mask u8 [n][target] are exactly lmx_h_tcn_features and lmx_h_xfm_mask of the clip's
+ * records (divisions against the record's f64 box, the velocity differenced before the crop, padding masked); T0 = 0 gives a zero series
+ * and a full mask.
+ * Refused with LMX_EINVAL before anything is launched, the argument named: a null or misaligned pointer (4 bytes; records and workspace
+ * 8), F < 1, max_det < 1, h or w below 1, n < 1, ndim outside {2, 3} or K < 3 or K > 4096 with kpts, kpts that do not fit the mode,
+ * target outside 1 .. 65536, n_cow outside 0 .. LMX_TLEAP_MAX_COW_CLASSES, a mode that is neither, and clip_first_host that does not
+ * start at 0, ascend strictly and end at F.  workspace: lmx_tleap_workspace_bytes(F, max_det) bytes on the device (the clip bounds and
+ * the row maps), 0 for a size it refuses.  No atomics; bits do not depend on the batch a clip rides in.  lmx_h_tleap_series is the same
+ * contract on HOST pointers in plain C++ (it calls lmx_h_tcn_features and lmx_h_xfm_mask for the second half). */
+enum { LMX_TLEAP_TRAINED = 0, LMX_TLEAP_HEURISTIC = 1, LMX_TLEAP_KEYPOINTS = 20, LMX_TLEAP_MAX_COW_CLASSES = 16 };
+typedef struct { int32_t frame, det; double bbox[4]; double confidence; int32_t n_kp, reserved; double keypoints[LMX_TLEAP_KEYPOINTS][3]; }
+    lmx_tleap_record_t;  /* 536 bytes */
+int64_t lmx_tleap_workspace_bytes(int F, int max_det);
+int lmx_k_tleap_series(const float* boxes, const float* scores, const int32_t* cls, const int32_t* counts, const float* kpts /* or NULL */,
+                       int K, int ndim, int F, int max_det, int h, int w, const int32_t* clip_first_host /* [n + 1] */, int n, int target,
+                       int mode, const int32_t* cow_classes_host /* [n_cow] */, int n_cow, int32_t* rows /* [n] */,
+                       lmx_tleap_record_t* records /* [F * max_det] */, float* series /* [n][target][44] */, uint8_t* mask /* [n][target] */,
+                       void* workspace, lmx_stream_t stream);
+int lmx_h_tleap_series(const float* boxes_host, const float* scores_host, const int32_t* cls_host, const int32_t* counts_host,
+                       const float* kpts_host, int K, int ndim, int F, int max_det, int h, int w, const int32_t* clip_first_host, int n,
+                       int target, int mode, const int32_t* cow_classes_host, int n_cow, int32_t* rows_host, lmx_tleap_record_t* records_host,
+                       float* series_host, uint8_t* mask_host);
+/* compute_locomotion_features (main.py:338-436) over one clip's records, on the host.  names_host: the 20 names the caller assigns to the
+ * keypoint slots; the features look up nose, throat, withers, tailbase and left_front_paw, right_front_paw, left_back_paw, right_back_paw
+ * BY NAME (the last slot with a name wins, as in a dict), so the heuristic names above yield every feature while a trained model's names
+ * match withers only and yield NONE: the reference's quirk, kept.  Rows with n_kp < 20 are skipped (main.py:360); fewer than 2 rows give
+ * nothing.  A keypoint counts when its confidence is > 0.3.  Sums are sequential, in doubles; a standard deviation is the population's,
+ * sqrt(sum((v - mean)^2) / count); the spine angle is acos(clamp(dot / (|v1| * |v2| + 1e-6), -1, 1)) * (180 / pi) with |v| = sqrt(x*x + y*y);
+ * head_bob_frequency is the sum of |sign(d[i + 1]) - sign(d[i])| over the differences d of the nose's y, halved; an asymmetry is
+ * |a - b| / (a + b + 1e-6); lameness_score is the mean of the scores that exist.  The reference OMITS keys: bit i of `present` says that
+ * field i (in the order below, back_arch_mean = bit 0) was computed, the others are 0.  numpy adds pairwise, so its last places may
+ * differ from these sequential sums. */
+typedef struct {
+  double back_arch_mean, back_arch_std, back_arch_score, head_bob_magnitude, head_bob_frequency, head_bob_score, stride_fl_mean,
+      stride_fl_std, stride_fr_mean, stride_fr_std, stride_rl_mean, stride_rl_std, stride_rr_mean, stride_rr_std, front_leg_asymmetry,
+      rear_leg_asymmetry, lameness_score;
+  uint32_t present, reserved;
+} lmx_tleap_locomotion_t;
+int lmx_h_tleap_locomotion(const lmx_tleap_record_t* records_host, int rows, const char* const* names_host /* [20] */,
+                           lmx_tleap_locomotion_t* out_host);
+
 /* ==== The graph transformer: a cow's lameness score, its MC-dropout spread, node scores and attention per graph (csrc/gfm.hip,
  * csrc/host_gfm.cpp) ====
  * Replaces services/graph-transformer-pipeline/app/model/{graphormer,encodings,attention,layers}.py: CowLamenessGraphormer over one

@@ -112,7 +112,7 @@ inline int lmx_gait_check_call(const char* who, int n, int T, int S, double p, i
 struct LmxGaitWindow {
   int first, rows, at;
 };
-inline LmxGaitWindow lmx_gait_window(int T0, int target) {
+LMX_GAIT_HD inline LmxGaitWindow lmx_gait_window(int T0, int target) {
   if (T0 >= target) return {(T0 - target) / 2, target, 0};
   return {0, T0, (target - T0) / 2};
 }

@@ -84,6 +84,13 @@ class Rect(C.Structure):  # lmx_rect_t
     _fields_ = [(n, C.c_int32) for n in ("x", "y", "w", "h")]
 
 
+class TleapLocomotion(C.Structure):  # lmx_tleap_locomotion_t: bit i of `present` is field i
+    KEYS = ("back_arch_mean", "back_arch_std", "back_arch_score", "head_bob_magnitude", "head_bob_frequency", "head_bob_score",
+            "stride_fl_mean", "stride_fl_std", "stride_fr_mean", "stride_fr_std", "stride_rl_mean", "stride_rl_std", "stride_rr_mean",
+            "stride_rr_std", "front_leg_asymmetry", "rear_leg_asymmetry", "lameness_score")
+    _fields_ = [(k, C.c_double) for k in KEYS] + [("present", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TcnWeights(C.Structure):  # lmx_tcn_weights_t: device pointers for lmx_k_tcn_forward, host pointers for lmx_h_tcn_forward
     MAX_BLOCKS = 8
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "n_blocks", "k", "head")] + [
@@ -320,6 +327,10 @@ SIGNATURES = {
     "lmx_xfm_info": (_I, [_VP, C.POINTER(XfmInfo)]),
     "lmx_xfm_score": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "lmx_xfm_score_host": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
+    "lmx_tleap_workspace_bytes": (_I64, [_I, _I]),
+    "lmx_k_tleap_series": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lmx_h_tleap_series": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP]),
+    "lmx_h_tleap_locomotion": (_I, [_VP, _I, C.POINTER(C.c_char_p), C.POINTER(TleapLocomotion)]),
     "lmx_h_gfm_graph": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lmx_gfm_workspace_bytes": (_I64, [_I, _I64, _I]),
     "lmx_k_gfm_forward": (_I, [C.POINTER(GfmWeights), C.POINTER(GfmGraphs), _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

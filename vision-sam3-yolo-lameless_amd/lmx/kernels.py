@@ -777,6 +777,82 @@ def xfm_mask(kp_conf, n_kp, det_conf, target=125):
     return out
 
 
+# ---- pose series (include/lmx.h "Pose series"; csrc/tleap.hip, csrc/host_tleap.cpp) ----------------------------------------------------
+TLEAP_TRAINED, TLEAP_HEURISTIC = 0, 1
+
+
+def tleap_record_dtype():
+    """lmx_tleap_record_t as a numpy structured dtype (536 bytes)."""
+    import numpy as np
+
+    return np.dtype([("frame", "<i4"), ("det", "<i4"), ("bbox", "<f8", (4,)), ("confidence", "<f8"), ("n_kp", "<i4"), ("reserved", "<i4"),
+                     ("keypoints", "<f8", (20, 3))])
+
+
+def tleap_series(boxes, scores, cls, counts, kpts, hw, clip_first, target=125, cow_classes=(), host=False):
+    """lmx_k_tleap_series (host=True: lmx_h_tleap_series on CPU tensors): the detector's outputs boxes f32 [F, max_det, 4], scores f32
+    [F, max_det], cls i32 [F, max_det], counts i32 [F] and kpts f32 [F, max_det, K, ndim] (None: the heuristic mode over `cow_classes`)
+    for n clips, clip c owning frames clip_first[c] .. clip_first[c + 1] -> (rows i32 [n], records uint8 [F * max_det, 536] to view with
+    tleap_record_dtype, series f32 [n, target, 44], mask uint8 [n, target]).  ONE launch; tensors stay where the operands are."""
+    import numpy as np
+
+    ops = [boxes, scores, cls, counts] + ([kpts] if kpts is not None else [])
+    if host:
+        if any(t.is_cuda for t in ops):
+            raise LmxError("tleap_series(host=True) takes CPU tensors")
+        dev = torch.device("cpu")
+    else:
+        dev = _dev(*ops)
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise LmxError(f"tleap_series: boxes of shape {tuple(boxes.shape)}, not [F, max_det, 4]")
+    F, max_det = int(boxes.shape[0]), int(boxes.shape[1])
+    want = {"boxes": (boxes, torch.float32, (F, max_det, 4)), "scores": (scores, torch.float32, (F, max_det)),
+            "cls": (cls, torch.int32, (F, max_det)), "counts": (counts, torch.int32, (F,))}
+    K, ndim = 0, 0
+    if kpts is not None:
+        if kpts.dim() != 4:
+            raise LmxError(f"tleap_series: kpts of shape {tuple(kpts.shape)}, not [F, max_det, K, ndim]")
+        K, ndim = int(kpts.shape[2]), int(kpts.shape[3])
+        want["kpts"] = (kpts, torch.float32, (F, max_det, K, ndim))
+    for name, (t, dt, shape) in want.items():
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise LmxError(f"tleap_series: {name} is {t.dtype} {tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}, expected {dt} {shape}")
+    first = np.ascontiguousarray(clip_first, np.int32)
+    if first.ndim != 1 or len(first) < 2:
+        raise LmxError("tleap_series: clip_first holds the n + 1 bounds of n >= 1 clips")
+    n, target = len(first) - 1, int(target)
+    cow = np.ascontiguousarray(list(cow_classes), np.int32)
+    rows = torch.empty((n,), dtype=torch.int32, device=dev)
+    records = torch.empty((max(F * max_det, 1), 536), dtype=torch.uint8, device=dev)
+    series = torch.empty((n, max(target, 1), 44), dtype=torch.float32, device=dev)
+    mask = torch.empty((n, max(target, 1)), dtype=torch.uint8, device=dev)
+    h, w = hw
+    lib = _lib.load()
+    args = [_ptr(boxes), _ptr(scores), _ptr(cls), _ptr(counts), _ptr(kpts), K, ndim, F, max_det, int(h), int(w), C.c_void_p(first.ctypes.data), n,
+            target, TLEAP_TRAINED if kpts is not None else TLEAP_HEURISTIC, C.c_void_p(cow.ctypes.data if len(cow) else 0), len(cow), _ptr(rows),
+            _ptr(records), _ptr(series), _ptr(mask)]
+    if host:
+        check(lib.lmx_h_tleap_series(*args), "lmx_h_tleap_series")
+    else:
+        ws = torch.empty((max(int(lib.lmx_tleap_workspace_bytes(F, max_det)), 8) // 8,), dtype=torch.int64, device=dev)
+        check(lib.lmx_k_tleap_series(*args, _ptr(ws), _stream(dev)), "lmx_k_tleap_series")
+    return rows, records, series, mask
+
+
+def tleap_locomotion(records, names):
+    """lmx_h_tleap_locomotion: a clip's records (numpy, tleap_record_dtype) and the 20 slot names -> {key: float} with the keys the
+    reference would have set, in its order."""
+    import numpy as np
+
+    rec = np.ascontiguousarray(records, tleap_record_dtype())
+    if len(names) != 20:
+        raise LmxError(f"tleap_locomotion: {len(names)} names for 20 keypoint slots")
+    arr = (C.c_char_p * 20)(*[str(n).encode() for n in names])
+    out = _lib.TleapLocomotion()
+    check(_lib.load().lmx_h_tleap_locomotion(C.c_void_p(rec.ctypes.data if len(rec) else 0), len(rec), arr, C.byref(out)), "lmx_h_tleap_locomotion")
+    return {k: float(getattr(out, k)) for i, k in enumerate(_lib.TleapLocomotion.KEYS) if out.present >> i & 1}
+
+
 # ---- the graph transformer (include/lmx.h "The graph transformer"; csrc/gfm.hip, csrc/host_gfm.cpp) -----------------------------------
 GFM_MAX_NODES = 95
 

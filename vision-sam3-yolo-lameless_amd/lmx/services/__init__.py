@@ -15,3 +15,4 @@ from .tcn_pipeline import TCNPipeline  # noqa: F401
 from .graph_transformer_pipeline import GraphTransformerPipeline  # noqa: F401
 from .transformer_pipeline import TransformerPipeline  # noqa: F401
 from .gnn_pipeline import GNNPipeline  # noqa: F401
+from .tleap_pipeline import TLEAPPipeline  # noqa: F401

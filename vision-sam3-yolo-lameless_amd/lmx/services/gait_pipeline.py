@@ -2,7 +2,11 @@
 alike: 44 features per frame from `{id}_tleap.json` (20 keypoints relative to the bounding box, centroid, box area, centroid
 velocity), centre-cropped or centre-padded to 125 steps; one clip per message or a whole backlog in one batch; the result written to
 `{id}_{NAME}.json` and published on `pipeline.{NAME}`.  A clip is the tuple of its padded arrays (`_clip`), scored by `_score` and turned
-into the result dictionary by `_results`: those three are the subclass's."""
+into the result dictionary by `_results`: those three are the subclass's.
+
+A consumer is EITHER subscribed to the bus (`start`: it reads `{id}_tleap.json` per message) OR handed clips by a ``TLEAPPipeline`` that
+lists it among its `consumers` (`process_clip` / `process_clips`: the arrays come from the device, no file is read) — not both, or every
+clip is scored and published twice."""
 import json
 import traceback
 from pathlib import Path
@@ -20,6 +24,7 @@ class GaitPipeline:
     N_SAMPLES = 10
     NAME = None                 # "tcn": the results' directory, file suffix, `pipeline` field and subject
     LABEL = None                # "TCN": the name in printed messages
+    USES_MASK = False           # the clip tuple is (series,) or, with the key-padding mask, (series, mask)
 
     def __init__(self, scorer, bus, config=None, tleap_dir="/app/data/results/tleap", results_dir=None):
         self.config = config or R.load_config()
@@ -116,6 +121,23 @@ class GaitPipeline:
         except Exception as e:  # noqa: BLE001
             print(f"  Error in {self.LABEL} pipeline: {e}")
             traceback.print_exc()
+
+    def _accept(self, video_id, clip):
+        """The clip tuple of a handed-over (series, mask), or None where _features would have returned None for its file."""
+        return tuple(clip[:2 if self.USES_MASK else 1])
+
+    async def process_clips(self, clips):
+        """(video_id, (series f32 [125, 44], mask bool [125])) pairs from ``TLEAPPipeline``: the same `_process` as for clips read from
+        `{id}_tleap.json` — same file, same message, bit for bit — without the JSON read.  Never raises, like process_video."""
+        try:
+            ready = [(video_id, self._accept(video_id, clip)) for video_id, clip in clips]
+            await self._process([(v, c) for v, c in ready if c is not None])
+        except Exception as e:  # noqa: BLE001
+            print(f"  Error in {self.LABEL} pipeline: {e}")
+            traceback.print_exc()
+
+    async def process_clip(self, video_id, clip):
+        await self.process_clips([(video_id, clip)])
 
     async def start(self):
         await self.nats_client.connect()

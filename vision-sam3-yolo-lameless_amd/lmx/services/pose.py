@@ -1,8 +1,8 @@
 """The model half of tleap-pipeline's pose estimation on liblmx: what `self.model(frame, verbose=False, conf=0.3)` and the
 `result.boxes[j]` / `result.keypoints[j].data[0]` unpacking produce (services/tleap-pipeline/app/main.py:142-171) for a
 batch of frames.  SURVEY.md §8f rank 2: same trunk and kernels as the detector, plus the Pose head (`lmx.yolo`, cv4 branch +
-`lmx_k_pose_gather`).  The bounding-box heuristics tleap blends in afterwards (main.py:173-200) are host-side product logic
-and stay where they are: this returns the `model_keypoints` dict they start from."""
+`lmx_k_pose_gather`).  This returns the `model_keypoints` dict that tleap's blend with the bounding-box heuristics (main.py:173-200)
+starts from; the blend itself, the heuristic estimator and the rest of the service are ``lmx.tleap`` and ``TLEAPPipeline``."""
 import numpy as np
 
 # services/tleap-pipeline/app/main.py:43-64 — the 20 cow keypoints of the project's trained pose model

@@ -114,6 +114,7 @@ class Clip:
         self.n_decoded = None          # known once a pass over the clip has finished
         if frames is not None:
             self.fps = int(fps)        # the reference truncates: int(cap.get(CAP_PROP_FPS)) (Appendix C-1)
+            self.fps_exact = float(fps)  # tleap-pipeline alone keeps the float (main.py:462)
             self.total_frames = int(len(frames))
             self.n_decoded = self.total_frames
             self.frame_hw = tuple(frames.shape[1:3]) if len(frames) else (0, 0)
@@ -133,6 +134,7 @@ class Clip:
             raise Exception(f"Failed to open video: {path}")
         c = Clip(path)
         c.fps = int(cap.get(cv2.CAP_PROP_FPS))
+        c.fps_exact = float(cap.get(cv2.CAP_PROP_FPS))
         c.total_frames = int(cap.get(cv2.CAP_PROP_FRAME_COUNT))
         c.frame_hw = (int(cap.get(cv2.CAP_PROP_FRAME_HEIGHT)), int(cap.get(cv2.CAP_PROP_FRAME_WIDTH)))
         cap.release()

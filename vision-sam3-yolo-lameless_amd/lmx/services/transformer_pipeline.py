@@ -18,6 +18,7 @@ class TransformerPipeline(GaitPipeline):
     NAME, LABEL = "transformer", "Transformer"
     MASK_BELOW = 0.3            # mean keypoint confidence x detection confidence
     SALIENCY_SHOWN = 20
+    USES_MASK = True
 
     def extract_features_from_tleap(self, tleap_data):
         """main.py:303-372: (float32 [frames, 44], bool [frames], True = masked), or (None, None) without pose_sequences.  The
@@ -51,6 +52,13 @@ class TransformerPipeline(GaitPipeline):
             print(f"  Every step of {video_id} is masked (low confidence): no score")
             return None
         return clip
+
+    def _accept(self, video_id, clip):
+        """As the base, with the refusal of _features"""
+        if clip[1].all():
+            print(f"  Every step of {video_id} is masked (low confidence): no score")
+            return None
+        return super()._accept(video_id, clip)
 
     def _score(self, video_ids, series, masks):
         """(severity, uncertainty, saliency) per clip from TWO launches over the stacked series"""
