@@ -1577,6 +1577,77 @@ int lmx_h_xfm_tensors(const char* who, const lmx_xfm_weights_t* config_host, lmx
 int lmx_h_gfm_tensors(const char* who, const lmx_gfm_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host);
 int lmx_h_gnn_tensors(const char* who, const lmx_gnn_weights_t* config_host, lmx_tensor_row_t* rows_host, int cap, int* n_host);
 
+/* ==== Vector store: cosine top-k over a gallery of unit rows in HBM (csrc/vstore.hip, csrc/host_vstore.cpp, csrc/vstore_model.hip) =======
+ * The one piece of arithmetic dinov3-pipeline (search_similar) and tracking-service (reid/matcher.py) go to Qdrant for.
+ *
+ * lmx_k_cosine_topk: gallery f32 unit rows [N][D] with a row stride of ldg elements (a store with spare capacity is a view), queries f32
+ * unit rows [Q][D], dense.  Query q sees the slots [0, limits[q]) (clamped to [0, N]), or [0, N) when limits is NULL: a backlog of B new
+ * rows is searched in ONE launch with the results of B search-then-append steps by giving query j the limit old_count + j.  For every
+ * query: the k best visible rows in descending score, scores compared as float values, exact ties to the LOWER slot first; ranks past
+ * the number of visible rows get slot -1 and score 0.  The order of (score, slot) pairs is total and a score is the PINNED DOT PRODUCT
+ * below, so a result is a function of the inputs alone: it depends on no launch geometry, on no other query of the batch and on no
+ * other row of the gallery, and there are no atomics.  A NaN score never ranks.
+ *
+ * THE PINNED DOT PRODUCT of a gallery row g and a query q, both of D elements:
+ *   256 partials p[0 .. 255], each +0 at the start;
+ *   partial j takes the elements j, j + 256, j + 512, ... in ascending order: p[j] = fmaf(g[i], q[i], p[j]); elements past D contribute
+ *   nothing (partials past D stay +0);
+ *   the partials are combined by halving: for w = 128, 64, ..., 1: p[j] = p[j] + p[j + w] for every j < w, each a single f32 add;
+ *   the score is p[0].
+ * (On the device: one wave per row, one 16-byte load per lane per 256 elements, lane l holds the partials 4 l .. 4 l + 3; the steps
+ * w >= 4 are xor-butterflies across lanes, the last two are inside the lane.)  At most ceil(D / 256) + 8 roundings lie on the longest
+ * path, each relative to at most sum |g[i] q[i]| <= 1: |score - exact| <= (ceil(D / 256) + 8) * 2^-24 for unit rows.
+ *
+ * Limits, refused with LMX_EINVAL and a message before anything is read, written or launched: D % 4 == 0 and 4 <= D <= 4096; 1 <= k <=
+ * 32; 0 <= N <= 2^31 - 1; 0 <= Q <= 65535; ldg >= D and ldg % 4 == 0; gallery and queries 16-byte aligned.  Row offsets are 64-bit.
+ * `workspace`: lmx_h_cosine_topk_workspace(N, Q, k) bytes, 8-byte aligned; it needs no clearing.  The call only enqueues on `stream`
+ * (two kernels).  lmx_h_cosine_topk_geometry: the scan's rows per workgroup pass, its query tile at dimension D (8 up to D = 1024, 4 up
+ * to 2048, 2 above) and its workgroups per CU, for tests that must reach every branch; none of them can show in a result.
+ * lmx_h_cosine_topk is the same arithmetic in plain C++ on HOST pointers (no alignment asked); the device is held to it bit for bit.
+ *
+ * lmx_k_unit_rows / lmx_h_unit_rows: raw rows [n][D] (dense; dtype LMX_VSTORE_F32 or LMX_VSTORE_F64) -> f32 unit rows with a row
+ * stride of ldo elements.  The sum of squares ss is taken in double in the same 256-partial order with fma; element i becomes
+ * (float)((double)x[i] / (sqrt(ss) + 1e-8)) — the epsilon and its place are those of reid/matcher.py and csrc/graph.h.  A zero row
+ * gives zeros.  Same limits on D. */
+#define LMX_VSTORE_F32 1
+#define LMX_VSTORE_F64 2
+int64_t lmx_h_cosine_topk_workspace(int64_t N, int Q, int k);
+int lmx_h_cosine_topk_geometry(int D, int* rows_host, int* tile_host, int* wg_per_cu_host);
+int lmx_k_cosine_topk(const float* gallery /* [N][ldg] */, int64_t N, int D, int64_t ldg, const float* queries /* [Q][D] */, int Q,
+                      const int32_t* limits /* NULL or [Q] */, int k, float* scores /* [Q][k] */, int32_t* slots /* [Q][k] */, void* workspace,
+                      lmx_stream_t stream);
+int lmx_h_cosine_topk(const float* gallery_host, int64_t N, int D, int64_t ldg, const float* queries_host, int Q, const int32_t* limits_host,
+                      int k, float* scores_host, int32_t* slots_host);
+int lmx_k_unit_rows(const void* raw /* [n][D] */, int dtype, int64_t n, int D, float* out /* [n][ldo] */, int64_t ldo, lmx_stream_t stream);
+int lmx_h_unit_rows(const void* raw_host, int dtype, int64_t n, int D, float* out_host, int64_t ldo);
+
+/* lmx_vstore: a growing gallery of unit rows in HBM behind a handle.  It maps nothing but SLOTS (row numbers 0 .. count - 1); ids and
+ * payloads belong to the caller.  lmx_vstore_open takes the current device; every later call must be made with that device current
+ * and a stream of that device (LMX_EINVAL otherwise, nothing launched).  lmx_vstore_put_host: one raw row from HOST memory, normalised
+ * by lmx_h_unit_rows; slot == count appends, a lower slot replaces in place, any other slot is refused.  lmx_vstore_append: n raw rows
+ * already on the DEVICE, normalised by lmx_k_unit_rows (the same bits).  The gallery grows by doubling; put_host, append and get_host
+ * are SYNCHRONOUS (they return with the row in place, and wait for the device's earlier work first).  lmx_vstore_get_host: the stored
+ * unit row; lmx_vstore_read_host: n of them from slot `first`; lmx_vstore_restore_host appends n rows that ARE unit rows as they stand,
+ * byte for byte (what read_host returned: a saved store comes back with the bits it had).  lmx_vstore_gallery: the rows as lmx_k_cosine_topk takes them; the pointer holds until the next put_host or append.
+ * lmx_vstore_search: raw queries [Q][dim] on the DEVICE are normalised and searched over the stored rows with lmx_k_cosine_topk; it
+ * enqueues on `stream`, except that the first search at a larger Q x k grows the handle's scratch synchronously.  limits as for
+ * lmx_k_cosine_topk (DEVICE memory, or NULL).  lmx_vstore_search_host takes the queries and limits from, and returns scores and slots
+ * in, HOST memory, on the handle's own stream, and synchronises (examples/vstore_search.c). */
+typedef struct lmx_vstore lmx_vstore;
+int lmx_vstore_open(int dim, int64_t capacity, lmx_vstore** out_host);
+void lmx_vstore_close(lmx_vstore* m);
+int64_t lmx_vstore_count(const lmx_vstore* m);
+int lmx_vstore_gallery(const lmx_vstore* m, const float** gallery, int64_t* ldg_host);
+int lmx_vstore_put_host(lmx_vstore* m, int64_t slot, const void* raw_host, int dtype);
+int lmx_vstore_append(lmx_vstore* m, const void* raw_rows, int dtype, int64_t n);
+int lmx_vstore_get_host(lmx_vstore* m, int64_t slot, float* out_host);
+int lmx_vstore_read_host(lmx_vstore* m, int64_t first, int64_t n, float* out_host);
+int lmx_vstore_restore_host(lmx_vstore* m, const float* unit_rows_host, int64_t n);
+int lmx_vstore_search(lmx_vstore* m, const void* raw_queries, int dtype, int Q, const int32_t* limits, int k, float* scores, int32_t* slots,
+                      lmx_stream_t stream);
+int lmx_vstore_search_host(lmx_vstore* m, const void* raw_queries_host, int dtype, int Q, const int32_t* limits_host, int k, float* scores_host,
+                           int32_t* slots_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -356,6 +356,23 @@ SIGNATURES = {
     "lmx_h_xfm_tensors": (_I, [C.c_char_p, C.POINTER(XfmWeights), C.POINTER(TensorRow), _I, C.POINTER(_I)]),
     "lmx_h_gfm_tensors": (_I, [C.c_char_p, C.POINTER(GfmWeights), C.POINTER(TensorRow), _I, C.POINTER(_I)]),
     "lmx_h_gnn_tensors": (_I, [C.c_char_p, C.POINTER(GnnWeights), C.POINTER(TensorRow), _I, C.POINTER(_I)]),
+    "lmx_h_cosine_topk_workspace": (_I64, [_I64, _I, _I]),
+    "lmx_h_cosine_topk_geometry": (_I, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "lmx_k_cosine_topk": (_I, [_VP, _I64, _I, _I64, _VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
+    "lmx_h_cosine_topk": (_I, [_VP, _I64, _I, _I64, _VP, _I, _VP, _I, _VP, _VP]),
+    "lmx_k_unit_rows": (_I, [_VP, _I, _I64, _I, _VP, _I64, _VP]),
+    "lmx_h_unit_rows": (_I, [_VP, _I, _I64, _I, _VP, _I64]),
+    "lmx_vstore_open": (_I, [_I, _I64, C.POINTER(_VP)]),
+    "lmx_vstore_close": (None, [_VP]),
+    "lmx_vstore_count": (_I64, [_VP]),
+    "lmx_vstore_gallery": (_I, [_VP, C.POINTER(_VP), C.POINTER(_I64)]),
+    "lmx_vstore_put_host": (_I, [_VP, _I64, _VP, _I]),
+    "lmx_vstore_append": (_I, [_VP, _VP, _I, _I64]),
+    "lmx_vstore_get_host": (_I, [_VP, _I64, _VP]),
+    "lmx_vstore_read_host": (_I, [_VP, _I64, _I64, _VP]),
+    "lmx_vstore_restore_host": (_I, [_VP, _VP, _I64]),
+    "lmx_vstore_search": (_I, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP, _VP]),
+    "lmx_vstore_search_host": (_I, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP]),
 }
 
 _lib = None

@@ -530,6 +530,48 @@ def frame_quality(frames, out=None):
     return out
 
 
+# ---- the vector store (include/lmx.h "Vector store", csrc/vstore.hip) ---------------------------------------------------------------
+VSTORE_DT = {torch.float32: 1, torch.float64: 2}  # LMX_VSTORE_F32, LMX_VSTORE_F64
+
+
+def unit_rows(raw, out=None):
+    """raw f32 or f64 [n,D], contiguous -> f32 unit rows [n,D] (lmx_k_unit_rows): the sum of squares in double in the pinned 256-partial
+    order, (float)((double)x / (sqrt(ss) + 1e-8)).  `out`: a [n,D] f32 view whose rows are contiguous (a slice of a gallery)."""
+    dev = _dev(raw, out)
+    if raw.dim() != 2 or not raw.is_contiguous() or raw.dtype not in VSTORE_DT:
+        raise LmxError(f"unit_rows: raw must be a contiguous f32 or f64 [n,D] tensor, got {raw.dtype} {tuple(raw.shape)} strides {raw.stride()}")
+    n, D = raw.shape
+    if out is None:
+        out = torch.empty((n, D), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != (n, D) or _rows(out, "unit_rows out")[2] < D:
+        raise LmxError(f"unit_rows: out must be an f32 [{n},{D}] tensor with contiguous rows")
+    check(_lib.load().lmx_k_unit_rows(_ptr(raw), VSTORE_DT[raw.dtype], n, D, _ptr(out), out.stride(0) if n > 1 else D, _stream(dev)), "lmx_k_unit_rows")
+    return out
+
+
+def cosine_topk(gallery, queries, k, limits=None):
+    """gallery f32 unit rows [N,D] (rows contiguous, any row stride that is a multiple of 4), queries f32 unit rows [Q,D], limits None or
+    int32 [Q] -> (scores f32 [Q,k], slots int32 [Q,k]) by lmx_k_cosine_topk: per query the k best of the slots [0, limits[q]) in descending
+    score, exact ties to the lower slot, slot -1 / score 0 past the visible rows."""
+    dev = _dev(gallery, queries, limits)
+    if gallery.dtype != torch.float32 or queries.dtype != torch.float32 or queries.dim() != 2 or not queries.is_contiguous():
+        raise LmxError(f"cosine_topk: f32 gallery and contiguous f32 queries [Q,D], got {gallery.dtype} and {queries.dtype} {tuple(queries.shape)}")
+    N, D, ldg = _rows(gallery, "cosine_topk gallery")
+    Q = queries.shape[0]
+    if queries.shape[1] != D:
+        raise LmxError(f"cosine_topk: queries of {queries.shape[1]} elements against rows of {D}")
+    if limits is not None and (limits.dtype != torch.int32 or tuple(limits.shape) != (Q,) or not limits.is_contiguous()):
+        raise LmxError(f"cosine_topk: limits must be a contiguous int32 [{Q}] tensor")
+    lib = _lib.load()
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    slots = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    nws = int(lib.lmx_h_cosine_topk_workspace(N, Q, k))
+    ws = torch.empty((max(nws, 8),), dtype=torch.uint8, device=dev)
+    check(lib.lmx_k_cosine_topk(_ptr(gallery), N, D, ldg if N > 1 else max(ldg, D), _ptr(queries), Q, _ptr(limits), k, _ptr(scores), _ptr(slots),
+                                _ptr(ws), _stream(dev)), "lmx_k_cosine_topk")
+    return scores, slots
+
+
 # ---- the weight tables of the TCN, the gait transformer, the graph transformer and GraphGPS -------------------------------------------
 # Which tensors a configuration calls for, their names, shapes and the pointer of lmx_<model>_weights_t each one fills, and which
 # configurations are accepted at all, are stated once, in the library (include/lmx.h lmx_h_<model>_tensors; csrc/weights_table.h).
