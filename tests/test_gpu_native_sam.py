@@ -16,7 +16,8 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # padding rows (nh < 1024), padding columns (nw < 1024), no padding
-SIZES = {"96x160": (96, 160), "150x100": (150, 100), "64x64": (64, 64)}
+# 139x157: w % 4 == 1 and w % 8 == 5 (mask rows at every byte residue, a partial last byte per row of mask_bits)
+SIZES = {"96x160": (96, 160), "150x100": (150, 100), "64x64": (64, 64), "139x157": (139, 157)}
 IMAGE_PLANS = {"S64": ("f16", "exact"), "S80": ("f16",)}
 GRID = [(name, plan) for name, plans in IMAGE_PLANS.items() for plan in plans]
 OUT = ("mask", "stats", "iou", "lowres", "mask_bits", "contour")
@@ -172,6 +173,23 @@ def test_segment_equals_encode_then_decode(models, name, plan):
     _assert_same(ns.segment(frames, boxes, plan), want, what=f"{name} {plan}")
     two_step = ns.decode(ns.encode(frames, plan), boxes, (h, w), plan)
     _assert_same(two_step, want, what=f"{name} {plan} encode + decode")
+
+
+@pytest.mark.parametrize("plan", ["f16", "exact"])
+def test_segment_at_an_odd_width(models, plan):
+    """139 x 157: the handle carves mask, mask_bits and contour space out of one workspace, here with w % 4 != 0 and w % 8 != 0;
+    besides equality with the Python plan, mask_bits is numpy.packbits of the mask that came back with it."""
+    h, w = SIZES["139x157"]
+    frames, boxes = models.frames(h, w)
+    want = models.ref("S64", plan, h, w)
+    got = models.handle("S64").segment(frames, boxes, plan)
+    _assert_same(got, want, what=f"S64 {plan} 139x157")
+    mask = got["mask"].cpu().numpy()
+    assert mask.shape == (3, h, w) and set(np.unique(mask)) <= {0, 1}
+    assert np.array_equal(got["mask_bits"].cpu().numpy(), np.packbits(mask, axis=-1))
+    areas = want["stats"][:, 0].tolist()
+    print(f"S64 {plan} 139x157: mask areas {areas}")
+    assert any(0 < a < h * w for a in areas), "every reference mask is empty or full: the bits say nothing"
 
 
 def test_an_output_left_out_corrupts_nothing(models):
