@@ -132,6 +132,25 @@ def test_batches_beyond_max_batch(models, name):
     assert torch.equal(nd.embed(frames[:1].contiguous())[0], got7[0]), "frame 0 alone differs from frame 0 inside the 7"
 
 
+@pytest.mark.parametrize("name", ["dinov2_base", "dinov3_float"])
+def test_a_call_leaves_nothing_behind_for_the_next(models, cuda, name):
+    """n = 3, then 1, then 3 frames on ONE handle with max_batch = 3 (Pillow recipe and float recipe).  A call's buffers lie where its
+    own walk of the plan puts them, so the smaller call lays them over what the larger one left and the larger one over that again:
+    each result equals, bit for bit, that of a fresh handle given the same call alone."""
+    from lmx import native
+
+    _, path = models.model(name)
+    frames = models.frames(270, 481, 3)
+    with native.NativeDino(path, 3, cuda) as nd:
+        for n in (3, 1, 3):
+            sub = frames[:n].contiguous()
+            got = nd.embed(sub)
+            with native.NativeDino(path, 3, cuda) as fresh:
+                want = fresh.embed(sub)
+            assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0
+            assert torch.equal(got, want), f"n = {n}: max abs difference {float((got - want).abs().max())}"
+
+
 def test_two_sizes_alternate_on_one_handle(models):
     emb, _ = models.model("dinov3_vitsplus16")
     nd = models.handle("dinov3_vitsplus16")

@@ -252,6 +252,25 @@ def test_chunks(models, plan):
     assert torch.equal(models.handle("S64", 2).encode(frames, plan), want["emb"])
 
 
+@pytest.mark.parametrize("plan", ["f16", "exact"])
+def test_a_call_leaves_nothing_behind_for_the_next(models, cuda, plan):
+    """n = 3, then 1, then 3 frames of 64 x 96 on ONE handle with max_batch = 3.  A call's buffers lie where its own walk of the plan
+    puts them, so the smaller call lays them over what the larger one left and the larger one over that again: each result equals,
+    bit for bit, that of a fresh handle given the same call alone."""
+    from lmx import native
+
+    frames, boxes = models.frames(64, 96, 3)
+    path = models.model("S64")[2]
+    with native.NativeSam(path, 3, cuda) as ns:
+        for n in (3, 1, 3):
+            f, b = frames[:n].contiguous(), boxes[:n].contiguous()
+            got = ns.segment(f, b, plan)
+            with native.NativeSam(path, 3, cuda) as fresh:
+                want = fresh.segment(f, b, plan)
+            _assert_same(got, want, what=f"{plan}, n = {n}")
+            assert bool(torch.isfinite(want["lowres"]).all()) and float(want["lowres"].std()) > 0
+
+
 def test_two_sizes_alternate_on_one_handle(models):
     ns = models.handle("S64")
     (fa, ba), (fb, bb) = models.frames(*SIZES["96x160"]), models.frames(*SIZES["150x100"])

@@ -4,6 +4,10 @@
 // HOST code only: there is no kernel in this file.  Every launch goes through the same extern "C" lmx_k_* entry point the ctypes
 // binding calls, with the descriptor filled as lmx/kernels.py fills it, so the embedding is the Python plan's bit for bit
 // (tests/test_gpu_native_dino.py).
+// The transformer's buffers come from a run of plan_run.h: lmx_dino_open_host walks embed_chunk counting at max_batch (they do not
+// depend on the frame size), every call walks it launching.  The run refuses a buffer of 2 GB or more by name.  That also keeps every
+// element index the kernels form below 2^31: the widest rows are qkv's 3 hidden and the MLP GEMM's 2 mlp columns (gated), and a row
+// index times either stays below the BYTES of the f16 qkv and MLP buffers, which the run bounds: no separate check on elements.
 #include <math.h>
 #include <string.h>
 
@@ -36,15 +40,14 @@ struct Layer {
 
 struct lmx_dino : LmxHandleCore {
   LmxDinoCfg cfg;
-  char* work = nullptr;  // the workspace of max_batch frames
+  char* work = nullptr;  // the workspace of max_batch frames: the patch matrix, then the arena of embed_chunk's buffers
+  LmxArena arena;        // ... as open counted it (base and cap); a call walks a copy
   // weights
   const void* pe_w = nullptr;
   const float *pe_b = nullptr, *prefix = nullptr, *pos = nullptr, *rope_cos = nullptr, *rope_sin = nullptr, *gf = nullptr, *bf = nullptr,
               *lut = nullptr;
   std::vector<Layer> layers;
-  // workspace: patch matrix, patch embedding, residual stream, LayerNorm rows, qkv, attention output, MLP intermediate, final rows
-  void *patches = nullptr, *xp = nullptr, *h = nullptr, *qkv = nullptr, *a = nullptr, *u = nullptr;
-  float *x = nullptr, *y = nullptr;
+  void* patches = nullptr;  // the patch matrix [max_batch, grid^2, k_pad], a field: its padding columns are zeroed once, at open
   float mean_std[6];
   std::map<std::pair<int, int>, FrameSize> sizes;
 };
@@ -56,57 +59,6 @@ void destroy(lmx_dino* m) {
   (void)hipFree(m->work);
   lmx_handle_free(m);
   delete m;
-}
-
-int open_into(lmx_dino* m, const char* path) {
-  const int max_batch = m->max_batch;
-  LmxDinoImage img;
-  LMX_TRY(lmx_dino_image_parse(path, &img));
-  const LmxDinoCfg& c = img.cfg;
-  const int64_t widest = (int64_t)(3 * c.hidden > 2 * c.mlp ? 3 * c.hidden : 2 * c.mlp);
-  LMX_REQUIRE((int64_t)max_batch * c.tokens * widest < ((int64_t)1 << 31),
-              "lmx_dino_open_host: max_batch %d x tokens %d x the widest row %lld does not fit 32-bit element indices", max_batch, c.tokens,
-              (long long)widest);
-  m->cfg = c;
-  for (int i = 0; i < 3; ++i) {
-    m->mean_std[i] = (float)c.mean[i];
-    m->mean_std[3 + i] = (float)c.std[i];
-  }
-  LMX_TRY(lmx_handle_upload_weights(m, "lmx_dino_open_host", path, img.data_offset, img.file_bytes));
-  const uint64_t base = img.data_offset;
-  auto at = [&](const LmxTensorRef& r) -> const void* { return r.nbytes ? m->weights + (r.offset - base) : nullptr; };
-  auto f32 = [&](const LmxTensorRef& r) { return static_cast<const float*>(at(r)); };
-  m->pe_w = at(img.pe_w);
-  m->pe_b = f32(img.pe_b);
-  m->prefix = f32(img.prefix);
-  m->pos = f32(img.pos);
-  m->rope_cos = f32(img.rope_cos);
-  m->rope_sin = f32(img.rope_sin);
-  m->gf = f32(img.gf);
-  m->bf = f32(img.bf);
-  m->lut = f32(img.lut);
-  for (const LmxDinoLayerRefs& r : img.layers)
-    m->layers.push_back(Layer{f32(r.g1), f32(r.b1), f32(r.bqkv), f32(r.bo), f32(r.ls1), f32(r.g2), f32(r.b2), f32(r.bb1), f32(r.bb2), f32(r.ls2),
-                              at(r.wqkv), at(r.wo), at(r.w1), at(r.w2)});
-
-  // the workspace of max_batch frames: one allocation, every buffer on a 256-byte boundary
-  const size_t B = (size_t)max_batch, T = (size_t)c.tokens, D = (size_t)c.hidden, I = (size_t)c.mlp, np = (size_t)c.grid * c.grid;
-  LmxLayout lay;
-  const size_t patch_bytes = B * np * c.k_pad * 2;
-  const size_t o_patches = lay.add(patch_bytes), o_xp = lay.add(B * np * D * 2), o_x = lay.add(B * T * D * 4), o_h = lay.add(B * T * D * 2),
-               o_qkv = lay.add(B * T * 3 * D * 2), o_a = lay.add(B * T * D * 2), o_u = lay.add(B * T * I * 2), o_y = lay.add(B * T * D * 4);
-  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->work), lay.total));
-  // the patch matrix's columns beyond 3 * patch^2 (k_pad) are never written by a kernel: zero once, as kernels.patchify_norm's torch.zeros
-  LMX_HIP(hipMemset(m->work + o_patches, 0, patch_bytes));
-  m->patches = m->work + o_patches;
-  m->xp = m->work + o_xp;
-  m->x = reinterpret_cast<float*>(m->work + o_x);
-  m->h = m->work + o_h;
-  m->qkv = m->work + o_qkv;
-  m->a = m->work + o_a;
-  m->u = m->work + o_u;
-  m->y = reinterpret_cast<float*>(m->work + o_y);
-  return LMX_OK;
 }
 
 // one axis of the float recipe: ATen's table, cut to the rows the centre crop keeps (TorchvisionBackend.center_crop: int((size - crop) / 2))
@@ -182,58 +134,110 @@ int prepare(lmx_dino* m, int h, int w, const FrameSize** out) {
   return LMX_OK;
 }
 
+// one walk of embed_chunk: counting at open (m null), or launching over a copy of the handle's arena
+struct DinoRun : LmxPlanRun {
+  LmxArena arena;
+  DinoRun(const char* fn_, const lmx_dino* m, hipStream_t st_) {
+    fn = fn_, model = "DINO", st = st_, launch = m != nullptr;
+    if (m) arena = m->arena;
+  }
+};
+
 // DinoEmbedder.preprocess + hidden_states + token_mean for n <= max_batch frames
-int embed_chunk(lmx_dino* m, const FrameSize& fs, const uint8_t* frames, int n, int h, int w, int rgb, float* emb, hipStream_t st) {
+int embed_chunk(DinoRun& R, const lmx_dino* m, const FrameSize& fs, const uint8_t* frames, int n, int h, int w, int rgb, float* emb) {
   const LmxDinoCfg& c = m->cfg;
   const int D = c.hidden, H = c.heads, hd = D / H, T = c.tokens, I = c.mlp, np = c.grid * c.grid, rows = n * T;
+  hipStream_t st = lmx_run_stream(R);
+  LmxArena* A = &R.arena;
+  R.rewind_to(A, 0);
   if (c.recipe_kind == LMX_RECIPE_FLOAT) {
-    LMX_TRY(lmx_k_float_resize_patchify(frames, m->patches, n, h, w, c.grid, c.grid, c.patch, c.k_pad, fs.bounds_h,
-                                        static_cast<const float*>(fs.kk_h), fs.ksize_h, fs.bounds_v, static_cast<const float*>(fs.kk_v), fs.ksize_v,
-                                        fs.seg_cols, (float)c.rescale, m->mean_std, rgb ? 0 : 1, st));
+    LMX_LAUNCH(R, lmx_k_float_resize_patchify(frames, m->patches, n, h, w, c.grid, c.grid, c.patch, c.k_pad, fs.bounds_h,
+                                              static_cast<const float*>(fs.kk_h), fs.ksize_h, fs.bounds_v, static_cast<const float*>(fs.kk_v), fs.ksize_v,
+                                              fs.seg_cols, (float)c.rescale, m->mean_std, rgb ? 0 : 1, st));
   } else {
-    LMX_TRY(lmx_k_pil_resize_h(frames, fs.tmp_h, n, h, w, fs.nw, fs.bounds_h, static_cast<const int32_t*>(fs.kk_h), fs.ksize_h, rgb ? 0 : 1, st));
+    LMX_LAUNCH(R, lmx_k_pil_resize_h(frames, fs.tmp_h, n, h, w, fs.nw, fs.bounds_h, static_cast<const int32_t*>(fs.kk_h), fs.ksize_h, rgb ? 0 : 1, st));
     const uint8_t* img = fs.tmp_h;
     if (fs.tmp_v) {
-      LMX_TRY(lmx_k_pil_resize_v(fs.tmp_h, fs.tmp_v, n, h, fs.nh, fs.nw, fs.bounds_v, static_cast<const int32_t*>(fs.kk_v), fs.ksize_v, st));
+      LMX_LAUNCH(R, lmx_k_pil_resize_v(fs.tmp_h, fs.tmp_v, n, h, fs.nh, fs.nw, fs.bounds_v, static_cast<const int32_t*>(fs.kk_v), fs.ksize_v, st));
       img = fs.tmp_v;
     }
-    LMX_TRY(lmx_k_patchify_norm(img, m->patches, n, fs.nh, fs.nw, (fs.nh - c.image) / 2, (fs.nw - c.image) / 2, c.grid, c.grid, c.patch, c.k_pad,
-                                m->lut, st));
+    LMX_LAUNCH(R, lmx_k_patchify_norm(img, m->patches, n, fs.nh, fs.nw, (fs.nh - c.image) / 2, (fs.nw - c.image) / 2, c.grid, c.grid, c.patch, c.k_pad,
+                                      m->lut, st));
   }
-  LMX_TRY(lmx_gemm_dense(m->patches, c.k_pad, m->pe_w, m->pe_b, m->xp, D, LMX_F16, n * np, D, c.k_pad, LMX_ACT_NONE, nullptr, nullptr, 0, st));
-  LMX_TRY(lmx_k_assemble_tokens(m->xp, m->prefix, m->pos, m->x, n, np, c.n_prefix, D, st));
+  const int64_t e16 = 2, e32 = 4, prows = (int64_t)n * np, trows = rows;  // bytes per element; patch and token rows
+  half_t *xp, *hn, *qkv, *a, *u;
+  float *x, *y;
+  LMX_TRY(R.take(A, "patch embedding", prows * D * e16, &xp));
+  LMX_LAUNCH(R, lmx_gemm_dense(m->patches, c.k_pad, m->pe_w, m->pe_b, xp, D, LMX_F16, n * np, D, c.k_pad, LMX_ACT_NONE, nullptr, nullptr, 0, st));
+  LMX_TRY(R.take(A, "residual stream", trows * D * e32, &x));
+  LMX_LAUNCH(R, lmx_k_assemble_tokens(xp, m->prefix, m->pos, x, n, np, c.n_prefix, D, st));
   const float scale = (float)pow((double)hd, -0.5), eps = (float)c.eps;
   const int act1 = c.gated ? LMX_ACT_SWIGLU : LMX_ACT_GELU, N1 = c.gated ? 2 * I : I;
-  half_t* q = static_cast<half_t*>(m->qkv);
+  // what every layer writes anew: LayerNorm rows, qkv, attention output, MLP intermediate
+  LMX_TRY(R.take(A, "LayerNorm rows", trows * D * e16, &hn));
+  LMX_TRY(R.take(A, "qkv", trows * 3 * D * e16, &qkv));
+  LMX_TRY(R.take(A, "attention output", trows * D * e16, &a));
+  LMX_TRY(R.take(A, "MLP intermediate", trows * I * e16, &u));
   for (const Layer& L : m->layers) {
-    LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, L.g1, L.b1, m->h, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
-    LMX_TRY(lmx_gemm_dense(m->h, D, L.wqkv, L.bqkv, m->qkv, 3 * D, LMX_F16, rows, 3 * D, D, LMX_ACT_NONE, nullptr, nullptr, 0, st));
+    LMX_LAUNCH(R, lmx_k_layernorm(x, LMX_F32, D, L.g1, L.b1, hn, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
+    LMX_LAUNCH(R, lmx_gemm_dense(hn, D, L.wqkv, L.bqkv, qkv, 3 * D, LMX_F16, rows, 3 * D, D, LMX_ACT_NONE, nullptr, nullptr, 0, st));
     if (m->rope_cos) {
-      LMX_TRY(lmx_k_rope(q, 3 * D, n, T, H, hd, c.n_prefix, m->rope_cos, m->rope_sin, st));
-      LMX_TRY(lmx_k_rope(q + D, 3 * D, n, T, H, hd, c.n_prefix, m->rope_cos, m->rope_sin, st));
+      LMX_LAUNCH(R, lmx_k_rope(qkv, 3 * D, n, T, H, hd, c.n_prefix, m->rope_cos, m->rope_sin, st));
+      LMX_LAUNCH(R, lmx_k_rope(qkv + D, 3 * D, n, T, H, hd, c.n_prefix, m->rope_cos, m->rope_sin, st));
     }
-    lmx_attn_desc ad;
-    memset(&ad, 0, sizeof(ad));
-    ad.Q = q;
-    ad.K = q + D;
-    ad.V = q + 2 * D;
-    ad.O = m->a;
-    ad.ldq = ad.ldk = ad.ldv = 3 * D;
-    ad.ldo = D;
-    ad.B = n;
-    ad.H = H;
-    ad.Tq = ad.Tk = T;
-    ad.hd = hd;
-    ad.scale = scale;
-    ad.mode = 0;
-    LMX_TRY(lmx_k_attention(&ad, st));
-    LMX_TRY(lmx_gemm_dense(m->a, D, L.wo, L.bo, m->x, D, LMX_F32, rows, D, D, LMX_ACT_NONE, L.ls1, m->x, D, st));
-    LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, L.g2, L.b2, m->h, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
-    LMX_TRY(lmx_gemm_dense(m->h, D, L.w1, L.bb1, m->u, I, LMX_F16, rows, N1, D, act1, nullptr, nullptr, 0, st));
-    LMX_TRY(lmx_gemm_dense(m->u, I, L.w2, L.bb2, m->x, D, LMX_F32, rows, D, I, LMX_ACT_NONE, L.ls2, m->x, D, st));
+    if (R.launch) {
+      const lmx_attn_desc ad = lmx_attn_flat(qkv, 3 * D, qkv + D, qkv + 2 * D, 3 * D, a, D, n, H, T, T, hd, scale);
+      LMX_TRY(lmx_k_attention(&ad, st));
+    }
+    LMX_LAUNCH(R, lmx_gemm_dense(a, D, L.wo, L.bo, x, D, LMX_F32, rows, D, D, LMX_ACT_NONE, L.ls1, x, D, st));
+    LMX_LAUNCH(R, lmx_k_layernorm(x, LMX_F32, D, L.g2, L.b2, hn, LMX_F16, D, rows, D, eps, LMX_ACT_NONE, st));
+    LMX_LAUNCH(R, lmx_gemm_dense(hn, D, L.w1, L.bb1, u, I, LMX_F16, rows, N1, D, act1, nullptr, nullptr, 0, st));
+    LMX_LAUNCH(R, lmx_gemm_dense(u, I, L.w2, L.bb2, x, D, LMX_F32, rows, D, I, LMX_ACT_NONE, L.ls2, x, D, st));
   }
-  LMX_TRY(lmx_k_layernorm(m->x, LMX_F32, D, m->gf, m->bf, m->y, LMX_F32, D, rows, D, eps, LMX_ACT_NONE, st));
-  return lmx_k_token_mean(m->y, LMX_F32, emb, n, T, D, st);
+  LMX_TRY(R.take(A, "final LayerNorm rows", trows * D * e32, &y));
+  LMX_LAUNCH(R, lmx_k_layernorm(x, LMX_F32, D, m->gf, m->bf, y, LMX_F32, D, rows, D, eps, LMX_ACT_NONE, st));
+  LMX_LAUNCH(R, lmx_k_token_mean(y, LMX_F32, emb, n, T, D, st));
+  return LMX_OK;
+}
+
+int open_into(lmx_dino* m, const char* path) {
+  const int max_batch = m->max_batch;
+  LmxDinoImage img;
+  LMX_TRY(lmx_dino_image_parse(path, &img));
+  const LmxDinoCfg& c = img.cfg;
+  m->cfg = c;
+  for (int i = 0; i < 3; ++i) {
+    m->mean_std[i] = (float)c.mean[i];
+    m->mean_std[3 + i] = (float)c.std[i];
+  }
+  LMX_TRY(lmx_handle_upload_weights(m, "lmx_dino_open_host", path, img.data_offset, img.file_bytes));
+  const uint64_t base = img.data_offset;
+  auto at = [&](const LmxTensorRef& r) -> const void* { return r.nbytes ? m->weights + (r.offset - base) : nullptr; };
+  auto f32 = [&](const LmxTensorRef& r) { return static_cast<const float*>(at(r)); };
+  m->pe_w = at(img.pe_w);
+  m->pe_b = f32(img.pe_b);
+  m->prefix = f32(img.prefix);
+  m->pos = f32(img.pos);
+  m->rope_cos = f32(img.rope_cos);
+  m->rope_sin = f32(img.rope_sin);
+  m->gf = f32(img.gf);
+  m->bf = f32(img.bf);
+  m->lut = f32(img.lut);
+  for (const LmxDinoLayerRefs& r : img.layers)
+    m->layers.push_back(Layer{f32(r.g1), f32(r.b1), f32(r.bqkv), f32(r.bo), f32(r.ls1), f32(r.g2), f32(r.b2), f32(r.bb1), f32(r.bb2), f32(r.ls2),
+                              at(r.wqkv), at(r.wo), at(r.w1), at(r.w2)});
+
+  // the workspace of max_batch frames: the patch matrix and what embed_chunk's plan asks for, one allocation
+  DinoRun R("lmx_dino_open_host", nullptr, nullptr);
+  LMX_TRY(embed_chunk(R, m, FrameSize(), nullptr, max_batch, 0, 0, 0, nullptr));
+  LmxArena whole;  // (the patch matrix is refused like every buffer)
+  LMX_TRY(R.take(&whole, "patch matrix", (int64_t)max_batch * c.grid * c.grid * c.k_pad * 2, &m->patches));
+  LMX_HIP(hipMalloc(reinterpret_cast<void**>(&m->work), whole.peak + R.arena.peak));
+  // the patch matrix's columns beyond 3 * patch^2 (k_pad) are never written by a kernel: zero once, as kernels.patchify_norm's torch.zeros
+  LMX_HIP(hipMemset(m->work, 0, whole.peak));
+  m->patches = m->work;
+  m->arena.base = m->work + whole.peak, m->arena.cap = m->arena.peak = R.arena.peak;
+  return LMX_OK;
 }
 
 int check_frames(const lmx_dino* m, const char* fn, const void* frames, int n, int h, int w, const void* emb) {
@@ -270,9 +274,10 @@ extern "C" int lmx_dino_embed(lmx_dino* m, const uint8_t* frames, int n, int h, 
   const FrameSize* fs = nullptr;
   LMX_TRY(prepare(m, h, w, &fs));  // a size seen before: a lookup
   const size_t frame_bytes = (size_t)h * w * 3;
+  DinoRun R("lmx_dino_embed", m, st);
   for (int done = 0; done < n; done += m->max_batch) {
     const int nb = n - done < m->max_batch ? n - done : m->max_batch;
-    LMX_TRY(embed_chunk(m, *fs, frames + (size_t)done * frame_bytes, nb, h, w, rgb, emb + (size_t)done * m->cfg.hidden, st));
+    LMX_TRY(embed_chunk(R, m, *fs, frames + (size_t)done * frame_bytes, nb, h, w, rgb, emb + (size_t)done * m->cfg.hidden));
   }
   return LMX_OK;
 }
@@ -289,10 +294,11 @@ extern "C" int lmx_dino_embed_host(lmx_dino* m, const uint8_t* frames_host, int 
   LMX_TRY(lmx_handle_grow_stage(m, lay.total));
   uint8_t* frames = reinterpret_cast<uint8_t*>(m->stage + o_frames);
   float* emb = reinterpret_cast<float*>(m->stage + o_emb);
+  DinoRun R("lmx_dino_embed_host", m, m->own);
   for (int done = 0; done < n; done += m->max_batch) {
     const int nb = n - done < m->max_batch ? n - done : m->max_batch;
     LMX_HIP(hipMemcpyAsync(frames, frames_host + (size_t)done * frame_bytes, nb * frame_bytes, hipMemcpyHostToDevice, m->own));
-    LMX_TRY(embed_chunk(m, *fs, frames, nb, h, w, rgb, emb, m->own));
+    LMX_TRY(embed_chunk(R, m, *fs, frames, nb, h, w, rgb, emb));
     LMX_HIP(hipMemcpyAsync(emb_host + (size_t)done * D, emb, nb * D * sizeof(float), hipMemcpyDeviceToHost, m->own));
     LMX_HIP(hipStreamSynchronize(m->own));
   }

@@ -6,8 +6,8 @@
 // Memory follows Python's tensors: what a chain updates in place there is updated in place here; where Python allocates a fresh
 // tensor this takes a distinct buffer — from the `stream` arena where it outlives its block (the residual stream's new tensors, the
 // next block's layer_norm1 rows, the f16 copies, the neck), from the `scratch` arena, rewound at every block, where it does not.
-// The trunk is written once over HieraRun, which first only counts (prepare: the arenas' sizes, each buffer refused by name from
-// 2 GB on) and then launches over the same offsets, so that allocation order and launch order are one piece of code.
+// The trunk is written once over HieraRun, a run of plan_run.h: a counting run (prepare) sizes the two arenas, each buffer refused by
+// name from 2 GB on, and a launching run walks the same code over the same offsets.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -21,8 +21,7 @@
 
 namespace {
 
-const int64_t HIERA_MAX_BUFFER_BYTES = 0x7fffffffll;  // the kernels index below 2 GB
-const int HIERA_KPAD_COLS = 152;                      // the patch matrix' columns: 7 * 7 * 3 padded to a multiple of 8
+const int HIERA_KPAD_COLS = 152;  // the patch matrix' columns: 7 * 7 * 3 padded to a multiple of 8
 
 struct HieraBlockW {
   LmxHieraBlock shape;
@@ -51,78 +50,27 @@ struct HieraBandTable {
   std::vector<const float*> x;   // per block: rows [join, H) of the stream entering it, [(H - join) * W][dim]
 };
 
-struct HieraArena {
-  char* base = nullptr;
-  size_t at = 0, peak = 0, cap = 0;
-};
-
 // one pass over the trunk: counting (launch false: no kernel runs, no pointer is followed) or launching
-struct HieraRun {
-  bool launch = false;
-  const char* fn = "";
-  HieraArena stream, scratch;
-  hipStream_t st = nullptr;
-
-  int take(HieraArena* a, const char* what, int64_t bytes, void** out) {
-    LMX_REQUIRE(bytes > 0 && bytes < HIERA_MAX_BUFFER_BYTES, "%s: buffer '%s' of the Hiera encoder has %lld bytes, the kernels index below 2 GB", fn, what,
-                (long long)bytes);
-    const size_t need = up256((size_t)bytes);
-    if (launch) LMX_REQUIRE(a->at + need <= a->cap, "%s: buffer '%s' of the Hiera encoder does not fit the prepared workspace", fn, what);
-    *out = launch ? a->base + a->at : nullptr;
-    a->at += need;
-    if (a->at > a->peak) a->peak = a->at;
-    return LMX_OK;
-  }
+struct HieraRun : LmxPlanRun {
+  LmxArena stream, scratch;
+  HieraRun() { model = "the Hiera encoder"; }
   template <class T>
   int keep(const char* what, int64_t bytes, T** out) {  // outlives its block
-    return take(&stream, what, bytes, reinterpret_cast<void**>(out));
+    return take(&stream, what, bytes, out);
   }
   template <class T>
   int tmp(const char* what, int64_t bytes, T** out) {  // dies with its block
-    return take(&scratch, what, bytes, reinterpret_cast<void**>(out));
+    return take(&scratch, what, bytes, out);
   }
 };
 
-#define HR_LAUNCH(call)         \
-  do {                          \
-    if (R.launch) LMX_TRY(call); \
-  } while (0)
+#define HR_LAUNCH(call) LMX_LAUNCH(R, call)
 
 // K.gemm: out [M or M / 4][N] = act(a [M][K] w^T + bias) (+ res), with the pooled-row mode (pool_h > 0: the rows of a are an
 // [n, pool_h, pool_w] grid, the result its 2 x 2 max-pool) and the ln_out rows of the projection
 inline int hiera_gemm(const void* a, int K, const void* w, const float* bias, void* out, int out_dtype, int M, int N, int act, const void* res, int res_rows,
                       int pool_h, int pool_w, void* ln_out, const float* ln_g, const float* ln_b, float ln_eps, hipStream_t st) {
-  lmx_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.A = a;
-  d.W = w;
-  d.bias = bias;
-  d.res = res;
-  d.C = out;
-  d.lda = K;
-  d.ldc = N;
-  d.ldr = res ? N : 0;
-  d.M = M;
-  d.N = N;
-  d.K = K;
-  d.act = act;
-  d.out_dtype = out_dtype;
-  d.a_mode = 0;
-  d.res_rows = res_rows;
-  d.a_rep = 1;
-  if (pool_h) {
-    d.a_mode = 2;
-    d.H = pool_h;
-    d.W_ = pool_w;
-  }
-  if (ln_out) {
-    d.ln_out = ln_out;
-    d.ln_gamma = ln_g;
-    d.ln_beta = ln_b;
-    d.ld_ln = N;
-    d.ln_eps = ln_eps;
-  }
-  return lmx_k_gemm(&d, st);
+  return lmx_gemm_dense_rep(a, K, w, bias, out, N, out_dtype, M, N, K, act, nullptr, res, N, res_rows, 1, st, pool_h, pool_w, ln_out, ln_g, ln_b, ln_eps);
 }
 
 // HieraEncoder._attention_half: [shortcut GEMM ->] qkv GEMM -> [Q-pool] -> attention -> proj GEMM + residual as separate launches, in
@@ -132,7 +80,7 @@ inline int hiera_attention_half(HieraRun& R, const lmx_hiera_block_t& P, const H
   const int H = P.H, W = P.W, Hq = P.Ho, Wq = P.Wo;
   const int64_t rows_in = (int64_t)n * H * W, rows_out = (int64_t)n * Hq * Wq;
   const float scale = (float)pow((double)hd, -0.5);
-  hipStream_t st = R.st;
+  hipStream_t st = lmx_run_stream(R);
   const float* res = *x;
   const bool fresh = P.shortcut != LMX_HIERA_SHORTCUT_NONE;  // the residual is a tensor of its own: so is the block's output
   if (P.shortcut == LMX_HIERA_SHORTCUT_POOLED_GEMM) {  // the shortcut's projection and its 2 x 2 max-pool in one launch
@@ -178,19 +126,8 @@ inline int hiera_attention_half(HieraRun& R, const lmx_hiera_block_t& P, const H
   half_t* a;
   LMX_TRY(R.tmp("attention output", rows_out * D * 2, &a));
   if (R.launch) {
-    lmx_attn_desc ad;
-    memset(&ad, 0, sizeof(ad));
-    ad.Q = q, ad.K = k, ad.V = v, ad.O = a;
-    ad.ldq = ldq, ad.ldk = ad.ldv = ldkv, ad.ldo = D;
-    ad.H = heads, ad.hd = hd, ad.scale = scale;
-    if (win > 0) {
-      const int nW = ((H + win - 1) / win) * ((W + win - 1) / win), wq = qs ? win / 2 : win;
-      ad.B = n * nW, ad.Tq = wq * wq, ad.Tk = win * win, ad.mode = 1;
-      ad.Gh = H, ad.Gw = W, ad.ws = win, ad.q_stride = qs ? 2 : 1;
-      ad.pad_k = B.padkv + D, ad.pad_v = B.padkv + 2 * D;
-    } else {
-      ad.B = n, ad.Tq = Hq * Wq, ad.Tk = H * W, ad.mode = 0;
-    }
+    const lmx_attn_desc ad = win > 0 ? lmx_attn_windowed(q, ldq, k, v, ldkv, a, D, n, heads, hd, scale, H, W, win, qs != 0, B.padkv + D, B.padkv + 2 * D)
+                                     : lmx_attn_flat(q, ldq, k, v, ldkv, a, D, n, heads, Hq * Wq, H * W, hd, scale);
     LMX_TRY(lmx_k_attention(&ad, st));
   }
   float* xo = *x;
@@ -211,7 +148,7 @@ inline int hiera_trunk(HieraRun& R, const HieraW& Wt, const lmx_hiera_block_t* p
   const lmx_hiera_config_t& c = Wt.cfg;
   const int g = c.image / 4, nb = Wt.n_blocks;
   const float eps = (float)c.eps;
-  hipStream_t st = R.st;
+  hipStream_t st = lmx_run_stream(R);
   const int H0 = plan[0].join ? plan[0].join : plan[0].H;
   float* x;
   LMX_TRY(R.keep("residual stream", (int64_t)n * H0 * g * c.hidden * 4, &x));
@@ -225,7 +162,7 @@ inline int hiera_trunk(HieraRun& R, const HieraW& Wt, const lmx_hiera_block_t* p
     const lmx_hiera_block_t& P = plan[i];
     const HieraBlockW& B = Wt.blocks[(size_t)i];
     const int Din = B.shape.dim, D = B.shape.D, heads = B.shape.heads;
-    R.scratch.at = 0;
+    R.rewind_to(&R.scratch, 0);  // what the last block took from the scratch arena is dead
     if (stop_at >= 0) {
       if (tap_need[i] > 0 && R.launch)
         LMX_HIP(hipMemcpyAsync(taps[i], x + (int64_t)tap_have[i] * P.W * Din, (size_t)(tap_need[i] - tap_have[i]) * P.W * Din * 4, hipMemcpyDeviceToDevice, st));

@@ -5,9 +5,10 @@
 // HOST code only: there is no kernel in this file.  Every launch goes through the same extern "C" lmx_k_* entry point the ctypes
 // binding calls, with the descriptor filled as lmx/kernels.py fills it, so the outputs are the Python plan's bit for bit on both
 // precision plans (tests/test_gpu_native_yolo.py).
-// The plan is written ONCE (forward) over a Run: in sizing mode (lmx_yolo_prepare) a Run only counts the bytes of the buffers the
-// plan asks for, in launch mode it hands out the same offsets inside the prepared workspace and enqueues — allocation order and
-// launch order cannot drift apart.
+// The plan is written ONCE (forward) over a Run, a run of plan_run.h: lmx_yolo_prepare walks it counting, which sizes the plan's
+// arena and the one f32 region of the exact plan, and every call walks it launching over the same offsets.  lmx_k_gemm itself checks
+// "smaller than 2 GB" for pooled rows (a_mode 2) only; for the dense and convolution launches this plan makes (a_mode 0 / 1) the
+// run's refusal of a buffer of 2 GB or more is the only guard: it is not redundant.
 #include <string.h>
 
 #include <map>
@@ -20,10 +21,6 @@
 
 namespace {
 
-// The GEMM kernels walk an operand with 32-bit byte offsets.  lmx_k_gemm itself checks "smaller than 2 GB" for pooled rows (a_mode 2)
-// only; for the dense and convolution launches this plan makes (a_mode 0 / 1) NOTHING in the launcher checks it, so the guard in
-// Run::alloc / need_scratch is the only one: it is not redundant.
-const int64_t MAX_BUFFER_BYTES = 0x7fffffffll;
 const float NMS_MAX_WH = 7680.f;
 
 // one convolution's operands under one plan
@@ -33,7 +30,7 @@ struct ConvW {
   int cout = 0, K = 0;                     // K: the columns of w
 };
 
-// an NHWC view of (a channel slice of) a workspace buffer: offset from the workspace's base, C channels of esz bytes, pixel stride ps
+// an NHWC view of (a channel slice of) a workspace buffer: offset from the plan arena's base, C channels of esz bytes, pixel stride ps
 struct Act {
   size_t off = 0;
   int H = 0, W = 0, C = 0, esz = 2;
@@ -57,8 +54,7 @@ struct Prepared {
   uint8_t* boxed = nullptr;  // letterboxed frames u8 [max_batch, oh, ow, 3]
   float* pred = nullptr;     // [max_batch, A, 4 + nc]
   void* nms_ws = nullptr;
-  char* plan = nullptr;      // the plan's buffers, then its f32 scratch
-  size_t plan_bytes = 0, scratch_bytes = 0;
+  LmxArena plan, scratch;    // the plan's buffers and the f32 region of the exact plan, as the counting walk sized them
 };
 
 }  // namespace
@@ -72,41 +68,29 @@ struct lmx_yolo : LmxHandleCore {
 
 namespace {
 
-// the plan's view of one launch sequence: sizing (launch == false: count, enqueue nothing) or launching n <= max_batch frames
-struct Run {
+// the plan's view of one launch sequence: counting (at prepare: enqueue nothing) or launching n <= max_batch frames
+struct Run : LmxPlanRun {
   const lmx_yolo* m;
   int precision, cm;  // cm: stored f16 channels per logical channel (1, or 3 for the exact plan's x3 triples)
-  bool launch;
   int n;
-  char* base;  // launch mode: the plan's region of the workspace
-  size_t off = 0, scratch = 0, scratch_at = 0;
-  hipStream_t st;
+  LmxArena plan, scratch;
+  hipStream_t stream() const { return lmx_run_stream(*this); }
 
-  void* at(const Act& a) const { return base + a.off; }
-  float* scratch_ptr() const { return reinterpret_cast<float*>(base + scratch_at); }
+  Run(const lmx_yolo* m_, int precision_, const char* fn_) : m(m_), precision(precision_), cm(precision_ == LMX_YOLO_EXACT ? 3 : 1), n(0) {
+    fn = fn_, model = "YOLOv8", kernels = "GEMM kernels";
+  }
+  void* at(const Act& a) const { return plan.base + a.off; }
 
-  // [max_batch, H, W, C] of esz-byte elements
+  // [max_batch, H, W, C] of esz-byte elements: every call finds a buffer where the count put it, whatever its n
   int alloc(int H, int W, int C, int esz, const char* what, Act* out) {
-    const int64_t bytes = (int64_t)m->max_batch * H * W * C * esz;
-    LMX_REQUIRE(bytes < MAX_BUFFER_BYTES, "lmx_yolo_prepare: buffer '%s' [%d, %d, %d, %d] of %d-byte elements has %lld bytes, the GEMM kernels index below 2 GB",
-                what, m->max_batch, H, W, C, esz, (long long)bytes);
-    out->off = off;
-    out->H = H;
-    out->W = W;
-    out->C = C;
-    out->esz = esz;
-    out->ps = C;
-    off += up256((size_t)bytes);
-    return LMX_OK;
+    *out = Act{plan.at, H, W, C, esz, C};
+    void* p;
+    return take(&plan, what, (int64_t)m->max_batch * H * W * C * esz, &p);
   }
   // the f32 output of an exact-plan convolution (parts partial sums): consumed by the lmx_k_split3 enqueued right behind it, so one
   // region serves them all in stream order
-  int need_scratch(int parts, int H, int W, int C, const char* what) {
-    const int64_t bytes = (int64_t)parts * m->max_batch * H * W * C * 4;
-    LMX_REQUIRE(bytes < MAX_BUFFER_BYTES, "lmx_yolo_prepare: f32 output of '%s' [%d, %d, %d, %d, %d] has %lld bytes, the GEMM kernels index below 2 GB", what,
-                parts, m->max_batch, H, W, C, (long long)bytes);
-    if ((size_t)bytes > scratch) scratch = (size_t)bytes;
-    return LMX_OK;
+  int scratch_for(int parts, int H, int W, int C, const char* what, float** out) {
+    return share(&scratch, what, (int64_t)parts * m->max_batch * H * W * C * 4, out);
   }
   int weights(const std::string& name, const ConvW** w) const {
     const auto it = m->conv[precision].find(name);
@@ -120,7 +104,7 @@ struct Run {
 int gemm1(Run& r, const Act& x, const ConvW& w, int act, const float* scale, void* C, int64_t ldc, int out_dtype) {
   LMX_REQUIRE(w.K == x.C, "lmx_yolo: a 1 x 1 convolution with %d weight columns reads %d channels", w.K, x.C);
   if (!r.launch) return LMX_OK;
-  return lmx_gemm_dense(r.at(x), x.ps, w.w, w.b, C, ldc, out_dtype, r.n * x.H * x.W, w.cout, x.C, act, scale, nullptr, 0, r.st);
+  return lmx_gemm_dense(r.at(x), x.ps, w.w, w.b, C, ldc, out_dtype, r.n * x.H * x.W, w.cout, x.C, act, scale, nullptr, 0, r.stream());
 }
 
 // K.conv3x3: 3 x 3 / pad 1 as implicit GEMM
@@ -128,37 +112,8 @@ int gemm3(Run& r, const Act& x, const ConvW& w, int act, int stride, const float
           int split_k) {
   LMX_REQUIRE(w.K == 9 * x.C, "lmx_yolo: a 3 x 3 convolution with %d weight columns reads %d channels", w.K, x.C);
   if (!r.launch) return LMX_OK;
-  const int Ho = (x.H - 1) / stride + 1, Wo = (x.W - 1) / stride + 1;
-  lmx_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.A = r.at(x);
-  d.W = w.w;
-  d.bias = w.b;
-  d.scale = scale;
-  d.C = C;
-  d.lda = x.ps;
-  d.ldc = ldc;
-  if (res) {
-    d.res = r.at(*res);
-    d.ldr = res->ps;
-  }
-  d.M = r.n * Ho * Wo;
-  d.N = w.cout;
-  d.K = 9 * x.C;
-  d.act = act;
-  d.out_dtype = out_dtype;
-  d.a_mode = 1;
-  d.H = x.H;
-  d.W_ = x.W;
-  d.Cin = x.C;
-  d.conv_stride = stride;
-  d.Ho = Ho;
-  d.Wo = Wo;
-  if (split_k > 1) {
-    d.split_k = split_k;
-    d.split_stride = (int64_t)r.n * Ho * Wo * w.cout;
-  }
-  return lmx_k_gemm(&d, r.st);
+  return lmx_gemm_conv3(r.at(x), x.ps, r.n, x.H, x.W, x.C, w.w, w.b, scale, C, ldc, out_dtype, w.cout, act, stride, res ? r.at(*res) : nullptr,
+                        res ? res->ps : 0, split_k, r.stream());
 }
 
 // P.conv3: Conv(k3) + SiLU (+ shortcut).  out_in: the consumer's slice to write into, or null for a buffer of the convolution's own
@@ -179,11 +134,12 @@ int conv3(Run& r, const Act x, const std::string& name, int stride, const Act* r
   // exact: the factor depends on the layer only (pixels of ONE frame), so a frame's bits do not depend on the batch it rides in
   const int sk = lmx_h_conv_split_k((int64_t)Ho * Wo, w->cout, w->K, x.C);
   LMX_REQUIRE(sk >= 1, "lmx_yolo: split factor of '%s'", name.c_str());
-  LMX_TRY(r.need_scratch(sk, Ho, Wo, w->cout, name.c_str()));
-  LMX_TRY(gemm3(r, x, *w, LMX_ACT_NONE, stride, w->s, nullptr, r.launch ? r.scratch_ptr() : nullptr, w->cout, LMX_F32, sk));
+  float* acc;
+  LMX_TRY(r.scratch_for(sk, Ho, Wo, w->cout, name.c_str(), &acc));
+  LMX_TRY(gemm3(r, x, *w, LMX_ACT_NONE, stride, w->s, nullptr, acc, w->cout, LMX_F32, sk));
   if (!r.launch) return LMX_OK;
-  return lmx_k_split3(r.scratch_ptr(), w->cout, LMX_ACT_SILU, res ? r.at(*res) : nullptr, res ? res->ps : 0, r.at(o), o.ps, (int64_t)r.n * Ho * Wo,
-                      w->cout, w->cout, sk, sk > 1 ? (int64_t)r.n * Ho * Wo * w->cout : 0, r.st);
+  return lmx_k_split3(acc, w->cout, LMX_ACT_SILU, res ? r.at(*res) : nullptr, res ? res->ps : 0, r.at(o), o.ps, (int64_t)r.n * Ho * Wo,
+                      w->cout, w->cout, sk, sk > 1 ? (int64_t)r.n * Ho * Wo * w->cout : 0, r.stream());
 }
 
 // P.conv1: Conv(k1) + SiLU into `out` (a slice of the consumer's buffer); g_out: the x3 group width of the output (0: all channels)
@@ -193,11 +149,12 @@ int conv1(Run& r, const Act& x, const std::string& name, const Act& out, int g_o
   LMX_REQUIRE(out.H == x.H && out.W == x.W && out.C == r.cm * w->cout, "lmx_yolo: '%s' writes [%d, %d, %d] into a slice of [%d, %d, %d]", name.c_str(),
               x.H, x.W, r.cm * w->cout, out.H, out.W, out.C);
   if (r.precision == LMX_YOLO_F16) return gemm1(r, x, *w, LMX_ACT_SILU, nullptr, r.launch ? r.at(out) : nullptr, out.ps, LMX_F16);
-  LMX_TRY(r.need_scratch(1, x.H, x.W, w->cout, name.c_str()));
-  LMX_TRY(gemm1(r, x, *w, LMX_ACT_NONE, w->s, r.launch ? r.scratch_ptr() : nullptr, w->cout, LMX_F32));
+  float* acc;
+  LMX_TRY(r.scratch_for(1, x.H, x.W, w->cout, name.c_str(), &acc));
+  LMX_TRY(gemm1(r, x, *w, LMX_ACT_NONE, w->s, acc, w->cout, LMX_F32));
   if (!r.launch) return LMX_OK;
-  return lmx_k_split3(r.scratch_ptr(), w->cout, LMX_ACT_SILU, nullptr, 0, r.at(out), out.ps, (int64_t)r.n * x.H * x.W, w->cout, g_out ? g_out : w->cout, 1,
-                      0, r.st);
+  return lmx_k_split3(acc, w->cout, LMX_ACT_SILU, nullptr, 0, r.at(out), out.ps, (int64_t)r.n * x.H * x.W, w->cout, g_out ? g_out : w->cout, 1,
+                      0, r.stream());
 }
 
 // P.head: the plain Conv2d(c, n_out, 1) that ends a Detect / Pose branch: f32 out, no activation
@@ -211,15 +168,15 @@ int head(Run& r, const Act& x, const std::string& name, const Act& out) {
 
 int pool5(Run& r, const Act& x, const Act& out) {
   if (!r.launch) return LMX_OK;
-  if (r.precision == LMX_YOLO_F16) return lmx_k_maxpool5(r.at(x), x.ps, r.at(out), out.ps, r.n, x.H, x.W, x.C, r.st);
-  return lmx_k_maxpool5_x3(r.at(x), x.ps, r.at(out), out.ps, r.n, x.H, x.W, x.C / 3, r.st);
+  if (r.precision == LMX_YOLO_F16) return lmx_k_maxpool5(r.at(x), x.ps, r.at(out), out.ps, r.n, x.H, x.W, x.C, r.stream());
+  return lmx_k_maxpool5_x3(r.at(x), x.ps, r.at(out), out.ps, r.n, x.H, x.W, x.C / 3, r.stream());
 }
 
 int up2(Run& r, const Act& x, const Act& out) {
   LMX_REQUIRE(out.H == 2 * x.H && out.W == 2 * x.W && out.C == x.C, "lmx_yolo: upsample of [%d, %d, %d] into a slice of [%d, %d, %d]", x.H, x.W, x.C, out.H,
               out.W, out.C);
   if (!r.launch) return LMX_OK;
-  return lmx_k_upsample2(r.at(x), x.ps, r.at(out), out.ps, r.n, x.H, x.W, x.C, r.st);
+  return lmx_k_upsample2(r.at(x), x.ps, r.at(out), out.ps, r.n, x.H, x.W, x.C, r.stream());
 }
 
 // YoloDetector._c2f: ONE buffer [H, W, (2 + nb) c]; cv1 writes channels [0, 2c), each bottleneck reads the previous c-wide slice and
@@ -273,9 +230,9 @@ int forward(Run& r, const uint8_t* boxed, int H, int W, float* pred, Act kraw[3]
   LMX_TRY(buf((H - 1) / 2 + 1, (W - 1) / 2 + 1, T[0].c2, "model.0", &x));                                  // 0
   if (r.launch) {
     if (r.precision == LMX_YOLO_F16)
-      LMX_TRY(lmx_k_stem_conv(boxed, m->stem_w, m->stem_b, r.at(x), r.n, H, W, T[0].c2, r.st));
+      LMX_TRY(lmx_k_stem_conv(boxed, m->stem_w, m->stem_b, r.at(x), r.n, H, W, T[0].c2, r.stream()));
     else
-      LMX_TRY(lmx_k_stem_conv_x3(boxed, m->stem_w, m->stem_b, r.at(x), r.n, H, W, T[0].c2, r.st));
+      LMX_TRY(lmx_k_stem_conv_x3(boxed, m->stem_w, m->stem_b, r.at(x), r.n, H, W, T[0].c2, r.stream()));
   }
   LMX_TRY(conv3(r, x, "model.1", 2, nullptr, nullptr, &x));                                                // 1
   LMX_TRY(buf(H / 4, W / 4, T[2].c2, "model.2", &b2));
@@ -317,7 +274,7 @@ int forward(Run& r, const uint8_t* boxed, int H, int W, float* pred, Act kraw[3]
     LMX_TRY(conv3(r, t, p + ".cv3" + s + ".1", 1, nullptr, nullptr, &t));
     LMX_TRY(head(r, t, p + ".cv3" + s + ".2", slice(hd, 64, ldh)));
     if (r.launch)
-      LMX_TRY(lmx_k_detect_decode(static_cast<const float*>(r.at(hd)), ldh, pred, r.n, feat.H, feat.W, cfg.nc, strides[l], a_off, A, r.st));
+      LMX_TRY(lmx_k_detect_decode(static_cast<const float*>(r.at(hd)), ldh, pred, r.n, feat.H, feat.W, cfg.nc, strides[l], a_off, A, r.stream()));
     a_off += feat.H * feat.W;
     if (cfg.kpt_k) {
       LMX_TRY(conv3(r, feat, p + ".cv4" + s + ".0", 1, nullptr, nullptr, &t));
@@ -388,18 +345,15 @@ int prepare(lmx_yolo* m, int h, int w, int precision, const Prepared** out) {
     ibeta.resize((size_t)g.rh * 2);
     LMX_TRY(lmx_h_letterbox_tables(h, w, g.rh, g.rw, xofs.data(), ialpha.data(), yofs.data(), ibeta.data()));
   }
-  // the plan in sizing mode: the bytes of its buffers and of its f32 scratch
-  Run r{m, precision, precision == LMX_YOLO_EXACT ? 3 : 1, false, 0, nullptr};
-  r.st = nullptr;
+  // the plan, counted: the bytes of its buffers and of its f32 region
+  Run r(m, precision, "lmx_yolo_prepare");
   Act kraw[3];
   LMX_TRY(forward(r, nullptr, g.oh, g.ow, nullptr, kraw));
-  P.plan_bytes = r.off;
-  P.scratch_bytes = up256(r.scratch);
   const int64_t B = m->max_batch, row = 4 + m->img.cfg.nc;
   const int64_t boxed_bytes = B * g.oh * g.ow * 3, pred_bytes = B * P.A * row * 4, nms_bytes = lmx_nms_workspace_bytes(m->max_batch, P.A);
-  LMX_REQUIRE(boxed_bytes < MAX_BUFFER_BYTES && pred_bytes < MAX_BUFFER_BYTES, "lmx_yolo_prepare: buffer '%s' of %lld bytes for max_batch %d is beyond 2 GB",
-              boxed_bytes < MAX_BUFFER_BYTES ? "pred" : "letterboxed frames", (long long)(boxed_bytes < MAX_BUFFER_BYTES ? pred_bytes : boxed_bytes),
-              m->max_batch);
+  LMX_REQUIRE(boxed_bytes < LMX_MAX_BUFFER_BYTES && pred_bytes < LMX_MAX_BUFFER_BYTES,
+              "lmx_yolo_prepare: buffer '%s' of %lld bytes for max_batch %d is beyond 2 GB", boxed_bytes < LMX_MAX_BUFFER_BYTES ? "pred" : "letterboxed frames",
+              (long long)(boxed_bytes < LMX_MAX_BUFFER_BYTES ? pred_bytes : boxed_bytes), m->max_batch);
   LMX_REQUIRE(nms_bytes > 0, "lmx_yolo_prepare: lmx_nms_workspace_bytes(%d, %d) = %lld", m->max_batch, P.A, (long long)nms_bytes);
   LmxLayout lay;
   const LmxUpload up[4] = {{lay.add(xofs.size() * 4), xofs.data(), xofs.size() * 4},
@@ -407,8 +361,7 @@ int prepare(lmx_yolo* m, int h, int w, int precision, const Prepared** out) {
                            {lay.add(yofs.size() * 4), yofs.data(), yofs.size() * 4},
                            {lay.add(ibeta.size() * 2), ibeta.data(), ibeta.size() * 2}};
   const size_t o_boxed = lay.add((size_t)boxed_bytes), o_pred = lay.add((size_t)pred_bytes), o_nms = lay.add((size_t)nms_bytes),
-               o_plan = lay.add(P.plan_bytes);
-  lay.add(P.scratch_bytes);  // the plan's f32 scratch, right behind its buffers
+               o_plan = lay.add(r.plan.peak), o_scratch = lay.add(r.scratch.peak);
   LMX_TRY(lmx_alloc_and_upload(lay.total, up, 4, &P.blob));
   if (resize) {
     P.xofs = reinterpret_cast<int32_t*>(P.blob + up[0].at);
@@ -419,30 +372,31 @@ int prepare(lmx_yolo* m, int h, int w, int precision, const Prepared** out) {
   P.boxed = reinterpret_cast<uint8_t*>(P.blob + o_boxed);
   P.pred = reinterpret_cast<float*>(P.blob + o_pred);
   P.nms_ws = P.blob + o_nms;
-  P.plan = P.blob + o_plan;
+  P.plan.base = P.blob + o_plan, P.plan.cap = r.plan.peak;
+  P.scratch.base = P.blob + o_scratch, P.scratch.cap = r.scratch.peak;
   const auto ins = m->prepared.emplace(key, P);
   if (out) *out = &ins.first->second;
   return LMX_OK;
 }
 
 // preprocess + forward_letterboxed for nb <= max_batch frames: pred f32 [nb, A, 4 + nc]
-int predict_chunk(const lmx_yolo* m, const Prepared& P, int precision, const uint8_t* frames, int nb, int h, int w, float* pred, Act kraw[3],
-                  hipStream_t st) {
+int predict_chunk(const lmx_yolo* m, const Prepared& P, const char* fn, int precision, const uint8_t* frames, int nb, int h, int w, float* pred,
+                  Act kraw[3], hipStream_t st) {
   const lmx_letterbox_geo_t& g = P.geo;
   LMX_TRY(lmx_k_letterbox(frames, P.boxed, nb, h, w, g.rh, g.rw, g.top, g.left, g.oh, g.ow, P.xofs, P.ialpha, P.yofs, P.ibeta, 1, st));
-  Run r{m, precision, precision == LMX_YOLO_EXACT ? 3 : 1, true, nb, P.plan};
-  r.scratch_at = P.plan_bytes;
-  r.st = st;
+  Run r(m, precision, fn);
+  r.launch = true, r.n = nb, r.st = st;
+  r.plan = P.plan, r.scratch = P.scratch;
   return forward(r, P.boxed, g.oh, g.ow, pred, kraw);
 }
 
 // detect / detect_pose for nb <= max_batch frames, writing the chunk's rows of the outputs
-int detect_chunk(const lmx_yolo* m, const Prepared& P, int precision, const uint8_t* frames, int nb, int h, int w, float conf, double iou, int max_det,
+int detect_chunk(const lmx_yolo* m, const Prepared& P, const char* fn, int precision, const uint8_t* frames, int nb, int h, int w, float conf, double iou, int max_det,
                  float* boxes, float* scores, int32_t* cls, int32_t* src, int32_t* counts, float* kpts, hipStream_t st) {
   const LmxYoloCfg& c = m->img.cfg;
   const lmx_letterbox_geo_t& g = P.geo;
   Act kraw[3];
-  LMX_TRY(predict_chunk(m, P, precision, frames, nb, h, w, P.pred, kraw, st));
+  LMX_TRY(predict_chunk(m, P, fn, precision, frames, nb, h, w, P.pred, kraw, st));
   // K.nms's torch.zeros / torch.full(-1): lmx_k_nms leaves rows beyond counts untouched
   const size_t rows = (size_t)nb * max_det;
   LMX_HIP(hipMemsetAsync(boxes, 0, rows * 16, st));
@@ -458,7 +412,7 @@ int detect_chunk(const lmx_yolo* m, const Prepared& P, int precision, const uint
   const double padx = (g.ow - gx) / 2, pady = (g.oh - gy) / 2;
   const int32_t hw[6] = {g.oh / 8, g.ow / 8, g.oh / 16, g.ow / 16, g.oh / 32, g.ow / 32};
   const float strides[3] = {8.f, 16.f, 32.f};
-  auto raw = [&](int l) { return reinterpret_cast<const float*>(P.plan + kraw[l].off); };
+  auto raw = [&](int l) { return reinterpret_cast<const float*>(P.plan.base + kraw[l].off); };
   return lmx_k_pose_gather(raw(0), raw(1), raw(2), c.nk_pad, hw, strides, src, counts, nb, max_det, c.kpt_k, c.kpt_ndim, (float)padx, (float)pady,
                            (float)g.gain, (float)g.sw, (float)g.sh, kpts, st);
 }
@@ -525,7 +479,7 @@ extern "C" int lmx_yolo_predict(lmx_yolo* m, const uint8_t* frames, int n, int h
   Act kraw[3];
   for (int done = 0; done < n; done += m->max_batch) {
     const int nb = n - done < m->max_batch ? n - done : m->max_batch;
-    LMX_TRY(predict_chunk(m, *P, precision, frames + (size_t)done * frame_bytes, nb, h, w, pred + (size_t)done * pred_row, kraw, st));
+    LMX_TRY(predict_chunk(m, *P, "lmx_yolo_predict", precision, frames + (size_t)done * frame_bytes, nb, h, w, pred + (size_t)done * pred_row, kraw, st));
   }
   return LMX_OK;
 }
@@ -541,7 +495,7 @@ extern "C" int lmx_yolo_detect(lmx_yolo* m, const uint8_t* frames, int n, int h,
   for (int done = 0; done < n; done += m->max_batch) {
     const int nb = n - done < m->max_batch ? n - done : m->max_batch;
     const size_t d = (size_t)done;
-    LMX_TRY(detect_chunk(m, *P, precision, frames + d * frame_bytes, nb, h, w, conf, iou, max_det, boxes + d * md * 4, scores + d * md, cls + d * md,
+    LMX_TRY(detect_chunk(m, *P, "lmx_yolo_detect", precision, frames + d * frame_bytes, nb, h, w, conf, iou, max_det, boxes + d * md * 4, scores + d * md, cls + d * md,
                          src + d * md, counts + d, kpts ? kpts + d * kp : nullptr, st));
   }
   return LMX_OK;
@@ -569,7 +523,7 @@ extern "C" int lmx_yolo_detect_host(lmx_yolo* m, const uint8_t* frames_host, int
   for (int done = 0; done < n; done += m->max_batch) {
     const size_t nb = (size_t)(n - done < m->max_batch ? n - done : m->max_batch), d = (size_t)done;
     LMX_HIP(hipMemcpyAsync(s, frames_host + d * frame_bytes, nb * frame_bytes, hipMemcpyHostToDevice, m->own));
-    LMX_TRY(detect_chunk(m, *P, precision, reinterpret_cast<const uint8_t*>(s), (int)nb, h, w, conf, iou, max_det, boxes, scores, cls, src, counts, kpts,
+    LMX_TRY(detect_chunk(m, *P, "lmx_yolo_detect_host", precision, reinterpret_cast<const uint8_t*>(s), (int)nb, h, w, conf, iou, max_det, boxes, scores, cls, src, counts, kpts,
                          m->own));
     LMX_HIP(hipMemcpyAsync(boxes_host + d * md * 4, boxes, nb * md * 16, hipMemcpyDeviceToHost, m->own));
     LMX_HIP(hipMemcpyAsync(scores_host + d * md, scores, nb * md * 4, hipMemcpyDeviceToHost, m->own));
